@@ -4,7 +4,7 @@ out=$1; shift
 : > $out
 for e in "$@"; do
   echo "=== [$e]" >> $out
-  env $e timeout -k 10 200 python bench.py --cpu-sample 0 --steps 10 --warmup 3 2>>$out | python -c "
+  env $e timeout -k 10 200 python bench.py --full --cpu-sample 0 --steps 10 --warmup 3 2>>$out | python -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

@@ -8,10 +8,10 @@ O=$R/gpurun_out/$tag
 mkdir -p $O
 export TMPDIR=/tmp
 # 1. the bench lines: pipelined default (with the CPU legs) and the stages back to back
-timeout -k 10 600 python3 bench.py --steps 20 > $O/bench_line.json 2> $O/bench.err
-timeout -k 10 300 python3 bench.py --steps 20 --pipeline 0 --cpu-sample 0 > $O/bench_line_serial.json 2> $O/bench_serial.err
+timeout -k 10 600 python3 bench.py --full --steps 20 > $O/bench_line.json 2> $O/bench.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --pipeline 0 --cpu-sample 0 > $O/bench_line_serial.json 2> $O/bench_serial.err
 # 2. rocprofv3 kernel trace of the same command (program directly after --)
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 $R/bench.py --steps 10 --cpu-sample 0 > $O/kt.log 2>&1)
+(cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 $R/bench.py --full --steps 10 --cpu-sample 0 > $O/kt.log 2>&1)
 python3 tools/launches_by_grid.py $O/kt > $O/launches_by_grid.txt
 python3 tools/timeline.py $O/kt 7 > $O/timeline_pipelined_step.txt
 rm -rf $O/kt/*/*.db
