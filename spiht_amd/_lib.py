@@ -51,6 +51,9 @@ SYMBOLS = [
     "spiht_pipeline_create", "spiht_pipeline_create_on", "spiht_pipeline_destroy", "spiht_pipeline_info", "spiht_pipeline_set_color3", "spiht_pipeline_submit",
     "spiht_pipeline_submit_gather", "spiht_pipeline_flush", "spiht_pipeline_synchronize", "spiht_pipeline_contexts",
     "spiht_geometry_mode", "spiht_wavelet_taps", "spiht_ctx_set_option", "spiht_ctx_get_option", "spiht_ctx_wide_stats", "spiht_l1_flags_words", "spiht_decode_lists_flags_batch_i32", "spiht_dequant_idwt_flags_batch_f64",
+    "spiht_encode_image_batch_u8", "spiht_decode_image_batch_u8", "spiht_encode_image_host_u8", "spiht_decode_image_host_u8",
+    "spiht_dwt_pyramid_batch_u8", "spiht_dequant_idwt_flags_batch_u8", "spiht_idwt_level1_flags_batch_u8", "spiht_pipeline_submit_u8",
+    "spiht_check_view_u8",
 ]
 
 
@@ -169,6 +172,19 @@ def lib():
         L.spiht_pipeline_flush.argtypes = [vp]
         L.spiht_pipeline_synchronize.argtypes = [vp]
         L.spiht_pipeline_contexts.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        # 8-bit pixels: the strides (int64 [4] or [3], bytes, NULL = dense CHW) follow the picture's pointer
+        L.spiht_encode_image_batch_u8.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, u64, vp,
+                                                  u64, vp, vp, vp]
+        L.spiht_decode_image_batch_u8.argtypes = [vp, vp, u64, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double,
+                                                  vp, vp, vp, vp]
+        L.spiht_encode_image_host_u8.argtypes = [vp, vp, vp, i64, i64, i64, i32, i32, i32, C.c_double, vp, u64, vp, u64,
+                                                 C.POINTER(u64), C.POINTER(u8)]
+        L.spiht_decode_image_host_u8.argtypes = [vp, vp, u64, u8, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp]
+        L.spiht_dwt_pyramid_batch_u8.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp]
+        L.spiht_dequant_idwt_flags_batch_u8.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp]
+        L.spiht_idwt_level1_flags_batch_u8.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp]
+        L.spiht_pipeline_submit_u8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        L.spiht_check_view_u8.argtypes = [i64, i64, i64, i64, vp, i32]
         L.spiht_ctx_lock.argtypes = [vp]
         L.spiht_ctx_unlock.argtypes = [vp]
         _lib = L

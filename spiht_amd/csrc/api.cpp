@@ -39,6 +39,10 @@ int spiht_launch_dwt_level_ext(const DwtKArgs *a, int planes, void *t_lo, void *
 int spiht_launch_idwt_level_per(const IdwtKArgs *a, int planes, double *t_lo, double *t_hi, const double *d_filt, int per,
                                 hipStream_t st);
 int spiht_launch_idwt_level(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc);
+int spiht_launch_dwt_level_u8(const DwtKArgs *a, const Px8 *px, int planes, hipStream_t st);
+int spiht_launch_idwt_level_u8(const IdwtKArgs *a, const Px8 *px, int planes, hipStream_t st, TileCtr *tc);
+int spiht_launch_u8_to_f64(const Px8 *px, int64_t B, double *out, hipStream_t st);
+int spiht_launch_f64_to_u8(const double *in, int rec_h, int rec_w, const Px8 *px, int64_t B, hipStream_t st);
 int spiht_launch_quant_plain(const double *in, int32_t *out, size_t n_per_plane, int planes, int c, const double *mults,
                              double q, uint32_t *maxabs, hipStream_t st);
 int spiht_launch_zero_pads(int L, const int64_t *hs, const int64_t *ws, const int64_t *offh, const int64_t *offw, int enc_h,
@@ -95,6 +99,8 @@ struct spiht_ctx {
     DevBuf tilebuf;      // tile counters of the persistent inverse-transform kernel
     TileCtr tilectr = {nullptr, {0, 0, 0, 0, 0, 0, 0, 0}, 0, 0, 0, 0};
     DevBuf himg, hrec;   // host-array image entry points: pixels in / out, coefficient array in
+    DevBuf pix;          // 8-bit pixels: the dense float64 picture of the routes that convert in a pass of their own
+    DevBuf hpix8;        // 8-bit host-array entry points: the picture's bytes on the device
     std::vector<double> mults_host;  // what ctx->mults holds (uploaded again only when the scales change)
     // colour model of the coded picture (spiht_ctx_set_color3): applied inside level 1 of the transforms of 3-channel images
     bool color_on = false;
@@ -428,7 +434,8 @@ extern "C" void spiht_ctx_destroy(spiht_ctx *ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     DevBuf *bufs[] = {&ctx->widebuf, &ctx->filt, &ctx->exttmp, &ctx->l1flags, &ctx->x, &ctx->dmsb, &ctx->lmsb, &ctx->maxabs, &ctx->out, &ctx->nbits, &ctx->maxn, &ctx->err,
                       &ctx->lists, &ctx->coeffs, &ctx->a0, &ctx->a1, &ctx->data, &ctx->nbytes, &ctx->rec, &ctx->mults,
-                      &ctx->img, &ctx->trace, &ctx->meta, &ctx->recz, &ctx->lspcnt, &ctx->himg, &ctx->hrec, &ctx->tilebuf};
+                      &ctx->img, &ctx->trace, &ctx->meta, &ctx->recz, &ctx->lspcnt, &ctx->himg, &ctx->hrec, &ctx->tilebuf,
+                      &ctx->pix, &ctx->hpix8};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &r : ctx->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -1137,16 +1144,29 @@ static int upload_filters(spiht_ctx *ctx, int wavelet, const double **d_filt) {
     return SPIHT_OK;
 }
 
+// px != nullptr: the picture is the 8-bit view *px of planes / c images (d_img unused).  The tiled level 1 reads it itself;
+// the two-pass levels get its float64 form from a conversion pass first.
 static int dwt_forward(spiht_ctx *ctx, const double *d_img, int planes, int c, const ImgGeom &ig, int wavelet, int mode,
-                       double q, const double *d_mults, int32_t *d_coeffs, uint32_t *d_maxabs = nullptr, bool f32 = false) {
+                       double q, const double *d_mults, int32_t *d_coeffs, uint32_t *d_maxabs = nullptr, bool f32 = false,
+                       const Px8 *px = nullptr) {
     const WaveletDef &wv = SPIHT_WAVELETS[wavelet];
     const size_t plane_out = (size_t)ig.enc_h * ig.enc_w;
-    if (f32 && ig.L == 0) return SPIHT_ERR_ARG;
+    if (f32 && (ig.L == 0 || px)) return SPIHT_ERR_ARG;
     bool color = ctx->color_on && c == 3;
     if (color && f32) return SPIHT_ERR_ARG;  // the colour model change is float64 (as colour-science's)
     // the plain two-pass level: the modes that compute their extension, periodization, and filters longer than the tiled
     // kernels take (db11.., sym11.., coif4.., dmey)
     const bool twopass = mode >= SPIHT_MODE_SMOOTH || wv.F > SPIHT_MAX_TAPS;
+    // (no 8-bit entry point reaches a transform of level 0: SPIHT refuses that geometry -- the root block's offspring fall
+    // outside the array -- before anything is transformed, on the float64 path as well)
+    if (px && ig.L == 0) return SPIHT_ERR_ARG;
+    if (px && twopass) {  // no 8-bit form of the two-pass level: the float64 picture as a pass of its own
+        StageTimer t(ctx, ST_DWT_L1);
+        CHK(ensure(ctx, ctx->pix, (size_t)planes * ig.hs[0] * ig.ws[0] * 8));
+        LAUNCHCHK(spiht_launch_u8_to_f64(px, planes / c, (double *)ctx->pix.p, ctx->stream));
+        d_img = (const double *)ctx->pix.p;
+        px = nullptr;
+    }
     const double *d_filt = nullptr;
     if (twopass && ig.L > 0) CHK(upload_filters(ctx, wavelet, &d_filt));
     if (color && twopass && ig.L > 0) {
@@ -1245,6 +1265,9 @@ static int dwt_forward(spiht_ctx *ctx, const double *d_img, int planes, int c, c
                 LAUNCHCHK(spiht_launch_dwt_level_ext(&b, np, t_lo, t_hi, bb, bb + (size_t)np * n_b * esz, bb + 2 * (size_t)np * n_b * esz,
                                                      bb + 3 * (size_t)np * n_b * esz, d_filt, ctx->stream));
             }
+        } else if (px && l == 1) {
+            StageTimer t(ctx, ST_DWT_L1);
+            LAUNCHCHK(spiht_launch_dwt_level_u8(&a, px, planes, ctx->stream));
         } else {
             StageTimer t(ctx, l == 1 ? ST_DWT_L1 : ST_DWT_REST);
             LAUNCHCHK(spiht_launch_dwt_level(&a, planes, ctx->stream));
@@ -1273,12 +1296,15 @@ static bool l1flags_geometry(const ImgGeom &ig, int F, L1Flags *fl) {
 }
 
 // d_flags: L1Flags words [planes, gy, gx] the decoder of d_rec left (nullptr: every level-1 tile reads its detail bands)
+// px != nullptr (l_lo == 1): the pixels go to the 8-bit view *px of planes / c images, cropped to px->h x px->w (d_out
+// unused).  The tiled level 1 writes it itself; the two-pass level goes through a conversion pass behind it.
 static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, const ImgGeom &ig, int wavelet, double q,
                        const double *d_mults, double *d_out, int l_hi = -1, int l_lo = 1, const double *d_a_in = nullptr,
-                       const uint32_t *d_flags = nullptr) {
+                       const uint32_t *d_flags = nullptr, const Px8 *px = nullptr) {
     const WaveletDef &wv = SPIHT_WAVELETS[wavelet];
     const int F = wv.F;
     if (l_hi < 0) l_hi = ig.L;
+    if (px && (l_lo != 1 || ig.L == 0)) return SPIHT_ERR_ARG;  // (level 0: see dwt_forward)
     const bool color = ctx->color_on && c == 3;
     if (ig.L == 0) {
         StageTimer t(ctx, ST_IDWT_REST);
@@ -1322,6 +1348,11 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
         if (l == 1 && !a.first && !a.color) a.flags = d_flags;
         memcpy(a.lo, wv.rec_lo, sizeof(double) * std::min(F, SPIHT_MAX_TAPS));
         memcpy(a.hi, wv.rec_hi, sizeof(double) * std::min(F, SPIHT_MAX_TAPS));
+        const bool conv8 = px && l == 1 && (ig.per || F > SPIHT_MAX_TAPS);  // 8-bit output through a pass of its own
+        if (conv8) {
+            CHK(ensure(ctx, ctx->pix, (size_t)planes * a.out_h * a.out_w * 8));
+            a.out = (double *)ctx->pix.p;
+        }
         if (ig.per || F > SPIHT_MAX_TAPS) {
             // periodization / a filter longer than the tiled kernels take: two plain passes through an intermediate (dwt.hip:
             // k_idwt_axis_per), a few planes at a time; the colour model of the picture as a pass of its own behind level 1
@@ -1345,6 +1376,10 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
             if (color && l == 1)
                 LAUNCHCHK(spiht_launch_color3(a.out, a.out, planes / 3, (size_t)a.out_h * a.out_w, ctx->col_inv.A, ctx->col_inv.M,
                                               ctx->col_inv.p, ctx->stream));
+            if (conv8) LAUNCHCHK(spiht_launch_f64_to_u8(a.out, a.out_h, a.out_w, px, planes / c, ctx->stream));
+        } else if (px && l == 1) {
+            StageTimer t(ctx, ST_IDWT_L1);
+            LAUNCHCHK(spiht_launch_idwt_level_u8(&a, px, planes, ctx->stream, ctx->tilectr.dev ? &ctx->tilectr : nullptr));
         } else {
             StageTimer t(ctx, l == 1 ? ST_IDWT_L1 : ST_IDWT_REST);
             LAUNCHCHK(spiht_launch_idwt_level(&a, planes, ctx->stream, ctx->tilectr.dev ? &ctx->tilectr : nullptr));
@@ -1355,6 +1390,59 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
     }
     return SPIHT_OK;
 }
+
+// ---- 8-bit pixels: the view of a [B, c, H, W] uint8 picture batch by byte strides (common.h: Px8) -------------------
+// strides: n == 4: (sb, sc, sh, sw); n == 3: (sc, sh, sw) of one picture; nullptr: dense CHW.  Strides are non-negative;
+// a view that is written must not overlap itself: sorted by stride, every dimension longer than 1 must step past all the
+// smaller ones reach.
+static int make_px8(const int64_t *strides, int n, int64_t B, int64_t c, int64_t h, int64_t w, bool out, Px8 *px) {
+    int64_t st[4] = {c * h * w, h * w, w, 1};
+    if (strides)
+        for (int i = 0; i < n; i++) st[4 - n + i] = strides[i];
+    if (n == 3) st[0] = 0;  // (one picture: no batch stride)
+    const int64_t ext[4] = {B, c, h, w};
+    __int128 span = 1;
+    for (int i = 0; i < 4; i++) {
+        if (st[i] < 0) return SPIHT_ERR_ARG;
+        if (ext[i] > 1) span += (__int128)(ext[i] - 1) * st[i];
+    }
+    if (span >= ((__int128)1 << 62)) return SPIHT_ERR_ARG;
+    if (out) {
+        int idx[4] = {0, 1, 2, 3};
+        std::sort(idx, idx + 4, [&](int x, int y) { return st[x] < st[y]; });
+        int64_t reach = 0;
+        for (int k = 0; k < 4; k++) {
+            const int i = idx[k];
+            if (ext[i] <= 1) continue;
+            if (st[i] < reach + 1) return SPIHT_ERR_ARG;
+            reach += (ext[i] - 1) * st[i];
+        }
+    }
+    memset(px, 0, sizeof(*px));
+    px->sb = st[0]; px->sc = st[1]; px->sh = st[2]; px->sw = st[3];
+    px->c = (int32_t)c; px->h = (int32_t)h; px->w = (int32_t)w;
+    return SPIHT_OK;
+}
+extern "C" int spiht_check_view_u8(int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output) {
+    if (B < 1 || c < 1 || H < 1 || W < 1 || !strides) return SPIHT_ERR_ARG;
+    Px8 px;
+    return make_px8(strides, 4, B, c, H, W, output != 0, &px);
+}
+// bytes from the view's first element to one past its last
+static uint64_t px8_span(const Px8 &px, int64_t B) {
+    return 1 + (uint64_t)(B - 1) * px.sb + (uint64_t)(px.c - 1) * px.sc + (uint64_t)(px.h - 1) * px.sh + (uint64_t)(px.w - 1) * px.sw;
+}
+// the view of pictures b0.. of a batch view (nullptr stays nullptr)
+struct Px8At {
+    Px8 v;
+    const Px8 *p;
+    Px8At(const Px8 *px, int64_t b0) : p(px ? &v : nullptr) {
+        if (!px) return;
+        v = *px;
+        if (v.in) v.in += b0 * v.sb;
+        if (v.out) v.out += b0 * v.sb;
+    }
+};
 
 static int check_img_args(int wavelet, int mode, int64_t B, int64_t c, int64_t H, int64_t W) {
     if (wavelet < 0 || wavelet >= SPIHT_NWAVELETS || mode < 0 || mode > SPIHT_MODE_PERIODIZATION) return SPIHT_ERR_ARG;
@@ -1397,8 +1485,8 @@ extern "C" int spiht_dwt_quant_batch_f32(spiht_ctx *ctx, const float *d_img, int
 
 static int dequant_idwt_batch(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B, int64_t c, int64_t H,
                               int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
-                              double *d_img_out) {
-    if (!ctx || !d_rec || !d_img_out) return SPIHT_ERR_ARG;
+                              double *d_img_out, const Px8 *px = nullptr) {
+    if (!ctx || !d_rec || (!d_img_out && !px)) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
     if (B == 0) return SPIHT_OK;
     ImgGeom ig;
@@ -1413,8 +1501,8 @@ static int dequant_idwt_batch(spiht_ctx *ctx, const int32_t *d_rec, const uint32
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         int nb = (int)std::min<int64_t>(chunk, B - b0);
         CHK(dwt_inverse(ctx, d_rec + (size_t)b0 * c * ig.enc_h * ig.enc_w, nb * (int)c, (int)c, ig, wavelet, q_scale,
-                        d_mults, d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, -1, 1, nullptr,
-                        flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr));
+                        d_mults, px ? nullptr : d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, -1, 1, nullptr,
+                        flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr, Px8At(px, b0).p));
     }
     return SPIHT_OK;
 }
@@ -1428,6 +1516,16 @@ extern "C" int spiht_dequant_idwt_flags_batch_f64(spiht_ctx *ctx, const int32_t 
                                                   double q_scale, const double *channel_mults, double *d_img_out) {
     return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_img_out);
 }
+extern "C" int spiht_dequant_idwt_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
+                                                 int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                                                 double q_scale, const double *channel_mults, uint8_t *d_img_out,
+                                                 const int64_t *out_strides) {
+    if (!d_img_out) return SPIHT_ERR_ARG;
+    Px8 px;
+    CHK(make_px8(out_strides, 4, B, c, H, W, true, &px));
+    px.out = d_img_out;
+    return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, nullptr, &px);
+}
 
 // The inverse transform in two parts, so that a pipelined caller can queue the coarse levels (a quarter of the bytes,
 // six small launches at 1080p) where no list decoder shares the GPU and only level 1 beside it (csrc/pipeline.cpp):
@@ -1435,14 +1533,14 @@ extern "C" int spiht_dequant_idwt_flags_batch_f64(spiht_ctx *ctx, const int32_t 
 //   level1: d_rec + d_approx -> pixels.  With fewer than two levels the coarse part does nothing and d_approx is not read.
 static int idwt_part(spiht_ctx *ctx, const int32_t *d_rec, double *d_approx, int64_t B, int64_t c, int64_t H, int64_t W,
                      int wavelet, int mode, int level, double q_scale, const double *channel_mults, double *d_img_out,
-                     const uint32_t *d_flags = nullptr) {
-    if (!ctx || !d_rec || (!d_approx && !d_img_out)) return SPIHT_ERR_ARG;
+                     const uint32_t *d_flags = nullptr, const Px8 *px = nullptr) {
+    if (!ctx || !d_rec || (!d_approx && !d_img_out && !px)) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
     if (B == 0) return SPIHT_OK;
     ImgGeom ig;
     CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
     if (ig.per) return SPIHT_ERR_ARG;  // (the two-part inverse is a schedule experiment of the tiled kernels)
-    const bool coarse = d_img_out == nullptr;
+    const bool coarse = d_img_out == nullptr && px == nullptr;
     if (coarse && ig.L < 2) return SPIHT_OK;
     if (!coarse && ig.L >= 2 && !d_approx) return SPIHT_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -1462,8 +1560,8 @@ static int idwt_part(spiht_ctx *ctx, const int32_t *d_rec, double *d_approx, int
             CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, d_mults, ap, ig.L, 2, nullptr));
         else
             CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, d_mults,
-                            d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, std::min(ig.L, 1), 1, ig.L >= 2 ? ap : nullptr,
-                            flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr));
+                            px ? nullptr : d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, std::min(ig.L, 1), 1,
+                            ig.L >= 2 ? ap : nullptr, flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr, Px8At(px, b0).p));
     }
     return SPIHT_OK;
 }
@@ -1489,6 +1587,17 @@ extern "C" int spiht_idwt_level1_flags_batch_f64(spiht_ctx *ctx, const int32_t *
     return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                      d_img_out, d_flags);
 }
+extern "C" int spiht_idwt_level1_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                                int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                                                double q_scale, const double *channel_mults, uint8_t *d_img_out,
+                                                const int64_t *out_strides) {
+    if (!d_img_out) return SPIHT_ERR_ARG;
+    Px8 px;
+    CHK(make_px8(out_strides, 4, B, c, H, W, true, &px));
+    px.out = d_img_out;
+    return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                     nullptr, d_flags, &px);
+}
 
 extern "C" int spiht_idwt_approx_shape(int64_t H, int64_t W, int wavelet, int level, int64_t *a_h, int64_t *a_w) {
     if (wavelet < 0 || wavelet >= SPIHT_NWAVELETS || !a_h || !a_w) return SPIHT_ERR_ARG;
@@ -1503,10 +1612,10 @@ extern "C" int spiht_idwt_approx_shape(int64_t H, int64_t W, int wavelet, int le
 static int encode_image_batch(spiht_ctx *ctx, const void *d_img_v, bool f32, int64_t B, int64_t c, int64_t H, int64_t W,
                               int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                               uint64_t max_bits, uint8_t *d_out, uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n,
-                              int32_t *d_coeffs) {
+                              int32_t *d_coeffs, const Px8 *px = nullptr) {
     const double *d_img = (const double *)d_img_v;
     const size_t esz = f32 ? 4 : 8;
-    if (!ctx || !d_img || !d_out || !d_nbits || !d_max_n) return SPIHT_ERR_ARG;
+    if (!ctx || (!d_img && !px) || !d_out || !d_nbits || !d_max_n) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
     if (B == 0) return SPIHT_OK;
     ImgGeom ig;
@@ -1527,8 +1636,8 @@ static int encode_image_batch(spiht_ctx *ctx, const void *d_img_v, bool f32, int
         }
         CHK(ensure(ctx, ctx->maxabs, (size_t)nb * 4));
         HIPCHK(hipMemsetAsync(ctx->maxabs.p, 0, (size_t)nb * 4, ctx->stream));
-        CHK(dwt_forward(ctx, (const double *)((const char *)d_img + (size_t)b0 * c * H * W * esz), nb * (int)c, (int)c, ig, wavelet,
-                        mode, q_scale, d_mults, co, (uint32_t *)ctx->maxabs.p, f32));
+        CHK(dwt_forward(ctx, px ? nullptr : (const double *)((const char *)d_img + (size_t)b0 * c * H * W * esz), nb * (int)c, (int)c,
+                        ig, wavelet, mode, q_scale, d_mults, co, (uint32_t *)ctx->maxabs.p, f32, Px8At(px, b0).p));
         CHK(encode_device(ctx, g, co, nb, max_bits, d_out + (size_t)b0 * slot_stride, slot_stride, d_nbits + b0,
                           d_max_n + b0, true));
     }
@@ -1550,12 +1659,23 @@ extern "C" int spiht_encode_image_batch_f32(spiht_ctx *ctx, const float *d_img, 
     return encode_image_batch(ctx, d_img, true, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, d_out,
                               slot_stride, d_nbits, d_max_n, d_coeffs);
 }
+extern "C" int spiht_encode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t B, int64_t c,
+                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                           const double *channel_mults, uint64_t max_bits, uint8_t *d_out,
+                                           uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs) {
+    if (!d_img) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, B, c, H, W));
+    Px8 px;
+    CHK(make_px8(strides, 4, B, c, H, W, false, &px));
+    px.in = d_img;
+    return encode_image_batch(ctx, nullptr, false, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, d_out,
+                              slot_stride, d_nbits, d_max_n, d_coeffs, &px);
+}
 
-extern "C" int spiht_decode_image_batch_f64(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
-                                            const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
-                                            int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
-                                            const double *channel_mults, double *d_img_out, int32_t *d_rec) {
-    if (!ctx || !d_data || !d_nbytes || !d_max_n || !d_img_out) return SPIHT_ERR_ARG;
+static int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
+                              const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                              double q_scale, const double *channel_mults, double *d_img_out, int32_t *d_rec, const Px8 *px) {
+    if (!ctx || !d_data || !d_nbytes || !d_max_n || (!d_img_out && !px)) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
     if (B == 0) return SPIHT_OK;
     ImgGeom ig;
@@ -1581,7 +1701,8 @@ extern "C" int spiht_decode_image_batch_f64(spiht_ctx *ctx, const uint8_t *d_dat
             CHK(decode_device(ctx, g, d_data + (size_t)b0 * slot_stride, slot_stride, d_nbytes + b0, d_max_n + b0, nb, rec,
                               nullptr, nullptr, 0, true, nullptr, flagged ? &fl : nullptr));
             CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, d_mults,
-                            d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, -1, 1, nullptr, flagged ? fl.p : nullptr));
+                            px ? nullptr : d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, -1, 1, nullptr, flagged ? fl.p : nullptr,
+                            Px8At(px, b0).p));
             continue;
         }
         // Internal coefficient array: it is all zero on entry and is left all zero -- after the inverse transform the
@@ -1599,7 +1720,8 @@ extern "C" int spiht_decode_image_batch_f64(spiht_ctx *ctx, const uint8_t *d_dat
         CHK(decode_device(ctx, g, d_data + (size_t)b0 * slot_stride, slot_stride, d_nbytes + b0, d_max_n + b0, nb, rec, nullptr,
                           nullptr, 0, false, &da, flagged ? &fl : nullptr));
         CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, d_mults,
-                        d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, -1, 1, nullptr, flagged ? fl.p : nullptr));
+                        px ? nullptr : d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, -1, 1, nullptr, flagged ? fl.p : nullptr,
+                        Px8At(px, b0).p));
         if (da.nslots >= nb) {
             StageTimer t(ctx, ST_MEMSET);
             LAUNCHCHK(spiht_launch_unscatter(&da, ctx->stream));
@@ -1609,16 +1731,37 @@ extern "C" int spiht_decode_image_batch_f64(spiht_ctx *ctx, const uint8_t *d_dat
     }
     return SPIHT_OK;  // asynchronous: errors surface in spiht_ctx_synchronize()
 }
+extern "C" int spiht_decode_image_batch_f64(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                            const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                            int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                            const double *channel_mults, double *d_img_out, int32_t *d_rec) {
+    return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                              d_img_out, d_rec, nullptr);
+}
+extern "C" int spiht_decode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                           const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                           const double *channel_mults, uint8_t *d_img_out, const int64_t *out_strides,
+                                           int32_t *d_rec) {
+    if (!d_img_out) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, B, c, H, W));
+    Px8 px;
+    CHK(make_px8(out_strides, 4, B, c, H, W, true, &px));
+    px.out = d_img_out;
+    return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                              nullptr, d_rec, &px);
+}
 
 // ------------------------------------------------------------------------------------------------
 // the drop-in calls on host arrays: encode_image / decode_image / decode_from_rec_arr of the reference's wrapper
 // (spiht_wrapper.py:142-216, 259-281) as one C call each.  Pixels, stream and coefficient array live in the
 // context's grow-only device buffers -- no allocation per call after the first of a given size.
 // ------------------------------------------------------------------------------------------------
+// px8: the picture is the host 8-bit view *px8 (img unused): only the bytes its strides span are uploaded
 static int encode_image_host(spiht_ctx *ctx, const void *img, bool f32, int64_t c, int64_t H, int64_t W, int wavelet,
                              int mode, int level, double q_scale, const double *channel_mults, uint64_t max_bits,
-                             uint8_t *out, uint64_t out_cap, uint64_t *out_nbits, uint8_t *max_n) {
-    if (!ctx || !img || !out_nbits || !max_n || (!out && out_cap)) return SPIHT_ERR_ARG;
+                             uint8_t *out, uint64_t out_cap, uint64_t *out_nbits, uint8_t *max_n, const Px8 *px8 = nullptr) {
+    if (!ctx || (!img && !px8) || !out_nbits || !max_n || (!out && out_cap)) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, 1, c, H, W));
     ImgGeom ig;
     CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
@@ -1630,18 +1773,21 @@ static int encode_image_host(spiht_ctx *ctx, const void *img, bool f32, int64_t 
     if (max_bits != 0) bits = std::min(bits, max_bits);
     if (bits >= 0xFFFFFF00ull * 8ull) return SPIHT_ERR_TOO_LARGE;
     const uint64_t slot = std::max<uint64_t>(4, ((bits + 7) / 8 + 3) & ~3ull);
-    const size_t img_bytes = (size_t)c * H * W * (f32 ? 4 : 8);
-    CHK(ensure(ctx, ctx->himg, img_bytes));
+    const size_t img_bytes = px8 ? (size_t)px8_span(*px8, 1) : (size_t)c * H * W * (f32 ? 4 : 8);
+    DevBuf &hb = px8 ? ctx->hpix8 : ctx->himg;
+    CHK(ensure(ctx, hb, img_bytes));
     CHK(ensure(ctx, ctx->out, slot));
     CHK(ensure(ctx, ctx->nbits, 8));
     CHK(ensure(ctx, ctx->maxn, 4));
     CHK(clear_err(ctx));
     {
         StageTimer t(ctx, ST_H2D);
-        HIPCHK(hipMemcpyAsync(ctx->himg.p, img, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(hb.p, px8 ? (const void *)px8->in : img, img_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    CHK(encode_image_batch(ctx, ctx->himg.p, f32, 1, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
-                           (uint8_t *)ctx->out.p, slot, (uint64_t *)ctx->nbits.p, (uint8_t *)ctx->maxn.p, nullptr));
+    Px8 dpx;
+    if (px8) { dpx = *px8; dpx.in = (const uint8_t *)hb.p; }
+    CHK(encode_image_batch(ctx, px8 ? nullptr : hb.p, f32, 1, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
+                           (uint8_t *)ctx->out.p, slot, (uint64_t *)ctx->nbits.p, (uint8_t *)ctx->maxn.p, nullptr, px8 ? &dpx : nullptr));
     uint64_t nbits = 0;
     uint8_t mn = 0;
     HIPCHK(hipMemcpyAsync(&nbits, ctx->nbits.p, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1672,11 +1818,24 @@ extern "C" int spiht_encode_image_host_f32(spiht_ctx *ctx, const float *img, int
     return encode_image_host(ctx, img, true, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out, out_cap,
                              out_nbits, max_n);
 }
+extern "C" int spiht_encode_image_host_u8(spiht_ctx *ctx, const uint8_t *img, const int64_t *strides, int64_t c, int64_t H,
+                                          int64_t W, int wavelet, int mode, int level, double q_scale,
+                                          const double *channel_mults, uint64_t max_bits, uint8_t *out, uint64_t out_cap,
+                                          uint64_t *out_nbits, uint8_t *max_n) {
+    if (!img) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, 1, c, H, W));
+    Px8 px;
+    CHK(make_px8(strides, 3, 1, c, H, W, false, &px));
+    px.in = img;
+    return encode_image_host(ctx, nullptr, false, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out, out_cap,
+                             out_nbits, max_n, &px);
+}
 
-extern "C" int spiht_decode_image_host_f64(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
-                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
-                                           const double *channel_mults, double *img_out) {
-    if (!ctx || !img_out || (!data && nbytes)) return SPIHT_ERR_ARG;
+// px8: the pixels go to the host 8-bit view *px8 (img_out unused), which is dense: c*H*W bytes
+static int decode_image_host(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H, int64_t W,
+                             int wavelet, int mode, int level, double q_scale, const double *channel_mults, double *img_out,
+                             const Px8 *px8 = nullptr) {
+    if (!ctx || (!img_out && !px8) || (!data && nbytes)) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, 1, c, H, W));
     ImgGeom ig;
     CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
@@ -1685,11 +1844,12 @@ extern "C" int spiht_decode_image_host_f64(spiht_ctx *ctx, const uint8_t *data, 
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     const uint64_t slot = std::max<uint64_t>(4, (nbytes + 3) & ~3ull);
-    const size_t out_bytes = (size_t)c * ig.rec_H * ig.rec_W * 8;
+    const size_t out_bytes = px8 ? (size_t)c * H * W : (size_t)c * ig.rec_H * ig.rec_W * 8;
+    DevBuf &hb = px8 ? ctx->hpix8 : ctx->himg;
     CHK(ensure(ctx, ctx->data, slot));
     CHK(ensure(ctx, ctx->nbytes, 8));
     CHK(ensure(ctx, ctx->maxn, 4));
-    CHK(ensure(ctx, ctx->himg, out_bytes));
+    CHK(ensure(ctx, hb, out_bytes));
     CHK(clear_err(ctx));
     {
         StageTimer t(ctx, ST_H2D);
@@ -1699,16 +1859,36 @@ extern "C" int spiht_decode_image_host_f64(spiht_ctx *ctx, const uint8_t *data, 
         HIPCHK(hipMemcpyAsync(ctx->maxn.p, &n, 1, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));  // &nbytes / &n are stack temporaries
     }
-    CHK(spiht_decode_image_batch_f64(ctx, (const uint8_t *)ctx->data.p, slot, (const uint64_t *)ctx->nbytes.p,
-                                     (const uint8_t *)ctx->maxn.p, 1, c, H, W, wavelet, mode, level, q_scale, channel_mults,
-                                     (double *)ctx->himg.p, nullptr));
+    Px8 dpx;
+    if (px8) { dpx = *px8; dpx.out = (uint8_t *)hb.p; }
+    CHK(decode_image_batch(ctx, (const uint8_t *)ctx->data.p, slot, (const uint64_t *)ctx->nbytes.p, (const uint8_t *)ctx->maxn.p, 1,
+                           c, H, W, wavelet, mode, level, q_scale, channel_mults, px8 ? nullptr : (double *)hb.p, nullptr,
+                           px8 ? &dpx : nullptr));
     CHK(read_err(ctx));
     {
         StageTimer t(ctx, ST_D2H);
-        HIPCHK(hipMemcpyAsync(img_out, ctx->himg.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(px8 ? (void *)px8->out : (void *)img_out, hb.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return SPIHT_OK;
+}
+extern "C" int spiht_decode_image_host_f64(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                           const double *channel_mults, double *img_out) {
+    return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out);
+}
+extern "C" int spiht_decode_image_host_u8(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                          int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                          const double *channel_mults, uint8_t *img_out, const int64_t *strides) {
+    if (!img_out) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, 1, c, H, W));
+    Px8 px;
+    CHK(make_px8(strides, 3, 1, c, H, W, true, &px));
+    // the copy back is of c*H*W bytes: only the two dense layouts, CHW and HWC
+    const bool chw = px.sw == 1 && px.sh == W && px.sc == H * W, hwc = px.sc == 1 && px.sw == c && px.sh == W * c;
+    if (!chw && !hwc) return SPIHT_ERR_ARG;
+    px.out = img_out;
+    return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, nullptr, &px);
 }
 
 extern "C" int spiht_dequant_idwt_host_f64(spiht_ctx *ctx, const int32_t *rec, int64_t c, int64_t H, int64_t W, int wavelet,
@@ -1742,10 +1922,10 @@ extern "C" int spiht_dequant_idwt_host_f64(spiht_ctx *ctx, const int32_t *rec, i
 // context while another context list-codes a different batch (bench.py)
 // ------------------------------------------------------------------------------------------------
 
-extern "C" int spiht_dwt_pyramid_batch_f64(spiht_ctx *ctx, const double *d_img, int64_t B, int64_t c, int64_t H, int64_t W,
-                                           int wavelet, int mode, int level, double q_scale, const double *channel_mults,
-                                           int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb, uint32_t *d_maxabs) {
-    if (!ctx || !d_img || !d_coeffs || !d_maxabs || (!d_dmsb) != (!d_lmsb)) return SPIHT_ERR_ARG;
+static int dwt_pyramid_batch(spiht_ctx *ctx, const double *d_img, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
+                             int level, double q_scale, const double *channel_mults, int32_t *d_coeffs, uint8_t *d_dmsb,
+                             uint8_t *d_lmsb, uint32_t *d_maxabs, const Px8 *px) {
+    if (!ctx || (!d_img && !px) || !d_coeffs || !d_maxabs || (!d_dmsb) != (!d_lmsb)) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
     if (B == 0) return SPIHT_OK;
     ImgGeom ig;
@@ -1761,13 +1941,32 @@ extern "C" int spiht_dwt_pyramid_batch_f64(spiht_ctx *ctx, const double *d_img, 
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         int nb = (int)std::min<int64_t>(chunk, B - b0);
         int32_t *co = d_coeffs + (size_t)b0 * g.n;
-        CHK(dwt_forward(ctx, d_img + (size_t)b0 * c * H * W, nb * (int)c, (int)c, ig, wavelet, mode, q_scale, d_mults, co,
-                        d_maxabs + b0, false));
+        CHK(dwt_forward(ctx, px ? nullptr : d_img + (size_t)b0 * c * H * W, nb * (int)c, (int)c, ig, wavelet, mode, q_scale, d_mults,
+                        co, d_maxabs + b0, false, Px8At(px, b0).p));
         if (!d_dmsb) continue;  // transform + max|coefficient| only: the pyramid is queued elsewhere (spiht_pyramid_batch_i32)
         StageTimer t(ctx, ST_PYRAMID);
         LAUNCHCHK(spiht_launch_pyramid(&g, nb, co, d_dmsb + (size_t)b0 * g.n, d_lmsb + (size_t)b0 * g.n, ctx->stream));
     }
     return SPIHT_OK;
+}
+extern "C" int spiht_dwt_pyramid_batch_f64(spiht_ctx *ctx, const double *d_img, int64_t B, int64_t c, int64_t H, int64_t W,
+                                           int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                           int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb, uint32_t *d_maxabs) {
+    if (!d_img) return SPIHT_ERR_ARG;
+    return dwt_pyramid_batch(ctx, d_img, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs, d_dmsb, d_lmsb, d_maxabs,
+                             nullptr);
+}
+extern "C" int spiht_dwt_pyramid_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t B, int64_t c,
+                                          int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                          const double *channel_mults, int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb,
+                                          uint32_t *d_maxabs) {
+    if (!d_img) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, B, c, H, W));
+    Px8 px;
+    CHK(make_px8(strides, 4, B, c, H, W, false, &px));
+    px.in = d_img;
+    return dwt_pyramid_batch(ctx, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs, d_dmsb, d_lmsb, d_maxabs,
+                             &px);
 }
 
 extern "C" int spiht_encode_lists_batch_i32(spiht_ctx *ctx, const int32_t *d_x, const uint8_t *d_dmsb,

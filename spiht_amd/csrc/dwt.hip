@@ -25,6 +25,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+
 #ifndef DW_TH
 #define DW_TH 12      // output rows per tile.  Level 1 of 256 1080p images: 12 rows 3.8-3.95 ms, 16 rows 4.05-4.2, 14: 4.1,
 #endif                // 10: 4.4, 20: 4.5, 24: 4.2 (25.9 KB of LDS per workgroup at 12 rows: six workgroups per CU)
@@ -131,11 +133,28 @@ __device__ __forceinline__ double dequant(int32_t r, double m, double q, bool ha
     return v / q;
 }
 
+// 8-bit pixels (common.h: Px8): k -> the double k / 255.0, numpy's P / 255 in every bit.  Not a division (a dozen float64
+// instructions; 28 of them per thread and tile cost level 1 of 256 1080p pictures about 0.4 ms) and not k * (1/255) alone
+// (24 of the 256 quotients differ): the product corrected once by its exact residual, which gives the correctly rounded
+// quotient for all 256 k (tests/test_u8_cpu.py proves the algorithm for all of them).
+// v -> (uint8)(clip(v, 0, 1) * 255.0) truncated, NaN -> 0 (fmax / fmin return the number of a NaN pair)
+__device__ __forceinline__ double px8_value(uint8_t k) {
+    const double x = (double)k, r = 1.0 / 255.0;
+    const double q = x * r;
+    return fma(fma(-q, 255.0, x), r, q);
+}
+__device__ __forceinline__ uint8_t px8_store_value(double v) {
+    const double c = fmin(fmax(v, 0.0), 1.0);
+    const double s = c * 255.0;
+    return (uint8_t)(uint32_t)s;
+}
+
 // grid: (ceil(out_w/TW), ceil(out_h/TH), planes).  LOM / HIM: bit j set = tap j of dec_lo / dec_hi is non-zero;
 // a zero tap contributes exactly nothing (0*x added to the running sum), so skipping it changes no bit and
 // removes a third (bior2.2) to a fifth of the float64 arithmetic.
 // One tile of k_dwt_level.
-template <int F, uint32_t LOM, uint32_t HIM, int PS, int NR>
+// U8: the level's input is the strided 8-bit picture a.px (common.h: Px8), converted on the loads.
+template <int F, uint32_t LOM, uint32_t HIM, int PS, int NR, bool U8 = false>
 __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS], double (&s_hi)[2][PS], uint32_t tbx, uint32_t tby,
                                          uint32_t tbz) {
     constexpr int NC = 2 * DW_TW + F - 2;  // input columns needed by the tile
@@ -145,7 +164,9 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
     constexpr int RS = HC + 1;
     const int plane = (int)tbz;
     const int oh0 = (int)tby * DW_TH, ow0 = (int)tbx * DW_TW;
-    const double *__restrict__ in = a.in + (size_t)plane * a.in_h * a.in_w;
+    const double *__restrict__ in = U8 ? nullptr : a.in + (size_t)plane * a.in_h * a.in_w;
+    // (the plane base in 64 bits, from the tile coordinates in vector registers: see below)
+    const uint8_t *__restrict__ in8 = U8 ? a.px.in + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
     const int tid = threadIdx.x;
 
     // input row needed for output row o, tap j: 2*o + 1 - j ; first needed row r0 = 2*oh0 + 1 - (F-1)
@@ -154,7 +175,7 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
     __shared__ long long s_off[NR];
     if (tid < NR) {
         const int gr = ext_index(r0 + tid, a.in_h, a.mode);
-        s_off[tid] = gr < 0 ? -1ll : (long long)gr * a.in_w;
+        s_off[tid] = gr < 0 ? -1ll : (long long)gr * (U8 ? a.px.sh : (long long)a.in_w);
     }
     __shared__ uint32_t s_amax;
     if (tid == 0) s_amax = 0;
@@ -171,7 +192,23 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
         // through an index the compiler cannot prove uniform, so that they stay in vector registers.
         int lz = 0;
         asm volatile("" : "+v"(lz));
-        if (a.mode != 3) {  // not zero padding: every index is inside the picture
+        if (U8) {  // byte loads at the same row offsets, ALL of them first (converted one by one behind its load, the
+                   // compiler waited for each load before it issued the next: level 1 took 7.1 instead of 4.3 ms), then
+                   // k -> k / 255.0
+            const long long co8 = gc < 0 ? 0 : (long long)gc * a.px.sw;
+            uint32_t raw[NR];
+            static_assert(NR <= 64, "one bit per row");
+            uint64_t okm = 0;  // bit r: row r is inside the picture (zero padding: a zero sample otherwise)
+#pragma unroll
+            for (int r = 0; r < NR; r++) {
+                const long long off = s_off[r + lz];
+                const bool ok = a.mode != 3 || (gc >= 0 && off >= 0);
+                okm |= (ok ? 1ull : 0ull) << r;
+                raw[r] = in8[ok ? off + co8 : 0];
+            }
+#pragma unroll
+            for (int r = 0; r < NR; r++) x[r] = ((okm >> r) & 1ull) ? px8_value((uint8_t)raw[r]) : 0.0;
+        } else if (a.mode != 3) {  // not zero padding: every index is inside the picture
 #pragma unroll
             for (int r = 0; r < NR; r++) x[r] = in[s_off[r + lz] + gc];
         } else {
@@ -243,7 +280,7 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
     }
 }
 
-template <int F, uint32_t LOM, uint32_t HIM>
+template <int F, uint32_t LOM, uint32_t HIM, bool U8 = false>  // U8: level 1 of an 8-bit picture (a.px; a.in unused)
 __global__ __launch_bounds__(DWF_BLOCK) void k_dwt_level(DwtKArgs a) {
     constexpr int NC = 2 * DW_TW + F - 2, NR = 2 * DW_TH + F - 2, HC = (NC + 1) / 2;
     // two column-parity planes; the padding makes the plane stride an odd multiple of 16 banks, so the even and odd
@@ -257,7 +294,7 @@ __global__ __launch_bounds__(DWF_BLOCK) void k_dwt_level(DwtKArgs a) {
     uint32_t lin = blockIdx.x;
     asm volatile("" : "+v"(lin));
     xcd_tile_at(lin, (a.out_w + DW_TW - 1) / DW_TW, (a.out_h + DW_TH - 1) / DW_TH, a.planes, tbx, tby, tbz);
-    dwt_tile<F, LOM, HIM, PS, NR>(a, s_lo, s_hi, tbx, tby, tbz);
+    dwt_tile<F, LOM, HIM, PS, NR, U8>(a, s_lo, s_hi, tbx, tby, tbz);
 }
 
 // ---- helpers of the persistent inverse-transform kernel (k_idwt_level_pf) -------------------------------------------
@@ -285,7 +322,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void *p, uint
 // a side stream -- cost the level 5 to 12 %: measured); this kernel then recomputes just the outputs whose order
 // matters (ov_h / ov_w: the last row and column of a bior level), one thread each, straight from global memory, and
 // overwrites them.  grid: (ceil(outputs / 256), planes).
-template <int F>
+template <int F, bool U8 = false>  // U8: level 1 of an 8-bit picture (a.px)
 __global__ __launch_bounds__(256) void k_dwt_edge(DwtKArgs a) {
     __shared__ double s_f[2][F];  // taps, indexed at run time below
     if (threadIdx.x < F) { s_f[0][threadIdx.x] = a.lo[threadIdx.x]; s_f[1][threadIdx.x] = a.hi[threadIdx.x]; }
@@ -301,7 +338,8 @@ __global__ __launch_bounds__(256) void k_dwt_edge(DwtKArgs a) {
         int oh, ow;
         if (t < nA) { oh = a.ov_h + t / a.out_w; ow = t % a.out_w; }
         else { const int u = t - nA; oh = u / nc; ow = a.ov_w + u % nc; }
-        const double *__restrict__ in = a.in + (size_t)plane * a.in_h * a.in_w;
+        const double *__restrict__ in = U8 ? nullptr : a.in + (size_t)plane * a.in_h * a.in_w;
+        const uint8_t *__restrict__ in8 = U8 ? a.px.in + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
         const int ir = 2 * oh + 1, ic = 2 * ow + 1;
         const int jbr = oh >= a.ov_h ? ir - a.in_h : -1, jbc = ow >= a.ov_w ? ic - a.in_w : -1;
         int gr[F];
@@ -318,7 +356,10 @@ __global__ __launch_bounds__(256) void k_dwt_edge(DwtKArgs a) {
             const int gc = ext_index(ic - j, a.in_w, a.mode);
             double xv[F];
 #pragma unroll
-            for (int r = 0; r < F; r++) xv[r] = (gc < 0 || gr[r] < 0) ? 0.0 : in[(size_t)gr[r] * a.in_w + gc];
+            for (int r = 0; r < F; r++) {
+                if (U8) xv[r] = (gc < 0 || gr[r] < 0) ? 0.0 : px8_value(in8[(int64_t)gr[r] * a.px.sh + (int64_t)gc * a.px.sw]);
+                else xv[r] = (gc < 0 || gr[r] < 0) ? 0.0 : in[(size_t)gr[r] * a.in_w + gc];
+            }
             double tl = 0.0, th = 0.0;
 #pragma unroll
             for (int s2 = 0; s2 < F; s2++) {
@@ -563,7 +604,7 @@ extern "C" int spiht_launch_color3(const double *d_in, double *d_out, int B, siz
 #ifndef C1_WPE
 #define C1_WPE 4
 #endif
-template <int F, uint32_t LOM, uint32_t HIM>
+template <int F, uint32_t LOM, uint32_t HIM, bool U8 = false>  // U8: an 8-bit picture (a.px; a.in unused)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C1_WPE, C1_WPE)))  // 128 VGPRs: left alone the compiler interleaves
 void k_dwt1_color(DwtKArgs a, uint32_t gx, uint32_t gy) {                       // the six powers of a step over 173 (2 waves / SIMD)
     constexpr int SW = (256 - (F - 2)) / 2;  // output columns per strip: exactly 256 input columns
@@ -581,14 +622,20 @@ void k_dwt1_color(DwtKArgs a, uint32_t gx, uint32_t gy) {                       
     const int ow0 = (int)tbx * SW, oa = (int)tby * C1_ROWS;
     const int ob = min(oa + C1_ROWS, a.out_h);
     const size_t npl = (size_t)a.in_h * a.in_w;
-    const double *__restrict__ in = a.in + (size_t)img * 3 * npl;
+    const double *__restrict__ in = U8 ? nullptr : a.in + (size_t)img * 3 * npl;
+    const uint8_t *__restrict__ in8 = U8 ? a.px.in + (int64_t)img * a.px.sb : nullptr;
     const int tid = threadIdx.x;
     const int gc = ext_index(2 * ow0 + 2 - F + tid, a.in_w, a.mode);
     auto ld = [&](int r, double &u0, double &u1, double &u2) {  // raw R, G, B of (row r, this column), extension applied
         const int gr = ext_index(r, a.in_h, a.mode);
         const bool z = gc < 0 || gr < 0;
-        const size_t o = z ? 0 : (size_t)gr * a.in_w + gc;
-        u0 = in[o]; u1 = in[o + npl]; u2 = in[o + 2 * npl];
+        if (U8) {  // (the pixel's three channels sc bytes apart: neighbours in an interleaved picture)
+            const int64_t o = z ? 0 : (int64_t)gr * a.px.sh + (int64_t)gc * a.px.sw;
+            u0 = px8_value(in8[o]); u1 = px8_value(in8[o + a.px.sc]); u2 = px8_value(in8[o + 2 * a.px.sc]);
+        } else {
+            const size_t o = z ? 0 : (size_t)gr * a.in_w + gc;
+            u0 = in[o]; u1 = in[o + npl]; u2 = in[o + 2 * npl];
+        }
         if (z) { u0 = 0.0; u1 = 0.0; u2 = 0.0; }
     };
     // "zero" extension pads the CONVERTED signal with zeros (pywt extends what it is given): convert, then zero
@@ -1061,7 +1108,7 @@ __global__ __launch_bounds__(256) void k_dequant_plain(const int32_t *in, double
 
 // grid: (ceil(out_w/TW), ceil(out_h/TH), planes).  LOM / HIM: non-zero taps of rec_lo / rec_hi (a product with a
 // zero tap adds exactly nothing to `ca*lo + cd*hi`, so it is skipped).
-template <int F, uint32_t LOM, uint32_t HIM>
+template <int F, uint32_t LOM, uint32_t HIM, bool U8 = false>  // U8: level 1 into an 8-bit picture (a.px; a.out unused)
 __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
     // band index k contributes to output n with tap t = n + F - 2 - 2k in [0,F):  k in [n/2, n/2 + F/2 - 1]
     constexpr int HF = F / 2;
@@ -1123,7 +1170,8 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
     double wl[HF], wh[HF];  // register window: tl/th of the last HF band rows (index HF-1 = newest)
 #pragma unroll
     for (int s = 0; s < HF; s++) { wl[s] = 0.0; wh[s] = 0.0; }
-    double *__restrict__ out = a.out + (size_t)plane * a.out_h * a.out_w;
+    double *__restrict__ out = U8 ? nullptr : a.out + (size_t)plane * a.out_h * a.out_w;
+    uint8_t *__restrict__ out8 = U8 ? a.px.out + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
     const int rbase = half * (IW_TH / 4);  // first band row (tile-relative) of this half
 #pragma unroll
     for (int rr = 0; rr < KHH; rr++) {
@@ -1167,7 +1215,11 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
                     if (hnz) sd += wh[s] * a.hi[mp + F - 2 - 2 * s];
                 }
                 const double sacc = (0.0 + sa) + sd;
-                if (m + mp < a.out_h && n < a.out_w) out[(size_t)(m + mp) * a.out_w + n] = sacc;
+                if (U8) {
+                    if (m + mp < a.px.h && n < a.px.w) out8[(int64_t)(m + mp) * a.px.sh + (int64_t)n * a.px.sw] = px8_store_value(sacc);
+                } else {
+                    if (m + mp < a.out_h && n < a.out_w) out[(size_t)(m + mp) * a.out_w + n] = sacc;
+                }
             }
         }
     }
@@ -1190,7 +1242,9 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
 // and are not read.  The loads stay unconditional -- a branch around them would make every later wait a wait for
 // everything -- and go through a buffer descriptor of the plane instead: an offset beyond it returns 0 without a trip
 // to memory.  The word of a tile is fetched when the tile's number becomes known, a tile of work ahead of its use.
-template <int F, uint32_t LOM, uint32_t HIM, bool FIRST, bool FLAGS = false>  // FIRST: coarsest level, the approximation comes from the packed array
+// U8: the output is the strided 8-bit picture a.px (common.h: Px8); the launcher sees to it that a plane's bytes span less
+// than 2^31 (32-bit buffer offsets).
+template <int F, uint32_t LOM, uint32_t HIM, bool FIRST, bool FLAGS = false, bool U8 = false>  // FIRST: coarsest level, the approximation comes from the packed array
 __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_t gx, uint32_t gy, uint32_t *ctr,
                                                                       TileBase cb) {
     static_assert(!(FIRST && FLAGS), "the flags are those of level 1 of a transform with two levels or more");
@@ -1305,8 +1359,13 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
         // stores stand in straight-line code.  With branches around them the compiler cannot count them, and the wait
         // for the next tile's samples at the top of the loop becomes a wait for these stores as well.
         const uint32_t row_bytes = (uint32_t)a.out_w * 8u;
-        const __amdgpu_buffer_rsrc_t orsrc = plane_rsrc(a.out + (size_t)plane * a.out_h * a.out_w, (uint32_t)a.out_h * row_bytes);
+        const __amdgpu_buffer_rsrc_t orsrc = U8 ? plane_rsrc(a.px.out + (int64_t)(plane / (uint32_t)a.c) * a.px.sb + (int64_t)(plane % (uint32_t)a.c) * a.px.sc,
+                                                             (uint32_t)((int64_t)(a.px.h - 1) * a.px.sh + (int64_t)(a.px.w - 1) * a.px.sw + 1))
+                                                : plane_rsrc(a.out + (size_t)plane * a.out_h * a.out_w, (uint32_t)a.out_h * row_bytes);
         const uint32_t voff0 = n < a.out_w ? (uint32_t)(2 * (kh0 + rbase)) * row_bytes + (uint32_t)n * 8u : BUF_OOB;
+        // (U8) the crop: columns x >= w by an offset beyond the descriptor, rows y >= h by a compare per store
+        const int y0 = 2 * (kh0 + rbase);
+        const uint32_t voff8 = n < a.px.w ? (uint32_t)y0 * (uint32_t)a.px.sh + (uint32_t)n * (uint32_t)a.px.sw : BUF_OOB;
 #pragma unroll
         for (int rr = 0; rr < KHH; rr++) {
             const int r = rbase + rr;
@@ -1342,8 +1401,14 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
                         if (hnz) sd += wh[s2] * a.hi[mp + F - 2 - 2 * s2];
                     }
                     const double sacc = (0.0 + sa) + sd;
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sacc), orsrc,
-                                                          voff0 + (uint32_t)(2 * (rr - (HF - 1)) + mp) * row_bytes, 0, 0);
+                    if constexpr (U8) {
+                        const int dy = 2 * (rr - (HF - 1)) + mp;
+                        __builtin_amdgcn_raw_buffer_store_b8(px8_store_value(sacc), orsrc,
+                                                             y0 + dy < a.px.h ? voff8 + (uint32_t)dy * (uint32_t)a.px.sh : BUF_OOB, 0, 0);
+                    } else {
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sacc), orsrc,
+                                                              voff0 + (uint32_t)(2 * (rr - (HF - 1)) + mp) * row_bytes, 0, 0);
+                    }
                 }
             }
         }
@@ -1381,7 +1446,7 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
 // result: the transformed picture in the coded colour model never exists in memory.  Arithmetic-bound, so the tile is
 // smaller than k_idwt_level's (IWC_TH rows: 38.6 KB of LDS for the three channels, four workgroups per CU).
 #define IWC_TH 8
-template <int F, uint32_t LOM, uint32_t HIM>
+template <int F, uint32_t LOM, uint32_t HIM, bool U8 = false>  // U8: an 8-bit picture (a.px; a.out unused)
 __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
     constexpr int HF = F / 2;
     constexpr int KH = IWC_TH / 2 + HF - 1, KW = IW_TW / 2 + HF - 1, KHH = IWC_TH / 4 + HF - 1;
@@ -1436,7 +1501,8 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
     for (int ch = 0; ch < 3; ch++)
 #pragma unroll
         for (int s = 0; s < HF; s++) { wl[ch][s] = 0.0; wh[ch][s] = 0.0; }
-    double *__restrict__ out = a.out + (size_t)img * 3 * opl;
+    double *__restrict__ out = U8 ? nullptr : a.out + (size_t)img * 3 * opl;
+    uint8_t *__restrict__ out8 = U8 ? a.px.out + (int64_t)img * a.px.sb : nullptr;
     const int rbase = half * (IWC_TH / 4);
 #pragma unroll
     for (int rr = 0; rr < KHH; rr++) {
@@ -1481,13 +1547,20 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
                     }
                     px[ch] = (0.0 + sa) + sd;
                 }
-                if (m + mp < a.out_h && n < a.out_w) {
+                if (U8 ? (m + mp < a.px.h && n < a.px.w) : (m + mp < a.out_h && n < a.out_w)) {
                     double w0, w1, w2;
                     color3_px(a.col, s_pw, px[0], px[1], px[2], w0, w1, w2);
-                    const size_t o = (size_t)(m + mp) * a.out_w + n;
-                    out[o] = w0;
-                    out[o + opl] = w1;
-                    out[o + 2 * opl] = w2;
+                    if (U8) {
+                        const int64_t o = (int64_t)(m + mp) * a.px.sh + (int64_t)n * a.px.sw;
+                        out8[o] = px8_store_value(w0);
+                        out8[o + a.px.sc] = px8_store_value(w1);
+                        out8[o + 2 * a.px.sc] = px8_store_value(w2);
+                    } else {
+                        const size_t o = (size_t)(m + mp) * a.out_w + n;
+                        out[o] = w0;
+                        out[o + opl] = w1;
+                        out[o + 2 * opl] = w2;
+                    }
                 }
             }
         }
@@ -1496,9 +1569,11 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
 
 // ---- host launchers -----------------------------------------------------------------------------
 
+// px != nullptr: level 1 of an 8-bit picture (the U8 kernels; a.in unused)
 template <int F, uint32_t LOM, uint32_t HIM>
-static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
+static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st, const Px8 *px) {
     a.planes = planes;
+    if (px) a.px = *px;
     a.ov_h = a.out_h;
     a.ov_w = a.out_w;
     if (a.f32) {
@@ -1513,7 +1588,8 @@ static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
         if (a.mode != 4) a.ov_h = min(a.out_h, (a.in_h + z + 2) / 2);
         if (a.mode != 4) a.ov_w = min(a.out_w, (a.in_w + z + 2) / 2);
         const uint32_t gx = (uint32_t)((a.out_w + SW - 1) / SW), gy = (uint32_t)((a.out_h + C1_ROWS - 1) / C1_ROWS);
-        hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
+        if (px) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, true>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
+        else hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
         return (int)hipGetLastError();
     }
     // Outputs summed in PyWavelets' overhang order: those with jb = 2o+1-N >= 0 (constant-edge mode keeps ascending order).
@@ -1526,28 +1602,35 @@ static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
     if (a.mode != 4) a.ov_h = min(a.out_h, (a.in_h + z + 2) / 2);
     if (a.mode != 4) a.ov_w = min(a.out_w, (a.in_w + z + 2) / 2);
     const uint32_t nt = (uint32_t)((a.out_w + DW_TW - 1) / DW_TW) * (uint32_t)((a.out_h + DW_TH - 1) / DW_TH) * (uint32_t)planes;
-    hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+    if (px) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
     const int n_edge = (a.out_h - a.ov_h) * a.out_w + a.ov_h * (a.out_w - a.ov_w);
-    if (n_edge > 0) hipLaunchKernelGGL(k_dwt_edge<F>, dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
+    if (n_edge > 0) {
+        if (px) hipLaunchKernelGGL((k_dwt_edge<F, true>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_dwt_edge<F>, dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
+    }
     return (int)hipGetLastError();
 }
 // specialised for the zero-tap pattern of the known filter bank of that length, generic otherwise
 template <int F, uint32_t LOM, uint32_t HIM>
-static int launch_dwt_F(const DwtKArgs &a, int planes, hipStream_t st) {
+static int launch_dwt_F(const DwtKArgs &a, int planes, hipStream_t st, const Px8 *px) {
     uint32_t lom = 0, him = 0;
     for (int j = 0; j < F; j++) {
         if (a.lo[j] != 0.0) lom |= 1u << j;
         if (a.hi[j] != 0.0) him |= 1u << j;
     }
-    if (lom == LOM && him == HIM) return launch_dwt_FM<F, LOM, HIM>(a, planes, st);
-    return launch_dwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st);
+    if (lom == LOM && him == HIM) return launch_dwt_FM<F, LOM, HIM>(a, planes, st, px);
+    return launch_dwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st, px);
 }
+// px != nullptr: level 1 into an 8-bit picture (the U8 kernels; a.out unused)
 template <int F, uint32_t LOM, uint32_t HIM>
-static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) {
+static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc, const Px8 *px) {
     a.planes = planes;
+    if (px) a.px = *px;
     if (a.color) {  // level 1 of a 3-channel image, colour model change on the stores
         uint32_t ntc = (uint32_t)((a.out_w + IW_TW - 1) / IW_TW) * (uint32_t)((a.out_h + IWC_TH - 1) / IWC_TH) * (uint32_t)(planes / 3);
-        hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
+        if (px) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, true>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
         return (int)hipGetLastError();
     }
     const uint32_t gx = (uint32_t)((a.out_w + IW_TW - 1) / IW_TW), gy = (uint32_t)((a.out_h + IW_TH - 1) / IW_TH);
@@ -1556,7 +1639,11 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) 
     // workgroups that fetch a tile ahead
     constexpr uint32_t pf_min = 20000u;
     const int num_cu = tc ? tc->num_cu : 0;
-    if (tc && tc->dev && num_cu >= 2 && nt >= pf_min && (uint64_t)(a.out_h + IW_TH) * a.out_w * 8u < (1ull << 31)) {  // (>= 8 workgroups: one per tile range at least)
+    // (the persistent kernel addresses a plane with 32-bit offsets: float64 planes by their size, the 8-bit output by the
+    // span of its strides)
+    const bool off32 = px ? (uint64_t)((px->h - 1) * px->sh + (px->w - 1) * px->sw) + 1u < (1ull << 31)
+                          : (uint64_t)(a.out_h + IW_TH) * a.out_w * 8u < (1ull << 31);
+    if (tc && tc->dev && num_cu >= 2 && nt >= pf_min && off32) {  // (>= 8 workgroups: one per tile range at least)
         const int g = tc->wg_per_cu > 0 ? tc->wg_per_cu : IWP_WG;
         const uint32_t G = (uint32_t)(num_cu * g);
         // A caller that asks for g < IWP_WG workgroups per CU wants the rest of the CU for somebody else -- the pipelined
@@ -1580,7 +1667,12 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) 
             tc->base[x] += (nt >> 3) + (x < (nt & 7u) ? 1u : 0u) + 2u * ((G + 7u - x) >> 3);
         }
         tc->started += G;
-        if (a.first) hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
+        if (px) {
+            if (a.first) hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, true, false, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
+            else if (a.flags && (uint64_t)a.enc_h * a.enc_w * 4u < (1ull << 31))
+                hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, true, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
+            else { a.flags = nullptr; hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, false, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb); }
+        } else if (a.first) hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
         else if (a.flags && (uint64_t)a.enc_h * a.enc_w * 4u < (1ull << 31))
             hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
         else { a.flags = nullptr; hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb); }
@@ -1592,51 +1684,68 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) 
         }
         return (int)e;
     }
-    hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
+    if (px) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, true>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
     return (int)hipGetLastError();
 }
 template <int F, uint32_t LOM, uint32_t HIM>
-static int launch_idwt_F(const IdwtKArgs &a, int planes, hipStream_t st, TileCtr *tc) {
+static int launch_idwt_F(const IdwtKArgs &a, int planes, hipStream_t st, TileCtr *tc, const Px8 *px) {
     uint32_t lom = 0, him = 0;
     for (int j = 0; j < F; j++) {
         if (a.lo[j] != 0.0) lom |= 1u << j;
         if (a.hi[j] != 0.0) him |= 1u << j;
     }
-    if (lom == LOM && him == HIM) return launch_idwt_FM<F, LOM, HIM>(a, planes, st, tc);
-    return launch_idwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st, tc);
+    if (lom == LOM && him == HIM) return launch_idwt_FM<F, LOM, HIM>(a, planes, st, tc, px);
+    return launch_idwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st, tc, px);
 }
 
-extern "C" int spiht_launch_dwt_level(const DwtKArgs *a, int planes, hipStream_t st) {
+static int spiht_launch_dwt_level_px(const DwtKArgs *a, int planes, hipStream_t st, const Px8 *px) {
     switch (a->F) {
-    case 2: return launch_dwt_F<2, 0x3u, 0x3u>(*a, planes, st);            // haar
-    case 6: return launch_dwt_F<6, 0x3Eu, 0x0Eu>(*a, planes, st);          // bior2.2
-    case 10: return launch_dwt_F<10, 0x3FEu, 0x0FEu>(*a, planes, st);      // bior4.4
-    case 18: return launch_dwt_F<18, 0x3FFFEu, 0x3FF8u>(*a, planes, st);   // bior6.8
+    case 2: return launch_dwt_F<2, 0x3u, 0x3u>(*a, planes, st, px);            // haar
+    case 6: return launch_dwt_F<6, 0x3Eu, 0x0Eu>(*a, planes, st, px);          // bior2.2
+    case 10: return launch_dwt_F<10, 0x3FEu, 0x0FEu>(*a, planes, st, px);      // bior4.4
+    case 18: return launch_dwt_F<18, 0x3FFFEu, 0x3FF8u>(*a, planes, st, px);   // bior6.8
     // every other even length up to SPIHT_MAX_TAPS (db / sym / coif / the other bior and rbio banks): all taps taken
-    case 4: return launch_dwt_F<4, 0xFu, 0xFu>(*a, planes, st);
-    case 8: return launch_dwt_F<8, 0xFFu, 0xFFu>(*a, planes, st);
-    case 12: return launch_dwt_F<12, 0xFFFu, 0xFFFu>(*a, planes, st);
-    case 14: return launch_dwt_F<14, 0x3FFFu, 0x3FFFu>(*a, planes, st);
-    case 16: return launch_dwt_F<16, 0xFFFFu, 0xFFFFu>(*a, planes, st);
-    case 20: return launch_dwt_F<20, 0xFFFFFu, 0xFFFFFu>(*a, planes, st);
+    case 4: return launch_dwt_F<4, 0xFu, 0xFu>(*a, planes, st, px);
+    case 8: return launch_dwt_F<8, 0xFFu, 0xFFu>(*a, planes, st, px);
+    case 12: return launch_dwt_F<12, 0xFFFu, 0xFFFu>(*a, planes, st, px);
+    case 14: return launch_dwt_F<14, 0x3FFFu, 0x3FFFu>(*a, planes, st, px);
+    case 16: return launch_dwt_F<16, 0xFFFFu, 0xFFFFu>(*a, planes, st, px);
+    case 20: return launch_dwt_F<20, 0xFFFFFu, 0xFFFFFu>(*a, planes, st, px);
     default: return -1;
     }
 }
+extern "C" int spiht_launch_dwt_level(const DwtKArgs *a, int planes, hipStream_t st) {
+    return spiht_launch_dwt_level_px(a, planes, st, nullptr);
+}
+// level 1 of an 8-bit picture (a->in unused); only the tiled routes (the caller converts in a pass of its own elsewhere)
+extern "C" int spiht_launch_dwt_level_u8(const DwtKArgs *a, const Px8 *px, int planes, hipStream_t st) {
+    if (!px || a->f32) return -1;
+    return spiht_launch_dwt_level_px(a, planes, st, px);
+}
 // tc: tile counters of the calling context (nullptr: fixed-stride tile order in the persistent kernel)
-extern "C" int spiht_launch_idwt_level(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc) {
+static int spiht_launch_idwt_level_px(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc, const Px8 *px) {
     switch (a->F) {
-    case 2: return launch_idwt_F<2, 0x3u, 0x3u>(*a, planes, st, tc);            // haar
-    case 6: return launch_idwt_F<6, 0x0Eu, 0x3Eu>(*a, planes, st, tc);          // bior2.2 rec_lo / rec_hi
-    case 10: return launch_idwt_F<10, 0x0FEu, 0x3FEu>(*a, planes, st, tc);      // bior4.4
-    case 18: return launch_idwt_F<18, 0x3FF8u, 0x3FFFEu>(*a, planes, st, tc);   // bior6.8
-    case 4: return launch_idwt_F<4, 0xFu, 0xFu>(*a, planes, st, tc);
-    case 8: return launch_idwt_F<8, 0xFFu, 0xFFu>(*a, planes, st, tc);
-    case 12: return launch_idwt_F<12, 0xFFFu, 0xFFFu>(*a, planes, st, tc);
-    case 14: return launch_idwt_F<14, 0x3FFFu, 0x3FFFu>(*a, planes, st, tc);
-    case 16: return launch_idwt_F<16, 0xFFFFu, 0xFFFFu>(*a, planes, st, tc);
-    case 20: return launch_idwt_F<20, 0xFFFFFu, 0xFFFFFu>(*a, planes, st, tc);
+    case 2: return launch_idwt_F<2, 0x3u, 0x3u>(*a, planes, st, tc, px);            // haar
+    case 6: return launch_idwt_F<6, 0x0Eu, 0x3Eu>(*a, planes, st, tc, px);          // bior2.2 rec_lo / rec_hi
+    case 10: return launch_idwt_F<10, 0x0FEu, 0x3FEu>(*a, planes, st, tc, px);      // bior4.4
+    case 18: return launch_idwt_F<18, 0x3FF8u, 0x3FFFEu>(*a, planes, st, tc, px);   // bior6.8
+    case 4: return launch_idwt_F<4, 0xFu, 0xFu>(*a, planes, st, tc, px);
+    case 8: return launch_idwt_F<8, 0xFFu, 0xFFu>(*a, planes, st, tc, px);
+    case 12: return launch_idwt_F<12, 0xFFFu, 0xFFFu>(*a, planes, st, tc, px);
+    case 14: return launch_idwt_F<14, 0x3FFFu, 0x3FFFu>(*a, planes, st, tc, px);
+    case 16: return launch_idwt_F<16, 0xFFFFu, 0xFFFFu>(*a, planes, st, tc, px);
+    case 20: return launch_idwt_F<20, 0xFFFFFu, 0xFFFFFu>(*a, planes, st, tc, px);
     default: return -1;
     }
+}
+extern "C" int spiht_launch_idwt_level(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc) {
+    return spiht_launch_idwt_level_px(a, planes, st, tc, nullptr);
+}
+// level 1 into an 8-bit picture (a->out unused)
+extern "C" int spiht_launch_idwt_level_u8(const IdwtKArgs *a, const Px8 *px, int planes, hipStream_t st, TileCtr *tc) {
+    if (!px) return -1;
+    return spiht_launch_idwt_level_px(a, planes, st, tc, px);
 }
 // pad strips of coeffs_to_array for `L` levels: hs/ws band sizes and offh/offw block offsets (index 1..L)
 extern "C" int spiht_launch_zero_pads(int L, const int64_t *hs, const int64_t *ws, const int64_t *offh, const int64_t *offw,
@@ -1665,5 +1774,38 @@ extern "C" int spiht_launch_quant_plain(const double *in, int32_t *out, size_t n
 extern "C" int spiht_launch_dequant_plain(const int32_t *in, double *out, size_t n_per_plane, int planes, int c,
                                           const double *mults, double q, hipStream_t st) {
     hipLaunchKernelGGL(k_dequant_plain, dim3(1024), dim3(256), 0, st, in, out, n_per_plane, planes, c, mults, q);
+    return (int)hipGetLastError();
+}
+
+// ---- 8-bit pixels to and from dense float64, for the routes whose level 1 has no 8-bit form ------------------------------
+// (level 0, the two-pass levels, the colour model change in front of a two-pass level).  One thread per sample, the same
+// conversions as the fused kernels (px8_value / px8_store_value).
+__global__ __launch_bounds__(256) void k_u8_to_f64(Px8 px, double *__restrict__ out, int64_t n) {  // out [B*c, h, w]
+    const int64_t hw = (int64_t)px.h * px.w;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
+        const int64_t p = t / hw, r = t - p * hw, y = r / px.w, x = r - y * px.w;
+        const int64_t o = (p / px.c) * px.sb + (p % px.c) * px.sc + y * px.sh + x * px.sw;
+        out[t] = px8_value(px.in[o]);
+    }
+}
+__global__ __launch_bounds__(256) void k_f64_to_u8(const double *__restrict__ in, int rec_h, int rec_w, Px8 px, int64_t n) {
+    const int64_t hw = (int64_t)px.h * px.w;  // n = B*c*h*w: the cropped picture
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
+        const int64_t p = t / hw, r = t - p * hw, y = r / px.w, x = r - y * px.w;
+        const int64_t o = (p / px.c) * px.sb + (p % px.c) * px.sc + y * px.sh + x * px.sw;
+        px.out[o] = px8_store_value(in[(p * rec_h + y) * rec_w + x]);
+    }
+}
+static unsigned pass_grid(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 8192); }
+extern "C" int spiht_launch_u8_to_f64(const Px8 *px, int64_t B, double *out, hipStream_t st) {
+    const int64_t n = B * px->c * (int64_t)px->h * px->w;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(k_u8_to_f64, dim3(pass_grid(n)), dim3(256), 0, st, *px, out, n);
+    return (int)hipGetLastError();
+}
+extern "C" int spiht_launch_f64_to_u8(const double *in, int rec_h, int rec_w, const Px8 *px, int64_t B, hipStream_t st) {
+    const int64_t n = B * px->c * (int64_t)px->h * px->w;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(k_f64_to_u8, dim3(pass_grid(n)), dim3(256), 0, st, in, rec_h, rec_w, *px, n);
     return (int)hipGetLastError();
 }

@@ -53,6 +53,10 @@ struct spiht_pipeline {
     bool pending = false;      // a batch whose inverse transform has not been queued yet
     int pending_slot = 0;
     double *pending_out = nullptr;
+    // ... or its 8-bit output (spiht_pipeline_submit_u8): every step keeps the form it was submitted with
+    uint8_t *pending_out8 = nullptr;
+    int64_t pending_str8[4] = {0, 0, 0, 0};
+    bool pending_str8_set = false;  // false: dense CHW
     // colour model of the coded pictures (spiht_pipeline_set_color3): the pipeline's own, put on the H context around its calls
     bool color_on = false;
     double cAf[9], cMf[9], cAi[9], cMi[9], cpf = 1.0, cpi = 1.0;
@@ -223,7 +227,15 @@ static int queue_inverse_coarse(spiht_pipeline *p, int s) {
     return SPIHT_OK;
 }
 static int queue_inverse_level1(spiht_pipeline *p, int s, double *d_img_out) {
-    if (p->approx)
+    if (p->pending_out8) {
+        const int64_t *str = p->pending_str8_set ? p->pending_str8 : nullptr;
+        if (p->approx)
+            CHK(spiht_idwt_level1_flags_batch_u8(p->Hc, p->rec[s], p->approx, p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode,
+                                                 p->level, p->q, p->mp(), p->pending_out8, str));
+        else
+            CHK(spiht_dequant_idwt_flags_batch_u8(p->Hc, p->rec[s], p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
+                                                  p->q, p->mp(), p->pending_out8, str));
+    } else if (p->approx)
         CHK(spiht_idwt_level1_flags_batch_f64(p->Hc, p->rec[s], p->approx, p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode,
                                               p->level, p->q, p->mp(), d_img_out));
     else
@@ -240,13 +252,25 @@ static int queue_inverse(spiht_pipeline *p, int s, double *d_img_out) {
     return queue_inverse_level1(p, s, d_img_out);
 }
 
+// the views of an 8-bit step (spiht_pipeline_submit_u8; its d_img / d_img_out are then null)
+struct Px8Step {
+    const uint8_t *in = nullptr;
+    const int64_t *in_strides = nullptr;
+    uint8_t *out = nullptr;
+    const int64_t *out_strides = nullptr;
+};
 static int submit_impl(spiht_pipeline *p, const double *d_img, uint8_t *d_out, uint64_t *d_nbits, uint8_t *d_max_n, double *d_img_out,
-                       spiht_comm *comm, uint8_t *d_all_slots, uint64_t *d_all_nbits, uint8_t *d_all_max_n, int rank) {
+                       spiht_comm *comm, uint8_t *d_all_slots, uint64_t *d_all_nbits, uint8_t *d_all_max_n, int rank,
+                       const Px8Step &u8 = Px8Step()) {
     const int s = (int)(p->step & 1), o = s ^ 1;
     spiht_ctx *L = p->Lc[s];
     // H: front half of the encoder
-    CHK(spiht_dwt_pyramid_batch_f64(p->Hc, d_img, p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level, p->q, p->mp(),
-                                    p->coeffs[s], p->dmsb[s], p->lmsb[s], p->maxabs[s]));
+    if (u8.in)
+        CHK(spiht_dwt_pyramid_batch_u8(p->Hc, u8.in, u8.in_strides, p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level, p->q,
+                                       p->mp(), p->coeffs[s], p->dmsb[s], p->lmsb[s], p->maxabs[s]));
+    else
+        CHK(spiht_dwt_pyramid_batch_f64(p->Hc, d_img, p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level, p->q, p->mp(),
+                                        p->coeffs[s], p->dmsb[s], p->lmsb[s], p->maxabs[s]));
     CHK(spiht_event_record(p->ev_a[s], p->Hc));
     // L: list coding, after the previous batch's decoder on the other context (list kernels never run beside one another)
     if (p->used[o]) CHK(spiht_ctx_wait_event(L, p->ev_d[o]));
@@ -291,6 +315,9 @@ static int submit_impl(spiht_pipeline *p, const double *d_img, uint8_t *d_out, u
     p->pending = true;
     p->pending_slot = s;
     p->pending_out = d_img_out;
+    p->pending_out8 = u8.out;
+    p->pending_str8_set = u8.out_strides != nullptr;
+    if (u8.out_strides) memcpy(p->pending_str8, u8.out_strides, sizeof(p->pending_str8));
     p->step++;
     return SPIHT_OK;
 }
@@ -313,6 +340,22 @@ extern "C" int spiht_pipeline_submit_gather(spiht_pipeline *p, const double *d_i
 extern "C" int spiht_pipeline_submit(spiht_pipeline *p, const double *d_img, uint8_t *d_out, uint64_t *d_nbits, uint8_t *d_max_n,
                                      double *d_img_out) {
     return spiht_pipeline_submit_gather(p, d_img, d_out, d_nbits, d_max_n, d_img_out, nullptr, nullptr, nullptr, nullptr, 0);
+}
+
+extern "C" int spiht_pipeline_submit_u8(spiht_pipeline *p, const uint8_t *d_img, const int64_t *in_strides, uint8_t *d_out,
+                                        uint64_t *d_nbits, uint8_t *d_max_n, uint8_t *d_img_out, const int64_t *out_strides) {
+    if (!p || !d_img || !d_out || !d_nbits || !d_max_n || !d_img_out) return SPIHT_ERR_ARG;
+    if (p->poisoned != SPIHT_OK) return p->poisoned;
+    // the views are checked before anything is queued: a bad one leaves the pipeline as it was
+    if (in_strides) CHK(spiht_check_view_u8(p->B, p->c, p->H, p->W, in_strides, 0));
+    if (out_strides) CHK(spiht_check_view_u8(p->B, p->c, p->H, p->W, out_strides, 1));
+    Px8Step u8;
+    u8.in = d_img; u8.in_strides = in_strides; u8.out = d_img_out; u8.out_strides = out_strides;
+    HScope sc(p);
+    int st = sc.st;
+    if (st == SPIHT_OK) st = submit_impl(p, nullptr, d_out, d_nbits, d_max_n, nullptr, nullptr, nullptr, nullptr, nullptr, 0, u8);
+    if (st != SPIHT_OK) p->poisoned = st;
+    return st;
 }
 
 extern "C" int spiht_pipeline_flush(spiht_pipeline *p) {

@@ -206,6 +206,96 @@ def decode_image(encoding_result: EncodingResult, spiht_settings: SpihtSettings,
     return out
 
 
+def check_u8_view(shape, strides, output):
+    """The library's rule for an 8-bit view (include/spiht_hip.h, *_u8; spiht_check_view_u8): byte strides of a (B, c, h, w)
+    or (c, h, w) `shape` are non-negative, and a view that is written does not overlap itself -- sorted by stride, every
+    dimension longer than one steps past the largest offset the smaller ones reach.  Raises ValueError.  No device needed."""
+    shape, strides = [int(x) for x in shape], [int(x) for x in strides]
+    if len(shape) != len(strides) or len(shape) not in (3, 4):
+        raise ValueError("%d strides for a %d-dimensional picture" % (len(strides), len(shape)))
+    if len(shape) == 3:
+        shape, strides = [1] + shape, [0] + strides
+    if min(shape) < 1:
+        raise ValueError("empty 8-bit picture %s" % (shape,))
+    st = np.ascontiguousarray(strides, dtype=np.int64)
+    if _lib.lib().spiht_check_view_u8(shape[0], shape[1], shape[2], shape[3], C.c_void_p(st.ctypes.data), int(bool(output))):
+        raise ValueError("the strides %s of the 8-bit %s %s are not supported (negative%s)"
+                         % (strides, "output" if output else "input", shape, ", or overlapping" if output else ""))
+
+
+def _u8_picture(image, spiht_settings):
+    """checks of encode_image_u8: a uint8 (c, h, w) array (or (h, w, c) given as such a view); negative strides copied"""
+    if not isinstance(image, np.ndarray) or image.dtype != np.uint8:
+        raise ValueError("encode_image_u8 takes a uint8 array, not %s" % (getattr(image, "dtype", type(image)),))
+    if image.ndim != 3:
+        raise ValueError('image ndim must be 3: c,h,w')
+    if spiht_settings.color_model is not None:
+        if spiht_settings.color_model not in color_models.SUPPORTED_MODELS:
+            color_models.convert(np.zeros((3, 1, 1)), 'RGB', spiht_settings.color_model)  # the reference's ValueError
+        if image.shape[0] != 3:
+            raise ValueError("colour conversion needs 3 channels")
+    if any(st < 0 for st in image.strides):
+        image = np.ascontiguousarray(image)
+    return image
+
+
+def encode_image_u8(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSettings(), level: Optional[int] = None,
+                    max_bits: Optional[int] = None, channels_last: bool = False):
+    """8-bit pixels: the EncodingResult of encode_image(image / 255.0, ...), field by field, with the conversion done on the
+    device (only the bytes cross the link).  image: uint8 (c, h, w), or (h, w, c) with channels_last -- any strides (an
+    RGBA buffer's rgba[..., :3] view goes as it is)."""
+    if isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and channels_last:
+        image = image.transpose(2, 0, 1)
+    image = _u8_picture(image, spiht_settings)
+    c, h, w = image.shape
+    wid, mid = _wavelet_mode_ids(spiht_settings)
+    g = _geometry(h, w, wid, level, mid)
+    mults, mults_p = _mults_arg(spiht_settings.per_channel_quant_scales, c)
+    if max_bits == None:  # noqa: E711  (as encode_image)
+        max_bits = 99999999999999999
+    max_bits = spiht_rs._as_usize(max_bits, "max_bits")
+    L = _lib.lib()
+    bound = C.c_uint64()
+    _lib.check(L.spiht_encode_bound(c, g["enc_h"], g["enc_w"], g["ll_h"], g["ll_w"], 0x3FFFFFFF, max_bits, C.byref(bound)))
+    out = np.empty(max(int(bound.value), 4), dtype=np.uint8)
+    nbits, mn = C.c_uint64(), C.c_uint8()
+    strides = np.array(image.strides, dtype=np.int64)
+    ctx = _lib.default_context()
+    with color_models.fused(ctx, spiht_settings.color_model):
+        _lib.check(L.spiht_encode_image_host_u8(
+            ctx.handle, C.c_void_p(image.ctypes.data), C.c_void_p(strides.ctypes.data), c, h, w, wid, mid,
+            -1 if level is None else int(level), float(spiht_settings.quantization_scale), mults_p, max_bits,
+            C.c_void_p(out.ctypes.data), out.size, C.byref(nbits), C.byref(mn)))
+    out = out[:(int(nbits.value) + 7) // 8]
+    return EncodingResult(out.tobytes(), h, w, c, int(mn.value), level)
+
+
+def decode_image_u8(encoding_result: EncodingResult, spiht_settings: SpihtSettings, channels_last: bool = False) -> np.ndarray:
+    """8-bit pixels: (np.clip(decode_image(r, s), 0, 1) * 255).astype(np.uint8) cropped to the encoded picture's h x w, with
+    the conversion done on the device.  Returns a new uint8 array (c, h, w), or (h, w, c) with channels_last."""
+    if encoding_result._encoding_version != ENCODER_DECODER_VERSION:
+        raise ValueError(encoding_result._encoding_version)
+    h, w, c, level = encoding_result.h, encoding_result.w, encoding_result.c, encoding_result.level
+    if spiht_settings.color_model is not None and c != 3:
+        raise ValueError("colour conversion needs 3 channels")
+    wid, mid = _wavelet_mode_ids(spiht_settings)
+    _geometry(h, w, wid, level, mid)
+    buf = spiht_rs._as_u8_vec(encoding_result.encoded_bytes)
+    n = spiht_rs._as_usize(encoding_result.max_n, "n")
+    if n > 255:
+        raise OverflowError("out of range integral type conversion attempted")
+    mults, mults_p = _mults_arg(spiht_settings.per_channel_quant_scales, c)
+    out = _lib.result_array((h, w, c) if channels_last else (c, h, w), np.uint8)
+    strides = np.array((1, w * c, c) if channels_last else (h * w, w, 1), dtype=np.int64)
+    ctx = _lib.default_context()
+    with color_models.fused(ctx, spiht_settings.color_model):
+        _lib.check(_lib.lib().spiht_decode_image_host_u8(
+            ctx.handle, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, n, c, h, w, wid, mid,
+            -1 if level is None else int(level), float(spiht_settings.quantization_scale), mults_p,
+            C.c_void_p(out.ctypes.data), C.c_void_p(strides.ctypes.data)))
+    return out
+
+
 def _band_sizes(h, w, wavelet, levels, mode="reflect"):
     """band heights / widths per level, [0] = the image: len' = (len + F - 1) // 2 (pywt.dwt_coeff_len), under periodization
     ceil(len / 2) -- the same rule with a two-tap filter"""
