@@ -120,13 +120,14 @@ class BatchCodec:
                 float(self.settings.quantization_scale), self._mults_p, self.max_bits, C.c_void_p(d_out), self.slot_stride,
                 C.c_void_p(d_nbits), C.c_void_p(d_max_n), None))
 
-    def decode_device_u8(self, d_data, d_nbytes, d_max_n, B, d_img_out, strides=None, d_rec=None):
+    def decode_device_u8(self, d_data, d_nbytes, d_max_n, B, d_img_out, strides=None, d_rec=None, slot_stride=None):
         """-> uint8 [B, c, H, W] on the device, cropped to H x W, laid out by `strides` (bytes; None: dense CHW; the bytes
         between the view's elements -- an RGBA buffer's alpha, row padding -- are not written)"""
         st, st_p = self._u8_strides(B, strides, True)
         with self._color():
             _lib.check(self.L.spiht_decode_image_batch_u8(
-                self.ctx.handle, C.c_void_p(d_data), self.slot_stride, C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
+                self.ctx.handle, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
+                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
                 self.c, self.H, self.W, self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
                 C.c_void_p(d_img_out), st_p, C.c_void_p(d_rec) if d_rec else None))
 
@@ -142,54 +143,14 @@ class BatchCodec:
         B = images.shape[0]
         if images.shape[1:] != (self.c, self.H, self.W):
             raise ValueError("encode_u8: pictures of shape %s, the codec's are %s" % (images.shape[1:], (self.c, self.H, self.W)))
-        ctx = self.ctx
-        d_img = DeviceArray(ctx, images.shape, np.uint8)
-        d_out = DeviceArray(ctx, (B, self.slot_stride), np.uint8)
-        d_nbits = DeviceArray(ctx, (B,), np.uint64)
-        d_maxn = DeviceArray(ctx, (B,), np.uint8)
-        try:
-            d_img.upload(images)
-            self.encode_device_u8(d_img.ptr, B, d_out.ptr, d_nbits.ptr, d_maxn.ptr)
-            ctx.synchronize()
-            out, nbits, maxn = d_out.download(), d_nbits.download(), d_maxn.download()
-        finally:
-            for d in (d_img, d_out, d_nbits, d_maxn):
-                d.free()
-        return [EncodingResult(out[b, :(int(nbits[b]) + 7) // 8].tobytes(), self.H, self.W, self.c, int(maxn[b]),
-                               self.level) for b in range(B)]
+        return self._encode_host(images, self.encode_device_u8)
 
     def decode_u8(self, results, channels_last=False):
         """list of EncodingResult (same geometry) -> uint8 [B, c, H, W] (or [B, H, W, c]), cropped to H x W"""
-        B = len(results)
-        stride = max(4, (max(len(r.encoded_bytes) for r in results) + 3) & ~3)
-        data = np.zeros((B, stride), dtype=np.uint8)
-        for b, r in enumerate(results):
-            data[b, :len(r.encoded_bytes)] = np.frombuffer(r.encoded_bytes, np.uint8)
-        nbytes = np.array([len(r.encoded_bytes) for r in results], dtype=np.uint64)
-        maxn = np.array([r.max_n for r in results], dtype=np.uint8)
         c, H, W = self.c, self.H, self.W
-        shape = (B, H, W, c) if channels_last else (B, c, H, W)
         strides = (H * W * c, 1, W * c, c) if channels_last else None
-        ctx = self.ctx
-        d_data = DeviceArray(ctx, data.shape, np.uint8)
-        d_nbytes = DeviceArray(ctx, (B,), np.uint64)
-        d_maxn = DeviceArray(ctx, (B,), np.uint8)
-        d_img = DeviceArray(ctx, shape, np.uint8)
-        try:
-            d_data.upload(data)
-            d_nbytes.upload(nbytes)
-            d_maxn.upload(maxn)
-            st, st_p = self._u8_strides(B, strides, True)
-            with self._color():
-                _lib.check(self.L.spiht_decode_image_batch_u8(
-                    ctx.handle, C.c_void_p(d_data.ptr), stride, C.c_void_p(d_nbytes.ptr), C.c_void_p(d_maxn.ptr), B, c, H, W,
-                    self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
-                    C.c_void_p(d_img.ptr), st_p, None))
-            ctx.synchronize()
-            return d_img.download()
-        finally:
-            for d in (d_data, d_nbytes, d_maxn, d_img):
-                d.free()
+        return self._decode_host(results, (H, W, c) if channels_last else (c, H, W), np.uint8,
+                                 lambda *a, slot_stride: self.decode_device_u8(*a, strides=strides, slot_stride=slot_stride))
 
     def nbits_to_nbytes(self, d_nbits, B, d_nbytes):
         _lib.check(self.L.spiht_nbits_to_nbytes(self.ctx.handle, C.c_void_p(d_nbits), int(B), C.c_void_p(d_nbytes)))
@@ -198,16 +159,24 @@ class BatchCodec:
     def encode(self, images):
         """images: float array [B,c,H,W] -> list of EncodingResult"""
         images = np.ascontiguousarray(images, dtype=self.pixel_dtype)
-        B = images.shape[0]
         assert images.shape[1:] == (self.c, self.H, self.W)
+        return self._encode_host(images, self.encode_device)
+
+    def decode(self, results):
+        """list of EncodingResult (same geometry) -> float64 [B,c,H',W']"""
+        return self._decode_host(results, (self.c, self.geom["rec_h"], self.geom["rec_w"]), np.float64, self.decode_device)
+
+    def _encode_host(self, images, encode_device):
+        """host pictures [B, ...] -> their device copy -> encode_device(d_img, B, d_out, d_nbits, d_max_n) -> EncodingResults"""
+        B = images.shape[0]
         ctx = self.ctx
-        d_img = DeviceArray(ctx, images.shape, self.pixel_dtype)
+        d_img = DeviceArray(ctx, images.shape, images.dtype)
         d_out = DeviceArray(ctx, (B, self.slot_stride), np.uint8)
         d_nbits = DeviceArray(ctx, (B,), np.uint64)
         d_maxn = DeviceArray(ctx, (B,), np.uint8)
         try:
             d_img.upload(images)
-            self.encode_device(d_img.ptr, B, d_out.ptr, d_nbits.ptr, d_maxn.ptr)
+            encode_device(d_img.ptr, B, d_out.ptr, d_nbits.ptr, d_maxn.ptr)
             ctx.synchronize()
             out, nbits, maxn = d_out.download(), d_nbits.download(), d_maxn.download()
         finally:
@@ -216,8 +185,9 @@ class BatchCodec:
         return [EncodingResult(out[b, :(int(nbits[b]) + 7) // 8].tobytes(), self.H, self.W, self.c, int(maxn[b]),
                                self.level) for b in range(B)]
 
-    def decode(self, results):
-        """list of EncodingResult (same geometry) -> float64 [B,c,H',W']"""
+    def _decode_host(self, results, shape, dtype, decode_device):
+        """the streams of `results` on the device, in slots of the longest one's size -> decode_device(d_data, d_nbytes,
+        d_max_n, B, d_img_out, slot_stride=...) into `dtype` pictures of `shape` -> host array [B, *shape]"""
         B = len(results)
         stride = max(4, (max(len(r.encoded_bytes) for r in results) + 3) & ~3)
         data = np.zeros((B, stride), dtype=np.uint8)
@@ -229,12 +199,12 @@ class BatchCodec:
         d_data = DeviceArray(ctx, data.shape, np.uint8)
         d_nbytes = DeviceArray(ctx, (B,), np.uint64)
         d_maxn = DeviceArray(ctx, (B,), np.uint8)
-        d_img = DeviceArray(ctx, (B, self.c, self.geom["rec_h"], self.geom["rec_w"]), np.float64)
+        d_img = DeviceArray(ctx, (B,) + tuple(shape), dtype)
         try:
             d_data.upload(data)
             d_nbytes.upload(nbytes)
             d_maxn.upload(maxn)
-            self.decode_device(d_data.ptr, d_nbytes.ptr, d_maxn.ptr, B, d_img.ptr, slot_stride=stride)
+            decode_device(d_data.ptr, d_nbytes.ptr, d_maxn.ptr, B, d_img.ptr, slot_stride=stride)
             ctx.synchronize()
             return d_img.download()
         finally:
@@ -328,20 +298,11 @@ class Pipeline:
     def submit_u8(self, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides=None, out_strides=None):
         """queue one step of 8-bit pictures (device pointers as ints): uint8 [B, c, H, W] in and out, laid out by byte strides
         (None: dense CHW), the output cropped to H x W.  Float64 and 8-bit steps may alternate."""
-        codec, vp = self.codec, C.c_void_p
-        shape = (self.B, codec.c, codec.H, codec.W)
-        keep = []
-        args = []
-        for st, out in ((in_strides, False), (out_strides, True)):
-            if st is None:
-                args.append(None)
-                continue
-            a = np.ascontiguousarray([int(x) for x in st], dtype=np.int64)
-            check_u8_view(shape, a, out)
-            keep.append(a)
-            args.append(vp(a.ctypes.data))
-        _lib.check(self.L.spiht_pipeline_submit_u8(self.handle, vp(d_img), args[0], vp(d_out), vp(d_nbits), vp(d_max_n),
-                                                   vp(d_img_out), args[1]))
+        vp = C.c_void_p
+        st_in, p_in = self.codec._u8_strides(self.B, in_strides, False)
+        st_out, p_out = self.codec._u8_strides(self.B, out_strides, True)
+        _lib.check(self.L.spiht_pipeline_submit_u8(self.handle, vp(d_img), p_in, vp(d_out), vp(d_nbits), vp(d_max_n),
+                                                   vp(d_img_out), p_out))
 
     def flush(self):
         _lib.check(self.L.spiht_pipeline_flush(self.handle))

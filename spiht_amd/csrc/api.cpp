@@ -39,8 +39,6 @@ int spiht_launch_dwt_level_ext(const DwtKArgs *a, int planes, void *t_lo, void *
 int spiht_launch_idwt_level_per(const IdwtKArgs *a, int planes, double *t_lo, double *t_hi, const double *d_filt, int per,
                                 hipStream_t st);
 int spiht_launch_idwt_level(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc);
-int spiht_launch_dwt_level_u8(const DwtKArgs *a, const Px8 *px, int planes, hipStream_t st);
-int spiht_launch_idwt_level_u8(const IdwtKArgs *a, const Px8 *px, int planes, hipStream_t st, TileCtr *tc);
 int spiht_launch_u8_to_f64(const Px8 *px, int64_t B, double *out, hipStream_t st);
 int spiht_launch_f64_to_u8(const double *in, int rec_h, int rec_w, const Px8 *px, int64_t B, hipStream_t st);
 int spiht_launch_quant_plain(const double *in, int32_t *out, size_t n_per_plane, int planes, int c, const double *mults,
@@ -730,6 +728,42 @@ extern "C" int spiht_encode_bound(int64_t c, int64_t h, int64_t w, int64_t ll_h,
     return SPIHT_OK;
 }
 
+// The result of a single encode (ctx->out, ctx->nbits, ctx->maxn) to the host; waits
+static int read_encoded(spiht_ctx *ctx, uint8_t *out, uint64_t out_cap, uint64_t *out_nbits, uint8_t *max_n) {
+    uint64_t nbits = 0;
+    uint8_t mn = 0;
+    HIPCHK(hipMemcpyAsync(&nbits, ctx->nbits.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&mn, ctx->maxn.p, 1, hipMemcpyDeviceToHost, ctx->stream));
+    CHK(read_err(ctx));  // synchronises
+    *out_nbits = nbits;
+    *max_n = mn;
+    const uint64_t nbytes = (nbits + 7) / 8;
+    if (nbytes > out_cap) return SPIHT_ERR_CAPACITY;
+    if (nbytes) {
+        StageTimer t(ctx, ST_D2H);
+        HIPCHK(hipMemcpyAsync(out, ctx->out.p, nbytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SPIHT_OK;
+}
+
+// One host stream for the decoder: its bytes into ctx->data, a slot of *slot bytes whose last word is zeroed first (the
+// bytes past the stream in it), its length and magnitude into ctx->nbytes / ctx->maxn; clears the error word and waits
+static int stage_stream(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, uint64_t *slot) {
+    *slot = std::max<uint64_t>(4, (nbytes + 3) & ~3ull);
+    CHK(ensure(ctx, ctx->data, *slot));
+    CHK(ensure(ctx, ctx->nbytes, 8));
+    CHK(ensure(ctx, ctx->maxn, 4));
+    CHK(clear_err(ctx));
+    StageTimer t(ctx, ST_H2D);
+    HIPCHK(hipMemsetAsync((char *)ctx->data.p + (*slot - 4), 0, 4, ctx->stream));
+    if (nbytes) HIPCHK(hipMemcpyAsync(ctx->data.p, data, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->nbytes.p, &nbytes, 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->maxn.p, &n, 1, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));  // &nbytes / &n are stack temporaries
+    return SPIHT_OK;
+}
+
 extern "C" int spiht_encode_i32(spiht_ctx *ctx, const int32_t *x, int64_t c, int64_t h, int64_t w, int64_t stride_c,
                                 int64_t stride_h, int64_t stride_w, int64_t ll_h, int64_t ll_w, uint64_t max_bits,
                                 uint8_t *out, uint64_t out_cap, uint64_t *out_nbits, uint8_t *max_n) {
@@ -775,21 +809,7 @@ extern "C" int spiht_encode_i32(spiht_ctx *ctx, const int32_t *x, int64_t c, int
     }
     CHK(encode_device(ctx, g, (const int32_t *)ctx->x.p, 1, max_bits, (uint8_t *)ctx->out.p, slot,
                       (uint64_t *)ctx->nbits.p, (uint8_t *)ctx->maxn.p));
-    uint64_t nbits = 0;
-    uint8_t mn = 0;
-    HIPCHK(hipMemcpyAsync(&nbits, ctx->nbits.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&mn, ctx->maxn.p, 1, hipMemcpyDeviceToHost, ctx->stream));
-    CHK(read_err(ctx));
-    *out_nbits = nbits;
-    *max_n = mn;
-    const uint64_t nbytes = (nbits + 7) / 8;
-    if (nbytes > out_cap) return SPIHT_ERR_CAPACITY;
-    if (nbytes) {
-        StageTimer t(ctx, ST_D2H);
-        HIPCHK(hipMemcpyAsync(out, ctx->out.p, nbytes, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return SPIHT_OK;
+    return read_encoded(ctx, out, out_cap, out_nbits, max_n);
 }
 
 extern "C" int spiht_decode_i32(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t h,
@@ -801,20 +821,9 @@ extern "C" int spiht_decode_i32(spiht_ctx *ctx, const uint8_t *data, uint64_t nb
     if (nbytes * 8 >= 0xFFFFFF00ull) return SPIHT_ERR_TOO_LARGE;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    const uint64_t slot = std::max<uint64_t>(4, (nbytes + 3) & ~3ull);
-    CHK(ensure(ctx, ctx->data, slot));
-    CHK(ensure(ctx, ctx->nbytes, 8));
-    CHK(ensure(ctx, ctx->maxn, 4));
     CHK(ensure(ctx, ctx->rec, (size_t)g.n * 4));
-    CHK(clear_err(ctx));
-    {
-        StageTimer t(ctx, ST_H2D);
-        HIPCHK(hipMemsetAsync(ctx->data.p, 0, slot, ctx->stream));
-        if (nbytes) HIPCHK(hipMemcpyAsync(ctx->data.p, data, nbytes, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->nbytes.p, &nbytes, 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->maxn.p, &n, 1, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));  // &nbytes / &n are stack temporaries
-    }
+    uint64_t slot;
+    CHK(stage_stream(ctx, data, nbytes, n, &slot));
     CHK(decode_device(ctx, g, (const uint8_t *)ctx->data.p, slot, (const uint64_t *)ctx->nbytes.p,
                       (const uint8_t *)ctx->maxn.p, 1, (int32_t *)ctx->rec.p));
     CHK(read_err(ctx));
@@ -839,6 +848,45 @@ static int tree_generations(const Geom &g) {
     return best;
 }
 
+// The decoder's trace of one stream and the sort behind it, in ctx->trace: ent[rows] u32 | 4 x u32[rows] sort buffers |
+// act[rows] u8 | in_bytes of the caller's own input | sort temp.  rows: one per bit of the nbytes stream, and one more.
+struct TraceScratch {
+    uint64_t rows;
+    uint32_t *ent, *k0, *v0, *k1, *v1;
+    uint8_t *act;
+    char *in, *tmp;
+    size_t tmp_bytes;
+    // what the metadata and budget kernels read of it (and of the stream at d_data)
+    MetaArgs meta_args(const Geom &g, const void *d_data) const {
+        MetaArgs ma;
+        memset(&ma, 0, sizeof(ma));
+        ma.g = g;
+        ma.rows = rows;
+        ma.tr_ent = ent;
+        ma.tr_act = act;
+        ma.data = (const uint8_t *)d_data;
+        ma.skey = k1;
+        ma.spos = v1;
+        return ma;
+    }
+};
+static int trace_scratch(spiht_ctx *ctx, uint64_t nbytes, size_t in_bytes, TraceScratch *t) {
+    t->rows = nbytes * 8 + 1;
+    if (spiht_meta_sort_temp_bytes(t->rows, &t->tmp_bytes) != 0) return SPIHT_ERR_INTERNAL;
+    const size_t r4 = align256(t->rows * 4), o_act = 5 * r4, o_in = o_act + align256(t->rows), o_tmp = o_in + align256(in_bytes);
+    CHK(ensure(ctx, ctx->trace, o_tmp + align256(t->tmp_bytes)));
+    char *tb = (char *)ctx->trace.p;
+    t->ent = (uint32_t *)tb;
+    t->k0 = (uint32_t *)(tb + r4);
+    t->v0 = (uint32_t *)(tb + 2 * r4);
+    t->k1 = (uint32_t *)(tb + 3 * r4);
+    t->v1 = (uint32_t *)(tb + 4 * r4);
+    t->act = (uint8_t *)(tb + o_act);
+    t->in = tb + o_in;
+    t->tmp = tb + o_tmp;
+    return SPIHT_OK;
+}
+
 extern "C" int spiht_decode_with_metadata_i32(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
                                               int64_t h, int64_t w, int64_t ll_h, int64_t ll_w, const int64_t *top_slice,
                                               const int64_t *other_slices, int64_t level, int32_t *out, int32_t *meta) {
@@ -860,54 +908,30 @@ extern "C" int spiht_decode_with_metadata_i32(spiht_ctx *ctx, const uint8_t *dat
         if (sl[t + 1] < sl[t] || sl[t + 3] < sl[t + 2]) return SPIHT_ERR_SHAPE;  // usize underflow in end - start (:606-608)
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    const uint64_t slot = std::max<uint64_t>(4, (nbytes + 3) & ~3ull);
-    const uint64_t rows = nbytes * 8 + 1;
-    size_t sort_bytes = 0;
-    if (spiht_meta_sort_temp_bytes(rows, &sort_bytes) != 0) return SPIHT_ERR_INTERNAL;
-    // trace scratch: ent[rows] u32 | 4 x u32[rows] sort buffers | act[rows] u8 | slices | sort temp
-    const size_t o_ent = 0, o_k0 = align256(rows * 4), o_v0 = o_k0 + align256(rows * 4), o_k1 = o_v0 + align256(rows * 4),
-                 o_v1 = o_k1 + align256(rows * 4), o_act = o_v1 + align256(rows * 4), o_sl = o_act + align256(rows),
-                 o_tmp = o_sl + align256(sl.size() * 4), total = o_tmp + align256(sort_bytes);
-    CHK(ensure(ctx, ctx->data, slot));
-    CHK(ensure(ctx, ctx->nbytes, 8));
-    CHK(ensure(ctx, ctx->maxn, 4));
+    TraceScratch tr;
+    CHK(trace_scratch(ctx, nbytes, sl.size() * 4, &tr));
     CHK(ensure(ctx, ctx->rec, (size_t)g.n * 4));
-    CHK(ensure(ctx, ctx->trace, total));
-    CHK(ensure(ctx, ctx->meta, rows * 32));
-    char *tb = (char *)ctx->trace.p;
-    CHK(clear_err(ctx));
+    CHK(ensure(ctx, ctx->meta, tr.rows * 32));
+    uint64_t slot;
+    CHK(stage_stream(ctx, data, nbytes, n, &slot));
     {
         StageTimer t(ctx, ST_H2D);
-        HIPCHK(hipMemsetAsync(ctx->data.p, 0, slot, ctx->stream));
-        if (nbytes) HIPCHK(hipMemcpyAsync(ctx->data.p, data, nbytes, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->nbytes.p, &nbytes, 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->maxn.p, &n, 1, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(tb + o_sl, sl.data(), sl.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemsetAsync(tb + o_act, TR_NONE, rows, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));  // stack / vector temporaries
+        HIPCHK(hipMemcpyAsync(tr.in, sl.data(), sl.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemsetAsync(tr.act, TR_NONE, tr.rows, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));  // (a vector temporary)
     }
     CHK(decode_device(ctx, g, (const uint8_t *)ctx->data.p, slot, (const uint64_t *)ctx->nbytes.p,
-                      (const uint8_t *)ctx->maxn.p, 1, (int32_t *)ctx->rec.p, (uint32_t *)(tb + o_ent),
-                      (uint8_t *)(tb + o_act), rows));
-    MetaArgs ma;
-    memset(&ma, 0, sizeof(ma));
-    ma.g = g;
+                      (const uint8_t *)ctx->maxn.p, 1, (int32_t *)ctx->rec.p, tr.ent, tr.act, tr.rows));
+    MetaArgs ma = tr.meta_args(g, ctx->data.p);
     ma.level = (int32_t)level;
-    ma.rows = rows;
-    ma.tr_ent = (const uint32_t *)(tb + o_ent);
-    ma.tr_act = (const uint8_t *)(tb + o_act);
-    ma.data = (const uint8_t *)ctx->data.p;
-    ma.slices = (const int32_t *)(tb + o_sl);
+    ma.slices = (const int32_t *)tr.in;
     ma.meta = (int32_t *)ctx->meta.p;
-    ma.skey = (const uint32_t *)(tb + o_k1);
-    ma.spos = (const uint32_t *)(tb + o_v1);
-    LAUNCHCHK(spiht_launch_metadata(&ma, (uint32_t *)(tb + o_k0), (uint32_t *)(tb + o_v0), (uint32_t *)(tb + o_k1),
-                                    (uint32_t *)(tb + o_v1), tb + o_tmp, sort_bytes, ctx->stream));
+    LAUNCHCHK(spiht_launch_metadata(&ma, tr.k0, tr.v0, tr.k1, tr.v1, tr.tmp, tr.tmp_bytes, ctx->stream));
     CHK(read_err(ctx));
     {
         StageTimer t(ctx, ST_D2H);
         HIPCHK(hipMemcpyAsync(out, ctx->rec.p, (size_t)g.n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(meta, ctx->meta.p, rows * 32, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(meta, ctx->meta.p, tr.rows * 32, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return SPIHT_OK;
@@ -931,46 +955,22 @@ extern "C" int spiht_decode_budgets_dev_i32(spiht_ctx *ctx, const uint8_t *data,
     if (nbytes * 8 >= 0xFFFFFF00ull) return SPIHT_ERR_TOO_LARGE;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    const uint64_t slot = std::max<uint64_t>(4, (nbytes + 3) & ~3ull);
-    const uint64_t rows = nbytes * 8 + 1;
-    size_t sort_bytes = 0;
-    if (spiht_meta_sort_temp_bytes(rows, &sort_bytes) != 0) return SPIHT_ERR_INTERNAL;
-    // trace scratch: ent[rows] u32 | 4 x u32[rows] sort buffers | act[rows] u8 | budgets | sort temp
-    const size_t o_ent = 0, o_k0 = align256(rows * 4), o_v0 = o_k0 + align256(rows * 4), o_k1 = o_v0 + align256(rows * 4),
-                 o_v1 = o_k1 + align256(rows * 4), o_act = o_v1 + align256(rows * 4), o_bud = o_act + align256(rows),
-                 o_tmp = o_bud + align256((size_t)K * 8), total = o_tmp + align256(sort_bytes);
-    CHK(ensure(ctx, ctx->data, slot));
-    CHK(ensure(ctx, ctx->nbytes, 8));
-    CHK(ensure(ctx, ctx->maxn, 4));
+    TraceScratch tr;
+    CHK(trace_scratch(ctx, nbytes, (size_t)K * 8, &tr));
     CHK(ensure(ctx, ctx->rec, (size_t)g.n * 4));
-    CHK(ensure(ctx, ctx->trace, total));
-    char *tb = (char *)ctx->trace.p;
-    CHK(clear_err(ctx));
+    uint64_t slot;
+    CHK(stage_stream(ctx, data, nbytes, n, &slot));
     {
         StageTimer t(ctx, ST_H2D);
-        HIPCHK(hipMemsetAsync(ctx->data.p, 0, slot, ctx->stream));
-        if (nbytes) HIPCHK(hipMemcpyAsync(ctx->data.p, data, nbytes, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->nbytes.p, &nbytes, 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->maxn.p, &n, 1, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(tb + o_bud, budgets_bits, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemsetAsync(tb + o_act, TR_NONE, rows, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));  // stack temporaries / the caller's arrays
+        HIPCHK(hipMemcpyAsync(tr.in, budgets_bits, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemsetAsync(tr.act, TR_NONE, tr.rows, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));  // (the caller's array)
     }
     HIPCHK(hipMemsetAsync(d_out, 0, (size_t)K * g.n * 4, ctx->stream));
     CHK(decode_device(ctx, g, (const uint8_t *)ctx->data.p, slot, (const uint64_t *)ctx->nbytes.p,
-                      (const uint8_t *)ctx->maxn.p, 1, (int32_t *)ctx->rec.p, (uint32_t *)(tb + o_ent),
-                      (uint8_t *)(tb + o_act), rows));
-    MetaArgs ma;
-    memset(&ma, 0, sizeof(ma));
-    ma.g = g;
-    ma.rows = rows;
-    ma.tr_ent = (const uint32_t *)(tb + o_ent);
-    ma.tr_act = (const uint8_t *)(tb + o_act);
-    ma.data = (const uint8_t *)ctx->data.p;
-    ma.skey = (const uint32_t *)(tb + o_k1);
-    ma.spos = (const uint32_t *)(tb + o_v1);
-    LAUNCHCHK(spiht_launch_budget_fold(&ma, (uint32_t *)(tb + o_k0), (uint32_t *)(tb + o_v0), (uint32_t *)(tb + o_k1),
-                                       (uint32_t *)(tb + o_v1), tb + o_tmp, sort_bytes, (const uint64_t *)(tb + o_bud), (int)K,
+                      (const uint8_t *)ctx->maxn.p, 1, (int32_t *)ctx->rec.p, tr.ent, tr.act, tr.rows));
+    const MetaArgs ma = tr.meta_args(g, ctx->data.p);
+    LAUNCHCHK(spiht_launch_budget_fold(&ma, tr.k0, tr.v0, tr.k1, tr.v1, tr.tmp, tr.tmp_bytes, (const uint64_t *)tr.in, (int)K,
                                        d_out, ctx->stream));
     return SPIHT_OK;
 }
@@ -1000,7 +1000,12 @@ extern "C" int spiht_decode_budgets_i32(spiht_ctx *ctx, const uint8_t *data, uin
 // batched, device-resident
 // ------------------------------------------------------------------------------------------------
 
-static int batch_chunk(const Geom &g) { return (int)std::max<int64_t>(1, 65535 / g.c); }
+// fn(b0, nb) over a batch of B images of c planes, in chunks of at most 65535 planes (a launch's grid.y / slot limit)
+template <class Fn> static int batch_chunks(int64_t B, int64_t c, Fn fn) {
+    const int chunk = (int)std::max<int64_t>(1, 65535 / c);
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) CHK(fn(b0, (int)std::min<int64_t>(chunk, B - b0)));
+    return SPIHT_OK;
+}
 
 extern "C" int spiht_encode_batch_i32(spiht_ctx *ctx, const int32_t *d_x, int64_t B, int64_t c, int64_t h, int64_t w,
                                       int64_t ll_h, int64_t ll_w, uint64_t max_bits, uint8_t *d_out,
@@ -1011,13 +1016,10 @@ extern "C" int spiht_encode_batch_i32(spiht_ctx *ctx, const int32_t *d_x, int64_
     if (B == 0) return SPIHT_OK;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    const int chunk = batch_chunk(g);
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        int nb = (int)std::min<int64_t>(chunk, B - b0);
-        CHK(encode_device(ctx, g, d_x + (size_t)b0 * g.n, nb, max_bits, d_out + (size_t)b0 * slot_stride, slot_stride,
-                          d_nbits + b0, d_max_n + b0));
-    }
-    return SPIHT_OK;  // asynchronous: errors surface in spiht_ctx_synchronize()
+    return batch_chunks(B, c, [&](int64_t b0, int nb) -> int {
+        return encode_device(ctx, g, d_x + (size_t)b0 * g.n, nb, max_bits, d_out + (size_t)b0 * slot_stride, slot_stride,
+                             d_nbits + b0, d_max_n + b0);
+    });  // asynchronous: errors surface in spiht_ctx_synchronize()
 }
 
 extern "C" int spiht_decode_batch_i32(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
@@ -1144,28 +1146,111 @@ static int upload_filters(spiht_ctx *ctx, int wavelet, const double **d_filt) {
     return SPIHT_OK;
 }
 
-// px != nullptr: the picture is the 8-bit view *px of planes / c images (d_img unused).  The tiled level 1 reads it itself;
-// the two-pass levels get its float64 form from a conversion pass first.
-static int dwt_forward(spiht_ctx *ctx, const double *d_img, int planes, int c, const ImgGeom &ig, int wavelet, int mode,
-                       double q, const double *d_mults, int32_t *d_coeffs, uint32_t *d_maxabs = nullptr, bool f32 = false,
-                       const Px8 *px = nullptr) {
+// ---- the pictures of an image call: float64, float32 or 8-bit pixels ----------------------------------------------------
+// Float pixels: a dense array at p, [B, c, H, W] (the inverse transform's output: [B, c, rec_H, rec_W]).  8-bit pixels: the
+// view px (common.h: Px8) of a [B, c, H, W] uint8 picture batch by byte strides, based at p.  The extern "C" entry points
+// make one; everything behind them passes it on.
+enum PicFmt { PIC_F64, PIC_F32, PIC_U8 };
+struct Pic {
+    PicFmt fmt = PIC_F64;
+    char *p = nullptr;  // the first picture
+    bool out = false;   // the call writes the pixels (else it reads them)
+    Px8 px = {};        // PIC_U8: strides and size (px.in / px.out unset: see u8())
+    // the view as the U8 kernels and the conversion passes take it
+    Px8 u8() const {
+        Px8 v = px;
+        if (out) v.out = (uint8_t *)p;
+        else v.in = (const uint8_t *)p;
+        return v;
+    }
+    // bytes from the first pixel to one past the last of B pictures (c, ig: the call's); what the host calls transfer
+    uint64_t bytes(int64_t B, int64_t c, const ImgGeom &ig) const {
+        if (fmt == PIC_U8)
+            return 1 + (uint64_t)(B - 1) * px.sb + (uint64_t)(px.c - 1) * px.sc + (uint64_t)(px.h - 1) * px.sh + (uint64_t)(px.w - 1) * px.sw;
+        return (uint64_t)B * c * (out ? ig.rec_H * ig.rec_W : ig.hs[0] * ig.ws[0]) * (fmt == PIC_F32 ? 4 : 8);
+    }
+    // the pictures from b0 on
+    Pic at(int64_t b0, int64_t c, const ImgGeom &ig) const {
+        Pic v = *this;
+        v.p += fmt == PIC_U8 ? b0 * px.sb : (int64_t)bytes(b0, c, ig);
+        return v;
+    }
+    // the same pictures at another address (a copy of their bytes)
+    Pic on(void *base) const {
+        Pic v = *this;
+        v.p = (char *)base;
+        return v;
+    }
+};
+static Pic dense_pic(const void *p, PicFmt fmt, bool out = false) {
+    Pic v;
+    v.fmt = fmt;
+    v.p = (char *)p;
+    v.out = out;
+    return v;
+}
+// strides: n == 4: (sb, sc, sh, sw); n == 3: (sc, sh, sw) of one picture; nullptr: dense CHW.  Strides are non-negative;
+// a view that is written must not overlap itself: sorted by stride, every dimension longer than 1 must step past all the
+// smaller ones reach.
+static int u8_pic(const void *p, bool out, const int64_t *strides, int n, int64_t B, int64_t c, int64_t h, int64_t w, Pic *v) {
+    int64_t st[4] = {c * h * w, h * w, w, 1};
+    if (strides)
+        for (int i = 0; i < n; i++) st[4 - n + i] = strides[i];
+    if (n == 3) st[0] = 0;  // (one picture: no batch stride)
+    const int64_t ext[4] = {B, c, h, w};
+    __int128 span = 1;
+    for (int i = 0; i < 4; i++) {
+        if (st[i] < 0) return SPIHT_ERR_ARG;
+        if (ext[i] > 1) span += (__int128)(ext[i] - 1) * st[i];
+    }
+    if (span >= ((__int128)1 << 62)) return SPIHT_ERR_ARG;
+    if (out) {
+        int idx[4] = {0, 1, 2, 3};
+        std::sort(idx, idx + 4, [&](int x, int y) { return st[x] < st[y]; });
+        int64_t reach = 0;
+        for (int k = 0; k < 4; k++) {
+            const int i = idx[k];
+            if (ext[i] <= 1) continue;
+            if (st[i] < reach + 1) return SPIHT_ERR_ARG;
+            reach += (ext[i] - 1) * st[i];
+        }
+    }
+    *v = dense_pic(p, PIC_U8, out);
+    v->px.sb = st[0]; v->px.sc = st[1]; v->px.sh = st[2]; v->px.sw = st[3];
+    v->px.c = (int32_t)c; v->px.h = (int32_t)h; v->px.w = (int32_t)w;
+    return SPIHT_OK;
+}
+extern "C" int spiht_check_view_u8(int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output) {
+    if (B < 1 || c < 1 || H < 1 || W < 1 || !strides) return SPIHT_ERR_ARG;
+    Pic v;
+    return u8_pic(nullptr, output != 0, strides, 4, B, c, H, W, &v);
+}
+
+// pictures `in` (planes / c of them) -> quantised packed array [planes, enc_h, enc_w].  The rules of the pixel formats:
+// float32 pixels are transformed in single precision, as PyWavelets does for float32 / float16 input (every level's input
+// must then be at least as long as the filter: SPIHT_ERR_ARG otherwise), at a level >= 1 and without the colour model.
+// 8-bit pixels need a level >= 1 (no entry point gets here with level 0: SPIHT refuses that geometry -- the root block's
+// offspring fall outside the array -- before anything is transformed, on the float64 path as well); the tiled level 1
+// reads them itself, the two-pass levels get their float64 form from a conversion pass first.
+static int dwt_forward(spiht_ctx *ctx, const Pic &in, int planes, int c, const ImgGeom &ig, int wavelet, int mode,
+                       double q, const double *d_mults, int32_t *d_coeffs, uint32_t *d_maxabs = nullptr) {
     const WaveletDef &wv = SPIHT_WAVELETS[wavelet];
     const size_t plane_out = (size_t)ig.enc_h * ig.enc_w;
-    if (f32 && (ig.L == 0 || px)) return SPIHT_ERR_ARG;
-    bool color = ctx->color_on && c == 3;
+    const bool f32 = in.fmt == PIC_F32;
+    bool u8 = in.fmt == PIC_U8, color = ctx->color_on && c == 3;
+    if ((f32 || u8) && ig.L == 0) return SPIHT_ERR_ARG;
     if (color && f32) return SPIHT_ERR_ARG;  // the colour model change is float64 (as colour-science's)
     // the plain two-pass level: the modes that compute their extension, periodization, and filters longer than the tiled
     // kernels take (db11.., sym11.., coif4.., dmey)
     const bool twopass = mode >= SPIHT_MODE_SMOOTH || wv.F > SPIHT_MAX_TAPS;
-    // (no 8-bit entry point reaches a transform of level 0: SPIHT refuses that geometry -- the root block's offspring fall
-    // outside the array -- before anything is transformed, on the float64 path as well)
-    if (px && ig.L == 0) return SPIHT_ERR_ARG;
-    if (px && twopass) {  // no 8-bit form of the two-pass level: the float64 picture as a pass of its own
+    const double *d_img = u8 ? nullptr : (const double *)in.p;
+    if (u8 && twopass) {  // no 8-bit form of the two-pass level: the float64 picture as a pass of its own
         StageTimer t(ctx, ST_DWT_L1);
         CHK(ensure(ctx, ctx->pix, (size_t)planes * ig.hs[0] * ig.ws[0] * 8));
-        LAUNCHCHK(spiht_launch_u8_to_f64(px, planes / c, (double *)ctx->pix.p, ctx->stream));
+        const Px8 px = in.u8();
+        LAUNCHCHK(spiht_launch_u8_to_f64(&px, planes / c, (double *)ctx->pix.p, ctx->stream));
         d_img = (const double *)ctx->pix.p;
-        px = nullptr;
+        u8 = false;
     }
     const double *d_filt = nullptr;
     if (twopass && ig.L > 0) CHK(upload_filters(ctx, wavelet, &d_filt));
@@ -1217,8 +1302,7 @@ static int dwt_forward(spiht_ctx *ctx, const double *d_img, int planes, int c, c
         CHK(ensure(ctx, ctx->a0, (size_t)planes * ig.hs[1] * ig.ws[1] * 8));
         if (ig.L >= 3) CHK(ensure(ctx, ctx->a1, (size_t)planes * ig.hs[2] * ig.ws[2] * 8));
     }
-    const double *in = d_img;
-    for (int l = 1; l <= ig.L; l++) {
+    for (int l = 1; l <= ig.L; l++) {  // (d_img: the level's input)
         DwtKArgs a;
         memset(&a, 0, sizeof(a));
         a.c = c;
@@ -1230,13 +1314,14 @@ static int dwt_forward(spiht_ctx *ctx, const double *d_img, int planes, int c, c
         a.enc_h = (int32_t)ig.enc_h; a.enc_w = (int32_t)ig.enc_w;
         a.last = (l == ig.L) ? 1 : 0;
         a.f32 = f32 ? 1 : 0;
-        a.in = in;
+        a.in = d_img;
         a.ll_out = a.last ? nullptr : (double *)((l & 1) ? ctx->a0.p : ctx->a1.p);
         a.coeffs = d_coeffs;
         a.mults = d_mults;
         a.maxabs = d_maxabs;
         a.q = q;
         if (color && l == 1) { a.color = 1; a.col = ctx->col_fwd; }
+        if (u8 && l == 1) a.px = in.u8();  // (the launcher takes the U8 kernels)
         const int Fc = std::min(wv.F, SPIHT_MAX_TAPS);  // (a longer filter goes by the device copy: two-pass level)
         memcpy(a.lo, wv.dec_lo, sizeof(double) * Fc);
         memcpy(a.hi, wv.dec_hi, sizeof(double) * Fc);
@@ -1265,14 +1350,11 @@ static int dwt_forward(spiht_ctx *ctx, const double *d_img, int planes, int c, c
                 LAUNCHCHK(spiht_launch_dwt_level_ext(&b, np, t_lo, t_hi, bb, bb + (size_t)np * n_b * esz, bb + 2 * (size_t)np * n_b * esz,
                                                      bb + 3 * (size_t)np * n_b * esz, d_filt, ctx->stream));
             }
-        } else if (px && l == 1) {
-            StageTimer t(ctx, ST_DWT_L1);
-            LAUNCHCHK(spiht_launch_dwt_level_u8(&a, px, planes, ctx->stream));
         } else {
             StageTimer t(ctx, l == 1 ? ST_DWT_L1 : ST_DWT_REST);
             LAUNCHCHK(spiht_launch_dwt_level(&a, planes, ctx->stream));
         }
-        in = a.ll_out;
+        d_img = a.ll_out;
     }
     return SPIHT_OK;
 }
@@ -1296,15 +1378,17 @@ static bool l1flags_geometry(const ImgGeom &ig, int F, L1Flags *fl) {
 }
 
 // d_flags: L1Flags words [planes, gy, gx] the decoder of d_rec left (nullptr: every level-1 tile reads its detail bands)
-// px != nullptr (l_lo == 1): the pixels go to the 8-bit view *px of planes / c images, cropped to px->h x px->w (d_out
-// unused).  The tiled level 1 writes it itself; the two-pass level goes through a conversion pass behind it.
+// 8-bit output (l_lo == 1, a level >= 1: see dwt_forward): cropped to the picture's size; the tiled level 1 writes it
+// itself, the two-pass level goes through a conversion pass behind it.
 static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, const ImgGeom &ig, int wavelet, double q,
-                       const double *d_mults, double *d_out, int l_hi = -1, int l_lo = 1, const double *d_a_in = nullptr,
-                       const uint32_t *d_flags = nullptr, const Px8 *px = nullptr) {
+                       const double *d_mults, const Pic &out, int l_hi = -1, int l_lo = 1, const double *d_a_in = nullptr,
+                       const uint32_t *d_flags = nullptr) {
     const WaveletDef &wv = SPIHT_WAVELETS[wavelet];
     const int F = wv.F;
     if (l_hi < 0) l_hi = ig.L;
-    if (px && (l_lo != 1 || ig.L == 0)) return SPIHT_ERR_ARG;  // (level 0: see dwt_forward)
+    const bool u8 = out.fmt == PIC_U8;
+    if (u8 && (l_lo != 1 || ig.L == 0)) return SPIHT_ERR_ARG;
+    double *d_out = u8 ? nullptr : (double *)out.p;
     const bool color = ctx->color_on && c == 3;
     if (ig.L == 0) {
         StageTimer t(ctx, ST_IDWT_REST);
@@ -1348,7 +1432,7 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
         if (l == 1 && !a.first && !a.color) a.flags = d_flags;
         memcpy(a.lo, wv.rec_lo, sizeof(double) * std::min(F, SPIHT_MAX_TAPS));
         memcpy(a.hi, wv.rec_hi, sizeof(double) * std::min(F, SPIHT_MAX_TAPS));
-        const bool conv8 = px && l == 1 && (ig.per || F > SPIHT_MAX_TAPS);  // 8-bit output through a pass of its own
+        const bool conv8 = u8 && l == 1 && (ig.per || F > SPIHT_MAX_TAPS);  // 8-bit output through a pass of its own
         if (conv8) {
             CHK(ensure(ctx, ctx->pix, (size_t)planes * a.out_h * a.out_w * 8));
             a.out = (double *)ctx->pix.p;
@@ -1376,11 +1460,12 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
             if (color && l == 1)
                 LAUNCHCHK(spiht_launch_color3(a.out, a.out, planes / 3, (size_t)a.out_h * a.out_w, ctx->col_inv.A, ctx->col_inv.M,
                                               ctx->col_inv.p, ctx->stream));
-            if (conv8) LAUNCHCHK(spiht_launch_f64_to_u8(a.out, a.out_h, a.out_w, px, planes / c, ctx->stream));
-        } else if (px && l == 1) {
-            StageTimer t(ctx, ST_IDWT_L1);
-            LAUNCHCHK(spiht_launch_idwt_level_u8(&a, px, planes, ctx->stream, ctx->tilectr.dev ? &ctx->tilectr : nullptr));
+            if (conv8) {
+                const Px8 px = out.u8();
+                LAUNCHCHK(spiht_launch_f64_to_u8(a.out, a.out_h, a.out_w, &px, planes / c, ctx->stream));
+            }
         } else {
+            if (u8 && l == 1) a.px = out.u8();  // (the launcher takes the U8 kernels)
             StageTimer t(ctx, l == 1 ? ST_IDWT_L1 : ST_IDWT_REST);
             LAUNCHCHK(spiht_launch_idwt_level(&a, planes, ctx->stream, ctx->tilectr.dev ? &ctx->tilectr : nullptr));
         }
@@ -1391,59 +1476,6 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
     return SPIHT_OK;
 }
 
-// ---- 8-bit pixels: the view of a [B, c, H, W] uint8 picture batch by byte strides (common.h: Px8) -------------------
-// strides: n == 4: (sb, sc, sh, sw); n == 3: (sc, sh, sw) of one picture; nullptr: dense CHW.  Strides are non-negative;
-// a view that is written must not overlap itself: sorted by stride, every dimension longer than 1 must step past all the
-// smaller ones reach.
-static int make_px8(const int64_t *strides, int n, int64_t B, int64_t c, int64_t h, int64_t w, bool out, Px8 *px) {
-    int64_t st[4] = {c * h * w, h * w, w, 1};
-    if (strides)
-        for (int i = 0; i < n; i++) st[4 - n + i] = strides[i];
-    if (n == 3) st[0] = 0;  // (one picture: no batch stride)
-    const int64_t ext[4] = {B, c, h, w};
-    __int128 span = 1;
-    for (int i = 0; i < 4; i++) {
-        if (st[i] < 0) return SPIHT_ERR_ARG;
-        if (ext[i] > 1) span += (__int128)(ext[i] - 1) * st[i];
-    }
-    if (span >= ((__int128)1 << 62)) return SPIHT_ERR_ARG;
-    if (out) {
-        int idx[4] = {0, 1, 2, 3};
-        std::sort(idx, idx + 4, [&](int x, int y) { return st[x] < st[y]; });
-        int64_t reach = 0;
-        for (int k = 0; k < 4; k++) {
-            const int i = idx[k];
-            if (ext[i] <= 1) continue;
-            if (st[i] < reach + 1) return SPIHT_ERR_ARG;
-            reach += (ext[i] - 1) * st[i];
-        }
-    }
-    memset(px, 0, sizeof(*px));
-    px->sb = st[0]; px->sc = st[1]; px->sh = st[2]; px->sw = st[3];
-    px->c = (int32_t)c; px->h = (int32_t)h; px->w = (int32_t)w;
-    return SPIHT_OK;
-}
-extern "C" int spiht_check_view_u8(int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output) {
-    if (B < 1 || c < 1 || H < 1 || W < 1 || !strides) return SPIHT_ERR_ARG;
-    Px8 px;
-    return make_px8(strides, 4, B, c, H, W, output != 0, &px);
-}
-// bytes from the view's first element to one past its last
-static uint64_t px8_span(const Px8 &px, int64_t B) {
-    return 1 + (uint64_t)(B - 1) * px.sb + (uint64_t)(px.c - 1) * px.sc + (uint64_t)(px.h - 1) * px.sh + (uint64_t)(px.w - 1) * px.sw;
-}
-// the view of pictures b0.. of a batch view (nullptr stays nullptr)
-struct Px8At {
-    Px8 v;
-    const Px8 *p;
-    Px8At(const Px8 *px, int64_t b0) : p(px ? &v : nullptr) {
-        if (!px) return;
-        v = *px;
-        if (v.in) v.in += b0 * v.sb;
-        if (v.out) v.out += b0 * v.sb;
-    }
-};
-
 static int check_img_args(int wavelet, int mode, int64_t B, int64_t c, int64_t H, int64_t W) {
     if (wavelet < 0 || wavelet >= SPIHT_NWAVELETS || mode < 0 || mode > SPIHT_MODE_PERIODIZATION) return SPIHT_ERR_ARG;
     if (B < 0 || c < 1 || H < 1 || W < 1) return SPIHT_ERR_ARG;
@@ -1451,132 +1483,141 @@ static int check_img_args(int wavelet, int mode, int64_t B, int64_t c, int64_t H
     return SPIHT_OK;
 }
 
-static int dwt_quant_batch(spiht_ctx *ctx, const void *d_img_v, bool f32, int64_t B, int64_t c, int64_t H, int64_t W,
-                           int wavelet, int mode, int level, double q_scale, const double *channel_mults, int32_t *d_coeffs) {
-    const double *d_img = (const double *)d_img_v;
-    const size_t esz = f32 ? 4 : 8;
-    if (!ctx || !d_img || !d_coeffs) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    if (B == 0) return SPIHT_OK;
+// The set-up of an image call on B pictures [c, H, W].  open(): the arguments and the geometry (coded: the coefficient
+// array's Geom for the list coder too); false ends the call with *st -- an error, or SPIHT_OK for an empty batch, whose
+// geometry is not looked at.  enter(): the context's lock, its device and the channel scales (nullptr: none uploaded).
+// chunks(): batch_chunks over the call's batch.
+struct ImgCall {
+    spiht_ctx *ctx = nullptr;
+    int64_t B = 0, c = 0;
+    int F = 0;
     ImgGeom ig;
-    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    const double *d_mults;
-    CHK(upload_mults(ctx, channel_mults, c, &d_mults));
-    const int chunk = (int)std::max<int64_t>(1, 65535 / c);
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        int nb = (int)std::min<int64_t>(chunk, B - b0);
-        CHK(dwt_forward(ctx, (const double *)((const char *)d_img + (size_t)b0 * c * H * W * esz), nb * (int)c, (int)c, ig, wavelet,
-                        mode, q_scale, d_mults, d_coeffs + (size_t)b0 * c * ig.enc_h * ig.enc_w, nullptr, f32));
+    Geom g;
+    const double *d_mults = nullptr;
+    std::unique_lock<std::recursive_mutex> lk;
+
+    bool open(int *st, spiht_ctx *ctx_, int64_t B_, int64_t c_, int64_t H, int64_t W, int wavelet, int mode, int level, bool coded) {
+        ctx = ctx_; B = B_; c = c_;
+        *st = check_img_args(wavelet, mode, B, c, H, W);
+        if (*st != SPIHT_OK || B == 0) return false;
+        F = SPIHT_WAVELETS[wavelet].F;
+        *st = img_geometry(H, W, F, level, &ig, mode);
+        if (*st == SPIHT_OK && coded) *st = make_geom(c, ig.enc_h, ig.enc_w, ig.ll_h, ig.ll_w, &g);
+        return *st == SPIHT_OK;
     }
-    return SPIHT_OK;
+    int enter(const double *channel_mults) {
+        lk = std::unique_lock<std::recursive_mutex>(ctx->mu);
+        HIPCHK(hipSetDevice(ctx->device));
+        return upload_mults(ctx, channel_mults, c, &d_mults);
+    }
+    template <class Fn> int chunks(Fn fn) const { return batch_chunks(B, c, fn); }
+    Pic at(const Pic &v, int64_t b0) const { return v.at(b0, c, ig); }
+};
+
+static int dwt_quant_batch(spiht_ctx *ctx, const Pic &in, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
+                           int level, double q_scale, const double *channel_mults, int32_t *d_coeffs) {
+    if (!ctx || !in.p || !d_coeffs) return SPIHT_ERR_ARG;
+    ImgCall k;
+    int st;
+    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, false)) return st;
+    CHK(k.enter(channel_mults));
+    return k.chunks([&](int64_t b0, int nb) -> int {
+        return dwt_forward(ctx, k.at(in, b0), nb * (int)c, (int)c, k.ig, wavelet, mode, q_scale, k.d_mults,
+                           d_coeffs + (size_t)b0 * c * k.ig.enc_h * k.ig.enc_w);
+    });
 }
 extern "C" int spiht_dwt_quant_batch_f64(spiht_ctx *ctx, const double *d_img, int64_t B, int64_t c, int64_t H, int64_t W,
                                          int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                                          int32_t *d_coeffs) {
-    return dwt_quant_batch(ctx, d_img, false, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs);
+    return dwt_quant_batch(ctx, dense_pic(d_img, PIC_F64), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs);
 }
 extern "C" int spiht_dwt_quant_batch_f32(spiht_ctx *ctx, const float *d_img, int64_t B, int64_t c, int64_t H, int64_t W,
                                          int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                                          int32_t *d_coeffs) {
-    return dwt_quant_batch(ctx, d_img, true, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs);
+    return dwt_quant_batch(ctx, dense_pic(d_img, PIC_F32), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs);
 }
 
 static int dequant_idwt_batch(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B, int64_t c, int64_t H,
                               int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
-                              double *d_img_out, const Px8 *px = nullptr) {
-    if (!ctx || !d_rec || (!d_img_out && !px)) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    if (B == 0) return SPIHT_OK;
-    ImgGeom ig;
-    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    const double *d_mults;
-    CHK(upload_mults(ctx, channel_mults, c, &d_mults));
-    const int chunk = (int)std::max<int64_t>(1, 65535 / c);
+                              const Pic &out) {
+    if (!ctx || !d_rec || !out.p) return SPIHT_ERR_ARG;
+    ImgCall k;
+    int st;
+    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, false)) return st;
+    CHK(k.enter(channel_mults));
     L1Flags fl;
-    const bool flagged = d_flags && !(ctx->color_on && c == 3) && l1flags_geometry(ig, SPIHT_WAVELETS[wavelet].F, &fl);
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        int nb = (int)std::min<int64_t>(chunk, B - b0);
-        CHK(dwt_inverse(ctx, d_rec + (size_t)b0 * c * ig.enc_h * ig.enc_w, nb * (int)c, (int)c, ig, wavelet, q_scale,
-                        d_mults, px ? nullptr : d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, -1, 1, nullptr,
-                        flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr, Px8At(px, b0).p));
-    }
-    return SPIHT_OK;
+    const bool flagged = d_flags && !(ctx->color_on && c == 3) && l1flags_geometry(k.ig, k.F, &fl);
+    return k.chunks([&](int64_t b0, int nb) -> int {
+        return dwt_inverse(ctx, d_rec + (size_t)b0 * c * k.ig.enc_h * k.ig.enc_w, nb * (int)c, (int)c, k.ig, wavelet, q_scale,
+                           k.d_mults, k.at(out, b0), -1, 1, nullptr, flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr);
+    });
 }
 extern "C" int spiht_dequant_idwt_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H,
                                             int64_t W, int wavelet, int mode, int level, double q_scale,
                                             const double *channel_mults, double *d_img_out) {
-    return dequant_idwt_batch(ctx, d_rec, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_img_out);
+    return dequant_idwt_batch(ctx, d_rec, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                              dense_pic(d_img_out, PIC_F64, true));
 }
 extern "C" int spiht_dequant_idwt_flags_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
                                                   int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                                                   double q_scale, const double *channel_mults, double *d_img_out) {
-    return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_img_out);
+    return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                              dense_pic(d_img_out, PIC_F64, true));
 }
 extern "C" int spiht_dequant_idwt_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
                                                  int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                                                  double q_scale, const double *channel_mults, uint8_t *d_img_out,
                                                  const int64_t *out_strides) {
     if (!d_img_out) return SPIHT_ERR_ARG;
-    Px8 px;
-    CHK(make_px8(out_strides, 4, B, c, H, W, true, &px));
-    px.out = d_img_out;
-    return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, nullptr, &px);
+    Pic out;
+    CHK(u8_pic(d_img_out, true, out_strides, 4, B, c, H, W, &out));
+    return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out);
 }
 
 // The inverse transform in two parts, so that a pipelined caller can queue the coarse levels (a quarter of the bytes,
 // six small launches at 1080p) where no list decoder shares the GPU and only level 1 beside it (csrc/pipeline.cpp):
-//   coarse: levels level..2 -> d_approx [B*c, 2*hs[2]-F+2, 2*ws[2]-F+2] (float64), the approximation level 1 starts from
+//   coarse (no `out` pictures): levels level..2 -> d_approx [B*c, 2*hs[2]-F+2, 2*ws[2]-F+2] (float64), the approximation
+//   level 1 starts from
 //   level1: d_rec + d_approx -> pixels.  With fewer than two levels the coarse part does nothing and d_approx is not read.
 static int idwt_part(spiht_ctx *ctx, const int32_t *d_rec, double *d_approx, int64_t B, int64_t c, int64_t H, int64_t W,
-                     int wavelet, int mode, int level, double q_scale, const double *channel_mults, double *d_img_out,
-                     const uint32_t *d_flags = nullptr, const Px8 *px = nullptr) {
-    if (!ctx || !d_rec || (!d_approx && !d_img_out && !px)) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    if (B == 0) return SPIHT_OK;
-    ImgGeom ig;
-    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
+                     int wavelet, int mode, int level, double q_scale, const double *channel_mults, const Pic &out,
+                     const uint32_t *d_flags = nullptr) {
+    if (!ctx || !d_rec || (!d_approx && !out.p)) return SPIHT_ERR_ARG;
+    ImgCall k;
+    int st;
+    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, false)) return st;
+    const ImgGeom &ig = k.ig;
     if (ig.per) return SPIHT_ERR_ARG;  // (the two-part inverse is a schedule experiment of the tiled kernels)
-    const bool coarse = d_img_out == nullptr && px == nullptr;
+    const bool coarse = !out.p;
     if (coarse && ig.L < 2) return SPIHT_OK;
     if (!coarse && ig.L >= 2 && !d_approx) return SPIHT_ERR_ARG;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    const double *d_mults;
-    CHK(upload_mults(ctx, channel_mults, c, &d_mults));
-    const int F = SPIHT_WAVELETS[wavelet].F;
+    CHK(k.enter(channel_mults));
+    const int F = k.F;
     const size_t a_plane = ig.L >= 2 ? (size_t)(2 * ig.hs[2] - F + 2) * (size_t)(2 * ig.ws[2] - F + 2) : 0;
-    const int chunk = (int)std::max<int64_t>(1, 65535 / c);
     L1Flags fl;
     const bool flagged = d_flags && !(ctx->color_on && c == 3) && l1flags_geometry(ig, F, &fl);
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int nb = (int)std::min<int64_t>(chunk, B - b0);
+    return k.chunks([&](int64_t b0, int nb) -> int {
         const int32_t *rec = d_rec + (size_t)b0 * c * ig.enc_h * ig.enc_w;
         double *ap = d_approx ? d_approx + (size_t)b0 * c * a_plane : nullptr;
         if (coarse)
-            CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, d_mults, ap, ig.L, 2, nullptr));
-        else
-            CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, d_mults,
-                            px ? nullptr : d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, std::min(ig.L, 1), 1,
-                            ig.L >= 2 ? ap : nullptr, flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr, Px8At(px, b0).p));
-    }
-    return SPIHT_OK;
+            return dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, k.d_mults, dense_pic(ap, PIC_F64, true), ig.L, 2,
+                               nullptr);
+        return dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, k.d_mults, k.at(out, b0), std::min(ig.L, 1), 1,
+                           ig.L >= 2 ? ap : nullptr, flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr);
+    });
 }
 extern "C" int spiht_idwt_coarse_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H, int64_t W,
                                            int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                                            double *d_approx) {
     if (!d_approx) return SPIHT_ERR_ARG;
-    return idwt_part(ctx, d_rec, d_approx, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, nullptr);
+    return idwt_part(ctx, d_rec, d_approx, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, Pic());
 }
 extern "C" int spiht_idwt_level1_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, int64_t B, int64_t c,
                                            int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                            const double *channel_mults, double *d_img_out) {
     if (!d_img_out) return SPIHT_ERR_ARG;
     return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
-                     d_img_out);
+                     dense_pic(d_img_out, PIC_F64, true));
 }
 
 // ... reading the decoder's occupancy words of the level-1 tiles (spiht_decode_lists_flags_batch_i32; NULL: reads everything)
@@ -1585,18 +1626,17 @@ extern "C" int spiht_idwt_level1_flags_batch_f64(spiht_ctx *ctx, const int32_t *
                                                  double q_scale, const double *channel_mults, double *d_img_out) {
     if (!d_img_out) return SPIHT_ERR_ARG;
     return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
-                     d_img_out, d_flags);
+                     dense_pic(d_img_out, PIC_F64, true), d_flags);
 }
 extern "C" int spiht_idwt_level1_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
                                                 int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                                                 double q_scale, const double *channel_mults, uint8_t *d_img_out,
                                                 const int64_t *out_strides) {
     if (!d_img_out) return SPIHT_ERR_ARG;
-    Px8 px;
-    CHK(make_px8(out_strides, 4, B, c, H, W, true, &px));
-    px.out = d_img_out;
-    return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
-                     nullptr, d_flags, &px);
+    Pic out;
+    CHK(u8_pic(d_img_out, true, out_strides, 4, B, c, H, W, &out));
+    return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out,
+                     d_flags);
 }
 
 extern "C" int spiht_idwt_approx_shape(int64_t H, int64_t W, int wavelet, int level, int64_t *a_h, int64_t *a_w) {
@@ -1609,26 +1649,16 @@ extern "C" int spiht_idwt_approx_shape(int64_t H, int64_t W, int wavelet, int le
     return SPIHT_OK;
 }
 
-static int encode_image_batch(spiht_ctx *ctx, const void *d_img_v, bool f32, int64_t B, int64_t c, int64_t H, int64_t W,
-                              int wavelet, int mode, int level, double q_scale, const double *channel_mults,
-                              uint64_t max_bits, uint8_t *d_out, uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n,
-                              int32_t *d_coeffs, const Px8 *px = nullptr) {
-    const double *d_img = (const double *)d_img_v;
-    const size_t esz = f32 ? 4 : 8;
-    if (!ctx || (!d_img && !px) || !d_out || !d_nbits || !d_max_n) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    if (B == 0) return SPIHT_OK;
-    ImgGeom ig;
-    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
-    Geom g;
-    CHK(make_geom(c, ig.enc_h, ig.enc_w, ig.ll_h, ig.ll_w, &g));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    const double *d_mults;
-    CHK(upload_mults(ctx, channel_mults, c, &d_mults));
-    const int chunk = batch_chunk(g);
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        int nb = (int)std::min<int64_t>(chunk, B - b0);
+static int encode_image_batch(spiht_ctx *ctx, const Pic &in, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
+                              int level, double q_scale, const double *channel_mults, uint64_t max_bits, uint8_t *d_out,
+                              uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs) {
+    if (!ctx || !in.p || !d_out || !d_nbits || !d_max_n) return SPIHT_ERR_ARG;
+    ImgCall k;
+    int st;
+    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, true)) return st;
+    CHK(k.enter(channel_mults));
+    const Geom &g = k.g;
+    return k.chunks([&](int64_t b0, int nb) -> int {
         int32_t *co = d_coeffs ? d_coeffs + (size_t)b0 * g.n : nullptr;
         if (!co) {
             CHK(ensure(ctx, ctx->coeffs, (size_t)nb * g.n * 4));
@@ -1636,28 +1666,27 @@ static int encode_image_batch(spiht_ctx *ctx, const void *d_img_v, bool f32, int
         }
         CHK(ensure(ctx, ctx->maxabs, (size_t)nb * 4));
         HIPCHK(hipMemsetAsync(ctx->maxabs.p, 0, (size_t)nb * 4, ctx->stream));
-        CHK(dwt_forward(ctx, px ? nullptr : (const double *)((const char *)d_img + (size_t)b0 * c * H * W * esz), nb * (int)c, (int)c,
-                        ig, wavelet, mode, q_scale, d_mults, co, (uint32_t *)ctx->maxabs.p, f32, Px8At(px, b0).p));
-        CHK(encode_device(ctx, g, co, nb, max_bits, d_out + (size_t)b0 * slot_stride, slot_stride, d_nbits + b0,
-                          d_max_n + b0, true));
-    }
-    return SPIHT_OK;  // asynchronous: errors surface in spiht_ctx_synchronize()
+        CHK(dwt_forward(ctx, k.at(in, b0), nb * (int)c, (int)c, k.ig, wavelet, mode, q_scale, k.d_mults, co,
+                        (uint32_t *)ctx->maxabs.p));
+        return encode_device(ctx, g, co, nb, max_bits, d_out + (size_t)b0 * slot_stride, slot_stride, d_nbits + b0, d_max_n + b0,
+                             true);
+    });  // asynchronous: errors surface in spiht_ctx_synchronize()
 }
 extern "C" int spiht_encode_image_batch_f64(spiht_ctx *ctx, const double *d_img, int64_t B, int64_t c, int64_t H,
                                             int64_t W, int wavelet, int mode, int level, double q_scale,
                                             const double *channel_mults, uint64_t max_bits, uint8_t *d_out,
                                             uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n,
                                             int32_t *d_coeffs) {
-    return encode_image_batch(ctx, d_img, false, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, d_out,
-                              slot_stride, d_nbits, d_max_n, d_coeffs);
+    return encode_image_batch(ctx, dense_pic(d_img, PIC_F64), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
+                              d_out, slot_stride, d_nbits, d_max_n, d_coeffs);
 }
 extern "C" int spiht_encode_image_batch_f32(spiht_ctx *ctx, const float *d_img, int64_t B, int64_t c, int64_t H,
                                             int64_t W, int wavelet, int mode, int level, double q_scale,
                                             const double *channel_mults, uint64_t max_bits, uint8_t *d_out,
                                             uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n,
                                             int32_t *d_coeffs) {
-    return encode_image_batch(ctx, d_img, true, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, d_out,
-                              slot_stride, d_nbits, d_max_n, d_coeffs);
+    return encode_image_batch(ctx, dense_pic(d_img, PIC_F32), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
+                              d_out, slot_stride, d_nbits, d_max_n, d_coeffs);
 }
 extern "C" int spiht_encode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t B, int64_t c,
                                            int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
@@ -1665,34 +1694,26 @@ extern "C" int spiht_encode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_img,
                                            uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs) {
     if (!d_img) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
-    Px8 px;
-    CHK(make_px8(strides, 4, B, c, H, W, false, &px));
-    px.in = d_img;
-    return encode_image_batch(ctx, nullptr, false, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, d_out,
-                              slot_stride, d_nbits, d_max_n, d_coeffs, &px);
+    Pic in;
+    CHK(u8_pic(d_img, false, strides, 4, B, c, H, W, &in));
+    return encode_image_batch(ctx, in, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, d_out, slot_stride,
+                              d_nbits, d_max_n, d_coeffs);
 }
 
 static int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
                               const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
-                              double q_scale, const double *channel_mults, double *d_img_out, int32_t *d_rec, const Px8 *px) {
-    if (!ctx || !d_data || !d_nbytes || !d_max_n || (!d_img_out && !px)) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    if (B == 0) return SPIHT_OK;
-    ImgGeom ig;
-    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
-    Geom g;
-    CHK(make_geom(c, ig.enc_h, ig.enc_w, ig.ll_h, ig.ll_w, &g));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    const double *d_mults;
-    CHK(upload_mults(ctx, channel_mults, c, &d_mults));
-    const int chunk = batch_chunk(g);
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        int nb = (int)std::min<int64_t>(chunk, B - b0);
+                              double q_scale, const double *channel_mults, const Pic &out, int32_t *d_rec) {
+    if (!ctx || !d_data || !d_nbytes || !d_max_n || !out.p) return SPIHT_ERR_ARG;
+    ImgCall k;
+    int st;
+    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, true)) return st;
+    CHK(k.enter(channel_mults));
+    const Geom &g = k.g;
+    return k.chunks([&](int64_t b0, int nb) -> int {
         int32_t *rec = d_rec ? d_rec + (size_t)b0 * g.n : nullptr;
         // the decoder tells the inverse transform which level-1 tiles hold anything (common.h: L1Flags)
         L1Flags fl;
-        const bool flagged = ctx->opt_l1_flags && !(ctx->color_on && c == 3) && l1flags_geometry(ig, SPIHT_WAVELETS[wavelet].F, &fl);
+        const bool flagged = ctx->opt_l1_flags && !(ctx->color_on && c == 3) && l1flags_geometry(k.ig, k.F, &fl);
         if (flagged) {
             CHK(ensure(ctx, ctx->l1flags, (size_t)nb * c * fl.gy * fl.gx * 4));
             fl.p = (uint32_t *)ctx->l1flags.p;
@@ -1700,10 +1721,8 @@ static int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t sl
         if (rec) {
             CHK(decode_device(ctx, g, d_data + (size_t)b0 * slot_stride, slot_stride, d_nbytes + b0, d_max_n + b0, nb, rec,
                               nullptr, nullptr, 0, true, nullptr, flagged ? &fl : nullptr));
-            CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, d_mults,
-                            px ? nullptr : d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, -1, 1, nullptr, flagged ? fl.p : nullptr,
-                            Px8At(px, b0).p));
-            continue;
+            return dwt_inverse(ctx, rec, nb * (int)c, (int)c, k.ig, wavelet, q_scale, k.d_mults, k.at(out, b0), -1, 1, nullptr,
+                               flagged ? fl.p : nullptr);
         }
         // Internal coefficient array: it is all zero on entry and is left all zero -- after the inverse transform the
         // cells the decoder wrote are cleared again through its own LSP lists (about 1 % of the array) instead of
@@ -1719,24 +1738,23 @@ static int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t sl
         DecArgs da;
         CHK(decode_device(ctx, g, d_data + (size_t)b0 * slot_stride, slot_stride, d_nbytes + b0, d_max_n + b0, nb, rec, nullptr,
                           nullptr, 0, false, &da, flagged ? &fl : nullptr));
-        CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, d_mults,
-                        px ? nullptr : d_img_out + (size_t)b0 * c * ig.rec_H * ig.rec_W, -1, 1, nullptr, flagged ? fl.p : nullptr,
-                        Px8At(px, b0).p));
+        CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, k.ig, wavelet, q_scale, k.d_mults, k.at(out, b0), -1, 1, nullptr,
+                        flagged ? fl.p : nullptr));
         if (da.nslots >= nb) {
             StageTimer t(ctx, ST_MEMSET);
             LAUNCHCHK(spiht_launch_unscatter(&da, ctx->stream));
         } else {
             ctx->recz_clean = false;  // slots were reused inside the launch: the lists of earlier images are gone
         }
-    }
-    return SPIHT_OK;  // asynchronous: errors surface in spiht_ctx_synchronize()
+        return SPIHT_OK;
+    });  // asynchronous: errors surface in spiht_ctx_synchronize()
 }
 extern "C" int spiht_decode_image_batch_f64(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
                                             const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
                                             int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                             const double *channel_mults, double *d_img_out, int32_t *d_rec) {
     return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
-                              d_img_out, d_rec, nullptr);
+                              dense_pic(d_img_out, PIC_F64, true), d_rec);
 }
 extern "C" int spiht_decode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
                                            const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
@@ -1745,11 +1763,10 @@ extern "C" int spiht_decode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_data
                                            int32_t *d_rec) {
     if (!d_img_out) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
-    Px8 px;
-    CHK(make_px8(out_strides, 4, B, c, H, W, true, &px));
-    px.out = d_img_out;
+    Pic out;
+    CHK(u8_pic(d_img_out, true, out_strides, 4, B, c, H, W, &out));
     return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
-                              nullptr, d_rec, &px);
+                              out, d_rec);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1757,24 +1774,21 @@ extern "C" int spiht_decode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_data
 // (spiht_wrapper.py:142-216, 259-281) as one C call each.  Pixels, stream and coefficient array live in the
 // context's grow-only device buffers -- no allocation per call after the first of a given size.
 // ------------------------------------------------------------------------------------------------
-// px8: the picture is the host 8-bit view *px8 (img unused): only the bytes its strides span are uploaded
-static int encode_image_host(spiht_ctx *ctx, const void *img, bool f32, int64_t c, int64_t H, int64_t W, int wavelet,
-                             int mode, int level, double q_scale, const double *channel_mults, uint64_t max_bits,
-                             uint8_t *out, uint64_t out_cap, uint64_t *out_nbits, uint8_t *max_n, const Px8 *px8 = nullptr) {
-    if (!ctx || (!img && !px8) || !out_nbits || !max_n || (!out && out_cap)) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, 1, c, H, W));
-    ImgGeom ig;
-    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
-    Geom g;
-    CHK(make_geom(c, ig.enc_h, ig.enc_w, ig.ll_h, ig.ll_w, &g));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    uint64_t bits = bound_bits(g, 0x3FFFFFFFu);
+// (an 8-bit picture: only the bytes its strides span are uploaded)
+static int encode_image_host(spiht_ctx *ctx, const Pic &img, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                             double q_scale, const double *channel_mults, uint64_t max_bits, uint8_t *out, uint64_t out_cap,
+                             uint64_t *out_nbits, uint8_t *max_n) {
+    if (!ctx || !img.p || !out_nbits || !max_n || (!out && out_cap)) return SPIHT_ERR_ARG;
+    ImgCall k;
+    int st;
+    if (!k.open(&st, ctx, 1, c, H, W, wavelet, mode, level, true)) return st;
+    CHK(k.enter(nullptr));  // (the channel scales: the batch call's)
+    uint64_t bits = bound_bits(k.g, 0x3FFFFFFFu);
     if (max_bits != 0) bits = std::min(bits, max_bits);
     if (bits >= 0xFFFFFF00ull * 8ull) return SPIHT_ERR_TOO_LARGE;
     const uint64_t slot = std::max<uint64_t>(4, ((bits + 7) / 8 + 3) & ~3ull);
-    const size_t img_bytes = px8 ? (size_t)px8_span(*px8, 1) : (size_t)c * H * W * (f32 ? 4 : 8);
-    DevBuf &hb = px8 ? ctx->hpix8 : ctx->himg;
+    const size_t img_bytes = (size_t)img.bytes(1, c, k.ig);
+    DevBuf &hb = img.fmt == PIC_U8 ? ctx->hpix8 : ctx->himg;
     CHK(ensure(ctx, hb, img_bytes));
     CHK(ensure(ctx, ctx->out, slot));
     CHK(ensure(ctx, ctx->nbits, 8));
@@ -1782,41 +1796,25 @@ static int encode_image_host(spiht_ctx *ctx, const void *img, bool f32, int64_t 
     CHK(clear_err(ctx));
     {
         StageTimer t(ctx, ST_H2D);
-        HIPCHK(hipMemcpyAsync(hb.p, px8 ? (const void *)px8->in : img, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(hb.p, img.p, img_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    Px8 dpx;
-    if (px8) { dpx = *px8; dpx.in = (const uint8_t *)hb.p; }
-    CHK(encode_image_batch(ctx, px8 ? nullptr : hb.p, f32, 1, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
-                           (uint8_t *)ctx->out.p, slot, (uint64_t *)ctx->nbits.p, (uint8_t *)ctx->maxn.p, nullptr, px8 ? &dpx : nullptr));
-    uint64_t nbits = 0;
-    uint8_t mn = 0;
-    HIPCHK(hipMemcpyAsync(&nbits, ctx->nbits.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&mn, ctx->maxn.p, 1, hipMemcpyDeviceToHost, ctx->stream));
-    CHK(read_err(ctx));  // synchronises
-    *out_nbits = nbits;
-    *max_n = mn;
-    const uint64_t nbytes = (nbits + 7) / 8;
-    if (nbytes > out_cap) return SPIHT_ERR_CAPACITY;
-    if (nbytes) {
-        StageTimer t(ctx, ST_D2H);
-        HIPCHK(hipMemcpyAsync(out, ctx->out.p, nbytes, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return SPIHT_OK;
+    CHK(encode_image_batch(ctx, img.on(hb.p), 1, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
+                           (uint8_t *)ctx->out.p, slot, (uint64_t *)ctx->nbits.p, (uint8_t *)ctx->maxn.p, nullptr));
+    return read_encoded(ctx, out, out_cap, out_nbits, max_n);
 }
 extern "C" int spiht_encode_image_host_f64(spiht_ctx *ctx, const double *img, int64_t c, int64_t H, int64_t W, int wavelet,
                                            int mode, int level, double q_scale, const double *channel_mults,
                                            uint64_t max_bits, uint8_t *out, uint64_t out_cap, uint64_t *out_nbits,
                                            uint8_t *max_n) {
-    return encode_image_host(ctx, img, false, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out, out_cap,
-                             out_nbits, max_n);
+    return encode_image_host(ctx, dense_pic(img, PIC_F64), c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out,
+                             out_cap, out_nbits, max_n);
 }
 extern "C" int spiht_encode_image_host_f32(spiht_ctx *ctx, const float *img, int64_t c, int64_t H, int64_t W, int wavelet,
                                            int mode, int level, double q_scale, const double *channel_mults,
                                            uint64_t max_bits, uint8_t *out, uint64_t out_cap, uint64_t *out_nbits,
                                            uint8_t *max_n) {
-    return encode_image_host(ctx, img, true, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out, out_cap,
-                             out_nbits, max_n);
+    return encode_image_host(ctx, dense_pic(img, PIC_F32), c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out,
+                             out_cap, out_nbits, max_n);
 }
 extern "C" int spiht_encode_image_host_u8(spiht_ctx *ctx, const uint8_t *img, const int64_t *strides, int64_t c, int64_t H,
                                           int64_t W, int wavelet, int mode, int level, double q_scale,
@@ -1824,50 +1822,33 @@ extern "C" int spiht_encode_image_host_u8(spiht_ctx *ctx, const uint8_t *img, co
                                           uint64_t *out_nbits, uint8_t *max_n) {
     if (!img) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, 1, c, H, W));
-    Px8 px;
-    CHK(make_px8(strides, 3, 1, c, H, W, false, &px));
-    px.in = img;
-    return encode_image_host(ctx, nullptr, false, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out, out_cap,
-                             out_nbits, max_n, &px);
+    Pic in;
+    CHK(u8_pic(img, false, strides, 3, 1, c, H, W, &in));
+    return encode_image_host(ctx, in, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out, out_cap, out_nbits,
+                             max_n);
 }
 
-// px8: the pixels go to the host 8-bit view *px8 (img_out unused), which is dense: c*H*W bytes
+// (an 8-bit picture: a dense one, CHW or HWC, so that it is c*H*W bytes)
 static int decode_image_host(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H, int64_t W,
-                             int wavelet, int mode, int level, double q_scale, const double *channel_mults, double *img_out,
-                             const Px8 *px8 = nullptr) {
-    if (!ctx || (!img_out && !px8) || (!data && nbytes)) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, 1, c, H, W));
-    ImgGeom ig;
-    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
+                             int wavelet, int mode, int level, double q_scale, const double *channel_mults, const Pic &img_out) {
+    if (!ctx || !img_out.p || (!data && nbytes)) return SPIHT_ERR_ARG;
+    ImgCall k;
+    int st;
+    if (!k.open(&st, ctx, 1, c, H, W, wavelet, mode, level, false)) return st;
     if (n > 30) return SPIHT_ERR_MAGNITUDE;
     if (nbytes * 8 >= 0xFFFFFF00ull) return SPIHT_ERR_TOO_LARGE;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    const uint64_t slot = std::max<uint64_t>(4, (nbytes + 3) & ~3ull);
-    const size_t out_bytes = px8 ? (size_t)c * H * W : (size_t)c * ig.rec_H * ig.rec_W * 8;
-    DevBuf &hb = px8 ? ctx->hpix8 : ctx->himg;
-    CHK(ensure(ctx, ctx->data, slot));
-    CHK(ensure(ctx, ctx->nbytes, 8));
-    CHK(ensure(ctx, ctx->maxn, 4));
+    CHK(k.enter(nullptr));  // (the channel scales: the batch call's)
+    const size_t out_bytes = (size_t)img_out.bytes(1, c, k.ig);
+    DevBuf &hb = img_out.fmt == PIC_U8 ? ctx->hpix8 : ctx->himg;
     CHK(ensure(ctx, hb, out_bytes));
-    CHK(clear_err(ctx));
-    {
-        StageTimer t(ctx, ST_H2D);
-        HIPCHK(hipMemsetAsync((char *)ctx->data.p + (slot - 4), 0, 4, ctx->stream));  // the bytes past the stream in its last word
-        if (nbytes) HIPCHK(hipMemcpyAsync(ctx->data.p, data, nbytes, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->nbytes.p, &nbytes, 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->maxn.p, &n, 1, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));  // &nbytes / &n are stack temporaries
-    }
-    Px8 dpx;
-    if (px8) { dpx = *px8; dpx.out = (uint8_t *)hb.p; }
+    uint64_t slot;
+    CHK(stage_stream(ctx, data, nbytes, n, &slot));
     CHK(decode_image_batch(ctx, (const uint8_t *)ctx->data.p, slot, (const uint64_t *)ctx->nbytes.p, (const uint8_t *)ctx->maxn.p, 1,
-                           c, H, W, wavelet, mode, level, q_scale, channel_mults, px8 ? nullptr : (double *)hb.p, nullptr,
-                           px8 ? &dpx : nullptr));
+                           c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out.on(hb.p), nullptr));
     CHK(read_err(ctx));
     {
         StageTimer t(ctx, ST_D2H);
-        HIPCHK(hipMemcpyAsync(px8 ? (void *)px8->out : (void *)img_out, hb.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(img_out.p, hb.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return SPIHT_OK;
@@ -1875,20 +1856,21 @@ static int decode_image_host(spiht_ctx *ctx, const uint8_t *data, uint64_t nbyte
 extern "C" int spiht_decode_image_host_f64(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
                                            int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                            const double *channel_mults, double *img_out) {
-    return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out);
+    return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                             dense_pic(img_out, PIC_F64, true));
 }
 extern "C" int spiht_decode_image_host_u8(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                           const double *channel_mults, uint8_t *img_out, const int64_t *strides) {
     if (!img_out) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, 1, c, H, W));
-    Px8 px;
-    CHK(make_px8(strides, 3, 1, c, H, W, true, &px));
+    Pic out;
+    CHK(u8_pic(img_out, true, strides, 3, 1, c, H, W, &out));
     // the copy back is of c*H*W bytes: only the two dense layouts, CHW and HWC
+    const Px8 &px = out.px;
     const bool chw = px.sw == 1 && px.sh == W && px.sc == H * W, hwc = px.sc == 1 && px.sw == c && px.sh == W * c;
     if (!chw && !hwc) return SPIHT_ERR_ARG;
-    px.out = img_out;
-    return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, nullptr, &px);
+    return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, out);
 }
 
 extern "C" int spiht_dequant_idwt_host_f64(spiht_ctx *ctx, const int32_t *rec, int64_t c, int64_t H, int64_t W, int wavelet,
@@ -1922,39 +1904,31 @@ extern "C" int spiht_dequant_idwt_host_f64(spiht_ctx *ctx, const int32_t *rec, i
 // context while another context list-codes a different batch (bench.py)
 // ------------------------------------------------------------------------------------------------
 
-static int dwt_pyramid_batch(spiht_ctx *ctx, const double *d_img, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
+static int dwt_pyramid_batch(spiht_ctx *ctx, const Pic &in, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
                              int level, double q_scale, const double *channel_mults, int32_t *d_coeffs, uint8_t *d_dmsb,
-                             uint8_t *d_lmsb, uint32_t *d_maxabs, const Px8 *px) {
-    if (!ctx || (!d_img && !px) || !d_coeffs || !d_maxabs || (!d_dmsb) != (!d_lmsb)) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    if (B == 0) return SPIHT_OK;
-    ImgGeom ig;
-    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
-    Geom g;
-    CHK(make_geom(c, ig.enc_h, ig.enc_w, ig.ll_h, ig.ll_w, &g));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    const double *d_mults;
-    CHK(upload_mults(ctx, channel_mults, c, &d_mults));
-    const int chunk = batch_chunk(g);
+                             uint8_t *d_lmsb, uint32_t *d_maxabs) {
+    if (!ctx || !in.p || !d_coeffs || !d_maxabs || (!d_dmsb) != (!d_lmsb)) return SPIHT_ERR_ARG;
+    ImgCall k;
+    int st;
+    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, true)) return st;
+    CHK(k.enter(channel_mults));
+    const Geom &g = k.g;
     HIPCHK(hipMemsetAsync(d_maxabs, 0, (size_t)B * 4, ctx->stream));
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        int nb = (int)std::min<int64_t>(chunk, B - b0);
+    return k.chunks([&](int64_t b0, int nb) -> int {
         int32_t *co = d_coeffs + (size_t)b0 * g.n;
-        CHK(dwt_forward(ctx, px ? nullptr : d_img + (size_t)b0 * c * H * W, nb * (int)c, (int)c, ig, wavelet, mode, q_scale, d_mults,
-                        co, d_maxabs + b0, false, Px8At(px, b0).p));
-        if (!d_dmsb) continue;  // transform + max|coefficient| only: the pyramid is queued elsewhere (spiht_pyramid_batch_i32)
+        CHK(dwt_forward(ctx, k.at(in, b0), nb * (int)c, (int)c, k.ig, wavelet, mode, q_scale, k.d_mults, co, d_maxabs + b0));
+        if (!d_dmsb) return SPIHT_OK;  // transform + max|coefficient| only: the pyramid is queued elsewhere (spiht_pyramid_batch_i32)
         StageTimer t(ctx, ST_PYRAMID);
         LAUNCHCHK(spiht_launch_pyramid(&g, nb, co, d_dmsb + (size_t)b0 * g.n, d_lmsb + (size_t)b0 * g.n, ctx->stream));
-    }
-    return SPIHT_OK;
+        return SPIHT_OK;
+    });
 }
 extern "C" int spiht_dwt_pyramid_batch_f64(spiht_ctx *ctx, const double *d_img, int64_t B, int64_t c, int64_t H, int64_t W,
                                            int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                                            int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb, uint32_t *d_maxabs) {
     if (!d_img) return SPIHT_ERR_ARG;
-    return dwt_pyramid_batch(ctx, d_img, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs, d_dmsb, d_lmsb, d_maxabs,
-                             nullptr);
+    return dwt_pyramid_batch(ctx, dense_pic(d_img, PIC_F64), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs,
+                             d_dmsb, d_lmsb, d_maxabs);
 }
 extern "C" int spiht_dwt_pyramid_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t B, int64_t c,
                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
@@ -1962,11 +1936,9 @@ extern "C" int spiht_dwt_pyramid_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, 
                                           uint32_t *d_maxabs) {
     if (!d_img) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
-    Px8 px;
-    CHK(make_px8(strides, 4, B, c, H, W, false, &px));
-    px.in = d_img;
-    return dwt_pyramid_batch(ctx, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs, d_dmsb, d_lmsb, d_maxabs,
-                             &px);
+    Pic in;
+    CHK(u8_pic(d_img, false, strides, 4, B, c, H, W, &in));
+    return dwt_pyramid_batch(ctx, in, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs, d_dmsb, d_lmsb, d_maxabs);
 }
 
 extern "C" int spiht_encode_lists_batch_i32(spiht_ctx *ctx, const int32_t *d_x, const uint8_t *d_dmsb,
@@ -1983,9 +1955,7 @@ extern "C" int spiht_encode_lists_batch_i32(spiht_ctx *ctx, const int32_t *d_x, 
     const uint64_t max_bits = max_bits_in == 0 ? SPIHT_MAX_BITS_UNLIMITED : max_bits_in;
     ListCaps caps;
     list_caps(g, std::min<uint64_t>(max_bits, slot_stride * 8), &caps, nullptr);
-    const int chunk = batch_chunk(g);
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        int nb = (int)std::min<int64_t>(chunk, B - b0);
+    return batch_chunks(B, c, [&](int64_t b0, int nb) -> int {
         int nslots = 0;
         ListPtrs lp;
         CHK(alloc_lists(ctx, caps, std::min(nb, ctx->num_cu), false, &nslots, &lp));
@@ -1993,11 +1963,10 @@ extern "C" int spiht_encode_lists_batch_i32(spiht_ctx *ctx, const int32_t *d_x, 
             StageTimer t(ctx, ST_MEMSET);
             HIPCHK(hipMemsetAsync(d_out + (size_t)b0 * slot_stride, 0, (size_t)nb * slot_stride, ctx->stream));
         }
-        CHK(encode_lists_device(ctx, g, d_x + (size_t)b0 * g.n, d_dmsb + (size_t)b0 * g.n, d_lmsb + (size_t)b0 * g.n,
-                                d_maxabs + b0, nb, max_bits, caps, nslots, lp, d_out + (size_t)b0 * slot_stride, slot_stride,
-                                d_nbits + b0, d_max_n + b0));
-    }
-    return SPIHT_OK;
+        return encode_lists_device(ctx, g, d_x + (size_t)b0 * g.n, d_dmsb + (size_t)b0 * g.n, d_lmsb + (size_t)b0 * g.n,
+                                   d_maxabs + b0, nb, max_bits, caps, nslots, lp, d_out + (size_t)b0 * slot_stride, slot_stride,
+                                   d_nbits + b0, d_max_n + b0);
+    });
 }
 
 static int decode_lists_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
@@ -2027,15 +1996,14 @@ extern "C" int spiht_decode_lists_flags_batch_i32(spiht_ctx *ctx, const uint8_t 
                                                   int64_t H, int64_t W, int wavelet, int mode, int level, int32_t *d_out_zeroed,
                                                   uint32_t *d_flags) {
     if (!ctx || !d_data || !d_nbytes || !d_max_n || !d_out_zeroed || B < 0) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    ImgGeom ig;
-    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, &ig, mode));
-    Geom g;
-    CHK(make_geom(c, ig.enc_h, ig.enc_w, ig.ll_h, ig.ll_w, &g));
+    ImgCall k;
+    int st;
+    // (one picture: an empty batch has its geometry checked too; decode_lists_batch takes the context)
+    if (!k.open(&st, ctx, 1, c, H, W, wavelet, mode, level, true)) return st;
     L1Flags fl;
-    const bool flagged = d_flags && l1flags_geometry(ig, SPIHT_WAVELETS[wavelet].F, &fl);
+    const bool flagged = d_flags && l1flags_geometry(k.ig, k.F, &fl);
     if (flagged) fl.p = d_flags;
-    return decode_lists_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, g, d_out_zeroed, flagged ? &fl : nullptr);
+    return decode_lists_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, k.g, d_out_zeroed, flagged ? &fl : nullptr);
 }
 
 // Puts the zeros back into the array the context's last spiht_decode_lists_batch_i32 scattered into (after its

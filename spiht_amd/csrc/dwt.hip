@@ -1569,11 +1569,11 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
 
 // ---- host launchers -----------------------------------------------------------------------------
 
-// px != nullptr: level 1 of an 8-bit picture (the U8 kernels; a.in unused)
+// a.px.in set: level 1 of an 8-bit picture (the U8 kernels; a.in unused)
 template <int F, uint32_t LOM, uint32_t HIM>
-static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st, const Px8 *px) {
+static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
     a.planes = planes;
-    if (px) a.px = *px;
+    const bool u8 = a.px.in != nullptr;
     a.ov_h = a.out_h;
     a.ov_w = a.out_w;
     if (a.f32) {
@@ -1588,7 +1588,7 @@ static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st, const Px8 *px) 
         if (a.mode != 4) a.ov_h = min(a.out_h, (a.in_h + z + 2) / 2);
         if (a.mode != 4) a.ov_w = min(a.out_w, (a.in_w + z + 2) / 2);
         const uint32_t gx = (uint32_t)((a.out_w + SW - 1) / SW), gy = (uint32_t)((a.out_h + C1_ROWS - 1) / C1_ROWS);
-        if (px) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, true>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
+        if (u8) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, true>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
         else hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
         return (int)hipGetLastError();
     }
@@ -1602,34 +1602,34 @@ static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st, const Px8 *px) 
     if (a.mode != 4) a.ov_h = min(a.out_h, (a.in_h + z + 2) / 2);
     if (a.mode != 4) a.ov_w = min(a.out_w, (a.in_w + z + 2) / 2);
     const uint32_t nt = (uint32_t)((a.out_w + DW_TW - 1) / DW_TW) * (uint32_t)((a.out_h + DW_TH - 1) / DW_TH) * (uint32_t)planes;
-    if (px) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+    if (u8) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
     else hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
     const int n_edge = (a.out_h - a.ov_h) * a.out_w + a.ov_h * (a.out_w - a.ov_w);
     if (n_edge > 0) {
-        if (px) hipLaunchKernelGGL((k_dwt_edge<F, true>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
+        if (u8) hipLaunchKernelGGL((k_dwt_edge<F, true>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_dwt_edge<F>, dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
     }
     return (int)hipGetLastError();
 }
 // specialised for the zero-tap pattern of the known filter bank of that length, generic otherwise
 template <int F, uint32_t LOM, uint32_t HIM>
-static int launch_dwt_F(const DwtKArgs &a, int planes, hipStream_t st, const Px8 *px) {
+static int launch_dwt_F(const DwtKArgs &a, int planes, hipStream_t st) {
     uint32_t lom = 0, him = 0;
     for (int j = 0; j < F; j++) {
         if (a.lo[j] != 0.0) lom |= 1u << j;
         if (a.hi[j] != 0.0) him |= 1u << j;
     }
-    if (lom == LOM && him == HIM) return launch_dwt_FM<F, LOM, HIM>(a, planes, st, px);
-    return launch_dwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st, px);
+    if (lom == LOM && him == HIM) return launch_dwt_FM<F, LOM, HIM>(a, planes, st);
+    return launch_dwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st);
 }
-// px != nullptr: level 1 into an 8-bit picture (the U8 kernels; a.out unused)
+// a.px.out set: level 1 into an 8-bit picture (the U8 kernels; a.out unused)
 template <int F, uint32_t LOM, uint32_t HIM>
-static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc, const Px8 *px) {
+static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) {
     a.planes = planes;
-    if (px) a.px = *px;
+    const bool u8 = a.px.out != nullptr;
     if (a.color) {  // level 1 of a 3-channel image, colour model change on the stores
         uint32_t ntc = (uint32_t)((a.out_w + IW_TW - 1) / IW_TW) * (uint32_t)((a.out_h + IWC_TH - 1) / IWC_TH) * (uint32_t)(planes / 3);
-        if (px) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, true>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
+        if (u8) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, true>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
         else hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
         return (int)hipGetLastError();
     }
@@ -1641,7 +1641,7 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc, 
     const int num_cu = tc ? tc->num_cu : 0;
     // (the persistent kernel addresses a plane with 32-bit offsets: float64 planes by their size, the 8-bit output by the
     // span of its strides)
-    const bool off32 = px ? (uint64_t)((px->h - 1) * px->sh + (px->w - 1) * px->sw) + 1u < (1ull << 31)
+    const bool off32 = u8 ? (uint64_t)((a.px.h - 1) * a.px.sh + (a.px.w - 1) * a.px.sw) + 1u < (1ull << 31)
                           : (uint64_t)(a.out_h + IW_TH) * a.out_w * 8u < (1ull << 31);
     if (tc && tc->dev && num_cu >= 2 && nt >= pf_min && off32) {  // (>= 8 workgroups: one per tile range at least)
         const int g = tc->wg_per_cu > 0 ? tc->wg_per_cu : IWP_WG;
@@ -1667,7 +1667,7 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc, 
             tc->base[x] += (nt >> 3) + (x < (nt & 7u) ? 1u : 0u) + 2u * ((G + 7u - x) >> 3);
         }
         tc->started += G;
-        if (px) {
+        if (u8) {
             if (a.first) hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, true, false, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
             else if (a.flags && (uint64_t)a.enc_h * a.enc_w * 4u < (1ull << 31))
                 hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, true, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
@@ -1684,68 +1684,54 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc, 
         }
         return (int)e;
     }
-    if (px) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, true>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
+    if (u8) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, true>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
     else hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
     return (int)hipGetLastError();
 }
 template <int F, uint32_t LOM, uint32_t HIM>
-static int launch_idwt_F(const IdwtKArgs &a, int planes, hipStream_t st, TileCtr *tc, const Px8 *px) {
+static int launch_idwt_F(const IdwtKArgs &a, int planes, hipStream_t st, TileCtr *tc) {
     uint32_t lom = 0, him = 0;
     for (int j = 0; j < F; j++) {
         if (a.lo[j] != 0.0) lom |= 1u << j;
         if (a.hi[j] != 0.0) him |= 1u << j;
     }
-    if (lom == LOM && him == HIM) return launch_idwt_FM<F, LOM, HIM>(a, planes, st, tc, px);
-    return launch_idwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st, tc, px);
+    if (lom == LOM && him == HIM) return launch_idwt_FM<F, LOM, HIM>(a, planes, st, tc);
+    return launch_idwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st, tc);
 }
 
-static int spiht_launch_dwt_level_px(const DwtKArgs *a, int planes, hipStream_t st, const Px8 *px) {
-    switch (a->F) {
-    case 2: return launch_dwt_F<2, 0x3u, 0x3u>(*a, planes, st, px);            // haar
-    case 6: return launch_dwt_F<6, 0x3Eu, 0x0Eu>(*a, planes, st, px);          // bior2.2
-    case 10: return launch_dwt_F<10, 0x3FEu, 0x0FEu>(*a, planes, st, px);      // bior4.4
-    case 18: return launch_dwt_F<18, 0x3FFFEu, 0x3FF8u>(*a, planes, st, px);   // bior6.8
-    // every other even length up to SPIHT_MAX_TAPS (db / sym / coif / the other bior and rbio banks): all taps taken
-    case 4: return launch_dwt_F<4, 0xFu, 0xFu>(*a, planes, st, px);
-    case 8: return launch_dwt_F<8, 0xFFu, 0xFFu>(*a, planes, st, px);
-    case 12: return launch_dwt_F<12, 0xFFFu, 0xFFFu>(*a, planes, st, px);
-    case 14: return launch_dwt_F<14, 0x3FFFu, 0x3FFFu>(*a, planes, st, px);
-    case 16: return launch_dwt_F<16, 0xFFFFu, 0xFFFFu>(*a, planes, st, px);
-    case 20: return launch_dwt_F<20, 0xFFFFFu, 0xFFFFFu>(*a, planes, st, px);
-    default: return -1;
-    }
-}
+// a->px.in set: level 1 of an 8-bit picture, tiled routes only (the caller converts for the two-pass level)
 extern "C" int spiht_launch_dwt_level(const DwtKArgs *a, int planes, hipStream_t st) {
-    return spiht_launch_dwt_level_px(a, planes, st, nullptr);
-}
-// level 1 of an 8-bit picture (a->in unused); only the tiled routes (the caller converts in a pass of its own elsewhere)
-extern "C" int spiht_launch_dwt_level_u8(const DwtKArgs *a, const Px8 *px, int planes, hipStream_t st) {
-    if (!px || a->f32) return -1;
-    return spiht_launch_dwt_level_px(a, planes, st, px);
-}
-// tc: tile counters of the calling context (nullptr: fixed-stride tile order in the persistent kernel)
-static int spiht_launch_idwt_level_px(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc, const Px8 *px) {
     switch (a->F) {
-    case 2: return launch_idwt_F<2, 0x3u, 0x3u>(*a, planes, st, tc, px);            // haar
-    case 6: return launch_idwt_F<6, 0x0Eu, 0x3Eu>(*a, planes, st, tc, px);          // bior2.2 rec_lo / rec_hi
-    case 10: return launch_idwt_F<10, 0x0FEu, 0x3FEu>(*a, planes, st, tc, px);      // bior4.4
-    case 18: return launch_idwt_F<18, 0x3FF8u, 0x3FFFEu>(*a, planes, st, tc, px);   // bior6.8
-    case 4: return launch_idwt_F<4, 0xFu, 0xFu>(*a, planes, st, tc, px);
-    case 8: return launch_idwt_F<8, 0xFFu, 0xFFu>(*a, planes, st, tc, px);
-    case 12: return launch_idwt_F<12, 0xFFFu, 0xFFFu>(*a, planes, st, tc, px);
-    case 14: return launch_idwt_F<14, 0x3FFFu, 0x3FFFu>(*a, planes, st, tc, px);
-    case 16: return launch_idwt_F<16, 0xFFFFu, 0xFFFFu>(*a, planes, st, tc, px);
-    case 20: return launch_idwt_F<20, 0xFFFFFu, 0xFFFFFu>(*a, planes, st, tc, px);
+    case 2: return launch_dwt_F<2, 0x3u, 0x3u>(*a, planes, st);            // haar
+    case 6: return launch_dwt_F<6, 0x3Eu, 0x0Eu>(*a, planes, st);          // bior2.2
+    case 10: return launch_dwt_F<10, 0x3FEu, 0x0FEu>(*a, planes, st);      // bior4.4
+    case 18: return launch_dwt_F<18, 0x3FFFEu, 0x3FF8u>(*a, planes, st);   // bior6.8
+    // every other even length up to SPIHT_MAX_TAPS (db / sym / coif / the other bior and rbio banks): all taps taken
+    case 4: return launch_dwt_F<4, 0xFu, 0xFu>(*a, planes, st);
+    case 8: return launch_dwt_F<8, 0xFFu, 0xFFu>(*a, planes, st);
+    case 12: return launch_dwt_F<12, 0xFFFu, 0xFFFu>(*a, planes, st);
+    case 14: return launch_dwt_F<14, 0x3FFFu, 0x3FFFu>(*a, planes, st);
+    case 16: return launch_dwt_F<16, 0xFFFFu, 0xFFFFu>(*a, planes, st);
+    case 20: return launch_dwt_F<20, 0xFFFFFu, 0xFFFFFu>(*a, planes, st);
     default: return -1;
     }
 }
+// tc: tile counters of the calling context (nullptr: fixed-stride tile order in the persistent kernel); a->px.out set: level 1
+// into an 8-bit picture
 extern "C" int spiht_launch_idwt_level(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc) {
-    return spiht_launch_idwt_level_px(a, planes, st, tc, nullptr);
-}
-// level 1 into an 8-bit picture (a->out unused)
-extern "C" int spiht_launch_idwt_level_u8(const IdwtKArgs *a, const Px8 *px, int planes, hipStream_t st, TileCtr *tc) {
-    if (!px) return -1;
-    return spiht_launch_idwt_level_px(a, planes, st, tc, px);
+    switch (a->F) {
+    case 2: return launch_idwt_F<2, 0x3u, 0x3u>(*a, planes, st, tc);            // haar
+    case 6: return launch_idwt_F<6, 0x0Eu, 0x3Eu>(*a, planes, st, tc);          // bior2.2 rec_lo / rec_hi
+    case 10: return launch_idwt_F<10, 0x0FEu, 0x3FEu>(*a, planes, st, tc);      // bior4.4
+    case 18: return launch_idwt_F<18, 0x3FF8u, 0x3FFFEu>(*a, planes, st, tc);   // bior6.8
+    case 4: return launch_idwt_F<4, 0xFu, 0xFu>(*a, planes, st, tc);
+    case 8: return launch_idwt_F<8, 0xFFu, 0xFFu>(*a, planes, st, tc);
+    case 12: return launch_idwt_F<12, 0xFFFu, 0xFFFu>(*a, planes, st, tc);
+    case 14: return launch_idwt_F<14, 0x3FFFu, 0x3FFFu>(*a, planes, st, tc);
+    case 16: return launch_idwt_F<16, 0xFFFFu, 0xFFFFu>(*a, planes, st, tc);
+    case 20: return launch_idwt_F<20, 0xFFFFFu, 0xFFFFFu>(*a, planes, st, tc);
+    default: return -1;
+    }
 }
 // pad strips of coeffs_to_array for `L` levels: hs/ws band sizes and offh/offw block offsets (index 1..L)
 extern "C" int spiht_launch_zero_pads(int L, const int64_t *hs, const int64_t *ws, const int64_t *offh, const int64_t *offw,

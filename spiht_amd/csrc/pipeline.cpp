@@ -30,6 +30,19 @@
         if (_s != SPIHT_OK) return _s; \
     } while (0)
 
+// The pictures of a step, in or out: float64 [B, c, H, W], or 8-bit (spiht_pipeline_submit_u8) laid out by byte strides
+// (none given: dense CHW).  The strides are copied: an output is written a step later.
+struct StepPics {
+    void *p = nullptr;
+    bool u8 = false, strided = false;
+    int64_t st[4] = {0, 0, 0, 0};
+    StepPics() = default;
+    StepPics(const void *p_, bool u8_, const int64_t *strides = nullptr) : p(const_cast<void *>(p_)), u8(u8_), strided(strides != nullptr) {
+        if (strides) memcpy(st, strides, sizeof(st));
+    }
+    const int64_t *strides() const { return strided ? st : nullptr; }
+};
+
 struct spiht_pipeline {
     int device = 0;
     int64_t B = 0, c = 0, H = 0, W = 0;
@@ -52,11 +65,7 @@ struct spiht_pipeline {
     uint64_t step = 0;
     bool pending = false;      // a batch whose inverse transform has not been queued yet
     int pending_slot = 0;
-    double *pending_out = nullptr;
-    // ... or its 8-bit output (spiht_pipeline_submit_u8): every step keeps the form it was submitted with
-    uint8_t *pending_out8 = nullptr;
-    int64_t pending_str8[4] = {0, 0, 0, 0};
-    bool pending_str8_set = false;  // false: dense CHW
+    StepPics pending_out;      // ... and its pictures (every step keeps the form it was submitted with)
     // colour model of the coded pictures (spiht_pipeline_set_color3): the pipeline's own, put on the H context around its calls
     bool color_on = false;
     double cAf[9], cMf[9], cAi[9], cMi[9], cpf = 1.0, cpi = 1.0;
@@ -226,50 +235,42 @@ static int queue_inverse_coarse(spiht_pipeline *p, int s) {
     CHK(spiht_event_record(p->ev_c, p->Hc));
     return SPIHT_OK;
 }
-static int queue_inverse_level1(spiht_pipeline *p, int s, double *d_img_out) {
-    if (p->pending_out8) {
-        const int64_t *str = p->pending_str8_set ? p->pending_str8 : nullptr;
+static int queue_inverse_level1(spiht_pipeline *p, int s, const StepPics &out) {
+    if (out.u8) {
         if (p->approx)
             CHK(spiht_idwt_level1_flags_batch_u8(p->Hc, p->rec[s], p->approx, p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode,
-                                                 p->level, p->q, p->mp(), p->pending_out8, str));
+                                                 p->level, p->q, p->mp(), (uint8_t *)out.p, out.strides()));
         else
             CHK(spiht_dequant_idwt_flags_batch_u8(p->Hc, p->rec[s], p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
-                                                  p->q, p->mp(), p->pending_out8, str));
+                                                  p->q, p->mp(), (uint8_t *)out.p, out.strides()));
     } else if (p->approx)
         CHK(spiht_idwt_level1_flags_batch_f64(p->Hc, p->rec[s], p->approx, p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode,
-                                              p->level, p->q, p->mp(), d_img_out));
+                                              p->level, p->q, p->mp(), (double *)out.p));
     else
         CHK(spiht_dequant_idwt_flags_batch_f64(p->Hc, p->rec[s], p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
-                                               p->q, p->mp(), d_img_out));
+                                               p->q, p->mp(), (double *)out.p));
     CHK(spiht_event_record(p->ev_i[s], p->Hc));
     // ... and the zeros back into the array as soon as that has read it, on the batch's own list-coding context
     CHK(spiht_ctx_wait_event(p->Lc[s], p->ev_i[s]));
     CHK(spiht_unscatter_lists_batch_i32(p->Lc[s], p->rec[s], p->B, p->c, p->enc_h, p->enc_w));
     return SPIHT_OK;
 }
-static int queue_inverse(spiht_pipeline *p, int s, double *d_img_out) {
+static int queue_inverse(spiht_pipeline *p, int s, const StepPics &out) {
     CHK(queue_inverse_coarse(p, s));
-    return queue_inverse_level1(p, s, d_img_out);
+    return queue_inverse_level1(p, s, out);
 }
 
-// the views of an 8-bit step (spiht_pipeline_submit_u8; its d_img / d_img_out are then null)
-struct Px8Step {
-    const uint8_t *in = nullptr;
-    const int64_t *in_strides = nullptr;
-    uint8_t *out = nullptr;
-    const int64_t *out_strides = nullptr;
-};
-static int submit_impl(spiht_pipeline *p, const double *d_img, uint8_t *d_out, uint64_t *d_nbits, uint8_t *d_max_n, double *d_img_out,
-                       spiht_comm *comm, uint8_t *d_all_slots, uint64_t *d_all_nbits, uint8_t *d_all_max_n, int rank,
-                       const Px8Step &u8 = Px8Step()) {
+static int submit_impl(spiht_pipeline *p, const StepPics &in, const StepPics &out, uint8_t *d_out, uint64_t *d_nbits, uint8_t *d_max_n,
+                       spiht_comm *comm = nullptr, uint8_t *d_all_slots = nullptr, uint64_t *d_all_nbits = nullptr,
+                       uint8_t *d_all_max_n = nullptr, int rank = 0) {
     const int s = (int)(p->step & 1), o = s ^ 1;
     spiht_ctx *L = p->Lc[s];
     // H: front half of the encoder
-    if (u8.in)
-        CHK(spiht_dwt_pyramid_batch_u8(p->Hc, u8.in, u8.in_strides, p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level, p->q,
-                                       p->mp(), p->coeffs[s], p->dmsb[s], p->lmsb[s], p->maxabs[s]));
+    if (in.u8)
+        CHK(spiht_dwt_pyramid_batch_u8(p->Hc, (const uint8_t *)in.p, in.strides(), p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
+                                       p->q, p->mp(), p->coeffs[s], p->dmsb[s], p->lmsb[s], p->maxabs[s]));
     else
-        CHK(spiht_dwt_pyramid_batch_f64(p->Hc, d_img, p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level, p->q, p->mp(),
+        CHK(spiht_dwt_pyramid_batch_f64(p->Hc, (const double *)in.p, p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level, p->q, p->mp(),
                                         p->coeffs[s], p->dmsb[s], p->lmsb[s], p->maxabs[s]));
     CHK(spiht_event_record(p->ev_a[s], p->Hc));
     // L: list coding, after the previous batch's decoder on the other context (list kernels never run beside one another)
@@ -314,10 +315,7 @@ static int submit_impl(spiht_pipeline *p, const double *d_img, uint8_t *d_out, u
     p->used[s] = true;
     p->pending = true;
     p->pending_slot = s;
-    p->pending_out = d_img_out;
-    p->pending_out8 = u8.out;
-    p->pending_str8_set = u8.out_strides != nullptr;
-    if (u8.out_strides) memcpy(p->pending_str8, u8.out_strides, sizeof(p->pending_str8));
+    p->pending_out = out;
     p->step++;
     return SPIHT_OK;
 }
@@ -330,7 +328,9 @@ extern "C" int spiht_pipeline_submit_gather(spiht_pipeline *p, const double *d_i
     if (p->poisoned != SPIHT_OK) return p->poisoned;
     HScope sc(p);
     int st = sc.st;
-    if (st == SPIHT_OK) st = submit_impl(p, d_img, d_out, d_nbits, d_max_n, d_img_out, comm, d_all_slots, d_all_nbits, d_all_max_n, rank);
+    if (st == SPIHT_OK)
+        st = submit_impl(p, StepPics(d_img, false), StepPics(d_img_out, false), d_out, d_nbits, d_max_n, comm, d_all_slots, d_all_nbits,
+                         d_all_max_n, rank);
     // a failure between the first and the last queued call leaves events, buffer sets and the pending inverse transform half
     // advanced: nothing later can be trusted, and every later call says so with the first error
     if (st != SPIHT_OK) p->poisoned = st;
@@ -349,11 +349,9 @@ extern "C" int spiht_pipeline_submit_u8(spiht_pipeline *p, const uint8_t *d_img,
     // the views are checked before anything is queued: a bad one leaves the pipeline as it was
     if (in_strides) CHK(spiht_check_view_u8(p->B, p->c, p->H, p->W, in_strides, 0));
     if (out_strides) CHK(spiht_check_view_u8(p->B, p->c, p->H, p->W, out_strides, 1));
-    Px8Step u8;
-    u8.in = d_img; u8.in_strides = in_strides; u8.out = d_img_out; u8.out_strides = out_strides;
     HScope sc(p);
     int st = sc.st;
-    if (st == SPIHT_OK) st = submit_impl(p, nullptr, d_out, d_nbits, d_max_n, nullptr, nullptr, nullptr, nullptr, nullptr, 0, u8);
+    if (st == SPIHT_OK) st = submit_impl(p, StepPics(d_img, true, in_strides), StepPics(d_img_out, true, out_strides), d_out, d_nbits, d_max_n);
     if (st != SPIHT_OK) p->poisoned = st;
     return st;
 }

@@ -158,21 +158,25 @@ def encode_image(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSetting
     img = np.ascontiguousarray(image, dtype=np.float32 if f32 else np.float64)
     if f32 and g["level"] == 0:
         raise ValueError("float32 pixels with level 0 are not supported; pass float64 pixels")
+    return _encode_host(ctx, L.spiht_encode_image_host_f32 if f32 else L.spiht_encode_image_host_f64, (C.c_void_p(img.ctypes.data),),
+                        (c, h, w), g, wid, mid, level, spiht_settings, mults_p, max_bits)
+
+
+def _encode_host(ctx, fn, pixels, chw, g, wid, mid, level, spiht_settings, mults_p, max_bits):
+    """the tail of encode_image / encode_image_u8: one C call fn(ctx, *pixels, c, h, w, ...) -- upload, DWT + quantise +
+    pyramid + list coder, stream back (the context keeps its device buffers) -- into a buffer of the stream's bound"""
+    c, h, w = chw
     bound = C.c_uint64()
-    _lib.check(L.spiht_encode_bound(c, g["enc_h"], g["enc_w"], g["ll_h"], g["ll_w"], 0x3FFFFFFF, max_bits,
-                                    C.byref(bound)))
+    _lib.check(_lib.lib().spiht_encode_bound(c, g["enc_h"], g["enc_w"], g["ll_h"], g["ll_w"], 0x3FFFFFFF, max_bits,
+                                             C.byref(bound)))
     out = np.empty(max(int(bound.value), 4), dtype=np.uint8)
     nbits, mn = C.c_uint64(), C.c_uint8()
-    # one C call: upload, DWT + quantise + pyramid + list coder, stream back (the context keeps its device buffers)
-    with color_models.fused(ctx, color_model):
-        _lib.check((L.spiht_encode_image_host_f32 if f32 else L.spiht_encode_image_host_f64)(
-            ctx.handle, C.c_void_p(img.ctypes.data), c, h, w, wid, mid, -1 if level is None else int(level),
-            float(spiht_settings.quantization_scale), mults_p, max_bits, C.c_void_p(out.ctypes.data), out.size,
-            C.byref(nbits), C.byref(mn)))
-    max_n = int(mn.value)
+    with color_models.fused(ctx, spiht_settings.color_model):
+        _lib.check(fn(ctx.handle, *pixels, c, h, w, wid, mid, -1 if level is None else int(level),
+                      float(spiht_settings.quantization_scale), mults_p, max_bits, C.c_void_p(out.ctypes.data), out.size,
+                      C.byref(nbits), C.byref(mn)))
     out = out[:(int(nbits.value) + 7) // 8]
-
-    return EncodingResult(out.tobytes(), h, w, c, max_n, level)
+    return EncodingResult(out.tobytes(), h, w, c, int(mn.value), level)
 
 
 def decode_image(encoding_result: EncodingResult, spiht_settings: SpihtSettings,
@@ -184,8 +188,26 @@ def decode_image(encoding_result: EncodingResult, spiht_settings: SpihtSettings,
         image = decode_from_rec_arr(**d, spiht_settings=spiht_settings)
         return image, spiht_metadata
     # decode_rec_array + decode_from_rec_arr (wrapper:218-281) as one C call: the coefficient array never leaves HBM
+    _check_version(encoding_result)
+    c = encoding_result.c
+    g, keep, args = _decode_args(encoding_result, spiht_settings)
+    out = _lib.result_array((c, g["rec_h"], g["rec_w"]), np.float64)  # (page-locked: the copy back is one DMA)
+    ctx = _lib.default_context()
+    if spiht_settings.color_model is not None and c != 3:
+        raise ValueError("colour conversion needs 3 channels")
+    with color_models.fused(ctx, spiht_settings.color_model):  # wrapper:278-279, inside the last level of the inverse transform
+        _lib.check(_lib.lib().spiht_decode_image_host_f64(ctx.handle, *args, C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def _check_version(encoding_result):
     if encoding_result._encoding_version != ENCODER_DECODER_VERSION:
         raise ValueError(encoding_result._encoding_version)
+
+
+def _decode_args(encoding_result, spiht_settings):
+    """the checks decode_image and decode_image_u8 share, in their order -> (geometry, the arrays the pointers point into --
+    kept by the caller until the call --, the arguments of the C call from the stream to the channel scales)"""
     h, w, c, level = encoding_result.h, encoding_result.w, encoding_result.c, encoding_result.level
     wid, mid = _wavelet_mode_ids(spiht_settings)
     g = _geometry(h, w, wid, level, mid)
@@ -194,16 +216,8 @@ def decode_image(encoding_result: EncodingResult, spiht_settings: SpihtSettings,
     if n > 255:
         raise OverflowError("out of range integral type conversion attempted")
     mults, mults_p = _mults_arg(spiht_settings.per_channel_quant_scales, c)
-    out = _lib.result_array((c, g["rec_h"], g["rec_w"]), np.float64)  # (page-locked: the copy back is one DMA)
-    ctx = _lib.default_context()
-    if spiht_settings.color_model is not None and c != 3:
-        raise ValueError("colour conversion needs 3 channels")
-    with color_models.fused(ctx, spiht_settings.color_model):  # wrapper:278-279, inside the last level of the inverse transform
-        _lib.check(_lib.lib().spiht_decode_image_host_f64(
-            ctx.handle, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, n, c, h, w, wid, mid,
-            -1 if level is None else int(level), float(spiht_settings.quantization_scale), mults_p,
-            C.c_void_p(out.ctypes.data)))
-    return out
+    return g, (buf, mults), (C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, n, c, h, w, wid, mid, -1 if level is None else int(level),
+               float(spiht_settings.quantization_scale), mults_p)
 
 
 def check_u8_view(shape, strides, output):
@@ -254,45 +268,26 @@ def encode_image_u8(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSett
     if max_bits == None:  # noqa: E711  (as encode_image)
         max_bits = 99999999999999999
     max_bits = spiht_rs._as_usize(max_bits, "max_bits")
-    L = _lib.lib()
-    bound = C.c_uint64()
-    _lib.check(L.spiht_encode_bound(c, g["enc_h"], g["enc_w"], g["ll_h"], g["ll_w"], 0x3FFFFFFF, max_bits, C.byref(bound)))
-    out = np.empty(max(int(bound.value), 4), dtype=np.uint8)
-    nbits, mn = C.c_uint64(), C.c_uint8()
     strides = np.array(image.strides, dtype=np.int64)
-    ctx = _lib.default_context()
-    with color_models.fused(ctx, spiht_settings.color_model):
-        _lib.check(L.spiht_encode_image_host_u8(
-            ctx.handle, C.c_void_p(image.ctypes.data), C.c_void_p(strides.ctypes.data), c, h, w, wid, mid,
-            -1 if level is None else int(level), float(spiht_settings.quantization_scale), mults_p, max_bits,
-            C.c_void_p(out.ctypes.data), out.size, C.byref(nbits), C.byref(mn)))
-    out = out[:(int(nbits.value) + 7) // 8]
-    return EncodingResult(out.tobytes(), h, w, c, int(mn.value), level)
+    return _encode_host(_lib.default_context(), _lib.lib().spiht_encode_image_host_u8,
+                        (C.c_void_p(image.ctypes.data), C.c_void_p(strides.ctypes.data)), (c, h, w), g, wid, mid, level,
+                        spiht_settings, mults_p, max_bits)
 
 
 def decode_image_u8(encoding_result: EncodingResult, spiht_settings: SpihtSettings, channels_last: bool = False) -> np.ndarray:
     """8-bit pixels: (np.clip(decode_image(r, s), 0, 1) * 255).astype(np.uint8) cropped to the encoded picture's h x w, with
     the conversion done on the device.  Returns a new uint8 array (c, h, w), or (h, w, c) with channels_last."""
-    if encoding_result._encoding_version != ENCODER_DECODER_VERSION:
-        raise ValueError(encoding_result._encoding_version)
-    h, w, c, level = encoding_result.h, encoding_result.w, encoding_result.c, encoding_result.level
+    _check_version(encoding_result)
+    h, w, c = encoding_result.h, encoding_result.w, encoding_result.c
     if spiht_settings.color_model is not None and c != 3:
         raise ValueError("colour conversion needs 3 channels")
-    wid, mid = _wavelet_mode_ids(spiht_settings)
-    _geometry(h, w, wid, level, mid)
-    buf = spiht_rs._as_u8_vec(encoding_result.encoded_bytes)
-    n = spiht_rs._as_usize(encoding_result.max_n, "n")
-    if n > 255:
-        raise OverflowError("out of range integral type conversion attempted")
-    mults, mults_p = _mults_arg(spiht_settings.per_channel_quant_scales, c)
+    _, keep, args = _decode_args(encoding_result, spiht_settings)
     out = _lib.result_array((h, w, c) if channels_last else (c, h, w), np.uint8)
     strides = np.array((1, w * c, c) if channels_last else (h * w, w, 1), dtype=np.int64)
     ctx = _lib.default_context()
     with color_models.fused(ctx, spiht_settings.color_model):
-        _lib.check(_lib.lib().spiht_decode_image_host_u8(
-            ctx.handle, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, n, c, h, w, wid, mid,
-            -1 if level is None else int(level), float(spiht_settings.quantization_scale), mults_p,
-            C.c_void_p(out.ctypes.data), C.c_void_p(strides.ctypes.data)))
+        _lib.check(_lib.lib().spiht_decode_image_host_u8(ctx.handle, *args, C.c_void_p(out.ctypes.data),
+                                                         C.c_void_p(strides.ctypes.data)))
     return out
 
 

@@ -388,15 +388,32 @@ def test_level1_tile_occupancy_words(oracle, case):
     ctx.memset(d_fl.ptr, 0xEE, d_fl.nbytes)  # (the call zero-fills them itself)
     _lib.check(L.spiht_decode_lists_flags_batch_i32(ctx.handle, vp(d_data.ptr), stride, vp(d_nb.ptr), vp(d_mn.ptr), B, c, H, W,
                                                     cd.wid, cd.mid, cd._lv, vp(d_rec.ptr), vp(d_fl.ptr if nw.value else None)))
+    a_h, a_w = C.c_int64(), C.c_int64()
+    _lib.check(L.spiht_idwt_approx_shape(H, W, cd.wid, cd._lv, C.byref(a_h), C.byref(a_w)))
+    d_ap = DeviceArray(ctx, (B * c, max(a_h.value, 1), max(a_w.value, 1)), np.float64)
+    q = float(s.quantization_scale)
     outs = []
-    for fl in (d_fl.ptr if nw.value else None, None):
+    # the inverse in one call, with and without the words; then in two (coarse levels, level 1), with and without them
+    for two, fl in ((False, d_fl.ptr if nw.value else None), (False, None), (True, d_fl.ptr if nw.value else None), (True, None)):
         d_img = DeviceArray(ctx, (B, c, g["rec_h"], g["rec_w"]), np.float64)
-        _lib.check(L.spiht_dequant_idwt_flags_batch_f64(ctx.handle, vp(d_rec.ptr), vp(fl), B, c, H, W, cd.wid, cd.mid, cd._lv,
-                                                        float(s.quantization_scale), None, vp(d_img.ptr)))
+        if not two:
+            _lib.check(L.spiht_dequant_idwt_flags_batch_f64(ctx.handle, vp(d_rec.ptr), vp(fl), B, c, H, W, cd.wid, cd.mid, cd._lv,
+                                                            q, None, vp(d_img.ptr)))
+        else:
+            _lib.check(L.spiht_idwt_coarse_batch_f64(ctx.handle, vp(d_rec.ptr), B, c, H, W, cd.wid, cd.mid, cd._lv, q, None,
+                                                     vp(d_ap.ptr)))
+            if fl is None:
+                _lib.check(L.spiht_idwt_level1_batch_f64(ctx.handle, vp(d_rec.ptr), vp(d_ap.ptr), B, c, H, W, cd.wid, cd.mid,
+                                                         cd._lv, q, None, vp(d_img.ptr)))
+            else:
+                _lib.check(L.spiht_idwt_level1_flags_batch_f64(ctx.handle, vp(d_rec.ptr), vp(d_ap.ptr), vp(fl), B, c, H, W, cd.wid,
+                                                               cd.mid, cd._lv, q, None, vp(d_img.ptr)))
         ctx.synchronize()
         outs.append(d_img.download())
         d_img.free()
-    assert np.array_equal(outs[0], outs[1])
+    d_ap.free()
+    for o in outs[1:]:
+        assert np.array_equal(outs[0], o)
     rec = d_rec.download().reshape(B, c, g["enc_h"], g["enc_w"])
     for b in range(B):
         ref = oracle.decode_image(res[b].encoded_bytes, res[b].max_n, c, H, W, wavelet, level, float(s.quantization_scale), None)

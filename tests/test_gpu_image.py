@@ -94,6 +94,12 @@ def test_batch_codec_matches_single_image_path(oracle):
     dec = codec.decode(results)
     for b in range(B):
         assert np.array_equal(dec[b], spiht_amd.decode_image(results[b], s))
+    # float32 pictures: the single-precision batch encoder gives the streams of encode_image of the same pictures
+    imgs32 = imgs.astype(np.float32)
+    results32 = BatchCodec(c, H, W, s, level, max_bits, pixel_dtype=np.float32).encode(imgs32)
+    for b in range(B):
+        one = spiht_amd.encode_image(imgs32[b], s, level=level, max_bits=max_bits)
+        assert (one.encoded_bytes, one.max_n) == (results32[b].encoded_bytes, results32[b].max_n)
     # ragged prefixes in one decode batch (make_gif.py:46-55)
     cut = [spiht_amd.EncodingResult(r.encoded_bytes[:k], H, W, c, r.max_n, level) for r, k in zip(results, [0, 1, 333, 750, 17])]
     dec = codec.decode(cut)
