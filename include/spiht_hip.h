@@ -151,6 +151,23 @@ int spiht_decode_batch_i32(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_
                            const uint8_t *d_max_n, int64_t B, int64_t c, int64_t h, int64_t w, int64_t ll_h,
                            int64_t ll_w, int32_t *d_out);
 
+/* decode_with_metadata of B streams at once (spiht_decode_with_metadata_i32 per stream, in one queue of work).
+ * d_data / slot_stride / d_nbytes / d_max_n: device, as in spiht_decode_batch_i32; top_slice / other_slices / level: HOST
+ * arrays, as in spiht_decode_with_metadata_i32 (read during the call only).  d_meta: device int32 [B, meta_rows, 8],
+ * meta_rows >= 8 * slot_stride + 1: rows [0, 8 * nbytes[b] + 1) of image b are what spiht_decode_with_metadata_i32 returns
+ * for that stream, every later row is zero.  d_out: device int32 [B, c, h, w] receiving the decoded arrays, or NULL.
+ * Host-side errors as the single call (SPIHT_ERR_SHAPE: tree deeper than `level`, a reversed slice; SPIHT_ERR_TOO_LARGE:
+ * c*h*w >= 2^28 or slot_stride >= 2^28), SPIHT_ERR_ARG for NULL pointers, slot_stride % 4 or meta_rows too small; B == 0
+ * does nothing.  max_n > 30 and nbytes > slot_stride are reported by spiht_ctx_synchronize().  Asynchronous.
+ * The images go in chunks; the context's scratch for a chunk -- the trace and the sort buffers, 21 bytes per record of
+ * (8 * slot_stride + 1) per image, plus rocPRIM's temporary for sorting them -- stays within 2 GiB (one image that needs
+ * more goes alone), whatever B is; with d_out NULL also a chunk's coefficient arrays.  Option "meta_chunk" (0: by that
+ * bound) caps the images per chunk. */
+int spiht_decode_with_metadata_batch_i32(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
+                                         const uint8_t *d_max_n, int64_t B, int64_t c, int64_t h, int64_t w, int64_t ll_h,
+                                         int64_t ll_w, const int64_t *top_slice, const int64_t *other_slices, int64_t level,
+                                         int32_t *d_out, int32_t *d_meta, uint64_t meta_rows);
+
 /* ---------------------------------------------------------------------------------------
  * Fused image path: pixels -> DWT -> quantise -> SPIHT and back, everything in HBM.
  * Mirrors spiht_wrapper.encode_image / decode_image (wrapper:142-216) without colour conversion.
@@ -316,7 +333,8 @@ int spiht_dequant_idwt_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, cons
  * kernel of the caller's), a group gives up after a bounded wait (tens of milliseconds) and the image is coded by one
  * workgroup instead, queued behind on the same stream -- same bits, never an error (spiht_ctx_wide_stats tells).
  * "idwt_groups" (default 0 = 4): persistent workgroups per CU of the large inverse-transform levels; 3 leaves a list
- * decoder's workgroup room beside them (the pipelined schedule sets it around its own calls). */
+ * decoder's workgroup room beside them (the pipelined schedule sets it around its own calls).  "meta_chunk" (default 0 =
+ * by the scratch bound, up to 65535): images per chunk of spiht_decode_with_metadata_batch_i32. */
 int spiht_ctx_set_option(spiht_ctx *ctx, const char *name, int64_t value);
 int spiht_ctx_get_option(spiht_ctx *ctx, const char *name, int64_t *value);
 /* The last encode call of this context that took the several-CUs-per-image path: its images (groups) and how many of them

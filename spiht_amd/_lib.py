@@ -53,7 +53,7 @@ SYMBOLS = [
     "spiht_geometry_mode", "spiht_wavelet_taps", "spiht_ctx_set_option", "spiht_ctx_get_option", "spiht_ctx_wide_stats", "spiht_l1_flags_words", "spiht_decode_lists_flags_batch_i32", "spiht_dequant_idwt_flags_batch_f64",
     "spiht_encode_image_batch_u8", "spiht_decode_image_batch_u8", "spiht_encode_image_host_u8", "spiht_decode_image_host_u8",
     "spiht_dwt_pyramid_batch_u8", "spiht_dequant_idwt_flags_batch_u8", "spiht_idwt_level1_flags_batch_u8", "spiht_pipeline_submit_u8",
-    "spiht_check_view_u8",
+    "spiht_check_view_u8", "spiht_decode_with_metadata_batch_i32",
 ]
 
 
@@ -112,6 +112,8 @@ def lib():
         L.spiht_decode_with_metadata_i32.argtypes = [vp, vp, u64, u8, i64, i64, i64, i64, i64, vp, vp, i64, vp, vp]
         L.spiht_encode_batch_i32.argtypes = [vp, vp, i64, i64, i64, i64, i64, i64, u64, vp, u64, vp, vp]
         L.spiht_decode_batch_i32.argtypes = [vp, vp, u64, vp, vp, i64, i64, i64, i64, i64, i64, vp]
+        L.spiht_decode_with_metadata_batch_i32.argtypes = [vp, vp, u64, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, i64, vp,
+                                                           vp, u64]
         L.spiht_wavelet_id.argtypes = [C.c_char_p]
         L.spiht_mode_id.argtypes = [C.c_char_p]
         L.spiht_wavelet_taps.argtypes = [i32]
@@ -250,7 +252,7 @@ class Context:
 
     def set_option(self, name, value):
         """a switch of the library (spiht_ctx_set_option): "l1_flags", "pads_persist", "wide_encode", "wide_groups",
-        "wide_solo", "idwt_groups"; results do not depend on them"""
+        "wide_solo", "idwt_groups", "meta_chunk"; results do not depend on them"""
         check(self._lib.spiht_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def get_option(self, name):

@@ -10,7 +10,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, color_models
-from .spiht_wrapper import EncodingResult, SpihtSettings, _geometry, _mults_arg, _wavelet_mode_ids, check_u8_view
+from . import spiht as spiht_rs
+from .spiht_wrapper import (EncodingResult, SpihtSettings, _geometry, _metadata_boxes, _mults_arg, _wavelet_mode_ids,
+                            check_u8_view)
 
 
 class DeviceArray:
@@ -73,6 +75,8 @@ class BatchCodec:
                                              self.geom["ll_w"], 0x3FFFFFFF, self.max_bits, C.byref(bound)))
         self.slot_stride = max(int(bound.value), 4)
         self._lv = -1 if level is None else int(level)
+        self._meta_slices = None   # decode_with_metadata_device: the sub-band boxes (host int64 arrays) and their level count
+        self._rec_scratch = None   # ... its coefficient arrays when the caller gives none
         if self.settings.color_model not in (None, "RGB"):
             if self.settings.color_model not in color_models.SUPPORTED_MODELS:
                 raise ValueError(f'{self.settings.color_model} is not a supported color model. '
@@ -101,6 +105,38 @@ class BatchCodec:
                 C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
                 float(self.settings.quantization_scale), self._mults_p, C.c_void_p(d_img_out),
                 C.c_void_p(d_rec) if d_rec else None))
+
+    def decode_with_metadata_device(self, d_data, d_nbytes, d_max_n, B, d_meta, meta_rows, d_img_out=None, d_rec=None,
+                                    slot_stride=None):
+        """decode_image(..., return_metadata=True) of B device-resident streams (the slots, nbytes and max_n of
+        encode_device + nbits_to_nbytes): the metadata tables into d_meta, int32 [B, meta_rows, 8] with meta_rows >=
+        8 * slot_stride + 1 (image b's rows past 8 * nbytes[b] + 1 are zero); the decoded coefficient arrays into d_rec
+        (int32 [B, c, enc_h, enc_w]) when given, and the pictures, float64 [B, c, H', W'], into d_img_out when given.
+        Queued on the codec's context (spiht_decode_with_metadata_batch_i32, then spiht_dequant_idwt_batch_f64)."""
+        g = self.geom
+        B = int(B)
+        if self._meta_slices is None:
+            top, other = _metadata_boxes(self.H, self.W, self.settings, g)
+            self._meta_slices = spiht_rs._metadata_args(self.c, g["enc_h"], g["enc_w"], g["ll_h"], g["ll_w"], top, other)[5:]
+        topv, oth, level = self._meta_slices
+        rec = d_rec
+        if rec is None and d_img_out is not None:
+            need = B * self.c * g["enc_h"] * g["enc_w"] * 4
+            if self._rec_scratch is None or self._rec_scratch.nbytes < need:
+                if self._rec_scratch is not None:
+                    self._rec_scratch.free()
+                self._rec_scratch = DeviceArray(self.ctx, (B, self.c, g["enc_h"], g["enc_w"]), np.int32)
+            rec = self._rec_scratch.ptr
+        _lib.check(self.L.spiht_decode_with_metadata_batch_i32(
+            self.ctx.handle, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
+            C.c_void_p(d_nbytes), C.c_void_p(d_max_n), B, self.c, g["enc_h"], g["enc_w"], g["ll_h"], g["ll_w"],
+            C.c_void_p(topv.ctypes.data), C.c_void_p(oth.ctypes.data), level, C.c_void_p(rec) if rec else None,
+            C.c_void_p(d_meta), int(meta_rows)))
+        if d_img_out is not None and B > 0:
+            with self._color():
+                _lib.check(self.L.spiht_dequant_idwt_batch_f64(
+                    self.ctx.handle, C.c_void_p(rec), B, self.c, self.H, self.W, self.wid, self.mid, self._lv,
+                    float(self.settings.quantization_scale), self._mults_p, C.c_void_p(d_img_out)))
 
     # ---- 8-bit pixels (include/spiht_hip.h, *_u8): whatever pixel_dtype says, the float64 arithmetic on k / 255 ----------
     def _u8_strides(self, B, strides, output):
@@ -166,6 +202,28 @@ class BatchCodec:
         """list of EncodingResult (same geometry) -> float64 [B,c,H',W']"""
         return self._decode_host(results, (self.c, self.geom["rec_h"], self.geom["rec_w"]), np.float64, self.decode_device)
 
+    def decode_with_metadata(self, results):
+        """list of EncodingResult (same geometry) -> (float64 [B,c,H',W'], [metadata_b]): the pictures of decode(results)
+        and, per stream, the table decode_image(results[b], settings, return_metadata=True) returns, int32
+        (8 * len(results[b].encoded_bytes) + 1, 8) -- from one batched call"""
+        B = len(results)
+        g = self.geom
+        if B == 0:
+            return np.zeros((0, self.c, g["rec_h"], g["rec_w"])), []
+        stride, d_in = self._streams_on_device(results)
+        meta_rows = 8 * stride + 1
+        d_img = DeviceArray(self.ctx, (B, self.c, g["rec_h"], g["rec_w"]), np.float64)
+        d_meta = DeviceArray(self.ctx, (B, meta_rows, 8), np.int32)
+        try:
+            self.decode_with_metadata_device(*(d.ptr for d in d_in), B, d_meta.ptr, meta_rows, d_img_out=d_img.ptr,
+                                             slot_stride=stride)
+            self.ctx.synchronize()
+            images, meta = d_img.download(), d_meta.download()
+        finally:
+            for d in d_in + (d_img, d_meta):
+                d.free()
+        return images, [meta[b, :8 * len(r.encoded_bytes) + 1] for b, r in enumerate(results)]
+
     def _encode_host(self, images, encode_device):
         """host pictures [B, ...] -> their device copy -> encode_device(d_img, B, d_out, d_nbits, d_max_n) -> EncodingResults"""
         B = images.shape[0]
@@ -189,27 +247,30 @@ class BatchCodec:
         """the streams of `results` on the device, in slots of the longest one's size -> decode_device(d_data, d_nbytes,
         d_max_n, B, d_img_out, slot_stride=...) into `dtype` pictures of `shape` -> host array [B, *shape]"""
         B = len(results)
-        stride = max(4, (max(len(r.encoded_bytes) for r in results) + 3) & ~3)
-        data = np.zeros((B, stride), dtype=np.uint8)
-        for b, r in enumerate(results):
-            data[b, :len(r.encoded_bytes)] = np.frombuffer(r.encoded_bytes, np.uint8)
-        nbytes = np.array([len(r.encoded_bytes) for r in results], dtype=np.uint64)
-        maxn = np.array([r.max_n for r in results], dtype=np.uint8)
-        ctx = self.ctx
-        d_data = DeviceArray(ctx, data.shape, np.uint8)
-        d_nbytes = DeviceArray(ctx, (B,), np.uint64)
-        d_maxn = DeviceArray(ctx, (B,), np.uint8)
-        d_img = DeviceArray(ctx, (B,) + tuple(shape), dtype)
+        stride, (d_data, d_nbytes, d_maxn) = self._streams_on_device(results)
+        d_img = DeviceArray(self.ctx, (B,) + tuple(shape), dtype)
         try:
-            d_data.upload(data)
-            d_nbytes.upload(nbytes)
-            d_maxn.upload(maxn)
             decode_device(d_data.ptr, d_nbytes.ptr, d_maxn.ptr, B, d_img.ptr, slot_stride=stride)
-            ctx.synchronize()
+            self.ctx.synchronize()
             return d_img.download()
         finally:
             for d in (d_data, d_nbytes, d_maxn, d_img):
                 d.free()
+
+    def _streams_on_device(self, results):
+        """the streams of `results` on the device, in slots of the longest one's size -> (slot_stride, (d_data, d_nbytes,
+        d_max_n)) -- DeviceArrays the caller frees"""
+        B = len(results)
+        stride = max(4, (max(len(r.encoded_bytes) for r in results) + 3) & ~3)
+        data = np.zeros((B, stride), dtype=np.uint8)
+        for b, r in enumerate(results):
+            data[b, :len(r.encoded_bytes)] = np.frombuffer(r.encoded_bytes, np.uint8)
+        d = (DeviceArray(self.ctx, data.shape, np.uint8), DeviceArray(self.ctx, (B,), np.uint64),
+             DeviceArray(self.ctx, (B,), np.uint8))
+        d[0].upload(data)
+        d[1].upload(np.array([len(r.encoded_bytes) for r in results], dtype=np.uint64))
+        d[2].upload(np.array([r.max_n for r in results], dtype=np.uint8))
+        return stride, d
 
     def decode_prefixes(self, result, byte_lengths, one_walk=True):
         """Progressive decoding (the pattern of the reference's make_gif.py:46-61): the pictures of the

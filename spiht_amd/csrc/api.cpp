@@ -30,6 +30,9 @@ int spiht_launch_metadata(const MetaArgs *a, uint32_t *keys_in, uint32_t *vals_i
                           void *temp, size_t temp_bytes, hipStream_t st);
 int spiht_launch_budget_fold(const MetaArgs *a, uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
                              void *temp, size_t temp_bytes, const uint64_t *d_budgets, int K, int32_t *d_out, hipStream_t st);
+int spiht_meta_batch_sort_temp_bytes(const MetaBatchArgs *a, size_t *bytes);
+int spiht_launch_metadata_batch(const MetaBatchArgs *a, uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_out,
+                                uint32_t *vals_out, void *temp, size_t temp_bytes, hipStream_t st);
 int spiht_launch_nbits_to_nbytes(const uint64_t *d_nbits, int B, uint64_t *d_nbytes, hipStream_t st);
 int spiht_launch_color3(const double *d_in, double *d_out, int B, size_t npix, const double *A, const double *M, double p,
                         hipStream_t st);
@@ -115,6 +118,7 @@ struct spiht_ctx {
     int opt_wide_solo = 24576;  // list entries up to which a plane stays with workgroup 0 (4 k ... 64 k measured the same)
     int opt_wide_g = 0;         // workgroups per image of that encoder (0: by the size of the image)
     int opt_wide_encode = 1;    // few images per call: one image on several CUs (2: whatever the image's size -- tests)
+    int64_t opt_meta_chunk = 0; // batched decode_with_metadata: images per chunk at most (0: by the scratch bound)
     int wide_per_cu = -1;       // workgroups of k_encode_wide a CU holds (occupancy query, once; 0: unknown -> one)
     std::vector<WideCtl> wide_forced;  // opt_wide_encode == 3 (tests): control blocks that say "gave up" before the launch
     int wide_last_groups = 0;   // groups of the last several-CUs-per-image launch (spiht_ctx_wide_stats)
@@ -848,8 +852,8 @@ static int tree_generations(const Geom &g) {
     return best;
 }
 
-// The decoder's trace of one stream and the sort behind it, in ctx->trace: ent[rows] u32 | 4 x u32[rows] sort buffers |
-// act[rows] u8 | in_bytes of the caller's own input | sort temp.  rows: one per bit of the nbytes stream, and one more.
+// The decoder's trace and the sort behind it, in ctx->trace: ent[rows] u32 | 4 x u32[rows] sort buffers | act[rows] u8 |
+// in_bytes of the caller's own input | sort temp.  One stream: rows = one per bit of the nbytes stream, and one more.
 struct TraceScratch {
     uint64_t rows;
     uint32_t *ent, *k0, *v0, *k1, *v1;
@@ -870,9 +874,9 @@ struct TraceScratch {
         return ma;
     }
 };
-static int trace_scratch(spiht_ctx *ctx, uint64_t nbytes, size_t in_bytes, TraceScratch *t) {
-    t->rows = nbytes * 8 + 1;
-    if (spiht_meta_sort_temp_bytes(t->rows, &t->tmp_bytes) != 0) return SPIHT_ERR_INTERNAL;
+static int trace_layout(spiht_ctx *ctx, uint64_t rows, size_t tmp_bytes, size_t in_bytes, TraceScratch *t) {
+    t->rows = rows;
+    t->tmp_bytes = tmp_bytes;
     const size_t r4 = align256(t->rows * 4), o_act = 5 * r4, o_in = o_act + align256(t->rows), o_tmp = o_in + align256(in_bytes);
     CHK(ensure(ctx, ctx->trace, o_tmp + align256(t->tmp_bytes)));
     char *tb = (char *)ctx->trace.p;
@@ -884,6 +888,26 @@ static int trace_scratch(spiht_ctx *ctx, uint64_t nbytes, size_t in_bytes, Trace
     t->act = (uint8_t *)(tb + o_act);
     t->in = tb + o_in;
     t->tmp = tb + o_tmp;
+    return SPIHT_OK;
+}
+static int trace_scratch(spiht_ctx *ctx, uint64_t nbytes, size_t in_bytes, TraceScratch *t) {
+    size_t tmp_bytes = 0;
+    if (spiht_meta_sort_temp_bytes(nbytes * 8 + 1, &tmp_bytes) != 0) return SPIHT_ERR_INTERNAL;
+    return trace_layout(ctx, nbytes * 8 + 1, tmp_bytes, in_bytes, t);
+}
+
+// top_slice / other_slices of decode_with_metadata as int32 {top[4], [level][3][4]}: a value outside [0, 2^31) is
+// SPIHT_ERR_ARG, a reversed slice SPIHT_ERR_SHAPE (usize underflow in end - start, encoder_decoder.rs:606-608)
+static int meta_slices(const int64_t *top_slice, const int64_t *other_slices, int64_t level, std::vector<int32_t> *out) {
+    std::vector<int32_t> &sl = *out;
+    sl.resize(4 + (size_t)level * 12);
+    for (size_t t = 0; t < sl.size(); t++) {
+        const int64_t v = t < 4 ? top_slice[t] : other_slices[t - 4];
+        if (v < 0 || v > 0x7FFFFFFF) return SPIHT_ERR_ARG;
+        sl[t] = (int32_t)v;
+    }
+    for (size_t t = 4; t < sl.size(); t += 4)
+        if (sl[t + 1] < sl[t] || sl[t + 3] < sl[t + 2]) return SPIHT_ERR_SHAPE;
     return SPIHT_OK;
 }
 
@@ -898,14 +922,8 @@ extern "C" int spiht_decode_with_metadata_i32(spiht_ctx *ctx, const uint8_t *dat
     if (n > 30) return SPIHT_ERR_MAGNITUDE;
     if (nbytes * 8 >= 0xFFFFFF00ull) return SPIHT_ERR_TOO_LARGE;
     if (level > 255 || tree_generations(g) > level) return SPIHT_ERR_SHAPE;  // other_slices[depth_i] out of bounds (:603)
-    std::vector<int32_t> sl(4 + (size_t)level * 12);
-    for (size_t t = 0; t < sl.size(); t++) {
-        const int64_t v = t < 4 ? top_slice[t] : other_slices[t - 4];
-        if (v < 0 || v > 0x7FFFFFFF) return SPIHT_ERR_ARG;
-        sl[t] = (int32_t)v;
-    }
-    for (size_t t = 4; t < sl.size(); t += 4)
-        if (sl[t + 1] < sl[t] || sl[t + 3] < sl[t + 2]) return SPIHT_ERR_SHAPE;  // usize underflow in end - start (:606-608)
+    std::vector<int32_t> sl;
+    CHK(meta_slices(top_slice, other_slices, level, &sl));
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     TraceScratch tr;
@@ -1032,6 +1050,72 @@ extern "C" int spiht_decode_batch_i32(spiht_ctx *ctx, const uint8_t *d_data, uin
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     CHK(decode_device(ctx, g, d_data, slot_stride, d_nbytes, d_max_n, (int)B, d_out));
+    return SPIHT_OK;  // asynchronous: errors surface in spiht_ctx_synchronize()
+}
+
+// decode_with_metadata of B device-resident streams.  In chunks of images: per chunk the traced decode of every image (trace
+// of image b at b * tr_stride), then the rows, the sort and the fold of metadata.hip over the chunk.  The chunk's trace and
+// sort buffers (21 bytes per record) stay within META_CHUNK_BYTES unless one image alone needs more; the keys b * n + node
+// (or the record indices) stay 32-bit.  The slices go to the kernels by value: nothing is read from the host afterwards.
+#define META_CHUNK_BYTES ((size_t)2 << 30)
+extern "C" int spiht_decode_with_metadata_batch_i32(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                                    const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                                    int64_t h, int64_t w, int64_t ll_h, int64_t ll_w, const int64_t *top_slice,
+                                                    const int64_t *other_slices, int64_t level, int32_t *d_out, int32_t *d_meta,
+                                                    uint64_t meta_rows) {
+    if (!ctx || !d_data || !d_nbytes || !d_max_n || !d_meta || B < 0 || !top_slice || level < 0 || (level > 0 && !other_slices))
+        return SPIHT_ERR_ARG;
+    Geom g;
+    CHK(make_geom(c, h, w, ll_h, ll_w, &g));
+    if (g.n >= (1u << 28)) return SPIHT_ERR_TOO_LARGE;  // list entries carry the filter in bits 28-29
+    if (slot_stride % 4 != 0) return SPIHT_ERR_ARG;
+    if (slot_stride >= (1ull << 28)) return SPIHT_ERR_TOO_LARGE;  // a chunk's record indices are 32-bit (and under 2^31)
+    const uint64_t tr_stride = 8 * slot_stride + 1;
+    if (meta_rows < tr_stride) return SPIHT_ERR_ARG;
+    if (level > 255 || tree_generations(g) > level) return SPIHT_ERR_SHAPE;  // other_slices[depth_i] out of bounds (:603)
+    std::vector<int32_t> sl;
+    CHK(meta_slices(top_slice, other_slices, level, &sl));
+    if (B == 0) return SPIHT_OK;
+    MetaBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g = g;
+    a.level = (int32_t)level;
+    a.tr_stride = (uint32_t)std::max<uint64_t>(tr_stride, 2);  // (FastDiv divides by 2 or more)
+    a.div_tr = fastdiv_make(a.tr_stride);
+    a.slot_stride = slot_stride;
+    a.meta_rows = meta_rows;
+    // the kernels read the levels the tree reaches (tree_generations <= 28 when n < 2^28)
+    memcpy(a.slices, sl.data(), std::min<size_t>(sl.size(), 4 + 12 * META_MAX_GEN) * 4);
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    int64_t chunk = 65535 / c;                                             // the decoder's slots, the kernels' grid.y
+    chunk = std::min<int64_t>(chunk, (int64_t)(0x80000000ull / a.tr_stride));  // record indices
+    chunk = std::min<int64_t>(chunk, (int64_t)(0xFFFFFFFFull / g.n));          // keys b * n + node, and nb * n for "none"
+    chunk = std::min<int64_t>(chunk, (int64_t)std::max<size_t>(1, META_CHUNK_BYTES / ((size_t)a.tr_stride * 21)));
+    if (ctx->opt_meta_chunk > 0) chunk = std::min<int64_t>(chunk, ctx->opt_meta_chunk);
+    chunk = std::max<int64_t>(chunk, 1);
+    if (!d_out) CHK(ensure(ctx, ctx->rec, (size_t)std::min<int64_t>(chunk, B) * g.n * 4));
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = (int)std::min<int64_t>(chunk, B - b0);
+        a.nb = nb;
+        a.key_none = (uint32_t)nb * g.n;
+        size_t tmp_bytes = 0;
+        if (spiht_meta_batch_sort_temp_bytes(&a, &tmp_bytes) != 0) return SPIHT_ERR_INTERNAL;
+        TraceScratch tr;
+        CHK(trace_layout(ctx, (uint64_t)nb * a.tr_stride, tmp_bytes, 0, &tr));
+        HIPCHK(hipMemsetAsync(tr.act, TR_NONE, tr.rows, ctx->stream));
+        const uint8_t *data = d_data + (size_t)b0 * slot_stride;
+        int32_t *rec = d_out ? d_out + (size_t)b0 * g.n : (int32_t *)ctx->rec.p;
+        CHK(decode_device(ctx, g, data, slot_stride, d_nbytes + b0, d_max_n + b0, nb, rec, tr.ent, tr.act, a.tr_stride));
+        a.tr_ent = tr.ent;
+        a.tr_act = tr.act;
+        a.data = data;
+        a.nbytes = d_nbytes + b0;
+        a.meta = d_meta + (size_t)b0 * meta_rows * 8;
+        a.skey = tr.k1;
+        a.spos = tr.v1;
+        LAUNCHCHK(spiht_launch_metadata_batch(&a, tr.k0, tr.v0, tr.k1, tr.v1, tr.tmp, tr.tmp_bytes, ctx->stream));
+    }
     return SPIHT_OK;  // asynchronous: errors surface in spiht_ctx_synchronize()
 }
 
@@ -2056,6 +2140,7 @@ extern "C" int spiht_ctx_set_option(spiht_ctx *ctx, const char *name, int64_t va
     else if (!strcmp(name, "wide_groups") && value <= 256) ctx->opt_wide_g = (int)value;
     else if (!strcmp(name, "wide_solo") && value <= (1 << 30)) ctx->opt_wide_solo = (int)value;
     else if (!strcmp(name, "pads_persist") && b01) ctx->opt_pads_persist = value != 0;
+    else if (!strcmp(name, "meta_chunk") && value <= 65535) ctx->opt_meta_chunk = value;
     else return SPIHT_ERR_ARG;
     return SPIHT_OK;
 }
@@ -2068,6 +2153,7 @@ extern "C" int spiht_ctx_get_option(spiht_ctx *ctx, const char *name, int64_t *v
     else if (!strcmp(name, "wide_groups")) *value = ctx->opt_wide_g;
     else if (!strcmp(name, "wide_solo")) *value = ctx->opt_wide_solo;
     else if (!strcmp(name, "pads_persist")) *value = ctx->opt_pads_persist;
+    else if (!strcmp(name, "meta_chunk")) *value = ctx->opt_meta_chunk;
     else if (!strcmp(name, "num_cu")) *value = ctx->num_cu;                    // (read-only: what the device reports)
     else if (!strcmp(name, "lds_per_cu")) *value = ctx->tilectr.lds_per_cu;
     else return SPIHT_ERR_ARG;

@@ -157,6 +157,31 @@ struct MetaArgs {
     const uint32_t *spos;     // record position, sorted by (node index, position)
 };
 
+// The batched form (k_meta_keys_batch / k_meta_rows_batch / k_meta_fold_batch, metadata.hip): a chunk of nb images whose
+// traces lie at b * tr_stride.  The slices travel by value (the call stays asynchronous and never reads the caller's host
+// arrays later); only the levels the tree reaches are read, and a tree has at most META_MAX_GEN generations (n < 2^28).
+#define META_MAX_GEN 32
+struct MetaBatchArgs {
+    Geom g;
+    int32_t level;            // number of detail levels (Slices.other_slices.len())
+    int32_t nb;               // images in the chunk
+    uint32_t tr_stride;       // records per image (8 * slot_stride + 1 or more); nb * tr_stride <= 2^31
+    uint32_t pad0;
+    FastDiv div_tr;           // record index -> image
+    uint64_t slot_stride;     // bytes per stream slot
+    uint64_t meta_rows;       // rows per image of meta (>= tr_stride)
+    uint32_t key_none;        // nb * n: the sort key of positions without an operation (keys b * n + node below it)
+    uint32_t pad;
+    const uint32_t *tr_ent;   // [nb, tr_stride]
+    const uint8_t *tr_act;    // [nb, tr_stride]
+    const uint8_t *data;      // [nb, slot_stride] stream bytes
+    const uint64_t *nbytes;   // [nb] valid bytes per slot (more than slot_stride: the decoder reads none)
+    int32_t *meta;            // [nb, meta_rows, 8]
+    const uint32_t *skey;     // sorted keys b * n + node (fold)
+    const uint32_t *spos;     // record index b * tr_stride + position, sorted by (image, node, position)
+    int32_t slices[4 + 12 * META_MAX_GEN];  // top {start_i,end_i,start_j,end_j}, then [generation - 1][3][4]
+};
+
 struct PyrArgs {
     Geom g;
     int32_t B;

@@ -5,7 +5,8 @@ Same names, argument meaning and return types:
     decode(data_u8, n, c, h, w, ll_h, ll_w) -> ndarray[int32, (c,h,w)]    lib.rs:35-42
     decode_with_metadata(data_u8, n, c, h, w, ll_h, ll_w, top_slice, other_slices)
         -> (ndarray[int32, (c,h,w)], ndarray[int32, (8*len+1, 8)])        lib.rs:47-56
-All three run on the GPU through libspiht_hip.so; there is no CPU path.
+All three run on the GPU through libspiht_hip.so; there is no CPU path.  New here: decode_budgets (many prefixes of one
+stream from one walk) and decode_with_metadata_batch (many streams in one batched call).
 """
 import ctypes as C
 
@@ -155,9 +156,34 @@ def decode_with_metadata(data_u8, n, c, h, w, ll_h, ll_w, top_slice, other_slice
     reads stream bit t: [action 0..6, local_h, local_w, channel, filter, depth, n, current coefficient value]
     (doc comment encoder_decoder.rs:616-630)."""
     buf = _as_u8_vec(data_u8)
+    n = _as_n(n)
+    c, h, w, ll_h, ll_w, topv, oth, level = _metadata_args(c, h, w, ll_h, ll_w, top_slice, other_slices)
+    rows = 8 * buf.size + 1
+    if c == 0:
+        return np.zeros((c, h, w), dtype=np.int32), np.zeros((rows, 8), dtype=np.int32)
+    if h == 0 or w == 0:
+        raise PanicException("ndarray: index out of bounds")  # the first metadata row reads rec_arr[(0,0,0)] (:683)
+    ctx = _lib.default_context()
+    L = _lib.lib()
+    out = np.empty((c, h, w), dtype=np.int32)
+    meta = np.empty((rows, 8), dtype=np.int32)
+    st = L.spiht_decode_with_metadata_i32(ctx.handle, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, n, c, h, w,
+                                          ll_h, ll_w, C.c_void_p(topv.ctypes.data), C.c_void_p(oth.ctypes.data),
+                                          level, C.c_void_p(out.ctypes.data), C.c_void_p(meta.ctypes.data))
+    _lib.check(st)
+    return out, meta
+
+
+def _as_n(n):
     n = _as_usize(n, "n")
     if n > 255:
         raise OverflowError("out of range integral type conversion attempted")
+    return n
+
+
+def _metadata_args(c, h, w, ll_h, ll_w, top_slice, other_slices):
+    """the checks of decode_with_metadata after the stream's, in its order -> (c, h, w, ll_h, ll_w, top_slice int64 [4],
+    other_slices int64 [level * 12] (one element when empty), level)"""
     c, h, w = _as_usize(c, "c"), _as_usize(h, "h"), _as_usize(w, "w")
     ll_h, ll_w = _as_usize(ll_h, "ll_h"), _as_usize(ll_w, "ll_w")
     top = _as_pairs(top_slice, "top_slice", 2)                      # Slices::from_vec indexes [0] and [1] (:518-523)
@@ -169,20 +195,50 @@ def decode_with_metadata(data_u8, n, c, h, w, ll_h, ll_w, top_slice, other_slice
         levels.append(fl)
     if ll_h <= 1 or ll_w <= 1:
         raise PanicException("assertion failed: ll_h > 1")
-    rows = 8 * buf.size + 1
-    if c == 0:
-        return np.zeros((c, h, w), dtype=np.int32), np.zeros((rows, 8), dtype=np.int32)
-    if h == 0 or w == 0:
-        raise PanicException("ndarray: index out of bounds")  # the first metadata row reads rec_arr[(0,0,0)] (:683)
     topv = np.array([top[0][0], top[0][1], top[1][0], top[1][1]], dtype=np.int64)
     oth = np.array([[[f[0][0], f[0][1], f[1][0], f[1][1]] for f in lv[:3]] for lv in levels], dtype=np.int64).reshape(-1)
     oth = np.ascontiguousarray(oth if oth.size else np.zeros(1, dtype=np.int64))
+    return c, h, w, ll_h, ll_w, topv, oth, len(levels)
+
+
+def decode_with_metadata_batch(streams, max_ns, c, h, w, ll_h, ll_w, top_slice, other_slices):
+    """decode_with_metadata of many streams of one geometry in one batched call on the device (new in this library:
+    spiht_decode_with_metadata_batch_i32).  streams: sequence of byte strings (anything decode_with_metadata takes);
+    max_ns: their n.  Returns (rec int32 (B, c, h, w), [metadata_b]) with rec[b], metadata_b == decode_with_metadata(
+    streams[b], max_ns[b], c, h, w, ll_h, ll_w, top_slice, other_slices); metadata_b is C-contiguous (8*len(streams[b])+1, 8).
+    The argument checks are those of decode_with_metadata, made once; ValueError when len(streams) != len(max_ns)."""
+    bufs = [_as_u8_vec(d) for d in streams]
+    ns = [_as_n(n) for n in max_ns]
+    if len(bufs) != len(ns):
+        raise ValueError("decode_with_metadata_batch: %d streams but %d max_ns" % (len(bufs), len(ns)))
+    c, h, w, ll_h, ll_w, topv, oth, level = _metadata_args(c, h, w, ll_h, ll_w, top_slice, other_slices)
+    B = len(bufs)
+    if c == 0:
+        return np.zeros((B, c, h, w), dtype=np.int32), [np.zeros((8 * b.size + 1, 8), dtype=np.int32) for b in bufs]
+    if h == 0 or w == 0:
+        raise PanicException("ndarray: index out of bounds")  # the first metadata row reads rec_arr[(0,0,0)] (:683)
+    if B == 0:
+        return np.zeros((0, c, h, w), dtype=np.int32), []
+    from .batch import DeviceArray
+    stride = max(4, (max(b.size for b in bufs) + 3) & ~3)
+    data = np.zeros((B, stride), dtype=np.uint8)
+    for b, buf in enumerate(bufs):
+        data[b, :buf.size] = buf
+    meta_rows = 8 * stride + 1
     ctx = _lib.default_context()
-    L = _lib.lib()
-    out = np.empty((c, h, w), dtype=np.int32)
-    meta = np.empty((rows, 8), dtype=np.int32)
-    st = L.spiht_decode_with_metadata_i32(ctx.handle, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, n, c, h, w,
-                                          ll_h, ll_w, C.c_void_p(topv.ctypes.data), C.c_void_p(oth.ctypes.data),
-                                          len(levels), C.c_void_p(out.ctypes.data), C.c_void_p(meta.ctypes.data))
-    _lib.check(st)
-    return out, meta
+    d = [DeviceArray(ctx, (B, stride), np.uint8), DeviceArray(ctx, (B,), np.uint64), DeviceArray(ctx, (B,), np.uint8),
+         DeviceArray(ctx, (B, c, h, w), np.int32), DeviceArray(ctx, (B, meta_rows, 8), np.int32)]
+    try:
+        d[0].upload(data)
+        d[1].upload(np.array([b.size for b in bufs], dtype=np.uint64))
+        d[2].upload(np.array(ns, dtype=np.uint8))
+        _lib.check(_lib.lib().spiht_decode_with_metadata_batch_i32(
+            ctx.handle, C.c_void_p(d[0].ptr), stride, C.c_void_p(d[1].ptr), C.c_void_p(d[2].ptr), B, c, h, w, ll_h, ll_w,
+            C.c_void_p(topv.ctypes.data), C.c_void_p(oth.ctypes.data), level, C.c_void_p(d[3].ptr), C.c_void_p(d[4].ptr),
+            meta_rows))
+        ctx.synchronize()
+        rec, meta = d[3].download(), d[4].download()
+    finally:
+        for x in d:
+            x.free()
+    return rec, [meta[b, :8 * buf.size + 1] for b, buf in enumerate(bufs)]

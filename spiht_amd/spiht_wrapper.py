@@ -302,6 +302,25 @@ def _band_sizes(h, w, wavelet, levels, mode="reflect"):
     return hs, ws
 
 
+def _metadata_boxes(h, w, spiht_settings, g):
+    """The boxes of the sub-bands inside the packed array of an h x w picture of geometry g (_geometry), as (start, end)
+    pairs per axis: the root block, then per level (coarsest first) the filters in the order the reference hands them
+    over, 'da', 'ad', 'dd' (wrapper:240) -> (top_slice, other_slices) of decode_with_metadata.  (The reference reads them
+    off pywt's slice objects, whose `start` is None on the approximation side -- which PyO3 refuses, wrapper:242-245; here
+    they come from the band sizes, so every start is a number.)"""
+    hs, ws = _band_sizes(h, w, spiht_settings.wavelet, g["level"], spiht_settings.mode)
+    top_box = [(0, g["ll_h"]), (0, g["ll_w"])]
+    level_boxes = []
+    row0, col0 = g["ll_h"], g["ll_w"]  # where the detail blocks of the level start
+    for lv in range(g["level"], 0, -1):
+        rows, cols = (row0, row0 + hs[lv]), (col0, col0 + ws[lv])
+        level_boxes.append([[rows, (0, ws[lv])],     # 'da': below the approximation
+                            [(0, hs[lv]), cols],     # 'ad': right of it
+                            [rows, cols]])           # 'dd': diagonal
+        row0, col0 = rows[1], cols[1]
+    return top_box, level_boxes
+
+
 def decode_rec_array(encoding_result: EncodingResult, spiht_settings: SpihtSettings, return_metadata: bool = False):
     """wrapper:218-257: stream -> int32 coefficient array (+ the coder's per-bit metadata)."""
     if encoding_result._encoding_version != ENCODER_DECODER_VERSION:
@@ -314,20 +333,7 @@ def decode_rec_array(encoding_result: EncodingResult, spiht_settings: SpihtSetti
     if not return_metadata:
         rec_arr = spiht_rs.decode(er.encoded_bytes, er.max_n, er.c, enc_h, enc_w, g["ll_h"], g["ll_w"])
     else:
-        # The boxes of the sub-bands inside the packed array, as (start, end) pairs per axis: the root block, then per
-        # level (coarsest first) the filters in the order the reference hands them over, 'da', 'ad', 'dd' (wrapper:240).
-        # (The reference reads them off pywt's slice objects, whose `start` is None on the approximation side -- which
-        # PyO3 refuses, wrapper:242-245; here they come from the band sizes, so every start is a number.)
-        hs, ws = _band_sizes(er.h, er.w, spiht_settings.wavelet, g["level"], spiht_settings.mode)
-        top_box = [(0, g["ll_h"]), (0, g["ll_w"])]
-        level_boxes = []
-        row0, col0 = g["ll_h"], g["ll_w"]  # where the detail blocks of the level start
-        for lv in range(g["level"], 0, -1):
-            rows, cols = (row0, row0 + hs[lv]), (col0, col0 + ws[lv])
-            level_boxes.append([[rows, (0, ws[lv])],     # 'da': below the approximation
-                                [(0, hs[lv]), cols],     # 'ad': right of it
-                                [rows, cols]])           # 'dd': diagonal
-            row0, col0 = rows[1], cols[1]
+        top_box, level_boxes = _metadata_boxes(er.h, er.w, spiht_settings, g)
         rec_arr, spiht_metadata = spiht_rs.decode_with_metadata(er.encoded_bytes, er.max_n, er.c, enc_h, enc_w, g["ll_h"],
                                                                 g["ll_w"], top_box, level_boxes)
     return dict(rec_arr=rec_arr, slices=slices, spiht_metadata=spiht_metadata, h=er.h, w=er.w, level=er.level)
