@@ -48,7 +48,8 @@ typedef struct spiht_ctx spiht_ctx;
 const char *spiht_strerror(int status);
 const char *spiht_last_hip_error(void);
 /* ABI version of this header; bumped on any signature change and on every round that adds entry points (now 2).  The
- * 8-bit pixel entry points (*_u8) are additions only -- no existing signature changed -- and the version stays at 2. */
+ * 8-bit and 16-bit pixel entry points (*_u8, *_u16) are additions only -- no existing signature changed -- and the version
+ * stays at 2. */
 int spiht_abi_version(void);
 
 /* One context per (process, GPU): device id, streams, scratch.  Thread-safe per context
@@ -217,19 +218,37 @@ int spiht_decode_image_batch_f64(spiht_ctx *ctx, const uint8_t *d_data, uint64_t
  *   decode: the float64 result v is stored as (uint8)(clip(v, 0, 1) * 255.0), truncated, CROPPED to H x W (the float64
  *           decode's rec_H x rec_W is one longer on an odd axis); NaN is stored as 0.
  * Level 1 of the transforms reads / writes the bytes itself; level 0 and the two-pass levels convert through a float64
- * pass of their own. */
+ * pass of their own.
+ *
+ * 16-bit pixels (*_u16): the same rules for a uint16 batch (native byte order) with 65535 in place of 255 -- sample k is
+ * coded as the double k / 65535.0, a result v is stored as (uint16)(clip(v, 0, 1) * 65535.0), truncated, NaN as 0.  The
+ * strides are still BYTE strides (numpy's .strides as they are); in addition every stride must be a multiple of 2 and
+ * the base pointer 2-byte aligned, and the overlap rule of an output view counts the sample's two bytes: every dimension
+ * longer than one must step past the last byte the smaller ones reach.  Interleaved HWC is sc = 2, sw = 2c; a 16-bit
+ * RGBA buffer is c = 3, sw = 8.  A stream does not record the pixel format it came from: any stream decodes into any
+ * format.  Each *_u16 call below is its *_u8 sibling in everything else: statuses, asynchrony, chunking. */
 /* The rule above on its own (no device work, no context): SPIHT_OK or SPIHT_ERR_ARG for the strides[4] of a [B, c, H, W]
  * view that is read (output 0) or written (output 1). */
 int spiht_check_view_u8(int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output);
+int spiht_check_view_u16(int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output);
 int spiht_encode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t B, int64_t c,
                                 int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                 const double *channel_mults, uint64_t max_bits, uint8_t *d_out, uint64_t slot_stride,
                                 uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs);
+int spiht_encode_image_batch_u16(spiht_ctx *ctx, const uint16_t *d_img, const int64_t *strides, int64_t B, int64_t c,
+                                 int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                 const double *channel_mults, uint64_t max_bits, uint8_t *d_out, uint64_t slot_stride,
+                                 uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs);
 int spiht_decode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
                                 const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H,
                                 int64_t W, int wavelet, int mode, int level, double q_scale,
                                 const double *channel_mults, uint8_t *d_img_out, const int64_t *out_strides,
                                 int32_t *d_rec);
+int spiht_decode_image_batch_u16(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                 const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H,
+                                 int64_t W, int wavelet, int mode, int level, double q_scale,
+                                 const double *channel_mults, uint16_t *d_img_out, const int64_t *out_strides,
+                                 int32_t *d_rec);
 
 /* DWT halves on their own (device pointers), for parity tests and profiling:
  * forward: float64 [B,c,H,W] -> int32 [B,c,enc_h,enc_w] (quantised, zero padded)  (wrapper:163-172)
@@ -282,10 +301,13 @@ int spiht_pyramid_batch_i32(spiht_ctx *ctx, const int32_t *d_x, int64_t B, int64
 int spiht_dwt_pyramid_batch_f64(spiht_ctx *ctx, const double *d_img, int64_t B, int64_t c, int64_t H, int64_t W,
                                 int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                                 int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb, uint32_t *d_maxabs);
-/* ... of 8-bit pictures (strides[4] as spiht_encode_image_batch_u8) */
+/* ... of 8-bit / 16-bit pictures (strides[4] as spiht_encode_image_batch_u8 / _u16) */
 int spiht_dwt_pyramid_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t B, int64_t c, int64_t H,
                                int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                                int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb, uint32_t *d_maxabs);
+int spiht_dwt_pyramid_batch_u16(spiht_ctx *ctx, const uint16_t *d_img, const int64_t *strides, int64_t B, int64_t c, int64_t H,
+                                int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb, uint32_t *d_maxabs);
 int spiht_encode_lists_batch_i32(spiht_ctx *ctx, const int32_t *d_x, const uint8_t *d_dmsb, const uint8_t *d_lmsb,
                                  const uint32_t *d_maxabs, int64_t B, int64_t c, int64_t h, int64_t w, int64_t ll_h,
                                  int64_t ll_w, uint64_t max_bits, uint8_t *d_out, uint64_t slot_stride,
@@ -313,10 +335,13 @@ int spiht_decode_lists_flags_batch_i32(spiht_ctx *ctx, const uint8_t *d_data, ui
 int spiht_dequant_idwt_flags_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B, int64_t c,
                                        int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                        const double *channel_mults, double *d_img_out);
-/* ... into 8-bit pictures (out_strides[4] and the crop as spiht_decode_image_batch_u8) */
+/* ... into 8-bit / 16-bit pictures (out_strides[4] and the crop as spiht_decode_image_batch_u8 / _u16) */
 int spiht_dequant_idwt_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B, int64_t c,
                                       int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                       const double *channel_mults, uint8_t *d_img_out, const int64_t *out_strides);
+int spiht_dequant_idwt_flags_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B, int64_t c,
+                                       int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                       const double *channel_mults, uint16_t *d_img_out, const int64_t *out_strides);
 /* Switches of this library's own making; the results are the same bits whatever they are set to.  "l1_flags" (default 1):
  * the occupancy words above inside the image-level decode calls; "pads_persist" (default 0): the caller promises that a
  * coefficient array this context's forward transform has filled is not written by anyone else before the same context
@@ -356,10 +381,13 @@ int spiht_idwt_approx_shape(int64_t H, int64_t W, int wavelet, int level, int64_
 int spiht_idwt_level1_flags_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
                                       int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                       const double *channel_mults, double *d_img_out);
-/* ... into 8-bit pictures (out_strides[4] and the crop as spiht_decode_image_batch_u8) */
+/* ... into 8-bit / 16-bit pictures (out_strides[4] and the crop as spiht_decode_image_batch_u8 / _u16) */
 int spiht_idwt_level1_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
                                      int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                      const double *channel_mults, uint8_t *d_img_out, const int64_t *out_strides);
+int spiht_idwt_level1_flags_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                      int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                      const double *channel_mults, uint16_t *d_img_out, const int64_t *out_strides);
 
 /* Colour model change on the device (the reference converts on the host through colour-science, color_models.py:6-13,
  * called from spiht_wrapper.py:158-160 and :278-279): B three-channel float64 images [B,3,npix]; per pixel
@@ -429,15 +457,21 @@ int spiht_decode_image_host_f64(spiht_ctx *ctx, const uint8_t *data, uint64_t nb
                                 double *img_out);
 int spiht_dequant_idwt_host_f64(spiht_ctx *ctx, const int32_t *rec, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
                                 int level, double q_scale, const double *channel_mults, double *img_out);
-/* 8-bit pixels on the host (see the *_u8 batch calls): strides[3] = (sc, sh, sw) in bytes, NULL = dense CHW.  Encode
- * uploads only the bytes the strides span (an RGBA buffer's first three channels need no host copy).  Decode writes
+/* 8-bit and 16-bit pixels on the host (see the *_u8 / *_u16 batch calls): strides[3] = (sc, sh, sw) in bytes, NULL =
+ * dense CHW.  Encode uploads only the bytes the strides span (an RGBA buffer's first three channels need no host copy).  Decode writes
  * img_out cropped to c x H x W, which must be dense CHW or dense HWC (anything else: SPIHT_ERR_ARG). */
 int spiht_encode_image_host_u8(spiht_ctx *ctx, const uint8_t *img, const int64_t *strides, int64_t c, int64_t H, int64_t W,
                                int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                                uint64_t max_bits, uint8_t *out, uint64_t out_cap, uint64_t *out_nbits, uint8_t *max_n);
+int spiht_encode_image_host_u16(spiht_ctx *ctx, const uint16_t *img, const int64_t *strides, int64_t c, int64_t H, int64_t W,
+                                int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                uint64_t max_bits, uint8_t *out, uint64_t out_cap, uint64_t *out_nbits, uint8_t *max_n);
 int spiht_decode_image_host_u8(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H,
                                int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                                uint8_t *img_out, const int64_t *strides);
+int spiht_decode_image_host_u16(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H,
+                                int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                uint16_t *img_out, const int64_t *strides);
 
 /* ---------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, every rank codes its own images (the reference's encode / decode
@@ -511,10 +545,12 @@ int spiht_pipeline_set_color3(spiht_pipeline *p, const double *A_f, const double
                               const double *M_i, double p_i);
 int spiht_pipeline_submit(spiht_pipeline *p, const double *d_img, uint8_t *d_out, uint64_t *d_nbits, uint8_t *d_max_n,
                           double *d_img_out);
-/* ... with 8-bit pictures in and out (the *_u8 batch calls: strides[4] in bytes, NULL = dense CHW; the output cropped to
- * H x W).  Every step keeps its own output form: float64 and 8-bit steps may alternate on one pipeline. */
+/* ... with 8-bit or 16-bit pictures in and out (the *_u8 / *_u16 batch calls: strides[4] in bytes, NULL = dense CHW; the
+ * output cropped to H x W).  Every step keeps its own output form: float64, 8-bit and 16-bit steps may alternate on one pipeline. */
 int spiht_pipeline_submit_u8(spiht_pipeline *p, const uint8_t *d_img, const int64_t *in_strides, uint8_t *d_out,
                              uint64_t *d_nbits, uint8_t *d_max_n, uint8_t *d_img_out, const int64_t *out_strides);
+int spiht_pipeline_submit_u16(spiht_pipeline *p, const uint16_t *d_img, const int64_t *in_strides, uint8_t *d_out,
+                              uint64_t *d_nbits, uint8_t *d_max_n, uint16_t *d_img_out, const int64_t *out_strides);
 int spiht_pipeline_flush(spiht_pipeline *p);
 int spiht_pipeline_synchronize(spiht_pipeline *p);
 int spiht_pipeline_contexts(spiht_pipeline *p, spiht_ctx **h, spiht_ctx **l0, spiht_ctx **l1);

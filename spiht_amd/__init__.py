@@ -8,5 +8,6 @@ from . import _lib as _lib_mod
 _lib_mod.lib()  # fail at import time, not at first use, when the HIP library has not been built
 
 from .spiht_wrapper import (encode_image, decode_image, EncodingResult, SpihtSettings,  # noqa: E402,F401
-                            ENCODER_DECODER_VERSION, encode_image_u8, decode_image_u8)
+                            ENCODER_DECODER_VERSION, encode_image_u8, decode_image_u8,
+                            encode_image_u16, decode_image_u16)
 from .spiht import encode, decode  # noqa: E402,F401

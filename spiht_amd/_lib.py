@@ -54,6 +54,9 @@ SYMBOLS = [
     "spiht_encode_image_batch_u8", "spiht_decode_image_batch_u8", "spiht_encode_image_host_u8", "spiht_decode_image_host_u8",
     "spiht_dwt_pyramid_batch_u8", "spiht_dequant_idwt_flags_batch_u8", "spiht_idwt_level1_flags_batch_u8", "spiht_pipeline_submit_u8",
     "spiht_check_view_u8", "spiht_decode_with_metadata_batch_i32",
+    "spiht_encode_image_batch_u16", "spiht_decode_image_batch_u16", "spiht_encode_image_host_u16", "spiht_decode_image_host_u16",
+    "spiht_dwt_pyramid_batch_u16", "spiht_dequant_idwt_flags_batch_u16", "spiht_idwt_level1_flags_batch_u16", "spiht_pipeline_submit_u16",
+    "spiht_check_view_u16",
 ]
 
 
@@ -187,6 +190,11 @@ def lib():
         L.spiht_idwt_level1_flags_batch_u8.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp]
         L.spiht_pipeline_submit_u8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         L.spiht_check_view_u8.argtypes = [i64, i64, i64, i64, vp, i32]
+        # 16-bit pixels: every *_u16 call takes what its *_u8 sibling takes
+        for name in SYMBOLS:
+            if name.endswith("_u16"):
+                getattr(L, name).argtypes = getattr(L, name[:-2] + "8").argtypes
+                getattr(L, name).restype = getattr(L, name[:-2] + "8").restype
         L.spiht_ctx_lock.argtypes = [vp]
         L.spiht_ctx_unlock.argtypes = [vp]
         _lib = L

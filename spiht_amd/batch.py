@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib, color_models
 from . import spiht as spiht_rs
 from .spiht_wrapper import (EncodingResult, SpihtSettings, _geometry, _metadata_boxes, _mults_arg, _wavelet_mode_ids,
-                            check_u8_view)
+                            check_u8_view, _check_int_view, _check_aligned, _is_dtype)
 
 
 class DeviceArray:
@@ -138,55 +138,93 @@ class BatchCodec:
                     self.ctx.handle, C.c_void_p(rec), B, self.c, self.H, self.W, self.wid, self.mid, self._lv,
                     float(self.settings.quantization_scale), self._mults_p, C.c_void_p(d_img_out)))
 
-    # ---- 8-bit pixels (include/spiht_hip.h, *_u8): whatever pixel_dtype says, the float64 arithmetic on k / 255 ----------
-    def _u8_strides(self, B, strides, output):
-        """byte strides (sb, sc, sh, sw) of a [B, c, H, W] uint8 view as a ctypes argument (None: dense CHW)"""
+    # ---- 8- and 16-bit pixels (include/spiht_hip.h, *_u8 / *_u16): whatever pixel_dtype says, the float64 arithmetic on
+    # k / 255 (k / 65535).  One implementation by the element type; the public names pick it. -------------------------------
+    def _int_strides(self, B, strides, output, dtype=np.uint8):
+        """byte strides (sb, sc, sh, sw) of a [B, c, H, W] uint8 / uint16 view as a ctypes argument (None: dense CHW)"""
         if strides is None:
             return None, None
         st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
-        check_u8_view((int(B), self.c, self.H, self.W), st, output)
+        _check_int_view(8 * np.dtype(dtype).itemsize, (int(B), self.c, self.H, self.W), st, output)
         return st, C.c_void_p(st.ctypes.data)
 
-    def encode_device_u8(self, d_img, B, d_out, d_nbits, d_max_n, strides=None):
-        """d_img: uint8 [B, c, H, W] on the device, laid out by `strides` (bytes; None: dense CHW)"""
-        st, st_p = self._u8_strides(B, strides, False)
+    def _u8_strides(self, B, strides, output):
+        return self._int_strides(B, strides, output, np.uint8)
+
+    def _encode_device_int(self, dtype, d_img, B, d_out, d_nbits, d_max_n, strides):
+        st, st_p = self._int_strides(B, strides, False, dtype)
+        _check_aligned(d_img, dtype)
+        fn = self.L.spiht_encode_image_batch_u16 if np.dtype(dtype).itemsize == 2 else self.L.spiht_encode_image_batch_u8
         with self._color():
-            _lib.check(self.L.spiht_encode_image_batch_u8(
+            _lib.check(fn(
                 self.ctx.handle, C.c_void_p(d_img), st_p, int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
                 float(self.settings.quantization_scale), self._mults_p, self.max_bits, C.c_void_p(d_out), self.slot_stride,
                 C.c_void_p(d_nbits), C.c_void_p(d_max_n), None))
 
-    def decode_device_u8(self, d_data, d_nbytes, d_max_n, B, d_img_out, strides=None, d_rec=None, slot_stride=None):
-        """-> uint8 [B, c, H, W] on the device, cropped to H x W, laid out by `strides` (bytes; None: dense CHW; the bytes
-        between the view's elements -- an RGBA buffer's alpha, row padding -- are not written)"""
-        st, st_p = self._u8_strides(B, strides, True)
+    def _decode_device_int(self, dtype, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride):
+        st, st_p = self._int_strides(B, strides, True, dtype)
+        _check_aligned(d_img_out, dtype)
+        fn = self.L.spiht_decode_image_batch_u16 if np.dtype(dtype).itemsize == 2 else self.L.spiht_decode_image_batch_u8
         with self._color():
-            _lib.check(self.L.spiht_decode_image_batch_u8(
+            _lib.check(fn(
                 self.ctx.handle, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
                 C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
                 self.c, self.H, self.W, self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
                 C.c_void_p(d_img_out), st_p, C.c_void_p(d_rec) if d_rec else None))
 
+    def _encode_int(self, dtype, name, images, channels_last):
+        images = np.asarray(images)
+        if not _is_dtype(images, dtype) or images.ndim != 4:
+            raise ValueError("%s takes a %s array [B, c, H, W]" % (name, np.dtype(dtype).name))
+        if channels_last:
+            images = images.transpose(0, 3, 1, 2)
+        images = np.ascontiguousarray(images, dtype=np.dtype(dtype).newbyteorder("="))
+        if images.shape[1:] != (self.c, self.H, self.W):
+            raise ValueError("%s: pictures of shape %s, the codec's are %s" % (name, images.shape[1:], (self.c, self.H, self.W)))
+        return self._encode_host(images, lambda d_img, *a: self._encode_device_int(dtype, d_img, *a, None))
+
+    def _decode_int(self, dtype, results, channels_last):
+        c, H, W, es = self.c, self.H, self.W, np.dtype(dtype).itemsize
+        strides = (H * W * c * es, es, W * c * es, c * es) if channels_last else None
+        return self._decode_host(results, (H, W, c) if channels_last else (c, H, W), dtype,
+                                 lambda *a, slot_stride: self._decode_device_int(dtype, *a, strides, None, slot_stride))
+
+    def encode_device_u8(self, d_img, B, d_out, d_nbits, d_max_n, strides=None):
+        """d_img: uint8 [B, c, H, W] on the device, laid out by `strides` (bytes; None: dense CHW)"""
+        self._encode_device_int(np.uint8, d_img, B, d_out, d_nbits, d_max_n, strides)
+
+    def decode_device_u8(self, d_data, d_nbytes, d_max_n, B, d_img_out, strides=None, d_rec=None, slot_stride=None):
+        """-> uint8 [B, c, H, W] on the device, cropped to H x W, laid out by `strides` (bytes; None: dense CHW; the bytes
+        between the view's elements -- an RGBA buffer's alpha, row padding -- are not written)"""
+        self._decode_device_int(np.uint8, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride)
+
     def encode_u8(self, images, channels_last=False):
         """images: uint8 [B, c, H, W] (or [B, H, W, c] with channels_last) -> list of EncodingResult (those of
         encode(images / 255.0))"""
-        images = np.asarray(images)
-        if images.dtype != np.uint8 or images.ndim != 4:
-            raise ValueError("encode_u8 takes a uint8 array [B, c, H, W]")
-        if channels_last:
-            images = images.transpose(0, 3, 1, 2)
-        images = np.ascontiguousarray(images)
-        B = images.shape[0]
-        if images.shape[1:] != (self.c, self.H, self.W):
-            raise ValueError("encode_u8: pictures of shape %s, the codec's are %s" % (images.shape[1:], (self.c, self.H, self.W)))
-        return self._encode_host(images, self.encode_device_u8)
+        return self._encode_int(np.uint8, "encode_u8", images, channels_last)
 
     def decode_u8(self, results, channels_last=False):
         """list of EncodingResult (same geometry) -> uint8 [B, c, H, W] (or [B, H, W, c]), cropped to H x W"""
-        c, H, W = self.c, self.H, self.W
-        strides = (H * W * c, 1, W * c, c) if channels_last else None
-        return self._decode_host(results, (H, W, c) if channels_last else (c, H, W), np.uint8,
-                                 lambda *a, slot_stride: self.decode_device_u8(*a, strides=strides, slot_stride=slot_stride))
+        return self._decode_int(np.uint8, results, channels_last)
+
+    def encode_device_u16(self, d_img, B, d_out, d_nbits, d_max_n, strides=None):
+        """d_img: uint16 [B, c, H, W] on the device (native byte order, even address), laid out by `strides` (BYTES, all
+        even; None: dense CHW)"""
+        self._encode_device_int(np.uint16, d_img, B, d_out, d_nbits, d_max_n, strides)
+
+    def decode_device_u16(self, d_data, d_nbytes, d_max_n, B, d_img_out, strides=None, d_rec=None, slot_stride=None):
+        """-> uint16 [B, c, H, W] on the device, cropped to H x W, laid out by `strides` (BYTES, all even; None: dense CHW;
+        what lies between the view's elements -- a 16-bit RGBA buffer's alpha, row padding -- is not written)"""
+        self._decode_device_int(np.uint16, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride)
+
+    def encode_u16(self, images, channels_last=False):
+        """images: uint16 [B, c, H, W] (or [B, H, W, c] with channels_last) -> list of EncodingResult (those of
+        encode(images / 65535.0))"""
+        return self._encode_int(np.uint16, "encode_u16", images, channels_last)
+
+    def decode_u16(self, results, channels_last=False):
+        """list of EncodingResult (same geometry) -> uint16 [B, c, H, W] (or [B, H, W, c]), cropped to H x W"""
+        return self._decode_int(np.uint16, results, channels_last)
 
     def nbits_to_nbytes(self, d_nbits, B, d_nbytes):
         _lib.check(self.L.spiht_nbits_to_nbytes(self.ctx.handle, C.c_void_p(d_nbits), int(B), C.c_void_p(d_nbytes)))
@@ -356,14 +394,24 @@ class Pipeline:
             _lib.check(self.L.spiht_pipeline_submit_gather(self.handle, vp(d_img), vp(d_out), vp(d_nbits), vp(d_max_n), vp(d_img_out),
                                                            comm.handle, vp(gathered[0]), vp(gathered[1]), vp(gathered[2]), int(rank)))
 
+    def _submit_int(self, dtype, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides, out_strides):
+        vp = C.c_void_p
+        st_in, p_in = self.codec._int_strides(self.B, in_strides, False, dtype)
+        st_out, p_out = self.codec._int_strides(self.B, out_strides, True, dtype)
+        _check_aligned(d_img, dtype)
+        _check_aligned(d_img_out, dtype)
+        fn = self.L.spiht_pipeline_submit_u16 if np.dtype(dtype).itemsize == 2 else self.L.spiht_pipeline_submit_u8
+        _lib.check(fn(self.handle, vp(d_img), p_in, vp(d_out), vp(d_nbits), vp(d_max_n), vp(d_img_out), p_out))
+
     def submit_u8(self, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides=None, out_strides=None):
         """queue one step of 8-bit pictures (device pointers as ints): uint8 [B, c, H, W] in and out, laid out by byte strides
-        (None: dense CHW), the output cropped to H x W.  Float64 and 8-bit steps may alternate."""
-        vp = C.c_void_p
-        st_in, p_in = self.codec._u8_strides(self.B, in_strides, False)
-        st_out, p_out = self.codec._u8_strides(self.B, out_strides, True)
-        _lib.check(self.L.spiht_pipeline_submit_u8(self.handle, vp(d_img), p_in, vp(d_out), vp(d_nbits), vp(d_max_n),
-                                                   vp(d_img_out), p_out))
+        (None: dense CHW), the output cropped to H x W.  Float64, 8-bit and 16-bit steps may alternate."""
+        self._submit_int(np.uint8, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides, out_strides)
+
+    def submit_u16(self, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides=None, out_strides=None):
+        """queue one step of 16-bit pictures (device pointers as ints): uint16 [B, c, H, W] in and out, laid out by BYTE
+        strides (all even; None: dense CHW), the output cropped to H x W."""
+        self._submit_int(np.uint16, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides, out_strides)
 
     def flush(self):
         _lib.check(self.L.spiht_pipeline_flush(self.handle))

@@ -42,8 +42,8 @@ int spiht_launch_dwt_level_ext(const DwtKArgs *a, int planes, void *t_lo, void *
 int spiht_launch_idwt_level_per(const IdwtKArgs *a, int planes, double *t_lo, double *t_hi, const double *d_filt, int per,
                                 hipStream_t st);
 int spiht_launch_idwt_level(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc);
-int spiht_launch_u8_to_f64(const Px8 *px, int64_t B, double *out, hipStream_t st);
-int spiht_launch_f64_to_u8(const double *in, int rec_h, int rec_w, const Px8 *px, int64_t B, hipStream_t st);
+int spiht_launch_px_to_f64(const PxView *px, int64_t B, double *out, hipStream_t st);
+int spiht_launch_f64_to_px(const double *in, int rec_h, int rec_w, const PxView *px, int64_t B, hipStream_t st);
 int spiht_launch_quant_plain(const double *in, int32_t *out, size_t n_per_plane, int planes, int c, const double *mults,
                              double q, uint32_t *maxabs, hipStream_t st);
 int spiht_launch_zero_pads(int L, const int64_t *hs, const int64_t *ws, const int64_t *offh, const int64_t *offw, int enc_h,
@@ -100,8 +100,8 @@ struct spiht_ctx {
     DevBuf tilebuf;      // tile counters of the persistent inverse-transform kernel
     TileCtr tilectr = {nullptr, {0, 0, 0, 0, 0, 0, 0, 0}, 0, 0, 0, 0};
     DevBuf himg, hrec;   // host-array image entry points: pixels in / out, coefficient array in
-    DevBuf pix;          // 8-bit pixels: the dense float64 picture of the routes that convert in a pass of their own
-    DevBuf hpix8;        // 8-bit host-array entry points: the picture's bytes on the device
+    DevBuf pix;          // 8- / 16-bit pixels: the dense float64 picture of the routes that convert in a pass of their own
+    DevBuf hpix8;        // 8- / 16-bit host-array entry points: the picture's bytes on the device
     std::vector<double> mults_host;  // what ctx->mults holds (uploaded again only when the scales change)
     // colour model of the coded picture (spiht_ctx_set_color3): applied inside level 1 of the transforms of 3-channel images
     bool color_on = false;
@@ -1230,33 +1230,34 @@ static int upload_filters(spiht_ctx *ctx, int wavelet, const double **d_filt) {
     return SPIHT_OK;
 }
 
-// ---- the pictures of an image call: float64, float32 or 8-bit pixels ----------------------------------------------------
-// Float pixels: a dense array at p, [B, c, H, W] (the inverse transform's output: [B, c, rec_H, rec_W]).  8-bit pixels: the
-// view px (common.h: Px8) of a [B, c, H, W] uint8 picture batch by byte strides, based at p.  The extern "C" entry points
-// make one; everything behind them passes it on.
-enum PicFmt { PIC_F64, PIC_F32, PIC_U8 };
+// ---- the pictures of an image call: float64, float32, 8-bit or 16-bit pixels ---------------------------------------------
+// Float pixels: a dense array at p, [B, c, H, W] (the inverse transform's output: [B, c, rec_H, rec_W]).  8- and 16-bit
+// pixels: the view px (common.h: PxView) of a [B, c, H, W] uint8 / uint16 picture batch by byte strides, based at p.  The
+// extern "C" entry points make one; everything behind them passes it on.
+enum PicFmt { PIC_F64, PIC_F32, PIC_U8, PIC_U16 };
 struct Pic {
     PicFmt fmt = PIC_F64;
     char *p = nullptr;  // the first picture
     bool out = false;   // the call writes the pixels (else it reads them)
-    Px8 px = {};        // PIC_U8: strides and size (px.in / px.out unset: see u8())
-    // the view as the U8 kernels and the conversion passes take it
-    Px8 u8() const {
-        Px8 v = px;
+    PxView px = {};     // integer pixels: strides, size and element size (px.in / px.out unset: see view())
+    bool integer() const { return fmt == PIC_U8 || fmt == PIC_U16; }
+    // the view as the integer kernels and the conversion passes take it
+    PxView view() const {
+        PxView v = px;
         if (out) v.out = (uint8_t *)p;
         else v.in = (const uint8_t *)p;
         return v;
     }
     // bytes from the first pixel to one past the last of B pictures (c, ig: the call's); what the host calls transfer
     uint64_t bytes(int64_t B, int64_t c, const ImgGeom &ig) const {
-        if (fmt == PIC_U8)
-            return 1 + (uint64_t)(B - 1) * px.sb + (uint64_t)(px.c - 1) * px.sc + (uint64_t)(px.h - 1) * px.sh + (uint64_t)(px.w - 1) * px.sw;
+        if (integer())
+            return (uint64_t)px.es + (uint64_t)(B - 1) * px.sb + (uint64_t)(px.c - 1) * px.sc + (uint64_t)(px.h - 1) * px.sh + (uint64_t)(px.w - 1) * px.sw;
         return (uint64_t)B * c * (out ? ig.rec_H * ig.rec_W : ig.hs[0] * ig.ws[0]) * (fmt == PIC_F32 ? 4 : 8);
     }
     // the pictures from b0 on
     Pic at(int64_t b0, int64_t c, const ImgGeom &ig) const {
         Pic v = *this;
-        v.p += fmt == PIC_U8 ? b0 * px.sb : (int64_t)bytes(b0, c, ig);
+        v.p += integer() ? b0 * px.sb : (int64_t)bytes(b0, c, ig);
         return v;
     }
     // the same pictures at another address (a copy of their bytes)
@@ -1273,18 +1274,19 @@ static Pic dense_pic(const void *p, PicFmt fmt, bool out = false) {
     v.out = out;
     return v;
 }
-// strides: n == 4: (sb, sc, sh, sw); n == 3: (sc, sh, sw) of one picture; nullptr: dense CHW.  Strides are non-negative;
-// a view that is written must not overlap itself: sorted by stride, every dimension longer than 1 must step past all the
-// smaller ones reach.
-static int u8_pic(const void *p, bool out, const int64_t *strides, int n, int64_t B, int64_t c, int64_t h, int64_t w, Pic *v) {
-    int64_t st[4] = {c * h * w, h * w, w, 1};
+// es: bytes per sample, 1 or 2.  strides (in bytes): n == 4: (sb, sc, sh, sw); n == 3: (sc, sh, sw) of one picture;
+// nullptr: dense CHW.  Strides are non-negative and, as the base, multiples of es; a view that is written must not overlap
+// itself: sorted by stride, every dimension longer than 1 must step past the last byte all the smaller ones reach.
+static int int_pic(const void *p, int es, bool out, const int64_t *strides, int n, int64_t B, int64_t c, int64_t h, int64_t w, Pic *v) {
+    int64_t st[4] = {c * h * w * es, h * w * es, w * es, es};
     if (strides)
         for (int i = 0; i < n; i++) st[4 - n + i] = strides[i];
     if (n == 3) st[0] = 0;  // (one picture: no batch stride)
     const int64_t ext[4] = {B, c, h, w};
-    __int128 span = 1;
+    __int128 span = es;
+    if ((uintptr_t)p % (uintptr_t)es != 0) return SPIHT_ERR_ARG;
     for (int i = 0; i < 4; i++) {
-        if (st[i] < 0) return SPIHT_ERR_ARG;
+        if (st[i] < 0 || st[i] % es != 0) return SPIHT_ERR_ARG;
         if (ext[i] > 1) span += (__int128)(ext[i] - 1) * st[i];
     }
     if (span >= ((__int128)1 << 62)) return SPIHT_ERR_ARG;
@@ -1295,11 +1297,12 @@ static int u8_pic(const void *p, bool out, const int64_t *strides, int n, int64_
         for (int k = 0; k < 4; k++) {
             const int i = idx[k];
             if (ext[i] <= 1) continue;
-            if (st[i] < reach + 1) return SPIHT_ERR_ARG;
+            if (st[i] < reach + es) return SPIHT_ERR_ARG;
             reach += (ext[i] - 1) * st[i];
         }
     }
-    *v = dense_pic(p, PIC_U8, out);
+    *v = dense_pic(p, es == 2 ? PIC_U16 : PIC_U8, out);
+    v->px.es = es;
     v->px.sb = st[0]; v->px.sc = st[1]; v->px.sh = st[2]; v->px.sw = st[3];
     v->px.c = (int32_t)c; v->px.h = (int32_t)h; v->px.w = (int32_t)w;
     return SPIHT_OK;
@@ -1307,13 +1310,18 @@ static int u8_pic(const void *p, bool out, const int64_t *strides, int n, int64_
 extern "C" int spiht_check_view_u8(int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output) {
     if (B < 1 || c < 1 || H < 1 || W < 1 || !strides) return SPIHT_ERR_ARG;
     Pic v;
-    return u8_pic(nullptr, output != 0, strides, 4, B, c, H, W, &v);
+    return int_pic(nullptr, 1, output != 0, strides, 4, B, c, H, W, &v);
+}
+extern "C" int spiht_check_view_u16(int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output) {
+    if (B < 1 || c < 1 || H < 1 || W < 1 || !strides) return SPIHT_ERR_ARG;
+    Pic v;
+    return int_pic(nullptr, 2, output != 0, strides, 4, B, c, H, W, &v);
 }
 
 // pictures `in` (planes / c of them) -> quantised packed array [planes, enc_h, enc_w].  The rules of the pixel formats:
 // float32 pixels are transformed in single precision, as PyWavelets does for float32 / float16 input (every level's input
 // must then be at least as long as the filter: SPIHT_ERR_ARG otherwise), at a level >= 1 and without the colour model.
-// 8-bit pixels need a level >= 1 (no entry point gets here with level 0: SPIHT refuses that geometry -- the root block's
+// 8- and 16-bit pixels need a level >= 1 (no entry point gets here with level 0: SPIHT refuses that geometry -- the root block's
 // offspring fall outside the array -- before anything is transformed, on the float64 path as well); the tiled level 1
 // reads them itself, the two-pass levels get their float64 form from a conversion pass first.
 static int dwt_forward(spiht_ctx *ctx, const Pic &in, int planes, int c, const ImgGeom &ig, int wavelet, int mode,
@@ -1321,18 +1329,18 @@ static int dwt_forward(spiht_ctx *ctx, const Pic &in, int planes, int c, const I
     const WaveletDef &wv = SPIHT_WAVELETS[wavelet];
     const size_t plane_out = (size_t)ig.enc_h * ig.enc_w;
     const bool f32 = in.fmt == PIC_F32;
-    bool u8 = in.fmt == PIC_U8, color = ctx->color_on && c == 3;
+    bool u8 = in.integer(), color = ctx->color_on && c == 3;  // (u8: 8- or 16-bit pixels)
     if ((f32 || u8) && ig.L == 0) return SPIHT_ERR_ARG;
     if (color && f32) return SPIHT_ERR_ARG;  // the colour model change is float64 (as colour-science's)
     // the plain two-pass level: the modes that compute their extension, periodization, and filters longer than the tiled
     // kernels take (db11.., sym11.., coif4.., dmey)
     const bool twopass = mode >= SPIHT_MODE_SMOOTH || wv.F > SPIHT_MAX_TAPS;
     const double *d_img = u8 ? nullptr : (const double *)in.p;
-    if (u8 && twopass) {  // no 8-bit form of the two-pass level: the float64 picture as a pass of its own
+    if (u8 && twopass) {  // no integer form of the two-pass level: the float64 picture as a pass of its own
         StageTimer t(ctx, ST_DWT_L1);
         CHK(ensure(ctx, ctx->pix, (size_t)planes * ig.hs[0] * ig.ws[0] * 8));
-        const Px8 px = in.u8();
-        LAUNCHCHK(spiht_launch_u8_to_f64(&px, planes / c, (double *)ctx->pix.p, ctx->stream));
+        const PxView px = in.view();
+        LAUNCHCHK(spiht_launch_px_to_f64(&px, planes / c, (double *)ctx->pix.p, ctx->stream));
         d_img = (const double *)ctx->pix.p;
         u8 = false;
     }
@@ -1405,7 +1413,7 @@ static int dwt_forward(spiht_ctx *ctx, const Pic &in, int planes, int c, const I
         a.maxabs = d_maxabs;
         a.q = q;
         if (color && l == 1) { a.color = 1; a.col = ctx->col_fwd; }
-        if (u8 && l == 1) a.px = in.u8();  // (the launcher takes the U8 kernels)
+        if (u8 && l == 1) a.px = in.view();  // (the launcher takes the kernels of its pixel kind)
         const int Fc = std::min(wv.F, SPIHT_MAX_TAPS);  // (a longer filter goes by the device copy: two-pass level)
         memcpy(a.lo, wv.dec_lo, sizeof(double) * Fc);
         memcpy(a.hi, wv.dec_hi, sizeof(double) * Fc);
@@ -1462,7 +1470,7 @@ static bool l1flags_geometry(const ImgGeom &ig, int F, L1Flags *fl) {
 }
 
 // d_flags: L1Flags words [planes, gy, gx] the decoder of d_rec left (nullptr: every level-1 tile reads its detail bands)
-// 8-bit output (l_lo == 1, a level >= 1: see dwt_forward): cropped to the picture's size; the tiled level 1 writes it
+// 8- / 16-bit output (l_lo == 1, a level >= 1: see dwt_forward): cropped to the picture's size; the tiled level 1 writes it
 // itself, the two-pass level goes through a conversion pass behind it.
 static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, const ImgGeom &ig, int wavelet, double q,
                        const double *d_mults, const Pic &out, int l_hi = -1, int l_lo = 1, const double *d_a_in = nullptr,
@@ -1470,7 +1478,7 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
     const WaveletDef &wv = SPIHT_WAVELETS[wavelet];
     const int F = wv.F;
     if (l_hi < 0) l_hi = ig.L;
-    const bool u8 = out.fmt == PIC_U8;
+    const bool u8 = out.integer();  // (8- or 16-bit pixels)
     if (u8 && (l_lo != 1 || ig.L == 0)) return SPIHT_ERR_ARG;
     double *d_out = u8 ? nullptr : (double *)out.p;
     const bool color = ctx->color_on && c == 3;
@@ -1516,7 +1524,7 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
         if (l == 1 && !a.first && !a.color) a.flags = d_flags;
         memcpy(a.lo, wv.rec_lo, sizeof(double) * std::min(F, SPIHT_MAX_TAPS));
         memcpy(a.hi, wv.rec_hi, sizeof(double) * std::min(F, SPIHT_MAX_TAPS));
-        const bool conv8 = u8 && l == 1 && (ig.per || F > SPIHT_MAX_TAPS);  // 8-bit output through a pass of its own
+        const bool conv8 = u8 && l == 1 && (ig.per || F > SPIHT_MAX_TAPS);  // integer output through a pass of its own
         if (conv8) {
             CHK(ensure(ctx, ctx->pix, (size_t)planes * a.out_h * a.out_w * 8));
             a.out = (double *)ctx->pix.p;
@@ -1545,11 +1553,11 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
                 LAUNCHCHK(spiht_launch_color3(a.out, a.out, planes / 3, (size_t)a.out_h * a.out_w, ctx->col_inv.A, ctx->col_inv.M,
                                               ctx->col_inv.p, ctx->stream));
             if (conv8) {
-                const Px8 px = out.u8();
-                LAUNCHCHK(spiht_launch_f64_to_u8(a.out, a.out_h, a.out_w, &px, planes / c, ctx->stream));
+                const PxView px = out.view();
+                LAUNCHCHK(spiht_launch_f64_to_px(a.out, a.out_h, a.out_w, &px, planes / c, ctx->stream));
             }
         } else {
-            if (u8 && l == 1) a.px = out.u8();  // (the launcher takes the U8 kernels)
+            if (u8 && l == 1) a.px = out.view();  // (the launcher takes the kernels of its pixel kind)
             StageTimer t(ctx, l == 1 ? ST_IDWT_L1 : ST_IDWT_REST);
             LAUNCHCHK(spiht_launch_idwt_level(&a, planes, ctx->stream, ctx->tilectr.dev ? &ctx->tilectr : nullptr));
         }
@@ -1648,14 +1656,28 @@ extern "C" int spiht_dequant_idwt_flags_batch_f64(spiht_ctx *ctx, const int32_t 
     return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                               dense_pic(d_img_out, PIC_F64, true));
 }
+static int dequant_idwt_flags_batch_px(int es, spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
+                                       int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                                       double q_scale, const double *channel_mults, void *d_img_out,
+                                       const int64_t *out_strides) {
+    if (!d_img_out) return SPIHT_ERR_ARG;
+    Pic out;
+    CHK(int_pic(d_img_out, es, true, out_strides, 4, B, c, H, W, &out));
+    return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out);
+}
 extern "C" int spiht_dequant_idwt_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
                                                  int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                                                  double q_scale, const double *channel_mults, uint8_t *d_img_out,
                                                  const int64_t *out_strides) {
-    if (!d_img_out) return SPIHT_ERR_ARG;
-    Pic out;
-    CHK(u8_pic(d_img_out, true, out_strides, 4, B, c, H, W, &out));
-    return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out);
+    return dequant_idwt_flags_batch_px(1, ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                                       d_img_out, out_strides);
+}
+extern "C" int spiht_dequant_idwt_flags_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
+                                                  int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                                                  double q_scale, const double *channel_mults, uint16_t *d_img_out,
+                                                  const int64_t *out_strides) {
+    return dequant_idwt_flags_batch_px(2, ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                                       d_img_out, out_strides);
 }
 
 // The inverse transform in two parts, so that a pipelined caller can queue the coarse levels (a quarter of the bytes,
@@ -1712,15 +1734,29 @@ extern "C" int spiht_idwt_level1_flags_batch_f64(spiht_ctx *ctx, const int32_t *
     return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                      dense_pic(d_img_out, PIC_F64, true), d_flags);
 }
+static int idwt_level1_flags_batch_px(int es, spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                      int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                                      double q_scale, const double *channel_mults, void *d_img_out,
+                                      const int64_t *out_strides) {
+    if (!d_img_out) return SPIHT_ERR_ARG;
+    Pic out;
+    CHK(int_pic(d_img_out, es, true, out_strides, 4, B, c, H, W, &out));
+    return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out,
+                     d_flags);
+}
 extern "C" int spiht_idwt_level1_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
                                                 int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                                                 double q_scale, const double *channel_mults, uint8_t *d_img_out,
                                                 const int64_t *out_strides) {
-    if (!d_img_out) return SPIHT_ERR_ARG;
-    Pic out;
-    CHK(u8_pic(d_img_out, true, out_strides, 4, B, c, H, W, &out));
-    return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out,
-                     d_flags);
+    return idwt_level1_flags_batch_px(1, ctx, d_rec, d_approx, d_flags, B, c, H, W, wavelet, mode, level, q_scale,
+                                      channel_mults, d_img_out, out_strides);
+}
+extern "C" int spiht_idwt_level1_flags_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                                 int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                                                 double q_scale, const double *channel_mults, uint16_t *d_img_out,
+                                                 const int64_t *out_strides) {
+    return idwt_level1_flags_batch_px(2, ctx, d_rec, d_approx, d_flags, B, c, H, W, wavelet, mode, level, q_scale,
+                                      channel_mults, d_img_out, out_strides);
 }
 
 extern "C" int spiht_idwt_approx_shape(int64_t H, int64_t W, int wavelet, int level, int64_t *a_h, int64_t *a_w) {
@@ -1772,16 +1808,30 @@ extern "C" int spiht_encode_image_batch_f32(spiht_ctx *ctx, const float *d_img, 
     return encode_image_batch(ctx, dense_pic(d_img, PIC_F32), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
                               d_out, slot_stride, d_nbits, d_max_n, d_coeffs);
 }
+static int encode_image_batch_px(int es, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t B, int64_t c,
+                                 int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                 const double *channel_mults, uint64_t max_bits, uint8_t *d_out,
+                                 uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs) {
+    if (!d_img) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, B, c, H, W));
+    Pic in;
+    CHK(int_pic(d_img, es, false, strides, 4, B, c, H, W, &in));
+    return encode_image_batch(ctx, in, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, d_out, slot_stride,
+                              d_nbits, d_max_n, d_coeffs);
+}
 extern "C" int spiht_encode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t B, int64_t c,
                                            int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                            const double *channel_mults, uint64_t max_bits, uint8_t *d_out,
                                            uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs) {
-    if (!d_img) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    Pic in;
-    CHK(u8_pic(d_img, false, strides, 4, B, c, H, W, &in));
-    return encode_image_batch(ctx, in, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, d_out, slot_stride,
-                              d_nbits, d_max_n, d_coeffs);
+    return encode_image_batch_px(1, ctx, d_img, strides, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
+                                 d_out, slot_stride, d_nbits, d_max_n, d_coeffs);
+}
+extern "C" int spiht_encode_image_batch_u16(spiht_ctx *ctx, const uint16_t *d_img, const int64_t *strides, int64_t B, int64_t c,
+                                            int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                            const double *channel_mults, uint64_t max_bits, uint8_t *d_out,
+                                            uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs) {
+    return encode_image_batch_px(2, ctx, d_img, strides, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
+                                 d_out, slot_stride, d_nbits, d_max_n, d_coeffs);
 }
 
 static int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
@@ -1840,17 +1890,33 @@ extern "C" int spiht_decode_image_batch_f64(spiht_ctx *ctx, const uint8_t *d_dat
     return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                               dense_pic(d_img_out, PIC_F64, true), d_rec);
 }
+static int decode_image_batch_px(int es, spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                 const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                 int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                 const double *channel_mults, void *d_img_out, const int64_t *out_strides,
+                                 int32_t *d_rec) {
+    if (!d_img_out) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, B, c, H, W));
+    Pic out;
+    CHK(int_pic(d_img_out, es, true, out_strides, 4, B, c, H, W, &out));
+    return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                              out, d_rec);
+}
 extern "C" int spiht_decode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
                                            const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
                                            int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                            const double *channel_mults, uint8_t *d_img_out, const int64_t *out_strides,
                                            int32_t *d_rec) {
-    if (!d_img_out) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    Pic out;
-    CHK(u8_pic(d_img_out, true, out_strides, 4, B, c, H, W, &out));
-    return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
-                              out, d_rec);
+    return decode_image_batch_px(1, ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale,
+                                 channel_mults, d_img_out, out_strides, d_rec);
+}
+extern "C" int spiht_decode_image_batch_u16(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                            const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                            int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                            const double *channel_mults, uint16_t *d_img_out, const int64_t *out_strides,
+                                            int32_t *d_rec) {
+    return decode_image_batch_px(2, ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale,
+                                 channel_mults, d_img_out, out_strides, d_rec);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1858,7 +1924,7 @@ extern "C" int spiht_decode_image_batch_u8(spiht_ctx *ctx, const uint8_t *d_data
 // (spiht_wrapper.py:142-216, 259-281) as one C call each.  Pixels, stream and coefficient array live in the
 // context's grow-only device buffers -- no allocation per call after the first of a given size.
 // ------------------------------------------------------------------------------------------------
-// (an 8-bit picture: only the bytes its strides span are uploaded)
+// (an 8- / 16-bit picture: only the bytes its strides span are uploaded)
 static int encode_image_host(spiht_ctx *ctx, const Pic &img, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                              double q_scale, const double *channel_mults, uint64_t max_bits, uint8_t *out, uint64_t out_cap,
                              uint64_t *out_nbits, uint8_t *max_n) {
@@ -1872,7 +1938,7 @@ static int encode_image_host(spiht_ctx *ctx, const Pic &img, int64_t c, int64_t 
     if (bits >= 0xFFFFFF00ull * 8ull) return SPIHT_ERR_TOO_LARGE;
     const uint64_t slot = std::max<uint64_t>(4, ((bits + 7) / 8 + 3) & ~3ull);
     const size_t img_bytes = (size_t)img.bytes(1, c, k.ig);
-    DevBuf &hb = img.fmt == PIC_U8 ? ctx->hpix8 : ctx->himg;
+    DevBuf &hb = img.integer() ? ctx->hpix8 : ctx->himg;
     CHK(ensure(ctx, hb, img_bytes));
     CHK(ensure(ctx, ctx->out, slot));
     CHK(ensure(ctx, ctx->nbits, 8));
@@ -1900,19 +1966,33 @@ extern "C" int spiht_encode_image_host_f32(spiht_ctx *ctx, const float *img, int
     return encode_image_host(ctx, dense_pic(img, PIC_F32), c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out,
                              out_cap, out_nbits, max_n);
 }
+static int encode_image_host_px(int es, spiht_ctx *ctx, const void *img, const int64_t *strides, int64_t c, int64_t H,
+                                int64_t W, int wavelet, int mode, int level, double q_scale,
+                                const double *channel_mults, uint64_t max_bits, uint8_t *out, uint64_t out_cap,
+                                uint64_t *out_nbits, uint8_t *max_n) {
+    if (!img) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, 1, c, H, W));
+    Pic in;
+    CHK(int_pic(img, es, false, strides, 3, 1, c, H, W, &in));
+    return encode_image_host(ctx, in, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out, out_cap, out_nbits,
+                             max_n);
+}
 extern "C" int spiht_encode_image_host_u8(spiht_ctx *ctx, const uint8_t *img, const int64_t *strides, int64_t c, int64_t H,
                                           int64_t W, int wavelet, int mode, int level, double q_scale,
                                           const double *channel_mults, uint64_t max_bits, uint8_t *out, uint64_t out_cap,
                                           uint64_t *out_nbits, uint8_t *max_n) {
-    if (!img) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, 1, c, H, W));
-    Pic in;
-    CHK(u8_pic(img, false, strides, 3, 1, c, H, W, &in));
-    return encode_image_host(ctx, in, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out, out_cap, out_nbits,
-                             max_n);
+    return encode_image_host_px(1, ctx, img, strides, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out,
+                                out_cap, out_nbits, max_n);
+}
+extern "C" int spiht_encode_image_host_u16(spiht_ctx *ctx, const uint16_t *img, const int64_t *strides, int64_t c, int64_t H,
+                                           int64_t W, int wavelet, int mode, int level, double q_scale,
+                                           const double *channel_mults, uint64_t max_bits, uint8_t *out, uint64_t out_cap,
+                                           uint64_t *out_nbits, uint8_t *max_n) {
+    return encode_image_host_px(2, ctx, img, strides, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out,
+                                out_cap, out_nbits, max_n);
 }
 
-// (an 8-bit picture: a dense one, CHW or HWC, so that it is c*H*W bytes)
+// (an 8- / 16-bit picture: a dense one, CHW or HWC, so that it is c*H*W samples)
 static int decode_image_host(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H, int64_t W,
                              int wavelet, int mode, int level, double q_scale, const double *channel_mults, const Pic &img_out) {
     if (!ctx || !img_out.p || (!data && nbytes)) return SPIHT_ERR_ARG;
@@ -1923,7 +2003,7 @@ static int decode_image_host(spiht_ctx *ctx, const uint8_t *data, uint64_t nbyte
     if (nbytes * 8 >= 0xFFFFFF00ull) return SPIHT_ERR_TOO_LARGE;
     CHK(k.enter(nullptr));  // (the channel scales: the batch call's)
     const size_t out_bytes = (size_t)img_out.bytes(1, c, k.ig);
-    DevBuf &hb = img_out.fmt == PIC_U8 ? ctx->hpix8 : ctx->himg;
+    DevBuf &hb = img_out.integer() ? ctx->hpix8 : ctx->himg;
     CHK(ensure(ctx, hb, out_bytes));
     uint64_t slot;
     CHK(stage_stream(ctx, data, nbytes, n, &slot));
@@ -1943,18 +2023,30 @@ extern "C" int spiht_decode_image_host_f64(spiht_ctx *ctx, const uint8_t *data, 
     return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                              dense_pic(img_out, PIC_F64, true));
 }
-extern "C" int spiht_decode_image_host_u8(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
-                                          int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
-                                          const double *channel_mults, uint8_t *img_out, const int64_t *strides) {
+static int decode_image_host_px(int es, spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                const double *channel_mults, void *img_out, const int64_t *strides) {
     if (!img_out) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, 1, c, H, W));
     Pic out;
-    CHK(u8_pic(img_out, true, strides, 3, 1, c, H, W, &out));
-    // the copy back is of c*H*W bytes: only the two dense layouts, CHW and HWC
-    const Px8 &px = out.px;
-    const bool chw = px.sw == 1 && px.sh == W && px.sc == H * W, hwc = px.sc == 1 && px.sw == c && px.sh == W * c;
+    CHK(int_pic(img_out, es, true, strides, 3, 1, c, H, W, &out));
+    // the copy back is of c*H*W samples: only the two dense layouts, CHW and HWC
+    const PxView &px = out.px;
+    const bool chw = px.sw == es && px.sh == W * es && px.sc == H * W * es, hwc = px.sc == es && px.sw == c * es && px.sh == W * c * es;
     if (!chw && !hwc) return SPIHT_ERR_ARG;
     return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, out);
+}
+extern "C" int spiht_decode_image_host_u8(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                          int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                          const double *channel_mults, uint8_t *img_out, const int64_t *strides) {
+    return decode_image_host_px(1, ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out,
+                                strides);
+}
+extern "C" int spiht_decode_image_host_u16(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                           const double *channel_mults, uint16_t *img_out, const int64_t *strides) {
+    return decode_image_host_px(2, ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out,
+                                strides);
 }
 
 extern "C" int spiht_dequant_idwt_host_f64(spiht_ctx *ctx, const int32_t *rec, int64_t c, int64_t H, int64_t W, int wavelet,
@@ -2014,15 +2106,29 @@ extern "C" int spiht_dwt_pyramid_batch_f64(spiht_ctx *ctx, const double *d_img, 
     return dwt_pyramid_batch(ctx, dense_pic(d_img, PIC_F64), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs,
                              d_dmsb, d_lmsb, d_maxabs);
 }
+static int dwt_pyramid_batch_px(int es, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t B, int64_t c,
+                                int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                const double *channel_mults, int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb,
+                                uint32_t *d_maxabs) {
+    if (!d_img) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, B, c, H, W));
+    Pic in;
+    CHK(int_pic(d_img, es, false, strides, 4, B, c, H, W, &in));
+    return dwt_pyramid_batch(ctx, in, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs, d_dmsb, d_lmsb, d_maxabs);
+}
 extern "C" int spiht_dwt_pyramid_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t B, int64_t c,
                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                           const double *channel_mults, int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb,
                                           uint32_t *d_maxabs) {
-    if (!d_img) return SPIHT_ERR_ARG;
-    CHK(check_img_args(wavelet, mode, B, c, H, W));
-    Pic in;
-    CHK(u8_pic(d_img, false, strides, 4, B, c, H, W, &in));
-    return dwt_pyramid_batch(ctx, in, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs, d_dmsb, d_lmsb, d_maxabs);
+    return dwt_pyramid_batch_px(1, ctx, d_img, strides, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs,
+                                d_dmsb, d_lmsb, d_maxabs);
+}
+extern "C" int spiht_dwt_pyramid_batch_u16(spiht_ctx *ctx, const uint16_t *d_img, const int64_t *strides, int64_t B, int64_t c,
+                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                           const double *channel_mults, int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb,
+                                           uint32_t *d_maxabs) {
+    return dwt_pyramid_batch_px(2, ctx, d_img, strides, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs,
+                                d_dmsb, d_lmsb, d_maxabs);
 }
 
 extern "C" int spiht_encode_lists_batch_i32(spiht_ctx *ctx, const int32_t *d_x, const uint8_t *d_dmsb,

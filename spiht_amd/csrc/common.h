@@ -197,15 +197,18 @@ struct Color3 {
     double A[9], M[9], p;
 };
 
-// 8-bit pixels at level 1 of the transforms (dwt.hip, the *_u8 kernels): a [B, c, h, w] uint8 view given by byte strides.
-// Forward: sample k is loaded as the double k / 255.0 (IEEE division: exactly numpy's P / 255).  Inverse: a value v is
-// stored as (uint8)(clip(v, 0, 1) * 255.0), truncated, and only for y < h, x < w (the picture's own size: the level's
+// 8- and 16-bit pixels at level 1 of the transforms (dwt.hip, the PX_U8 / PX_U16 kernels): a [B, c, h, w] uint8 or uint16
+// view given by BYTE strides (both kinds: the pointers stay byte pointers, a 16-bit sample is read / written at its byte
+// address, which is even -- the entry points check base and strides).  With D = 255 (es == 1) or 65535 (es == 2):
+// Forward: sample k is loaded as the double k / D (IEEE division: exactly numpy's P / D).  Inverse: a value v is
+// stored as (uintN)(clip(v, 0, 1) * D), truncated, and only for y < h, x < w (the picture's own size: the level's
 // output is one longer where h / w is odd).  Plane index p = b*c + ch; its base b*sb + ch*sc is formed in 64 bits.
-struct Px8 {
+struct PxView {
     const uint8_t *in;     // forward: the pixels read
     uint8_t *out;          // inverse: the pixels written
     int64_t sb, sc, sh, sw;
-    int32_t c, h, w, pad;
+    int32_t c, h, w;
+    int32_t es;            // element size in bytes: 1 or 2 (the launchers pick the kernels' pixel kind from it)
 };
 
 // One forward DWT level (dwt.hip)
@@ -229,7 +232,7 @@ struct DwtKArgs {
     float lo_f[SPIHT_MAX_TAPS], hi_f[SPIHT_MAX_TAPS];  // ... as PyWavelets' single-precision transform has them (f32 levels)
     int32_t color, pad2;   // level 1 of a 3-channel image with the colour model change on its loads (k_dwt1_color)
     Color3 col;
-    Px8 px;                // level 1 of an 8-bit picture: the kernels' U8 instantiations read it instead of `in`
+    PxView px;             // level 1 of an 8- / 16-bit picture: the kernels' integer instantiations read it instead of `in`
 };
 
 // One inverse DWT level (dwt.hip)
@@ -267,5 +270,5 @@ struct IdwtKArgs {
     double lo[SPIHT_MAX_TAPS], hi[SPIHT_MAX_TAPS];  // rec_lo, rec_hi
     int32_t color, pad2;       // level 1 of a 3-channel image with the colour model change on its stores (k_idwt1_color)
     Color3 col;
-    Px8 px;                    // level 1 into an 8-bit picture: the kernels' U8 instantiations write it instead of `out`
+    PxView px;                 // level 1 into an 8- / 16-bit picture: the kernels' integer instantiations write it instead of `out`
 };

@@ -1,4 +1,4 @@
-// 2-D separable DWT / inverse DWT for the SPIHT image path (gfx950), float64.
+// 2-D separable DWT / inverse DWT for the SPIHT image path (gfx950), float64 (level 1 also from / into 8- and 16-bit pixels).
 //
 // Replaces the PyWavelets calls of the reference wrapper
 //   encode: pywt.wavedec2 -> coeffs_to_array -> channel_mults*arr -> quantize   (spiht_wrapper.py:163-172)
@@ -133,7 +133,7 @@ __device__ __forceinline__ double dequant(int32_t r, double m, double q, bool ha
     return v / q;
 }
 
-// 8-bit pixels (common.h: Px8): k -> the double k / 255.0, numpy's P / 255 in every bit.  Not a division (a dozen float64
+// 8-bit pixels (common.h: PxView): k -> the double k / 255.0, numpy's P / 255 in every bit.  Not a division (a dozen float64
 // instructions; 28 of them per thread and tile cost level 1 of 256 1080p pictures about 0.4 ms) and not k * (1/255) alone
 // (24 of the 256 quotients differ): the product corrected once by its exact residual, which gives the correctly rounded
 // quotient for all 256 k (tests/test_u8_cpu.py proves the algorithm for all of them).
@@ -148,13 +148,44 @@ __device__ __forceinline__ uint8_t px8_store_value(double v) {
     const double s = c * 255.0;
     return (uint8_t)(uint32_t)s;
 }
+// 16-bit pixels: the same rules with 65535 for 255.  k * (1/65535) alone misses 88 of the 65536 quotients; the corrected
+// product gives all of them (tests/test_u16_cpu.py proves it), and (uint16)((k / 65535.0) * 65535.0) is k for every k.
+__device__ __forceinline__ double px16_value(uint16_t k) {
+    const double x = (double)k, r = 1.0 / 65535.0;
+    const double q = x * r;
+    return fma(fma(-q, 65535.0, x), r, q);
+}
+__device__ __forceinline__ uint16_t px16_store_value(double v) {
+    const double c = fmin(fmax(v, 0.0), 1.0);
+    const double s = c * 65535.0;
+    return (uint16_t)(uint32_t)s;
+}
+// The pixel kind of a level-1 kernel (template parameter PX): PX_F64 reads / writes the dense float64 planes a.in / a.out,
+// the integer kinds the strided view a.px (common.h: PxView; byte strides, so a sample's address is formed in bytes for
+// both) -- the value of an integer kind is its element size.
+enum PxKind : int { PX_F64 = 0, PX_U8 = 1, PX_U16 = 2 };
+template <int PX> __device__ __forceinline__ uint32_t px_load(const uint8_t *p) {  // the raw sample, not yet converted
+    if constexpr (PX == PX_U16) return *reinterpret_cast<const uint16_t *>(p);
+    else return *p;
+}
+template <int PX> __device__ __forceinline__ double px_value(uint32_t raw) {
+    if constexpr (PX == PX_U16) return px16_value((uint16_t)raw);
+    else return px8_value((uint8_t)raw);
+}
+// p[o] = the stored form of v.  The 8-bit statement is the one the kernels held before there was a second integer kind,
+// as a statement of its own: their instruction order stays what it was.
+#define PX_STORE(PX, p, o, v)                                                               \
+    do {                                                                                    \
+        if constexpr ((PX) == PX_U16) *reinterpret_cast<uint16_t *>((p) + (o)) = px16_store_value(v); \
+        else (p)[o] = px8_store_value(v);                                                   \
+    } while (0)
 
 // grid: (ceil(out_w/TW), ceil(out_h/TH), planes).  LOM / HIM: bit j set = tap j of dec_lo / dec_hi is non-zero;
 // a zero tap contributes exactly nothing (0*x added to the running sum), so skipping it changes no bit and
 // removes a third (bior2.2) to a fifth of the float64 arithmetic.
 // One tile of k_dwt_level.
-// U8: the level's input is the strided 8-bit picture a.px (common.h: Px8), converted on the loads.
-template <int F, uint32_t LOM, uint32_t HIM, int PS, int NR, bool U8 = false>
+// PX != PX_F64: the level's input is the strided 8- or 16-bit picture a.px (common.h: PxView), converted on the loads.
+template <int F, uint32_t LOM, uint32_t HIM, int PS, int NR, int PX = PX_F64>
 __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS], double (&s_hi)[2][PS], uint32_t tbx, uint32_t tby,
                                          uint32_t tbz) {
     constexpr int NC = 2 * DW_TW + F - 2;  // input columns needed by the tile
@@ -164,9 +195,9 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
     constexpr int RS = HC + 1;
     const int plane = (int)tbz;
     const int oh0 = (int)tby * DW_TH, ow0 = (int)tbx * DW_TW;
-    const double *__restrict__ in = U8 ? nullptr : a.in + (size_t)plane * a.in_h * a.in_w;
+    const double *__restrict__ in = PX ? nullptr : a.in + (size_t)plane * a.in_h * a.in_w;
     // (the plane base in 64 bits, from the tile coordinates in vector registers: see below)
-    const uint8_t *__restrict__ in8 = U8 ? a.px.in + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
+    const uint8_t *__restrict__ in8 = PX ? a.px.in + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
     const int tid = threadIdx.x;
 
     // input row needed for output row o, tap j: 2*o + 1 - j ; first needed row r0 = 2*oh0 + 1 - (F-1)
@@ -175,7 +206,7 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
     __shared__ long long s_off[NR];
     if (tid < NR) {
         const int gr = ext_index(r0 + tid, a.in_h, a.mode);
-        s_off[tid] = gr < 0 ? -1ll : (long long)gr * (U8 ? a.px.sh : (long long)a.in_w);
+        s_off[tid] = gr < 0 ? -1ll : (long long)gr * (PX ? a.px.sh : (long long)a.in_w);
     }
     __shared__ uint32_t s_amax;
     if (tid == 0) s_amax = 0;
@@ -192,9 +223,9 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
         // through an index the compiler cannot prove uniform, so that they stay in vector registers.
         int lz = 0;
         asm volatile("" : "+v"(lz));
-        if (U8) {  // byte loads at the same row offsets, ALL of them first (converted one by one behind its load, the
-                   // compiler waited for each load before it issued the next: level 1 took 7.1 instead of 4.3 ms), then
-                   // k -> k / 255.0
+        if (PX) {  // byte / 16-bit loads at the same row offsets, ALL of them first (converted one by one behind its load,
+                   // the compiler waited for each load before it issued the next: level 1 took 7.1 instead of 4.3 ms),
+                   // then k -> k / 255.0 (k / 65535.0)
             const long long co8 = gc < 0 ? 0 : (long long)gc * a.px.sw;
             uint32_t raw[NR];
             static_assert(NR <= 64, "one bit per row");
@@ -204,10 +235,10 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
                 const long long off = s_off[r + lz];
                 const bool ok = a.mode != 3 || (gc >= 0 && off >= 0);
                 okm |= (ok ? 1ull : 0ull) << r;
-                raw[r] = in8[ok ? off + co8 : 0];
+                raw[r] = px_load<PX>(in8 + (ok ? off + co8 : 0));
             }
 #pragma unroll
-            for (int r = 0; r < NR; r++) x[r] = ((okm >> r) & 1ull) ? px8_value((uint8_t)raw[r]) : 0.0;
+            for (int r = 0; r < NR; r++) x[r] = ((okm >> r) & 1ull) ? px_value<PX>(raw[r]) : 0.0;
         } else if (a.mode != 3) {  // not zero padding: every index is inside the picture
 #pragma unroll
             for (int r = 0; r < NR; r++) x[r] = in[s_off[r + lz] + gc];
@@ -280,7 +311,7 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
     }
 }
 
-template <int F, uint32_t LOM, uint32_t HIM, bool U8 = false>  // U8: level 1 of an 8-bit picture (a.px; a.in unused)
+template <int F, uint32_t LOM, uint32_t HIM, int PX = PX_F64>  // PX_U8 / PX_U16: level 1 of an 8- / 16-bit picture (a.px; a.in unused)
 __global__ __launch_bounds__(DWF_BLOCK) void k_dwt_level(DwtKArgs a) {
     constexpr int NC = 2 * DW_TW + F - 2, NR = 2 * DW_TH + F - 2, HC = (NC + 1) / 2;
     // two column-parity planes; the padding makes the plane stride an odd multiple of 16 banks, so the even and odd
@@ -294,7 +325,7 @@ __global__ __launch_bounds__(DWF_BLOCK) void k_dwt_level(DwtKArgs a) {
     uint32_t lin = blockIdx.x;
     asm volatile("" : "+v"(lin));
     xcd_tile_at(lin, (a.out_w + DW_TW - 1) / DW_TW, (a.out_h + DW_TH - 1) / DW_TH, a.planes, tbx, tby, tbz);
-    dwt_tile<F, LOM, HIM, PS, NR, U8>(a, s_lo, s_hi, tbx, tby, tbz);
+    dwt_tile<F, LOM, HIM, PS, NR, PX>(a, s_lo, s_hi, tbx, tby, tbz);
 }
 
 // ---- helpers of the persistent inverse-transform kernel (k_idwt_level_pf) -------------------------------------------
@@ -322,7 +353,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void *p, uint
 // a side stream -- cost the level 5 to 12 %: measured); this kernel then recomputes just the outputs whose order
 // matters (ov_h / ov_w: the last row and column of a bior level), one thread each, straight from global memory, and
 // overwrites them.  grid: (ceil(outputs / 256), planes).
-template <int F, bool U8 = false>  // U8: level 1 of an 8-bit picture (a.px)
+template <int F, int PX = PX_F64>  // PX_U8 / PX_U16: level 1 of an 8- / 16-bit picture (a.px)
 __global__ __launch_bounds__(256) void k_dwt_edge(DwtKArgs a) {
     __shared__ double s_f[2][F];  // taps, indexed at run time below
     if (threadIdx.x < F) { s_f[0][threadIdx.x] = a.lo[threadIdx.x]; s_f[1][threadIdx.x] = a.hi[threadIdx.x]; }
@@ -338,8 +369,8 @@ __global__ __launch_bounds__(256) void k_dwt_edge(DwtKArgs a) {
         int oh, ow;
         if (t < nA) { oh = a.ov_h + t / a.out_w; ow = t % a.out_w; }
         else { const int u = t - nA; oh = u / nc; ow = a.ov_w + u % nc; }
-        const double *__restrict__ in = U8 ? nullptr : a.in + (size_t)plane * a.in_h * a.in_w;
-        const uint8_t *__restrict__ in8 = U8 ? a.px.in + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
+        const double *__restrict__ in = PX ? nullptr : a.in + (size_t)plane * a.in_h * a.in_w;
+        const uint8_t *__restrict__ in8 = PX ? a.px.in + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
         const int ir = 2 * oh + 1, ic = 2 * ow + 1;
         const int jbr = oh >= a.ov_h ? ir - a.in_h : -1, jbc = ow >= a.ov_w ? ic - a.in_w : -1;
         int gr[F];
@@ -357,7 +388,7 @@ __global__ __launch_bounds__(256) void k_dwt_edge(DwtKArgs a) {
             double xv[F];
 #pragma unroll
             for (int r = 0; r < F; r++) {
-                if (U8) xv[r] = (gc < 0 || gr[r] < 0) ? 0.0 : px8_value(in8[(int64_t)gr[r] * a.px.sh + (int64_t)gc * a.px.sw]);
+                if (PX) xv[r] = (gc < 0 || gr[r] < 0) ? 0.0 : px_value<PX>(px_load<PX>(in8 + ((int64_t)gr[r] * a.px.sh + (int64_t)gc * a.px.sw)));
                 else xv[r] = (gc < 0 || gr[r] < 0) ? 0.0 : in[(size_t)gr[r] * a.in_w + gc];
             }
             double tl = 0.0, th = 0.0;
@@ -604,7 +635,7 @@ extern "C" int spiht_launch_color3(const double *d_in, double *d_out, int B, siz
 #ifndef C1_WPE
 #define C1_WPE 4
 #endif
-template <int F, uint32_t LOM, uint32_t HIM, bool U8 = false>  // U8: an 8-bit picture (a.px; a.in unused)
+template <int F, uint32_t LOM, uint32_t HIM, int PX = PX_F64>  // PX_U8 / PX_U16: an 8- / 16-bit picture (a.px; a.in unused)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C1_WPE, C1_WPE)))  // 128 VGPRs: left alone the compiler interleaves
 void k_dwt1_color(DwtKArgs a, uint32_t gx, uint32_t gy) {                       // the six powers of a step over 173 (2 waves / SIMD)
     constexpr int SW = (256 - (F - 2)) / 2;  // output columns per strip: exactly 256 input columns
@@ -622,16 +653,17 @@ void k_dwt1_color(DwtKArgs a, uint32_t gx, uint32_t gy) {                       
     const int ow0 = (int)tbx * SW, oa = (int)tby * C1_ROWS;
     const int ob = min(oa + C1_ROWS, a.out_h);
     const size_t npl = (size_t)a.in_h * a.in_w;
-    const double *__restrict__ in = U8 ? nullptr : a.in + (size_t)img * 3 * npl;
-    const uint8_t *__restrict__ in8 = U8 ? a.px.in + (int64_t)img * a.px.sb : nullptr;
+    const double *__restrict__ in = PX ? nullptr : a.in + (size_t)img * 3 * npl;
+    const uint8_t *__restrict__ in8 = PX ? a.px.in + (int64_t)img * a.px.sb : nullptr;
     const int tid = threadIdx.x;
     const int gc = ext_index(2 * ow0 + 2 - F + tid, a.in_w, a.mode);
     auto ld = [&](int r, double &u0, double &u1, double &u2) {  // raw R, G, B of (row r, this column), extension applied
         const int gr = ext_index(r, a.in_h, a.mode);
         const bool z = gc < 0 || gr < 0;
-        if (U8) {  // (the pixel's three channels sc bytes apart: neighbours in an interleaved picture)
+        if (PX) {  // (the pixel's three channels sc bytes apart: neighbours in an interleaved picture)
             const int64_t o = z ? 0 : (int64_t)gr * a.px.sh + (int64_t)gc * a.px.sw;
-            u0 = px8_value(in8[o]); u1 = px8_value(in8[o + a.px.sc]); u2 = px8_value(in8[o + 2 * a.px.sc]);
+            u0 = px_value<PX>(px_load<PX>(in8 + o)); u1 = px_value<PX>(px_load<PX>(in8 + (o + a.px.sc)));
+            u2 = px_value<PX>(px_load<PX>(in8 + (o + 2 * a.px.sc)));
         } else {
             const size_t o = z ? 0 : (size_t)gr * a.in_w + gc;
             u0 = in[o]; u1 = in[o + npl]; u2 = in[o + 2 * npl];
@@ -1108,7 +1140,7 @@ __global__ __launch_bounds__(256) void k_dequant_plain(const int32_t *in, double
 
 // grid: (ceil(out_w/TW), ceil(out_h/TH), planes).  LOM / HIM: non-zero taps of rec_lo / rec_hi (a product with a
 // zero tap adds exactly nothing to `ca*lo + cd*hi`, so it is skipped).
-template <int F, uint32_t LOM, uint32_t HIM, bool U8 = false>  // U8: level 1 into an 8-bit picture (a.px; a.out unused)
+template <int F, uint32_t LOM, uint32_t HIM, int PX = PX_F64>  // PX_U8 / PX_U16: level 1 into an 8- / 16-bit picture (a.px; a.out unused)
 __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
     // band index k contributes to output n with tap t = n + F - 2 - 2k in [0,F):  k in [n/2, n/2 + F/2 - 1]
     constexpr int HF = F / 2;
@@ -1170,8 +1202,8 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
     double wl[HF], wh[HF];  // register window: tl/th of the last HF band rows (index HF-1 = newest)
 #pragma unroll
     for (int s = 0; s < HF; s++) { wl[s] = 0.0; wh[s] = 0.0; }
-    double *__restrict__ out = U8 ? nullptr : a.out + (size_t)plane * a.out_h * a.out_w;
-    uint8_t *__restrict__ out8 = U8 ? a.px.out + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
+    double *__restrict__ out = PX ? nullptr : a.out + (size_t)plane * a.out_h * a.out_w;
+    uint8_t *__restrict__ out8 = PX ? a.px.out + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
     const int rbase = half * (IW_TH / 4);  // first band row (tile-relative) of this half
 #pragma unroll
     for (int rr = 0; rr < KHH; rr++) {
@@ -1215,8 +1247,8 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
                     if (hnz) sd += wh[s] * a.hi[mp + F - 2 - 2 * s];
                 }
                 const double sacc = (0.0 + sa) + sd;
-                if (U8) {
-                    if (m + mp < a.px.h && n < a.px.w) out8[(int64_t)(m + mp) * a.px.sh + (int64_t)n * a.px.sw] = px8_store_value(sacc);
+                if (PX) {
+                    if (m + mp < a.px.h && n < a.px.w) PX_STORE(PX, out8, (int64_t)(m + mp) * a.px.sh + (int64_t)n * a.px.sw, sacc);
                 } else {
                     if (m + mp < a.out_h && n < a.out_w) out[(size_t)(m + mp) * a.out_w + n] = sacc;
                 }
@@ -1242,9 +1274,9 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
 // and are not read.  The loads stay unconditional -- a branch around them would make every later wait a wait for
 // everything -- and go through a buffer descriptor of the plane instead: an offset beyond it returns 0 without a trip
 // to memory.  The word of a tile is fetched when the tile's number becomes known, a tile of work ahead of its use.
-// U8: the output is the strided 8-bit picture a.px (common.h: Px8); the launcher sees to it that a plane's bytes span less
-// than 2^31 (32-bit buffer offsets).
-template <int F, uint32_t LOM, uint32_t HIM, bool FIRST, bool FLAGS = false, bool U8 = false>  // FIRST: coarsest level, the approximation comes from the packed array
+// PX_U8 / PX_U16: the output is the strided 8- / 16-bit picture a.px (common.h: PxView); the launcher sees to it that a
+// plane's bytes span less than 2^31 (32-bit buffer offsets).
+template <int F, uint32_t LOM, uint32_t HIM, bool FIRST, bool FLAGS = false, int PX = PX_F64>  // FIRST: coarsest level, the approximation comes from the packed array
 __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_t gx, uint32_t gy, uint32_t *ctr,
                                                                       TileBase cb) {
     static_assert(!(FIRST && FLAGS), "the flags are those of level 1 of a transform with two levels or more");
@@ -1359,11 +1391,11 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
         // stores stand in straight-line code.  With branches around them the compiler cannot count them, and the wait
         // for the next tile's samples at the top of the loop becomes a wait for these stores as well.
         const uint32_t row_bytes = (uint32_t)a.out_w * 8u;
-        const __amdgpu_buffer_rsrc_t orsrc = U8 ? plane_rsrc(a.px.out + (int64_t)(plane / (uint32_t)a.c) * a.px.sb + (int64_t)(plane % (uint32_t)a.c) * a.px.sc,
-                                                             (uint32_t)((int64_t)(a.px.h - 1) * a.px.sh + (int64_t)(a.px.w - 1) * a.px.sw + 1))
+        const __amdgpu_buffer_rsrc_t orsrc = PX ? plane_rsrc(a.px.out + (int64_t)(plane / (uint32_t)a.c) * a.px.sb + (int64_t)(plane % (uint32_t)a.c) * a.px.sc,
+                                                             (uint32_t)((int64_t)(a.px.h - 1) * a.px.sh + (int64_t)(a.px.w - 1) * a.px.sw + PX))
                                                 : plane_rsrc(a.out + (size_t)plane * a.out_h * a.out_w, (uint32_t)a.out_h * row_bytes);
         const uint32_t voff0 = n < a.out_w ? (uint32_t)(2 * (kh0 + rbase)) * row_bytes + (uint32_t)n * 8u : BUF_OOB;
-        // (U8) the crop: columns x >= w by an offset beyond the descriptor, rows y >= h by a compare per store
+        // (integer pixels) the crop: columns x >= w by an offset beyond the descriptor, rows y >= h by a compare per store
         const int y0 = 2 * (kh0 + rbase);
         const uint32_t voff8 = n < a.px.w ? (uint32_t)y0 * (uint32_t)a.px.sh + (uint32_t)n * (uint32_t)a.px.sw : BUF_OOB;
 #pragma unroll
@@ -1401,10 +1433,14 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
                         if (hnz) sd += wh[s2] * a.hi[mp + F - 2 - 2 * s2];
                     }
                     const double sacc = (0.0 + sa) + sd;
-                    if constexpr (U8) {
+                    if constexpr (PX == PX_U8) {
                         const int dy = 2 * (rr - (HF - 1)) + mp;
                         __builtin_amdgcn_raw_buffer_store_b8(px8_store_value(sacc), orsrc,
                                                              y0 + dy < a.px.h ? voff8 + (uint32_t)dy * (uint32_t)a.px.sh : BUF_OOB, 0, 0);
+                    } else if constexpr (PX == PX_U16) {
+                        const int dy = 2 * (rr - (HF - 1)) + mp;
+                        __builtin_amdgcn_raw_buffer_store_b16(px16_store_value(sacc), orsrc,
+                                                              y0 + dy < a.px.h ? voff8 + (uint32_t)dy * (uint32_t)a.px.sh : BUF_OOB, 0, 0);
                     } else {
                         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sacc), orsrc,
                                                               voff0 + (uint32_t)(2 * (rr - (HF - 1)) + mp) * row_bytes, 0, 0);
@@ -1446,7 +1482,7 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
 // result: the transformed picture in the coded colour model never exists in memory.  Arithmetic-bound, so the tile is
 // smaller than k_idwt_level's (IWC_TH rows: 38.6 KB of LDS for the three channels, four workgroups per CU).
 #define IWC_TH 8
-template <int F, uint32_t LOM, uint32_t HIM, bool U8 = false>  // U8: an 8-bit picture (a.px; a.out unused)
+template <int F, uint32_t LOM, uint32_t HIM, int PX = PX_F64>  // PX_U8 / PX_U16: an 8- / 16-bit picture (a.px; a.out unused)
 __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
     constexpr int HF = F / 2;
     constexpr int KH = IWC_TH / 2 + HF - 1, KW = IW_TW / 2 + HF - 1, KHH = IWC_TH / 4 + HF - 1;
@@ -1501,8 +1537,8 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
     for (int ch = 0; ch < 3; ch++)
 #pragma unroll
         for (int s = 0; s < HF; s++) { wl[ch][s] = 0.0; wh[ch][s] = 0.0; }
-    double *__restrict__ out = U8 ? nullptr : a.out + (size_t)img * 3 * opl;
-    uint8_t *__restrict__ out8 = U8 ? a.px.out + (int64_t)img * a.px.sb : nullptr;
+    double *__restrict__ out = PX ? nullptr : a.out + (size_t)img * 3 * opl;
+    uint8_t *__restrict__ out8 = PX ? a.px.out + (int64_t)img * a.px.sb : nullptr;
     const int rbase = half * (IWC_TH / 4);
 #pragma unroll
     for (int rr = 0; rr < KHH; rr++) {
@@ -1547,14 +1583,14 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
                     }
                     px[ch] = (0.0 + sa) + sd;
                 }
-                if (U8 ? (m + mp < a.px.h && n < a.px.w) : (m + mp < a.out_h && n < a.out_w)) {
+                if (PX ? (m + mp < a.px.h && n < a.px.w) : (m + mp < a.out_h && n < a.out_w)) {
                     double w0, w1, w2;
                     color3_px(a.col, s_pw, px[0], px[1], px[2], w0, w1, w2);
-                    if (U8) {
+                    if (PX) {
                         const int64_t o = (int64_t)(m + mp) * a.px.sh + (int64_t)n * a.px.sw;
-                        out8[o] = px8_store_value(w0);
-                        out8[o + a.px.sc] = px8_store_value(w1);
-                        out8[o + 2 * a.px.sc] = px8_store_value(w2);
+                        PX_STORE(PX, out8, o, w0);
+                        PX_STORE(PX, out8, o + a.px.sc, w1);
+                        PX_STORE(PX, out8, o + 2 * a.px.sc, w2);
                     } else {
                         const size_t o = (size_t)(m + mp) * a.out_w + n;
                         out[o] = w0;
@@ -1569,11 +1605,11 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
 
 // ---- host launchers -----------------------------------------------------------------------------
 
-// a.px.in set: level 1 of an 8-bit picture (the U8 kernels; a.in unused)
+// a.px.in set: level 1 of an 8- or 16-bit picture (the kernels of the kind a.px.es names; a.in unused)
 template <int F, uint32_t LOM, uint32_t HIM>
 static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
     a.planes = planes;
-    const bool u8 = a.px.in != nullptr;
+    const int px = a.px.in == nullptr ? PX_F64 : a.px.es == 2 ? PX_U16 : PX_U8;
     a.ov_h = a.out_h;
     a.ov_w = a.out_w;
     if (a.f32) {
@@ -1588,7 +1624,8 @@ static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
         if (a.mode != 4) a.ov_h = min(a.out_h, (a.in_h + z + 2) / 2);
         if (a.mode != 4) a.ov_w = min(a.out_w, (a.in_w + z + 2) / 2);
         const uint32_t gx = (uint32_t)((a.out_w + SW - 1) / SW), gy = (uint32_t)((a.out_h + C1_ROWS - 1) / C1_ROWS);
-        if (u8) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, true>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
+        if (px == PX_U16) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, PX_U16>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
+        else if (px == PX_U8) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, PX_U8>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
         else hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
         return (int)hipGetLastError();
     }
@@ -1602,11 +1639,13 @@ static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
     if (a.mode != 4) a.ov_h = min(a.out_h, (a.in_h + z + 2) / 2);
     if (a.mode != 4) a.ov_w = min(a.out_w, (a.in_w + z + 2) / 2);
     const uint32_t nt = (uint32_t)((a.out_w + DW_TW - 1) / DW_TW) * (uint32_t)((a.out_h + DW_TH - 1) / DW_TH) * (uint32_t)planes;
-    if (u8) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+    if (px == PX_U16) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U16>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+    else if (px == PX_U8) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U8>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
     else hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
     const int n_edge = (a.out_h - a.ov_h) * a.out_w + a.ov_h * (a.out_w - a.ov_w);
     if (n_edge > 0) {
-        if (u8) hipLaunchKernelGGL((k_dwt_edge<F, true>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
+        if (px == PX_U16) hipLaunchKernelGGL((k_dwt_edge<F, PX_U16>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
+        else if (px == PX_U8) hipLaunchKernelGGL((k_dwt_edge<F, PX_U8>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_dwt_edge<F>, dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
     }
     return (int)hipGetLastError();
@@ -1622,14 +1661,23 @@ static int launch_dwt_F(const DwtKArgs &a, int planes, hipStream_t st) {
     if (lom == LOM && him == HIM) return launch_dwt_FM<F, LOM, HIM>(a, planes, st);
     return launch_dwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st);
 }
-// a.px.out set: level 1 into an 8-bit picture (the U8 kernels; a.out unused)
+// the persistent kernel of one pixel kind: coarsest level / with the L1Flags words / without
+template <int F, uint32_t LOM, uint32_t HIM, int PX>
+static void launch_idwt_pf(IdwtKArgs &a, uint32_t G, uint32_t pad, hipStream_t st, uint32_t gx, uint32_t gy, uint32_t *ctr, const TileBase &cb) {
+    if (a.first) hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, true, false, PX>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
+    else if (a.flags && (uint64_t)a.enc_h * a.enc_w * 4u < (1ull << 31))
+        hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, true, PX>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
+    else { a.flags = nullptr; hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, false, PX>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb); }
+}
+// a.px.out set: level 1 into an 8- or 16-bit picture (the kernels of the kind a.px.es names; a.out unused)
 template <int F, uint32_t LOM, uint32_t HIM>
 static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) {
     a.planes = planes;
-    const bool u8 = a.px.out != nullptr;
+    const int px = a.px.out == nullptr ? PX_F64 : a.px.es == 2 ? PX_U16 : PX_U8;
     if (a.color) {  // level 1 of a 3-channel image, colour model change on the stores
         uint32_t ntc = (uint32_t)((a.out_w + IW_TW - 1) / IW_TW) * (uint32_t)((a.out_h + IWC_TH - 1) / IWC_TH) * (uint32_t)(planes / 3);
-        if (u8) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, true>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
+        if (px == PX_U16) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, PX_U16>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
+        else if (px == PX_U8) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, PX_U8>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
         else hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
         return (int)hipGetLastError();
     }
@@ -1639,9 +1687,9 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) 
     // workgroups that fetch a tile ahead
     constexpr uint32_t pf_min = 20000u;
     const int num_cu = tc ? tc->num_cu : 0;
-    // (the persistent kernel addresses a plane with 32-bit offsets: float64 planes by their size, the 8-bit output by the
-    // span of its strides)
-    const bool off32 = u8 ? (uint64_t)((a.px.h - 1) * a.px.sh + (a.px.w - 1) * a.px.sw) + 1u < (1ull << 31)
+    // (the persistent kernel addresses a plane with 32-bit offsets: float64 planes by their size, the 8- / 16-bit output by
+    // the byte span of its strides)
+    const bool off32 = px ? (uint64_t)((a.px.h - 1) * a.px.sh + (a.px.w - 1) * a.px.sw) + (uint64_t)px < (1ull << 31)
                           : (uint64_t)(a.out_h + IW_TH) * a.out_w * 8u < (1ull << 31);
     if (tc && tc->dev && num_cu >= 2 && nt >= pf_min && off32) {  // (>= 8 workgroups: one per tile range at least)
         const int g = tc->wg_per_cu > 0 ? tc->wg_per_cu : IWP_WG;
@@ -1667,15 +1715,9 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) 
             tc->base[x] += (nt >> 3) + (x < (nt & 7u) ? 1u : 0u) + 2u * ((G + 7u - x) >> 3);
         }
         tc->started += G;
-        if (u8) {
-            if (a.first) hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, true, false, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
-            else if (a.flags && (uint64_t)a.enc_h * a.enc_w * 4u < (1ull << 31))
-                hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, true, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
-            else { a.flags = nullptr; hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, false, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb); }
-        } else if (a.first) hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
-        else if (a.flags && (uint64_t)a.enc_h * a.enc_w * 4u < (1ull << 31))
-            hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, true>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
-        else { a.flags = nullptr; hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb); }
+        if (px == PX_U16) launch_idwt_pf<F, LOM, HIM, PX_U16>(a, G, pad, st, gx, gy, ctr, cb);
+        else if (px == PX_U8) launch_idwt_pf<F, LOM, HIM, PX_U8>(a, G, pad, st, gx, gy, ctr, cb);
+        else launch_idwt_pf<F, LOM, HIM, PX_F64>(a, G, pad, st, gx, gy, ctr, cb);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {  // the launch did not happen: counters and book-keeping start over together
             (void)hipMemsetAsync(tc->dev, 0, TILECTR_WORDS * sizeof(uint32_t), st);
@@ -1684,7 +1726,8 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) 
         }
         return (int)e;
     }
-    if (u8) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, true>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
+    if (px == PX_U16) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, PX_U16>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
+    else if (px == PX_U8) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, PX_U8>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
     else hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
     return (int)hipGetLastError();
 }
@@ -1699,7 +1742,7 @@ static int launch_idwt_F(const IdwtKArgs &a, int planes, hipStream_t st, TileCtr
     return launch_idwt_FM<F, (1u << F) - 1u, (1u << F) - 1u>(a, planes, st, tc);
 }
 
-// a->px.in set: level 1 of an 8-bit picture, tiled routes only (the caller converts for the two-pass level)
+// a->px.in set: level 1 of an 8- or 16-bit picture, tiled routes only (the caller converts for the two-pass level)
 extern "C" int spiht_launch_dwt_level(const DwtKArgs *a, int planes, hipStream_t st) {
     switch (a->F) {
     case 2: return launch_dwt_F<2, 0x3u, 0x3u>(*a, planes, st);            // haar
@@ -1717,7 +1760,7 @@ extern "C" int spiht_launch_dwt_level(const DwtKArgs *a, int planes, hipStream_t
     }
 }
 // tc: tile counters of the calling context (nullptr: fixed-stride tile order in the persistent kernel); a->px.out set: level 1
-// into an 8-bit picture
+// into an 8- or 16-bit picture
 extern "C" int spiht_launch_idwt_level(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc) {
     switch (a->F) {
     case 2: return launch_idwt_F<2, 0x3u, 0x3u>(*a, planes, st, tc);            // haar
@@ -1763,35 +1806,39 @@ extern "C" int spiht_launch_dequant_plain(const int32_t *in, double *out, size_t
     return (int)hipGetLastError();
 }
 
-// ---- 8-bit pixels to and from dense float64, for the routes whose level 1 has no 8-bit form ------------------------------
+// ---- 8- and 16-bit pixels to and from dense float64, for the routes whose level 1 has no integer form ------------------------
 // (level 0, the two-pass levels, the colour model change in front of a two-pass level).  One thread per sample, the same
-// conversions as the fused kernels (px8_value / px8_store_value).
-__global__ __launch_bounds__(256) void k_u8_to_f64(Px8 px, double *__restrict__ out, int64_t n) {  // out [B*c, h, w]
+// conversions as the fused kernels (px_value / PX_STORE); the kind is the view's element size.
+template <int PX>
+__global__ __launch_bounds__(256) void k_px_to_f64(PxView px, double *__restrict__ out, int64_t n) {  // out [B*c, h, w]
     const int64_t hw = (int64_t)px.h * px.w;
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
         const int64_t p = t / hw, r = t - p * hw, y = r / px.w, x = r - y * px.w;
         const int64_t o = (p / px.c) * px.sb + (p % px.c) * px.sc + y * px.sh + x * px.sw;
-        out[t] = px8_value(px.in[o]);
+        out[t] = px_value<PX>(px_load<PX>(px.in + o));
     }
 }
-__global__ __launch_bounds__(256) void k_f64_to_u8(const double *__restrict__ in, int rec_h, int rec_w, Px8 px, int64_t n) {
+template <int PX>
+__global__ __launch_bounds__(256) void k_f64_to_px(const double *__restrict__ in, int rec_h, int rec_w, PxView px, int64_t n) {
     const int64_t hw = (int64_t)px.h * px.w;  // n = B*c*h*w: the cropped picture
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
         const int64_t p = t / hw, r = t - p * hw, y = r / px.w, x = r - y * px.w;
         const int64_t o = (p / px.c) * px.sb + (p % px.c) * px.sc + y * px.sh + x * px.sw;
-        px.out[o] = px8_store_value(in[(p * rec_h + y) * rec_w + x]);
+        PX_STORE(PX, px.out, o, in[(p * rec_h + y) * rec_w + x]);
     }
 }
 static unsigned pass_grid(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 8192); }
-extern "C" int spiht_launch_u8_to_f64(const Px8 *px, int64_t B, double *out, hipStream_t st) {
+extern "C" int spiht_launch_px_to_f64(const PxView *px, int64_t B, double *out, hipStream_t st) {
     const int64_t n = B * px->c * (int64_t)px->h * px->w;
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_u8_to_f64, dim3(pass_grid(n)), dim3(256), 0, st, *px, out, n);
+    if (px->es == 2) hipLaunchKernelGGL(k_px_to_f64<PX_U16>, dim3(pass_grid(n)), dim3(256), 0, st, *px, out, n);
+    else hipLaunchKernelGGL(k_px_to_f64<PX_U8>, dim3(pass_grid(n)), dim3(256), 0, st, *px, out, n);
     return (int)hipGetLastError();
 }
-extern "C" int spiht_launch_f64_to_u8(const double *in, int rec_h, int rec_w, const Px8 *px, int64_t B, hipStream_t st) {
+extern "C" int spiht_launch_f64_to_px(const double *in, int rec_h, int rec_w, const PxView *px, int64_t B, hipStream_t st) {
     const int64_t n = B * px->c * (int64_t)px->h * px->w;
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_f64_to_u8, dim3(pass_grid(n)), dim3(256), 0, st, in, rec_h, rec_w, *px, n);
+    if (px->es == 2) hipLaunchKernelGGL(k_f64_to_px<PX_U16>, dim3(pass_grid(n)), dim3(256), 0, st, in, rec_h, rec_w, *px, n);
+    else hipLaunchKernelGGL(k_f64_to_px<PX_U8>, dim3(pass_grid(n)), dim3(256), 0, st, in, rec_h, rec_w, *px, n);
     return (int)hipGetLastError();
 }

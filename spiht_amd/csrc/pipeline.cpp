@@ -30,14 +30,15 @@
         if (_s != SPIHT_OK) return _s; \
     } while (0)
 
-// The pictures of a step, in or out: float64 [B, c, H, W], or 8-bit (spiht_pipeline_submit_u8) laid out by byte strides
-// (none given: dense CHW).  The strides are copied: an output is written a step later.
+// The pictures of a step, in or out: float64 [B, c, H, W], or 8- / 16-bit (spiht_pipeline_submit_u8 / _u16) laid out by
+// byte strides (none given: dense CHW).  The strides are copied: an output is written a step later.
 struct StepPics {
     void *p = nullptr;
-    bool u8 = false, strided = false;
+    int es = 0;  // bytes per integer sample, 1 or 2; 0: float64
+    bool strided = false;
     int64_t st[4] = {0, 0, 0, 0};
     StepPics() = default;
-    StepPics(const void *p_, bool u8_, const int64_t *strides = nullptr) : p(const_cast<void *>(p_)), u8(u8_), strided(strides != nullptr) {
+    StepPics(const void *p_, int es_, const int64_t *strides = nullptr) : p(const_cast<void *>(p_)), es(es_), strided(strides != nullptr) {
         if (strides) memcpy(st, strides, sizeof(st));
     }
     const int64_t *strides() const { return strided ? st : nullptr; }
@@ -236,7 +237,14 @@ static int queue_inverse_coarse(spiht_pipeline *p, int s) {
     return SPIHT_OK;
 }
 static int queue_inverse_level1(spiht_pipeline *p, int s, const StepPics &out) {
-    if (out.u8) {
+    if (out.es == 2) {
+        if (p->approx)
+            CHK(spiht_idwt_level1_flags_batch_u16(p->Hc, p->rec[s], p->approx, p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode,
+                                                  p->level, p->q, p->mp(), (uint16_t *)out.p, out.strides()));
+        else
+            CHK(spiht_dequant_idwt_flags_batch_u16(p->Hc, p->rec[s], p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
+                                                   p->q, p->mp(), (uint16_t *)out.p, out.strides()));
+    } else if (out.es == 1) {
         if (p->approx)
             CHK(spiht_idwt_level1_flags_batch_u8(p->Hc, p->rec[s], p->approx, p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode,
                                                  p->level, p->q, p->mp(), (uint8_t *)out.p, out.strides()));
@@ -266,7 +274,10 @@ static int submit_impl(spiht_pipeline *p, const StepPics &in, const StepPics &ou
     const int s = (int)(p->step & 1), o = s ^ 1;
     spiht_ctx *L = p->Lc[s];
     // H: front half of the encoder
-    if (in.u8)
+    if (in.es == 2)
+        CHK(spiht_dwt_pyramid_batch_u16(p->Hc, (const uint16_t *)in.p, in.strides(), p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
+                                        p->q, p->mp(), p->coeffs[s], p->dmsb[s], p->lmsb[s], p->maxabs[s]));
+    else if (in.es == 1)
         CHK(spiht_dwt_pyramid_batch_u8(p->Hc, (const uint8_t *)in.p, in.strides(), p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
                                        p->q, p->mp(), p->coeffs[s], p->dmsb[s], p->lmsb[s], p->maxabs[s]));
     else
@@ -329,7 +340,7 @@ extern "C" int spiht_pipeline_submit_gather(spiht_pipeline *p, const double *d_i
     HScope sc(p);
     int st = sc.st;
     if (st == SPIHT_OK)
-        st = submit_impl(p, StepPics(d_img, false), StepPics(d_img_out, false), d_out, d_nbits, d_max_n, comm, d_all_slots, d_all_nbits,
+        st = submit_impl(p, StepPics(d_img, 0), StepPics(d_img_out, 0), d_out, d_nbits, d_max_n, comm, d_all_slots, d_all_nbits,
                          d_all_max_n, rank);
     // a failure between the first and the last queued call leaves events, buffer sets and the pending inverse transform half
     // advanced: nothing later can be trusted, and every later call says so with the first error
@@ -342,18 +353,29 @@ extern "C" int spiht_pipeline_submit(spiht_pipeline *p, const double *d_img, uin
     return spiht_pipeline_submit_gather(p, d_img, d_out, d_nbits, d_max_n, d_img_out, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
-extern "C" int spiht_pipeline_submit_u8(spiht_pipeline *p, const uint8_t *d_img, const int64_t *in_strides, uint8_t *d_out,
-                                        uint64_t *d_nbits, uint8_t *d_max_n, uint8_t *d_img_out, const int64_t *out_strides) {
+// a step of 8- or 16-bit pictures (es: bytes per sample)
+static int submit_px(spiht_pipeline *p, int es, const void *d_img, const int64_t *in_strides, uint8_t *d_out, uint64_t *d_nbits,
+                     uint8_t *d_max_n, void *d_img_out, const int64_t *out_strides) {
     if (!p || !d_img || !d_out || !d_nbits || !d_max_n || !d_img_out) return SPIHT_ERR_ARG;
     if (p->poisoned != SPIHT_OK) return p->poisoned;
     // the views are checked before anything is queued: a bad one leaves the pipeline as it was
-    if (in_strides) CHK(spiht_check_view_u8(p->B, p->c, p->H, p->W, in_strides, 0));
-    if (out_strides) CHK(spiht_check_view_u8(p->B, p->c, p->H, p->W, out_strides, 1));
+    const auto check = es == 2 ? spiht_check_view_u16 : spiht_check_view_u8;
+    if ((uintptr_t)d_img % (uintptr_t)es != 0 || (uintptr_t)d_img_out % (uintptr_t)es != 0) return SPIHT_ERR_ARG;
+    if (in_strides) CHK(check(p->B, p->c, p->H, p->W, in_strides, 0));
+    if (out_strides) CHK(check(p->B, p->c, p->H, p->W, out_strides, 1));
     HScope sc(p);
     int st = sc.st;
-    if (st == SPIHT_OK) st = submit_impl(p, StepPics(d_img, true, in_strides), StepPics(d_img_out, true, out_strides), d_out, d_nbits, d_max_n);
+    if (st == SPIHT_OK) st = submit_impl(p, StepPics(d_img, es, in_strides), StepPics(d_img_out, es, out_strides), d_out, d_nbits, d_max_n);
     if (st != SPIHT_OK) p->poisoned = st;
     return st;
+}
+extern "C" int spiht_pipeline_submit_u8(spiht_pipeline *p, const uint8_t *d_img, const int64_t *in_strides, uint8_t *d_out,
+                                        uint64_t *d_nbits, uint8_t *d_max_n, uint8_t *d_img_out, const int64_t *out_strides) {
+    return submit_px(p, 1, d_img, in_strides, d_out, d_nbits, d_max_n, d_img_out, out_strides);
+}
+extern "C" int spiht_pipeline_submit_u16(spiht_pipeline *p, const uint16_t *d_img, const int64_t *in_strides, uint8_t *d_out,
+                                         uint64_t *d_nbits, uint8_t *d_max_n, uint16_t *d_img_out, const int64_t *out_strides) {
+    return submit_px(p, 2, d_img, in_strides, d_out, d_nbits, d_max_n, d_img_out, out_strides);
 }
 
 extern "C" int spiht_pipeline_flush(spiht_pipeline *p) {

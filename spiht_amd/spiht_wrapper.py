@@ -163,7 +163,7 @@ def encode_image(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSetting
 
 
 def _encode_host(ctx, fn, pixels, chw, g, wid, mid, level, spiht_settings, mults_p, max_bits):
-    """the tail of encode_image / encode_image_u8: one C call fn(ctx, *pixels, c, h, w, ...) -- upload, DWT + quantise +
+    """the tail of encode_image / encode_image_u8 / encode_image_u16: one C call fn(ctx, *pixels, c, h, w, ...) -- upload, DWT + quantise +
     pyramid + list coder, stream back (the context keeps its device buffers) -- into a buffer of the stream's bound"""
     c, h, w = chw
     bound = C.c_uint64()
@@ -206,7 +206,7 @@ def _check_version(encoding_result):
 
 
 def _decode_args(encoding_result, spiht_settings):
-    """the checks decode_image and decode_image_u8 share, in their order -> (geometry, the arrays the pointers point into --
+    """the checks decode_image, decode_image_u8 and decode_image_u16 share, in their order -> (geometry, the arrays the pointers point into --
     kept by the caller until the call --, the arguments of the C call from the stream to the channel scales)"""
     h, w, c, level = encoding_result.h, encoding_result.w, encoding_result.c, encoding_result.level
     wid, mid = _wavelet_mode_ids(spiht_settings)
@@ -220,27 +220,52 @@ def _decode_args(encoding_result, spiht_settings):
                float(spiht_settings.quantization_scale), mults_p)
 
 
-def check_u8_view(shape, strides, output):
-    """The library's rule for an 8-bit view (include/spiht_hip.h, *_u8; spiht_check_view_u8): byte strides of a (B, c, h, w)
-    or (c, h, w) `shape` are non-negative, and a view that is written does not overlap itself -- sorted by stride, every
-    dimension longer than one steps past the largest offset the smaller ones reach.  Raises ValueError.  No device needed."""
+def _check_int_view(bits, shape, strides, output):
+    """check_u8_view / check_u16_view: `bits` 8 or 16"""
     shape, strides = [int(x) for x in shape], [int(x) for x in strides]
     if len(shape) != len(strides) or len(shape) not in (3, 4):
         raise ValueError("%d strides for a %d-dimensional picture" % (len(strides), len(shape)))
     if len(shape) == 3:
         shape, strides = [1] + shape, [0] + strides
     if min(shape) < 1:
-        raise ValueError("empty 8-bit picture %s" % (shape,))
+        raise ValueError("empty %d-bit picture %s" % (bits, shape))
     st = np.ascontiguousarray(strides, dtype=np.int64)
-    if _lib.lib().spiht_check_view_u8(shape[0], shape[1], shape[2], shape[3], C.c_void_p(st.ctypes.data), int(bool(output))):
-        raise ValueError("the strides %s of the 8-bit %s %s are not supported (negative%s)"
-                         % (strides, "output" if output else "input", shape, ", or overlapping" if output else ""))
+    fn = _lib.lib().spiht_check_view_u16 if bits == 16 else _lib.lib().spiht_check_view_u8
+    if fn(shape[0], shape[1], shape[2], shape[3], C.c_void_p(st.ctypes.data), int(bool(output))):
+        raise ValueError("the strides %s of the %d-bit %s %s are not supported (negative%s%s)"
+                         % (strides, bits, "output" if output else "input", shape, ", odd" if bits == 16 else "",
+                            ", or overlapping" if output else ""))
 
 
-def _u8_picture(image, spiht_settings):
-    """checks of encode_image_u8: a uint8 (c, h, w) array (or (h, w, c) given as such a view); negative strides copied"""
-    if not isinstance(image, np.ndarray) or image.dtype != np.uint8:
-        raise ValueError("encode_image_u8 takes a uint8 array, not %s" % (getattr(image, "dtype", type(image)),))
+def check_u8_view(shape, strides, output):
+    """The library's rule for an 8-bit view (include/spiht_hip.h, *_u8; spiht_check_view_u8): byte strides of a (B, c, h, w)
+    or (c, h, w) `shape` are non-negative, and a view that is written does not overlap itself -- sorted by stride, every
+    dimension longer than one steps past the largest offset the smaller ones reach.  Raises ValueError.  No device needed."""
+    _check_int_view(8, shape, strides, output)
+
+
+def check_u16_view(shape, strides, output):
+    """The library's rule for a 16-bit view (include/spiht_hip.h, *_u16; spiht_check_view_u16): as check_u8_view, the strides
+    still in BYTES (numpy's .strides as they are) and all of them even; the overlap rule counts a sample's two bytes."""
+    _check_int_view(16, shape, strides, output)
+
+
+def _check_aligned(ptr, dtype):
+    """a uint16 picture starts at an even address (the 16-bit loads and stores of the device)"""
+    if int(ptr) % np.dtype(dtype).itemsize:
+        raise ValueError("the %d-bit picture at address %#x is not aligned to its samples" % (8 * np.dtype(dtype).itemsize, int(ptr)))
+
+
+def _is_dtype(a, dtype):
+    """a numpy array of `dtype` in either byte order"""
+    return isinstance(a, np.ndarray) and a.dtype.newbyteorder("=") == np.dtype(dtype)
+
+
+def _int_picture(image, spiht_settings, dtype, name):
+    """checks of encode_image_u8 / encode_image_u16: a (c, h, w) array of `dtype` (or (h, w, c) given as such a view);
+    negative strides and the other byte order are copied into a native contiguous array"""
+    if not _is_dtype(image, dtype):
+        raise ValueError("%s takes a %s array, not %s" % (name, np.dtype(dtype).name, getattr(image, "dtype", type(image)),))
     if image.ndim != 3:
         raise ValueError('image ndim must be 3: c,h,w')
     if spiht_settings.color_model is not None:
@@ -248,19 +273,19 @@ def _u8_picture(image, spiht_settings):
             color_models.convert(np.zeros((3, 1, 1)), 'RGB', spiht_settings.color_model)  # the reference's ValueError
         if image.shape[0] != 3:
             raise ValueError("colour conversion needs 3 channels")
-    if any(st < 0 for st in image.strides):
-        image = np.ascontiguousarray(image)
+    if any(st < 0 for st in image.strides) or not image.dtype.isnative:
+        image = np.ascontiguousarray(image, dtype=np.dtype(dtype).newbyteorder("="))
     return image
 
 
-def encode_image_u8(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSettings(), level: Optional[int] = None,
-                    max_bits: Optional[int] = None, channels_last: bool = False):
-    """8-bit pixels: the EncodingResult of encode_image(image / 255.0, ...), field by field, with the conversion done on the
-    device (only the bytes cross the link).  image: uint8 (c, h, w), or (h, w, c) with channels_last -- any strides (an
-    RGBA buffer's rgba[..., :3] view goes as it is)."""
-    if isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and channels_last:
+def _u8_picture(image, spiht_settings):
+    return _int_picture(image, spiht_settings, np.uint8, "encode_image_u8")
+
+
+def _encode_image_int(image, spiht_settings, level, max_bits, channels_last, dtype, name, fn_name):
+    if _is_dtype(image, dtype) and image.ndim == 3 and channels_last:
         image = image.transpose(2, 0, 1)
-    image = _u8_picture(image, spiht_settings)
+    image = _int_picture(image, spiht_settings, dtype, name)
     c, h, w = image.shape
     wid, mid = _wavelet_mode_ids(spiht_settings)
     g = _geometry(h, w, wid, level, mid)
@@ -269,26 +294,56 @@ def encode_image_u8(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSett
         max_bits = 99999999999999999
     max_bits = spiht_rs._as_usize(max_bits, "max_bits")
     strides = np.array(image.strides, dtype=np.int64)
-    return _encode_host(_lib.default_context(), _lib.lib().spiht_encode_image_host_u8,
+    _check_int_view(8 * np.dtype(dtype).itemsize, image.shape, strides, False)
+    _check_aligned(image.ctypes.data, dtype)
+    return _encode_host(_lib.default_context(), getattr(_lib.lib(), fn_name),
                         (C.c_void_p(image.ctypes.data), C.c_void_p(strides.ctypes.data)), (c, h, w), g, wid, mid, level,
                         spiht_settings, mults_p, max_bits)
 
 
-def decode_image_u8(encoding_result: EncodingResult, spiht_settings: SpihtSettings, channels_last: bool = False) -> np.ndarray:
-    """8-bit pixels: (np.clip(decode_image(r, s), 0, 1) * 255).astype(np.uint8) cropped to the encoded picture's h x w, with
-    the conversion done on the device.  Returns a new uint8 array (c, h, w), or (h, w, c) with channels_last."""
+def _decode_image_int(encoding_result, spiht_settings, channels_last, dtype, fn_name):
     _check_version(encoding_result)
     h, w, c = encoding_result.h, encoding_result.w, encoding_result.c
     if spiht_settings.color_model is not None and c != 3:
         raise ValueError("colour conversion needs 3 channels")
     _, keep, args = _decode_args(encoding_result, spiht_settings)
-    out = _lib.result_array((h, w, c) if channels_last else (c, h, w), np.uint8)
-    strides = np.array((1, w * c, c) if channels_last else (h * w, w, 1), dtype=np.int64)
+    out = _lib.result_array((h, w, c) if channels_last else (c, h, w), dtype)
+    strides = np.array((1, w * c, c) if channels_last else (h * w, w, 1), dtype=np.int64) * np.dtype(dtype).itemsize
     ctx = _lib.default_context()
     with color_models.fused(ctx, spiht_settings.color_model):
-        _lib.check(_lib.lib().spiht_decode_image_host_u8(ctx.handle, *args, C.c_void_p(out.ctypes.data),
-                                                         C.c_void_p(strides.ctypes.data)))
+        _lib.check(getattr(_lib.lib(), fn_name)(ctx.handle, *args, C.c_void_p(out.ctypes.data), C.c_void_p(strides.ctypes.data)))
     return out
+
+
+def encode_image_u8(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSettings(), level: Optional[int] = None,
+                    max_bits: Optional[int] = None, channels_last: bool = False):
+    """8-bit pixels: the EncodingResult of encode_image(image / 255.0, ...), field by field, with the conversion done on the
+    device (only the bytes cross the link).  image: uint8 (c, h, w), or (h, w, c) with channels_last -- any strides (an
+    RGBA buffer's rgba[..., :3] view goes as it is)."""
+    return _encode_image_int(image, spiht_settings, level, max_bits, channels_last, np.uint8, "encode_image_u8",
+                             "spiht_encode_image_host_u8")
+
+
+def decode_image_u8(encoding_result: EncodingResult, spiht_settings: SpihtSettings, channels_last: bool = False) -> np.ndarray:
+    """8-bit pixels: (np.clip(decode_image(r, s), 0, 1) * 255).astype(np.uint8) cropped to the encoded picture's h x w, with
+    the conversion done on the device.  Returns a new uint8 array (c, h, w), or (h, w, c) with channels_last."""
+    return _decode_image_int(encoding_result, spiht_settings, channels_last, np.uint8, "spiht_decode_image_host_u8")
+
+
+def encode_image_u16(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSettings(), level: Optional[int] = None,
+                     max_bits: Optional[int] = None, channels_last: bool = False):
+    """16-bit pixels: the EncodingResult of encode_image(image / 65535.0, ...), field by field, with the conversion done on
+    the device (two bytes per sample cross the link).  image: uint16 (c, h, w), or (h, w, c) with channels_last -- any
+    non-negative strides (a 16-bit RGBA buffer's rgba[..., :3] view goes as it is); the other byte order is copied."""
+    return _encode_image_int(image, spiht_settings, level, max_bits, channels_last, np.uint16, "encode_image_u16",
+                             "spiht_encode_image_host_u16")
+
+
+def decode_image_u16(encoding_result: EncodingResult, spiht_settings: SpihtSettings, channels_last: bool = False) -> np.ndarray:
+    """16-bit pixels: (np.clip(decode_image(r, s), 0, 1) * 65535).astype(np.uint16) cropped to the encoded picture's h x w,
+    with the conversion done on the device.  Returns a new uint16 array (c, h, w), or (h, w, c) with channels_last.  The
+    stream may come from any pixel format."""
+    return _decode_image_int(encoding_result, spiht_settings, channels_last, np.uint16, "spiht_decode_image_host_u16")
 
 
 def _band_sizes(h, w, wavelet, levels, mode="reflect"):
