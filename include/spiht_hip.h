@@ -474,6 +474,67 @@ int spiht_decode_image_host_u16(spiht_ctx *ctx, const uint8_t *data, uint64_t nb
                                 uint16_t *img_out, const int64_t *strides);
 
 /* ---------------------------------------------------------------------------------------
+ * Reduced-resolution decode: the picture at 1/2^reduce size straight from a stream (what JPEG 2000 calls resolution
+ * levels).  The coefficient array is a Mallat pyramid, and pywt.waverec2 passes through the picture at 1/2, 1/4, ... size
+ * on its way up: a reduced decode runs levels L .. reduce + 1 of the inverse transform and nothing below, 0 <= reduce <= L
+ * (L: the levels used; anything else: SPIHT_ERR_ARG before anything is queued).  With hs[l], ws[l] the band sizes of the
+ * geometry (hs[0] = H), F the filter length (2 under periodization) and D = (rec / channel_mults) / q_scale:
+ *   float64   R = pywt.waverec2(coeffs[:L - reduce + 1], wavelet, mode) * 2^-reduce, uncropped as the full-size calls:
+ *             [c, 2 hs[reduce+1] - F + 2, 2 ws[reduce+1] - F + 2]; reduce == L: D[:, :ll_h, :ll_w] * 2^-L.  The factor
+ *             takes out the approximation band's DC gain of 2 per level; it is applied as q_scale * 2^reduce, which is
+ *             exact (a q_scale for which that overflows: SPIHT_ERR_ARG).  reduce == 0: the full-size call in every bit.
+ *   colour    with spiht_ctx_set_color3 set, the model -> RGB change per pixel of R (three channels)
+ *   8/16-bit  (uintN)(clip(R, 0, 1) * 255 or 65535) cropped to [c, hs[reduce], ws[reduce]]: the rule of the *_u8 / *_u16
+ *             calls one pyramid level up; strides are those of that picture
+ * R is PyWavelets' approximation band: it carries a rim of extension samples, hs[reduce] >= ceil(H / 2^reduce).
+ * The list decoder parses every bit whatever the resolution; what is saved is the inverse transform's fine levels, their
+ * HBM traffic and the bytes of the picture. */
+/* Sizes of a reduced decode; pure arithmetic, no device.  rec_h x rec_w: the float64 picture; pic_h x pic_w: the integer
+ * picture (hs[reduce] x ws[reduce]); in_h x in_w = ceil(H / 2^reduce) x ceil(W / 2^reduce), the size a 2^reduce-fold
+ * downsampling of the picture has, and off_y, off_x where that window lies centred in either picture:
+ * (pic - in) / 2, rounded down; 0 under periodization.  Output pointers may be NULL. */
+int spiht_reduced_shape(int64_t H, int64_t W, int wavelet, int mode, int level, int reduce, int *level_used, int64_t *rec_h,
+                        int64_t *rec_w, int64_t *pic_h, int64_t *pic_w, int64_t *off_y, int64_t *off_x, int64_t *in_h,
+                        int64_t *in_w);
+/* spiht_dequant_idwt_batch_f64 / spiht_dequant_idwt_flags_batch_u8 / _u16 (without occupancy words: they belong to level 1)
+ * at reduced size: device coefficient arrays [B, c, enc_h, enc_w] -> pictures.  Asynchronous. */
+int spiht_dequant_idwt_reduced_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H, int64_t W,
+                                         int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                         double *d_img_out, int reduce);
+int spiht_dequant_idwt_reduced_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H, int64_t W,
+                                        int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                        uint8_t *d_img_out, const int64_t *out_strides, int reduce);
+int spiht_dequant_idwt_reduced_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H, int64_t W,
+                                         int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                         uint16_t *d_img_out, const int64_t *out_strides, int reduce);
+/* spiht_decode_image_batch_f64 / _u8 / _u16 at reduced size: streams in device slots -> pictures.  Asynchronous as those;
+ * the internal coefficient array is left all zero, as after a full-size call. */
+int spiht_decode_image_reduced_batch_f64(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
+                                         const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
+                                         int mode, int level, double q_scale, const double *channel_mults, double *d_img_out,
+                                         int32_t *d_rec, int reduce);
+int spiht_decode_image_reduced_batch_u8(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
+                                        const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
+                                        int mode, int level, double q_scale, const double *channel_mults, uint8_t *d_img_out,
+                                        const int64_t *out_strides, int32_t *d_rec, int reduce);
+int spiht_decode_image_reduced_batch_u16(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
+                                         const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
+                                         int mode, int level, double q_scale, const double *channel_mults, uint16_t *d_img_out,
+                                         const int64_t *out_strides, int32_t *d_rec, int reduce);
+/* spiht_decode_image_host_f64 / _u8 / _u16 at reduced size: one stream in a host array -> one picture in a host array of the
+ * reduced size (img_out: float64 [c, rec_h, rec_w]; integer [c, pic_h, pic_w], dense CHW or HWC): only the reduced
+ * picture's bytes cross the link.  Synchronous. */
+int spiht_decode_image_reduced_host_f64(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H,
+                                        int64_t W, int wavelet, int mode, int level, double q_scale,
+                                        const double *channel_mults, double *img_out, int reduce);
+int spiht_decode_image_reduced_host_u8(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H,
+                                       int64_t W, int wavelet, int mode, int level, double q_scale,
+                                       const double *channel_mults, uint8_t *img_out, const int64_t *strides, int reduce);
+int spiht_decode_image_reduced_host_u16(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H,
+                                        int64_t W, int wavelet, int mode, int level, double q_scale,
+                                        const double *channel_mults, uint16_t *img_out, const int64_t *strides, int reduce);
+
+/* ---------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, every rank codes its own images (the reference's encode / decode
  * are pure functions of one image, src/lib.rs:24-42 -- nothing is exchanged while coding); the ONE exchange of the
  * path is the gather of the finished streams.  It runs on RCCL (ncclAllGather over xGMI), inside this library, on

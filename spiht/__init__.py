@@ -20,4 +20,7 @@ del _name, _mod
 
 globals().update({_k: getattr(_impl, _k) for _k in ("encode_image", "decode_image", "EncodingResult", "SpihtSettings",
                                                     "ENCODER_DECODER_VERSION", "encode", "decode")})
+# beyond the reference's names: the reduced-resolution decode
+globals().update({_k: getattr(_impl, _k) for _k in ("decode_image_reduced", "decode_image_reduced_u8",
+                                                    "decode_image_reduced_u16", "reduced_shape")})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

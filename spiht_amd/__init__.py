@@ -9,5 +9,6 @@ _lib_mod.lib()  # fail at import time, not at first use, when the HIP library ha
 
 from .spiht_wrapper import (encode_image, decode_image, EncodingResult, SpihtSettings,  # noqa: E402,F401
                             ENCODER_DECODER_VERSION, encode_image_u8, decode_image_u8,
-                            encode_image_u16, decode_image_u16)
+                            encode_image_u16, decode_image_u16, decode_image_reduced, decode_image_reduced_u8,
+                            decode_image_reduced_u16, reduced_shape)
 from .spiht import encode, decode  # noqa: E402,F401

@@ -57,6 +57,10 @@ SYMBOLS = [
     "spiht_encode_image_batch_u16", "spiht_decode_image_batch_u16", "spiht_encode_image_host_u16", "spiht_decode_image_host_u16",
     "spiht_dwt_pyramid_batch_u16", "spiht_dequant_idwt_flags_batch_u16", "spiht_idwt_level1_flags_batch_u16", "spiht_pipeline_submit_u16",
     "spiht_check_view_u16",
+    "spiht_reduced_shape",
+    "spiht_dequant_idwt_reduced_batch_f64", "spiht_dequant_idwt_reduced_batch_u8", "spiht_dequant_idwt_reduced_batch_u16",
+    "spiht_decode_image_reduced_batch_f64", "spiht_decode_image_reduced_batch_u8", "spiht_decode_image_reduced_batch_u16",
+    "spiht_decode_image_reduced_host_f64", "spiht_decode_image_reduced_host_u8", "spiht_decode_image_reduced_host_u16",
 ]
 
 
@@ -190,6 +194,14 @@ def lib():
         L.spiht_idwt_level1_flags_batch_u8.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp]
         L.spiht_pipeline_submit_u8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         L.spiht_check_view_u8.argtypes = [i64, i64, i64, i64, vp, i32]
+        # reduced-resolution decode: the full-size call's arguments, then `reduce`
+        L.spiht_reduced_shape.argtypes = [i64, i64, i32, i32, i32, i32, C.POINTER(i32)] + [C.POINTER(i64)] * 8
+        L.spiht_dequant_idwt_reduced_batch_f64.argtypes = L.spiht_dequant_idwt_batch_f64.argtypes + [i32]
+        L.spiht_dequant_idwt_reduced_batch_u8.argtypes = [vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp, i32]
+        L.spiht_decode_image_reduced_batch_f64.argtypes = L.spiht_decode_image_batch_f64.argtypes + [i32]
+        L.spiht_decode_image_reduced_batch_u8.argtypes = L.spiht_decode_image_batch_u8.argtypes + [i32]
+        L.spiht_decode_image_reduced_host_f64.argtypes = L.spiht_decode_image_host_f64.argtypes + [i32]
+        L.spiht_decode_image_reduced_host_u8.argtypes = L.spiht_decode_image_host_u8.argtypes + [i32]
         # 16-bit pixels: every *_u16 call takes what its *_u8 sibling takes
         for name in SYMBOLS:
             if name.endswith("_u16"):

@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib, color_models
 from . import spiht as spiht_rs
 from .spiht_wrapper import (EncodingResult, SpihtSettings, _geometry, _metadata_boxes, _mults_arg, _wavelet_mode_ids,
-                            check_u8_view, _check_int_view, _check_aligned, _is_dtype)
+                            check_u8_view, _check_int_view, _check_aligned, _is_dtype, reduced_shape)
 
 
 class DeviceArray:
@@ -226,6 +226,79 @@ class BatchCodec:
         """list of EncodingResult (same geometry) -> uint16 [B, c, H, W] (or [B, H, W, c]), cropped to H x W"""
         return self._decode_int(np.uint16, results, channels_last)
 
+    # ---- reduced-resolution decode (include/spiht_hip.h, *_reduced_*): pictures at 1/2^reduce size, 0 <= reduce <= L.
+    # What spiht_wrapper.decode_image_reduced* return, for B streams in one queue of kernels. ------------------------------
+    def reduced_shape(self, reduce):
+        """spiht_wrapper.reduced_shape of the codec's pictures"""
+        return reduced_shape(self.H, self.W, self.settings, self.level, reduce)
+
+    def decode_reduced_device(self, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, d_rec=None, slot_stride=None):
+        """decode_device at 1/2^reduce size -> float64 [B, c, rec_h, rec_w] on the device (reduced_shape)"""
+        self.reduced_shape(reduce)
+        with self._color():
+            _lib.check(self.L.spiht_decode_image_reduced_batch_f64(
+                self.ctx.handle, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
+                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
+                float(self.settings.quantization_scale), self._mults_p, C.c_void_p(d_img_out),
+                C.c_void_p(d_rec) if d_rec else None, int(reduce)))
+
+    def _decode_reduced_device_int(self, dtype, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides, d_rec, slot_stride):
+        rs = self.reduced_shape(reduce)
+        st = st_p = None
+        if strides is not None:
+            st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
+            _check_int_view(8 * np.dtype(dtype).itemsize, (int(B), self.c, rs["pic_h"], rs["pic_w"]), st, True)
+            st_p = C.c_void_p(st.ctypes.data)
+        _check_aligned(d_img_out, dtype)
+        fn = (self.L.spiht_decode_image_reduced_batch_u16 if np.dtype(dtype).itemsize == 2
+              else self.L.spiht_decode_image_reduced_batch_u8)
+        with self._color():
+            _lib.check(fn(
+                self.ctx.handle, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
+                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
+                self.c, self.H, self.W, self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
+                C.c_void_p(d_img_out), st_p, C.c_void_p(d_rec) if d_rec else None, int(reduce)))
+
+    def decode_reduced_device_u8(self, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides=None, d_rec=None,
+                                 slot_stride=None):
+        """-> uint8 [B, c, pic_h, pic_w] on the device (reduced_shape), laid out by `strides` (bytes; None: dense CHW; what
+        lies between the view's elements is not written)"""
+        self._decode_reduced_device_int(np.uint8, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides, d_rec, slot_stride)
+
+    def decode_reduced_device_u16(self, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides=None, d_rec=None,
+                                  slot_stride=None):
+        """-> uint16 [B, c, pic_h, pic_w] on the device, laid out by `strides` (BYTES, all even; None: dense CHW)"""
+        self._decode_reduced_device_int(np.uint16, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides, d_rec, slot_stride)
+
+    def decode_reduced(self, results, reduce, crop=False):
+        """list of EncodingResult (same geometry) -> float64 [B, c, rec_h, rec_w]: decode_image_reduced of each; crop=True:
+        the centred in_h x in_w window (a view)"""
+        rs = self.reduced_shape(reduce)
+        out = self._decode_host(results, (self.c, rs["rec_h"], rs["rec_w"]), np.float64,
+                                lambda *a, slot_stride: self.decode_reduced_device(*a, reduce, slot_stride=slot_stride))
+        if not crop:
+            return out
+        return out[:, :, rs["off_y"]:rs["off_y"] + rs["in_h"], rs["off_x"]:rs["off_x"] + rs["in_w"]]
+
+    def _decode_reduced_int(self, dtype, results, reduce, crop, channels_last):
+        rs = self.reduced_shape(reduce)
+        c, h, w, es = self.c, rs["pic_h"], rs["pic_w"], np.dtype(dtype).itemsize
+        strides = (h * w * c * es, es, w * c * es, c * es) if channels_last else None
+        out = self._decode_host(results, (h, w, c) if channels_last else (c, h, w), dtype,
+                                lambda *a, slot_stride: self._decode_reduced_device_int(dtype, *a, reduce, strides, None, slot_stride))
+        if not crop:
+            return out
+        ys, xs = slice(rs["off_y"], rs["off_y"] + rs["in_h"]), slice(rs["off_x"], rs["off_x"] + rs["in_w"])
+        return out[:, ys, xs, :] if channels_last else out[:, :, ys, xs]
+
+    def decode_reduced_u8(self, results, reduce, crop=False, channels_last=False):
+        """list of EncodingResult -> uint8 [B, c, pic_h, pic_w] (or [B, pic_h, pic_w, c]): decode_image_reduced_u8 of each"""
+        return self._decode_reduced_int(np.uint8, results, reduce, crop, channels_last)
+
+    def decode_reduced_u16(self, results, reduce, crop=False, channels_last=False):
+        """list of EncodingResult -> uint16 [B, c, pic_h, pic_w] (or [B, pic_h, pic_w, c]): decode_image_reduced_u16 of each"""
+        return self._decode_reduced_int(np.uint16, results, reduce, crop, channels_last)
+
     def nbits_to_nbytes(self, d_nbits, B, d_nbytes):
         _lib.check(self.L.spiht_nbits_to_nbytes(self.ctx.handle, C.c_void_p(d_nbits), int(B), C.c_void_p(d_nbytes)))
 
@@ -310,15 +383,20 @@ class BatchCodec:
         d[2].upload(np.array([r.max_n for r in results], dtype=np.uint8))
         return stride, d
 
-    def decode_prefixes(self, result, byte_lengths, one_walk=True):
+    def decode_prefixes(self, result, byte_lengths, one_walk=True, reduce=0):
         """Progressive decoding (the pattern of the reference's make_gif.py:46-61): the pictures of the
         prefixes `result.encoded_bytes[:k]` for every k in byte_lengths -> float64 [K,c,H',W'] (in the order given).
         one_walk (default): the stream is walked ONCE, to the longest prefix, and every tree node replays its operations
         into the K coefficient arrays (spiht_decode_budgets_dev_i32); then one batched inverse transform.
-        one_walk=False: K streams in one batch, every prefix decoded by its own workgroup (K walks on K CUs)."""
+        one_walk=False: K streams in one batch, every prefix decoded by its own workgroup (K walks on K CUs).
+        reduce: the pictures at 1/2^reduce size (decode_reduced: float64 [K,c,rec_h,rec_w]) -- preview frames at thumbnail
+        size; the walk is the same, the inverse transform of the K arrays stops `reduce` levels early."""
         lens = [int(k) for k in byte_lengths]
+        rs = self.reduced_shape(reduce) if reduce else None
         if not one_walk or not lens:
             pre = [EncodingResult(result.encoded_bytes[:k], result.h, result.w, result.c, result.max_n, result.level) for k in lens]
+            if reduce:
+                return self.decode_reduced(pre, reduce) if pre else np.zeros((0, self.c, rs["rec_h"], rs["rec_w"]))
             return self.decode(pre)
         g = self.geom
         K = len(lens)
@@ -327,15 +405,18 @@ class BatchCodec:
         bud = np.ascontiguousarray([8 * min(lens[i], total) for i in order], dtype=np.uint64)
         data = np.frombuffer(result.encoded_bytes[:max(min(k, total) for k in lens)], dtype=np.uint8)
         d_rec = DeviceArray(self.ctx, (K, self.c, g["enc_h"], g["enc_w"]), np.int32)
-        d_img = DeviceArray(self.ctx, (K, self.c, g["rec_h"], g["rec_w"]), np.float64)
+        d_img = DeviceArray(self.ctx, (K, self.c) + ((rs["rec_h"], rs["rec_w"]) if reduce else (g["rec_h"], g["rec_w"])), np.float64)
         try:
             _lib.check(self.L.spiht_decode_budgets_dev_i32(
                 self.ctx.handle, C.c_void_p(data.ctypes.data if data.size else 0), data.size, int(result.max_n), self.c,
                 g["enc_h"], g["enc_w"], g["ll_h"], g["ll_w"], C.c_void_p(bud.ctypes.data), K, C.c_void_p(d_rec.ptr)))
+            idwt_args = (self.ctx.handle, C.c_void_p(d_rec.ptr), K, self.c, self.H, self.W, self.wid, self.mid, self._lv,
+                         float(self.settings.quantization_scale), self._mults_p, C.c_void_p(d_img.ptr))
             with self._color():
-                _lib.check(self.L.spiht_dequant_idwt_batch_f64(
-                    self.ctx.handle, C.c_void_p(d_rec.ptr), K, self.c, self.H, self.W, self.wid, self.mid, self._lv,
-                    float(self.settings.quantization_scale), self._mults_p, C.c_void_p(d_img.ptr)))
+                if reduce:
+                    _lib.check(self.L.spiht_dequant_idwt_reduced_batch_f64(*idwt_args, int(reduce)))
+                else:
+                    _lib.check(self.L.spiht_dequant_idwt_batch_f64(*idwt_args))
             self.ctx.synchronize()
             out = d_img.download()
         finally:

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -48,6 +49,7 @@ int spiht_launch_quant_plain(const double *in, int32_t *out, size_t n_per_plane,
                              double q, uint32_t *maxabs, hipStream_t st);
 int spiht_launch_zero_pads(int L, const int64_t *hs, const int64_t *ws, const int64_t *offh, const int64_t *offw, int enc_h,
                            int enc_w, int32_t *coeffs, int planes, hipStream_t st);
+int spiht_launch_ll_to_pic(const LlPicArgs *a, int planes, hipStream_t st);
 int spiht_launch_dequant_plain(const int32_t *in, double *out, size_t n_per_plane, int planes, int c,
                                const double *mults, double q, hipStream_t st);
 }
@@ -227,6 +229,7 @@ struct ImgGeom {
     int64_t offh[SPIHT_MAX_LEVELS + 1], offw[SPIHT_MAX_LEVELS + 1];  // detail block offsets per level
     int64_t ll_h, ll_w, enc_h, enc_w, rec_H, rec_W;
     bool per;  // periodization: ceil(n / 2) coefficients per level and 2 n samples back (the rule below with a two-tap filter)
+    int l0;    // levels dropped below level 1 of this geometry (reduced_geometry; 0: level 1 is the picture's own)
 };
 
 // mode: only periodization changes the geometry (pywt.dwt_coeff_len); the level count follows the real filter length whatever
@@ -237,6 +240,7 @@ static int img_geometry(int64_t H, int64_t W, int F_real, int level, ImgGeom *g,
     if (L < 0) L = std::min(dwt_max_level(H, F_real), dwt_max_level(W, F_real));
     if (L > SPIHT_MAX_LEVELS) return SPIHT_ERR_ARG;
     g->per = mode == SPIHT_MODE_PERIODIZATION;
+    g->l0 = 0;
     const int F = g->per ? 2 : F_real;
     g->L = L;
     g->hs[0] = H;
@@ -263,6 +267,37 @@ static int img_geometry(int64_t H, int64_t W, int F_real, int level, ImgGeom *g,
     }
     g->rec_H = rh;
     g->rec_W = rw;
+    return SPIHT_OK;
+}
+
+// Reduced-resolution decode: the geometry that makes the picture of pyramid level k (hs[k] x ws[k], 1/2^k size) out of
+// the SAME packed array.  The top-left corner of the array is itself the packed array of that picture at L - k levels --
+// same root block, same detail blocks at the same offsets -- so the geometry is ig with its k finest levels dropped and
+// the levels renumbered; enc_h / enc_w stay the full array's (they are the strides the kernels address it with).  The
+// inverse transform run on it stops at level k + 1 of the stream: that level is "level 1" to everything that makes a
+// picture (integer store, colour change, conversion pass).  rec_H x rec_W: what waverec2 returns for coeffs[:L - k + 1],
+// the root block itself for k == L.  F: the length rule's filter length (2 under periodization).
+static int reduced_geometry(const ImgGeom &ig, int F_real, int k, ImgGeom *r) {
+    if (k < 0 || k > ig.L) return SPIHT_ERR_ARG;
+    const int F = ig.per ? 2 : F_real;
+    *r = ig;
+    r->L = ig.L - k;
+    r->l0 = ig.l0 + k;
+    for (int l = 0; l <= r->L; l++) {
+        r->hs[l] = ig.hs[l + k]; r->ws[l] = ig.ws[l + k];
+        r->offh[l] = ig.offh[l + k]; r->offw[l] = ig.offw[l + k];  // ([0] is never read)
+    }
+    r->rec_H = r->L ? 2 * r->hs[1] - F + 2 : ig.ll_h;
+    r->rec_W = r->L ? 2 * r->ws[1] - F + 2 : ig.ll_w;
+    return SPIHT_OK;
+}
+// The quantisation scale of a reduced decode.  The approximation band carries a DC gain of 2 per level; R_k takes it out:
+// waverec2(coeffs[:L - k + 1]) * 2^-k.  Dividing by q * 2^k instead of q scales every dequantised value by exactly 2^-k, and
+// IEEE division, products and sums commute with a power of two (no subnormals in reach: |rec| >= 1, k <= SPIHT_MAX_LEVELS,
+// q an ordinary number) -- so no kernel multiplies by a gain: the levels run as they are with this q.
+static int reduced_q(double q, int k, double *qk) {
+    *qk = k ? ldexp(q, k) : q;
+    if (k && !(std::isfinite(*qk) && std::isfinite(q))) return SPIHT_ERR_ARG;  // (q * 2^k overflows)
     return SPIHT_OK;
 }
 
@@ -1472,6 +1507,9 @@ static bool l1flags_geometry(const ImgGeom &ig, int F, L1Flags *fl) {
 // d_flags: L1Flags words [planes, gy, gx] the decoder of d_rec left (nullptr: every level-1 tile reads its detail bands)
 // 8- / 16-bit output (l_lo == 1, a level >= 1: see dwt_forward): cropped to the picture's size; the tiled level 1 writes it
 // itself, the two-pass level goes through a conversion pass behind it.
+// A reduced geometry (reduced_geometry: ig.l0 = k levels dropped) runs the same way: its level 1 is level k + 1 of the
+// stream and makes the picture of that size -- integer store, crop, colour change, conversion pass; also as the coarsest
+// level (l == ig.L) -- and q is the caller's q * 2^k (reduced_q).  No d_flags then: the words belong to the stream's level 1.
 static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, const ImgGeom &ig, int wavelet, double q,
                        const double *d_mults, const Pic &out, int l_hi = -1, int l_lo = 1, const double *d_a_in = nullptr,
                        const uint32_t *d_flags = nullptr) {
@@ -1479,9 +1517,21 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
     const int F = wv.F;
     if (l_hi < 0) l_hi = ig.L;
     const bool u8 = out.integer();  // (8- or 16-bit pixels)
-    if (u8 && (l_lo != 1 || ig.L == 0)) return SPIHT_ERR_ARG;
+    if (u8 && (l_lo != 1 || (ig.L == 0 && ig.l0 == 0))) return SPIHT_ERR_ARG;
     double *d_out = u8 ? nullptr : (double *)out.p;
     const bool color = ctx->color_on && c == 3;
+    if (ig.L == 0 && ig.l0 > 0) {  // a reduced decode down to the root block: the window of the array, as the picture
+        StageTimer t(ctx, ST_IDWT_REST);
+        LlPicArgs a;
+        memset(&a, 0, sizeof(a));
+        a.rec = d_rec;
+        a.enc_h = (int32_t)ig.enc_h; a.enc_w = (int32_t)ig.enc_w; a.ll_h = (int32_t)ig.ll_h; a.ll_w = (int32_t)ig.ll_w;
+        a.c = c; a.mults = d_mults; a.q = q; a.out = d_out;
+        if (color) { a.color = 1; a.col = ctx->col_inv; }
+        if (u8) a.px = out.view();
+        LAUNCHCHK(spiht_launch_ll_to_pic(&a, planes, ctx->stream));
+        return SPIHT_OK;
+    }
     if (ig.L == 0) {
         StageTimer t(ctx, ST_IDWT_REST);
         LAUNCHCHK(spiht_launch_dequant_plain(d_rec, d_out, (size_t)ig.enc_h * ig.enc_w, planes, c, d_mults, q, ctx->stream));
@@ -1534,7 +1584,7 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
             // k_idwt_axis_per), a few planes at a time; the colour model of the picture as a pass of its own behind level 1
             const double *d_filt;
             CHK(upload_filters(ctx, wavelet, &d_filt));
-            StageTimer t(ctx, l == 1 ? ST_IDWT_L1 : ST_IDWT_REST);
+            StageTimer t(ctx, l + ig.l0 == 1 ? ST_IDWT_L1 : ST_IDWT_REST);
             a.color = 0;
             const size_t per_plane = (size_t)2 * a.band_h * a.out_w * 8;
             int pc = (int)std::max<size_t>(1, ((size_t)1 << 30) / per_plane);
@@ -1558,7 +1608,7 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
             }
         } else {
             if (u8 && l == 1) a.px = out.view();  // (the launcher takes the kernels of its pixel kind)
-            StageTimer t(ctx, l == 1 ? ST_IDWT_L1 : ST_IDWT_REST);
+            StageTimer t(ctx, l + ig.l0 == 1 ? ST_IDWT_L1 : ST_IDWT_REST);
             LAUNCHCHK(spiht_launch_idwt_level(&a, planes, ctx->stream, ctx->tilectr.dev ? &ctx->tilectr : nullptr));
         }
         a_in = a.out;
@@ -1584,6 +1634,8 @@ struct ImgCall {
     int64_t B = 0, c = 0;
     int F = 0;
     ImgGeom ig;
+    ImgGeom pig;  // the geometry the pictures are made with: ig, or its reduced form (reduce())
+    double q = 0; // ... and the quantisation scale that goes with it (reduce())
     Geom g;
     const double *d_mults = nullptr;
     std::unique_lock<std::recursive_mutex> lk;
@@ -1595,6 +1647,15 @@ struct ImgCall {
         F = SPIHT_WAVELETS[wavelet].F;
         *st = img_geometry(H, W, F, level, &ig, mode);
         if (*st == SPIHT_OK && coded) *st = make_geom(c, ig.enc_h, ig.enc_w, ig.ll_h, ig.ll_w, &g);
+        pig = ig;
+        return *st == SPIHT_OK;
+    }
+    // pictures of 1/2^k size (0: the call as it always was); before anything is queued
+    bool reduce(int *st, int k, double q_scale) {
+        q = q_scale;
+        if (k == 0) return true;
+        *st = reduced_geometry(ig, F, k, &pig);
+        if (*st == SPIHT_OK) *st = reduced_q(q_scale, k, &q);
         return *st == SPIHT_OK;
     }
     int enter(const double *channel_mults) {
@@ -1603,7 +1664,7 @@ struct ImgCall {
         return upload_mults(ctx, channel_mults, c, &d_mults);
     }
     template <class Fn> int chunks(Fn fn) const { return batch_chunks(B, c, fn); }
-    Pic at(const Pic &v, int64_t b0) const { return v.at(b0, c, ig); }
+    Pic at(const Pic &v, int64_t b0) const { return v.at(b0, c, v.out ? pig : ig); }
 };
 
 static int dwt_quant_batch(spiht_ctx *ctx, const Pic &in, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
@@ -1631,16 +1692,16 @@ extern "C" int spiht_dwt_quant_batch_f32(spiht_ctx *ctx, const float *d_img, int
 
 static int dequant_idwt_batch(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B, int64_t c, int64_t H,
                               int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
-                              const Pic &out) {
+                              const Pic &out, int reduce = 0) {
     if (!ctx || !d_rec || !out.p) return SPIHT_ERR_ARG;
     ImgCall k;
     int st;
-    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, false)) return st;
+    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, false) || !k.reduce(&st, reduce, q_scale)) return st;
     CHK(k.enter(channel_mults));
     L1Flags fl;
-    const bool flagged = d_flags && !(ctx->color_on && c == 3) && l1flags_geometry(k.ig, k.F, &fl);
+    const bool flagged = d_flags && reduce == 0 && !(ctx->color_on && c == 3) && l1flags_geometry(k.ig, k.F, &fl);
     return k.chunks([&](int64_t b0, int nb) -> int {
-        return dwt_inverse(ctx, d_rec + (size_t)b0 * c * k.ig.enc_h * k.ig.enc_w, nb * (int)c, (int)c, k.ig, wavelet, q_scale,
+        return dwt_inverse(ctx, d_rec + (size_t)b0 * c * k.ig.enc_h * k.ig.enc_w, nb * (int)c, (int)c, k.pig, wavelet, k.q,
                            k.d_mults, k.at(out, b0), -1, 1, nullptr, flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr);
     });
 }
@@ -1836,18 +1897,19 @@ extern "C" int spiht_encode_image_batch_u16(spiht_ctx *ctx, const uint16_t *d_im
 
 static int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
                               const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
-                              double q_scale, const double *channel_mults, const Pic &out, int32_t *d_rec) {
+                              double q_scale, const double *channel_mults, const Pic &out, int32_t *d_rec, int reduce = 0) {
     if (!ctx || !d_data || !d_nbytes || !d_max_n || !out.p) return SPIHT_ERR_ARG;
     ImgCall k;
     int st;
-    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, true)) return st;
+    if (!k.open(&st, ctx, B, c, H, W, wavelet, mode, level, true) || !k.reduce(&st, reduce, q_scale)) return st;
     CHK(k.enter(channel_mults));
     const Geom &g = k.g;
     return k.chunks([&](int64_t b0, int nb) -> int {
         int32_t *rec = d_rec ? d_rec + (size_t)b0 * g.n : nullptr;
         // the decoder tells the inverse transform which level-1 tiles hold anything (common.h: L1Flags)
         L1Flags fl;
-        const bool flagged = ctx->opt_l1_flags && !(ctx->color_on && c == 3) && l1flags_geometry(k.ig, k.F, &fl);
+        // (a reduced decode never reaches the stream's level 1: it asks for no words and passes none)
+        const bool flagged = ctx->opt_l1_flags && reduce == 0 && !(ctx->color_on && c == 3) && l1flags_geometry(k.ig, k.F, &fl);
         if (flagged) {
             CHK(ensure(ctx, ctx->l1flags, (size_t)nb * c * fl.gy * fl.gx * 4));
             fl.p = (uint32_t *)ctx->l1flags.p;
@@ -1855,7 +1917,7 @@ static int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t sl
         if (rec) {
             CHK(decode_device(ctx, g, d_data + (size_t)b0 * slot_stride, slot_stride, d_nbytes + b0, d_max_n + b0, nb, rec,
                               nullptr, nullptr, 0, true, nullptr, flagged ? &fl : nullptr));
-            return dwt_inverse(ctx, rec, nb * (int)c, (int)c, k.ig, wavelet, q_scale, k.d_mults, k.at(out, b0), -1, 1, nullptr,
+            return dwt_inverse(ctx, rec, nb * (int)c, (int)c, k.pig, wavelet, k.q, k.d_mults, k.at(out, b0), -1, 1, nullptr,
                                flagged ? fl.p : nullptr);
         }
         // Internal coefficient array: it is all zero on entry and is left all zero -- after the inverse transform the
@@ -1872,7 +1934,8 @@ static int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t sl
         DecArgs da;
         CHK(decode_device(ctx, g, d_data + (size_t)b0 * slot_stride, slot_stride, d_nbytes + b0, d_max_n + b0, nb, rec, nullptr,
                           nullptr, 0, false, &da, flagged ? &fl : nullptr));
-        CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, k.ig, wavelet, q_scale, k.d_mults, k.at(out, b0), -1, 1, nullptr,
+        // (a reduced inverse reads a corner of the array only; the decoder wrote all over it: its whole LSP is cleared)
+        CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, k.pig, wavelet, k.q, k.d_mults, k.at(out, b0), -1, 1, nullptr,
                         flagged ? fl.p : nullptr));
         if (da.nslots >= nb) {
             StageTimer t(ctx, ST_MEMSET);
@@ -1994,21 +2057,22 @@ extern "C" int spiht_encode_image_host_u16(spiht_ctx *ctx, const uint16_t *img, 
 
 // (an 8- / 16-bit picture: a dense one, CHW or HWC, so that it is c*H*W samples)
 static int decode_image_host(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H, int64_t W,
-                             int wavelet, int mode, int level, double q_scale, const double *channel_mults, const Pic &img_out) {
+                             int wavelet, int mode, int level, double q_scale, const double *channel_mults, const Pic &img_out,
+                             int reduce = 0) {
     if (!ctx || !img_out.p || (!data && nbytes)) return SPIHT_ERR_ARG;
     ImgCall k;
     int st;
-    if (!k.open(&st, ctx, 1, c, H, W, wavelet, mode, level, false)) return st;
+    if (!k.open(&st, ctx, 1, c, H, W, wavelet, mode, level, false) || !k.reduce(&st, reduce, q_scale)) return st;
     if (n > 30) return SPIHT_ERR_MAGNITUDE;
     if (nbytes * 8 >= 0xFFFFFF00ull) return SPIHT_ERR_TOO_LARGE;
     CHK(k.enter(nullptr));  // (the channel scales: the batch call's)
-    const size_t out_bytes = (size_t)img_out.bytes(1, c, k.ig);
+    const size_t out_bytes = (size_t)img_out.bytes(1, c, k.pig);  // (a reduced picture: only its bytes come back)
     DevBuf &hb = img_out.integer() ? ctx->hpix8 : ctx->himg;
     CHK(ensure(ctx, hb, out_bytes));
     uint64_t slot;
     CHK(stage_stream(ctx, data, nbytes, n, &slot));
     CHK(decode_image_batch(ctx, (const uint8_t *)ctx->data.p, slot, (const uint64_t *)ctx->nbytes.p, (const uint8_t *)ctx->maxn.p, 1,
-                           c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out.on(hb.p), nullptr));
+                           c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out.on(hb.p), nullptr, reduce));
     CHK(read_err(ctx));
     {
         StageTimer t(ctx, ST_D2H);
@@ -2073,6 +2137,139 @@ extern "C" int spiht_dequant_idwt_host_f64(spiht_ctx *ctx, const int32_t *rec, i
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return SPIHT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// reduced-resolution decode: the picture at 1/2^reduce size straight from the coefficient array or the stream
+// (include/spiht_hip.h).  The calls above with a reduced geometry behind them (reduced_geometry / reduced_q): levels
+// L .. reduce + 1 of the inverse transform run, nothing below.  The list decoder is the same: it parses every bit.
+// ------------------------------------------------------------------------------------------------
+static int reduced_open(int64_t H, int64_t W, int wavelet, int mode, int level, int reduce, ImgGeom *ig, ImgGeom *pig) {
+    if (wavelet < 0 || wavelet >= SPIHT_NWAVELETS || mode < 0 || mode > SPIHT_MODE_PERIODIZATION) return SPIHT_ERR_ARG;
+    CHK(img_geometry(H, W, SPIHT_WAVELETS[wavelet].F, level, ig, mode));
+    return reduced_geometry(*ig, SPIHT_WAVELETS[wavelet].F, reduce, pig);
+}
+extern "C" int spiht_reduced_shape(int64_t H, int64_t W, int wavelet, int mode, int level, int reduce, int *level_used,
+                                   int64_t *rec_h, int64_t *rec_w, int64_t *pic_h, int64_t *pic_w, int64_t *off_y,
+                                   int64_t *off_x, int64_t *in_h, int64_t *in_w) {
+    ImgGeom ig, pig;
+    CHK(reduced_open(H, W, wavelet, mode, level, reduce, &ig, &pig));
+    const int64_t ih = (H + ((int64_t)1 << reduce) - 1) >> reduce, iw = (W + ((int64_t)1 << reduce) - 1) >> reduce;
+    if (level_used) *level_used = ig.L;
+    if (rec_h) *rec_h = pig.rec_H;
+    if (rec_w) *rec_w = pig.rec_W;
+    if (pic_h) *pic_h = pig.hs[0];
+    if (pic_w) *pic_w = pig.ws[0];
+    if (off_y) *off_y = ig.per ? 0 : (pig.hs[0] - ih) / 2;
+    if (off_x) *off_x = ig.per ? 0 : (pig.ws[0] - iw) / 2;
+    if (in_h) *in_h = ih;
+    if (in_w) *in_w = iw;
+    return SPIHT_OK;
+}
+// the integer view of a reduced call: B pictures [c, hs[reduce], ws[reduce]] by n strides
+static int reduced_int_pic(void *p, int es, const int64_t *strides, int n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
+                           int mode, int level, int reduce, Pic *out) {
+    if (!p) return SPIHT_ERR_ARG;
+    CHK(check_img_args(wavelet, mode, B, c, H, W));
+    ImgGeom ig, pig;
+    CHK(reduced_open(H, W, wavelet, mode, level, reduce, &ig, &pig));
+    return int_pic(p, es, true, strides, n, B, c, pig.hs[0], pig.ws[0], out);
+}
+
+extern "C" int spiht_dequant_idwt_reduced_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H,
+                                                    int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                    const double *channel_mults, double *d_img_out, int reduce) {
+    return dequant_idwt_batch(ctx, d_rec, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                              dense_pic(d_img_out, PIC_F64, true), reduce);
+}
+static int dequant_idwt_reduced_batch_px(int es, spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H, int64_t W,
+                                         int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                         void *d_img_out, const int64_t *out_strides, int reduce) {
+    Pic out;
+    CHK(reduced_int_pic(d_img_out, es, out_strides, 4, B, c, H, W, wavelet, mode, level, reduce, &out));
+    return dequant_idwt_batch(ctx, d_rec, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out, reduce);
+}
+extern "C" int spiht_dequant_idwt_reduced_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H,
+                                                   int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                   const double *channel_mults, uint8_t *d_img_out,
+                                                   const int64_t *out_strides, int reduce) {
+    return dequant_idwt_reduced_batch_px(1, ctx, d_rec, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_img_out,
+                                         out_strides, reduce);
+}
+extern "C" int spiht_dequant_idwt_reduced_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H,
+                                                    int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                    const double *channel_mults, uint16_t *d_img_out,
+                                                    const int64_t *out_strides, int reduce) {
+    return dequant_idwt_reduced_batch_px(2, ctx, d_rec, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_img_out,
+                                         out_strides, reduce);
+}
+
+extern "C" int spiht_decode_image_reduced_batch_f64(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                                    const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                                    int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                    const double *channel_mults, double *d_img_out, int32_t *d_rec,
+                                                    int reduce) {
+    return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                              dense_pic(d_img_out, PIC_F64, true), d_rec, reduce);
+}
+static int decode_image_reduced_batch_px(int es, spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                         const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H,
+                                         int64_t W, int wavelet, int mode, int level, double q_scale,
+                                         const double *channel_mults, void *d_img_out, const int64_t *out_strides,
+                                         int32_t *d_rec, int reduce) {
+    Pic out;
+    CHK(reduced_int_pic(d_img_out, es, out_strides, 4, B, c, H, W, wavelet, mode, level, reduce, &out));
+    return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                              out, d_rec, reduce);
+}
+extern "C" int spiht_decode_image_reduced_batch_u8(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                                   const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                                   int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                   const double *channel_mults, uint8_t *d_img_out,
+                                                   const int64_t *out_strides, int32_t *d_rec, int reduce) {
+    return decode_image_reduced_batch_px(1, ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale,
+                                         channel_mults, d_img_out, out_strides, d_rec, reduce);
+}
+extern "C" int spiht_decode_image_reduced_batch_u16(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                                    const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                                    int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                    const double *channel_mults, uint16_t *d_img_out,
+                                                    const int64_t *out_strides, int32_t *d_rec, int reduce) {
+    return decode_image_reduced_batch_px(2, ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale,
+                                         channel_mults, d_img_out, out_strides, d_rec, reduce);
+}
+
+extern "C" int spiht_decode_image_reduced_host_f64(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                                   int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                   const double *channel_mults, double *img_out, int reduce) {
+    return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                             dense_pic(img_out, PIC_F64, true), reduce);
+}
+static int decode_image_reduced_host_px(int es, spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                        int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                        const double *channel_mults, void *img_out, const int64_t *strides, int reduce) {
+    Pic out;
+    CHK(reduced_int_pic(img_out, es, strides, 3, 1, c, H, W, wavelet, mode, level, reduce, &out));
+    // the copy back is of c * pic_h * pic_w samples: only the two dense layouts, CHW and HWC
+    const PxView &px = out.px;
+    const int64_t h = px.h, w = px.w;
+    const bool chw = px.sw == es && px.sh == w * es && px.sc == h * w * es, hwc = px.sc == es && px.sw == c * es && px.sh == w * c * es;
+    if (!chw && !hwc) return SPIHT_ERR_ARG;
+    return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, out, reduce);
+}
+extern "C" int spiht_decode_image_reduced_host_u8(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                                  int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                  const double *channel_mults, uint8_t *img_out, const int64_t *strides,
+                                                  int reduce) {
+    return decode_image_reduced_host_px(1, ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out,
+                                        strides, reduce);
+}
+extern "C" int spiht_decode_image_reduced_host_u16(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                                   int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                   const double *channel_mults, uint16_t *img_out, const int64_t *strides,
+                                                   int reduce) {
+    return decode_image_reduced_host_px(2, ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out,
+                                        strides, reduce);
 }
 
 // ------------------------------------------------------------------------------------------------

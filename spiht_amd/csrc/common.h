@@ -272,3 +272,15 @@ struct IdwtKArgs {
     Color3 col;
     PxView px;                 // level 1 into an 8- / 16-bit picture: the kernels' integer instantiations write it instead of `out`
 };
+
+// The root block as a picture (dwt.hip: k_ll_to_pic): a reduced-resolution decode that runs no synthesis level
+struct LlPicArgs {
+    const int32_t *rec;    // [planes, enc_h, enc_w]
+    int32_t enc_h, enc_w, ll_h, ll_w;
+    int32_t c, color;
+    const double *mults;   // device [c] or null
+    double q;
+    double *out;           // float64 pictures [planes, ll_h, ll_w] (PX_F64)
+    PxView px;             // integer pictures
+    Color3 col;
+};

@@ -1842,3 +1842,58 @@ extern "C" int spiht_launch_f64_to_px(const double *in, int rec_h, int rec_w, co
     else hipLaunchKernelGGL(k_f64_to_px<PX_U8>, dim3(pass_grid(n)), dim3(256), 0, st, in, rec_h, rec_w, *px, n);
     return (int)hipGetLastError();
 }
+
+// ---- reduced-resolution decode that stops at the root block (reduce == level): no synthesis level runs at all ------------
+// The picture is the root block itself: the ll_h x ll_w window in the top-left corner of the packed int32 array, dequantised
+// ((r / m) / q, the statement of every other kernel here; q already carries the 2^level of the approximation band's gain),
+// through the colour model change for a three-channel picture (color3_px: the bits of k_color3 on the dequantised planes),
+// stored as float64 [units, ll_h, ll_w] or through the strided 8- / 16-bit view, cropped to it.  One thread per pixel (per
+// three-channel pixel with colour), plain vector stores.  grid: (tiles of 256 pixels, plane) -- (.., image) with colour.
+template <int PX>
+__global__ __launch_bounds__(256) void k_ll_to_pic(LlPicArgs a) {
+    __shared__ SpowLds s_pw;
+    if (a.color) {  // (kernel-uniform)
+        spow_lds_fill(s_pw, threadIdx.x);
+        __syncthreads();
+    }
+    const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (t >= a.ll_h * a.ll_w) return;
+    const int y = t / a.ll_w, x = t - y * a.ll_w;
+    const bool has_m = a.mults != nullptr;
+    const size_t cpl = (size_t)a.enc_h * a.enc_w, opl = (size_t)a.ll_h * a.ll_w;
+    const size_t ro = (size_t)y * a.enc_w + x;
+    const int nch = a.color ? 3 : 1;
+    const int plane0 = (int)blockIdx.y * nch;
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int ch = 0; ch < nch; ch++) {
+        const int plane = plane0 + ch;
+        v[ch] = dequant(a.rec[(size_t)plane * cpl + ro], has_m ? a.mults[plane % a.c] : 1.0, a.q, has_m);
+    }
+    if (a.color) {
+        double w0, w1, w2;
+        color3_px(a.col, s_pw, v[0], v[1], v[2], w0, w1, w2);
+        v[0] = w0; v[1] = w1; v[2] = w2;
+    }
+    if (PX) {
+        if (y >= a.px.h || x >= a.px.w) return;
+        for (int ch = 0; ch < nch; ch++) {
+            const int plane = plane0 + ch;
+            uint8_t *p = a.px.out + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc;
+            PX_STORE(PX, p, (int64_t)y * a.px.sh + (int64_t)x * a.px.sw, v[ch]);
+        }
+    } else {
+        for (int ch = 0; ch < nch; ch++) a.out[(size_t)(plane0 + ch) * opl + t] = v[ch];
+    }
+}
+// planes: B*c of the launch (at most 65535); a->color: c == 3 and col set; a->px.out set: an 8- / 16-bit picture
+extern "C" int spiht_launch_ll_to_pic(const LlPicArgs *a, int planes, hipStream_t st) {
+    const int64_t npix = (int64_t)a->ll_h * a->ll_w;
+    const int units = a->color ? planes / 3 : planes;
+    if (npix <= 0 || units <= 0) return 0;
+    if (npix >= (1ll << 31) - 256 || units > 65535) return -1;
+    const dim3 grid((unsigned)((npix + 255) / 256), (unsigned)units);
+    if (a->px.out == nullptr) hipLaunchKernelGGL(k_ll_to_pic<PX_F64>, grid, dim3(256), 0, st, *a);
+    else if (a->px.es == 2) hipLaunchKernelGGL(k_ll_to_pic<PX_U16>, grid, dim3(256), 0, st, *a);
+    else hipLaunchKernelGGL(k_ll_to_pic<PX_U8>, grid, dim3(256), 0, st, *a);
+    return (int)hipGetLastError();
+}

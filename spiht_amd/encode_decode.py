@@ -13,7 +13,8 @@ from typing import Optional
 
 import numpy as np
 
-from .spiht_wrapper import EncodingResult, SpihtSettings, decode_image, encode_image, get_slices_and_h_w
+from .spiht_wrapper import (EncodingResult, SpihtSettings, decode_image, decode_image_reduced_u8, encode_image,
+                            get_slices_and_h_w)
 from .utils import imload, imsave, load_encoding, save_encoding
 
 _ARGS = [  # (flag, type, default, help): the reference tool's options, then ours
@@ -27,6 +28,7 @@ _ARGS = [  # (flag, type, default, help): the reference tool's options, then our
     ("--out", str, "reconstructed.png", "save reconstructed image to this file path"),
     ("--save", str, None, "also write the encoding to this file"),
     ("--load", str, None, "decode this encoding instead of encoding the image"),
+    ("--reduce", int, 0, "decode at 1/2^K size (K pyramid levels below full size) and save that picture"),
 ]
 
 
@@ -89,6 +91,13 @@ def main(args):
     if args.save:
         save_encoding(args.save, enc)
         print("  encoding written to", args.save)
+    if args.reduce:
+        # the 8-bit picture of pyramid level K, straight from the stream (no distance: there is no original of that size)
+        small, secs = timed(decode_image_reduced_u8, enc, p.settings, args.reduce)
+        print("decoded at 1/%d size in %.3f s: %d x %d" % (2 ** args.reduce, secs, small.shape[1], small.shape[2]))
+        imsave(args.out, small / 255)
+        print("  picture written to", args.out)
+        return enc, small
     decoded, secs = timed(decode_image, enc, p.settings)
     decoded = np.asarray(decoded)[:, :h, :w]  # the inverse transform of an odd-sized picture is one sample longer
     print("decoded in %.3f s, mean squared error %.5f" % (secs, float(((picture - decoded) ** 2).mean())))

@@ -346,6 +346,104 @@ def decode_image_u16(encoding_result: EncodingResult, spiht_settings: SpihtSetti
     return _decode_image_int(encoding_result, spiht_settings, channels_last, np.uint16, "spiht_decode_image_host_u16")
 
 
+def reduced_shape(h: int, w: int, spiht_settings: SpihtSettings, level: Optional[int], reduce: int):
+    """Sizes of a reduced-resolution decode of an h x w picture coded with `level` levels (None: as encode_image picks
+    it), `reduce` pyramid levels below full size (spiht_reduced_shape; no device needed).  Returns a dict:
+    level -- the levels L the stream has; rec_h, rec_w -- the float64 picture decode_image_reduced returns; pic_h, pic_w --
+    the 8- / 16-bit picture (the band size hs[reduce], ws[reduce]); in_h, in_w -- ceil(h / 2^reduce), ceil(w / 2^reduce),
+    the size of the picture downsampled 2^reduce-fold; off_y, off_x -- where that window lies in either picture (crop=True).
+    ValueError unless 0 <= reduce <= L."""
+    wid, mid = _wavelet_mode_ids(spiht_settings)
+    if level is not None and level < 0:
+        raise ValueError("Level value of %d is too low . Minimum level is 0." % level)
+    g = _geometry(h, w, wid, level, mid)
+    reduce = _reduce_arg(reduce, g["level"])
+    lv = C.c_int()
+    v = [C.c_int64() for _ in range(8)]
+    _lib.check(_lib.lib().spiht_reduced_shape(int(h), int(w), wid, mid, -1 if level is None else int(level), reduce,
+                                              C.byref(lv), *[C.byref(t) for t in v]))
+    names = ("rec_h", "rec_w", "pic_h", "pic_w", "off_y", "off_x", "in_h", "in_w")
+    return dict(level=lv.value, **{k: t.value for k, t in zip(names, v)})
+
+
+def _reduce_arg(reduce, levels):
+    if isinstance(reduce, bool) or not isinstance(reduce, (int, np.integer)):
+        raise TypeError("reduce must be an integer, not %s" % type(reduce).__name__)
+    if not 0 <= reduce <= levels:
+        raise ValueError("reduce = %d: a stream of %d levels decodes at reduce 0 .. %d" % (reduce, levels, levels))
+    return int(reduce)
+
+
+def _crop_window(picture, rs, crop, channels_last=False):
+    """crop=True: the centred in_h x in_w window of a reduced picture (a view)"""
+    if not crop:
+        return picture
+    ys, xs = slice(rs["off_y"], rs["off_y"] + rs["in_h"]), slice(rs["off_x"], rs["off_x"] + rs["in_w"])
+    return picture[ys, xs, :] if channels_last else picture[:, ys, xs]
+
+
+def decode_image_reduced(encoding_result: EncodingResult, spiht_settings: SpihtSettings, reduce: int,
+                         crop: bool = False) -> np.ndarray:
+    """The picture at 1/2^reduce size straight from the stream, 0 <= reduce <= L (the stream's levels; ValueError
+    otherwise): levels L .. reduce + 1 of the inverse transform run on the GPU and nothing below, and only the small picture
+    comes back.  Returns float64 (c, rec_h, rec_w) (reduced_shape):
+
+        pywt.waverec2(coeffs[:L - reduce + 1], wavelet, mode) * 2 ** -reduce
+
+    of the dequantised coefficients -- PyWavelets' approximation band with the DC gain of 2 per level taken out --,
+    uncropped as decode_image's; for reduce == L the root block itself; with a colour model, changed back to RGB per pixel.
+    reduce=0 is decode_image(encoding_result, spiht_settings) in every bit.
+
+    The band carries a rim of extension samples (its size is hs[reduce] >= ceil(h / 2^reduce); with bior4.4 the rim
+    approaches four samples a side).  crop=True returns the centred ceil(h / 2^reduce) x ceil(w / 2^reduce) window of it, as
+    a view: offset (hs[reduce] - ceil(h / 2^reduce)) // 2 per axis, 0 under periodization.  That window is the downsampled
+    picture to within a sample: the sampling phase of an even-length filter is not an integer."""
+    _check_version(encoding_result)
+    er = encoding_result
+    rs = reduced_shape(er.h, er.w, spiht_settings, er.level, reduce)
+    if spiht_settings.color_model is not None and er.c != 3:
+        raise ValueError("colour conversion needs 3 channels")
+    _, keep, args = _decode_args(er, spiht_settings)
+    out = _lib.result_array((er.c, rs["rec_h"], rs["rec_w"]), np.float64)
+    ctx = _lib.default_context()
+    with color_models.fused(ctx, spiht_settings.color_model):
+        _lib.check(_lib.lib().spiht_decode_image_reduced_host_f64(ctx.handle, *args, C.c_void_p(out.ctypes.data), int(reduce)))
+    return _crop_window(out, rs, crop)
+
+
+def _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, dtype, fn_name):
+    _check_version(encoding_result)
+    er = encoding_result
+    rs = reduced_shape(er.h, er.w, spiht_settings, er.level, reduce)
+    c, h, w = er.c, rs["pic_h"], rs["pic_w"]
+    if spiht_settings.color_model is not None and c != 3:
+        raise ValueError("colour conversion needs 3 channels")
+    _, keep, args = _decode_args(er, spiht_settings)
+    out = _lib.result_array((h, w, c) if channels_last else (c, h, w), dtype)
+    strides = np.array((1, w * c, c) if channels_last else (h * w, w, 1), dtype=np.int64) * np.dtype(dtype).itemsize
+    ctx = _lib.default_context()
+    with color_models.fused(ctx, spiht_settings.color_model):
+        _lib.check(getattr(_lib.lib(), fn_name)(ctx.handle, *args, C.c_void_p(out.ctypes.data), C.c_void_p(strides.ctypes.data),
+                                                int(reduce)))
+    return _crop_window(out, rs, crop, channels_last)
+
+
+def decode_image_reduced_u8(encoding_result: EncodingResult, spiht_settings: SpihtSettings, reduce: int, crop: bool = False,
+                            channels_last: bool = False) -> np.ndarray:
+    """8-bit pixels at 1/2^reduce size: (np.clip(decode_image_reduced(r, s, reduce), 0, 1) * 255).astype(np.uint8) cropped to
+    the band size (c, pic_h, pic_w) (reduced_shape) -- the rule of decode_image_u8 one pyramid level up --, converted on the
+    device; (pic_h, pic_w, c) with channels_last.  crop=True: the centred window, as decode_image_reduced."""
+    return _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, np.uint8,
+                                     "spiht_decode_image_reduced_host_u8")
+
+
+def decode_image_reduced_u16(encoding_result: EncodingResult, spiht_settings: SpihtSettings, reduce: int, crop: bool = False,
+                             channels_last: bool = False) -> np.ndarray:
+    """16-bit pixels at 1/2^reduce size: as decode_image_reduced_u8 with 65535 for 255."""
+    return _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, np.uint16,
+                                     "spiht_decode_image_reduced_host_u16")
+
+
 def _band_sizes(h, w, wavelet, levels, mode="reflect"):
     """band heights / widths per level, [0] = the image: len' = (len + F - 1) // 2 (pywt.dwt_coeff_len), under periodization
     ceil(len / 2) -- the same rule with a two-tap filter"""
