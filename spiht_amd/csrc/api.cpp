@@ -610,10 +610,6 @@ static int encode_device(spiht_ctx *ctx, const Geom &g, const int32_t *d_x, int 
     int nslots = 0;
     ListPtrs lp;
     CHK(alloc_lists(ctx, caps, std::min(B, ctx->num_cu), false, &nslots, &lp));
-    {
-        StageTimer t(ctx, ST_MEMSET);
-        HIPCHK(hipMemsetAsync(d_out, 0, (size_t)B * slot_stride, ctx->stream));
-    }
     if (!have_maxabs) {
         StageTimer t(ctx, ST_ABSMAX);
         LAUNCHCHK(spiht_launch_absmax(d_x, B, g.n, (uint32_t *)ctx->maxabs.p, ctx->stream));
@@ -650,6 +646,10 @@ static int encode_lists_device(spiht_ctx *ctx, const Geom &g, const int32_t *d_x
     a.lip0 = lp.lip0; a.lip1 = lp.lip1; a.lsp = lp.lsp; a.lis0 = lp.lis0; a.lis1 = lp.lis1; a.lis2 = lp.lis2;
     a.err = (uint32_t *)ctx->err.p;
     memcpy(a.log2_thresh, ctx->log2_thresh, sizeof(a.log2_thresh));
+    // The slots come out zero past the stream's last bit.  k_encode clears its image's slot itself before it writes into it:
+    // a fill queued in front of the kernel was seen to land on words the kernel had already written when the stream had
+    // just waited for events of two other streams (the pipeline's second step), which cost a stream its first few hundred
+    // bytes now and then.
     // Few images per call: each on a group of G workgroups (encode_wide.hip) instead of one -- a single image's list coding
     // is bound by the one CU it runs on.  Every workgroup of a group must be resident at once: B * G within what the device
     // holds of that kernel (asked of the runtime once per context).
@@ -668,6 +668,10 @@ static int encode_lists_device(spiht_ctx *ctx, const Geom &g, const int32_t *d_x
         CHK(ensure(ctx, ctx->widebuf, ctl_bytes + desc_bytes));
         w.ctl = (WideCtl *)ctx->widebuf.p;
         w.desc = (uint64_t *)((char *)ctx->widebuf.p + ctl_bytes);
+        {  // its chunks OR their first and last word into the slot: the slots start all-zero
+            StageTimer t(ctx, ST_MEMSET);
+            HIPCHK(hipMemsetAsync(d_out, 0, (size_t)B * slot_stride, ctx->stream));
+        }
         StageTimer t(ctx, ST_ENC_LISTS);
         HIPCHK(hipMemsetAsync(ctx->widebuf.p, 0, ctl_bytes + desc_bytes, ctx->stream));
         ctx->wide_last_groups = B;
@@ -2346,10 +2350,6 @@ extern "C" int spiht_encode_lists_batch_i32(spiht_ctx *ctx, const int32_t *d_x, 
         int nslots = 0;
         ListPtrs lp;
         CHK(alloc_lists(ctx, caps, std::min(nb, ctx->num_cu), false, &nslots, &lp));
-        {
-            StageTimer t(ctx, ST_MEMSET);
-            HIPCHK(hipMemsetAsync(d_out + (size_t)b0 * slot_stride, 0, (size_t)nb * slot_stride, ctx->stream));
-        }
         return encode_lists_device(ctx, g, d_x + (size_t)b0 * g.n, d_dmsb + (size_t)b0 * g.n, d_lmsb + (size_t)b0 * g.n,
                                    d_maxabs + b0, nb, max_bits, caps, nslots, lp, d_out + (size_t)b0 * slot_stride, slot_stride,
                                    d_nbits + b0, d_max_n + b0);

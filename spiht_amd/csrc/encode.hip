@@ -111,9 +111,11 @@ void k_encode(EncArgs a) {
 
     for (int b = (int)blockIdx.x; b < a.B; b += (int)gridDim.x) {
         // behind k_encode_wide (a.redo: one slot per image): only the images whose group of workgroups gave up for lack of
-        // residency are coded here, from scratch -- what that kernel left in the slot goes first
-        if (a.redo) {
-            if (!(a.redo[b].bad & 2u)) continue;
+        // residency are coded here, from scratch
+        if (a.redo && !(a.redo[b].bad & 2u)) continue;
+        // the slot is cleared here, by the workgroup that writes it (whole words below, the tail stays zero): no fill in
+        // front of the launch to be ordered with, and what k_encode_wide left in the slot goes as well
+        {
             uint32_t *zw = reinterpret_cast<uint32_t *>(a.out + (size_t)b * a.slot_stride);
             for (uint64_t t = tid; t < a.slot_stride / 4; t += BLOCK) zw[t] = 0;
             __syncthreads();

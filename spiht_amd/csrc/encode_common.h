@@ -4,7 +4,7 @@
 #pragma once
 #include "common.h"
 
-__device__ __forceinline__ uint32_t iabs_u(int32_t x) { return (uint32_t)(x < 0 ? -x : x); }
+__device__ __forceinline__ uint32_t iabs_u(int32_t x) { return x < 0 ? 0u - (uint32_t)x : (uint32_t)x; }  // (INT32_MIN -> 2^31, no signed overflow)
 
 
 __device__ __forceinline__ void decomp(const Geom &g, uint32_t idx, uint32_t &k, uint32_t &i, uint32_t &j) {

@@ -23,7 +23,7 @@
 #include <string.h>
 
 __device__ __forceinline__ uint32_t msb_code(uint32_t v) { return v ? 32u - (uint32_t)__clz((int)v) : 0u; }
-__device__ __forceinline__ uint32_t iabs_u(int32_t x) { return (uint32_t)(x < 0 ? -x : x); }
+__device__ __forceinline__ uint32_t iabs_u(int32_t x) { return x < 0 ? 0u - (uint32_t)x : (uint32_t)x; }  // (INT32_MIN -> 2^31, no signed overflow)
 
 // max |x| per image (encoder_decoder.rs:165).  grid: (blocks, B)
 __global__ __launch_bounds__(256) void k_absmax(const int32_t *__restrict__ x, uint32_t n, uint32_t *__restrict__ maxabs) {

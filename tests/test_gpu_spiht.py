@@ -331,7 +331,8 @@ def test_medium_realistic(oracle):
 
 @pytest.mark.parametrize("wide", [False, True])
 def test_random_geometries_and_budgets(oracle, wide):
-    """seeded random sweep: channels, odd / even sizes, LL blocks of every parity, magnitudes from 0 to 2^29, budgets
+    """seeded random sweep: channels, odd / even sizes, LL blocks of every parity, magnitudes from 0 to below 2^29 (the rest
+    of the range, up to 2^30 - 1, and the steps of the start-plane rule: tests/test_gpu_coder_edges.py), budgets
     from a few bits to unlimited -- stream, max_n and decoded array against the oracle, decode of random prefixes too.
     wide: the same cases through the several-CUs-per-image encoder (forced on for these small arrays, 2 to 9 workgroups)"""
     import spiht_amd
