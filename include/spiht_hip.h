@@ -59,7 +59,15 @@ int spiht_ctx_create(int device, spiht_ctx **out);
  * kernels of several contexts wait for room on the CUs); 0: as spiht_ctx_create. */
 int spiht_ctx_create_priority(int device, int priority, spiht_ctx **out);
 void spiht_ctx_destroy(spiht_ctx *ctx);
-/* Block until everything queued on the context's stream has finished. */
+/* Block until everything queued on the context's stream has finished.  Returns (and clears) what the device-side guards of
+ * the asynchronous calls queued before it recorded: SPIHT_ERR_MAGNITUDE, SPIHT_ERR_CAPACITY or SPIHT_ERR_INTERNAL.
+ * The rule for that latched error: it is reported exactly once, by the first call on the context that waits for its
+ * stream.  Those calls are spiht_ctx_synchronize() and the calls that take or return host arrays: spiht_encode_i32,
+ * spiht_decode_i32, spiht_decode_with_metadata_i32, spiht_decode_budgets_i32, spiht_decode_budgets_dev_i32 (it waits while
+ * it uploads the stream), spiht_encode_image_host_f64 / _f32 / _u8 / _u16, spiht_decode_image_host_f64 / _u8 / _u16,
+ * spiht_decode_image_reduced_host_f64 / _u8 / _u16.  (spiht_pipeline_synchronize reports for the pipeline's contexts.)
+ * Such a call looks at the error before it starts its own work: it returns the earlier call's status without running, and
+ * the same call made again works normally.  Outputs of the images that tripped no guard are valid either way. */
 int spiht_ctx_synchronize(spiht_ctx *ctx);
 /* Order across contexts without blocking the host: everything queued on `ctx` after this call waits (on the
  * device) for everything queued on `other` before it.  Lets one context's stream encode step i+1 while another

@@ -481,22 +481,14 @@ extern "C" void spiht_ctx_destroy(spiht_ctx *ctx) {
     delete ctx;
 }
 
-static int read_err(spiht_ctx *ctx);
-static int clear_err(spiht_ctx *ctx);
-// Waits for the context's stream and reports (then clears) what the device-side guards of the batched calls
-// queued since the last synchronize recorded.
+static int take_err(spiht_ctx *ctx);
+// Waits for the context's stream and reports (then clears) what the device-side guards of the calls queued before it
+// recorded and no call has reported yet (take_err: the one place of that rule).
 extern "C" int spiht_ctx_synchronize(spiht_ctx *ctx) {
     if (!ctx) return SPIHT_ERR_ARG;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    int st = read_err(ctx);  // includes the stream synchronize
-    if (st != SPIHT_OK) {
-        ctx->recz_clean = false;  // a guard tripped: the decoder's lists may not describe what it wrote
-        ctx->last_dec_valid = false;
-        (void)clear_err(ctx);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    return st;
+    return take_err(ctx);
 }
 extern "C" int spiht_ctx_wait_on(spiht_ctx *ctx, spiht_ctx *other) {
     if (!ctx || !other || ctx->device != other->device) return SPIHT_ERR_ARG;
@@ -553,6 +545,19 @@ static int read_err(spiht_ctx *ctx) {
         return SPIHT_ERR_INTERNAL;
     }
     return SPIHT_OK;
+}
+// The latched error: waits for the stream and, when the word is set, returns its status, clears the word and stops trusting
+// what the decoder left behind (a guard tripped: its lists may not describe what it wrote).  An error is reported once,
+// by the first call that waits for the stream: spiht_ctx_synchronize(), or a synchronous single call -- those look before
+// their own work (what an earlier batched call left belongs to the caller: the single call does not run) and after it.
+static int take_err(spiht_ctx *ctx) {
+    const int st = read_err(ctx);  // includes the stream synchronize
+    if (st == SPIHT_OK || st == SPIHT_ERR_HIP) return st;
+    ctx->recz_clean = false;
+    ctx->last_dec_valid = false;
+    (void)clear_err(ctx);
+    (void)hipStreamSynchronize(ctx->stream);
+    return st;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -777,7 +782,7 @@ static int read_encoded(spiht_ctx *ctx, uint8_t *out, uint64_t out_cap, uint64_t
     uint8_t mn = 0;
     HIPCHK(hipMemcpyAsync(&nbits, ctx->nbits.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(&mn, ctx->maxn.p, 1, hipMemcpyDeviceToHost, ctx->stream));
-    CHK(read_err(ctx));  // synchronises
+    CHK(take_err(ctx));  // synchronises
     *out_nbits = nbits;
     *max_n = mn;
     const uint64_t nbytes = (nbits + 7) / 8;
@@ -791,13 +796,14 @@ static int read_encoded(spiht_ctx *ctx, uint8_t *out, uint64_t out_cap, uint64_t
 }
 
 // One host stream for the decoder: its bytes into ctx->data, a slot of *slot bytes whose last word is zeroed first (the
-// bytes past the stream in it), its length and magnitude into ctx->nbytes / ctx->maxn; clears the error word and waits
+// bytes past the stream in it), its length and magnitude into ctx->nbytes / ctx->maxn; waits, and returns the error an
+// earlier batched call has latched, if any (take_err)
 static int stage_stream(spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, uint64_t *slot) {
     *slot = std::max<uint64_t>(4, (nbytes + 3) & ~3ull);
     CHK(ensure(ctx, ctx->data, *slot));
     CHK(ensure(ctx, ctx->nbytes, 8));
     CHK(ensure(ctx, ctx->maxn, 4));
-    CHK(clear_err(ctx));
+    CHK(take_err(ctx));
     StageTimer t(ctx, ST_H2D);
     HIPCHK(hipMemsetAsync((char *)ctx->data.p + (*slot - 4), 0, 4, ctx->stream));
     if (nbytes) HIPCHK(hipMemcpyAsync(ctx->data.p, data, nbytes, hipMemcpyHostToDevice, ctx->stream));
@@ -845,7 +851,7 @@ extern "C" int spiht_encode_i32(spiht_ctx *ctx, const int32_t *x, int64_t c, int
     CHK(ensure(ctx, ctx->out, slot));
     CHK(ensure(ctx, ctx->nbits, 8));
     CHK(ensure(ctx, ctx->maxn, 4));
-    CHK(clear_err(ctx));
+    CHK(take_err(ctx));
     {
         StageTimer t(ctx, ST_H2D);
         HIPCHK(hipMemcpyAsync(ctx->x.p, src, (size_t)g.n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -869,7 +875,7 @@ extern "C" int spiht_decode_i32(spiht_ctx *ctx, const uint8_t *data, uint64_t nb
     CHK(stage_stream(ctx, data, nbytes, n, &slot));
     CHK(decode_device(ctx, g, (const uint8_t *)ctx->data.p, slot, (const uint64_t *)ctx->nbytes.p,
                       (const uint8_t *)ctx->maxn.p, 1, (int32_t *)ctx->rec.p));
-    CHK(read_err(ctx));
+    CHK(take_err(ctx));
     {
         StageTimer t(ctx, ST_D2H);
         HIPCHK(hipMemcpyAsync(out, ctx->rec.p, (size_t)g.n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -984,7 +990,7 @@ extern "C" int spiht_decode_with_metadata_i32(spiht_ctx *ctx, const uint8_t *dat
     ma.slices = (const int32_t *)tr.in;
     ma.meta = (int32_t *)ctx->meta.p;
     LAUNCHCHK(spiht_launch_metadata(&ma, tr.k0, tr.v0, tr.k1, tr.v1, tr.tmp, tr.tmp_bytes, ctx->stream));
-    CHK(read_err(ctx));
+    CHK(take_err(ctx));
     {
         StageTimer t(ctx, ST_D2H);
         HIPCHK(hipMemcpyAsync(out, ctx->rec.p, (size_t)g.n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1044,7 +1050,7 @@ extern "C" int spiht_decode_budgets_i32(spiht_ctx *ctx, const uint8_t *data, uin
     const size_t bytes = (size_t)K * g.n * 4;
     CHK(ensure(ctx, ctx->hrec, bytes));
     CHK(spiht_decode_budgets_dev_i32(ctx, data, nbytes, n, c, h, w, ll_h, ll_w, budgets_bits, K, (int32_t *)ctx->hrec.p));
-    CHK(read_err(ctx));
+    CHK(take_err(ctx));
     {
         StageTimer t(ctx, ST_D2H);
         HIPCHK(hipMemcpyAsync(out, ctx->hrec.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -2010,7 +2016,7 @@ static int encode_image_host(spiht_ctx *ctx, const Pic &img, int64_t c, int64_t 
     CHK(ensure(ctx, ctx->out, slot));
     CHK(ensure(ctx, ctx->nbits, 8));
     CHK(ensure(ctx, ctx->maxn, 4));
-    CHK(clear_err(ctx));
+    CHK(take_err(ctx));
     {
         StageTimer t(ctx, ST_H2D);
         HIPCHK(hipMemcpyAsync(hb.p, img.p, img_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -2077,7 +2083,7 @@ static int decode_image_host(spiht_ctx *ctx, const uint8_t *data, uint64_t nbyte
     CHK(stage_stream(ctx, data, nbytes, n, &slot));
     CHK(decode_image_batch(ctx, (const uint8_t *)ctx->data.p, slot, (const uint64_t *)ctx->nbytes.p, (const uint8_t *)ctx->maxn.p, 1,
                            c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out.on(hb.p), nullptr, reduce));
-    CHK(read_err(ctx));
+    CHK(take_err(ctx));
     {
         StageTimer t(ctx, ST_D2H);
         HIPCHK(hipMemcpyAsync(img_out.p, hb.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
