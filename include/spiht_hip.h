@@ -543,6 +543,33 @@ int spiht_decode_image_reduced_host_u16(spiht_ctx *ctx, const uint8_t *data, uin
                                         const double *channel_mults, uint16_t *img_out, const int64_t *strides, int reduce);
 
 /* ---------------------------------------------------------------------------------------
+ * Rate-distortion reductions: how far K decoded versions of one picture are from the original, computed where they lie.
+ * A SPIHT stream decodes at any prefix; spiht_decode_budgets_dev_i32 + spiht_dequant_idwt_batch_* give the K coefficient
+ * arrays and pictures of K prefixes in HBM, and these calls turn them into K small rows -- nothing but those rows has to
+ * cross the link (spiht_amd/rd.py builds the curve and the cut to a target quality on them).  Additions only: the ABI
+ * version stays at 2.  All pointers are DEVICE pointers; asynchronous on the context's stream like the *_batch_* calls;
+ * argument errors are returned before anything is queued.  1 <= K <= 65535, c <= 65535, K*c < 2^31 (SPIHT_ERR_ARG /
+ * _TOO_LARGE).  The per-workgroup partial sums live in a grow-only buffer of the context.
+ *   spiht_sqerr_i32  d_x int32 [c, h, w], d_y int32 [K, c, h, w], dense; c*h*w < 2^28 (SPIHT_ERR_TOO_LARGE).
+ *                    d_out uint64 [K][2] = (lo, hi) of E[k] = sum (x - y[k])^2 as an exact 128-bit unsigned integer.
+ *   spiht_sse_f64    d_pic float64 [c, H, W], d_dec float64 [K, c, rec_h, rec_w] (uncropped, as the decode calls return
+ *                    them; rec_h >= H and rec_w >= W, else SPIHT_ERR_ARG).  d_out double [K][c]: S[k, ch] = the sum over
+ *                    the H x W window of (p - d) * (p - d), every term rounded and then added (no fused multiply-add), in
+ *                    an order fixed by (H, W) alone: the same bits from call to call, for any K and wherever a picture
+ *                    lies in d_dec.  H*W < 2^30.
+ *   spiht_sse_u8 / _u16  d_pic: the original by byte strides[3] = (sc, sh, sw) (NULL: dense CHW), under the rules of
+ *                    spiht_check_view_u8 / _u16 for a view that is read; d_dec uint8 / uint16 [K, c, H, W] dense.
+ *                    d_out uint64 [K][c], exact (65535^2 * 2^30 < 2^63: H*W < 2^30). */
+int spiht_sqerr_i32(spiht_ctx *ctx, const int32_t *d_x, const int32_t *d_y, int64_t K, int64_t c, int64_t h, int64_t w,
+                    uint64_t *d_out);
+int spiht_sse_f64(spiht_ctx *ctx, const double *d_pic, const double *d_dec, int64_t K, int64_t c, int64_t H, int64_t W,
+                  int64_t rec_h, int64_t rec_w, double *d_out);
+int spiht_sse_u8(spiht_ctx *ctx, const uint8_t *d_pic, const int64_t *strides, const uint8_t *d_dec, int64_t K, int64_t c,
+                 int64_t H, int64_t W, uint64_t *d_out);
+int spiht_sse_u16(spiht_ctx *ctx, const uint16_t *d_pic, const int64_t *strides, const uint16_t *d_dec, int64_t K, int64_t c,
+                  int64_t H, int64_t W, uint64_t *d_out);
+
+/* ---------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, every rank codes its own images (the reference's encode / decode
  * are pure functions of one image, src/lib.rs:24-42 -- nothing is exchanged while coding); the ONE exchange of the
  * path is the gather of the finished streams.  It runs on RCCL (ncclAllGather over xGMI), inside this library, on

@@ -10,7 +10,7 @@ import sys
 
 import spiht_amd as _impl
 
-_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode")
+_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode", "rd")
 for _name in _SUBMODULES:
     # `spiht.spiht` is the reference's compiled extension (src/lib.rs:58-65); here spiht_amd/spiht.py over the C ABI
     _mod = importlib.import_module("spiht_amd." + _name)
@@ -23,4 +23,7 @@ globals().update({_k: getattr(_impl, _k) for _k in ("encode_image", "decode_imag
 # beyond the reference's names: the reduced-resolution decode
 globals().update({_k: getattr(_impl, _k) for _k in ("decode_image_reduced", "decode_image_reduced_u8",
                                                     "decode_image_reduced_u16", "reduced_shape")})
+# ... the rate-distortion curve of a stream and the cut to a target quality
+globals().update({_k: getattr(_impl, _k) for _k in ("RDCurve", "rd_curve", "rd_curve_u8", "rd_curve_u16", "cut_to_psnr",
+                                                    "cut_to_psnr_u8", "cut_to_psnr_u16")})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

@@ -12,3 +12,5 @@ from .spiht_wrapper import (encode_image, decode_image, EncodingResult, SpihtSet
                             encode_image_u16, decode_image_u16, decode_image_reduced, decode_image_reduced_u8,
                             decode_image_reduced_u16, reduced_shape)
 from .spiht import encode, decode  # noqa: E402,F401
+from .rd import (RDCurve, rd_curve, rd_curve_u8, rd_curve_u16, cut_to_psnr, cut_to_psnr_u8,  # noqa: E402,F401
+                 cut_to_psnr_u16)

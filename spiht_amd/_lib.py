@@ -61,6 +61,7 @@ SYMBOLS = [
     "spiht_dequant_idwt_reduced_batch_f64", "spiht_dequant_idwt_reduced_batch_u8", "spiht_dequant_idwt_reduced_batch_u16",
     "spiht_decode_image_reduced_batch_f64", "spiht_decode_image_reduced_batch_u8", "spiht_decode_image_reduced_batch_u16",
     "spiht_decode_image_reduced_host_f64", "spiht_decode_image_reduced_host_u8", "spiht_decode_image_reduced_host_u16",
+    "spiht_sqerr_i32", "spiht_sse_f64", "spiht_sse_u8", "spiht_sse_u16",
 ]
 
 
@@ -202,6 +203,10 @@ def lib():
         L.spiht_decode_image_reduced_batch_u8.argtypes = L.spiht_decode_image_batch_u8.argtypes + [i32]
         L.spiht_decode_image_reduced_host_f64.argtypes = L.spiht_decode_image_host_f64.argtypes + [i32]
         L.spiht_decode_image_reduced_host_u8.argtypes = L.spiht_decode_image_host_u8.argtypes + [i32]
+        # rate-distortion reductions: device pointers, K, the picture's sizes, the device row(s) they fill
+        L.spiht_sqerr_i32.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp]
+        L.spiht_sse_f64.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, i64, vp]
+        L.spiht_sse_u8.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, vp]
         # 16-bit pixels: every *_u16 call takes what its *_u8 sibling takes
         for name in SYMBOLS:
             if name.endswith("_u16"):

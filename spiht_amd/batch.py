@@ -6,6 +6,7 @@ bitstreams stay in HBM between the stages.  Device buffers may come from this mo
 C ABI) or from anyone else (e.g. a torch tensor's data_ptr()) -- the C ABI takes plain pointers.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -151,7 +152,7 @@ class BatchCodec:
     def _u8_strides(self, B, strides, output):
         return self._int_strides(B, strides, output, np.uint8)
 
-    def _encode_device_int(self, dtype, d_img, B, d_out, d_nbits, d_max_n, strides):
+    def _encode_device_int(self, dtype, d_img, B, d_out, d_nbits, d_max_n, strides, d_coeffs=None):
         st, st_p = self._int_strides(B, strides, False, dtype)
         _check_aligned(d_img, dtype)
         fn = self.L.spiht_encode_image_batch_u16 if np.dtype(dtype).itemsize == 2 else self.L.spiht_encode_image_batch_u8
@@ -159,7 +160,7 @@ class BatchCodec:
             _lib.check(fn(
                 self.ctx.handle, C.c_void_p(d_img), st_p, int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
                 float(self.settings.quantization_scale), self._mults_p, self.max_bits, C.c_void_p(d_out), self.slot_stride,
-                C.c_void_p(d_nbits), C.c_void_p(d_max_n), None))
+                C.c_void_p(d_nbits), C.c_void_p(d_max_n), C.c_void_p(d_coeffs) if d_coeffs else None))
 
     def _decode_device_int(self, dtype, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride):
         st, st_p = self._int_strides(B, strides, True, dtype)
@@ -298,6 +299,69 @@ class BatchCodec:
     def decode_reduced_u16(self, results, reduce, crop=False, channels_last=False):
         """list of EncodingResult -> uint16 [B, c, pic_h, pic_w] (or [B, pic_h, pic_w, c]): decode_image_reduced_u16 of each"""
         return self._decode_reduced_int(np.uint16, results, reduce, crop, channels_last)
+
+    # ---- rate-distortion curve and cut (spiht_amd/rd.py; include/spiht_hip.h: spiht_sqerr_i32, spiht_sse_*) ---------------
+    def rd_curve(self, image, result=None, byte_lengths=None, points=32, max_bytes=2 ** 31):
+        """How good the prefixes of one stream are -> rd.RDCurve, rows in the order of byte_lengths.  image: one float
+        picture (c, H, W) of the codec's geometry.  result: a stream of it (X, the array the coefficient error is taken
+        against, is then the forward transform of `image` with the codec's settings); None: the picture is encoded first,
+        with the codec's max_bits, and X is the encoder's own quantised array.  byte_lengths: prefix lengths (None: `points`
+        lengths evenly spaced over 1 .. len(stream), the full length among them); a length past the end means the whole
+        stream, as in decode_prefixes.
+        Everything stays in HBM: the picture goes up once; per group of lengths the stream is walked once
+        (spiht_decode_budgets_dev_i32), the arrays are compared (spiht_sqerr_i32), inverse-transformed in one batched launch
+        and compared with the picture (spiht_sse_f64); the K rows come back.  A group holds as many lengths as keep
+        K_g c (enc_h enc_w 4 + rec_h rec_w 8) bytes within max_bytes, at least one; the numbers do not depend on it."""
+        from . import rd
+        return rd.codec_rd_curve(self, image, result, byte_lengths, points, max_bytes)[0]
+
+    def rd_curve_u8(self, image, result=None, byte_lengths=None, points=32, max_bytes=2 ** 31):
+        """rd_curve of a uint8 picture (c, H, W): the distances are those between 8-bit pictures (decode_image_u8 of the
+        prefix against `image`), exact integers; peak 255"""
+        from . import rd
+        return rd.codec_rd_curve(self, image, result, byte_lengths, points, max_bytes, np.uint8)[0]
+
+    def rd_curve_u16(self, image, result=None, byte_lengths=None, points=32, max_bytes=2 ** 31):
+        """rd_curve of a uint16 picture (c, H, W); peak 65535"""
+        from . import rd
+        return rd.codec_rd_curve(self, image, result, byte_lengths, points, max_bytes, np.uint16)[0]
+
+    def _cut_to_psnr(self, image, result, target_db, points, dtype):
+        from . import rd
+        target = rd._target_arg(target_db, "target_db")
+        return rd.codec_cut(self, image, result, points, dtype, "psnr", lambda v: v >= target)
+
+    def cut_to_psnr(self, image, result, target_db, points=32):
+        """A prefix of `result` (a stream of the float picture `image`) that reaches target_db -> (EncodingResult, psnr, met).
+        If the whole stream stays below the target: the whole stream, met False.  Otherwise the returned length L satisfies
+        psnr(L) >= target_db and (L == 0 or psnr(L - 1) < target_db).  That is a crossing, not the shortest such prefix
+        there is: PSNR over prefixes need not be monotone (the filters are biorthogonal, the integer formats clip), and the
+        search -- at most `points` lengths per round, evenly spaced between a length that fails and one that passes, one
+        rd_curve call per round, at most ceil(log(n + 1) / log(points + 1)) rounds after the look at the whole stream --
+        ends at one place where the curve crosses the target."""
+        return self._cut_to_psnr(image, result, target_db, points, None)
+
+    def cut_to_psnr_u8(self, image, result, target_db, points=32):
+        """cut_to_psnr on the 8-bit curve (rd_curve_u8)"""
+        return self._cut_to_psnr(image, result, target_db, points, np.uint8)
+
+    def cut_to_psnr_u16(self, image, result, target_db, points=32):
+        """cut_to_psnr on the 16-bit curve (rd_curve_u16)"""
+        return self._cut_to_psnr(image, result, target_db, points, np.uint16)
+
+    def cut_to_sqerr(self, image, result, max_sqerr, points=32):
+        """A prefix of `result` whose coefficient error E = sum (X - X_L)^2 is at most max_sqerr -> (EncodingResult, E, met);
+        the whole stream with met False when even that is above it.  The arithmetic is exact (128-bit sums, Python ints),
+        and the returned length L satisfies E(L) <= max_sqerr and (L == 0 or E(L - 1) > max_sqerr).  Where E does not
+        increase with the length that is the shortest such prefix.  E falls almost everywhere, but not everywhere: the
+        decoder puts a coefficient found significant at plane n at 1.5 * 2^n, and a first refinement bit of 0 moves it to
+        2^n -- away from a true value above 1.25 * 2^n -- so a prefix that ends in a refinement pass can be a little worse
+        than the one a byte shorter (the CPU oracle shows 32 such steps among the 3521 prefixes of one 37 x 53 test
+        picture's full stream).  A target inside such a step gets a crossing, as in cut_to_psnr."""
+        from . import rd
+        if isinstance(max_sqerr, float) and math.isnan(max_sqerr):
+            raise ValueError("max_sqerr is NaN")
+        return rd.codec_cut(self, image, result, points, None, "coef_sqerr", lambda v: v <= max_sqerr)
 
     def nbits_to_nbytes(self, d_nbits, B, d_nbytes):
         _lib.check(self.L.spiht_nbits_to_nbytes(self.ctx.handle, C.c_void_p(d_nbits), int(B), C.c_void_p(d_nbytes)))

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "common.h"
+#include "rd.h"
 #include "wavelets.h"
 
 extern "C" {
@@ -52,6 +53,11 @@ int spiht_launch_zero_pads(int L, const int64_t *hs, const int64_t *ws, const in
 int spiht_launch_ll_to_pic(const LlPicArgs *a, int planes, hipStream_t st);
 int spiht_launch_dequant_plain(const int32_t *in, double *out, size_t n_per_plane, int planes, int c,
                                const double *mults, double q, hipStream_t st);
+int spiht_launch_sqerr_i32(const int32_t *d_x, const int32_t *d_y, int K, int c, uint32_t hw, uint64_t *part, uint64_t *d_out,
+                           hipStream_t st);
+int spiht_launch_sse_f64(const double *d_pic, const double *d_dec, int K, int c, int H, int W, int rec_h, int rec_w, double *part,
+                         double *d_out, hipStream_t st);
+int spiht_launch_sse_px(const PxView *px, const void *d_dec, int K, uint64_t *part, uint64_t *d_out, hipStream_t st);
 }
 
 static thread_local std::string g_hip_err;
@@ -128,6 +134,7 @@ struct spiht_ctx {
     int filt_wavelet = -1;
     // decoder output of the fused image path: kept all-zero between calls (k_unscatter), so no per-call zero-fill
     DevBuf recz, lspcnt;
+    DevBuf rdpart;              // per-workgroup partial sums of the rate-distortion reductions (rd.hip)
     bool recz_clean = false;
     // spiht_decode_lists_batch_i32 -> spiht_unscatter_lists_batch_i32: the launch whose scatter can still be undone
     DecArgs last_dec;
@@ -472,7 +479,7 @@ extern "C" void spiht_ctx_destroy(spiht_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->widebuf, &ctx->filt, &ctx->exttmp, &ctx->l1flags, &ctx->x, &ctx->dmsb, &ctx->lmsb, &ctx->maxabs, &ctx->out, &ctx->nbits, &ctx->maxn, &ctx->err,
                       &ctx->lists, &ctx->coeffs, &ctx->a0, &ctx->a1, &ctx->data, &ctx->nbytes, &ctx->rec, &ctx->mults,
                       &ctx->img, &ctx->trace, &ctx->meta, &ctx->recz, &ctx->lspcnt, &ctx->himg, &ctx->hrec, &ctx->tilebuf,
-                      &ctx->pix, &ctx->hpix8};
+                      &ctx->pix, &ctx->hpix8, &ctx->rdpart};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &r : ctx->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -2280,6 +2287,64 @@ extern "C" int spiht_decode_image_reduced_host_u16(spiht_ctx *ctx, const uint8_t
                                                    int reduce) {
     return decode_image_reduced_host_px(2, ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out,
                                         strides, reduce);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rate-distortion reductions (rd.hip): K decoded arrays / pictures against the original -> K small rows, all in HBM
+// ------------------------------------------------------------------------------------------------
+extern "C" int spiht_sqerr_i32(spiht_ctx *ctx, const int32_t *d_x, const int32_t *d_y, int64_t K, int64_t c, int64_t h, int64_t w,
+                               uint64_t *d_out) {
+    if (!ctx || !d_x || !d_y || !d_out || K < 1 || K > 65535 || c < 1 || h < 1 || w < 1) return SPIHT_ERR_ARG;
+    if (c > 65535 || h >= (1 << 28) || w >= (1 << 28) || (__int128)c * h * w >= (1 << 28)) return SPIHT_ERR_TOO_LARGE;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint32_t hw = (uint32_t)(h * w);
+    CHK(ensure(ctx, ctx->rdpart, (size_t)K * c * rd_tiles(hw, RD_TILE_I32) * 16));
+    LAUNCHCHK(spiht_launch_sqerr_i32(d_x, d_y, (int)K, (int)c, hw, (uint64_t *)ctx->rdpart.p, d_out, ctx->stream));
+    return SPIHT_OK;
+}
+// the checks the pixel-domain sums share: K as above, a picture of fewer than 2^30 samples per channel (the 64-bit sums),
+// K * c within a grid's x extent
+static int sse_args(spiht_ctx *ctx, const void *d_pic, const void *d_dec, int64_t K, int64_t c, int64_t H, int64_t W,
+                    const void *d_out) {
+    if (!ctx || !d_pic || !d_dec || !d_out || K < 1 || K > 65535 || c < 1 || H < 1 || W < 1) return SPIHT_ERR_ARG;
+    if (c > 65535 || H >= (1 << 30) || W >= (1 << 30) || H * W >= (1 << 30)) return SPIHT_ERR_TOO_LARGE;
+    if (K * c > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;  // (the second launch: one workgroup / thread per (k, channel))
+    return SPIHT_OK;
+}
+extern "C" int spiht_sse_f64(spiht_ctx *ctx, const double *d_pic, const double *d_dec, int64_t K, int64_t c, int64_t H, int64_t W,
+                             int64_t rec_h, int64_t rec_w, double *d_out) {
+    CHK(sse_args(ctx, d_pic, d_dec, K, c, H, W, d_out));
+    if (rec_h < H || rec_w < W) return SPIHT_ERR_ARG;
+    if (rec_h >= (1 << 30) || rec_w >= (1 << 30)) return SPIHT_ERR_TOO_LARGE;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->rdpart, (size_t)K * c * rd_tiles(H, RD_TILE_ROWS) * 8));
+    LAUNCHCHK(spiht_launch_sse_f64(d_pic, d_dec, (int)K, (int)c, (int)H, (int)W, (int)rec_h, (int)rec_w, (double *)ctx->rdpart.p,
+                                   d_out, ctx->stream));
+    return SPIHT_OK;
+}
+// es: bytes per sample.  strides: (sc, sh, sw) of the original in bytes, NULL = dense CHW; d_dec: dense [K, c, H, W]
+static int sse_px(int es, spiht_ctx *ctx, const void *d_pic, const int64_t *strides, const void *d_dec, int64_t K, int64_t c,
+                  int64_t H, int64_t W, uint64_t *d_out) {
+    CHK(sse_args(ctx, d_pic, d_dec, K, c, H, W, d_out));
+    if ((uintptr_t)d_dec % (uintptr_t)es != 0) return SPIHT_ERR_ARG;
+    Pic pic;
+    CHK(int_pic(d_pic, es, false, strides, 3, 1, c, H, W, &pic));
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->rdpart, (size_t)K * c * rd_tiles((uint64_t)H * W, RD_TILE_PX) * 8));
+    const PxView px = pic.view();
+    LAUNCHCHK(spiht_launch_sse_px(&px, d_dec, (int)K, (uint64_t *)ctx->rdpart.p, d_out, ctx->stream));
+    return SPIHT_OK;
+}
+extern "C" int spiht_sse_u8(spiht_ctx *ctx, const uint8_t *d_pic, const int64_t *strides, const uint8_t *d_dec, int64_t K,
+                            int64_t c, int64_t H, int64_t W, uint64_t *d_out) {
+    return sse_px(1, ctx, d_pic, strides, d_dec, K, c, H, W, d_out);
+}
+extern "C" int spiht_sse_u16(spiht_ctx *ctx, const uint16_t *d_pic, const int64_t *strides, const uint16_t *d_dec, int64_t K,
+                             int64_t c, int64_t H, int64_t W, uint64_t *d_out) {
+    return sse_px(2, ctx, d_pic, strides, d_dec, K, c, H, W, d_out);
 }
 
 // ------------------------------------------------------------------------------------------------

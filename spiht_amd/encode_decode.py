@@ -15,6 +15,7 @@ import numpy as np
 
 from .spiht_wrapper import (EncodingResult, SpihtSettings, decode_image, decode_image_reduced_u8, encode_image,
                             get_slices_and_h_w)
+from .rd import cut_to_psnr, rd_curve
 from .utils import imload, imsave, load_encoding, save_encoding
 
 _ARGS = [  # (flag, type, default, help): the reference tool's options, then ours
@@ -29,6 +30,8 @@ _ARGS = [  # (flag, type, default, help): the reference tool's options, then our
     ("--save", str, None, "also write the encoding to this file"),
     ("--load", str, None, "decode this encoding instead of encoding the image"),
     ("--reduce", int, 0, "decode at 1/2^K size (K pyramid levels below full size) and save that picture"),
+    ("--psnr", float, None, "cut the stream to the shortest prefix found that reaches this PSNR in dB (of the float picture)"),
+    ("--rd-curve", int, None, "print N rows of the stream's rate-distortion curve: bytes, bpp, PSNR"),
 ]
 
 
@@ -88,6 +91,17 @@ def main(args):
         print("encoding %d x %d x %d at %.3f bpp" % (c, h, w, args.bpp))
         enc, secs = timed(encode_image, picture, p.settings, p.level, p.max_bits)
     report_encoding(enc, p.settings, secs)
+    if args.rd_curve is not None:
+        # (a loaded stream carries its own level: the one the decode below uses)
+        curve, secs = timed(lambda: rd_curve(picture, p.settings, enc.level, result=enc, points=args.rd_curve))
+        print("rate-distortion curve, %d prefixes in %.3f s" % (len(curve.byte_lengths), secs))
+        print("  %10s %10s %10s" % ("bytes", "bpp", "PSNR dB"))
+        for nbytes, bpp, db in zip(curve.byte_lengths, curve.bpp, curve.psnr):
+            print("  %10d %10.4f %10.3f" % (nbytes, bpp, db))
+    if args.psnr is not None:
+        (enc, db, met), secs = timed(cut_to_psnr, picture, enc, args.psnr, p.settings)
+        print("cut to %.2f dB in %.3f s: %d bytes, PSNR %.3f dB%s" % (args.psnr, secs, len(enc.encoded_bytes), db,
+                                                                   "" if met else " (the whole stream: target not reached)"))
     if args.save:
         save_encoding(args.save, enc)
         print("  encoding written to", args.save)
