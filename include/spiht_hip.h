@@ -570,6 +570,63 @@ int spiht_sse_u16(spiht_ctx *ctx, const uint16_t *d_pic, const int64_t *strides,
                   int64_t H, int64_t W, uint64_t *d_out);
 
 /* ---------------------------------------------------------------------------------------
+ * Tiled pictures (csrc/tiles.hip): one picture as gy x gx equal tiles of th x tw, every tile coded as a picture of its own by
+ * the batched calls above -- so a tile's stream is exactly what the single-image encode gives for the tile's pixels.  Tiles
+ * are in row-major order; tile (i, j) covers rows i*th .. i*th+th-1 and columns j*tw .. j*tw+tw-1 of the picture EXTENDED BY
+ * EDGE REPLICATION to (gy*th) x (gx*tw): numpy's np.pad(P, mode="edge").  One tile shape per picture, th, tw >= 8.
+ * Additions only: the ABI version stays at 2; the next change of an EXISTING signature bumps it.
+ * All pointers of the four copy calls are DEVICE pointers; they are asynchronous on the context's stream like the *_batch_*
+ * calls, argument errors are returned before anything is queued, and no byte outside the stated output is written.
+ *   spiht_tile_grid    gy = ceil(H / th), gx = ceil(W / tw); T = gy * gx.  Pure arithmetic, no device.  SPIHT_ERR_ARG for
+ *                      H, W < 1 or th, tw < 8; SPIHT_ERR_TOO_LARGE for H, W >= 2^30 or th, tw > 2^24.
+ *   spiht_tile_cut_*   d_img: N pictures [N, c, H, W] -> d_tiles: dense [N * T, c, th, tw] of the same element type (picture n's
+ *                      tiles at rows [n*T, (n+1)*T)).  _u8 / _u16: strides[4] = (sb, sc, sh, sw) in bytes under the rules of
+ *                      spiht_check_view_u8 / _u16 for a view that is read (NULL: dense CHW), so HWC and RGBA views are cut as
+ *                      they lie; _f32 / _f64: dense CHW.  N * T < 2^31, c <= 65535.
+ *   spiht_tile_paste_* d_tiles: dense [(i1-i0) * (j1-j0), c, rh, rw], the tiles of the sub-grid [i0, i1) x [j0, j1) in
+ *                      row-major order, rh >= th, rw >= tw (the float64 decode's rec_H x rec_W is one longer on an odd axis;
+ *                      the integer decodes are cropped already) -> d_out: the window [c, wh, ww] of the H x W picture whose
+ *                      first sample is picture sample (y0, x0).  Every output sample comes from the one tile that owns it;
+ *                      rows / columns >= th / tw of a tile and the replicated padding are never read into the window.  The
+ *                      window must lie in the picture and the sub-grid must hold every tile it meets (SPIHT_ERR_ARG).
+ *                      _u8 / _u16: out_strides[3] = (sc, sh, sw) in bytes under the rule for a view that is WRITTEN (NULL:
+ *                      dense CHW): what lies between the view's samples -- an RGBA buffer's alpha -- is not written.
+ *   spiht_tile_pack    T stream slots (slot_stride apart, as the batched encode calls leave them) + d_nbits [T] -> d_packed:
+ *                      the streams' bytes one behind the other, stream t ceil(nbits[t] / 8) bytes long (the rounding of
+ *                      spiht_nbits_to_nbytes), and d_lens: uint32 [T], those lengths.  An exclusive scan of the lengths on the
+ *                      device, then the gather.  Nothing is written at or past d_packed + packed_cap (T * slot_stride always
+ *                      suffices; the table tells the host what the run needs).  A zero-length stream and T = 1 are ordinary.
+ *   spiht_tile_unpack  the inverse: d_packed (packed_bytes long) + d_lens [T] -> T slots, every byte of a slot past its
+ *                      stream's end zero, and d_nbytes: uint64 [T] -- what the batched decode calls take.  A length is taken
+ *                      as at most slot_stride; bytes a table claims past packed_bytes read as zero.
+ * slot_stride: a multiple of 4, at most 2^29. */
+int spiht_tile_grid(int64_t H, int64_t W, int64_t th, int64_t tw, int64_t *gy, int64_t *gx);
+int spiht_tile_cut_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H, int64_t W,
+                      int64_t th, int64_t tw, uint8_t *d_tiles);
+int spiht_tile_cut_u16(spiht_ctx *ctx, const uint16_t *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H, int64_t W,
+                       int64_t th, int64_t tw, uint16_t *d_tiles);
+int spiht_tile_cut_f32(spiht_ctx *ctx, const float *d_img, int64_t N, int64_t c, int64_t H, int64_t W, int64_t th, int64_t tw,
+                       float *d_tiles);
+int spiht_tile_cut_f64(spiht_ctx *ctx, const double *d_img, int64_t N, int64_t c, int64_t H, int64_t W, int64_t th, int64_t tw,
+                       double *d_tiles);
+int spiht_tile_paste_u8(spiht_ctx *ctx, const uint8_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                        int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0, int64_t wh,
+                        int64_t ww, uint8_t *d_out, const int64_t *out_strides);
+int spiht_tile_paste_u16(spiht_ctx *ctx, const uint16_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                         int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
+                         int64_t wh, int64_t ww, uint16_t *d_out, const int64_t *out_strides);
+int spiht_tile_paste_f32(spiht_ctx *ctx, const float *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W, int64_t th,
+                         int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0, int64_t wh,
+                         int64_t ww, float *d_out);
+int spiht_tile_paste_f64(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                         int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
+                         int64_t wh, int64_t ww, double *d_out);
+int spiht_tile_pack(spiht_ctx *ctx, const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbits, int64_t T,
+                    uint8_t *d_packed, uint64_t packed_cap, uint32_t *d_lens);
+int spiht_tile_unpack(spiht_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint32_t *d_lens, int64_t T,
+                      uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes);
+
+/* ---------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, every rank codes its own images (the reference's encode / decode
  * are pure functions of one image, src/lib.rs:24-42 -- nothing is exchanged while coding); the ONE exchange of the
  * path is the gather of the finished streams.  It runs on RCCL (ncclAllGather over xGMI), inside this library, on

@@ -10,7 +10,7 @@ import sys
 
 import spiht_amd as _impl
 
-_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode", "rd")
+_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode", "rd", "tiles")
 for _name in _SUBMODULES:
     # `spiht.spiht` is the reference's compiled extension (src/lib.rs:58-65); here spiht_amd/spiht.py over the C ABI
     _mod = importlib.import_module("spiht_amd." + _name)
@@ -26,4 +26,10 @@ globals().update({_k: getattr(_impl, _k) for _k in ("decode_image_reduced", "dec
 # ... the rate-distortion curve of a stream and the cut to a target quality
 globals().update({_k: getattr(_impl, _k) for _k in ("RDCurve", "rd_curve", "rd_curve_u8", "rd_curve_u16", "cut_to_psnr",
                                                     "cut_to_psnr_u8", "cut_to_psnr_u16")})
+# ... tiled pictures: one stream per tile, parallel and windowed decode
+globals().update({_k: getattr(_impl, _k) for _k in ("TiledCodec", "TiledResult", "tile_grid", "window_tiles",
+                                                    "encode_image_tiled", "encode_image_tiled_u8", "encode_image_tiled_u16",
+                                                    "decode_image_tiled", "decode_image_tiled_u8", "decode_image_tiled_u16",
+                                                    "decode_image_window", "decode_image_window_u8",
+                                                    "decode_image_window_u16")})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

@@ -62,6 +62,9 @@ SYMBOLS = [
     "spiht_decode_image_reduced_batch_f64", "spiht_decode_image_reduced_batch_u8", "spiht_decode_image_reduced_batch_u16",
     "spiht_decode_image_reduced_host_f64", "spiht_decode_image_reduced_host_u8", "spiht_decode_image_reduced_host_u16",
     "spiht_sqerr_i32", "spiht_sse_f64", "spiht_sse_u8", "spiht_sse_u16",
+    "spiht_tile_grid", "spiht_tile_cut_u8", "spiht_tile_cut_u16", "spiht_tile_cut_f32", "spiht_tile_cut_f64",
+    "spiht_tile_paste_u8", "spiht_tile_paste_u16", "spiht_tile_paste_f32", "spiht_tile_paste_f64",
+    "spiht_tile_pack", "spiht_tile_unpack",
 ]
 
 
@@ -207,6 +210,14 @@ def lib():
         L.spiht_sqerr_i32.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp]
         L.spiht_sse_f64.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, i64, vp]
         L.spiht_sse_u8.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, vp]
+        # tiled pictures: geometry, the two picture <-> tile-batch copies per element type, streams <-> one run of bytes
+        L.spiht_tile_grid.argtypes = [i64, i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]
+        L.spiht_tile_cut_u8.argtypes = [vp, vp, vp] + [i64] * 6 + [vp]
+        L.spiht_tile_cut_f32.argtypes = L.spiht_tile_cut_f64.argtypes = [vp, vp] + [i64] * 6 + [vp]
+        L.spiht_tile_paste_u8.argtypes = [vp, vp] + [i64] * 15 + [vp, vp]
+        L.spiht_tile_paste_f32.argtypes = L.spiht_tile_paste_f64.argtypes = [vp, vp] + [i64] * 15 + [vp]
+        L.spiht_tile_pack.argtypes = [vp, vp, u64, vp, i64, vp, u64, vp]
+        L.spiht_tile_unpack.argtypes = [vp, vp, u64, vp, i64, vp, u64, vp]
         # 16-bit pixels: every *_u16 call takes what its *_u8 sibling takes
         for name in SYMBOLS:
             if name.endswith("_u16"):

@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "rd.h"
+#include "tiles.h"
 #include "wavelets.h"
 
 extern "C" {
@@ -58,6 +59,12 @@ int spiht_launch_sqerr_i32(const int32_t *d_x, const int32_t *d_y, int K, int c,
 int spiht_launch_sse_f64(const double *d_pic, const double *d_dec, int K, int c, int H, int W, int rec_h, int rec_w, double *part,
                          double *d_out, hipStream_t st);
 int spiht_launch_sse_px(const PxView *px, const void *d_dec, int K, uint64_t *part, uint64_t *d_out, hipStream_t st);
+int spiht_launch_tile_cut(const TileCutArgs *a, int es, int64_t NT, hipStream_t st);
+int spiht_launch_tile_paste(const TilePasteArgs *a, int es, int64_t ntiles, hipStream_t st);
+int spiht_launch_tile_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbytes, int64_t T, uint64_t *d_off,
+                           uint8_t *d_packed, uint64_t cap, uint32_t *d_lens, hipStream_t st);
+int spiht_launch_tile_unpack(const uint8_t *d_packed, uint64_t packed_bytes, const uint32_t *d_lens, int64_t T, uint64_t *d_off,
+                             uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes, hipStream_t st);
 }
 
 static thread_local std::string g_hip_err;
@@ -135,6 +142,7 @@ struct spiht_ctx {
     // decoder output of the fused image path: kept all-zero between calls (k_unscatter), so no per-call zero-fill
     DevBuf recz, lspcnt;
     DevBuf rdpart;              // per-workgroup partial sums of the rate-distortion reductions (rd.hip)
+    DevBuf tilescr;             // tiled pictures (tiles.hip): byte lengths and offsets of the streams pack / unpack move
     bool recz_clean = false;
     // spiht_decode_lists_batch_i32 -> spiht_unscatter_lists_batch_i32: the launch whose scatter can still be undone
     DecArgs last_dec;
@@ -479,7 +487,7 @@ extern "C" void spiht_ctx_destroy(spiht_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->widebuf, &ctx->filt, &ctx->exttmp, &ctx->l1flags, &ctx->x, &ctx->dmsb, &ctx->lmsb, &ctx->maxabs, &ctx->out, &ctx->nbits, &ctx->maxn, &ctx->err,
                       &ctx->lists, &ctx->coeffs, &ctx->a0, &ctx->a1, &ctx->data, &ctx->nbytes, &ctx->rec, &ctx->mults,
                       &ctx->img, &ctx->trace, &ctx->meta, &ctx->recz, &ctx->lspcnt, &ctx->himg, &ctx->hrec, &ctx->tilebuf,
-                      &ctx->pix, &ctx->hpix8, &ctx->rdpart};
+                      &ctx->pix, &ctx->hpix8, &ctx->rdpart, &ctx->tilescr};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &r : ctx->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -2345,6 +2353,152 @@ extern "C" int spiht_sse_u8(spiht_ctx *ctx, const uint8_t *d_pic, const int64_t 
 extern "C" int spiht_sse_u16(spiht_ctx *ctx, const uint16_t *d_pic, const int64_t *strides, const uint16_t *d_dec, int64_t K,
                              int64_t c, int64_t H, int64_t W, uint64_t *d_out) {
     return sse_px(2, ctx, d_pic, strides, d_dec, K, c, H, W, d_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// tiled pictures (tiles.hip): one picture <-> a dense batch of equal tiles, T stream slots <-> one run of bytes
+// ------------------------------------------------------------------------------------------------
+extern "C" int spiht_tile_grid(int64_t H, int64_t W, int64_t th, int64_t tw, int64_t *gy, int64_t *gx) {
+    if (H < 1 || W < 1 || th < 8 || tw < 8) return SPIHT_ERR_ARG;
+    if (H >= (1 << 30) || W >= (1 << 30) || th > (1 << 24) || tw > (1 << 24)) return SPIHT_ERR_TOO_LARGE;
+    if (gy) *gy = (H + th - 1) / th;
+    if (gx) *gx = (W + tw - 1) / tw;
+    return SPIHT_OK;
+}
+// in: the picture batch (dense_pic of a float format, or int_pic's checked view)
+static int tile_cut(spiht_ctx *ctx, const Pic &in, int es, int64_t N, int64_t c, int64_t H, int64_t W, int64_t th, int64_t tw,
+                    void *d_tiles) {
+    if (!ctx || !in.p || !d_tiles || N < 0 || c < 1 || (uintptr_t)in.p % es || (uintptr_t)d_tiles % es) return SPIHT_ERR_ARG;
+    int64_t gy, gx;
+    CHK(spiht_tile_grid(H, W, th, tw, &gy, &gx));
+    if (c > 65535 || (__int128)N * gy * gx > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    if (N == 0) return SPIHT_OK;
+    TileCutArgs a;
+    a.in = (const uint8_t *)in.p;
+    if (in.integer()) {
+        a.sb = in.px.sb; a.sc = in.px.sc; a.sh = in.px.sh; a.sw = in.px.sw;
+    } else {
+        a.sw = es; a.sh = W * es; a.sc = H * a.sh; a.sb = c * a.sc;
+    }
+    a.out = (uint8_t *)d_tiles;
+    a.c = (int32_t)c; a.H = (int32_t)H; a.W = (int32_t)W; a.th = (int32_t)th; a.tw = (int32_t)tw;
+    a.gy = (int32_t)gy; a.gx = (int32_t)gx; a.rows = 0;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    LAUNCHCHK(spiht_launch_tile_cut(&a, es, N * gy * gx, ctx->stream));
+    return SPIHT_OK;
+}
+static int tile_cut_px(int es, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
+                       int64_t W, int64_t th, int64_t tw, void *d_tiles) {
+    if (N < 0 || c < 1 || H < 1 || W < 1) return SPIHT_ERR_ARG;
+    Pic pic;
+    CHK(int_pic(d_img, es, false, strides, 4, std::max<int64_t>(N, 1), c, H, W, &pic));
+    return tile_cut(ctx, pic, es, N, c, H, W, th, tw, d_tiles);
+}
+extern "C" int spiht_tile_cut_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
+                                 int64_t W, int64_t th, int64_t tw, uint8_t *d_tiles) {
+    return tile_cut_px(1, ctx, d_img, strides, N, c, H, W, th, tw, d_tiles);
+}
+extern "C" int spiht_tile_cut_u16(spiht_ctx *ctx, const uint16_t *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
+                                  int64_t W, int64_t th, int64_t tw, uint16_t *d_tiles) {
+    return tile_cut_px(2, ctx, d_img, strides, N, c, H, W, th, tw, d_tiles);
+}
+extern "C" int spiht_tile_cut_f32(spiht_ctx *ctx, const float *d_img, int64_t N, int64_t c, int64_t H, int64_t W, int64_t th,
+                                  int64_t tw, float *d_tiles) {
+    return tile_cut(ctx, dense_pic(d_img, PIC_F32), 4, N, c, H, W, th, tw, d_tiles);
+}
+extern "C" int spiht_tile_cut_f64(spiht_ctx *ctx, const double *d_img, int64_t N, int64_t c, int64_t H, int64_t W, int64_t th,
+                                  int64_t tw, double *d_tiles) {
+    return tile_cut(ctx, dense_pic(d_img, PIC_F64), 8, N, c, H, W, th, tw, d_tiles);
+}
+
+// out: the window (dense_pic of a float format, or int_pic's checked view of [c, wh, ww])
+static int tile_paste(spiht_ctx *ctx, const void *d_tiles, const Pic &out, int es, int64_t c, int64_t rh, int64_t rw, int64_t H,
+                      int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
+                      int64_t wh, int64_t ww) {
+    if (!ctx || !d_tiles || !out.p || c < 1 || (uintptr_t)d_tiles % es || (uintptr_t)out.p % es) return SPIHT_ERR_ARG;
+    int64_t gy, gx;
+    CHK(spiht_tile_grid(H, W, th, tw, &gy, &gx));
+    if (rh < th || rw < tw || rh > th + (1 << 24) || rw > tw + (1 << 24)) return SPIHT_ERR_ARG;
+    if (i0 < 0 || i1 <= i0 || i1 > gy || j0 < 0 || j1 <= j0 || j1 > gx) return SPIHT_ERR_ARG;
+    // the window lies in the picture, and the sub-grid holds every tile it meets
+    if (y0 < 0 || x0 < 0 || wh < 1 || ww < 1 || y0 + wh > H || x0 + ww > W) return SPIHT_ERR_ARG;
+    if (y0 / th < i0 || (y0 + wh - 1) / th >= i1 || x0 / tw < j0 || (x0 + ww - 1) / tw >= j1) return SPIHT_ERR_ARG;
+    if (c > 65535 || (__int128)(i1 - i0) * (j1 - j0) > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    TilePasteArgs a;
+    a.tiles = (const uint8_t *)d_tiles;
+    a.out = (uint8_t *)out.p;
+    if (out.integer()) {
+        a.sc = out.px.sc; a.sh = out.px.sh; a.sw = out.px.sw;
+    } else {
+        a.sw = es; a.sh = ww * es; a.sc = wh * a.sh;
+    }
+    a.c = (int32_t)c; a.rh = (int32_t)rh; a.rw = (int32_t)rw; a.th = (int32_t)th; a.tw = (int32_t)tw;
+    a.i0 = (int32_t)i0; a.j0 = (int32_t)j0; a.nj = (int32_t)(j1 - j0);
+    a.y0 = (int32_t)y0; a.x0 = (int32_t)x0; a.wh = (int32_t)wh; a.ww = (int32_t)ww; a.rows = 0;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    LAUNCHCHK(spiht_launch_tile_paste(&a, es, (i1 - i0) * (j1 - j0), ctx->stream));
+    return SPIHT_OK;
+}
+static int tile_paste_px(int es, spiht_ctx *ctx, const void *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                         int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0, int64_t wh,
+                         int64_t ww, void *d_out, const int64_t *out_strides) {
+    if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
+    Pic pic;
+    CHK(int_pic(d_out, es, true, out_strides, 3, 1, c, wh, ww, &pic));
+    return tile_paste(ctx, d_tiles, pic, es, c, rh, rw, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww);
+}
+extern "C" int spiht_tile_paste_u8(spiht_ctx *ctx, const uint8_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                                   int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
+                                   int64_t wh, int64_t ww, uint8_t *d_out, const int64_t *out_strides) {
+    return tile_paste_px(1, ctx, d_tiles, c, rh, rw, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww, d_out, out_strides);
+}
+extern "C" int spiht_tile_paste_u16(spiht_ctx *ctx, const uint16_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H,
+                                    int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                                    int64_t x0, int64_t wh, int64_t ww, uint16_t *d_out, const int64_t *out_strides) {
+    return tile_paste_px(2, ctx, d_tiles, c, rh, rw, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww, d_out, out_strides);
+}
+extern "C" int spiht_tile_paste_f32(spiht_ctx *ctx, const float *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                                    int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
+                                    int64_t wh, int64_t ww, float *d_out) {
+    return tile_paste(ctx, d_tiles, dense_pic(d_out, PIC_F32, true), 4, c, rh, rw, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww);
+}
+extern "C" int spiht_tile_paste_f64(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                                    int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
+                                    int64_t wh, int64_t ww, double *d_out) {
+    return tile_paste(ctx, d_tiles, dense_pic(d_out, PIC_F64, true), 8, c, rh, rw, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww);
+}
+
+// the checks pack and unpack share; the scratch: uint64 [T] byte lengths (pack), uint64 [T] offsets
+static int tile_streams_args(spiht_ctx *ctx, const void *a, const void *b, const void *d, const void *e, uint64_t slot_stride,
+                             int64_t T) {
+    if (!ctx || !a || !b || !d || !e || T < 0 || slot_stride == 0 || slot_stride % 4) return SPIHT_ERR_ARG;
+    if (T > 0x7FFFFFFF || slot_stride > ((uint64_t)1 << 29)) return SPIHT_ERR_TOO_LARGE;
+    return SPIHT_OK;
+}
+extern "C" int spiht_tile_pack(spiht_ctx *ctx, const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbits, int64_t T,
+                               uint8_t *d_packed, uint64_t packed_cap, uint32_t *d_lens) {
+    CHK(tile_streams_args(ctx, d_slots, d_nbits, d_packed, d_lens, slot_stride, T));
+    if (T == 0) return SPIHT_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->tilescr, (size_t)T * 16));
+    uint64_t *d_nbytes = (uint64_t *)ctx->tilescr.p, *d_off = d_nbytes + T;
+    CHK(spiht_nbits_to_nbytes(ctx, d_nbits, T, d_nbytes));
+    LAUNCHCHK(spiht_launch_tile_pack(d_slots, slot_stride, d_nbytes, T, d_off, d_packed, packed_cap, d_lens, ctx->stream));
+    return SPIHT_OK;
+}
+extern "C" int spiht_tile_unpack(spiht_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, const uint32_t *d_lens, int64_t T,
+                                 uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes) {
+    CHK(tile_streams_args(ctx, d_packed, d_lens, d_slots, d_nbytes, slot_stride, T));
+    if (T == 0) return SPIHT_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->tilescr, (size_t)T * 16));
+    LAUNCHCHK(spiht_launch_tile_unpack(d_packed, packed_bytes, d_lens, T, (uint64_t *)ctx->tilescr.p + T, d_slots, slot_stride,
+                                       d_nbytes, ctx->stream));
+    return SPIHT_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,0 +1,277 @@
+// Tiled pictures (gfx950): one picture as a batch of equal tiles, each coded as a picture of its own by the batched calls.
+//   k_tile_cut     picture batch [N, c, H, W] -> dense tile batch [N * T, c, th, tw]; samples past the picture's bottom /
+//                  right edge repeat the last row / column (numpy's np.pad(mode="edge"))
+//   k_tile_paste   dense tile batch of a sub-grid -> a window of the picture; every sample from the one tile that owns it
+//   k_tile_scan    stream lengths -> their exclusive prefix sums (one workgroup)
+//   k_tile_pack    T stream slots -> one contiguous run of bytes
+//   k_tile_unpack  the run -> T zero-padded slots
+// All of them are copies with index arithmetic.  A lane stores 16 bytes at a 16-byte-aligned address of the destination
+// wherever the destination is contiguous; what lies in front of the first and behind the last such address of a row (a
+// stream) goes element by element (byte by byte).  The source side: cut / paste load 16 bytes where the source address is
+// aligned as well and element by element where it is not; pack / unpack, whose two sides are never aligned to one another,
+// load the aligned 32-bit words around the bytes and shift them into place.
+#include "tiles.h"
+
+#include <algorithm>
+
+template <int ES> struct ElemOf;
+template <> struct ElemOf<1> { typedef uint8_t type; };
+template <> struct ElemOf<2> { typedef uint16_t type; };
+template <> struct ElemOf<4> { typedef uint32_t type; };
+template <> struct ElemOf<8> { typedef uint64_t type; };
+
+// One row: n elements of ES bytes, element k from src + min(k, nvalid - 1) * ss (replication past nvalid) to dst + k * ds.
+// The lanes lane, lane + nlanes, ... of the caller share the row.  dst, src and the strides are multiples of ES.
+template <int ES>
+__device__ __forceinline__ void copy_row(uint8_t *dst, int64_t ds, const uint8_t *src, int64_t ss, int n, int nvalid, int lane,
+                                         int nlanes) {
+    typedef typename ElemOf<ES>::type T;
+    constexpr int EPV = 16 / ES;
+    if (ds != ES) {  // a strided destination (HWC, RGBA): what lies between the elements is not written
+        for (int k = lane; k < n; k += nlanes)
+            *reinterpret_cast<T *>(dst + (int64_t)k * ds) = *reinterpret_cast<const T *>(src + (int64_t)min(k, nvalid - 1) * ss);
+        return;
+    }
+    const int a = (int)((uintptr_t)dst & 15), nbytes = n * ES;
+    const int nvec = (a + nbytes + 15) >> 4;
+    for (int v = lane; v < nvec; v += nlanes) {
+        const int p = 16 * v - a;  // bytes from dst; a multiple of ES, negative in the first vector of an unaligned row
+        const int k0 = p / ES;
+        if (p >= 0 && p + 16 <= nbytes) {
+            const uint8_t *s = src + (int64_t)k0 * ss;
+            uint4 q;
+            if (ss == ES && k0 + EPV <= nvalid && ((uintptr_t)s & 15) == 0) {
+                q = *reinterpret_cast<const uint4 *>(s);
+            } else {
+                T e[EPV];
+#pragma unroll
+                for (int i = 0; i < EPV; i++) e[i] = *reinterpret_cast<const T *>(src + (int64_t)min(k0 + i, nvalid - 1) * ss);
+                __builtin_memcpy(&q, e, 16);
+            }
+            *reinterpret_cast<uint4 *>(dst + p) = q;
+        } else {
+#pragma unroll
+            for (int i = 0; i < EPV; i++) {
+                const int k = k0 + i;
+                if (k >= 0 && k < n)
+                    *reinterpret_cast<T *>(dst + (int64_t)k * ES) = *reinterpret_cast<const T *>(src + (int64_t)min(k, nvalid - 1) * ss);
+            }
+        }
+    }
+}
+
+// grid (N * T, c, row chunks); block (bx, by): bx lanes along a row, by rows at a time
+template <int ES>
+__global__ __launch_bounds__(TL_THREADS) void k_tile_cut(const TileCutArgs a) {
+    const uint32_t nt = blockIdx.x, ch = blockIdx.y, T = (uint32_t)a.gy * (uint32_t)a.gx;
+    const uint32_t n = nt / T, t = nt - n * T;
+    const int i = (int)(t / (uint32_t)a.gx), j = (int)(t - (uint32_t)i * (uint32_t)a.gx);
+    const int X0 = j * a.tw, nvalid = min(a.tw, a.W - X0);
+    const uint8_t *src0 = a.in + (int64_t)n * a.sb + (int64_t)ch * a.sc + (int64_t)X0 * a.sw;
+    uint8_t *dst0 = a.out + ((size_t)nt * a.c + ch) * (size_t)a.th * a.tw * ES;
+    const int ya = (int)blockIdx.z * a.rows, yb = min(ya + a.rows, a.th);
+    for (int y = ya + (int)threadIdx.y; y < yb; y += (int)blockDim.y) {
+        const int Y = min(i * a.th + y, a.H - 1);
+        copy_row<ES>(dst0 + (size_t)y * a.tw * ES, ES, src0 + (int64_t)Y * a.sh, a.sw, a.tw, nvalid, (int)threadIdx.x, (int)blockDim.x);
+    }
+}
+
+// grid (tiles of the sub-grid, c, row chunks); a tile that does not meet the window has nothing to do
+template <int ES>
+__global__ __launch_bounds__(TL_THREADS) void k_tile_paste(const TilePasteArgs a) {
+    const uint32_t s = blockIdx.x, ch = blockIdx.y;
+    const int si = (int)(s / (uint32_t)a.nj), sj = (int)(s - (uint32_t)si * (uint32_t)a.nj);
+    const int i = a.i0 + si, j = a.j0 + sj;
+    const int Ya = max(i * a.th, a.y0), Yb = min((i + 1) * a.th, a.y0 + a.wh);
+    const int Xa = max(j * a.tw, a.x0), Xb = min((j + 1) * a.tw, a.x0 + a.ww);
+    if (Xb <= Xa || Yb <= Ya) return;
+    const int n = Xb - Xa;
+    const uint8_t *src0 = a.tiles + ((size_t)s * a.c + ch) * (size_t)a.rh * a.rw * ES + (size_t)(Xa - j * a.tw) * ES;
+    uint8_t *dst0 = a.out + (int64_t)ch * a.sc + (int64_t)(Xa - a.x0) * a.sw;
+    const int ya = Ya + (int)blockIdx.z * a.rows, yb = min(ya + a.rows, Yb);
+    for (int Y = ya + (int)threadIdx.y; Y < yb; Y += (int)blockDim.y)
+        copy_row<ES>(dst0 + (int64_t)(Y - a.y0) * a.sh, a.sw, src0 + (size_t)(Y - i * a.th) * a.rw * ES, ES, n, n, (int)threadIdx.x,
+                     (int)blockDim.x);
+}
+
+// in[T] (each taken as min(in[t], lim)) -> off[t] = the sum of those before t, out[t] = the clipped value in the other
+// width.  One workgroup: 256 lengths per round, a carry between rounds.
+template <typename TIN, typename TOUT>
+__global__ __launch_bounds__(TL_THREADS) void k_tile_scan(const TIN *__restrict__ in, uint32_t T, uint64_t lim,
+                                                          uint64_t *__restrict__ off, TOUT *__restrict__ out) {
+    __shared__ uint64_t wsum[TL_THREADS / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < T; base += TL_THREADS) {
+        const uint32_t idx = base + tid;
+        uint64_t v = 0;
+        if (idx < T) v = min((uint64_t)in[idx], lim);
+        uint64_t x = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint64_t y = __shfl_up(x, o);
+            if ((int)lane >= o) x += y;
+        }
+        if (lane == 63) wsum[wv] = x;
+        __syncthreads();
+        uint64_t pre = 0, total = 0;
+        for (uint32_t k = 0; k < TL_THREADS / 64; k++) {
+            if (k < wv) pre += wsum[k];
+            total += wsum[k];
+        }
+        if (idx < T) {
+            off[idx] = carry + pre + x - v;
+            out[idx] = (TOUT)v;
+        }
+        carry += total;
+        __syncthreads();
+    }
+}
+
+// a 16-byte load from an address that is only 4-byte aligned
+struct __attribute__((packed, aligned(4))) U32x4u {
+    uint32_t v[4];
+};
+
+// One workgroup's share (chunk) of n_total destination bytes at dst: byte pos is src[pos] for pos < n_copy and zero behind.
+// Chunks are cut at 16-byte-aligned addresses of dst.  [lo, hi) is what may be read around src (lo 4-byte aligned): a vector
+// whose source words lie inside it is loaded as aligned 32-bit words and shifted, any other byte by byte.
+__device__ __forceinline__ void copy_bytes(uint8_t *dst, const uint8_t *src, uint64_t n_total, uint64_t n_copy, const uint8_t *lo,
+                                           const uint8_t *hi, uint32_t chunk) {
+    const int64_t nt = (int64_t)n_total, nc = (int64_t)n_copy;
+    const int64_t pbase = (int64_t)chunk * TL_CHUNK - (int64_t)((uintptr_t)dst & 15);
+    if (pbase >= nt) return;
+#pragma unroll
+    for (int r = 0; r < TL_CHUNK / 16 / TL_THREADS; r++) {
+        const int64_t p = pbase + 16 * (int64_t)(r * TL_THREADS + (int)threadIdx.x);
+        if (p >= nt || p + 16 <= 0) continue;
+        if (p >= 0 && p + 16 <= nt) {
+            uint4 q = make_uint4(0, 0, 0, 0);
+            if (p + 16 <= nc) {
+                const uint8_t *s = src + p;
+                const uint32_t m = (uint32_t)((uintptr_t)s & 3);
+                const uint8_t *sa = s - m;
+                if (sa >= lo && sa + (m ? 20 : 16) <= hi) {
+                    const U32x4u w = *reinterpret_cast<const U32x4u *>(sa);
+                    uint32_t w4 = 0;
+                    if (m) w4 = *reinterpret_cast<const uint32_t *>(sa + 16);
+                    q.x = __builtin_amdgcn_alignbyte(w.v[1], w.v[0], m);
+                    q.y = __builtin_amdgcn_alignbyte(w.v[2], w.v[1], m);
+                    q.z = __builtin_amdgcn_alignbyte(w.v[3], w.v[2], m);
+                    q.w = __builtin_amdgcn_alignbyte(w4, w.v[3], m);
+                } else {
+                    uint8_t e[16];
+#pragma unroll
+                    for (int i = 0; i < 16; i++) e[i] = s[i];
+                    __builtin_memcpy(&q, e, 16);
+                }
+            } else if (p < nc) {
+                uint8_t e[16];
+#pragma unroll
+                for (int i = 0; i < 16; i++) e[i] = p + i < nc ? src[p + i] : (uint8_t)0;
+                __builtin_memcpy(&q, e, 16);
+            }
+            *reinterpret_cast<uint4 *>(dst + p) = q;
+        } else {
+            for (int i = 0; i < 16; i++) {
+                const int64_t pos = p + i;
+                if (pos >= 0 && pos < nt) dst[pos] = pos < nc ? src[pos] : (uint8_t)0;
+            }
+        }
+    }
+}
+
+// grid (T, chunks of a slot).  Stream t: lens[t] bytes of slot t to packed + off[t]; nothing is written at or past cap.
+__global__ __launch_bounds__(TL_THREADS) void k_tile_pack(const uint8_t *__restrict__ slots, uint64_t slot_stride,
+                                                          const uint32_t *__restrict__ lens, const uint64_t *__restrict__ off,
+                                                          uint8_t *__restrict__ packed, uint64_t cap) {
+    const uint32_t t = blockIdx.x;
+    const uint64_t o = off[t];
+    if (o >= cap) return;
+    const uint64_t len = min((uint64_t)lens[t], cap - o);
+    const uint8_t *src = slots + (size_t)t * slot_stride;
+    copy_bytes(packed + o, src, len, len, src, src + slot_stride, blockIdx.y);
+}
+
+// grid (T, chunks of a slot).  Slot t: the nbytes[t] bytes at packed + off[t] (those that lie inside the run), then zeros up
+// to slot_stride.
+__global__ __launch_bounds__(TL_THREADS) void k_tile_unpack(const uint8_t *__restrict__ packed, uint64_t packed_bytes,
+                                                            const uint64_t *__restrict__ nbytes, const uint64_t *__restrict__ off,
+                                                            uint8_t *__restrict__ slots, uint64_t slot_stride) {
+    const uint32_t t = blockIdx.x;
+    const uint64_t o = off[t];
+    const uint64_t len = o < packed_bytes ? min(nbytes[t], packed_bytes - o) : 0;
+    copy_bytes(slots + (size_t)t * slot_stride, packed + min(o, packed_bytes), slot_stride, len, packed, packed + packed_bytes,
+               blockIdx.y);
+}
+
+// ---- host launchers ------------------------------------------------------------------------------------------------------
+
+// The workgroup's shape for rows of `units` pieces (16-byte vectors, or elements of a strided row) of row_bytes bytes, `rows`
+// of them: bx lanes along the row (a power of two), 256 / bx rows at a time, about TL_BLOCK_BYTES per workgroup.
+static void row_blocks(int64_t units, int64_t row_bytes, int64_t rows, dim3 *block, int *rows_per_wg, uint32_t *gz) {
+    int bx = 1;
+    while (bx < units && bx < TL_THREADS) bx *= 2;
+    const int by = TL_THREADS / bx;
+    int64_t per = (int64_t)by * std::max<int64_t>(1, TL_BLOCK_BYTES / std::max<int64_t>(1, row_bytes * by));
+    if ((rows + per - 1) / per > 65535) per = ((rows + 65534) / 65535 + by - 1) / by * by;
+    *block = dim3(bx, by);
+    *rows_per_wg = (int)per;
+    *gz = (uint32_t)std::max<int64_t>(1, (rows + per - 1) / per);
+}
+
+template <int ES>
+static int launch_cut(TileCutArgs a, int64_t NT, hipStream_t st) {
+    dim3 block;
+    uint32_t gz;
+    row_blocks(((int64_t)a.tw * ES + 15) / 16 + 1, (int64_t)a.tw * ES, a.th, &block, &a.rows, &gz);
+    hipLaunchKernelGGL(k_tile_cut<ES>, dim3((uint32_t)NT, a.c, gz), block, 0, st, a);
+    return (int)hipGetLastError();
+}
+extern "C" int spiht_launch_tile_cut(const TileCutArgs *a, int es, int64_t NT, hipStream_t st) {
+    switch (es) {
+    case 1: return launch_cut<1>(*a, NT, st);
+    case 2: return launch_cut<2>(*a, NT, st);
+    case 4: return launch_cut<4>(*a, NT, st);
+    default: return launch_cut<8>(*a, NT, st);
+    }
+}
+
+template <int ES>
+static int launch_paste(TilePasteArgs a, int64_t ntiles, hipStream_t st) {
+    dim3 block;
+    uint32_t gz;
+    const int64_t n = std::min<int64_t>(a.tw, a.ww);  // the longest row piece a tile gives
+    row_blocks(a.sw == ES ? (n * ES + 15) / 16 + 1 : n, n * ES, std::min<int64_t>(a.th, a.wh), &block, &a.rows, &gz);
+    hipLaunchKernelGGL(k_tile_paste<ES>, dim3((uint32_t)ntiles, a.c, gz), block, 0, st, a);
+    return (int)hipGetLastError();
+}
+extern "C" int spiht_launch_tile_paste(const TilePasteArgs *a, int es, int64_t ntiles, hipStream_t st) {
+    switch (es) {
+    case 1: return launch_paste<1>(*a, ntiles, st);
+    case 2: return launch_paste<2>(*a, ntiles, st);
+    case 4: return launch_paste<4>(*a, ntiles, st);
+    default: return launch_paste<8>(*a, ntiles, st);
+    }
+}
+
+static uint32_t slot_chunks(uint64_t slot_stride) { return (uint32_t)((slot_stride + 15 + TL_CHUNK - 1) / TL_CHUNK); }
+
+// d_nbytes [T] (scratch: the streams' byte lengths) -> d_off [T] (scratch), d_lens [T]; then the gather
+extern "C" int spiht_launch_tile_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbytes, int64_t T,
+                                      uint64_t *d_off, uint8_t *d_packed, uint64_t cap, uint32_t *d_lens, hipStream_t st) {
+    hipLaunchKernelGGL((k_tile_scan<uint64_t, uint32_t>), dim3(1), dim3(TL_THREADS), 0, st, d_nbytes, (uint32_t)T, slot_stride, d_off,
+                       d_lens);
+    hipLaunchKernelGGL(k_tile_pack, dim3((uint32_t)T, slot_chunks(slot_stride)), dim3(TL_THREADS), 0, st, d_slots, slot_stride,
+                       (const uint32_t *)d_lens, (const uint64_t *)d_off, d_packed, cap);
+    return (int)hipGetLastError();
+}
+// d_lens [T] -> d_off [T] (scratch), d_nbytes [T]; then the scatter into zero-padded slots
+extern "C" int spiht_launch_tile_unpack(const uint8_t *d_packed, uint64_t packed_bytes, const uint32_t *d_lens, int64_t T,
+                                        uint64_t *d_off, uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes,
+                                        hipStream_t st) {
+    hipLaunchKernelGGL((k_tile_scan<uint32_t, uint64_t>), dim3(1), dim3(TL_THREADS), 0, st, d_lens, (uint32_t)T, slot_stride, d_off,
+                       d_nbytes);
+    hipLaunchKernelGGL(k_tile_unpack, dim3((uint32_t)T, slot_chunks(slot_stride)), dim3(TL_THREADS), 0, st, d_packed, packed_bytes,
+                       (const uint64_t *)d_nbytes, (const uint64_t *)d_off, d_slots, slot_stride);
+    return (int)hipGetLastError();
+}

@@ -16,6 +16,7 @@ import numpy as np
 from .spiht_wrapper import (EncodingResult, SpihtSettings, decode_image, decode_image_reduced_u8, encode_image,
                             get_slices_and_h_w)
 from .rd import cut_to_psnr, rd_curve
+from .tiles import decode_image_tiled, decode_image_window, encode_image_tiled
 from .utils import imload, imsave, load_encoding, save_encoding
 
 _ARGS = [  # (flag, type, default, help): the reference tool's options, then ours
@@ -32,6 +33,8 @@ _ARGS = [  # (flag, type, default, help): the reference tool's options, then our
     ("--reduce", int, 0, "decode at 1/2^K size (K pyramid levels below full size) and save that picture"),
     ("--psnr", float, None, "cut the stream to the shortest prefix found that reaches this PSNR in dB (of the float picture)"),
     ("--rd-curve", int, None, "print N rows of the stream's rate-distortion curve: bytes, bpp, PSNR"),
+    ("--tile", int, None, "code the picture as tiles of N x N, one stream per tile (the bit budget is shared equally)"),
+    ("--window", str, None, "with --tile: decode only the window Y0,X0,H,W of the picture and save that"),
 ]
 
 
@@ -81,8 +84,40 @@ def report_encoding(enc: EncodingResult, settings: SpihtSettings, seconds: Optio
     print("  level %s, start plane %d, coarsest band %d x %d" % (enc.level, enc.max_n, slices[0][1].stop, slices[0][2].stop))
 
 
+def main_tiled(args, picture):
+    """--tile N [--window Y0,X0,H,W]: the picture as tiles of N x N.  The level is a tile's (--level, or the default of an
+    N x N picture); the bit budget of --bpp is shared equally among the tiles."""
+    c, h, w = picture.shape
+    if args.load or args.save or args.reduce or args.psnr is not None or args.rd_curve is not None:
+        raise SystemExit("--tile goes with --bpp, --level, the settings, --window and --out only")
+    p = plan(args, c, h, w)
+    level = default_level(args.tile, args.tile) if args.level is None else args.level
+    print("encoding %d x %d x %d at %.3f bpp as tiles of %d x %d" % (c, h, w, args.bpp, args.tile, args.tile))
+    enc, secs = timed(encode_image_tiled, picture, args.tile, p.settings, level, p.max_bits)
+    gy, gx = enc.grid()
+    print("encoded in %.3f s: %d x %d tiles, %.2f KiB" % (secs, gy, gx, len(enc.encoded_bytes) / 1024))
+    if args.window:
+        y0, x0, wh, ww = [int(v) for v in args.window.split(",")]
+        decoded, secs = timed(decode_image_window, enc, p.settings, y0, x0, wh, ww)
+        ref = picture[:, y0:y0 + wh, x0:x0 + ww]
+        print("decoded the window %d x %d at (%d, %d) in %.3f s" % (wh, ww, y0, x0, secs))
+    else:
+        decoded, secs = timed(decode_image_tiled, enc, p.settings)
+        ref = picture
+        print("decoded in %.3f s" % secs)
+    decoded = np.asarray(decoded)
+    print("  mean squared error %.5f" % float(((ref - decoded) ** 2).mean()))
+    imsave(args.out, decoded)
+    print("  picture written to", args.out)
+    return enc, decoded
+
+
 def main(args):
     picture = imload(args.image_filename)
+    if args.tile is not None:
+        return main_tiled(args, picture)
+    if args.window:
+        raise SystemExit("--window needs --tile")
     c, h, w = picture.shape
     p = plan(args, c, h, w)
     if args.load:

@@ -1,0 +1,466 @@
+"""Tiled pictures: one picture as a grid of equal tiles, one SPIHT stream per tile.
+
+A single decode is one workgroup walking one stream; the batched calls code one image per workgroup.  A tiled picture is a
+batch of tiles: the picture is cut into gy x gx tiles of th x tw on the device (edge tiles padded by replication, numpy's
+np.pad(mode="edge")), the tiles are coded by a BatchCodec(c, th, tw) in one batched call, and the T streams are packed into
+one run of bytes with a table of lengths.  Every tile stream is exactly what encode_image gives for that tile's pixels
+(TiledResult.tile(i, j) is an ordinary EncodingResult that the reference decodes).  Decoding is the way back -- unpack,
+one batched decode, paste -- and a window of the picture needs only the tiles it meets.
+
+The four copies (cut, paste, pack, unpack) are HIP kernels of the library (csrc/tiles.hip, include/spiht_hip.h:
+spiht_tile_*); nothing here touches a sample on the host.
+"""
+import ctypes as C
+import struct
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+
+from . import _lib
+from .batch import BatchCodec, DeviceArray
+from .spiht_wrapper import (ENCODER_DECODER_VERSION, EncodingResult, SpihtSettings, _check_aligned, _check_int_view,
+                            _check_version, _is_dtype)
+
+MAGIC = b"SPTL"
+CONTAINER_VERSION = 1
+_HEADER = struct.Struct("<4sBBHIIII")
+
+
+def _tile_arg(tile):
+    if isinstance(tile, (tuple, list)):
+        if len(tile) != 2:
+            raise ValueError("tile is an int or (th, tw)")
+        return int(tile[0]), int(tile[1])
+    return int(tile), int(tile)
+
+
+def tile_grid(H, W, th, tw):
+    """(gy, gx) = (ceil(H / th), ceil(W / tw)): the tiles of an H x W picture, row-major (spiht_tile_grid; no device).
+    ValueError for an empty picture or a tile side below 8."""
+    gy, gx = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().spiht_tile_grid(int(H), int(W), int(th), int(tw), C.byref(gy), C.byref(gx)))
+    return int(gy.value), int(gx.value)
+
+
+def window_tiles(H, W, th, tw, y0, x0, h, w):
+    """The sub-grid (i0, i1, j0, j1) of the tiles that meet the window [y0, y0 + h) x [x0, x0 + w): rows i0 <= i < i1,
+    columns j0 <= j < j1.  A window that is empty or leaves the H x W picture: ValueError."""
+    y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+    tile_grid(H, W, th, tw)
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+        raise ValueError("the window (%d, %d, %d, %d) is empty or leaves the %d x %d picture" % (y0, x0, h, w, H, W))
+    return y0 // th, (y0 + h - 1) // th + 1, x0 // tw, (x0 + w - 1) // tw + 1
+
+
+@dataclass
+class TiledResult:
+    """The streams of one tiled picture.  h, w, c: the PICTURE; th, tw: the tile; max_n, nbytes: one entry per tile,
+    row-major; encoded_bytes: the tiles' streams one behind the other."""
+    h: int
+    w: int
+    c: int
+    th: int
+    tw: int
+    level: Optional[int]
+    max_n: List[int]
+    nbytes: List[int]
+    encoded_bytes: bytes
+    _encoding_version: str = ENCODER_DECODER_VERSION
+
+    def grid(self):
+        return tile_grid(self.h, self.w, self.th, self.tw)
+
+    def _offsets(self):
+        return np.concatenate(([0], np.cumsum(np.asarray(self.nbytes, dtype=np.int64))))
+
+    def tile(self, i, j):
+        """Tile (i, j) as an ordinary EncodingResult with h = th, w = tw: what encode_image gives for the tile's pixels,
+        and a stream the reference itself decodes."""
+        gy, gx = self.grid()
+        if not (0 <= i < gy and 0 <= j < gx):
+            raise IndexError("tile (%d, %d) of a %d x %d grid" % (i, j, gy, gx))
+        t = i * gx + j
+        off = self._offsets()
+        return EncodingResult(self.encoded_bytes[int(off[t]):int(off[t + 1])], self.th, self.tw, self.c, int(self.max_n[t]),
+                              self.level, self._encoding_version)
+
+    def to_bytes(self):
+        """The container, little-endian: b"SPTL", u8 version = 1, u8 level (255 = None), u16 c, u32 H, W, th, tw, then
+        T x u32 nbytes, T x u8 max_n, then the packed streams."""
+        T = len(self.nbytes)
+        if len(self.max_n) != T or sum(self.nbytes) != len(self.encoded_bytes):
+            raise ValueError("the tables do not describe %d tiles of %d bytes" % (T, len(self.encoded_bytes)))
+        if self.level is not None and not 0 <= int(self.level) < 255:
+            raise ValueError("level %r does not fit the container" % (self.level,))
+        level = 255 if self.level is None else int(self.level)
+        return (_HEADER.pack(MAGIC, CONTAINER_VERSION, level, self.c, self.h, self.w, self.th, self.tw)
+                + np.asarray(self.nbytes, dtype="<u4").tobytes() + np.asarray(self.max_n, dtype=np.uint8).tobytes()
+                + bytes(self.encoded_bytes))
+
+    @staticmethod
+    def from_bytes(data):
+        """Inverse of to_bytes.  ValueError on a wrong magic or version, a short table, or a length sum that is not the
+        remaining byte count."""
+        data = bytes(data)
+        if len(data) < _HEADER.size:
+            raise ValueError("a tiled container has a %d-byte header; got %d bytes" % (_HEADER.size, len(data)))
+        magic, version, level, c, h, w, th, tw = _HEADER.unpack_from(data, 0)
+        if magic != MAGIC:
+            raise ValueError("not a tiled container: magic %r" % (magic,))
+        if version != CONTAINER_VERSION:
+            raise ValueError("tiled container version %d, this reader knows %d" % (version, CONTAINER_VERSION))
+        gy, gx = tile_grid(h, w, th, tw)
+        T = gy * gx
+        if len(data) < _HEADER.size + 5 * T:
+            raise ValueError("the tables of %d tiles need %d bytes; %d are left" % (T, 5 * T, len(data) - _HEADER.size))
+        nbytes = np.frombuffer(data, dtype="<u4", count=T, offset=_HEADER.size).astype(np.int64)
+        max_n = np.frombuffer(data, dtype=np.uint8, count=T, offset=_HEADER.size + 4 * T)
+        rest = len(data) - _HEADER.size - 5 * T
+        if int(nbytes.sum()) != rest:
+            raise ValueError("the table's lengths add up to %d bytes; %d follow it" % (int(nbytes.sum()), rest))
+        return TiledResult(h, w, c, th, tw, None if level == 255 else level, [int(v) for v in max_n], [int(v) for v in nbytes],
+                           data[_HEADER.size + 5 * T:])
+
+
+def _ptr(x):
+    """the device address of a DeviceArray, or the integer itself"""
+    return int(x.ptr) if hasattr(x, "ptr") else int(x)
+
+
+class TiledCodec:
+    """encode / decode pictures [c, H, W] as tiles of `tile` = th x tw (an int or (th, tw), sides >= 8).
+
+    settings / level / max_bits have the meaning of encode_image for EVERY TILE: level=None is the default level of a th x tw
+    picture, each tile's bit budget is max_bits // T (None stays None), and whatever encode_image refuses for a th x tw
+    picture is refused here, in the constructor.  The colour model change is per pixel and happens inside the tile codec.
+    pixel_dtype float32: the encoder runs PyWavelets' single-precision arithmetic, as encode_image does for float32 pixels."""
+
+    def __init__(self, c, H, W, tile, settings=None, level=None, max_bits=None, ctx=None, pixel_dtype=np.float64):
+        self.c, self.H, self.W = int(c), int(H), int(W)
+        self.th, self.tw = _tile_arg(tile)
+        self.gy, self.gx = tile_grid(self.H, self.W, self.th, self.tw)
+        self.T = self.gy * self.gx
+        self.settings = settings if settings is not None else SpihtSettings()
+        self.level = level
+        self.max_bits = max_bits
+        if self.settings.color_model not in (None, "RGB"):
+            pixel_dtype = np.float64  # as encode_image: colour pictures are coded in float64
+        self.codec = BatchCodec(self.c, self.th, self.tw, self.settings, level, None if max_bits is None else int(max_bits) // self.T,
+                                ctx, pixel_dtype)
+        self.ctx, self.L = self.codec.ctx, self.codec.L
+        self.pixel_dtype = self.codec.pixel_dtype
+        self.last_tiles_decoded = 0  # tiles the last decode call ran
+        self._bufs = {}
+
+    # ---- device scratch, grow-only per name ------------------------------------------------------
+    def _buf(self, name, nbytes):
+        b = self._bufs.get(name)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()
+            b = self._bufs[name] = DeviceArray(self.ctx, (int(nbytes) + int(nbytes) // 4 + 16,), np.uint8)
+        return b
+
+    def close(self):
+        for b in self._bufs.values():
+            b.free()
+        self._bufs = {}
+
+    def _strides_arg(self, shape, strides, output, dtype):
+        if strides is None:
+            return None, None
+        st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
+        _check_int_view(8 * np.dtype(dtype).itemsize, shape, st, output)
+        return st, C.c_void_p(st.ctypes.data)
+
+    # ---- device-resident forms ---------------------------------------------------------------------
+    def encode_device(self, d_img, N, d_packed, d_lens, d_max_n, strides=None):
+        """d_img: DeviceArray of N pictures [N, c, H, W] -- float64 (float32 for a float32 codec), or uint8 / uint16 laid out by
+        `strides` (bytes (sb, sc, sh, sw); None: dense CHW).  -> d_packed: the N * T streams one behind the other (uint8, at
+        least N * T * codec.slot_stride bytes always suffice; nothing is written past the array), d_lens: uint32 [N * T] their
+        lengths, d_max_n: uint8 [N * T].  Picture n's tiles are rows [n * T, (n + 1) * T).  One cut, one batched encode, one
+        pack, queued on the codec's context."""
+        N = int(N)
+        dt = np.dtype(d_img.dtype)
+        NT, vp = N * self.T, C.c_void_p
+        if N < 1:
+            raise ValueError("encode_device: no pictures")
+        d_tiles = self._buf("tiles", NT * self.c * self.th * self.tw * dt.itemsize)
+        geom = (N, self.c, self.H, self.W, self.th, self.tw)
+        if dt.kind == "u":
+            st, st_p = self._strides_arg((N, self.c, self.H, self.W), strides, False, dt)
+            _check_aligned(d_img.ptr, dt)
+            cut = self.L.spiht_tile_cut_u16 if dt.itemsize == 2 else self.L.spiht_tile_cut_u8
+            _lib.check(cut(self.ctx.handle, vp(d_img.ptr), st_p, *geom, vp(d_tiles.ptr)))
+        else:
+            if dt != self.pixel_dtype or strides is not None:
+                raise ValueError("encode_device: %s pictures, the codec's are dense %s" % (dt.name, self.pixel_dtype.name))
+            cut = self.L.spiht_tile_cut_f32 if dt.itemsize == 4 else self.L.spiht_tile_cut_f64
+            _lib.check(cut(self.ctx.handle, vp(d_img.ptr), *geom, vp(d_tiles.ptr)))
+        stride = self.codec.slot_stride
+        d_slots = self._buf("slots", NT * stride)
+        d_nbits = self._buf("nbits", NT * 8)
+        if dt.kind == "u":
+            enc = self.codec.encode_device_u16 if dt.itemsize == 2 else self.codec.encode_device_u8
+            enc(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
+        else:
+            self.codec.encode_device(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
+        _lib.check(self.L.spiht_tile_pack(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, vp(d_packed.ptr),
+                                          d_packed.nbytes, vp(d_lens.ptr)))
+
+    def decode_window_device(self, d_packed, packed_bytes, d_lens, d_max_n, sub, window, d_out, strides=None, slot_stride=None):
+        """d_packed / d_lens / d_max_n: the streams, lengths (uint32) and start planes (uint8) of the tiles of the sub-grid
+        sub = (i0, i1, j0, j1) in row-major order -- only those are unpacked and decoded.  window = (y0, x0, h, w) inside the
+        picture and inside the sub-grid.  -> d_out: DeviceArray [c, h, w], float64, or uint8 / uint16 laid out by `strides`
+        (bytes (sc, sh, sw); None: dense CHW; what lies between the view's samples is not written).  slot_stride: bytes per
+        stream slot the streams are unpacked into, a multiple of 4 no stream is longer than (None: the codec's bound).
+        One unpack, one batched decode, one paste, queued on the codec's context."""
+        i0, i1, j0, j1 = [int(v) for v in sub]
+        y0, x0, h, w = [int(v) for v in window]
+        need = window_tiles(self.H, self.W, self.th, self.tw, y0, x0, h, w)
+        if not (0 <= i0 <= need[0] and need[1] <= i1 <= self.gy and 0 <= j0 <= need[2] and need[3] <= j1 <= self.gx):
+            raise ValueError("the sub-grid %s does not hold the tiles %s of the window %s" % ((i0, i1, j0, j1), need, (y0, x0, h, w)))
+        n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
+        dt = np.dtype(d_out.dtype)
+        stride = self.codec.slot_stride if slot_stride is None else int(slot_stride)
+        d_slots = self._buf("slots", n * stride)
+        d_nbytes = self._buf("nbytes", n * 8)
+        _lib.check(self.L.spiht_tile_unpack(self.ctx.handle, vp(_ptr(d_packed)), int(packed_bytes), vp(_ptr(d_lens)), n,
+                                            vp(d_slots.ptr), stride, vp(d_nbytes.ptr)))
+        max_n = _ptr(d_max_n)
+        grid_args = (self.H, self.W, self.th, self.tw, i0, i1, j0, j1, y0, x0, h, w)
+        if dt.kind == "u":
+            st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
+            _check_aligned(d_out.ptr, dt)
+            d_dec = self._buf("dec", n * self.c * self.th * self.tw * dt.itemsize)
+            dec = self.codec.decode_device_u16 if dt.itemsize == 2 else self.codec.decode_device_u8
+            dec(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, slot_stride=stride)
+            paste = self.L.spiht_tile_paste_u16 if dt.itemsize == 2 else self.L.spiht_tile_paste_u8
+            _lib.check(paste(self.ctx.handle, vp(d_dec.ptr), self.c, self.th, self.tw, *grid_args, vp(d_out.ptr), st_p))
+        else:
+            if dt != np.float64 or strides is not None:
+                raise ValueError("decode: the float form gives dense float64 pictures")
+            rh, rw = self.codec.geom["rec_h"], self.codec.geom["rec_w"]
+            d_dec = self._buf("dec", n * self.c * rh * rw * 8)
+            self.codec.decode_device(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, slot_stride=stride)
+            _lib.check(self.L.spiht_tile_paste_f64(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *grid_args, vp(d_out.ptr)))
+        self.last_tiles_decoded = n
+
+    def decode_device(self, d_packed, packed_bytes, d_lens, d_max_n, d_out, strides=None, slot_stride=None):
+        """decode_window_device of the whole picture: all T tiles -> d_out [c, H, W]"""
+        self.decode_window_device(d_packed, packed_bytes, d_lens, d_max_n, (0, self.gy, 0, self.gx), (0, 0, self.H, self.W), d_out,
+                                  strides, slot_stride)
+
+    # ---- host forms ----------------------------------------------------------------------------------
+    def _encode_host(self, images, dtype, channels_last, name):
+        images = np.asarray(images)
+        single = images.ndim == 3
+        if single:
+            images = images[None]
+        if images.ndim != 4:
+            raise ValueError("%s takes a picture [c, H, W] or pictures [N, c, H, W]" % name)
+        dtype = np.dtype(dtype)
+        strides = None
+        if dtype.kind == "u":
+            if not _is_dtype(images, dtype):
+                raise ValueError("%s takes a %s array, not %s" % (name, dtype.name, images.dtype))
+            images = np.ascontiguousarray(images, dtype=dtype.newbyteorder("="))
+            if channels_last:
+                N, H, W, c = images.shape
+                es = dtype.itemsize
+                strides = (H * W * c * es, es, W * c * es, c * es)
+                shape = (N, c, H, W)
+            else:
+                shape = images.shape
+        else:
+            images = np.ascontiguousarray(images, dtype=dtype)
+            shape = images.shape
+        if tuple(shape[1:]) != (self.c, self.H, self.W):
+            raise ValueError("%s: pictures of shape %s, the codec's are %s" % (name, tuple(shape[1:]), (self.c, self.H, self.W)))
+        N, NT = shape[0], shape[0] * self.T
+        d_img = self._buf("img", images.nbytes)
+        d_img_view = _View(d_img.ptr, dtype)
+        self.ctx.upload(d_img.ptr, images)
+        d_packed = self._buf("packed", NT * self.codec.slot_stride)
+        d_lens = self._buf("lens", NT * 4)
+        d_maxn = self._buf("maxn", NT)
+        self.encode_device(d_img_view, N, d_packed, d_lens, d_maxn, strides)
+        self.ctx.synchronize()
+        lens = np.empty(NT, dtype=np.uint32)
+        maxn = np.empty(NT, dtype=np.uint8)
+        self.ctx.download(lens, d_lens.ptr)   # the table: one download
+        self.ctx.download(maxn, d_maxn.ptr)
+        total = int(lens.sum(dtype=np.int64))
+        run = np.empty(total, dtype=np.uint8)
+        if total:
+            self.ctx.download(run, d_packed.ptr)  # the streams of all pictures: one download
+        out, off = [], np.concatenate(([0], np.cumsum(lens, dtype=np.int64)))
+        for n in range(N):
+            a, b = n * self.T, (n + 1) * self.T
+            out.append(TiledResult(self.H, self.W, self.c, self.th, self.tw, self.level, [int(v) for v in maxn[a:b]],
+                                   [int(v) for v in lens[a:b]], run[int(off[a]):int(off[b])].tobytes()))
+        return out[0] if single else out
+
+    def encode(self, image_or_images):
+        """one float picture [c, H, W] -> TiledResult; N pictures [N, c, H, W] -> a list of them -- from one cut, one batched
+        encode of the N * T tiles and one pack; the packed bytes and the table come back in one download each"""
+        return self._encode_host(image_or_images, self.pixel_dtype, False, "encode")
+
+    def encode_u8(self, image_or_images, channels_last=False):
+        """uint8 pictures [c, H, W] / [N, c, H, W] (or [H, W, c] / [N, H, W, c] with channels_last) -> what encode gives for
+        pictures / 255.0"""
+        return self._encode_host(image_or_images, np.uint8, channels_last, "encode_u8")
+
+    def encode_u16(self, image_or_images, channels_last=False):
+        """uint16 pictures -> what encode gives for pictures / 65535.0"""
+        return self._encode_host(image_or_images, np.uint16, channels_last, "encode_u16")
+
+    def _check_result(self, r):
+        _check_version(r)
+        if (r.h, r.w, r.c, r.th, r.tw) != (self.H, self.W, self.c, self.th, self.tw):
+            raise ValueError("a result of geometry %s, the codec's is %s" % ((r.h, r.w, r.c, r.th, r.tw),
+                                                                            (self.H, self.W, self.c, self.th, self.tw)))
+        if len(r.nbytes) != self.T or len(r.max_n) != self.T or sum(r.nbytes) != len(r.encoded_bytes):
+            raise ValueError("the tables of the result do not describe %d tiles of %d bytes" % (self.T, len(r.encoded_bytes)))
+
+    def _decode_host(self, result, window, dtype, channels_last):
+        self._check_result(result)
+        y0, x0, h, w = [int(v) for v in window]
+        i0, i1, j0, j1 = sub = window_tiles(self.H, self.W, self.th, self.tw, y0, x0, h, w)
+        dtype = np.dtype(dtype)
+        # the streams of the sub-grid's tiles (a row of it is contiguous in the run), their lengths and start planes: one upload
+        off = result._offsets()
+        ts = [i * self.gx + j for i in range(i0, i1) for j in range(j0, j1)]
+        n = len(ts)
+        lens = np.asarray([result.nbytes[t] for t in ts], dtype=np.uint32)
+        nb = int(lens.sum(dtype=np.int64))
+        head = 4 * n + ((n + 3) & ~3)
+        blob = np.zeros(head + max(nb, 1), dtype=np.uint8)
+        blob[:4 * n] = lens.view(np.uint8)
+        blob[4 * n:5 * n] = np.asarray([result.max_n[t] for t in ts], dtype=np.uint8)
+        data = np.frombuffer(result.encoded_bytes, dtype=np.uint8)
+        p = head
+        for i in range(i0, i1):
+            a, b = int(off[i * self.gx + j0]), int(off[i * self.gx + j1])
+            blob[p:p + b - a] = data[a:b]
+            p += b - a
+        d_in = self._buf("in", blob.nbytes)
+        self.ctx.upload(d_in.ptr, blob)
+        es = dtype.itemsize
+        strides = (es, w * self.c * es, self.c * es) if channels_last else None
+        d_out = self._buf("out", self.c * h * w * es)
+        stride = max(4, (int(lens.max()) + 3) & ~3)
+        self.decode_window_device(d_in.ptr + head, nb, d_in.ptr, d_in.ptr + 4 * n, sub, (y0, x0, h, w), _View(d_out.ptr, dtype),
+                                  strides, stride)
+        self.ctx.synchronize()
+        out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w), dtype)
+        self.ctx.download(out, d_out.ptr)
+        return out
+
+    def decode(self, result):
+        """TiledResult -> float64 [c, H, W]: one upload, one unpack, one batched decode of all T tiles, one paste.  Unlike
+        decode_image, whose float64 picture is one longer on an odd axis (pywt.waverec2's size), the result is CROPPED to the
+        picture's H x W: a tile's extra row and column belong to no picture sample."""
+        return self._decode_host(result, (0, 0, self.H, self.W), np.float64, False)
+
+    def decode_u8(self, result, channels_last=False):
+        """-> uint8 [c, H, W] (or [H, W, c]): the rule of decode_image_u8 per tile"""
+        return self._decode_host(result, (0, 0, self.H, self.W), np.uint8, channels_last)
+
+    def decode_u16(self, result, channels_last=False):
+        """-> uint16 [c, H, W] (or [H, W, c])"""
+        return self._decode_host(result, (0, 0, self.H, self.W), np.uint16, channels_last)
+
+    def decode_window(self, result, y0, x0, h, w):
+        """-> float64 [c, h, w] = decode(result)[:, y0:y0 + h, x0:x0 + w]; only the tiles that meet the window are uploaded,
+        unpacked and decoded (last_tiles_decoded tells how many).  A window that leaves the picture: ValueError."""
+        return self._decode_host(result, (y0, x0, h, w), np.float64, False)
+
+    def decode_window_u8(self, result, y0, x0, h, w, channels_last=False):
+        """decode_window into uint8 [c, h, w] (or [h, w, c])"""
+        return self._decode_host(result, (y0, x0, h, w), np.uint8, channels_last)
+
+    def decode_window_u16(self, result, y0, x0, h, w, channels_last=False):
+        """decode_window into uint16 [c, h, w] (or [h, w, c])"""
+        return self._decode_host(result, (y0, x0, h, w), np.uint16, channels_last)
+
+
+class _View:
+    """a device address with an element type (what the device forms need of a DeviceArray), owning nothing"""
+
+    def __init__(self, ptr, dtype):
+        self.ptr, self.dtype = int(ptr), np.dtype(dtype)
+
+
+# ---- top-level conveniences, after the single-image calls -------------------------------------------------------------
+_codecs = {}
+
+
+def _codec_for(c, H, W, tile, settings, level, max_bits, pixel_dtype=np.float64):
+    """a TiledCodec per geometry and settings, kept (a few of them) so that repeated calls reuse its device buffers"""
+    th, tw = _tile_arg(tile)
+    key = (c, H, W, th, tw, repr(settings), level, max_bits, np.dtype(pixel_dtype).name, id(_lib.default_context()))
+    codec = _codecs.get(key)
+    if codec is None:
+        while len(_codecs) >= 4:
+            _codecs.pop(next(iter(_codecs))).close()
+        codec = _codecs[key] = TiledCodec(c, H, W, (th, tw), settings, level, max_bits, None, pixel_dtype)
+    return codec
+
+
+def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_last, name):
+    if not isinstance(image, np.ndarray) or image.ndim != 3:
+        raise ValueError('image ndim must be 3: c,h,w')
+    c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
+    if dtype is None:
+        dtype = np.float32 if image.dtype in (np.float32, np.float16) else np.float64
+    codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if np.dtype(dtype).kind == "f" else np.float64)
+    return codec._encode_host(image, codec.pixel_dtype if np.dtype(dtype).kind == "f" else dtype, channels_last, name)
+
+
+def encode_image_tiled(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None):
+    """encode_image of a picture (c, h, w) as tiles of `tile` (an int or (th, tw)) -> TiledResult.  level and max_bits are
+    per tile as in TiledCodec: every tile gets max_bits // T bits; float32 pixels run the single-precision transform."""
+    return _encode_tiled(image, tile, spiht_settings, level, max_bits, None, False, "encode_image_tiled")
+
+
+def encode_image_tiled_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False):
+    """uint8 pixels: the TiledResult of encode_image_tiled(image / 255.0, ...)"""
+    return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint8, channels_last, "encode_image_tiled_u8")
+
+
+def encode_image_tiled_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False):
+    """uint16 pixels: the TiledResult of encode_image_tiled(image / 65535.0, ...)"""
+    return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint16, channels_last, "encode_image_tiled_u16")
+
+
+def _decode_tiled(result, spiht_settings, window, dtype, channels_last):
+    codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None)
+    return codec._decode_host(result, (0, 0, result.h, result.w) if window is None else window, dtype, channels_last)
+
+
+def decode_image_tiled(result, spiht_settings):
+    """TiledResult -> float64 (c, h, w), cropped to the picture's size (see TiledCodec.decode)"""
+    return _decode_tiled(result, spiht_settings, None, np.float64, False)
+
+
+def decode_image_tiled_u8(result, spiht_settings, channels_last=False):
+    return _decode_tiled(result, spiht_settings, None, np.uint8, channels_last)
+
+
+def decode_image_tiled_u16(result, spiht_settings, channels_last=False):
+    return _decode_tiled(result, spiht_settings, None, np.uint16, channels_last)
+
+
+def decode_image_window(result, spiht_settings, y0, x0, h, w):
+    """the window [y0, y0 + h) x [x0, x0 + w) of the picture -> float64 (c, h, w), decoding only the tiles it meets"""
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.float64, False)
+
+
+def decode_image_window_u8(result, spiht_settings, y0, x0, h, w, channels_last=False):
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint8, channels_last)
+
+
+def decode_image_window_u16(result, spiht_settings, y0, x0, h, w, channels_last=False):
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint16, channels_last)
