@@ -627,6 +627,39 @@ int spiht_tile_unpack(spiht_ctx *ctx, const uint8_t *d_packed, uint64_t packed_b
                       uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes);
 
 /* ---------------------------------------------------------------------------------------
+ * Rate allocation across the tiles of a picture (csrc/alloc.hip; the rule is spiht_amd/alloc.py).  The tiles are coded past
+ * their share of the budget; K prefixes of every tile's stream are decoded and measured; every tile is cut where one more
+ * byte buys the same drop in distortion, and spiht_tile_pack takes the cut lengths.  Additions only: the ABI version stays
+ * at 2.  All pointers are DEVICE pointers; asynchronous on the context's stream; argument errors are returned before anything
+ * is queued; no byte outside the stated outputs is written.  1 <= K <= 255, N * T < 2^31, strides multiples of 4 below 2^29.
+ *   spiht_tile_prefix_slots  the NT slots a batched encode left (slot_stride, d_nbits) -> G * NT slots of out_stride bytes for
+ *                      the candidates k0 .. k0 + G - 1 (k0 + G <= K + 1): slot (k - k0) * NT + t holds the first
+ *                      R_t[k] = ceil(n_t k / K) bytes of slot t, n_t = ceil(nbits[t] / 8), and zeros behind them;
+ *                      d_nbytes uint64 [G * NT]: those lengths.  d_max_n [NT] -> d_max_n_out [G * NT], the start planes
+ *                      repeated for the batched decode (both NULL: not wanted).  d_slots and d_out 4-byte aligned.
+ *   spiht_sse_tiles_*  d_tiles [N * T, c, th, tw], the cut tiles (spiht_tile_cut_*); d_dec [G, N * T, c, rh, rw] of the same
+ *                      element type, rh >= th, rw >= tw -> d_out [G][N * T]: the sum over all channels of the squared error
+ *                      over the tile's VALID extent, its first min(th, H - i th) rows and min(tw, W - j tw) columns; rows and
+ *                      columns past it are never read.  _f64: double; every term (p - d) * (p - d) rounded, then added, in an
+ *                      order fixed by (c, th, tw) and the extent alone: the same bits for any G and grouping.  _u8 / _u16:
+ *                      uint64, exact (c th tw < 2^32).  1 <= G <= 65535, c <= 65535, th tw < 2^30, G * N * T < 2^31.
+ *   spiht_tile_allocate  d_nbits [N * T] (the full streams), d_D [K + 1][N * T] (kind 0: float64, 1: uint64, converted with one
+ *                      rounding), budget_bytes for each picture -> d_nbits_out uint64 [N * T] = 8 * the bytes alloc.allocate
+ *                      gives, d_lambda double [N] (may be NULL) = its lambda*.  One workgroup per picture; the hulls live in
+ *                      a grow-only buffer of the context. */
+int spiht_tile_prefix_slots(spiht_ctx *ctx, const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbits, int64_t NT,
+                            int64_t K, int64_t k0, int64_t G, uint8_t *d_out, uint64_t out_stride, uint64_t *d_nbytes,
+                            const uint8_t *d_max_n, uint8_t *d_max_n_out);
+int spiht_sse_tiles_f64(spiht_ctx *ctx, const double *d_tiles, const double *d_dec, int64_t G, int64_t N, int64_t c, int64_t H,
+                        int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, double *d_out);
+int spiht_sse_tiles_u8(spiht_ctx *ctx, const uint8_t *d_tiles, const uint8_t *d_dec, int64_t G, int64_t N, int64_t c, int64_t H,
+                       int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out);
+int spiht_sse_tiles_u16(spiht_ctx *ctx, const uint16_t *d_tiles, const uint16_t *d_dec, int64_t G, int64_t N, int64_t c, int64_t H,
+                        int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out);
+int spiht_tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D, int kind, int64_t K, int64_t N, int64_t T,
+                        uint64_t budget_bytes, uint64_t *d_nbits_out, double *d_lambda);
+
+/* ---------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, every rank codes its own images (the reference's encode / decode
  * are pure functions of one image, src/lib.rs:24-42 -- nothing is exchanged while coding); the ONE exchange of the
  * path is the gather of the finished streams.  It runs on RCCL (ncclAllGather over xGMI), inside this library, on

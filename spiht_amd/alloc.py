@@ -1,0 +1,126 @@
+"""Rate allocation across the tiles of a picture: the rule, in Python and numpy, with no device.
+
+Every tile of a tiled picture is an embedded stream, so any byte prefix of it is a stream.  A tile coded past its share of
+the budget and measured at K prefixes has a rate-distortion curve; cutting every tile where one more byte buys the same
+drop in distortion (equal slope on the lower convex hull of the curves) spends a fixed total where it helps most.  This
+module is the statement the kernel spiht_tile_allocate (csrc/alloc.hip) is held to, bit for bit: every slope is one rounded
+float64 subtraction and one rounded float64 division, and nothing else here rounds.
+"""
+import math
+
+import numpy as np
+
+SPREAD = 4.0
+POINTS = 16
+MAX_POINTS = 255
+
+
+def points_arg(points):
+    if isinstance(points, bool) or not isinstance(points, (int, np.integer)):
+        raise TypeError("points must be an integer, not %s" % type(points).__name__)
+    if not 1 <= points <= MAX_POINTS:
+        raise ValueError("points = %d: 1 .. %d lengths per tile" % (points, MAX_POINTS))
+    return int(points)
+
+
+def spread_arg(spread):
+    if isinstance(spread, bool) or not isinstance(spread, (int, float, np.integer, np.floating)):
+        raise TypeError("spread must be a number, not %s" % type(spread).__name__)
+    spread = float(spread)
+    if not spread >= 1.0 or math.isinf(spread):
+        raise ValueError("spread = %r: a finite factor >= 1" % spread)
+    return spread
+
+
+def allocate_arg(allocate):
+    if allocate not in (None, "rd"):
+        raise ValueError('allocate is None or "rd", not %r' % (allocate,))
+    return allocate
+
+
+def ceiling_bits(max_bits, T, spread=SPREAD):
+    """the bit budget every tile is coded with before the cut: min(max_bits, floor(spread * (max_bits // T))), rounded down
+    to whole bytes -- so a full stream either ends by itself or has exactly that many bits, and every prefix of L >= 1 bytes
+    is encode_image(tile, max_bits=8 L)"""
+    max_bits, T = int(max_bits), int(T)
+    if max_bits < 0 or T < 1:
+        raise ValueError("ceiling_bits: max_bits >= 0 and T >= 1")
+    return min(max_bits, math.floor(spread_arg(spread) * (max_bits // T))) // 8 * 8
+
+
+def tile_lengths(n, K):
+    """the K + 1 candidate byte lengths of a stream of n bytes: R[k] = ceil(n k / K); R[0] = 0, R[K] = n"""
+    n, K = int(n), points_arg(K)
+    return [-(-n * k // K) for k in range(K + 1)]
+
+
+def _f64(D):
+    """float64 with one rounding: exact integer sums (Python ints, uint64) round once, floats are taken as they are"""
+    return [float(int(v)) if isinstance(v, (int, np.integer)) else float(v) for v in D]
+
+
+def slope(R, D, a, b):
+    """(D[a] - D[b]) / float64(R[b] - R[a]): distortion dropped per byte from a to b; one rounded subtraction, one rounded
+    division"""
+    return float((np.float64(D[a]) - np.float64(D[b])) / np.float64(int(R[b]) - int(R[a])))
+
+
+def lower_hull(R, D):
+    """indices of the lower convex hull of the points (R[k], D[k]), k = 0 .. K, from k = 0; R non-decreasing.  A point no
+    longer than the top, or not strictly better, is skipped (curves need not be monotone); the edges' slopes are strictly
+    decreasing."""
+    D = _f64(D)
+    s = [0]
+    for k in range(1, len(R)):
+        if R[k] == R[s[-1]] or not D[k] < D[s[-1]]:
+            continue
+        while len(s) >= 2 and slope(R, D, s[-2], s[-1]) <= slope(R, D, s[-1], k):
+            s.pop()
+        s.append(k)
+    return s
+
+
+def hull_edges(R, D):
+    """the hull edges of all tiles, tile by tile: (slope, delta R, R of the end vertex, tile)"""
+    edges = []
+    for t in range(len(R)):
+        Dt = _f64(D[t])
+        h = lower_hull(R[t], Dt)
+        for a, b in zip(h, h[1:]):
+            edges.append((slope(R[t], Dt, a, b), int(R[t][b]) - int(R[t][a]), int(R[t][b]), t))
+    return edges
+
+
+def allocate(R, D, budget_bytes):
+    """R, D: [T][K + 1] candidate lengths and their distortions; budget_bytes: the bytes of all tiles together.
+    -> (bytes per tile, lambda*).  lambda* is the smallest edge slope whose edges and all steeper ones fit the budget (inf if
+    none does): every tile goes to the last vertex it reaches over edges of slope >= lambda*.  What is left of the budget goes
+    to the edges of the next slope below, min(delta R, rest) each in tile order -- a partial edge is a valid prefix.  The sum
+    is min(budget_bytes, the tiles' last hull vertices together)."""
+    budget = int(budget_bytes)
+    if budget < 0:
+        raise ValueError("budget_bytes = %d is negative" % budget)
+    edges = hull_edges(R, D)
+    lam, cost = math.inf, 0
+    by_slope = {}
+    for s, dr, _, _ in edges:
+        by_slope[s] = by_slope.get(s, 0) + dr
+    for s in sorted(by_slope, reverse=True):  # cost(s) grows as s falls: the last slope that still fits
+        cost += by_slope[s]
+        if cost > budget:
+            break
+        lam = s
+    out = [0] * len(R)
+    for s, _, end, t in edges:
+        if s >= lam:
+            out[t] = max(out[t], end)
+    rest = budget - sum(out)
+    below = [e[0] for e in edges if e[0] < lam]
+    if below:
+        nxt = max(below)
+        for s, dr, _, t in edges:  # at most one edge of a slope per tile, the tiles ascending
+            if s == nxt and rest > 0:
+                give = min(dr, rest)
+                out[t] += give
+                rest -= give
+    return out, lam

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "alloc.h"
 #include "common.h"
 #include "rd.h"
 #include "tiles.h"
@@ -65,6 +66,12 @@ int spiht_launch_tile_pack(const uint8_t *d_slots, uint64_t slot_stride, const u
                            uint8_t *d_packed, uint64_t cap, uint32_t *d_lens, hipStream_t st);
 int spiht_launch_tile_unpack(const uint8_t *d_packed, uint64_t packed_bytes, const uint32_t *d_lens, int64_t T, uint64_t *d_off,
                              uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes, hipStream_t st);
+int spiht_launch_tile_prefix_slots(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbits, int64_t NT, int K, int k0,
+                                   int G, uint8_t *d_out, uint64_t out_stride, uint64_t *d_nbytes, const uint8_t *d_max_n,
+                                   uint8_t *d_max_n_out, hipStream_t st);
+int spiht_launch_sse_tiles(const TileSseArgs *a, int es, int64_t G, hipStream_t st);
+int spiht_launch_tile_allocate(const uint64_t *d_nbits, const void *d_D, int kind, int K, int64_t N, int64_t T, uint64_t budget,
+                               void *scratch, uint64_t *d_nbits_out, double *d_lambda, hipStream_t st);
 }
 
 static thread_local std::string g_hip_err;
@@ -143,6 +150,7 @@ struct spiht_ctx {
     DevBuf recz, lspcnt;
     DevBuf rdpart;              // per-workgroup partial sums of the rate-distortion reductions (rd.hip)
     DevBuf tilescr;             // tiled pictures (tiles.hip): byte lengths and offsets of the streams pack / unpack move
+    DevBuf allocscr;            // rate allocation across tiles (alloc.hip): the tiles' hulls
     bool recz_clean = false;
     // spiht_decode_lists_batch_i32 -> spiht_unscatter_lists_batch_i32: the launch whose scatter can still be undone
     DecArgs last_dec;
@@ -487,7 +495,7 @@ extern "C" void spiht_ctx_destroy(spiht_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->widebuf, &ctx->filt, &ctx->exttmp, &ctx->l1flags, &ctx->x, &ctx->dmsb, &ctx->lmsb, &ctx->maxabs, &ctx->out, &ctx->nbits, &ctx->maxn, &ctx->err,
                       &ctx->lists, &ctx->coeffs, &ctx->a0, &ctx->a1, &ctx->data, &ctx->nbytes, &ctx->rec, &ctx->mults,
                       &ctx->img, &ctx->trace, &ctx->meta, &ctx->recz, &ctx->lspcnt, &ctx->himg, &ctx->hrec, &ctx->tilebuf,
-                      &ctx->pix, &ctx->hpix8, &ctx->rdpart, &ctx->tilescr};
+                      &ctx->pix, &ctx->hpix8, &ctx->rdpart, &ctx->tilescr, &ctx->allocscr};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &r : ctx->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -2498,6 +2506,75 @@ extern "C" int spiht_tile_unpack(spiht_ctx *ctx, const uint8_t *d_packed, uint64
     CHK(ensure(ctx, ctx->tilescr, (size_t)T * 16));
     LAUNCHCHK(spiht_launch_tile_unpack(d_packed, packed_bytes, d_lens, T, (uint64_t *)ctx->tilescr.p + T, d_slots, slot_stride,
                                        d_nbytes, ctx->stream));
+    return SPIHT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// rate allocation across tiles (alloc.hip): prefixes of every tile's stream, their error sums, the cut of equal slope
+// ------------------------------------------------------------------------------------------------
+extern "C" int spiht_tile_prefix_slots(spiht_ctx *ctx, const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbits,
+                                       int64_t NT, int64_t K, int64_t k0, int64_t G, uint8_t *d_out, uint64_t out_stride,
+                                       uint64_t *d_nbytes, const uint8_t *d_max_n, uint8_t *d_max_n_out) {
+    CHK(tile_streams_args(ctx, d_slots, d_nbits, d_out, d_nbytes, slot_stride, NT));
+    if (out_stride == 0 || out_stride % 4 || (uintptr_t)d_slots % 4 || (uintptr_t)d_out % 4 || (uintptr_t)d_nbits % 8 ||
+        (uintptr_t)d_nbytes % 8)
+        return SPIHT_ERR_ARG;
+    if (K < 1 || K > 255 || k0 < 0 || G < 1 || k0 + G > K + 1 || !d_max_n != !d_max_n_out) return SPIHT_ERR_ARG;
+    if (out_stride > ((uint64_t)1 << 29) || G * NT > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    if (NT == 0) return SPIHT_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    LAUNCHCHK(spiht_launch_tile_prefix_slots(d_slots, slot_stride, d_nbits, NT, (int)K, (int)k0, (int)G, d_out, out_stride, d_nbytes,
+                                             d_max_n, d_max_n_out, ctx->stream));
+    return SPIHT_OK;
+}
+// es: bytes per sample (8: float64).  d_tiles [N * T, c, th, tw], d_dec [G, N * T, c, rh, rw] -> d_out [G][N * T]
+static int sse_tiles(int es, spiht_ctx *ctx, const void *d_tiles, const void *d_dec, int64_t G, int64_t N, int64_t c, int64_t H,
+                     int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, void *d_out) {
+    if (!ctx || !d_tiles || !d_dec || !d_out || G < 1 || G > 65535 || N < 1 || c < 1) return SPIHT_ERR_ARG;
+    if ((uintptr_t)d_tiles % es || (uintptr_t)d_dec % es || (uintptr_t)d_out % 8) return SPIHT_ERR_ARG;
+    int64_t gy, gx;
+    CHK(spiht_tile_grid(H, W, th, tw, &gy, &gx));
+    if (rh < th || rw < tw) return SPIHT_ERR_ARG;
+    if (c > 65535 || th * tw >= (1 << 30) || rh >= (1 << 30) || rw >= (1 << 30) || al_chunks(th) > 65535) return SPIHT_ERR_TOO_LARGE;
+    if (es != 8 && (__int128)c * th * tw >= ((__int128)1 << 32)) return SPIHT_ERR_TOO_LARGE;  // the exact 64-bit sum of a tile
+    if ((__int128)G * N * gy * gx > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    TileSseArgs a;
+    a.tiles = d_tiles; a.dec = d_dec; a.out = d_out;
+    a.c = (int32_t)c; a.H = (int32_t)H; a.W = (int32_t)W; a.th = (int32_t)th; a.tw = (int32_t)tw; a.rh = (int32_t)rh;
+    a.rw = (int32_t)rw; a.gx = (int32_t)gx;
+    a.T = (uint32_t)(gy * gx); a.NT = (uint32_t)(N * gy * gx); a.chunks = al_chunks(th);
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->rdpart, (size_t)G * a.NT * c * a.chunks * 8));
+    a.part = ctx->rdpart.p;
+    LAUNCHCHK(spiht_launch_sse_tiles(&a, es, G, ctx->stream));
+    return SPIHT_OK;
+}
+extern "C" int spiht_sse_tiles_f64(spiht_ctx *ctx, const double *d_tiles, const double *d_dec, int64_t G, int64_t N, int64_t c,
+                                   int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, double *d_out) {
+    return sse_tiles(8, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out);
+}
+extern "C" int spiht_sse_tiles_u8(spiht_ctx *ctx, const uint8_t *d_tiles, const uint8_t *d_dec, int64_t G, int64_t N, int64_t c,
+                                  int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out) {
+    return sse_tiles(1, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out);
+}
+extern "C" int spiht_sse_tiles_u16(spiht_ctx *ctx, const uint16_t *d_tiles, const uint16_t *d_dec, int64_t G, int64_t N, int64_t c,
+                                   int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out) {
+    return sse_tiles(2, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out);
+}
+extern "C" int spiht_tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D, int kind, int64_t K, int64_t N,
+                                   int64_t T, uint64_t budget_bytes, uint64_t *d_nbits_out, double *d_lambda) {
+    if (!ctx || !d_nbits || !d_D || !d_nbits_out || (kind != 0 && kind != 1) || K < 1 || K > 255 || N < 0 || T < 1)
+        return SPIHT_ERR_ARG;
+    if ((uintptr_t)d_nbits % 8 || (uintptr_t)d_D % 8 || (uintptr_t)d_nbits_out % 8 || (uintptr_t)d_lambda % 8) return SPIHT_ERR_ARG;
+    if ((__int128)N * T > 0x7FFFFFFF || budget_bytes > ((uint64_t)1 << 60)) return SPIHT_ERR_TOO_LARGE;
+    if (N == 0) return SPIHT_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->allocscr, al_scratch_bytes((uint64_t)N * T, (uint64_t)K)));
+    LAUNCHCHK(spiht_launch_tile_allocate(d_nbits, d_D, kind, (int)K, N, T, budget_bytes, ctx->allocscr.p, d_nbits_out, d_lambda,
+                                         ctx->stream));
     return SPIHT_OK;
 }
 

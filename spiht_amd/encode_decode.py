@@ -35,6 +35,8 @@ _ARGS = [  # (flag, type, default, help): the reference tool's options, then our
     ("--rd-curve", int, None, "print N rows of the stream's rate-distortion curve: bytes, bpp, PSNR"),
     ("--tile", int, None, "code the picture as tiles of N x N, one stream per tile (the bit budget is shared equally)"),
     ("--window", str, None, "with --tile: decode only the window Y0,X0,H,W of the picture and save that"),
+    ("--allocate", str, None, "with --tile: 'rd' shares the bit budget between the tiles by their rate-distortion curves"),
+    ("--points", int, 16, "with --allocate rd: prefixes measured per tile"),
 ]
 
 
@@ -86,14 +88,15 @@ def report_encoding(enc: EncodingResult, settings: SpihtSettings, seconds: Optio
 
 def main_tiled(args, picture):
     """--tile N [--window Y0,X0,H,W]: the picture as tiles of N x N.  The level is a tile's (--level, or the default of an
-    N x N picture); the bit budget of --bpp is shared equally among the tiles."""
+    N x N picture); the bit budget of --bpp is shared equally among the tiles, or with --allocate rd [--points K] by their
+    rate-distortion curves."""
     c, h, w = picture.shape
     if args.load or args.save or args.reduce or args.psnr is not None or args.rd_curve is not None:
         raise SystemExit("--tile goes with --bpp, --level, the settings, --window and --out only")
     p = plan(args, c, h, w)
     level = default_level(args.tile, args.tile) if args.level is None else args.level
     print("encoding %d x %d x %d at %.3f bpp as tiles of %d x %d" % (c, h, w, args.bpp, args.tile, args.tile))
-    enc, secs = timed(encode_image_tiled, picture, args.tile, p.settings, level, p.max_bits)
+    enc, secs = timed(encode_image_tiled, picture, args.tile, p.settings, level, p.max_bits, args.allocate, args.points)
     gy, gx = enc.grid()
     print("encoded in %.3f s: %d x %d tiles, %.2f KiB" % (secs, gy, gx, len(enc.encoded_bytes) / 1024))
     if args.window:
@@ -116,8 +119,8 @@ def main(args):
     picture = imload(args.image_filename)
     if args.tile is not None:
         return main_tiled(args, picture)
-    if args.window:
-        raise SystemExit("--window needs --tile")
+    if args.window or args.allocate:
+        raise SystemExit("--window and --allocate need --tile")
     c, h, w = picture.shape
     p = plan(args, c, h, w)
     if args.load:

@@ -9,6 +9,11 @@ one batched decode, paste -- and a window of the picture needs only the tiles it
 
 The four copies (cut, paste, pack, unpack) are HIP kernels of the library (csrc/tiles.hip, include/spiht_hip.h:
 spiht_tile_*); nothing here touches a sample on the host.
+
+allocate="rd" shares the bit budget between the tiles by their rate-distortion curves instead of equally: every tile is coded
+past its share, K prefixes of every tile are decoded and measured on the device, and every tile is cut where one more byte
+buys the same drop in distortion (alloc.py is the rule, csrc/alloc.hip the kernels).  The container and every decoder are
+unchanged: a tile's stream is still encode_image of the tile's pixels, at max_bits = 8 * its length.
 """
 import ctypes as C
 import struct
@@ -17,7 +22,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, alloc
 from .batch import BatchCodec, DeviceArray
 from .spiht_wrapper import (ENCODER_DECODER_VERSION, EncodingResult, SpihtSettings, _check_aligned, _check_int_view,
                             _check_version, _is_dtype)
@@ -123,6 +128,37 @@ class TiledResult:
                            data[_HEADER.size + 5 * T:])
 
 
+@dataclass
+class TileCurves:
+    """What allocate="rd" measured of one picture, one row per tile: lengths [T][K + 1] -- the candidate byte lengths
+    alloc.tile_lengths(nbytes[t], K); sse [T][K + 1] -- the squared error of the tile's valid region at each, summed over the
+    channels: float64, or uint64 (exact) for 8- / 16-bit pixels; nbytes [T] -- the full streams; max_n [T] -- start planes."""
+    lengths: List[List[int]]
+    sse: np.ndarray
+    nbytes: List[int]
+    max_n: List[int]
+
+
+@dataclass
+class TileAllocation:
+    """the cut of one picture: lam -- lambda*, the drop in squared error per byte every tile was cut at (inf: the budget lies
+    below every tile's first hull edge); nbytes -- the bytes per tile"""
+    lam: float
+    nbytes: List[int]
+
+
+def _alloc_args(allocate, points, spread, max_bits, pixel_dtype):
+    """the host checks of the three keywords, before a context is asked for"""
+    alloc.allocate_arg(allocate)
+    points, spread = alloc.points_arg(points), alloc.spread_arg(spread)
+    if allocate is not None:
+        if max_bits is None:
+            raise ValueError('allocate="rd" shares a budget: max_bits is required')
+        if np.dtype(pixel_dtype) in (np.float32, np.float16):
+            raise ValueError('allocate="rd" takes the pictures of a float64 codec')
+    return points, spread
+
+
 def _ptr(x):
     """the device address of a DeviceArray, or the integer itself"""
     return int(x.ptr) if hasattr(x, "ptr") else int(x)
@@ -134,23 +170,36 @@ class TiledCodec:
     settings / level / max_bits have the meaning of encode_image for EVERY TILE: level=None is the default level of a th x tw
     picture, each tile's bit budget is max_bits // T (None stays None), and whatever encode_image refuses for a th x tw
     picture is refused here, in the constructor.  The colour model change is per pixel and happens inside the tile codec.
-    pixel_dtype float32: the encoder runs PyWavelets' single-precision arithmetic, as encode_image does for float32 pixels."""
+    pixel_dtype float32: the encoder runs PyWavelets' single-precision arithmetic, as encode_image does for float32 pixels.
 
-    def __init__(self, c, H, W, tile, settings=None, level=None, max_bits=None, ctx=None, pixel_dtype=np.float64):
+    allocate="rd" (max_bits required; not for a float32 codec): the tiles share max_bits by their rate-distortion curves.
+    Every tile is coded with the ceiling alloc.ceiling_bits(max_bits, T, spread), measured at `points` prefixes and cut at
+    equal slope (alloc.allocate); the lengths add up to max_bits // 8 whenever the tiles' hulls can take that much.
+    max_bytes (an attribute) bounds the device memory of the prefixes decoded at a time; results do not depend on it."""
+
+    def __init__(self, c, H, W, tile, settings=None, level=None, max_bits=None, ctx=None, pixel_dtype=np.float64, allocate=None,
+                 points=alloc.POINTS, spread=alloc.SPREAD):
+        self.settings = settings if settings is not None else SpihtSettings()
+        if self.settings.color_model not in (None, "RGB"):
+            pixel_dtype = np.float64  # as encode_image: colour pictures are coded in float64
+        self.points, self.spread = _alloc_args(allocate, points, spread, max_bits, pixel_dtype)
+        self.allocate = allocate
         self.c, self.H, self.W = int(c), int(H), int(W)
         self.th, self.tw = _tile_arg(tile)
         self.gy, self.gx = tile_grid(self.H, self.W, self.th, self.tw)
         self.T = self.gy * self.gx
-        self.settings = settings if settings is not None else SpihtSettings()
         self.level = level
         self.max_bits = max_bits
-        if self.settings.color_model not in (None, "RGB"):
-            pixel_dtype = np.float64  # as encode_image: colour pictures are coded in float64
-        self.codec = BatchCodec(self.c, self.th, self.tw, self.settings, level, None if max_bits is None else int(max_bits) // self.T,
-                                ctx, pixel_dtype)
+        if allocate is not None:
+            tile_bits = alloc.ceiling_bits(max_bits, self.T, self.spread)
+        else:
+            tile_bits = None if max_bits is None else int(max_bits) // self.T
+        self.codec = BatchCodec(self.c, self.th, self.tw, self.settings, level, tile_bits, ctx, pixel_dtype)
         self.ctx, self.L = self.codec.ctx, self.codec.L
         self.pixel_dtype = self.codec.pixel_dtype
         self.last_tiles_decoded = 0  # tiles the last decode call ran
+        self.last_allocation = None  # allocate="rd": the TileAllocation of the last host encode (a list for several pictures)
+        self.max_bytes = 2 ** 31     # allocate="rd": device bytes of the prefixes decoded at a time
         self._bufs = {}
 
     # ---- device scratch, grow-only per name ------------------------------------------------------
@@ -180,7 +229,9 @@ class TiledCodec:
         `strides` (bytes (sb, sc, sh, sw); None: dense CHW).  -> d_packed: the N * T streams one behind the other (uint8, at
         least N * T * codec.slot_stride bytes always suffice; nothing is written past the array), d_lens: uint32 [N * T] their
         lengths, d_max_n: uint8 [N * T].  Picture n's tiles are rows [n * T, (n + 1) * T).  One cut, one batched encode, one
-        pack, queued on the codec's context."""
+        pack, queued on the codec's context.  allocate="rd": between the encode and the pack, per group of candidate lengths,
+        the prefix slots, one batched decode of them and the per-tile error sums; then one spiht_tile_allocate, whose lengths
+        the pack takes.  No host wait anywhere."""
         N = int(N)
         dt = np.dtype(d_img.dtype)
         NT, vp = N * self.T, C.c_void_p
@@ -206,8 +257,41 @@ class TiledCodec:
             enc(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
         else:
             self.codec.encode_device(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
+        if self.allocate is not None:
+            d_nbits = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n)
         _lib.check(self.L.spiht_tile_pack(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, vp(d_packed.ptr),
                                           d_packed.nbytes, vp(d_lens.ptr)))
+
+    def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n):
+        """the NT full streams in d_slots -> the buffer of the cut lengths in bits (uint64 [NT]); the table of distortions
+        stays in the buffer "D" ([K + 1][NT]) and lambda* in "lambda" ([N]) for the host forms"""
+        NT, K, vp, c = N * self.T, self.points, C.c_void_p, self.c
+        stride = self.codec.slot_stride
+        integer = dt.kind == "u"
+        rh, rw = (self.th, self.tw) if integer else (self.codec.geom["rec_h"], self.codec.geom["rec_w"])
+        G = max(1, min(K + 1, int(self.max_bytes) // (NT * (stride + c * rh * rw * dt.itemsize + 9))))
+        d_pre = self._buf("pre", G * NT * stride)
+        d_prebytes = self._buf("prebytes", G * NT * 8)
+        d_premaxn = self._buf("premaxn", G * NT)
+        d_dec = self._buf("dec", G * NT * c * rh * rw * dt.itemsize)
+        d_D = self._buf("D", (K + 1) * NT * 8)
+        d_cut = self._buf("cut", NT * 8)
+        d_lam = self._buf("lambda", N * 8)
+        if integer:
+            dec = self.codec.decode_device_u16 if dt.itemsize == 2 else self.codec.decode_device_u8
+            sse = self.L.spiht_sse_tiles_u16 if dt.itemsize == 2 else self.L.spiht_sse_tiles_u8
+        else:
+            dec, sse = self.codec.decode_device, self.L.spiht_sse_tiles_f64
+        for k0 in range(0, K + 1, G):
+            g = min(G, K + 1 - k0)
+            _lib.check(self.L.spiht_tile_prefix_slots(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, K, k0, g,
+                                                      vp(d_pre.ptr), stride, vp(d_prebytes.ptr), vp(d_max_n.ptr), vp(d_premaxn.ptr)))
+            dec(d_pre.ptr, d_prebytes.ptr, d_premaxn.ptr, g * NT, d_dec.ptr, slot_stride=stride)
+            _lib.check(sse(self.ctx.handle, vp(d_tiles.ptr), vp(d_dec.ptr), g, N, c, self.H, self.W, self.th, self.tw, rh, rw,
+                           vp(d_D.ptr + 8 * k0 * NT)))
+        _lib.check(self.L.spiht_tile_allocate(self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if integer else 0, K, N, self.T,
+                                              int(self.max_bits) // 8, vp(d_cut.ptr), vp(d_lam.ptr)))
+        return d_cut
 
     def decode_window_device(self, d_packed, packed_bytes, d_lens, d_max_n, sub, window, d_out, strides=None, slot_stride=None):
         """d_packed / d_lens / d_max_n: the streams, lengths (uint32) and start planes (uint8) of the tiles of the sub-grid
@@ -215,7 +299,10 @@ class TiledCodec:
         picture and inside the sub-grid.  -> d_out: DeviceArray [c, h, w], float64, or uint8 / uint16 laid out by `strides`
         (bytes (sc, sh, sw); None: dense CHW; what lies between the view's samples is not written).  slot_stride: bytes per
         stream slot the streams are unpacked into, a multiple of 4 no stream is longer than (None: the codec's bound).
-        One unpack, one batched decode, one paste, queued on the codec's context."""
+        One unpack, one batched decode, one paste, queued on the codec's context.
+        Streams of an allocate="rd" encoder: a tile may be longer than the bound of an equal-split codec, and
+        spiht_tile_unpack takes a length as at most slot_stride -- the tile would be cut short.  Pass slot_stride >= the longest
+        length of d_lens (the host forms size the slots by the longest stream already)."""
         i0, i1, j0, j1 = [int(v) for v in sub]
         y0, x0, h, w = [int(v) for v in window]
         need = window_tiles(self.H, self.W, self.th, self.tw, y0, x0, h, w)
@@ -296,6 +383,11 @@ class TiledCodec:
         if total:
             self.ctx.download(run, d_packed.ptr)  # the streams of all pictures: one download
         out, off = [], np.concatenate(([0], np.cumsum(lens, dtype=np.int64)))
+        if self.allocate is not None:
+            lam = np.empty(N, dtype=np.float64)
+            self.ctx.download(lam, self._bufs["lambda"].ptr)
+            cuts = [TileAllocation(float(lam[n]), [int(v) for v in lens[n * self.T:(n + 1) * self.T]]) for n in range(N)]
+            self.last_allocation = cuts[0] if single else cuts
         for n in range(N):
             a, b = n * self.T, (n + 1) * self.T
             out.append(TiledResult(self.H, self.W, self.c, self.th, self.tw, self.level, [int(v) for v in maxn[a:b]],
@@ -315,6 +407,27 @@ class TiledCodec:
     def encode_u16(self, image_or_images, channels_last=False):
         """uint16 pictures -> what encode gives for pictures / 65535.0"""
         return self._encode_host(image_or_images, np.uint16, channels_last, "encode_u16")
+
+    def tile_curves(self, image, dtype=None):
+        """The curves allocate="rd" cuts by, of one picture [c, H, W] (dtype None: the codec's float pixels; np.uint8 /
+        np.uint16: integer pixels) -> TileCurves.  alloc.allocate(curves.lengths, curves.sse, max_bits // 8) gives the lengths
+        of encode / encode_u8 / encode_u16 of that picture; last_allocation is set as by them."""
+        if self.allocate is None:
+            raise ValueError('tile_curves: the codec was not built with allocate="rd"')
+        image = np.asarray(image)
+        if image.ndim != 3:
+            raise ValueError("tile_curves takes one picture [c, H, W]")
+        dtype = self.pixel_dtype if dtype is None else np.dtype(dtype)
+        self._encode_host(image, dtype, False, "tile_curves")
+        T, K = self.T, self.points
+        D = np.empty((K + 1, T), dtype=np.uint64 if dtype.kind == "u" else np.float64)
+        nbits = np.empty(T, dtype=np.uint64)
+        maxn = np.empty(T, dtype=np.uint8)
+        self.ctx.download(D, self._bufs["D"].ptr)
+        self.ctx.download(nbits, self._bufs["nbits"].ptr)
+        self.ctx.download(maxn, self._bufs["maxn"].ptr)
+        nbytes = [(int(v) + 7) // 8 for v in nbits]
+        return TileCurves([alloc.tile_lengths(n, K) for n in nbytes], np.ascontiguousarray(D.T), nbytes, [int(v) for v in maxn])
 
     def _check_result(self, r):
         _check_version(r)
@@ -397,42 +510,55 @@ class _View:
 _codecs = {}
 
 
-def _codec_for(c, H, W, tile, settings, level, max_bits, pixel_dtype=np.float64):
+def _codec_for(c, H, W, tile, settings, level, max_bits, pixel_dtype=np.float64, allocate=None, points=alloc.POINTS,
+               spread=alloc.SPREAD):
     """a TiledCodec per geometry and settings, kept (a few of them) so that repeated calls reuse its device buffers"""
     th, tw = _tile_arg(tile)
-    key = (c, H, W, th, tw, repr(settings), level, max_bits, np.dtype(pixel_dtype).name, id(_lib.default_context()))
+    if getattr(settings, "color_model", None) not in (None, "RGB"):
+        pixel_dtype = np.float64  # as TiledCodec: colour pictures are coded in float64
+    points, spread = _alloc_args(allocate, points, spread, max_bits, pixel_dtype)
+    key = (c, H, W, th, tw, repr(settings), level, max_bits, np.dtype(pixel_dtype).name, allocate, points, spread,
+           id(_lib.default_context()))
     codec = _codecs.get(key)
     if codec is None:
         while len(_codecs) >= 4:
             _codecs.pop(next(iter(_codecs))).close()
-        codec = _codecs[key] = TiledCodec(c, H, W, (th, tw), settings, level, max_bits, None, pixel_dtype)
+        codec = _codecs[key] = TiledCodec(c, H, W, (th, tw), settings, level, max_bits, None, pixel_dtype, allocate, points, spread)
     return codec
 
 
-def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_last, name):
+def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_last, name, allocate=None, points=alloc.POINTS,
+                  spread=alloc.SPREAD):
     if not isinstance(image, np.ndarray) or image.ndim != 3:
         raise ValueError('image ndim must be 3: c,h,w')
     c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
     if dtype is None:
         dtype = np.float32 if image.dtype in (np.float32, np.float16) else np.float64
-    codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if np.dtype(dtype).kind == "f" else np.float64)
+    codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if np.dtype(dtype).kind == "f" else np.float64,
+                       allocate, points, spread)
     return codec._encode_host(image, codec.pixel_dtype if np.dtype(dtype).kind == "f" else dtype, channels_last, name)
 
 
-def encode_image_tiled(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None):
+def encode_image_tiled(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, allocate=None, points=alloc.POINTS,
+                       spread=alloc.SPREAD):
     """encode_image of a picture (c, h, w) as tiles of `tile` (an int or (th, tw)) -> TiledResult.  level and max_bits are
-    per tile as in TiledCodec: every tile gets max_bits // T bits; float32 pixels run the single-precision transform."""
-    return _encode_tiled(image, tile, spiht_settings, level, max_bits, None, False, "encode_image_tiled")
+    per tile as in TiledCodec: every tile gets max_bits // T bits; float32 pixels run the single-precision transform.
+    allocate="rd" (with points, spread): the tiles share max_bits by their rate-distortion curves, as in TiledCodec."""
+    return _encode_tiled(image, tile, spiht_settings, level, max_bits, None, False, "encode_image_tiled", allocate, points, spread)
 
 
-def encode_image_tiled_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False):
-    """uint8 pixels: the TiledResult of encode_image_tiled(image / 255.0, ...)"""
-    return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint8, channels_last, "encode_image_tiled_u8")
+def encode_image_tiled_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False,
+                          allocate=None, points=alloc.POINTS, spread=alloc.SPREAD):
+    """uint8 pixels: the TiledResult of encode_image_tiled(image / 255.0, ...); allocate="rd" measures 8-bit decodes"""
+    return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint8, channels_last, "encode_image_tiled_u8", allocate,
+                         points, spread)
 
 
-def encode_image_tiled_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False):
-    """uint16 pixels: the TiledResult of encode_image_tiled(image / 65535.0, ...)"""
-    return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint16, channels_last, "encode_image_tiled_u16")
+def encode_image_tiled_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False,
+                           allocate=None, points=alloc.POINTS, spread=alloc.SPREAD):
+    """uint16 pixels: the TiledResult of encode_image_tiled(image / 65535.0, ...); allocate="rd" measures 16-bit decodes"""
+    return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint16, channels_last, "encode_image_tiled_u16", allocate,
+                         points, spread)
 
 
 def _decode_tiled(result, spiht_settings, window, dtype, channels_last):
