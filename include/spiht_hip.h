@@ -660,6 +660,30 @@ int spiht_tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D
                         uint64_t budget_bytes, uint64_t *d_nbits_out, double *d_lambda);
 
 /* ---------------------------------------------------------------------------------------
+ * Quality layers of a tiled picture (csrc/layers.hip; the rule is spiht_amd/alloc.py, allocate_layers).  The allocation is
+ * run at Q growing budgets on one table of distortions; the lengths nest, and the run stores for every tile the bytes between
+ * consecutive allocations, layer-major: layer q is, for t = 0 .. T-1, bytes [B(q-1, t), B(q, t)) of tile t's stream, B(-1) = 0.
+ * The run through layer q is the whole picture at budget q.  Additions only: the ABI version stays at 2.  All pointers are
+ * DEVICE pointers; asynchronous on the context's stream; argument errors are returned before anything is queued; no byte
+ * outside the stated outputs is written.  1 <= Q <= 255, N * Q * T < 2^31, slot_stride a multiple of 4, at most 2^29.
+ *   spiht_layer_pack   the N * T slots a batched encode left + d_cum_bits uint64 [Q][N * T], row q what the q-th
+ *                      spiht_tile_allocate wrote (bits) -> d_cum uint32 [N][Q][T]: B(q, t) = max over q' <= q of
+ *                      min(ceil(bits / 8), slot_stride) -- total: a table that does not nest still gives a valid run;
+ *                      d_packed: picture n's run behind picture n - 1's, inside a picture layer-major, then tile;
+ *                      d_pic_bytes uint64 [N]: the runs' lengths.  Nothing is written at or past d_packed + packed_cap
+ *                      (N * T * slot_stride always suffices).  The pieces' offsets live in a grow-only buffer of the context.
+ *   spiht_layer_unpack d_layers (layers_bytes long): one picture's run or a prefix of it; d_cum uint32 [Q][T] its table ->
+ *                      S slots of slot_stride bytes: slot s receives tile d_sel[s] (an entry outside [0, T) is clamped), or
+ *                      tile s when d_sel is NULL (then S <= T): its pieces of the layers 0 .. upto - 1 one behind the other,
+ *                      then zeros up to slot_stride; d_nbytes uint64 [S] = min(cum[upto-1][t], slot_stride).  1 <= upto <= Q.
+ *                      Bytes the table claims past layers_bytes read as zero; a table that falls in q is taken as its running
+ *                      maximum. */
+int spiht_layer_pack(spiht_ctx *ctx, const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_cum_bits, int64_t Q, int64_t N,
+                     int64_t T, uint8_t *d_packed, uint64_t packed_cap, uint32_t *d_cum, uint64_t *d_pic_bytes);
+int spiht_layer_unpack(spiht_ctx *ctx, const uint8_t *d_layers, uint64_t layers_bytes, const uint32_t *d_cum, int64_t Q, int64_t T,
+                       int64_t upto, const int32_t *d_sel, int64_t S, uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes);
+
+/* ---------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, every rank codes its own images (the reference's encode / decode
  * are pure functions of one image, src/lib.rs:24-42 -- nothing is exchanged while coding); the ONE exchange of the
  * path is the gather of the finished streams.  It runs on RCCL (ncclAllGather over xGMI), inside this library, on

@@ -32,4 +32,9 @@ globals().update({_k: getattr(_impl, _k) for _k in ("TiledCodec", "TiledResult",
                                                     "decode_image_tiled", "decode_image_tiled_u8", "decode_image_tiled_u16",
                                                     "decode_image_window", "decode_image_window_u8",
                                                     "decode_image_window_u16")})
+# ... quality layers of a tiled picture: any prefix of the file decodes
+globals().update({_k: getattr(_impl, _k) for _k in ("LayeredResult", "encode_image_layered", "encode_image_layered_u8",
+                                                    "encode_image_layered_u16", "decode_image_layered", "decode_image_layered_u8",
+                                                    "decode_image_layered_u16", "decode_image_layered_window",
+                                                    "decode_image_layered_window_u8", "decode_image_layered_window_u16")})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

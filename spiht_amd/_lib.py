@@ -66,6 +66,7 @@ SYMBOLS = [
     "spiht_tile_paste_u8", "spiht_tile_paste_u16", "spiht_tile_paste_f32", "spiht_tile_paste_f64",
     "spiht_tile_pack", "spiht_tile_unpack",
     "spiht_tile_prefix_slots", "spiht_sse_tiles_f64", "spiht_sse_tiles_u8", "spiht_sse_tiles_u16", "spiht_tile_allocate",
+    "spiht_layer_pack", "spiht_layer_unpack",
 ]
 
 
@@ -223,6 +224,9 @@ def lib():
         L.spiht_tile_prefix_slots.argtypes = [vp, vp, u64, vp, i64, i64, i64, i64, vp, u64, vp, vp, vp]
         L.spiht_sse_tiles_f64.argtypes = L.spiht_sse_tiles_u8.argtypes = [vp, vp, vp] + [i64] * 9 + [vp]
         L.spiht_tile_allocate.argtypes = [vp, vp, vp, i32, i64, i64, i64, u64, vp, vp]
+        # quality layers of a tiled picture: the streams in layer-major order and back
+        L.spiht_layer_pack.argtypes = [vp, vp, u64, vp, i64, i64, i64, vp, u64, vp, vp]
+        L.spiht_layer_unpack.argtypes = [vp, vp, u64, vp, i64, i64, i64, vp, i64, vp, u64, vp]
         # 16-bit pixels: every *_u16 call takes what its *_u8 sibling takes
         for name in SYMBOLS:
             if name.endswith("_u16"):

@@ -124,3 +124,66 @@ def allocate(R, D, budget_bytes):
                 out[t] += give
                 rest -= give
     return out, lam
+
+
+MAX_LAYERS = 255
+
+
+def layer_budgets(max_bits, layers):
+    """the bit budgets of the Q quality layers of a tiled picture, 1 <= Q <= MAX_LAYERS, the last one max_bits.
+    layers: an int Q -- [max_bits >> (Q - 1 - q) for q in range(Q)], every layer twice the one before (ValueError if these
+    do not strictly increase: max_bits is too small for Q halvings); or a sequence of strictly increasing non-negative ints
+    whose last entry is max_bits.  The byte budget of a layer is bits // 8, as for allocate="rd"; two layers of the same
+    byte budget are ordinary (the later one is empty)."""
+    if isinstance(max_bits, bool) or not isinstance(max_bits, (int, np.integer)):
+        raise TypeError("max_bits must be an integer, not %s" % type(max_bits).__name__)
+    max_bits = int(max_bits)
+    if max_bits < 0:
+        raise ValueError("max_bits = %d is negative" % max_bits)
+    if isinstance(layers, bool) or isinstance(layers, (str, bytes)):
+        raise TypeError("layers must be an integer or a sequence of integers, not %s" % type(layers).__name__)
+    if isinstance(layers, (int, np.integer)):
+        Q = int(layers)
+        if not 1 <= Q <= MAX_LAYERS:
+            raise ValueError("layers = %d: 1 .. %d layers" % (Q, MAX_LAYERS))
+        out = [max_bits >> (Q - 1 - q) for q in range(Q)]
+        if any(b <= a for a, b in zip(out, out[1:])):
+            raise ValueError("layers = %d: halving max_bits = %d that often does not give increasing budgets" % (Q, max_bits))
+        return out
+    try:
+        seq = list(layers)
+    except TypeError:
+        raise TypeError("layers must be an integer or a sequence of integers, not %s" % type(layers).__name__)
+    for b in seq:
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)):
+            raise TypeError("a layer's budget must be an integer, not %s" % type(b).__name__)
+    out = [int(b) for b in seq]
+    if not 1 <= len(out) <= MAX_LAYERS:
+        raise ValueError("%d layers: 1 .. %d" % (len(out), MAX_LAYERS))
+    if out[0] < 0 or any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError("the layers' budgets must be non-negative and strictly increasing: %r" % (out,))
+    if out[-1] != max_bits:
+        raise ValueError("the last layer's budget is %d, max_bits is %d" % (out[-1], max_bits))
+    return out
+
+
+def allocate_layers(R, D, budgets_bytes):
+    """R, D: [T][K + 1] as for allocate; budgets_bytes: Q non-decreasing byte budgets.  -> (cum, lams): cum[q], lams[q] =
+    allocate(R, D, budgets_bytes[q]).
+
+    The rows NEST: cum[q][t] <= cum[q + 1][t] for every tile, and lams[q] >= lams[q + 1] -- so a tile's stream cut at cum[q][t]
+    is a prefix of its stream cut at cum[q + 1][t], and the bytes between them are what layer q + 1 adds.  Why: the cost of
+    the edges of slope >= s grows as s falls, so for budgets b1 <= b2, lambda*(b2) <= lambda*(b1).  A tile's hull edges have
+    strictly decreasing slopes, so the edges it takes at b1 (those of slope >= lambda*(b1)) are the first of those it takes at
+    b2.  If lambda*(b2) < lambda*(b1), the slope the rest of b1 went to is >= lambda*(b2): those edges, partial at b1, are
+    whole at b2.  If the two are equal, the same next slope takes min(delta R, rest) in tile order, and what a tile gets does
+    not fall as the rest grows.  The last row is what allocate="rd" gives for the whole budget."""
+    budgets = [int(b) for b in budgets_bytes]
+    if any(b < a for a, b in zip(budgets, budgets[1:])):
+        raise ValueError("budgets_bytes must not fall: %r" % (budgets,))
+    cum, lams = [], []
+    for b in budgets:
+        out, lam = allocate(R, D, b)
+        cum.append(out)
+        lams.append(lam)
+    return cum, lams

@@ -72,6 +72,11 @@ int spiht_launch_tile_prefix_slots(const uint8_t *d_slots, uint64_t slot_stride,
 int spiht_launch_sse_tiles(const TileSseArgs *a, int es, int64_t G, hipStream_t st);
 int spiht_launch_tile_allocate(const uint64_t *d_nbits, const void *d_D, int kind, int K, int64_t N, int64_t T, uint64_t budget,
                                void *scratch, uint64_t *d_nbits_out, double *d_lambda, hipStream_t st);
+int spiht_launch_layer_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_cum_bits, int64_t Q, int64_t N, int64_t T,
+                            uint64_t *d_off, uint8_t *d_packed, uint64_t cap, uint32_t *d_cum, uint64_t *d_pic_bytes, hipStream_t st);
+int spiht_launch_layer_unpack(const uint8_t *d_layers, uint64_t layers_bytes, const uint32_t *d_cum, int64_t T, int64_t upto,
+                              const int32_t *d_sel, int64_t S, uint64_t *d_off, uint32_t *d_M, uint8_t *d_slots, uint64_t slot_stride,
+                              uint64_t *d_nbytes, hipStream_t st);
 }
 
 static thread_local std::string g_hip_err;
@@ -151,6 +156,7 @@ struct spiht_ctx {
     DevBuf rdpart;              // per-workgroup partial sums of the rate-distortion reductions (rd.hip)
     DevBuf tilescr;             // tiled pictures (tiles.hip): byte lengths and offsets of the streams pack / unpack move
     DevBuf allocscr;            // rate allocation across tiles (alloc.hip): the tiles' hulls
+    DevBuf layerscr;            // quality layers (layers.hip): the pieces' offsets in the run, the table's running maximum
     bool recz_clean = false;
     // spiht_decode_lists_batch_i32 -> spiht_unscatter_lists_batch_i32: the launch whose scatter can still be undone
     DecArgs last_dec;
@@ -495,7 +501,7 @@ extern "C" void spiht_ctx_destroy(spiht_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->widebuf, &ctx->filt, &ctx->exttmp, &ctx->l1flags, &ctx->x, &ctx->dmsb, &ctx->lmsb, &ctx->maxabs, &ctx->out, &ctx->nbits, &ctx->maxn, &ctx->err,
                       &ctx->lists, &ctx->coeffs, &ctx->a0, &ctx->a1, &ctx->data, &ctx->nbytes, &ctx->rec, &ctx->mults,
                       &ctx->img, &ctx->trace, &ctx->meta, &ctx->recz, &ctx->lspcnt, &ctx->himg, &ctx->hrec, &ctx->tilebuf,
-                      &ctx->pix, &ctx->hpix8, &ctx->rdpart, &ctx->tilescr, &ctx->allocscr};
+                      &ctx->pix, &ctx->hpix8, &ctx->rdpart, &ctx->tilescr, &ctx->allocscr, &ctx->layerscr};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &r : ctx->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -2575,6 +2581,45 @@ extern "C" int spiht_tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, cons
     CHK(ensure(ctx, ctx->allocscr, al_scratch_bytes((uint64_t)N * T, (uint64_t)K)));
     LAUNCHCHK(spiht_launch_tile_allocate(d_nbits, d_D, kind, (int)K, N, T, budget_bytes, ctx->allocscr.p, d_nbits_out, d_lambda,
                                          ctx->stream));
+    return SPIHT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// quality layers of a tiled picture (layers.hip): the tiles' streams in layer-major order and back
+// ------------------------------------------------------------------------------------------------
+static int layer_args(spiht_ctx *ctx, const void *a, const void *b, const void *d, const void *e, const void *f, uint64_t slot_stride,
+                      int64_t Q, int64_t N, int64_t T) {
+    if (!ctx || !a || !b || !d || !e || !f || slot_stride == 0 || slot_stride % 4) return SPIHT_ERR_ARG;
+    if (Q < 1 || Q > 255 || N < 0 || T < 1) return SPIHT_ERR_ARG;
+    if (slot_stride > ((uint64_t)1 << 29) || (__int128)N * Q * T > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    return SPIHT_OK;
+}
+extern "C" int spiht_layer_pack(spiht_ctx *ctx, const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_cum_bits, int64_t Q,
+                                int64_t N, int64_t T, uint8_t *d_packed, uint64_t packed_cap, uint32_t *d_cum, uint64_t *d_pic_bytes) {
+    CHK(layer_args(ctx, d_slots, d_cum_bits, d_packed, d_cum, d_pic_bytes, slot_stride, Q, N, T));
+    if ((uintptr_t)d_cum_bits % 8 || (uintptr_t)d_cum % 4 || (uintptr_t)d_pic_bytes % 8) return SPIHT_ERR_ARG;
+    if (N == 0) return SPIHT_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->layerscr, (size_t)(N * Q * T) * 8));
+    LAUNCHCHK(spiht_launch_layer_pack(d_slots, slot_stride, d_cum_bits, Q, N, T, (uint64_t *)ctx->layerscr.p, d_packed, packed_cap,
+                                      d_cum, d_pic_bytes, ctx->stream));
+    return SPIHT_OK;
+}
+extern "C" int spiht_layer_unpack(spiht_ctx *ctx, const uint8_t *d_layers, uint64_t layers_bytes, const uint32_t *d_cum, int64_t Q,
+                                  int64_t T, int64_t upto, const int32_t *d_sel, int64_t S, uint8_t *d_slots, uint64_t slot_stride,
+                                  uint64_t *d_nbytes) {
+    CHK(layer_args(ctx, d_layers, d_cum, d_slots, d_nbytes, d_nbytes, slot_stride, Q, 1, T));
+    if (upto < 1 || upto > Q || S < 0 || (!d_sel && S > T)) return SPIHT_ERR_ARG;
+    if ((uintptr_t)d_cum % 4 || (uintptr_t)d_sel % 4 || (uintptr_t)d_nbytes % 8) return SPIHT_ERR_ARG;
+    if (S > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    if (S == 0) return SPIHT_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(ensure(ctx, ctx->layerscr, (size_t)(upto * T) * 12));
+    uint64_t *d_off = (uint64_t *)ctx->layerscr.p;
+    LAUNCHCHK(spiht_launch_layer_unpack(d_layers, layers_bytes, d_cum, T, upto, d_sel, S, d_off, (uint32_t *)(d_off + upto * T), d_slots,
+                                        slot_stride, d_nbytes, ctx->stream));
     return SPIHT_OK;
 }
 

@@ -16,7 +16,8 @@ import numpy as np
 from .spiht_wrapper import (EncodingResult, SpihtSettings, decode_image, decode_image_reduced_u8, encode_image,
                             get_slices_and_h_w)
 from .rd import cut_to_psnr, rd_curve
-from .tiles import decode_image_tiled, decode_image_window, encode_image_tiled
+from .tiles import (decode_image_layered, decode_image_layered_window, decode_image_tiled, decode_image_window,
+                    encode_image_layered, encode_image_tiled)
 from .utils import imload, imsave, load_encoding, save_encoding
 
 _ARGS = [  # (flag, type, default, help): the reference tool's options, then ours
@@ -37,6 +38,8 @@ _ARGS = [  # (flag, type, default, help): the reference tool's options, then our
     ("--window", str, None, "with --tile: decode only the window Y0,X0,H,W of the picture and save that"),
     ("--allocate", str, None, "with --tile: 'rd' shares the bit budget between the tiles by their rate-distortion curves"),
     ("--points", int, 16, "with --allocate rd: prefixes measured per tile"),
+    ("--layers", str, None, "with --tile N --allocate rd: Q quality layers, or their bit budgets b0,b1,... (the last one the "
+                            "picture's); decodes after every layer"),
 ]
 
 
@@ -96,6 +99,8 @@ def main_tiled(args, picture):
     p = plan(args, c, h, w)
     level = default_level(args.tile, args.tile) if args.level is None else args.level
     print("encoding %d x %d x %d at %.3f bpp as tiles of %d x %d" % (c, h, w, args.bpp, args.tile, args.tile))
+    if args.layers is not None:
+        return main_layered(args, picture, p, level)
     enc, secs = timed(encode_image_tiled, picture, args.tile, p.settings, level, p.max_bits, args.allocate, args.points)
     gy, gx = enc.grid()
     print("encoded in %.3f s: %d x %d tiles, %.2f KiB" % (secs, gy, gx, len(enc.encoded_bytes) / 1024))
@@ -115,12 +120,38 @@ def main_tiled(args, picture):
     return enc, decoded
 
 
+def main_layered(args, picture, p, level):
+    """--layers Q | b0,b1,...: the tiled picture in quality layers; the file is cut after every layer and decoded"""
+    c, h, w = picture.shape
+    if args.allocate != "rd":
+        raise SystemExit("--layers needs --tile N --allocate rd")
+    layers = [int(v) for v in args.layers.split(",")]
+    layers = layers[0] if len(layers) == 1 else layers
+    enc, secs = timed(encode_image_layered, picture, args.tile, p.settings, level, p.max_bits, layers, args.points)
+    gy, gx = enc.grid()
+    print("encoded in %.3f s: %d x %d tiles, %d layers, %.2f KiB" % (secs, gy, gx, enc.layers, len(enc.to_bytes()) / 1024))
+    window = [int(v) for v in args.window.split(",")] if args.window else None
+    ref = picture if window is None else picture[:, window[0]:window[0] + window[2], window[1]:window[1] + window[3]]
+    print("  %6s %12s %10s" % ("layer", "file bytes", "PSNR dB"))
+    for q, end in enumerate(enc.layer_ends()):
+        if window is None:
+            decoded = decode_image_layered(enc, p.settings, q + 1)
+        else:
+            decoded = decode_image_layered_window(enc, p.settings, *window, q + 1)
+        mse = float(((ref - np.asarray(decoded)) ** 2).mean())
+        print("  %6d %12d %10.3f" % (q, end, 10 * math.log10(1.0 / mse) if mse > 0 else math.inf))
+    decoded = np.asarray(decoded)
+    imsave(args.out, decoded)
+    print("  picture written to", args.out)
+    return enc, decoded
+
+
 def main(args):
     picture = imload(args.image_filename)
     if args.tile is not None:
         return main_tiled(args, picture)
-    if args.window or args.allocate:
-        raise SystemExit("--window and --allocate need --tile")
+    if args.window or args.allocate or args.layers:
+        raise SystemExit("--window, --allocate and --layers need --tile")
     c, h, w = picture.shape
     p = plan(args, c, h, w)
     if args.load:

@@ -14,6 +14,12 @@ allocate="rd" shares the bit budget between the tiles by their rate-distortion c
 past its share, K prefixes of every tile are decoded and measured on the device, and every tile is cut where one more byte
 buys the same drop in distortion (alloc.py is the rule, csrc/alloc.hip the kernels).  The container and every decoder are
 unchanged: a tile's stream is still encode_image of the tile's pixels, at max_bits = 8 * its length.
+
+Quality layers (encode_layered, LayeredResult): the allocation is run at Q growing budgets on the one table of distortions;
+the cuts nest (alloc.allocate_layers), and the container stores for every tile the bytes between consecutive cuts, layer by
+layer.  The file through layer q is the whole picture at budget q, and any prefix of the file that holds the tables decodes.
+The coder is untouched: two more copies (csrc/layers.hip, spiht_layer_*) put the slots into that order and gather a tile's
+pieces back into a decoder slot.
 """
 import ctypes as C
 import struct
@@ -30,6 +36,9 @@ from .spiht_wrapper import (ENCODER_DECODER_VERSION, EncodingResult, SpihtSettin
 MAGIC = b"SPTL"
 CONTAINER_VERSION = 1
 _HEADER = struct.Struct("<4sBBHIIII")
+LAYERED_MAGIC = b"SPTQ"
+LAYERED_VERSION = 1
+_LAYERED_HEADER = struct.Struct("<4sBBHIIIIHH")
 
 
 def _tile_arg(tile):
@@ -126,6 +135,121 @@ class TiledResult:
             raise ValueError("the table's lengths add up to %d bytes; %d follow it" % (int(nbytes.sum()), rest))
         return TiledResult(h, w, c, th, tw, None if level == 255 else level, [int(v) for v in max_n], [int(v) for v in nbytes],
                            data[_HEADER.size + 5 * T:])
+
+
+@dataclass
+class LayeredResult:
+    """The streams of one tiled picture in Q quality layers.  h, w, c, th, tw, level, max_n: as TiledResult; cum [Q][T]:
+    cum[q][t] the bytes of tile t through layer q, non-decreasing in q; encoded_bytes: the layers one behind the other,
+    layer q being, for t = 0 .. T - 1, the bytes [cum[q - 1][t], cum[q][t]) of tile t's stream (cum[-1] = 0)."""
+    h: int
+    w: int
+    c: int
+    th: int
+    tw: int
+    level: Optional[int]
+    max_n: List[int]
+    cum: List[List[int]]
+    encoded_bytes: bytes
+    _encoding_version: str = ENCODER_DECODER_VERSION
+
+    @property
+    def layers(self):
+        return len(self.cum)
+
+    def grid(self):
+        return tile_grid(self.h, self.w, self.th, self.tw)
+
+    def _table(self):
+        """(cum [Q][T], piece lengths [Q][T], piece offsets in encoded_bytes [Q][T]) as int64; ValueError if the tables do not
+        describe encoded_bytes"""
+        T = len(self.max_n)
+        cum = np.asarray(self.cum, dtype=np.int64)
+        if cum.ndim != 2 or not 1 <= cum.shape[0] <= alloc.MAX_LAYERS or cum.shape[1] != T or T < 1:
+            raise ValueError("cum is [Q][T] with 1 <= Q <= %d; got shape %s for %d tiles" % (alloc.MAX_LAYERS, cum.shape, T))
+        lens = np.diff(cum, axis=0, prepend=0)
+        if (lens < 0).any() or (cum >= 2 ** 32).any():
+            raise ValueError("cum must not fall from a layer to the next and must fit 32 bits")
+        if int(lens.sum()) != len(self.encoded_bytes):
+            raise ValueError("the table's pieces add up to %d bytes; the layers hold %d" % (int(lens.sum()), len(self.encoded_bytes)))
+        off = (np.cumsum(lens.reshape(-1)) - lens.reshape(-1)).reshape(lens.shape)
+        return cum, lens, off
+
+    def layer_ends(self):
+        """the Q lengths of to_bytes() at which each layer is complete: where a server cuts the file"""
+        cum, lens, _ = self._table()
+        head = _LAYERED_HEADER.size + 4 * cum.size + cum.shape[1]
+        return [head + int(v) for v in np.cumsum(lens.sum(axis=1))]
+
+    def tiled(self, upto=None):
+        """the TiledResult of the first `upto` layers (None: all; 1 <= upto <= Q): tile t is its pieces one behind the other,
+        nbytes = cum[upto - 1].  Host-side numpy, for every decoder of a TiledResult and the reference's per-tile decode; the
+        device path is TiledCodec.decode_layered."""
+        cum, lens, off = self._table()
+        upto = _upto_arg(upto, cum.shape[0])
+        data = np.frombuffer(self.encoded_bytes, dtype=np.uint8)
+        parts = [data[int(off[q, t]):int(off[q, t] + lens[q, t])] for t in range(cum.shape[1]) for q in range(upto)]
+        run = np.concatenate(parts) if parts else data[:0]
+        return TiledResult(self.h, self.w, self.c, self.th, self.tw, self.level, [int(v) for v in self.max_n],
+                           [int(v) for v in cum[upto - 1]], run.tobytes(), self._encoding_version)
+
+    def to_bytes(self):
+        """The container, little-endian: b"SPTQ", u8 version = 1, u8 level (255 = None), u16 c, u32 H, W, th, tw, u16 Q, u16 0
+        (28 bytes), then Q x T u32 cum (row q tile-major), T x u8 max_n, then the layers.  Every prefix at least
+        28 + 4 Q T + T bytes long is a picture (from_bytes)."""
+        cum, _, _ = self._table()
+        if self.level is not None and not 0 <= int(self.level) < 255:
+            raise ValueError("level %r does not fit the container" % (self.level,))
+        level = 255 if self.level is None else int(self.level)
+        return (_LAYERED_HEADER.pack(LAYERED_MAGIC, LAYERED_VERSION, level, self.c, self.h, self.w, self.th, self.tw, cum.shape[0], 0)
+                + cum.astype("<u4").tobytes() + np.asarray(self.max_n, dtype=np.uint8).tobytes() + bytes(self.encoded_bytes))
+
+    @staticmethod
+    def from_bytes(data):
+        """Inverse of to_bytes, of the file or of a PREFIX of it that holds header and tables.  With a < total stream bytes
+        behind the tables the table is clipped: the piece (q, t) at stream offset o of length l keeps clamp(a - o, 0, l)
+        bytes and cum'[q][t] = cum'[q - 1][t] + kept; Q stays (absent layers are empty).  The result is an ordinary
+        LayeredResult.  ValueError: wrong magic or version, fewer bytes than header and tables, a table that falls from a
+        layer to the next, more bytes than the table accounts for."""
+        data = bytes(data)
+        if len(data) < _LAYERED_HEADER.size:
+            raise ValueError("a layered container has a %d-byte header; got %d bytes" % (_LAYERED_HEADER.size, len(data)))
+        magic, version, level, c, h, w, th, tw, Q, _ = _LAYERED_HEADER.unpack_from(data, 0)
+        if magic != LAYERED_MAGIC:
+            raise ValueError("not a layered tiled container: magic %r" % (magic,))
+        if version != LAYERED_VERSION:
+            raise ValueError("layered container version %d, this reader knows %d" % (version, LAYERED_VERSION))
+        if not 1 <= Q <= alloc.MAX_LAYERS:
+            raise ValueError("a layered container has 1 .. %d layers, not %d" % (alloc.MAX_LAYERS, Q))
+        gy, gx = tile_grid(h, w, th, tw)
+        T = gy * gx
+        head = _LAYERED_HEADER.size + 4 * Q * T + T
+        if len(data) < head:
+            raise ValueError("header and tables of %d layers of %d tiles are %d bytes; got %d" % (Q, T, head, len(data)))
+        cum = np.frombuffer(data, dtype="<u4", count=Q * T, offset=_LAYERED_HEADER.size).astype(np.int64).reshape(Q, T)
+        max_n = np.frombuffer(data, dtype=np.uint8, count=T, offset=_LAYERED_HEADER.size + 4 * Q * T)
+        lens = np.diff(cum, axis=0, prepend=0)
+        if (lens < 0).any():
+            raise ValueError("the table falls from a layer to the next")
+        a, total = len(data) - head, int(lens.sum())
+        if a > total:
+            raise ValueError("the table's pieces add up to %d bytes; %d follow it" % (total, a))
+        if a < total:
+            flat = lens.reshape(-1)
+            off = np.cumsum(flat) - flat
+            cum = np.cumsum(np.clip(a - off, 0, flat).reshape(Q, T), axis=0)
+        return LayeredResult(h, w, c, th, tw, None if level == 255 else level, [int(v) for v in max_n],
+                             [[int(v) for v in row] for row in cum], data[head:])
+
+
+def _upto_arg(upto, Q):
+    if upto is None:
+        return Q
+    if isinstance(upto, bool) or not isinstance(upto, (int, np.integer)):
+        raise TypeError("upto must be an integer or None, not %s" % type(upto).__name__)
+    if not 1 <= upto <= Q:
+        raise ValueError("upto = %d: 1 .. %d layers" % (upto, Q))
+    return int(upto)
 
 
 @dataclass
@@ -232,11 +356,22 @@ class TiledCodec:
         pack, queued on the codec's context.  allocate="rd": between the encode and the pack, per group of candidate lengths,
         the prefix slots, one batched decode of them and the per-tile error sums; then one spiht_tile_allocate, whose lengths
         the pack takes.  No host wait anywhere."""
+        N, vp = int(N), C.c_void_p
+        dt, d_tiles, d_slots, d_nbits = self._encode_slots(d_img, N, d_max_n, strides, "encode_device")
+        NT, stride = N * self.T, self.codec.slot_stride
+        if self.allocate is not None:
+            d_nbits = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n)
+        _lib.check(self.L.spiht_tile_pack(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, vp(d_packed.ptr),
+                                          d_packed.nbytes, vp(d_lens.ptr)))
+
+    def _encode_slots(self, d_img, N, d_max_n, strides, name):
+        """the cut and the batched encode of the N * T tiles -> (element type, the buffers of the tiles, the stream slots and
+        the streams' lengths in bits)"""
         N = int(N)
         dt = np.dtype(d_img.dtype)
         NT, vp = N * self.T, C.c_void_p
         if N < 1:
-            raise ValueError("encode_device: no pictures")
+            raise ValueError("%s: no pictures" % name)
         d_tiles = self._buf("tiles", NT * self.c * self.th * self.tw * dt.itemsize)
         geom = (N, self.c, self.H, self.W, self.th, self.tw)
         if dt.kind == "u":
@@ -246,7 +381,7 @@ class TiledCodec:
             _lib.check(cut(self.ctx.handle, vp(d_img.ptr), st_p, *geom, vp(d_tiles.ptr)))
         else:
             if dt != self.pixel_dtype or strides is not None:
-                raise ValueError("encode_device: %s pictures, the codec's are dense %s" % (dt.name, self.pixel_dtype.name))
+                raise ValueError("%s: %s pictures, the codec's are dense %s" % (name, dt.name, self.pixel_dtype.name))
             cut = self.L.spiht_tile_cut_f32 if dt.itemsize == 4 else self.L.spiht_tile_cut_f64
             _lib.check(cut(self.ctx.handle, vp(d_img.ptr), *geom, vp(d_tiles.ptr)))
         stride = self.codec.slot_stride
@@ -257,14 +392,22 @@ class TiledCodec:
             enc(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
         else:
             self.codec.encode_device(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
-        if self.allocate is not None:
-            d_nbits = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n)
-        _lib.check(self.L.spiht_tile_pack(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, vp(d_packed.ptr),
-                                          d_packed.nbytes, vp(d_lens.ptr)))
+        return dt, d_tiles, d_slots, d_nbits
 
     def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n):
         """the NT full streams in d_slots -> the buffer of the cut lengths in bits (uint64 [NT]); the table of distortions
         stays in the buffer "D" ([K + 1][NT]) and lambda* in "lambda" ([N]) for the host forms"""
+        NT, K, vp = N * self.T, self.points, C.c_void_p
+        d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n)
+        d_cut = self._buf("cut", NT * 8)
+        d_lam = self._buf("lambda", N * 8)
+        _lib.check(self.L.spiht_tile_allocate(self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, K, N, self.T,
+                                              int(self.max_bits) // 8, vp(d_cut.ptr), vp(d_lam.ptr)))
+        return d_cut
+
+    def _measure_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n):
+        """the NT full streams in d_slots -> the buffer "D": float64 / uint64 [K + 1][NT], the error of every tile at its K + 1
+        candidate lengths"""
         NT, K, vp, c = N * self.T, self.points, C.c_void_p, self.c
         stride = self.codec.slot_stride
         integer = dt.kind == "u"
@@ -275,8 +418,6 @@ class TiledCodec:
         d_premaxn = self._buf("premaxn", G * NT)
         d_dec = self._buf("dec", G * NT * c * rh * rw * dt.itemsize)
         d_D = self._buf("D", (K + 1) * NT * 8)
-        d_cut = self._buf("cut", NT * 8)
-        d_lam = self._buf("lambda", N * 8)
         if integer:
             dec = self.codec.decode_device_u16 if dt.itemsize == 2 else self.codec.decode_device_u8
             sse = self.L.spiht_sse_tiles_u16 if dt.itemsize == 2 else self.L.spiht_sse_tiles_u8
@@ -289,9 +430,39 @@ class TiledCodec:
             dec(d_pre.ptr, d_prebytes.ptr, d_premaxn.ptr, g * NT, d_dec.ptr, slot_stride=stride)
             _lib.check(sse(self.ctx.handle, vp(d_tiles.ptr), vp(d_dec.ptr), g, N, c, self.H, self.W, self.th, self.tw, rh, rw,
                            vp(d_D.ptr + 8 * k0 * NT)))
-        _lib.check(self.L.spiht_tile_allocate(self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if integer else 0, K, N, self.T,
-                                              int(self.max_bits) // 8, vp(d_cut.ptr), vp(d_lam.ptr)))
-        return d_cut
+        return d_D
+
+    def encode_layered_device(self, d_img, N, layers, d_packed, d_cum, d_max_n, d_pic_bytes, strides=None):
+        """encode_device in Q quality layers (allocate="rd" codecs; layers: alloc.layer_budgets(max_bits, layers)).  d_img, N,
+        d_max_n, strides: as encode_device.  -> d_packed: picture n's layers behind picture n - 1's, inside a picture layer by
+        layer and tile by tile (N * T * codec.slot_stride bytes always suffice; nothing is written past the array); d_cum: uint32
+        [N][Q][T], the bytes of every tile through every layer; d_pic_bytes: uint64 [N], the pictures' lengths in d_packed.
+        What encode_device queues up to the table of distortions, then Q spiht_tile_allocate on that one table -- the cuts
+        stay in the buffers "cuts" (bits, uint64 [Q][N * T]) and "lambdas" ([Q][N]) -- then one spiht_layer_pack.  No host
+        wait anywhere.  The last layer's cut is encode_device's.  Returns Q."""
+        if self.allocate is None:
+            raise ValueError('encode_layered: the codec was not built with allocate="rd"')
+        budgets = alloc.layer_budgets(self.max_bits, layers)
+        N, Q, vp = int(N), len(budgets), C.c_void_p
+        dt, d_tiles, d_slots, d_nbits = self._encode_slots(d_img, N, d_max_n, strides, "encode_layered_device")
+        NT = N * self.T
+        d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n)
+        d_cuts = self._buf("cuts", Q * NT * 8)
+        d_lams = self._buf("lambdas", Q * N * 8)
+        for q, bits in enumerate(budgets):
+            _lib.check(self.L.spiht_tile_allocate(self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, self.points,
+                                                  N, self.T, bits // 8, vp(d_cuts.ptr + 8 * q * NT), vp(d_lams.ptr + 8 * q * N)))
+        _lib.check(self.L.spiht_layer_pack(self.ctx.handle, vp(d_slots.ptr), self.codec.slot_stride, vp(d_cuts.ptr), Q, N, self.T,
+                                           vp(_ptr(d_packed)), int(d_packed.nbytes), vp(_ptr(d_cum)), vp(_ptr(d_pic_bytes))))
+        return Q
+
+    def _sub_window(self, sub, window):
+        i0, i1, j0, j1 = [int(v) for v in sub]
+        y0, x0, h, w = [int(v) for v in window]
+        need = window_tiles(self.H, self.W, self.th, self.tw, y0, x0, h, w)
+        if not (0 <= i0 <= need[0] and need[1] <= i1 <= self.gy and 0 <= j0 <= need[2] and need[3] <= j1 <= self.gx):
+            raise ValueError("the sub-grid %s does not hold the tiles %s of the window %s" % ((i0, i1, j0, j1), need, (y0, x0, h, w)))
+        return (i0, i1, j0, j1), (y0, x0, h, w)
 
     def decode_window_device(self, d_packed, packed_bytes, d_lens, d_max_n, sub, window, d_out, strides=None, slot_stride=None):
         """d_packed / d_lens / d_max_n: the streams, lengths (uint32) and start planes (uint8) of the tiles of the sub-grid
@@ -303,19 +474,20 @@ class TiledCodec:
         Streams of an allocate="rd" encoder: a tile may be longer than the bound of an equal-split codec, and
         spiht_tile_unpack takes a length as at most slot_stride -- the tile would be cut short.  Pass slot_stride >= the longest
         length of d_lens (the host forms size the slots by the longest stream already)."""
-        i0, i1, j0, j1 = [int(v) for v in sub]
-        y0, x0, h, w = [int(v) for v in window]
-        need = window_tiles(self.H, self.W, self.th, self.tw, y0, x0, h, w)
-        if not (0 <= i0 <= need[0] and need[1] <= i1 <= self.gy and 0 <= j0 <= need[2] and need[3] <= j1 <= self.gx):
-            raise ValueError("the sub-grid %s does not hold the tiles %s of the window %s" % ((i0, i1, j0, j1), need, (y0, x0, h, w)))
+        (i0, i1, j0, j1), (y0, x0, h, w) = self._sub_window(sub, window)
         n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
-        dt = np.dtype(d_out.dtype)
         stride = self.codec.slot_stride if slot_stride is None else int(slot_stride)
         d_slots = self._buf("slots", n * stride)
         d_nbytes = self._buf("nbytes", n * 8)
         _lib.check(self.L.spiht_tile_unpack(self.ctx.handle, vp(_ptr(d_packed)), int(packed_bytes), vp(_ptr(d_lens)), n,
                                             vp(d_slots.ptr), stride, vp(d_nbytes.ptr)))
-        max_n = _ptr(d_max_n)
+        self._decode_slots(d_slots, d_nbytes, _ptr(d_max_n), stride, (i0, i1, j0, j1), (y0, x0, h, w), d_out, strides)
+
+    def _decode_slots(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides):
+        """the zero-padded slots of the sub-grid's tiles -> the window: one batched decode, one paste"""
+        (i0, i1, j0, j1), (y0, x0, h, w) = sub, window
+        n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
+        dt = np.dtype(d_out.dtype)
         grid_args = (self.H, self.W, self.th, self.tw, i0, i1, j0, j1, y0, x0, h, w)
         if dt.kind == "u":
             st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
@@ -339,36 +511,29 @@ class TiledCodec:
         self.decode_window_device(d_packed, packed_bytes, d_lens, d_max_n, (0, self.gy, 0, self.gx), (0, 0, self.H, self.W), d_out,
                                   strides, slot_stride)
 
+    def decode_layers_device(self, d_layers, layers_bytes, d_cum, d_max_n, Q, upto, sub, window, d_out, strides=None,
+                             slot_stride=None, d_sel=None):
+        """decode_window_device of a layered run.  d_layers / layers_bytes: the layers, or a prefix of them, that the table
+        d_cum (uint32 [Q][n]) describes: those of the n tiles of the sub-grid in row-major order.  With d_sel (int32 [n]) the
+        run and the table ([Q][T]) are the whole picture's and d_sel names the sub-grid's tiles in it.  d_max_n: uint8 [n], the
+        start planes of the sub-grid's tiles.  The layers 0 .. upto - 1 are decoded.  sub, window, d_out, strides: as
+        decode_window_device; slot_stride: a multiple of 4 no tile is longer than through layer upto - 1 (None: the codec's
+        bound; the host forms size the slots by the longest gathered tile).
+        One layer-unpack, one batched decode, one paste, queued on the codec's context."""
+        sub, window = self._sub_window(sub, window)
+        n, vp = (sub[1] - sub[0]) * (sub[3] - sub[2]), C.c_void_p
+        stride = self.codec.slot_stride if slot_stride is None else int(slot_stride)
+        d_slots = self._buf("slots", n * stride)
+        d_nbytes = self._buf("nbytes", n * 8)
+        _lib.check(self.L.spiht_layer_unpack(self.ctx.handle, vp(_ptr(d_layers)), int(layers_bytes), vp(_ptr(d_cum)), int(Q),
+                                             n if d_sel is None else self.T, int(upto), None if d_sel is None else vp(_ptr(d_sel)), n,
+                                             vp(d_slots.ptr), stride, vp(d_nbytes.ptr)))
+        self._decode_slots(d_slots, d_nbytes, _ptr(d_max_n), stride, sub, window, d_out, strides)
+
     # ---- host forms ----------------------------------------------------------------------------------
     def _encode_host(self, images, dtype, channels_last, name):
-        images = np.asarray(images)
-        single = images.ndim == 3
-        if single:
-            images = images[None]
-        if images.ndim != 4:
-            raise ValueError("%s takes a picture [c, H, W] or pictures [N, c, H, W]" % name)
-        dtype = np.dtype(dtype)
-        strides = None
-        if dtype.kind == "u":
-            if not _is_dtype(images, dtype):
-                raise ValueError("%s takes a %s array, not %s" % (name, dtype.name, images.dtype))
-            images = np.ascontiguousarray(images, dtype=dtype.newbyteorder("="))
-            if channels_last:
-                N, H, W, c = images.shape
-                es = dtype.itemsize
-                strides = (H * W * c * es, es, W * c * es, c * es)
-                shape = (N, c, H, W)
-            else:
-                shape = images.shape
-        else:
-            images = np.ascontiguousarray(images, dtype=dtype)
-            shape = images.shape
-        if tuple(shape[1:]) != (self.c, self.H, self.W):
-            raise ValueError("%s: pictures of shape %s, the codec's are %s" % (name, tuple(shape[1:]), (self.c, self.H, self.W)))
-        N, NT = shape[0], shape[0] * self.T
-        d_img = self._buf("img", images.nbytes)
-        d_img_view = _View(d_img.ptr, dtype)
-        self.ctx.upload(d_img.ptr, images)
+        single, N, d_img_view, strides = self._upload_pictures(images, dtype, channels_last, name)
+        NT = N * self.T
         d_packed = self._buf("packed", NT * self.codec.slot_stride)
         d_lens = self._buf("lens", NT * 4)
         d_maxn = self._buf("maxn", NT)
@@ -407,6 +572,84 @@ class TiledCodec:
     def encode_u16(self, image_or_images, channels_last=False):
         """uint16 pictures -> what encode gives for pictures / 65535.0"""
         return self._encode_host(image_or_images, np.uint16, channels_last, "encode_u16")
+
+    def _upload_pictures(self, images, dtype, channels_last, name):
+        """the host checks of _encode_host and the upload -> (single, N, the device view, strides)"""
+        images = np.asarray(images)
+        single = images.ndim == 3
+        if single:
+            images = images[None]
+        if images.ndim != 4:
+            raise ValueError("%s takes a picture [c, H, W] or pictures [N, c, H, W]" % name)
+        dtype = np.dtype(dtype)
+        strides = None
+        if dtype.kind == "u":
+            if not _is_dtype(images, dtype):
+                raise ValueError("%s takes a %s array, not %s" % (name, dtype.name, images.dtype))
+            images = np.ascontiguousarray(images, dtype=dtype.newbyteorder("="))
+            if channels_last:
+                N, H, W, c = images.shape
+                es = dtype.itemsize
+                strides = (H * W * c * es, es, W * c * es, c * es)
+                shape = (N, c, H, W)
+            else:
+                shape = images.shape
+        else:
+            images = np.ascontiguousarray(images, dtype=dtype)
+            shape = images.shape
+        if tuple(shape[1:]) != (self.c, self.H, self.W):
+            raise ValueError("%s: pictures of shape %s, the codec's are %s" % (name, tuple(shape[1:]), (self.c, self.H, self.W)))
+        d_img = self._buf("img", images.nbytes)
+        self.ctx.upload(d_img.ptr, images)
+        return single, shape[0], _View(d_img.ptr, dtype), strides
+
+    def _encode_layered_host(self, images, layers, dtype, channels_last, name):
+        if self.allocate is None:
+            raise ValueError('%s: the codec was not built with allocate="rd"' % name)
+        Q = len(alloc.layer_budgets(self.max_bits, layers))
+        single, N, d_img, strides = self._upload_pictures(images, dtype, channels_last, name)
+        T, NT = self.T, N * self.T
+        d_packed = self._buf("packed", NT * self.codec.slot_stride)
+        d_cum = self._buf("cum", N * Q * T * 4)
+        d_maxn = self._buf("maxn", NT)
+        d_pic = self._buf("picbytes", N * 8)
+        self.encode_layered_device(d_img, N, layers, d_packed, d_cum, d_maxn, d_pic, strides)
+        self.ctx.synchronize()
+        cum = np.empty((N, Q, T), dtype=np.uint32)
+        maxn = np.empty(NT, dtype=np.uint8)
+        pic = np.empty(N, dtype=np.uint64)
+        lam = np.empty((Q, N), dtype=np.float64)
+        self.ctx.download(cum, d_cum.ptr)     # the tables: one download each
+        self.ctx.download(maxn, d_maxn.ptr)
+        self.ctx.download(pic, d_pic.ptr)
+        self.ctx.download(lam, self._bufs["lambdas"].ptr)
+        off = np.concatenate(([0], np.cumsum(pic.astype(np.int64))))
+        run = np.empty(int(off[-1]), dtype=np.uint8)
+        if run.size:
+            self.ctx.download(run, d_packed.ptr)  # the layers of all pictures: one download
+        out, cuts = [], []
+        for n in range(N):
+            rows = [[int(v) for v in row] for row in cum[n]]
+            cuts.append([TileAllocation(float(lam[q, n]), rows[q]) for q in range(Q)])
+            out.append(LayeredResult(self.H, self.W, self.c, self.th, self.tw, self.level, [int(v) for v in maxn[n * T:(n + 1) * T]],
+                                     rows, run[int(off[n]):int(off[n + 1])].tobytes()))
+        self.last_allocation = cuts[0] if single else cuts
+        return out[0] if single else out
+
+    def encode_layered(self, image_or_images, layers):
+        """encode in quality layers (a codec built with allocate="rd"; otherwise ValueError).  layers: an int Q or the layers'
+        bit budgets, the last one max_bits (alloc.layer_budgets).  -> LayeredResult, or a list for [N, c, H, W];
+        result.tiled() is what encode gives.  last_allocation: a list of Q TileAllocation, one per layer (a list of such lists
+        for several pictures)."""
+        return self._encode_layered_host(image_or_images, layers, self.pixel_dtype, False, "encode_layered")
+
+    def encode_layered_u8(self, image_or_images, layers, channels_last=False):
+        """encode_layered of uint8 pictures, as encode_u8"""
+        return self._encode_layered_host(image_or_images, layers, np.uint8, channels_last, "encode_layered_u8")
+
+    def encode_layered_u16(self, image_or_images, layers, channels_last=False):
+        """encode_layered of uint16 pictures, as encode_u16"""
+        return self._encode_layered_host(image_or_images, layers, np.uint16, channels_last, "encode_layered_u16")
 
     def tile_curves(self, image, dtype=None):
         """The curves allocate="rd" cuts by, of one picture [c, H, W] (dtype None: the codec's float pixels; np.uint8 /
@@ -470,6 +713,71 @@ class TiledCodec:
         out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w), dtype)
         self.ctx.download(out, d_out.ptr)
         return out
+
+    def _decode_layered_host(self, result, window, upto, dtype, channels_last):
+        _check_version(result)
+        if (result.h, result.w, result.c, result.th, result.tw) != (self.H, self.W, self.c, self.th, self.tw) \
+                or len(result.max_n) != self.T:
+            raise ValueError("a result of geometry %s, the codec's is %s" % ((result.h, result.w, result.c, result.th, result.tw),
+                                                                            (self.H, self.W, self.c, self.th, self.tw)))
+        cum, lens, off = result._table()
+        upto = _upto_arg(upto, cum.shape[0])
+        y0, x0, h, w = [int(v) for v in window]
+        i0, i1, j0, j1 = sub = window_tiles(self.H, self.W, self.th, self.tw, y0, x0, h, w)
+        dtype = np.dtype(dtype)
+        # the table, the start planes and the pieces of the sub-grid's tiles in the layers below upto -- per layer a row of the
+        # sub-grid is contiguous in the file: one upload
+        ts = [i * self.gx + j for i in range(i0, i1) for j in range(j0, j1)]
+        n = len(ts)
+        sub_cum = np.ascontiguousarray(cum[:upto, ts], dtype=np.uint32)
+        nb = int(sub_cum[-1].sum(dtype=np.int64))
+        head = 4 * upto * n + ((n + 3) & ~3)
+        blob = np.zeros(head + max(nb, 1), dtype=np.uint8)
+        blob[:4 * upto * n] = sub_cum.reshape(-1).view(np.uint8)
+        blob[4 * upto * n:4 * upto * n + n] = np.asarray([result.max_n[t] for t in ts], dtype=np.uint8)
+        data = np.frombuffer(result.encoded_bytes, dtype=np.uint8)
+        p = head
+        for q in range(upto):
+            for i in range(i0, i1):
+                a = int(off[q, i * self.gx + j0])
+                b = int(off[q, i * self.gx + j1 - 1] + lens[q, i * self.gx + j1 - 1])
+                blob[p:p + b - a] = data[a:b]
+                p += b - a
+        d_in = self._buf("in", blob.nbytes)
+        self.ctx.upload(d_in.ptr, blob)
+        es = dtype.itemsize
+        strides = (es, w * self.c * es, self.c * es) if channels_last else None
+        d_out = self._buf("out", self.c * h * w * es)
+        stride = max(4, (int(sub_cum[-1].max()) + 3) & ~3)
+        self.decode_layers_device(d_in.ptr + head, nb, d_in.ptr, d_in.ptr + 4 * upto * n, upto, upto, sub, (y0, x0, h, w),
+                                  _View(d_out.ptr, dtype), strides, stride)
+        self.ctx.synchronize()
+        out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w), dtype)
+        self.ctx.download(out, d_out.ptr)
+        return out
+
+    def decode_layered(self, result, upto=None):
+        """LayeredResult -> float64 [c, H, W] from its first `upto` layers (None: all): what decode gives for
+        result.tiled(upto), with the tiles' pieces gathered on the device -- one upload, one layer-unpack, one batched decode,
+        one paste.  A prefix of a file (LayeredResult.from_bytes) decodes like any other result."""
+        return self._decode_layered_host(result, (0, 0, self.H, self.W), upto, np.float64, False)
+
+    def decode_layered_u8(self, result, upto=None, channels_last=False):
+        return self._decode_layered_host(result, (0, 0, self.H, self.W), upto, np.uint8, channels_last)
+
+    def decode_layered_u16(self, result, upto=None, channels_last=False):
+        return self._decode_layered_host(result, (0, 0, self.H, self.W), upto, np.uint16, channels_last)
+
+    def decode_layered_window(self, result, y0, x0, h, w, upto=None):
+        """-> float64 [c, h, w] = decode_layered(result, upto)[:, y0:y0 + h, x0:x0 + w]; only the pieces of the tiles that meet
+        the window, of the layers below upto, are uploaded (last_tiles_decoded tells how many tiles)"""
+        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.float64, False)
+
+    def decode_layered_window_u8(self, result, y0, x0, h, w, upto=None, channels_last=False):
+        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.uint8, channels_last)
+
+    def decode_layered_window_u16(self, result, y0, x0, h, w, upto=None, channels_last=False):
+        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.uint16, channels_last)
 
     def decode(self, result):
         """TiledResult -> float64 [c, H, W]: one upload, one unpack, one batched decode of all T tiles, one paste.  Unlike
@@ -590,3 +898,62 @@ def decode_image_window_u8(result, spiht_settings, y0, x0, h, w, channels_last=F
 
 def decode_image_window_u16(result, spiht_settings, y0, x0, h, w, channels_last=False):
     return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint16, channels_last)
+
+
+def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype, channels_last, name, points, spread):
+    if not isinstance(image, np.ndarray) or image.ndim != 3:
+        raise ValueError('image ndim must be 3: c,h,w')
+    c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
+    codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, np.float64, "rd", points, spread)
+    return codec._encode_layered_host(image, layers, codec.pixel_dtype if dtype is None else dtype, channels_last, name)
+
+
+def encode_image_layered(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=1, points=alloc.POINTS,
+                         spread=alloc.SPREAD):
+    """encode_image_tiled(..., allocate="rd") of a float64 picture (c, h, w) in quality layers -> LayeredResult.  layers: an
+    int Q or the layers' bit budgets, the last one max_bits (alloc.layer_budgets); result.tiled() is the TiledResult of
+    encode_image_tiled, and any prefix of result.to_bytes() that holds the tables is a picture."""
+    return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, None, False, "encode_image_layered", points, spread)
+
+
+def encode_image_layered_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=1, points=alloc.POINTS,
+                            spread=alloc.SPREAD, channels_last=False):
+    return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, np.uint8, channels_last, "encode_image_layered_u8",
+                           points, spread)
+
+
+def encode_image_layered_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=1, points=alloc.POINTS,
+                             spread=alloc.SPREAD, channels_last=False):
+    return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, np.uint16, channels_last, "encode_image_layered_u16",
+                           points, spread)
+
+
+def _decode_layered(result, spiht_settings, window, upto, dtype, channels_last):
+    codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None)
+    return codec._decode_layered_host(result, (0, 0, result.h, result.w) if window is None else window, upto, dtype, channels_last)
+
+
+def decode_image_layered(result, spiht_settings, upto=None):
+    """LayeredResult -> float64 (c, h, w) from its first `upto` layers (None: all), cropped as decode_image_tiled"""
+    return _decode_layered(result, spiht_settings, None, upto, np.float64, False)
+
+
+def decode_image_layered_u8(result, spiht_settings, upto=None, channels_last=False):
+    return _decode_layered(result, spiht_settings, None, upto, np.uint8, channels_last)
+
+
+def decode_image_layered_u16(result, spiht_settings, upto=None, channels_last=False):
+    return _decode_layered(result, spiht_settings, None, upto, np.uint16, channels_last)
+
+
+def decode_image_layered_window(result, spiht_settings, y0, x0, h, w, upto=None):
+    """the window of the picture from its first `upto` layers, decoding only the tiles it meets"""
+    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.float64, False)
+
+
+def decode_image_layered_window_u8(result, spiht_settings, y0, x0, h, w, upto=None, channels_last=False):
+    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.uint8, channels_last)
+
+
+def decode_image_layered_window_u16(result, spiht_settings, y0, x0, h, w, upto=None, channels_last=False):
+    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.uint16, channels_last)
