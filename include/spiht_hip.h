@@ -627,6 +627,39 @@ int spiht_tile_unpack(spiht_ctx *ctx, const uint8_t *d_packed, uint64_t packed_b
                       uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes);
 
 /* ---------------------------------------------------------------------------------------
+ * Tiled pictures at reduced resolution: the tiles decoded by spiht_decode_image_reduced_batch_* at 1/2^reduce size, assembled
+ * into the picture at 1/2^reduce size.  reduce = k is allowed when 0 <= k <= L (the tile codec's levels) and 2^k divides th
+ * and tw, so that the seams between tiles fall on whole reduced samples.  With thk = th >> k, twk = tw >> k,
+ * Hk = ceil(H / 2^k), Wk = ceil(W / 2^k), sample (Y, X) of the reduced picture [c, Hk, Wk] is sample
+ * (off_y + Y - i thk, off_x + X - j twk) of the reduced decode of tile (i, j) = (Y / thk, X / twk): that decode's centred
+ * window (spiht_reduced_shape of a th x tw picture; in_h x in_w = thk x twk).  Additions only: the ABI version stays at 2.
+ *   spiht_tile_reduced_grid  the geometry, pure arithmetic, no device: level_used = L; thk, twk, Hk, Wk; gy, gx (the grid of
+ *                      the full picture, which is the reduced one's); rec_h x rec_w, the float64 reduced tile, pic_h x pic_w,
+ *                      the 8- / 16-bit one; off_y, off_x, the origin of the tile's own samples in either.  level: -1 for the
+ *                      default of a th x tw picture.  Every output pointer may be NULL.  SPIHT_ERR_ARG for what
+ *                      spiht_tile_grid or spiht_reduced_shape refuse and for a tile side that 2^reduce does not divide.
+ *   spiht_tile_mosaic_*  spiht_tile_paste_* with a source origin, for tiles of any side >= 1.  d_tiles: dense
+ *                      [(i1-i0) * (j1-j0), c, rh, rw], the tiles of the sub-grid in row-major order; tile (i, j) gives its
+ *                      samples [oy, oy + th) x [ox, ox + tw): oy, ox >= 0, rh >= oy + th, rw >= ox + tw.  H, W, th, tw are
+ *                      the sizes of the picture and the tile BEING ASSEMBLED (the reduced ones: Hk, Wk, thk, twk), th, tw >= 1.
+ *                      The rules for the window (y0, x0, wh, ww), the sub-grid and the output view (out_strides) are
+ *                      spiht_tile_paste_*'s; asynchronous on the context's stream; argument errors are returned before anything
+ *                      is queued; no byte outside the stated output is written.  With oy = ox = 0 and th, tw >= 8 the output
+ *                      is spiht_tile_paste_*'s. */
+int spiht_tile_reduced_grid(int64_t H, int64_t W, int64_t th, int64_t tw, int wavelet, int mode, int level, int reduce,
+                            int *level_used, int64_t *thk, int64_t *twk, int64_t *Hk, int64_t *Wk, int64_t *gy, int64_t *gx,
+                            int64_t *rec_h, int64_t *rec_w, int64_t *pic_h, int64_t *pic_w, int64_t *off_y, int64_t *off_x);
+int spiht_tile_mosaic_u8(spiht_ctx *ctx, const uint8_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy, int64_t ox,
+                         int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                         int64_t x0, int64_t wh, int64_t ww, uint8_t *d_out, const int64_t *out_strides);
+int spiht_tile_mosaic_u16(spiht_ctx *ctx, const uint16_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy, int64_t ox,
+                          int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                          int64_t x0, int64_t wh, int64_t ww, uint16_t *d_out, const int64_t *out_strides);
+int spiht_tile_mosaic_f64(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy, int64_t ox,
+                          int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                          int64_t x0, int64_t wh, int64_t ww, double *d_out);
+
+/* ---------------------------------------------------------------------------------------
  * Rate allocation across the tiles of a picture (csrc/alloc.hip; the rule is spiht_amd/alloc.py).  The tiles are coded past
  * their share of the budget; K prefixes of every tile's stream are decoded and measured; every tile is cut where one more
  * byte buys the same drop in distortion, and spiht_tile_pack takes the cut lengths.  Additions only: the ABI version stays

@@ -37,4 +37,6 @@ globals().update({_k: getattr(_impl, _k) for _k in ("LayeredResult", "encode_ima
                                                     "encode_image_layered_u16", "decode_image_layered", "decode_image_layered_u8",
                                                     "decode_image_layered_u16", "decode_image_layered_window",
                                                     "decode_image_layered_window_u8", "decode_image_layered_window_u16")})
+# ... tiled pictures at reduced resolution: the sizes of decode*(..., reduce=k)
+globals().update({_k: getattr(_impl, _k) for _k in ("tiled_reduced_shape",)})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

@@ -14,7 +14,7 @@ from .spiht_wrapper import (encode_image, decode_image, EncodingResult, SpihtSet
 from .spiht import encode, decode  # noqa: E402,F401
 from .rd import (RDCurve, rd_curve, rd_curve_u8, rd_curve_u16, cut_to_psnr, cut_to_psnr_u8,  # noqa: E402,F401
                  cut_to_psnr_u16)
-from .tiles import (TiledCodec, TiledResult, TileCurves, TileAllocation, tile_grid, window_tiles,  # noqa: E402,F401
+from .tiles import (TiledCodec, TiledResult, TileCurves, TileAllocation, tile_grid, window_tiles, tiled_reduced_shape,  # noqa: E402,F401
                     encode_image_tiled, encode_image_tiled_u8, encode_image_tiled_u16, decode_image_tiled, decode_image_tiled_u8, decode_image_tiled_u16,
                     decode_image_window, decode_image_window_u8, decode_image_window_u16,
                     LayeredResult, encode_image_layered, encode_image_layered_u8, encode_image_layered_u16, decode_image_layered,

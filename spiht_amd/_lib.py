@@ -65,6 +65,7 @@ SYMBOLS = [
     "spiht_tile_grid", "spiht_tile_cut_u8", "spiht_tile_cut_u16", "spiht_tile_cut_f32", "spiht_tile_cut_f64",
     "spiht_tile_paste_u8", "spiht_tile_paste_u16", "spiht_tile_paste_f32", "spiht_tile_paste_f64",
     "spiht_tile_pack", "spiht_tile_unpack",
+    "spiht_tile_reduced_grid", "spiht_tile_mosaic_u8", "spiht_tile_mosaic_u16", "spiht_tile_mosaic_f64",
     "spiht_tile_prefix_slots", "spiht_sse_tiles_f64", "spiht_sse_tiles_u8", "spiht_sse_tiles_u16", "spiht_tile_allocate",
     "spiht_layer_pack", "spiht_layer_unpack",
 ]
@@ -220,6 +221,10 @@ def lib():
         L.spiht_tile_paste_f32.argtypes = L.spiht_tile_paste_f64.argtypes = [vp, vp] + [i64] * 15 + [vp]
         L.spiht_tile_pack.argtypes = [vp, vp, u64, vp, i64, vp, u64, vp]
         L.spiht_tile_unpack.argtypes = [vp, vp, u64, vp, i64, vp, u64, vp]
+        # ... at reduced resolution: the geometry, and the paste with a source origin
+        L.spiht_tile_reduced_grid.argtypes = [i64, i64, i64, i64, i32, i32, i32, i32, C.POINTER(i32)] + [C.POINTER(i64)] * 12
+        L.spiht_tile_mosaic_u8.argtypes = [vp, vp] + [i64] * 17 + [vp, vp]
+        L.spiht_tile_mosaic_f64.argtypes = [vp, vp] + [i64] * 17 + [vp]
         # rate allocation across tiles: prefixes of the tiles' streams, their error sums, the cut
         L.spiht_tile_prefix_slots.argtypes = [vp, vp, u64, vp, i64, i64, i64, i64, vp, u64, vp, vp, vp]
         L.spiht_sse_tiles_f64.argtypes = L.spiht_sse_tiles_u8.argtypes = [vp, vp, vp] + [i64] * 9 + [vp]

@@ -62,6 +62,7 @@ int spiht_launch_sse_f64(const double *d_pic, const double *d_dec, int K, int c,
 int spiht_launch_sse_px(const PxView *px, const void *d_dec, int K, uint64_t *part, uint64_t *d_out, hipStream_t st);
 int spiht_launch_tile_cut(const TileCutArgs *a, int es, int64_t NT, hipStream_t st);
 int spiht_launch_tile_paste(const TilePasteArgs *a, int es, int64_t ntiles, hipStream_t st);
+int spiht_launch_tile_mosaic(const TileMosaicArgs *a, int es, hipStream_t st);
 int spiht_launch_tile_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbytes, int64_t T, uint64_t *d_off,
                            uint8_t *d_packed, uint64_t cap, uint32_t *d_lens, hipStream_t st);
 int spiht_launch_tile_unpack(const uint8_t *d_packed, uint64_t packed_bytes, const uint32_t *d_lens, int64_t T, uint64_t *d_off,
@@ -2482,6 +2483,86 @@ extern "C" int spiht_tile_paste_f64(spiht_ctx *ctx, const double *d_tiles, int64
                                     int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
                                     int64_t wh, int64_t ww, double *d_out) {
     return tile_paste(ctx, d_tiles, dense_pic(d_out, PIC_F64, true), 8, c, rh, rw, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww);
+}
+
+// tiled pictures at reduced resolution: the geometry (no device) and the assembly of reduced tiles (k_tile_mosaic)
+extern "C" int spiht_tile_reduced_grid(int64_t H, int64_t W, int64_t th, int64_t tw, int wavelet, int mode, int level, int reduce,
+                                       int *level_used, int64_t *thk, int64_t *twk, int64_t *Hk, int64_t *Wk, int64_t *gy,
+                                       int64_t *gx, int64_t *rec_h, int64_t *rec_w, int64_t *pic_h, int64_t *pic_w,
+                                       int64_t *off_y, int64_t *off_x) {
+    int64_t ty, tx;
+    CHK(spiht_tile_grid(H, W, th, tw, &ty, &tx));
+    // the reduced decode of one tile: refuses a reduce outside 0 .. L
+    CHK(spiht_reduced_shape(th, tw, wavelet, mode, level, reduce, level_used, rec_h, rec_w, pic_h, pic_w, off_y, off_x, nullptr,
+                            nullptr));
+    const int64_t m = ((int64_t)1 << reduce) - 1;
+    if ((th & m) || (tw & m)) return SPIHT_ERR_ARG;  // a seam between two reduced samples
+    if (thk) *thk = th >> reduce;
+    if (twk) *twk = tw >> reduce;
+    if (Hk) *Hk = (H + m) >> reduce;
+    if (Wk) *Wk = (W + m) >> reduce;
+    if (gy) *gy = ty;
+    if (gx) *gx = tx;
+    return SPIHT_OK;
+}
+// out: the window (dense_pic of float64, or int_pic's checked view of [c, wh, ww]); H, W, th, tw: the picture and the tile
+// being assembled (the reduced ones)
+static int tile_mosaic(spiht_ctx *ctx, const void *d_tiles, const Pic &out, int es, int64_t c, int64_t rh, int64_t rw, int64_t oy,
+                       int64_t ox, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1,
+                       int64_t y0, int64_t x0, int64_t wh, int64_t ww) {
+    if (!ctx || !d_tiles || !out.p || c < 1 || (uintptr_t)d_tiles % es || (uintptr_t)out.p % es) return SPIHT_ERR_ARG;
+    if (H < 1 || W < 1 || th < 1 || tw < 1 || oy < 0 || ox < 0) return SPIHT_ERR_ARG;
+    if (H >= (1 << 30) || W >= (1 << 30) || th > (1 << 24) || tw > (1 << 24)) return SPIHT_ERR_TOO_LARGE;
+    if (oy > (1 << 24) || ox > (1 << 24) || rh < oy + th || rw < ox + tw || rh > th + (1 << 25) || rw > tw + (1 << 25))
+        return SPIHT_ERR_ARG;
+    const int64_t gy = (H + th - 1) / th, gx = (W + tw - 1) / tw;
+    if (i0 < 0 || i1 <= i0 || i1 > gy || j0 < 0 || j1 <= j0 || j1 > gx) return SPIHT_ERR_ARG;
+    // the window lies in the picture, and the sub-grid holds every tile it meets
+    if (y0 < 0 || x0 < 0 || wh < 1 || ww < 1 || y0 + wh > H || x0 + ww > W) return SPIHT_ERR_ARG;
+    if (y0 / th < i0 || (y0 + wh - 1) / th >= i1 || x0 / tw < j0 || (x0 + ww - 1) / tw >= j1) return SPIHT_ERR_ARG;
+    if (c > 65535 || (__int128)(i1 - i0) * (j1 - j0) > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    TileMosaicArgs a;
+    a.tiles = (const uint8_t *)d_tiles;
+    a.out = (uint8_t *)out.p;
+    if (out.integer()) {
+        a.sc = out.px.sc; a.sh = out.px.sh; a.sw = out.px.sw;
+    } else {
+        a.sw = es; a.sh = ww * es; a.sc = wh * a.sh;
+    }
+    a.c = (int32_t)c; a.rh = (int32_t)rh; a.rw = (int32_t)rw; a.oy = (int32_t)oy; a.ox = (int32_t)ox;
+    a.th = (int32_t)th; a.tw = (int32_t)tw; a.i0 = (int32_t)i0; a.j0 = (int32_t)j0; a.nj = (int32_t)(j1 - j0);
+    a.y0 = (int32_t)y0; a.x0 = (int32_t)x0; a.wh = (int32_t)wh; a.ww = (int32_t)ww; a.rows = 0;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    LAUNCHCHK(spiht_launch_tile_mosaic(&a, es, ctx->stream));
+    return SPIHT_OK;
+}
+static int tile_mosaic_px(int es, spiht_ctx *ctx, const void *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy, int64_t ox,
+                          int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                          int64_t x0, int64_t wh, int64_t ww, void *d_out, const int64_t *out_strides) {
+    if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
+    Pic pic;
+    CHK(int_pic(d_out, es, true, out_strides, 3, 1, c, wh, ww, &pic));
+    return tile_mosaic(ctx, d_tiles, pic, es, c, rh, rw, oy, ox, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww);
+}
+extern "C" int spiht_tile_mosaic_u8(spiht_ctx *ctx, const uint8_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy,
+                                    int64_t ox, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0,
+                                    int64_t j1, int64_t y0, int64_t x0, int64_t wh, int64_t ww, uint8_t *d_out,
+                                    const int64_t *out_strides) {
+    return tile_mosaic_px(1, ctx, d_tiles, c, rh, rw, oy, ox, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww, d_out, out_strides);
+}
+extern "C" int spiht_tile_mosaic_u16(spiht_ctx *ctx, const uint16_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy,
+                                     int64_t ox, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0,
+                                     int64_t j1, int64_t y0, int64_t x0, int64_t wh, int64_t ww, uint16_t *d_out,
+                                     const int64_t *out_strides) {
+    return tile_mosaic_px(2, ctx, d_tiles, c, rh, rw, oy, ox, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww, d_out, out_strides);
+}
+extern "C" int spiht_tile_mosaic_f64(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy,
+                                     int64_t ox, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0,
+                                     int64_t j1, int64_t y0, int64_t x0, int64_t wh, int64_t ww, double *d_out) {
+    if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
+    return tile_mosaic(ctx, d_tiles, dense_pic(d_out, PIC_F64, true), 8, c, rh, rw, oy, ox, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh,
+                       ww);
 }
 
 // the checks pack and unpack share; the scratch: uint64 [T] byte lengths (pack), uint64 [T] offsets

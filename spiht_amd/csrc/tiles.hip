@@ -2,6 +2,8 @@
 //   k_tile_cut     picture batch [N, c, H, W] -> dense tile batch [N * T, c, th, tw]; samples past the picture's bottom /
 //                  right edge repeat the last row / column (numpy's np.pad(mode="edge"))
 //   k_tile_paste   dense tile batch of a sub-grid -> a window of the picture; every sample from the one tile that owns it
+//   k_tile_mosaic  the paste of reduced tiles: a source origin inside the tile, tile sides down to 1, workgroups that own rows
+//                  of the window and gather across the tiles
 //   k_tile_scan    stream lengths -> their exclusive prefix sums (one workgroup)
 //   k_tile_pack    T stream slots -> one contiguous run of bytes
 //   k_tile_unpack  the run -> T zero-padded slots
@@ -93,6 +95,79 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_paste(const TilePasteArgs a
     for (int Y = ya + (int)threadIdx.y; Y < yb; Y += (int)blockDim.y)
         copy_row<ES>(dst0 + (int64_t)(Y - a.y0) * a.sh, a.sw, src0 + (size_t)(Y - i * a.th) * a.rw * ES, ES, n, n, (int)threadIdx.x,
                      (int)blockDim.x);
+}
+
+// One row of the mosaic: n elements of ES bytes, element k being picture column x0 + k, taken from the tile that owns it.
+// row: the address of the row's sample of picture column j0 * tw (the first sample the row's first tile of the sub-grid
+// gives); tile j's samples lie (j - j0) * tstep bytes further on.  A 16-byte vector of the destination may span several
+// tiles (8-bit tiles of 2 columns: eight); a vector that lies in one tile and has an aligned source is one 16-byte load,
+// any other is gathered element by element, stepping to the next tile at each seam.  The lanes lane, lane + nlanes, ... of
+// the caller share the row: consecutive lanes store consecutive vectors.
+template <int ES>
+__device__ __forceinline__ void mosaic_row(uint8_t *dst, int64_t ds, const uint8_t *row, int64_t tstep, uint32_t tw, int j0, int x0,
+                                           int n, int lane, int nlanes) {
+    typedef typename ElemOf<ES>::type T;
+    constexpr int EPV = 16 / ES;
+    auto src = [&](int X) {  // picture column X >= 0
+        const uint32_t j = (uint32_t)X / tw, tx = (uint32_t)X - j * tw;
+        return row + (int64_t)((int)j - j0) * tstep + (size_t)tx * ES;
+    };
+    if (ds != ES) {  // a strided destination (HWC, RGBA): what lies between the elements is not written
+        for (int k = lane; k < n; k += nlanes) *reinterpret_cast<T *>(dst + (int64_t)k * ds) = *reinterpret_cast<const T *>(src(x0 + k));
+        return;
+    }
+    const int a = (int)((uintptr_t)dst & 15);
+    const int64_t nbytes = (int64_t)n * ES;
+    const int nvec = (int)((a + nbytes + 15) >> 4);
+    for (int v = lane; v < nvec; v += nlanes) {
+        const int64_t p = 16 * (int64_t)v - a;  // bytes from dst; a multiple of ES, negative in the first vector of an unaligned row
+        const int k0 = (int)(p / ES);
+        if (p >= 0 && p + 16 <= nbytes) {
+            const uint32_t X = (uint32_t)(x0 + k0), j = X / tw;
+            uint32_t tx = X - j * tw;
+            const uint8_t *s = row + (int64_t)((int)j - j0) * tstep + (size_t)tx * ES;
+            uint4 q;
+            if (tx + EPV <= tw && ((uintptr_t)s & 15) == 0) {
+                q = *reinterpret_cast<const uint4 *>(s);
+            } else {
+                T e[EPV];
+#pragma unroll
+                for (int i = 0; i < EPV; i++) {
+                    e[i] = *reinterpret_cast<const T *>(s);
+                    s += ES;
+                    if (++tx == tw) {  // the seam: the same row of the next tile
+                        tx = 0;
+                        s += tstep - (int64_t)tw * ES;
+                    }
+                }
+                __builtin_memcpy(&q, e, 16);
+            }
+            *reinterpret_cast<uint4 *>(dst + p) = q;
+        } else {
+#pragma unroll
+            for (int i = 0; i < EPV; i++) {
+                const int k = k0 + i;
+                if (k >= 0 && k < n) *reinterpret_cast<T *>(dst + (int64_t)k * ES) = *reinterpret_cast<const T *>(src(x0 + k));
+            }
+        }
+    }
+}
+
+// grid (row chunks of the window, c); block (bx, by): bx lanes along a window row, by rows at a time.  Picture-centric: a
+// workgroup's rows cross every tile of the sub-grid's row that the window meets.
+template <int ES>
+__global__ __launch_bounds__(TL_THREADS) void k_tile_mosaic(const TileMosaicArgs a) {
+    const uint32_t ch = blockIdx.y;
+    const size_t plane = (size_t)a.rh * a.rw * ES;
+    const int64_t ya = (int64_t)blockIdx.x * a.rows;
+    const int yb = (int)min(ya + a.rows, (int64_t)a.wh);
+    for (int y = (int)ya + (int)threadIdx.y; y < yb; y += (int)blockDim.y) {
+        const int Y = a.y0 + y, i = Y / a.th;
+        const uint8_t *row = a.tiles + ((size_t)(i - a.i0) * a.nj * a.c + ch) * plane
+                             + ((size_t)(Y - i * a.th + a.oy) * a.rw + a.ox) * ES;
+        mosaic_row<ES>(a.out + (int64_t)ch * a.sc + (int64_t)y * a.sh, a.sw, row, (int64_t)((size_t)a.c * plane), (uint32_t)a.tw, a.j0,
+                       a.x0, a.ww, (int)threadIdx.x, (int)blockDim.x);
+    }
 }
 
 // in[T] (each taken as min(in[t], lim)) -> off[t] = the sum of those before t, out[t] = the clipped value in the other
@@ -199,6 +274,29 @@ extern "C" int spiht_launch_tile_paste(const TilePasteArgs *a, int es, int64_t n
     case 2: return launch_paste<2>(*a, ntiles, st);
     case 4: return launch_paste<4>(*a, ntiles, st);
     default: return launch_paste<8>(*a, ntiles, st);
+    }
+}
+
+template <int ES>
+static int launch_mosaic(TileMosaicArgs a, hipStream_t st) {
+    dim3 block;
+    uint32_t gz;
+    const int64_t n = a.ww;  // a workgroup's rows are the window's
+    row_blocks(a.sw == ES ? (n * ES + 15) / 16 + 1 : n, n * ES, a.wh, &block, &a.rows, &gz);
+    // a small (reduced) picture: fewer rows per workgroup, down to one pass of the block, until there are workgroups for
+    // every CU a few times over
+    while ((int64_t)gz * a.c < TL_MOSAIC_WGS && a.rows > (int)block.y) {
+        a.rows = std::max<int>((int)block.y, a.rows / 2 / (int)block.y * (int)block.y);
+        gz = (uint32_t)((a.wh + a.rows - 1) / a.rows);
+    }
+    hipLaunchKernelGGL(k_tile_mosaic<ES>, dim3(gz, a.c), block, 0, st, a);
+    return (int)hipGetLastError();
+}
+extern "C" int spiht_launch_tile_mosaic(const TileMosaicArgs *a, int es, hipStream_t st) {
+    switch (es) {
+    case 1: return launch_mosaic<1>(*a, st);
+    case 2: return launch_mosaic<2>(*a, st);
+    default: return launch_mosaic<8>(*a, st);
     }
 }
 

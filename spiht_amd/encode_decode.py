@@ -16,8 +16,9 @@ import numpy as np
 from .spiht_wrapper import (EncodingResult, SpihtSettings, decode_image, decode_image_reduced_u8, encode_image,
                             get_slices_and_h_w)
 from .rd import cut_to_psnr, rd_curve
-from .tiles import (decode_image_layered, decode_image_layered_window, decode_image_tiled, decode_image_window,
-                    encode_image_layered, encode_image_tiled)
+from .tiles import (decode_image_layered, decode_image_layered_u8, decode_image_layered_window, decode_image_layered_window_u8,
+                    decode_image_tiled, decode_image_tiled_u8, decode_image_window, decode_image_window_u8, encode_image_layered,
+                    encode_image_tiled)
 from .utils import imload, imsave, load_encoding, save_encoding
 
 _ARGS = [  # (flag, type, default, help): the reference tool's options, then ours
@@ -35,7 +36,8 @@ _ARGS = [  # (flag, type, default, help): the reference tool's options, then our
     ("--psnr", float, None, "cut the stream to the shortest prefix found that reaches this PSNR in dB (of the float picture)"),
     ("--rd-curve", int, None, "print N rows of the stream's rate-distortion curve: bytes, bpp, PSNR"),
     ("--tile", int, None, "code the picture as tiles of N x N, one stream per tile (the bit budget is shared equally)"),
-    ("--window", str, None, "with --tile: decode only the window Y0,X0,H,W of the picture and save that"),
+    ("--window", str, None, "with --tile: decode only the window Y0,X0,H,W of the picture and save that (with --reduce K: of "
+                            "the picture at 1/2^K size, in its coordinates)"),
     ("--allocate", str, None, "with --tile: 'rd' shares the bit budget between the tiles by their rate-distortion curves"),
     ("--points", int, 16, "with --allocate rd: prefixes measured per tile"),
     ("--layers", str, None, "with --tile N --allocate rd: Q quality layers, or their bit budgets b0,b1,... (the last one the "
@@ -90,12 +92,12 @@ def report_encoding(enc: EncodingResult, settings: SpihtSettings, seconds: Optio
 
 
 def main_tiled(args, picture):
-    """--tile N [--window Y0,X0,H,W]: the picture as tiles of N x N.  The level is a tile's (--level, or the default of an
-    N x N picture); the bit budget of --bpp is shared equally among the tiles, or with --allocate rd [--points K] by their
-    rate-distortion curves."""
+    """--tile N [--window Y0,X0,H,W] [--reduce K]: the picture as tiles of N x N.  The level is a tile's (--level, or the default
+    of an N x N picture); the bit budget of --bpp is shared equally among the tiles, or with --allocate rd [--points K] by
+    their rate-distortion curves.  --reduce K saves the 8-bit picture at 1/2^K size (the window in its coordinates)."""
     c, h, w = picture.shape
-    if args.load or args.save or args.reduce or args.psnr is not None or args.rd_curve is not None:
-        raise SystemExit("--tile goes with --bpp, --level, the settings, --window and --out only")
+    if args.load or args.save or args.psnr is not None or args.rd_curve is not None:
+        raise SystemExit("--tile goes with --bpp, --level, the settings, --window, --reduce and --out only")
     p = plan(args, c, h, w)
     level = default_level(args.tile, args.tile) if args.level is None else args.level
     print("encoding %d x %d x %d at %.3f bpp as tiles of %d x %d" % (c, h, w, args.bpp, args.tile, args.tile))
@@ -104,6 +106,13 @@ def main_tiled(args, picture):
     enc, secs = timed(encode_image_tiled, picture, args.tile, p.settings, level, p.max_bits, args.allocate, args.points)
     gy, gx = enc.grid()
     print("encoded in %.3f s: %d x %d tiles, %.2f KiB" % (secs, gy, gx, len(enc.encoded_bytes) / 1024))
+    if args.reduce:
+        # the 8-bit picture of pyramid level K (no distance: there is no original of that size)
+        if args.window:
+            small, secs = timed(lambda: decode_image_window_u8(enc, p.settings, *_window(args), reduce=args.reduce))
+        else:
+            small, secs = timed(lambda: decode_image_tiled_u8(enc, p.settings, reduce=args.reduce))
+        return enc, save_reduced(args, small, secs)
     if args.window:
         y0, x0, wh, ww = [int(v) for v in args.window.split(",")]
         decoded, secs = timed(decode_image_window, enc, p.settings, y0, x0, wh, ww)
@@ -120,6 +129,18 @@ def main_tiled(args, picture):
     return enc, decoded
 
 
+def _window(args):
+    return [int(v) for v in args.window.split(",")]
+
+
+def save_reduced(args, small, secs):
+    print("decoded %s at 1/%d size in %.3f s: %d x %d" % ("the window" if args.window else "the picture", 2 ** args.reduce, secs,
+                                                          small.shape[1], small.shape[2]))
+    imsave(args.out, small / 255)
+    print("  picture written to", args.out)
+    return small
+
+
 def main_layered(args, picture, p, level):
     """--layers Q | b0,b1,...: the tiled picture in quality layers; the file is cut after every layer and decoded"""
     c, h, w = picture.shape
@@ -130,7 +151,16 @@ def main_layered(args, picture, p, level):
     enc, secs = timed(encode_image_layered, picture, args.tile, p.settings, level, p.max_bits, layers, args.points)
     gy, gx = enc.grid()
     print("encoded in %.3f s: %d x %d tiles, %d layers, %.2f KiB" % (secs, gy, gx, enc.layers, len(enc.to_bytes()) / 1024))
-    window = [int(v) for v in args.window.split(",")] if args.window else None
+    window = _window(args) if args.window else None
+    if args.reduce:
+        # every layer at 1/2^K size; the last one is saved
+        for q, end in enumerate(enc.layer_ends()):
+            if window is None:
+                small, secs = timed(lambda: decode_image_layered_u8(enc, p.settings, q + 1, reduce=args.reduce))
+            else:
+                small, secs = timed(lambda: decode_image_layered_window_u8(enc, p.settings, *window, q + 1, reduce=args.reduce))
+            print("  layer %d, %d file bytes" % (q, end))
+        return enc, save_reduced(args, small, secs)
     ref = picture if window is None else picture[:, window[0]:window[0] + window[2], window[1]:window[1] + window[3]]
     print("  %6s %12s %10s" % ("layer", "file bytes", "PSNR dB"))
     for q, end in enumerate(enc.layer_ends()):

@@ -20,6 +20,11 @@ the cuts nest (alloc.allocate_layers), and the container stores for every tile t
 layer.  The file through layer q is the whole picture at budget q, and any prefix of the file that holds the tables decodes.
 The coder is untouched: two more copies (csrc/layers.hip, spiht_layer_*) put the slots into that order and gather a tile's
 pieces back into a decoder slot.
+
+Reduced resolution (every decode call's reduce=k; tiled_reduced_shape): the tiles are decoded at 1/2^k size by the batched
+reduced decode and assembled into the picture at 1/2^k size by one more copy (k_tile_mosaic, spiht_tile_mosaic_*), which takes
+every sample from the centred window of its tile's reduced decode.  It composes with windows (given in the reduced picture's
+coordinates) and with quality layers.
 """
 import ctypes as C
 import struct
@@ -31,7 +36,7 @@ import numpy as np
 from . import _lib, alloc
 from .batch import BatchCodec, DeviceArray
 from .spiht_wrapper import (ENCODER_DECODER_VERSION, EncodingResult, SpihtSettings, _check_aligned, _check_int_view,
-                            _check_version, _is_dtype)
+                            _check_version, _is_dtype, _wavelet_mode_ids)
 
 MAGIC = b"SPTL"
 CONTAINER_VERSION = 1
@@ -59,12 +64,45 @@ def tile_grid(H, W, th, tw):
 
 def window_tiles(H, W, th, tw, y0, x0, h, w):
     """The sub-grid (i0, i1, j0, j1) of the tiles that meet the window [y0, y0 + h) x [x0, x0 + w): rows i0 <= i < i1,
-    columns j0 <= j < j1.  A window that is empty or leaves the H x W picture: ValueError."""
+    columns j0 <= j < j1.  A window that is empty or leaves the H x W picture: ValueError.  Pure arithmetic; the tile may be
+    a reduced one of any side >= 1 (tiled_reduced_shape: Hk, Wk, thk, twk)."""
+    H, W, th, tw = int(H), int(W), int(th), int(tw)
     y0, x0, h, w = int(y0), int(x0), int(h), int(w)
-    tile_grid(H, W, th, tw)
+    if H < 1 or W < 1 or th < 1 or tw < 1:
+        raise ValueError("a %d x %d picture in tiles of %d x %d" % (H, W, th, tw))
     if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
         raise ValueError("the window (%d, %d, %d, %d) is empty or leaves the %d x %d picture" % (y0, x0, h, w, H, W))
     return y0 // th, (y0 + h - 1) // th + 1, x0 // tw, (x0 + w - 1) // tw + 1
+
+
+_REDUCED_NAMES = ("thk", "twk", "Hk", "Wk", "gy", "gx", "rec_h", "rec_w", "pic_h", "pic_w", "off_y", "off_x")
+
+
+def tiled_reduced_shape(H, W, tile, settings, level, reduce):
+    """Sizes of a tiled picture decoded at 1/2^reduce size (spiht_tile_reduced_grid; no device).  H, W: the picture; tile: an
+    int or (th, tw); level: the tile codec's (None: the default of a th x tw picture).  Returns a dict: level -- the levels L
+    of a tile's stream; thk, twk = th >> reduce, tw >> reduce -- the reduced tile; Hk, Wk = ceil(H / 2^reduce),
+    ceil(W / 2^reduce) -- the reduced picture; gy, gx -- the grid; rec_h, rec_w / pic_h, pic_w -- the float64 / 8- and 16-bit
+    reduced decode of one tile (reduced_shape of a th x tw picture); off_y, off_x -- where the tile's own thk x twk samples lie
+    in either.  ValueError unless 0 <= reduce <= L and 2^reduce divides th and tw; TypeError for a reduce that is no integer."""
+    th, tw = _tile_arg(tile)
+    wid, mid = _wavelet_mode_ids(settings if settings is not None else SpihtSettings())
+    if level is not None and level < 0:
+        raise ValueError("Level value of %d is too low . Minimum level is 0." % level)
+    if isinstance(reduce, bool) or not isinstance(reduce, (int, np.integer)):
+        raise TypeError("reduce must be an integer, not %s" % type(reduce).__name__)
+    if not 0 <= reduce < 64:
+        raise ValueError("reduce = %d" % reduce)
+    tile_grid(H, W, th, tw)  # (its own refusals, in its own words)
+    lv = C.c_int()
+    v = [C.c_int64() for _ in _REDUCED_NAMES]
+    try:
+        _lib.check(_lib.lib().spiht_tile_reduced_grid(int(H), int(W), th, tw, wid, mid, -1 if level is None else int(level),
+                                                      int(reduce), C.byref(lv), *[C.byref(t) for t in v]))
+    except ValueError:
+        raise ValueError("reduce = %d of a %d x %d picture in tiles of %d x %d: 0 <= reduce <= the tile's levels, and 2^reduce "
+                         "divides both tile sides" % (reduce, H, W, th, tw)) from None
+    return dict(level=lv.value, **{k: t.value for k, t in zip(_REDUCED_NAMES, v)})
 
 
 @dataclass
@@ -325,6 +363,7 @@ class TiledCodec:
         self.last_allocation = None  # allocate="rd": the TileAllocation of the last host encode (a list for several pictures)
         self.max_bytes = 2 ** 31     # allocate="rd": device bytes of the prefixes decoded at a time
         self._bufs = {}
+        self._reduced = {}           # reduce -> tiled_reduced_shape
 
     # ---- device scratch, grow-only per name ------------------------------------------------------
     def _buf(self, name, nbytes):
@@ -456,15 +495,27 @@ class TiledCodec:
                                            vp(_ptr(d_packed)), int(d_packed.nbytes), vp(_ptr(d_cum)), vp(_ptr(d_pic_bytes))))
         return Q
 
-    def _sub_window(self, sub, window):
+    def reduced_shape(self, reduce):
+        """tiled_reduced_shape of the codec's pictures: TypeError / ValueError for a reduce the codec does not decode at"""
+        rs = self._reduced.get(reduce) if isinstance(reduce, (int, np.integer)) and not isinstance(reduce, bool) else None
+        if rs is None:  # (a reduce of another type is refused here, before it becomes a key)
+            rs = self._reduced[int(reduce)] = tiled_reduced_shape(self.H, self.W, (self.th, self.tw), self.settings, self.level, reduce)
+        return rs
+
+    def _window_arg(self, window, rs):
+        """None: the whole (reduced) picture"""
+        return (0, 0, rs["Hk"], rs["Wk"]) if window is None else tuple(int(v) for v in window)
+
+    def _sub_window(self, sub, window, rs):
         i0, i1, j0, j1 = [int(v) for v in sub]
         y0, x0, h, w = [int(v) for v in window]
-        need = window_tiles(self.H, self.W, self.th, self.tw, y0, x0, h, w)
+        need = window_tiles(rs["Hk"], rs["Wk"], rs["thk"], rs["twk"], y0, x0, h, w)
         if not (0 <= i0 <= need[0] and need[1] <= i1 <= self.gy and 0 <= j0 <= need[2] and need[3] <= j1 <= self.gx):
             raise ValueError("the sub-grid %s does not hold the tiles %s of the window %s" % ((i0, i1, j0, j1), need, (y0, x0, h, w)))
         return (i0, i1, j0, j1), (y0, x0, h, w)
 
-    def decode_window_device(self, d_packed, packed_bytes, d_lens, d_max_n, sub, window, d_out, strides=None, slot_stride=None):
+    def decode_window_device(self, d_packed, packed_bytes, d_lens, d_max_n, sub, window, d_out, strides=None, slot_stride=None,
+                             reduce=0):
         """d_packed / d_lens / d_max_n: the streams, lengths (uint32) and start planes (uint8) of the tiles of the sub-grid
         sub = (i0, i1, j0, j1) in row-major order -- only those are unpacked and decoded.  window = (y0, x0, h, w) inside the
         picture and inside the sub-grid.  -> d_out: DeviceArray [c, h, w], float64, or uint8 / uint16 laid out by `strides`
@@ -473,21 +524,29 @@ class TiledCodec:
         One unpack, one batched decode, one paste, queued on the codec's context.
         Streams of an allocate="rd" encoder: a tile may be longer than the bound of an equal-split codec, and
         spiht_tile_unpack takes a length as at most slot_stride -- the tile would be cut short.  Pass slot_stride >= the longest
-        length of d_lens (the host forms size the slots by the longest stream already)."""
-        (i0, i1, j0, j1), (y0, x0, h, w) = self._sub_window(sub, window)
+        length of d_lens (the host forms size the slots by the longest stream already).
+        reduce = k > 0 (0 <= k <= the tile's levels, 2^k dividing th and tw; reduced_shape(k) gives the sizes): the picture at
+        1/2^k size, [c, Hk, Wk].  The window is in ITS coordinates and the tiles are those it meets in the thk x twk grid;
+        sample (Y, X) is the reduced decode of its tile (decode_image_reduced*(result.tile(i, j), settings, k, crop=True)).
+        The same unpack, one batched reduced decode, one mosaic (spiht_tile_mosaic_*); reduce = 0 is the paste above."""
+        rs = self.reduced_shape(reduce)
+        (i0, i1, j0, j1), (y0, x0, h, w) = self._sub_window(sub, self._window_arg(window, rs), rs)
         n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
         stride = self.codec.slot_stride if slot_stride is None else int(slot_stride)
         d_slots = self._buf("slots", n * stride)
         d_nbytes = self._buf("nbytes", n * 8)
         _lib.check(self.L.spiht_tile_unpack(self.ctx.handle, vp(_ptr(d_packed)), int(packed_bytes), vp(_ptr(d_lens)), n,
                                             vp(d_slots.ptr), stride, vp(d_nbytes.ptr)))
-        self._decode_slots(d_slots, d_nbytes, _ptr(d_max_n), stride, (i0, i1, j0, j1), (y0, x0, h, w), d_out, strides)
+        self._decode_slots(d_slots, d_nbytes, _ptr(d_max_n), stride, (i0, i1, j0, j1), (y0, x0, h, w), d_out, strides, rs, reduce)
 
-    def _decode_slots(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides):
-        """the zero-padded slots of the sub-grid's tiles -> the window: one batched decode, one paste"""
+    def _decode_slots(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, reduce):
+        """the zero-padded slots of the sub-grid's tiles -> the window: one batched decode, one paste (reduce > 0: one batched
+        reduced decode, one mosaic)"""
         (i0, i1, j0, j1), (y0, x0, h, w) = sub, window
         n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
         dt = np.dtype(d_out.dtype)
+        if reduce:
+            return self._decode_slots_reduced(d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, int(reduce))
         grid_args = (self.H, self.W, self.th, self.tw, i0, i1, j0, j1, y0, x0, h, w)
         if dt.kind == "u":
             st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
@@ -506,21 +565,46 @@ class TiledCodec:
             _lib.check(self.L.spiht_tile_paste_f64(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *grid_args, vp(d_out.ptr)))
         self.last_tiles_decoded = n
 
-    def decode_device(self, d_packed, packed_bytes, d_lens, d_max_n, d_out, strides=None, slot_stride=None):
-        """decode_window_device of the whole picture: all T tiles -> d_out [c, H, W]"""
-        self.decode_window_device(d_packed, packed_bytes, d_lens, d_max_n, (0, self.gy, 0, self.gx), (0, 0, self.H, self.W), d_out,
-                                  strides, slot_stride)
+    def _decode_slots_reduced(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, k):
+        (i0, i1, j0, j1), (y0, x0, h, w) = sub, window
+        n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
+        dt = np.dtype(d_out.dtype)
+        grid_args = (rs["off_y"], rs["off_x"], rs["Hk"], rs["Wk"], rs["thk"], rs["twk"], i0, i1, j0, j1, y0, x0, h, w)
+        if dt.kind == "u":
+            st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
+            _check_aligned(d_out.ptr, dt)
+            rh, rw = rs["pic_h"], rs["pic_w"]
+            d_dec = self._buf("dec", n * self.c * rh * rw * dt.itemsize)
+            dec = self.codec.decode_reduced_device_u16 if dt.itemsize == 2 else self.codec.decode_reduced_device_u8
+            dec(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, k, slot_stride=stride)
+            mosaic = self.L.spiht_tile_mosaic_u16 if dt.itemsize == 2 else self.L.spiht_tile_mosaic_u8
+            _lib.check(mosaic(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *grid_args, vp(d_out.ptr), st_p))
+        else:
+            if dt != np.float64 or strides is not None:
+                raise ValueError("decode: the float form gives dense float64 pictures")
+            rh, rw = rs["rec_h"], rs["rec_w"]
+            d_dec = self._buf("dec", n * self.c * rh * rw * 8)
+            self.codec.decode_reduced_device(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, k, slot_stride=stride)
+            _lib.check(self.L.spiht_tile_mosaic_f64(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *grid_args, vp(d_out.ptr)))
+        self.last_tiles_decoded = n
+
+    def decode_device(self, d_packed, packed_bytes, d_lens, d_max_n, d_out, strides=None, slot_stride=None, reduce=0):
+        """decode_window_device of the whole picture: all T tiles -> d_out [c, H, W] (reduce = k: [c, Hk, Wk])"""
+        self.decode_window_device(d_packed, packed_bytes, d_lens, d_max_n, (0, self.gy, 0, self.gx), None, d_out, strides,
+                                  slot_stride, reduce)
 
     def decode_layers_device(self, d_layers, layers_bytes, d_cum, d_max_n, Q, upto, sub, window, d_out, strides=None,
-                             slot_stride=None, d_sel=None):
+                             slot_stride=None, d_sel=None, reduce=0):
         """decode_window_device of a layered run.  d_layers / layers_bytes: the layers, or a prefix of them, that the table
         d_cum (uint32 [Q][n]) describes: those of the n tiles of the sub-grid in row-major order.  With d_sel (int32 [n]) the
         run and the table ([Q][T]) are the whole picture's and d_sel names the sub-grid's tiles in it.  d_max_n: uint8 [n], the
         start planes of the sub-grid's tiles.  The layers 0 .. upto - 1 are decoded.  sub, window, d_out, strides: as
         decode_window_device; slot_stride: a multiple of 4 no tile is longer than through layer upto - 1 (None: the codec's
         bound; the host forms size the slots by the longest gathered tile).
-        One layer-unpack, one batched decode, one paste, queued on the codec's context."""
-        sub, window = self._sub_window(sub, window)
+        One layer-unpack, one batched decode, one paste, queued on the codec's context.  reduce: as decode_window_device (the
+        window in the reduced picture's coordinates; None: all of it)."""
+        rs = self.reduced_shape(reduce)
+        sub, window = self._sub_window(sub, self._window_arg(window, rs), rs)
         n, vp = (sub[1] - sub[0]) * (sub[3] - sub[2]), C.c_void_p
         stride = self.codec.slot_stride if slot_stride is None else int(slot_stride)
         d_slots = self._buf("slots", n * stride)
@@ -528,7 +612,7 @@ class TiledCodec:
         _lib.check(self.L.spiht_layer_unpack(self.ctx.handle, vp(_ptr(d_layers)), int(layers_bytes), vp(_ptr(d_cum)), int(Q),
                                              n if d_sel is None else self.T, int(upto), None if d_sel is None else vp(_ptr(d_sel)), n,
                                              vp(d_slots.ptr), stride, vp(d_nbytes.ptr)))
-        self._decode_slots(d_slots, d_nbytes, _ptr(d_max_n), stride, sub, window, d_out, strides)
+        self._decode_slots(d_slots, d_nbytes, _ptr(d_max_n), stride, sub, window, d_out, strides, rs, reduce)
 
     # ---- host forms ----------------------------------------------------------------------------------
     def _encode_host(self, images, dtype, channels_last, name):
@@ -680,10 +764,11 @@ class TiledCodec:
         if len(r.nbytes) != self.T or len(r.max_n) != self.T or sum(r.nbytes) != len(r.encoded_bytes):
             raise ValueError("the tables of the result do not describe %d tiles of %d bytes" % (self.T, len(r.encoded_bytes)))
 
-    def _decode_host(self, result, window, dtype, channels_last):
+    def _decode_host(self, result, window, dtype, channels_last, reduce=0):
         self._check_result(result)
-        y0, x0, h, w = [int(v) for v in window]
-        i0, i1, j0, j1 = sub = window_tiles(self.H, self.W, self.th, self.tw, y0, x0, h, w)
+        rs = self.reduced_shape(reduce)
+        y0, x0, h, w = self._window_arg(window, rs)
+        i0, i1, j0, j1 = sub = window_tiles(rs["Hk"], rs["Wk"], rs["thk"], rs["twk"], y0, x0, h, w)
         dtype = np.dtype(dtype)
         # the streams of the sub-grid's tiles (a row of it is contiguous in the run), their lengths and start planes: one upload
         off = result._offsets()
@@ -708,13 +793,13 @@ class TiledCodec:
         d_out = self._buf("out", self.c * h * w * es)
         stride = max(4, (int(lens.max()) + 3) & ~3)
         self.decode_window_device(d_in.ptr + head, nb, d_in.ptr, d_in.ptr + 4 * n, sub, (y0, x0, h, w), _View(d_out.ptr, dtype),
-                                  strides, stride)
+                                  strides, stride, reduce)
         self.ctx.synchronize()
         out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w), dtype)
         self.ctx.download(out, d_out.ptr)
         return out
 
-    def _decode_layered_host(self, result, window, upto, dtype, channels_last):
+    def _decode_layered_host(self, result, window, upto, dtype, channels_last, reduce=0):
         _check_version(result)
         if (result.h, result.w, result.c, result.th, result.tw) != (self.H, self.W, self.c, self.th, self.tw) \
                 or len(result.max_n) != self.T:
@@ -722,8 +807,9 @@ class TiledCodec:
                                                                             (self.H, self.W, self.c, self.th, self.tw)))
         cum, lens, off = result._table()
         upto = _upto_arg(upto, cum.shape[0])
-        y0, x0, h, w = [int(v) for v in window]
-        i0, i1, j0, j1 = sub = window_tiles(self.H, self.W, self.th, self.tw, y0, x0, h, w)
+        rs = self.reduced_shape(reduce)
+        y0, x0, h, w = self._window_arg(window, rs)
+        i0, i1, j0, j1 = sub = window_tiles(rs["Hk"], rs["Wk"], rs["thk"], rs["twk"], y0, x0, h, w)
         dtype = np.dtype(dtype)
         # the table, the start planes and the pieces of the sub-grid's tiles in the layers below upto -- per layer a row of the
         # sub-grid is contiguous in the file: one upload
@@ -750,61 +836,67 @@ class TiledCodec:
         d_out = self._buf("out", self.c * h * w * es)
         stride = max(4, (int(sub_cum[-1].max()) + 3) & ~3)
         self.decode_layers_device(d_in.ptr + head, nb, d_in.ptr, d_in.ptr + 4 * upto * n, upto, upto, sub, (y0, x0, h, w),
-                                  _View(d_out.ptr, dtype), strides, stride)
+                                  _View(d_out.ptr, dtype), strides, stride, None, reduce)
         self.ctx.synchronize()
         out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w), dtype)
         self.ctx.download(out, d_out.ptr)
         return out
 
-    def decode_layered(self, result, upto=None):
+    def decode_layered(self, result, upto=None, reduce=0):
         """LayeredResult -> float64 [c, H, W] from its first `upto` layers (None: all): what decode gives for
         result.tiled(upto), with the tiles' pieces gathered on the device -- one upload, one layer-unpack, one batched decode,
-        one paste.  A prefix of a file (LayeredResult.from_bytes) decodes like any other result."""
-        return self._decode_layered_host(result, (0, 0, self.H, self.W), upto, np.float64, False)
+        one paste.  A prefix of a file (LayeredResult.from_bytes) decodes like any other result.  reduce: as decode."""
+        return self._decode_layered_host(result, None, upto, np.float64, False, reduce)
 
-    def decode_layered_u8(self, result, upto=None, channels_last=False):
-        return self._decode_layered_host(result, (0, 0, self.H, self.W), upto, np.uint8, channels_last)
+    def decode_layered_u8(self, result, upto=None, channels_last=False, reduce=0):
+        return self._decode_layered_host(result, None, upto, np.uint8, channels_last, reduce)
 
-    def decode_layered_u16(self, result, upto=None, channels_last=False):
-        return self._decode_layered_host(result, (0, 0, self.H, self.W), upto, np.uint16, channels_last)
+    def decode_layered_u16(self, result, upto=None, channels_last=False, reduce=0):
+        return self._decode_layered_host(result, None, upto, np.uint16, channels_last, reduce)
 
-    def decode_layered_window(self, result, y0, x0, h, w, upto=None):
+    def decode_layered_window(self, result, y0, x0, h, w, upto=None, reduce=0):
         """-> float64 [c, h, w] = decode_layered(result, upto)[:, y0:y0 + h, x0:x0 + w]; only the pieces of the tiles that meet
-        the window, of the layers below upto, are uploaded (last_tiles_decoded tells how many tiles)"""
-        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.float64, False)
+        the window, of the layers below upto, are uploaded (last_tiles_decoded tells how many tiles).  reduce: as decode_window."""
+        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.float64, False, reduce)
 
-    def decode_layered_window_u8(self, result, y0, x0, h, w, upto=None, channels_last=False):
-        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.uint8, channels_last)
+    def decode_layered_window_u8(self, result, y0, x0, h, w, upto=None, channels_last=False, reduce=0):
+        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.uint8, channels_last, reduce)
 
-    def decode_layered_window_u16(self, result, y0, x0, h, w, upto=None, channels_last=False):
-        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.uint16, channels_last)
+    def decode_layered_window_u16(self, result, y0, x0, h, w, upto=None, channels_last=False, reduce=0):
+        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.uint16, channels_last, reduce)
 
-    def decode(self, result):
+    def decode(self, result, reduce=0):
         """TiledResult -> float64 [c, H, W]: one upload, one unpack, one batched decode of all T tiles, one paste.  Unlike
         decode_image, whose float64 picture is one longer on an odd axis (pywt.waverec2's size), the result is CROPPED to the
-        picture's H x W: a tile's extra row and column belong to no picture sample."""
-        return self._decode_host(result, (0, 0, self.H, self.W), np.float64, False)
+        picture's H x W: a tile's extra row and column belong to no picture sample.
+        reduce = k > 0: the picture at 1/2^k size, float64 [c, Hk, Wk] = [c, ceil(H / 2^k), ceil(W / 2^k)] (reduced_shape(k);
+        0 <= k <= the tile's levels and 2^k dividing both tile sides, else ValueError): sample (Y, X) is sample
+        (Y - i thk, X - j twk) of decode_image_reduced(result.tile(i, j), settings, k, crop=True), (i, j) = (Y // thk, X // twk).
+        One batched reduced decode of the tiles and one mosaic: only the small picture is assembled and comes back."""
+        return self._decode_host(result, None, np.float64, False, reduce)
 
-    def decode_u8(self, result, channels_last=False):
-        """-> uint8 [c, H, W] (or [H, W, c]): the rule of decode_image_u8 per tile"""
-        return self._decode_host(result, (0, 0, self.H, self.W), np.uint8, channels_last)
+    def decode_u8(self, result, channels_last=False, reduce=0):
+        """-> uint8 [c, H, W] (or [H, W, c]): the rule of decode_image_u8 per tile (reduce = k: of decode_image_reduced_u8)"""
+        return self._decode_host(result, None, np.uint8, channels_last, reduce)
 
-    def decode_u16(self, result, channels_last=False):
+    def decode_u16(self, result, channels_last=False, reduce=0):
         """-> uint16 [c, H, W] (or [H, W, c])"""
-        return self._decode_host(result, (0, 0, self.H, self.W), np.uint16, channels_last)
+        return self._decode_host(result, None, np.uint16, channels_last, reduce)
 
-    def decode_window(self, result, y0, x0, h, w):
+    def decode_window(self, result, y0, x0, h, w, reduce=0):
         """-> float64 [c, h, w] = decode(result)[:, y0:y0 + h, x0:x0 + w]; only the tiles that meet the window are uploaded,
-        unpacked and decoded (last_tiles_decoded tells how many).  A window that leaves the picture: ValueError."""
-        return self._decode_host(result, (y0, x0, h, w), np.float64, False)
+        unpacked and decoded (last_tiles_decoded tells how many).  A window that leaves the picture: ValueError.
+        reduce = k > 0: the window is given in the REDUCED picture's coordinates, inside Hk x Wk, and the result is
+        decode(result, reduce=k)[:, y0:y0 + h, x0:x0 + w]; the tiles decoded are those it meets in the thk x twk grid."""
+        return self._decode_host(result, (y0, x0, h, w), np.float64, False, reduce)
 
-    def decode_window_u8(self, result, y0, x0, h, w, channels_last=False):
+    def decode_window_u8(self, result, y0, x0, h, w, channels_last=False, reduce=0):
         """decode_window into uint8 [c, h, w] (or [h, w, c])"""
-        return self._decode_host(result, (y0, x0, h, w), np.uint8, channels_last)
+        return self._decode_host(result, (y0, x0, h, w), np.uint8, channels_last, reduce)
 
-    def decode_window_u16(self, result, y0, x0, h, w, channels_last=False):
+    def decode_window_u16(self, result, y0, x0, h, w, channels_last=False, reduce=0):
         """decode_window into uint16 [c, h, w] (or [h, w, c])"""
-        return self._decode_host(result, (y0, x0, h, w), np.uint16, channels_last)
+        return self._decode_host(result, (y0, x0, h, w), np.uint16, channels_last, reduce)
 
 
 class _View:
@@ -869,35 +961,37 @@ def encode_image_tiled_u16(image, tile, spiht_settings=SpihtSettings(), level=No
                          points, spread)
 
 
-def _decode_tiled(result, spiht_settings, window, dtype, channels_last):
+def _decode_tiled(result, spiht_settings, window, dtype, channels_last, reduce=0):
     codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None)
-    return codec._decode_host(result, (0, 0, result.h, result.w) if window is None else window, dtype, channels_last)
+    return codec._decode_host(result, window, dtype, channels_last, reduce)
 
 
-def decode_image_tiled(result, spiht_settings):
-    """TiledResult -> float64 (c, h, w), cropped to the picture's size (see TiledCodec.decode)"""
-    return _decode_tiled(result, spiht_settings, None, np.float64, False)
+def decode_image_tiled(result, spiht_settings, reduce=0):
+    """TiledResult -> float64 (c, h, w), cropped to the picture's size (see TiledCodec.decode); reduce = k: the picture at
+    1/2^k size, (c, ceil(h / 2^k), ceil(w / 2^k)) (tiled_reduced_shape)"""
+    return _decode_tiled(result, spiht_settings, None, np.float64, False, reduce)
 
 
-def decode_image_tiled_u8(result, spiht_settings, channels_last=False):
-    return _decode_tiled(result, spiht_settings, None, np.uint8, channels_last)
+def decode_image_tiled_u8(result, spiht_settings, channels_last=False, reduce=0):
+    return _decode_tiled(result, spiht_settings, None, np.uint8, channels_last, reduce)
 
 
-def decode_image_tiled_u16(result, spiht_settings, channels_last=False):
-    return _decode_tiled(result, spiht_settings, None, np.uint16, channels_last)
+def decode_image_tiled_u16(result, spiht_settings, channels_last=False, reduce=0):
+    return _decode_tiled(result, spiht_settings, None, np.uint16, channels_last, reduce)
 
 
-def decode_image_window(result, spiht_settings, y0, x0, h, w):
-    """the window [y0, y0 + h) x [x0, x0 + w) of the picture -> float64 (c, h, w), decoding only the tiles it meets"""
-    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.float64, False)
+def decode_image_window(result, spiht_settings, y0, x0, h, w, reduce=0):
+    """the window [y0, y0 + h) x [x0, x0 + w) of the picture -> float64 (c, h, w), decoding only the tiles it meets; reduce = k:
+    the window of the picture at 1/2^k size, in that picture's coordinates"""
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.float64, False, reduce)
 
 
-def decode_image_window_u8(result, spiht_settings, y0, x0, h, w, channels_last=False):
-    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint8, channels_last)
+def decode_image_window_u8(result, spiht_settings, y0, x0, h, w, channels_last=False, reduce=0):
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint8, channels_last, reduce)
 
 
-def decode_image_window_u16(result, spiht_settings, y0, x0, h, w, channels_last=False):
-    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint16, channels_last)
+def decode_image_window_u16(result, spiht_settings, y0, x0, h, w, channels_last=False, reduce=0):
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint16, channels_last, reduce)
 
 
 def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype, channels_last, name, points, spread):
@@ -928,32 +1022,33 @@ def encode_image_layered_u16(image, tile, spiht_settings=SpihtSettings(), level=
                            points, spread)
 
 
-def _decode_layered(result, spiht_settings, window, upto, dtype, channels_last):
+def _decode_layered(result, spiht_settings, window, upto, dtype, channels_last, reduce=0):
     codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None)
-    return codec._decode_layered_host(result, (0, 0, result.h, result.w) if window is None else window, upto, dtype, channels_last)
+    return codec._decode_layered_host(result, window, upto, dtype, channels_last, reduce)
 
 
-def decode_image_layered(result, spiht_settings, upto=None):
-    """LayeredResult -> float64 (c, h, w) from its first `upto` layers (None: all), cropped as decode_image_tiled"""
-    return _decode_layered(result, spiht_settings, None, upto, np.float64, False)
+def decode_image_layered(result, spiht_settings, upto=None, reduce=0):
+    """LayeredResult -> float64 (c, h, w) from its first `upto` layers (None: all), cropped as decode_image_tiled; reduce: as
+    decode_image_tiled"""
+    return _decode_layered(result, spiht_settings, None, upto, np.float64, False, reduce)
 
 
-def decode_image_layered_u8(result, spiht_settings, upto=None, channels_last=False):
-    return _decode_layered(result, spiht_settings, None, upto, np.uint8, channels_last)
+def decode_image_layered_u8(result, spiht_settings, upto=None, channels_last=False, reduce=0):
+    return _decode_layered(result, spiht_settings, None, upto, np.uint8, channels_last, reduce)
 
 
-def decode_image_layered_u16(result, spiht_settings, upto=None, channels_last=False):
-    return _decode_layered(result, spiht_settings, None, upto, np.uint16, channels_last)
+def decode_image_layered_u16(result, spiht_settings, upto=None, channels_last=False, reduce=0):
+    return _decode_layered(result, spiht_settings, None, upto, np.uint16, channels_last, reduce)
 
 
-def decode_image_layered_window(result, spiht_settings, y0, x0, h, w, upto=None):
-    """the window of the picture from its first `upto` layers, decoding only the tiles it meets"""
-    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.float64, False)
+def decode_image_layered_window(result, spiht_settings, y0, x0, h, w, upto=None, reduce=0):
+    """the window of the picture from its first `upto` layers, decoding only the tiles it meets; reduce: as decode_image_window"""
+    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.float64, False, reduce)
 
 
-def decode_image_layered_window_u8(result, spiht_settings, y0, x0, h, w, upto=None, channels_last=False):
-    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.uint8, channels_last)
+def decode_image_layered_window_u8(result, spiht_settings, y0, x0, h, w, upto=None, channels_last=False, reduce=0):
+    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.uint8, channels_last, reduce)
 
 
-def decode_image_layered_window_u16(result, spiht_settings, y0, x0, h, w, upto=None, channels_last=False):
-    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.uint16, channels_last)
+def decode_image_layered_window_u16(result, spiht_settings, y0, x0, h, w, upto=None, channels_last=False, reduce=0):
+    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.uint16, channels_last, reduce)
