@@ -693,6 +693,29 @@ int spiht_tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D
                         uint64_t budget_bytes, uint64_t *d_nbits_out, double *d_lambda);
 
 /* ---------------------------------------------------------------------------------------
+ * Region of interest (csrc/roi.hip; the rule is spiht_amd/alloc.py).  A weight map steers the allocation above: the table
+ * spiht_tile_allocate cuts by holds the squared error WEIGHTED per pixel position.  Additions only: the ABI version stays at 2.
+ *   spiht_sse_tiles_w_*  the arguments, checks and limits of spiht_sse_tiles_*, then d_w uint8 [N or 1][H][W], the weights in
+ *                      PICTURE coordinates, the same for every channel and candidate, at any byte address; w_stride: bytes
+ *                      from one picture's map to the next, 0 = one map for all N pictures, else >= H * W.  -> d_out [G][N * T]:
+ *                      the sum over the channels and the tile's valid extent of w[i th + y][j tw + x] * (p - d)^2, tile (i, j).
+ *                      No byte outside the map is read: nothing past a tile's valid extent, nothing for the padding of edge tiles.
+ *                      _f64: double; every term double(w) * ((p - d) * (p - d)), the subtraction, the square and the product
+ *                      rounded once each, added in the order of spiht_sse_tiles_f64 -- a map of ones gives its bits, and the
+ *                      bits do not depend on G or the grouping.  _u8 / _u16: uint64, exact; c * th * tw <= 2^24
+ *                      (255 * 65535^2 * 2^24 < 2^64), else SPIHT_ERR_ARG.  d_w NULL or 0 < w_stride < H * W: SPIHT_ERR_ARG.
+ *                      Asynchronous on the context's stream; argument errors are returned before anything is queued. */
+int spiht_sse_tiles_w_f64(spiht_ctx *ctx, const double *d_tiles, const double *d_dec, int64_t G, int64_t N, int64_t c, int64_t H,
+                          int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, double *d_out, const uint8_t *d_w,
+                          uint64_t w_stride);
+int spiht_sse_tiles_w_u8(spiht_ctx *ctx, const uint8_t *d_tiles, const uint8_t *d_dec, int64_t G, int64_t N, int64_t c, int64_t H,
+                         int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out, const uint8_t *d_w,
+                         uint64_t w_stride);
+int spiht_sse_tiles_w_u16(spiht_ctx *ctx, const uint16_t *d_tiles, const uint16_t *d_dec, int64_t G, int64_t N, int64_t c, int64_t H,
+                          int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out, const uint8_t *d_w,
+                          uint64_t w_stride);
+
+/* ---------------------------------------------------------------------------------------
  * Quality layers of a tiled picture (csrc/layers.hip; the rule is spiht_amd/alloc.py, allocate_layers).  The allocation is
  * run at Q growing budgets on one table of distortions; the lengths nest, and the run stores for every tile the bytes between
  * consecutive allocations, layer-major: layer q is, for t = 0 .. T-1, bytes [B(q-1, t), B(q, t)) of tile t's stream, B(-1) = 0.

@@ -39,4 +39,6 @@ globals().update({_k: getattr(_impl, _k) for _k in ("LayeredResult", "encode_ima
                                                     "decode_image_layered_window_u8", "decode_image_layered_window_u16")})
 # ... tiled pictures at reduced resolution: the sizes of decode*(..., reduce=k)
 globals().update({_k: getattr(_impl, _k) for _k in ("tiled_reduced_shape",)})
+# ... region of interest: the weight map that the encode calls of tiled pictures take as roi=
+globals().update({_k: getattr(_impl, _k) for _k in ("roi_map",)})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

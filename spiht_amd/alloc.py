@@ -126,6 +126,52 @@ def allocate(R, D, budget_bytes):
     return out, lam
 
 
+ROI_MAX_TILE_SAMPLES = 2 ** 24
+
+
+def roi_arg(roi, N, H, W):
+    """a weight map of a call on N pictures of H x W -> contiguous uint8 [H, W] (one map for all pictures) or [N, H, W].
+    roi: a bool or uint8 array of either shape (True is weight 1).  Another dtype: TypeError; another shape: ValueError.
+
+    The map steers allocate="rd": the table the tiles are cut by holds, for tile (i, j) of th x tw with valid extent vh x vw and
+    candidate k, D_w[t][k] = sum over the channels and y < vh, x < vw of w[i th + y, j tw + x] * (p - d)^2 -- the same weight for
+    every channel.  Integer pictures: exact in uint64, for c th tw <= ROI_MAX_TILE_SAMPLES (255 * 65535^2 * 2^24 < 2^64).
+    float64: every term float64(w) * ((p - d) * (p - d)), three roundings, added in the order of the unweighted sum, so a map
+    of ones gives the unweighted table in every bit.  tile_lengths, lower_hull, allocate and allocate_layers are unchanged: a
+    tile whose weights are all zero has D = 0 at every k, its hull is the single vertex 0, and it gets no bytes."""
+    roi = np.asarray(roi)
+    if roi.dtype != np.bool_ and roi.dtype != np.uint8:
+        raise TypeError("roi must be a bool or uint8 array, not %s" % roi.dtype)
+    if roi.shape != (int(H), int(W)) and roi.shape != (int(N), int(H), int(W)):
+        raise ValueError("roi of shape %s: the weights of %d picture(s) are [%d, %d] or [%d, %d, %d]"
+                         % (roi.shape, N, H, W, N, H, W))
+    return np.ascontiguousarray(roi).view(np.uint8)
+
+
+def roi_map(H, W, boxes, weight=255, background=1):
+    """uint8 [H, W]: `background` everywhere, `weight` inside every box (y0, x0, h, w) of `boxes`; a box (y0, x0, h, w, weight)
+    carries its own weight.  Boxes are clipped to the picture; where boxes overlap, the larger weight holds.  Weights are
+    integers in 0 .. 255, else ValueError."""
+    def weight_arg(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255:
+            raise ValueError("%s = %r: an integer in 0 .. 255" % (name, v))
+        return int(v)
+    weight, background = weight_arg("weight", weight), weight_arg("background", background)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError("a %d x %d picture" % (H, W))
+    inside = np.full((H, W), -1, dtype=np.int16)  # the largest weight of the boxes that hold the pixel; -1: none does
+    for box in boxes:
+        if len(box) not in (4, 5):
+            raise ValueError("a box is (y0, x0, h, w) or (y0, x0, h, w, weight), not %r" % (tuple(box),))
+        y0, x0, h, w = [int(v) for v in box[:4]]
+        wt = weight_arg("a box's weight", box[4]) if len(box) == 5 else weight
+        ya, yb, xa, xb = max(y0, 0), min(y0 + h, H), max(x0, 0), min(x0 + w, W)
+        if ya < yb and xa < xb:
+            inside[ya:yb, xa:xb] = np.maximum(inside[ya:yb, xa:xb], wt)
+    return np.where(inside >= 0, inside, background).astype(np.uint8)
+
+
 MAX_LAYERS = 255
 
 

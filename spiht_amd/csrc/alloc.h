@@ -1,5 +1,5 @@
-// Rate allocation across tiles (alloc.hip): how the launchers cut the work, shared with api.cpp, which checks the arguments
-// and sizes the context's buffers from it.
+// Rate allocation across tiles (alloc.hip, roi.hip): how the launchers cut the work, shared with api.cpp, which checks the
+// arguments and sizes the context's buffers from it, and what the error-sum kernels of both files share.
 #pragma once
 #include "common.h"
 
@@ -15,7 +15,27 @@ struct TileSseArgs {
     uint32_t T, NT, chunks;
 };
 
+// the weighted forms (roi.hip): the same sums, every term times the weight of its pixel position
+struct TileSseWArgs {
+    TileSseArgs a;
+    const uint8_t *w;   // [N or 1][H][W], in picture coordinates
+    uint64_t w_stride;  // bytes from one picture's map to the next; 0: one map for all pictures
+};
+
 static inline uint32_t al_chunks(int64_t th) { return (uint32_t)((th + AL_TILE_ROWS - 1) / AL_TILE_ROWS); }
+
+// the valid extent of tile t of a picture batch: rows and columns that are picture samples, not replicated padding
+__device__ __forceinline__ void valid_extent(const TileSseArgs &a, uint32_t t, int &vh, int &vw) {
+    const uint32_t tl = t % a.T;
+    const int i = (int)(tl / (uint32_t)a.gx), j = (int)(tl - (uint32_t)i * (uint32_t)a.gx);
+    vh = min(a.th, a.H - i * a.th);
+    vw = min(a.tw, a.W - j * a.tw);
+}
+
+// two float64 at an address that is only 8-byte aligned: which samples a lane adds must not depend on where the tile lies
+struct __attribute__((aligned(8))) F64x2 {
+    double a, b;
+};
 
 // spiht_tile_allocate's scratch, per tile: K + 1 hull vertices (float64 distortion, uint32 length), K edge slopes, a count
 static inline size_t al_scratch_bytes(uint64_t NT, uint64_t K) { return (size_t)(NT * ((K + 1) * 12 + K * 8 + 4)); }

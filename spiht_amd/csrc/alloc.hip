@@ -31,19 +31,6 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_prefix_slots(const uint8_t 
 
 // ---- per-tile error sums -----------------------------------------------------------------------------------------------------
 
-// the valid extent of tile t of a picture batch: rows and columns that are picture samples, not replicated padding
-__device__ __forceinline__ void valid_extent(const TileSseArgs &a, uint32_t t, int &vh, int &vw) {
-    const uint32_t tl = t % a.T;
-    const int i = (int)(tl / (uint32_t)a.gx), j = (int)(tl - (uint32_t)i * (uint32_t)a.gx);
-    vh = min(a.th, a.H - i * a.th);
-    vw = min(a.tw, a.W - j * a.tw);
-}
-
-// two float64 at an address that is only 8-byte aligned: which samples a lane adds must not depend on where the tile lies
-struct __attribute__((aligned(8))) F64x2 {
-    double a, b;
-};
-
 // grid (G * NT, chunks, c).  The partition is a function of (th, vh, vw) alone: a workgroup takes AL_TILE_ROWS rows of one
 // channel, wavefront wv the rows wv, wv + 4, ... of them, lane l the columns 2 l, 2 l + 1, then 128 further on; a lane adds
 // its terms in that order, the wavefront by the __shfl_down tree, thread 0 the four wavefronts in order.
@@ -296,6 +283,12 @@ extern "C" int spiht_launch_sse_tiles(const TileSseArgs *a, int es, int64_t G, h
         else hipLaunchKernelGGL(k_sse_tiles_px<uint8_t>, grid, dim3(AL_THREADS), 0, st, *a);
         hipLaunchKernelGGL(k_sum_tiles<uint64_t>, dim3((n + 63) / 64), dim3(64), 0, st, *a, n);
     }
+    return (int)hipGetLastError();
+}
+// the second launch alone, for the weighted forms (roi.hip), whose partials it adds: n sums, float64 (es 8) or uint64
+extern "C" int spiht_launch_sum_tiles(const TileSseArgs *a, int es, uint32_t n, hipStream_t st) {
+    if (es == 8) hipLaunchKernelGGL(k_sum_tiles<double>, dim3((n + 63) / 64), dim3(64), 0, st, *a, n);
+    else hipLaunchKernelGGL(k_sum_tiles<uint64_t>, dim3((n + 63) / 64), dim3(64), 0, st, *a, n);
     return (int)hipGetLastError();
 }
 extern "C" int spiht_launch_tile_allocate(const uint64_t *d_nbits, const void *d_D, int kind, int K, int64_t N, int64_t T,

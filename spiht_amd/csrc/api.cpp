@@ -71,6 +71,7 @@ int spiht_launch_tile_prefix_slots(const uint8_t *d_slots, uint64_t slot_stride,
                                    int G, uint8_t *d_out, uint64_t out_stride, uint64_t *d_nbytes, const uint8_t *d_max_n,
                                    uint8_t *d_max_n_out, hipStream_t st);
 int spiht_launch_sse_tiles(const TileSseArgs *a, int es, int64_t G, hipStream_t st);
+int spiht_launch_sse_tiles_w(const TileSseWArgs *q, int es, int64_t G, hipStream_t st);
 int spiht_launch_tile_allocate(const uint64_t *d_nbits, const void *d_D, int kind, int K, int64_t N, int64_t T, uint64_t budget,
                                void *scratch, uint64_t *d_nbits_out, double *d_lambda, hipStream_t st);
 int spiht_launch_layer_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_cum_bits, int64_t Q, int64_t N, int64_t T,
@@ -2615,14 +2616,20 @@ extern "C" int spiht_tile_prefix_slots(spiht_ctx *ctx, const uint8_t *d_slots, u
                                              d_max_n, d_max_n_out, ctx->stream));
     return SPIHT_OK;
 }
-// es: bytes per sample (8: float64).  d_tiles [N * T, c, th, tw], d_dec [G, N * T, c, rh, rw] -> d_out [G][N * T]
+// es: bytes per sample (8: float64).  d_tiles [N * T, c, th, tw], d_dec [G, N * T, c, rh, rw] -> d_out [G][N * T].  weighted:
+// every term times d_w [N or 1][H][W] (roi.hip)
 static int sse_tiles(int es, spiht_ctx *ctx, const void *d_tiles, const void *d_dec, int64_t G, int64_t N, int64_t c, int64_t H,
-                     int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, void *d_out) {
+                     int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, void *d_out, bool weighted = false,
+                     const uint8_t *d_w = nullptr, uint64_t w_stride = 0) {
     if (!ctx || !d_tiles || !d_dec || !d_out || G < 1 || G > 65535 || N < 1 || c < 1) return SPIHT_ERR_ARG;
+    if (weighted && !d_w) return SPIHT_ERR_ARG;
     if ((uintptr_t)d_tiles % es || (uintptr_t)d_dec % es || (uintptr_t)d_out % 8) return SPIHT_ERR_ARG;
     int64_t gy, gx;
     CHK(spiht_tile_grid(H, W, th, tw, &gy, &gx));
     if (rh < th || rw < tw) return SPIHT_ERR_ARG;
+    if (weighted && w_stride != 0 && w_stride < (uint64_t)H * (uint64_t)W) return SPIHT_ERR_ARG;
+    // the exact 64-bit sum of a weighted tile: 255 * 65535^2 * 2^24 < 2^64
+    if (weighted && es != 8 && (__int128)c * th * tw > ((__int128)1 << 24)) return SPIHT_ERR_ARG;
     if (c > 65535 || th * tw >= (1 << 30) || rh >= (1 << 30) || rw >= (1 << 30) || al_chunks(th) > 65535) return SPIHT_ERR_TOO_LARGE;
     if (es != 8 && (__int128)c * th * tw >= ((__int128)1 << 32)) return SPIHT_ERR_TOO_LARGE;  // the exact 64-bit sum of a tile
     if ((__int128)G * N * gy * gx > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
@@ -2635,7 +2642,13 @@ static int sse_tiles(int es, spiht_ctx *ctx, const void *d_tiles, const void *d_
     HIPCHK(hipSetDevice(ctx->device));
     CHK(ensure(ctx, ctx->rdpart, (size_t)G * a.NT * c * a.chunks * 8));
     a.part = ctx->rdpart.p;
-    LAUNCHCHK(spiht_launch_sse_tiles(&a, es, G, ctx->stream));
+    if (weighted) {
+        TileSseWArgs q;
+        q.a = a; q.w = d_w; q.w_stride = w_stride;
+        LAUNCHCHK(spiht_launch_sse_tiles_w(&q, es, G, ctx->stream));
+    } else {
+        LAUNCHCHK(spiht_launch_sse_tiles(&a, es, G, ctx->stream));
+    }
     return SPIHT_OK;
 }
 extern "C" int spiht_sse_tiles_f64(spiht_ctx *ctx, const double *d_tiles, const double *d_dec, int64_t G, int64_t N, int64_t c,
@@ -2649,6 +2662,21 @@ extern "C" int spiht_sse_tiles_u8(spiht_ctx *ctx, const uint8_t *d_tiles, const 
 extern "C" int spiht_sse_tiles_u16(spiht_ctx *ctx, const uint16_t *d_tiles, const uint16_t *d_dec, int64_t G, int64_t N, int64_t c,
                                    int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out) {
     return sse_tiles(2, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out);
+}
+extern "C" int spiht_sse_tiles_w_f64(spiht_ctx *ctx, const double *d_tiles, const double *d_dec, int64_t G, int64_t N, int64_t c,
+                                     int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, double *d_out,
+                                     const uint8_t *d_w, uint64_t w_stride) {
+    return sse_tiles(8, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out, true, d_w, w_stride);
+}
+extern "C" int spiht_sse_tiles_w_u8(spiht_ctx *ctx, const uint8_t *d_tiles, const uint8_t *d_dec, int64_t G, int64_t N, int64_t c,
+                                    int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out,
+                                    const uint8_t *d_w, uint64_t w_stride) {
+    return sse_tiles(1, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out, true, d_w, w_stride);
+}
+extern "C" int spiht_sse_tiles_w_u16(spiht_ctx *ctx, const uint16_t *d_tiles, const uint16_t *d_dec, int64_t G, int64_t N, int64_t c,
+                                     int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out,
+                                     const uint8_t *d_w, uint64_t w_stride) {
+    return sse_tiles(2, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out, true, d_w, w_stride);
 }
 extern "C" int spiht_tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D, int kind, int64_t K, int64_t N,
                                    int64_t T, uint64_t budget_bytes, uint64_t *d_nbits_out, double *d_lambda) {

@@ -15,6 +15,7 @@ import numpy as np
 
 from .spiht_wrapper import (EncodingResult, SpihtSettings, decode_image, decode_image_reduced_u8, encode_image,
                             get_slices_and_h_w)
+from .alloc import roi_map
 from .rd import cut_to_psnr, rd_curve
 from .tiles import (decode_image_layered, decode_image_layered_u8, decode_image_layered_window, decode_image_layered_window_u8,
                     decode_image_tiled, decode_image_tiled_u8, decode_image_window, decode_image_window_u8, encode_image_layered,
@@ -50,7 +51,35 @@ def build_parser():
     parser.add_argument("image_filename")
     for flag, typ, default, text in _ARGS:
         parser.add_argument(flag, type=typ, default=default, help=text)
+    parser.add_argument("--roi", action="append", default=None, metavar="Y0,X0,H,W[:WEIGHT[:BACKGROUND]]",
+                        help="with --tile N --allocate rd: a region of interest; the tiles share the bit budget by the squared "
+                             "error weighted WEIGHT (255) inside the box and BACKGROUND (1) outside; repeatable, the larger "
+                             "weight holds where regions overlap and the smallest background outside all of them")
     return parser
+
+
+def roi_from_args(args, h, w):
+    """--roi Y0,X0,H,W[:WEIGHT[:BACKGROUND]], once or several times -> the weight map uint8 [h, w], or None"""
+    if not args.roi:
+        return None
+    if args.allocate != "rd":
+        raise SystemExit("--roi needs --tile N --allocate rd")
+    boxes, backgrounds = [], []
+    for text in args.roi:
+        parts = text.split(":")
+        try:
+            box = [int(v) for v in parts[0].split(",")]
+            extra = [int(v) for v in parts[1:]]
+        except ValueError:
+            raise SystemExit("--roi %s: Y0,X0,H,W[:WEIGHT[:BACKGROUND]] in integers" % text)
+        if len(box) != 4 or len(extra) > 2:
+            raise SystemExit("--roi %s: Y0,X0,H,W[:WEIGHT[:BACKGROUND]]" % text)
+        boxes.append(box + [extra[0] if extra else 255])
+        backgrounds += extra[1:]
+    try:
+        return roi_map(h, w, boxes, background=min(backgrounds, default=1))
+    except ValueError as e:
+        raise SystemExit("--roi: %s" % e)
 
 
 def default_level(h, w):
@@ -94,16 +123,18 @@ def report_encoding(enc: EncodingResult, settings: SpihtSettings, seconds: Optio
 def main_tiled(args, picture):
     """--tile N [--window Y0,X0,H,W] [--reduce K]: the picture as tiles of N x N.  The level is a tile's (--level, or the default
     of an N x N picture); the bit budget of --bpp is shared equally among the tiles, or with --allocate rd [--points K] by
-    their rate-distortion curves.  --reduce K saves the 8-bit picture at 1/2^K size (the window in its coordinates)."""
+    their rate-distortion curves, which --roi Y0,X0,H,W[:WEIGHT[:BACKGROUND]] weights per pixel.  --reduce K saves the 8-bit picture at 1/2^K size (the window in its coordinates)."""
     c, h, w = picture.shape
     if args.load or args.save or args.psnr is not None or args.rd_curve is not None:
         raise SystemExit("--tile goes with --bpp, --level, the settings, --window, --reduce and --out only")
     p = plan(args, c, h, w)
     level = default_level(args.tile, args.tile) if args.level is None else args.level
     print("encoding %d x %d x %d at %.3f bpp as tiles of %d x %d" % (c, h, w, args.bpp, args.tile, args.tile))
+    roi = roi_from_args(args, h, w)
     if args.layers is not None:
-        return main_layered(args, picture, p, level)
-    enc, secs = timed(encode_image_tiled, picture, args.tile, p.settings, level, p.max_bits, args.allocate, args.points)
+        return main_layered(args, picture, p, level, roi)
+    enc, secs = timed(lambda: encode_image_tiled(picture, args.tile, p.settings, level, p.max_bits, args.allocate, args.points,
+                                                 roi=roi))
     gy, gx = enc.grid()
     print("encoded in %.3f s: %d x %d tiles, %.2f KiB" % (secs, gy, gx, len(enc.encoded_bytes) / 1024))
     if args.reduce:
@@ -141,14 +172,15 @@ def save_reduced(args, small, secs):
     return small
 
 
-def main_layered(args, picture, p, level):
+def main_layered(args, picture, p, level, roi=None):
     """--layers Q | b0,b1,...: the tiled picture in quality layers; the file is cut after every layer and decoded"""
     c, h, w = picture.shape
     if args.allocate != "rd":
         raise SystemExit("--layers needs --tile N --allocate rd")
     layers = [int(v) for v in args.layers.split(",")]
     layers = layers[0] if len(layers) == 1 else layers
-    enc, secs = timed(encode_image_layered, picture, args.tile, p.settings, level, p.max_bits, layers, args.points)
+    enc, secs = timed(lambda: encode_image_layered(picture, args.tile, p.settings, level, p.max_bits, layers, args.points,
+                                                   roi=roi))
     gy, gx = enc.grid()
     print("encoded in %.3f s: %d x %d tiles, %d layers, %.2f KiB" % (secs, gy, gx, enc.layers, len(enc.to_bytes()) / 1024))
     window = _window(args) if args.window else None
@@ -180,8 +212,8 @@ def main(args):
     picture = imload(args.image_filename)
     if args.tile is not None:
         return main_tiled(args, picture)
-    if args.window or args.allocate or args.layers:
-        raise SystemExit("--window, --allocate and --layers need --tile")
+    if args.window or args.allocate or args.layers or args.roi:
+        raise SystemExit("--window, --allocate, --layers and --roi need --tile")
     c, h, w = picture.shape
     p = plan(args, c, h, w)
     if args.load:

@@ -21,6 +21,11 @@ layer.  The file through layer q is the whole picture at budget q, and any prefi
 The coder is untouched: two more copies (csrc/layers.hip, spiht_layer_*) put the slots into that order and gather a tile's
 pieces back into a decoder slot.
 
+Region of interest (the encode calls' roi=, the device forms' d_roi=): a uint8 weight per pixel position, and allocate="rd"
+cuts the tiles by the squared error weighted with it (alloc.roi_arg is the rule, csrc/roi.hip the weighted error sums), so
+the bytes -- with layers, the first layers -- go where the caller says the picture matters.  Streams, containers and decoders
+are untouched.
+
 Reduced resolution (every decode call's reduce=k; tiled_reduced_shape): the tiles are decoded at 1/2^k size by the batched
 reduced decode and assembled into the picture at 1/2^k size by one more copy (k_tile_mosaic, spiht_tile_mosaic_*), which takes
 every sample from the centred window of its tile's reduced decode.  It composes with windows (given in the reduced picture's
@@ -387,19 +392,52 @@ class TiledCodec:
         return st, C.c_void_p(st.ctypes.data)
 
     # ---- device-resident forms ---------------------------------------------------------------------
-    def encode_device(self, d_img, N, d_packed, d_lens, d_max_n, strides=None):
+    # ---- region of interest ----------------------------------------------------------------------
+    def _roi_check(self, dtype, name):
+        """what a call with a weight map needs of the codec, before anything is uploaded or queued"""
+        if self.allocate is None:
+            raise ValueError('%s: a weight map steers allocate="rd"; the codec was not built with it' % name)
+        if np.dtype(dtype).kind == "u" and self.c * self.th * self.tw > alloc.ROI_MAX_TILE_SAMPLES:
+            raise ValueError("%s: the exact weighted sum of integer pixels takes tiles of c * th * tw <= 2^24 samples, not %d"
+                             % (name, self.c * self.th * self.tw))
+
+    def _roi_device(self, d_roi, roi_stride, dtype, name):
+        """the device map of a device form -> None, or (address, bytes from one picture's map to the next)"""
+        if d_roi is None:
+            return None
+        self._roi_check(dtype, name)
+        roi_stride = int(roi_stride)
+        if roi_stride != 0 and roi_stride < self.H * self.W:
+            raise ValueError("%s: roi_stride = %d: 0 (one map for all pictures) or at least H * W = %d"
+                             % (name, roi_stride, self.H * self.W))
+        return _ptr(d_roi), roi_stride
+
+    def _roi_upload(self, roi, N):
+        """the host map of a host form -> (d_roi, roi_stride) for the device form: one upload"""
+        if roi is None:
+            return None, 0
+        roi = alloc.roi_arg(roi, N, self.H, self.W)
+        d_roi = self._buf("roi", roi.nbytes)
+        self.ctx.upload(d_roi.ptr, roi)
+        return d_roi, 0 if roi.ndim == 2 else self.H * self.W
+
+    def encode_device(self, d_img, N, d_packed, d_lens, d_max_n, strides=None, d_roi=None, roi_stride=0):
         """d_img: DeviceArray of N pictures [N, c, H, W] -- float64 (float32 for a float32 codec), or uint8 / uint16 laid out by
         `strides` (bytes (sb, sc, sh, sw); None: dense CHW).  -> d_packed: the N * T streams one behind the other (uint8, at
         least N * T * codec.slot_stride bytes always suffice; nothing is written past the array), d_lens: uint32 [N * T] their
         lengths, d_max_n: uint8 [N * T].  Picture n's tiles are rows [n * T, (n + 1) * T).  One cut, one batched encode, one
         pack, queued on the codec's context.  allocate="rd": between the encode and the pack, per group of candidate lengths,
         the prefix slots, one batched decode of them and the per-tile error sums; then one spiht_tile_allocate, whose lengths
-        the pack takes.  No host wait anywhere."""
+        the pack takes.  No host wait anywhere.
+        d_roi (allocate="rd" codecs; otherwise ValueError): a device weight map, uint8 [H, W] for all pictures (roi_stride 0)
+        or [N, H, W] with roi_stride >= H * W bytes from one picture's map to the next, at any address.  The error sums are
+        then the weighted ones (spiht_sse_tiles_w_*; alloc.roi_arg has the rule); nothing else in the path changes."""
         N, vp = int(N), C.c_void_p
+        roi = self._roi_device(d_roi, roi_stride, d_img.dtype, "encode_device")
         dt, d_tiles, d_slots, d_nbits = self._encode_slots(d_img, N, d_max_n, strides, "encode_device")
         NT, stride = N * self.T, self.codec.slot_stride
         if self.allocate is not None:
-            d_nbits = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n)
+            d_nbits = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi)
         _lib.check(self.L.spiht_tile_pack(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, vp(d_packed.ptr),
                                           d_packed.nbytes, vp(d_lens.ptr)))
 
@@ -433,20 +471,20 @@ class TiledCodec:
             self.codec.encode_device(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
         return dt, d_tiles, d_slots, d_nbits
 
-    def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n):
+    def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi=None):
         """the NT full streams in d_slots -> the buffer of the cut lengths in bits (uint64 [NT]); the table of distortions
         stays in the buffer "D" ([K + 1][NT]) and lambda* in "lambda" ([N]) for the host forms"""
         NT, K, vp = N * self.T, self.points, C.c_void_p
-        d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n)
+        d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi)
         d_cut = self._buf("cut", NT * 8)
         d_lam = self._buf("lambda", N * 8)
         _lib.check(self.L.spiht_tile_allocate(self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, K, N, self.T,
                                               int(self.max_bits) // 8, vp(d_cut.ptr), vp(d_lam.ptr)))
         return d_cut
 
-    def _measure_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n):
+    def _measure_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi=None):
         """the NT full streams in d_slots -> the buffer "D": float64 / uint64 [K + 1][NT], the error of every tile at its K + 1
-        candidate lengths"""
+        candidate lengths; roi = (address, stride) of a device weight map: the weighted error"""
         NT, K, vp, c = N * self.T, self.points, C.c_void_p, self.c
         stride = self.codec.slot_stride
         integer = dt.kind == "u"
@@ -459,33 +497,40 @@ class TiledCodec:
         d_D = self._buf("D", (K + 1) * NT * 8)
         if integer:
             dec = self.codec.decode_device_u16 if dt.itemsize == 2 else self.codec.decode_device_u8
-            sse = self.L.spiht_sse_tiles_u16 if dt.itemsize == 2 else self.L.spiht_sse_tiles_u8
+            kind = "u16" if dt.itemsize == 2 else "u8"
         else:
-            dec, sse = self.codec.decode_device, self.L.spiht_sse_tiles_f64
+            dec, kind = self.codec.decode_device, "f64"
+        if roi is None:
+            sse, w_args = getattr(self.L, "spiht_sse_tiles_" + kind), ()
+        else:
+            sse, w_args = getattr(self.L, "spiht_sse_tiles_w_" + kind), (vp(roi[0]), roi[1])
         for k0 in range(0, K + 1, G):
             g = min(G, K + 1 - k0)
             _lib.check(self.L.spiht_tile_prefix_slots(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, K, k0, g,
                                                       vp(d_pre.ptr), stride, vp(d_prebytes.ptr), vp(d_max_n.ptr), vp(d_premaxn.ptr)))
             dec(d_pre.ptr, d_prebytes.ptr, d_premaxn.ptr, g * NT, d_dec.ptr, slot_stride=stride)
             _lib.check(sse(self.ctx.handle, vp(d_tiles.ptr), vp(d_dec.ptr), g, N, c, self.H, self.W, self.th, self.tw, rh, rw,
-                           vp(d_D.ptr + 8 * k0 * NT)))
+                           vp(d_D.ptr + 8 * k0 * NT), *w_args))
         return d_D
 
-    def encode_layered_device(self, d_img, N, layers, d_packed, d_cum, d_max_n, d_pic_bytes, strides=None):
+    def encode_layered_device(self, d_img, N, layers, d_packed, d_cum, d_max_n, d_pic_bytes, strides=None, d_roi=None,
+                              roi_stride=0):
         """encode_device in Q quality layers (allocate="rd" codecs; layers: alloc.layer_budgets(max_bits, layers)).  d_img, N,
         d_max_n, strides: as encode_device.  -> d_packed: picture n's layers behind picture n - 1's, inside a picture layer by
         layer and tile by tile (N * T * codec.slot_stride bytes always suffice; nothing is written past the array); d_cum: uint32
         [N][Q][T], the bytes of every tile through every layer; d_pic_bytes: uint64 [N], the pictures' lengths in d_packed.
         What encode_device queues up to the table of distortions, then Q spiht_tile_allocate on that one table -- the cuts
         stay in the buffers "cuts" (bits, uint64 [Q][N * T]) and "lambdas" ([Q][N]) -- then one spiht_layer_pack.  No host
-        wait anywhere.  The last layer's cut is encode_device's.  Returns Q."""
+        wait anywhere.  The last layer's cut is encode_device's.  Returns Q.
+        d_roi, roi_stride: a device weight map, as encode_device; the first layers then hold the bytes of the tiles it favours."""
         if self.allocate is None:
             raise ValueError('encode_layered: the codec was not built with allocate="rd"')
         budgets = alloc.layer_budgets(self.max_bits, layers)
         N, Q, vp = int(N), len(budgets), C.c_void_p
+        roi = self._roi_device(d_roi, roi_stride, d_img.dtype, "encode_layered_device")
         dt, d_tiles, d_slots, d_nbits = self._encode_slots(d_img, N, d_max_n, strides, "encode_layered_device")
         NT = N * self.T
-        d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n)
+        d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi)
         d_cuts = self._buf("cuts", Q * NT * 8)
         d_lams = self._buf("lambdas", Q * N * 8)
         for q, bits in enumerate(budgets):
@@ -615,13 +660,15 @@ class TiledCodec:
         self._decode_slots(d_slots, d_nbytes, _ptr(d_max_n), stride, sub, window, d_out, strides, rs, reduce)
 
     # ---- host forms ----------------------------------------------------------------------------------
-    def _encode_host(self, images, dtype, channels_last, name):
+    def _encode_host(self, images, dtype, channels_last, name, roi=None):
+        if roi is not None:
+            self._roi_check(dtype, name)
         single, N, d_img_view, strides = self._upload_pictures(images, dtype, channels_last, name)
         NT = N * self.T
         d_packed = self._buf("packed", NT * self.codec.slot_stride)
         d_lens = self._buf("lens", NT * 4)
         d_maxn = self._buf("maxn", NT)
-        self.encode_device(d_img_view, N, d_packed, d_lens, d_maxn, strides)
+        self.encode_device(d_img_view, N, d_packed, d_lens, d_maxn, strides, *self._roi_upload(roi, N))
         self.ctx.synchronize()
         lens = np.empty(NT, dtype=np.uint32)
         maxn = np.empty(NT, dtype=np.uint8)
@@ -643,19 +690,23 @@ class TiledCodec:
                                    [int(v) for v in lens[a:b]], run[int(off[a]):int(off[b])].tobytes()))
         return out[0] if single else out
 
-    def encode(self, image_or_images):
+    def encode(self, image_or_images, roi=None):
         """one float picture [c, H, W] -> TiledResult; N pictures [N, c, H, W] -> a list of them -- from one cut, one batched
-        encode of the N * T tiles and one pack; the packed bytes and the table come back in one download each"""
-        return self._encode_host(image_or_images, self.pixel_dtype, False, "encode")
+        encode of the N * T tiles and one pack; the packed bytes and the table come back in one download each.
+        roi (allocate="rd" codecs; otherwise ValueError): a weight map, bool or uint8 [H, W] for all pictures or [N, H, W]
+        (alloc.roi_arg, alloc.roi_map), uploaded once: the tiles share the budget by the squared error weighted per pixel, so
+        the bytes go where the map is large and a tile of zero weights gets none.  The streams, the container and every
+        decoder are as without it; last_allocation and tile_curves report the weighted table's numbers."""
+        return self._encode_host(image_or_images, self.pixel_dtype, False, "encode", roi)
 
-    def encode_u8(self, image_or_images, channels_last=False):
+    def encode_u8(self, image_or_images, channels_last=False, roi=None):
         """uint8 pictures [c, H, W] / [N, c, H, W] (or [H, W, c] / [N, H, W, c] with channels_last) -> what encode gives for
         pictures / 255.0"""
-        return self._encode_host(image_or_images, np.uint8, channels_last, "encode_u8")
+        return self._encode_host(image_or_images, np.uint8, channels_last, "encode_u8", roi)
 
-    def encode_u16(self, image_or_images, channels_last=False):
+    def encode_u16(self, image_or_images, channels_last=False, roi=None):
         """uint16 pictures -> what encode gives for pictures / 65535.0"""
-        return self._encode_host(image_or_images, np.uint16, channels_last, "encode_u16")
+        return self._encode_host(image_or_images, np.uint16, channels_last, "encode_u16", roi)
 
     def _upload_pictures(self, images, dtype, channels_last, name):
         """the host checks of _encode_host and the upload -> (single, N, the device view, strides)"""
@@ -687,9 +738,11 @@ class TiledCodec:
         self.ctx.upload(d_img.ptr, images)
         return single, shape[0], _View(d_img.ptr, dtype), strides
 
-    def _encode_layered_host(self, images, layers, dtype, channels_last, name):
+    def _encode_layered_host(self, images, layers, dtype, channels_last, name, roi=None):
         if self.allocate is None:
             raise ValueError('%s: the codec was not built with allocate="rd"' % name)
+        if roi is not None:
+            self._roi_check(dtype, name)
         Q = len(alloc.layer_budgets(self.max_bits, layers))
         single, N, d_img, strides = self._upload_pictures(images, dtype, channels_last, name)
         T, NT = self.T, N * self.T
@@ -697,7 +750,7 @@ class TiledCodec:
         d_cum = self._buf("cum", N * Q * T * 4)
         d_maxn = self._buf("maxn", NT)
         d_pic = self._buf("picbytes", N * 8)
-        self.encode_layered_device(d_img, N, layers, d_packed, d_cum, d_maxn, d_pic, strides)
+        self.encode_layered_device(d_img, N, layers, d_packed, d_cum, d_maxn, d_pic, strides, *self._roi_upload(roi, N))
         self.ctx.synchronize()
         cum = np.empty((N, Q, T), dtype=np.uint32)
         maxn = np.empty(NT, dtype=np.uint8)
@@ -720,32 +773,34 @@ class TiledCodec:
         self.last_allocation = cuts[0] if single else cuts
         return out[0] if single else out
 
-    def encode_layered(self, image_or_images, layers):
+    def encode_layered(self, image_or_images, layers, roi=None):
         """encode in quality layers (a codec built with allocate="rd"; otherwise ValueError).  layers: an int Q or the layers'
         bit budgets, the last one max_bits (alloc.layer_budgets).  -> LayeredResult, or a list for [N, c, H, W];
         result.tiled() is what encode gives.  last_allocation: a list of Q TileAllocation, one per layer (a list of such lists
-        for several pictures)."""
-        return self._encode_layered_host(image_or_images, layers, self.pixel_dtype, False, "encode_layered")
+        for several pictures).  roi: a weight map, as encode -- the first layers then hold the bytes of the tiles it favours,
+        so a truncated file shows the region of interest first."""
+        return self._encode_layered_host(image_or_images, layers, self.pixel_dtype, False, "encode_layered", roi)
 
-    def encode_layered_u8(self, image_or_images, layers, channels_last=False):
+    def encode_layered_u8(self, image_or_images, layers, channels_last=False, roi=None):
         """encode_layered of uint8 pictures, as encode_u8"""
-        return self._encode_layered_host(image_or_images, layers, np.uint8, channels_last, "encode_layered_u8")
+        return self._encode_layered_host(image_or_images, layers, np.uint8, channels_last, "encode_layered_u8", roi)
 
-    def encode_layered_u16(self, image_or_images, layers, channels_last=False):
+    def encode_layered_u16(self, image_or_images, layers, channels_last=False, roi=None):
         """encode_layered of uint16 pictures, as encode_u16"""
-        return self._encode_layered_host(image_or_images, layers, np.uint16, channels_last, "encode_layered_u16")
+        return self._encode_layered_host(image_or_images, layers, np.uint16, channels_last, "encode_layered_u16", roi)
 
-    def tile_curves(self, image, dtype=None):
+    def tile_curves(self, image, dtype=None, roi=None):
         """The curves allocate="rd" cuts by, of one picture [c, H, W] (dtype None: the codec's float pixels; np.uint8 /
         np.uint16: integer pixels) -> TileCurves.  alloc.allocate(curves.lengths, curves.sse, max_bits // 8) gives the lengths
-        of encode / encode_u8 / encode_u16 of that picture; last_allocation is set as by them."""
+        of encode / encode_u8 / encode_u16 of that picture; last_allocation is set as by them.  roi: the weight map of that
+        encode call -- sse is then the weighted error."""
         if self.allocate is None:
             raise ValueError('tile_curves: the codec was not built with allocate="rd"')
         image = np.asarray(image)
         if image.ndim != 3:
             raise ValueError("tile_curves takes one picture [c, H, W]")
         dtype = self.pixel_dtype if dtype is None else np.dtype(dtype)
-        self._encode_host(image, dtype, False, "tile_curves")
+        self._encode_host(image, dtype, False, "tile_curves", roi)
         T, K = self.T, self.points
         D = np.empty((K + 1, T), dtype=np.uint64 if dtype.kind == "u" else np.float64)
         nbits = np.empty(T, dtype=np.uint64)
@@ -928,7 +983,7 @@ def _codec_for(c, H, W, tile, settings, level, max_bits, pixel_dtype=np.float64,
 
 
 def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_last, name, allocate=None, points=alloc.POINTS,
-                  spread=alloc.SPREAD):
+                  spread=alloc.SPREAD, roi=None):
     if not isinstance(image, np.ndarray) or image.ndim != 3:
         raise ValueError('image ndim must be 3: c,h,w')
     c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
@@ -936,29 +991,31 @@ def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_
         dtype = np.float32 if image.dtype in (np.float32, np.float16) else np.float64
     codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if np.dtype(dtype).kind == "f" else np.float64,
                        allocate, points, spread)
-    return codec._encode_host(image, codec.pixel_dtype if np.dtype(dtype).kind == "f" else dtype, channels_last, name)
+    return codec._encode_host(image, codec.pixel_dtype if np.dtype(dtype).kind == "f" else dtype, channels_last, name, roi)
 
 
 def encode_image_tiled(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, allocate=None, points=alloc.POINTS,
-                       spread=alloc.SPREAD):
+                       spread=alloc.SPREAD, roi=None):
     """encode_image of a picture (c, h, w) as tiles of `tile` (an int or (th, tw)) -> TiledResult.  level and max_bits are
     per tile as in TiledCodec: every tile gets max_bits // T bits; float32 pixels run the single-precision transform.
-    allocate="rd" (with points, spread): the tiles share max_bits by their rate-distortion curves, as in TiledCodec."""
-    return _encode_tiled(image, tile, spiht_settings, level, max_bits, None, False, "encode_image_tiled", allocate, points, spread)
+    allocate="rd" (with points, spread): the tiles share max_bits by their rate-distortion curves, as in TiledCodec.
+    roi (with allocate="rd"): a weight map [h, w], bool or uint8 (roi_map), that steers the shares, as in TiledCodec.encode."""
+    return _encode_tiled(image, tile, spiht_settings, level, max_bits, None, False, "encode_image_tiled", allocate, points, spread,
+                         roi)
 
 
 def encode_image_tiled_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False,
-                          allocate=None, points=alloc.POINTS, spread=alloc.SPREAD):
+                          allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None):
     """uint8 pixels: the TiledResult of encode_image_tiled(image / 255.0, ...); allocate="rd" measures 8-bit decodes"""
     return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint8, channels_last, "encode_image_tiled_u8", allocate,
-                         points, spread)
+                         points, spread, roi)
 
 
 def encode_image_tiled_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False,
-                           allocate=None, points=alloc.POINTS, spread=alloc.SPREAD):
+                           allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None):
     """uint16 pixels: the TiledResult of encode_image_tiled(image / 65535.0, ...); allocate="rd" measures 16-bit decodes"""
     return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint16, channels_last, "encode_image_tiled_u16", allocate,
-                         points, spread)
+                         points, spread, roi)
 
 
 def _decode_tiled(result, spiht_settings, window, dtype, channels_last, reduce=0):
@@ -994,32 +1051,34 @@ def decode_image_window_u16(result, spiht_settings, y0, x0, h, w, channels_last=
     return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint16, channels_last, reduce)
 
 
-def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype, channels_last, name, points, spread):
+def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype, channels_last, name, points, spread, roi=None):
     if not isinstance(image, np.ndarray) or image.ndim != 3:
         raise ValueError('image ndim must be 3: c,h,w')
     c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
     codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, np.float64, "rd", points, spread)
-    return codec._encode_layered_host(image, layers, codec.pixel_dtype if dtype is None else dtype, channels_last, name)
+    return codec._encode_layered_host(image, layers, codec.pixel_dtype if dtype is None else dtype, channels_last, name, roi)
 
 
 def encode_image_layered(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=1, points=alloc.POINTS,
-                         spread=alloc.SPREAD):
+                         spread=alloc.SPREAD, roi=None):
     """encode_image_tiled(..., allocate="rd") of a float64 picture (c, h, w) in quality layers -> LayeredResult.  layers: an
     int Q or the layers' bit budgets, the last one max_bits (alloc.layer_budgets); result.tiled() is the TiledResult of
-    encode_image_tiled, and any prefix of result.to_bytes() that holds the tables is a picture."""
-    return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, None, False, "encode_image_layered", points, spread)
+    encode_image_tiled, and any prefix of result.to_bytes() that holds the tables is a picture.  roi: a weight map, as
+    encode_image_tiled -- the first layers then hold the region of interest."""
+    return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, None, False, "encode_image_layered", points, spread,
+                           roi)
 
 
 def encode_image_layered_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=1, points=alloc.POINTS,
-                            spread=alloc.SPREAD, channels_last=False):
+                            spread=alloc.SPREAD, channels_last=False, roi=None):
     return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, np.uint8, channels_last, "encode_image_layered_u8",
-                           points, spread)
+                           points, spread, roi)
 
 
 def encode_image_layered_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=1, points=alloc.POINTS,
-                             spread=alloc.SPREAD, channels_last=False):
+                             spread=alloc.SPREAD, channels_last=False, roi=None):
     return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, np.uint16, channels_last, "encode_image_layered_u16",
-                           points, spread)
+                           points, spread, roi)
 
 
 def _decode_layered(result, spiht_settings, window, upto, dtype, channels_last, reduce=0):
