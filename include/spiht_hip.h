@@ -693,6 +693,21 @@ int spiht_tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D
                         uint64_t budget_bytes, uint64_t *d_nbits_out, double *d_lambda);
 
 /* ---------------------------------------------------------------------------------------
+ * A target quality across tiles (csrc/alloc.hip: k_tile_allocate_target; the rule is alloc.allocate_target).  Addition only:
+ * the ABI version stays at 2.
+ *   spiht_tile_allocate_target  the arguments, checks and limits of spiht_tile_allocate, and d_target double [N]: per picture
+ *                      the squared error of the whole picture to reach (NULL: SPIHT_ERR_ARG, before anything is queued).
+ *                      -> d_nbits_out uint64 [N * T] = 8 * the bytes alloc.allocate_target gives: every tile at the hull vertex
+ *                      of the steepest common slope at which the total error (a float64 sum in the fixed order of
+ *                      alloc.total_distortion) is at or below the target, if those bytes fit budget_bytes; else the cut of
+ *                      spiht_tile_allocate at budget_bytes.  d_lambda double [N]: that slope, or lambda* of the budget;
+ *                      d_dist double [N]: the total error reached, NaN in the budget branch; d_met uint32 [N]: 1 if the target
+ *                      was reached within the budget, else 0.  The three may be NULL.  One launch, one workgroup per picture. */
+int spiht_tile_allocate_target(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D, int kind, int64_t K, int64_t N, int64_t T,
+                               uint64_t budget_bytes, const double *d_target /* [N] squared errors */, uint64_t *d_nbits_out,
+                               double *d_lambda, double *d_dist, uint32_t *d_met);
+
+/* ---------------------------------------------------------------------------------------
  * Region of interest (csrc/roi.hip; the rule is spiht_amd/alloc.py).  A weight map steers the allocation above: the table
  * spiht_tile_allocate cuts by holds the squared error WEIGHTED per pixel position.  Additions only: the ABI version stays at 2.
  *   spiht_sse_tiles_w_*  the arguments, checks and limits of spiht_sse_tiles_*, then d_w uint8 [N or 1][H][W], the weights in

@@ -41,4 +41,6 @@ globals().update({_k: getattr(_impl, _k) for _k in ("LayeredResult", "encode_ima
 globals().update({_k: getattr(_impl, _k) for _k in ("tiled_reduced_shape",)})
 # ... region of interest: the weight map that the encode calls of tiled pictures take as roi=
 globals().update({_k: getattr(_impl, _k) for _k in ("roi_map",)})
+# ... target quality: the squared error that the encode calls' target_psnr= stands for
+globals().update({_k: getattr(_impl, _k) for _k in ("target_sqerr",)})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

@@ -69,6 +69,7 @@ SYMBOLS = [
     "spiht_tile_prefix_slots", "spiht_sse_tiles_f64", "spiht_sse_tiles_u8", "spiht_sse_tiles_u16", "spiht_tile_allocate",
     "spiht_layer_pack", "spiht_layer_unpack",
     "spiht_sse_tiles_w_f64", "spiht_sse_tiles_w_u8", "spiht_sse_tiles_w_u16",
+    "spiht_tile_allocate_target",
 ]
 
 
@@ -230,6 +231,8 @@ def lib():
         L.spiht_tile_prefix_slots.argtypes = [vp, vp, u64, vp, i64, i64, i64, i64, vp, u64, vp, vp, vp]
         L.spiht_sse_tiles_f64.argtypes = L.spiht_sse_tiles_u8.argtypes = [vp, vp, vp] + [i64] * 9 + [vp]
         L.spiht_tile_allocate.argtypes = [vp, vp, vp, i32, i64, i64, i64, u64, vp, vp]
+        # ... at a target squared error per picture: the targets, then the cut, lambda, the error reached, whether it was met
+        L.spiht_tile_allocate_target.argtypes = [vp, vp, vp, i32, i64, i64, i64, u64, vp, vp, vp, vp, vp]
         # ... steered by a weight map: the unweighted call's arguments, then the map and its stride between pictures
         L.spiht_sse_tiles_w_f64.argtypes = L.spiht_sse_tiles_w_u8.argtypes = L.spiht_sse_tiles_f64.argtypes + [vp, u64]
         # quality layers of a tiled picture: the streams in layer-major order and back

@@ -233,3 +233,141 @@ def allocate_layers(R, D, budgets_bytes):
         cum.append(out)
         lams.append(lam)
     return cum, lams
+
+
+# ---- a target quality in place of a size -------------------------------------------------------------------------------------
+
+SUM_LANES = 256
+
+
+def total_distortion(values):
+    """the float64 sum of T non-negative float64 values in an order fixed by T alone -- the order of a 256-thread workgroup
+    (k_tile_allocate_target, csrc/alloc.hip, adds in it):
+      1. accumulator i of 256 starts at +0.0 and adds values[i], values[i + 256], ... in ascending order;
+      2. within each run of 64 accumulators, six rounds x[i] <- x[i] + x[i ^ off], off = 32, 16, 8, 4, 2, 1 (addition
+         commutes, so after them all 64 hold the same bits);
+      3. the four results are added in order, ((r0 + r1) + r2) + r3.
+    Every addition is rounded to nearest once.  A rounded addition does not fall when an operand grows, and the order does not
+    depend on the values, so the sum is MONOTONE in every term: raising one value never lowers it.  allocate_target relies on
+    that -- the total over the vertices reached does not rise as the slope falls."""
+    v = np.asarray(_f64(values), dtype=np.float64)
+    rounds = -(-len(v) // SUM_LANES)
+    acc = np.zeros(SUM_LANES)
+    if rounds:  # (a missing value adds nothing; + 0.0 leaves a non-negative accumulator as it is)
+        for row in np.concatenate([v, np.zeros(rounds * SUM_LANES - len(v))]).reshape(rounds, SUM_LANES):
+            acc = acc + row
+    lane = np.arange(SUM_LANES)
+    for off in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[lane ^ off]
+    return float(((acc[0] + acc[64]) + acc[128]) + acc[192])
+
+
+def target_sqerr(db, peak, c, weight_sum):
+    """the squared error of a c-channel picture at a PSNR of db: float(c * weight_sum) * (peak * peak) / 10 ** (db / 10).
+    weight_sum: H * W without a weight map, the Python-int sum of the uint8 map with one -- a map of ones gives the unweighted
+    target in every bit.  The PSNR of a (weighted) squared error is rd.psnr_of(dist / (c * weight_sum), peak).  db: a finite
+    number, else TypeError / ValueError; weight_sum = 0 (a map of zeros): ValueError."""
+    if isinstance(db, bool) or not isinstance(db, (int, float, np.integer, np.floating)):
+        raise TypeError("a target PSNR must be a number, not %s" % type(db).__name__)
+    db = float(db)
+    if not math.isfinite(db):
+        raise ValueError("a target PSNR of %r dB" % db)
+    c, weight_sum, peak = int(c), int(weight_sum), float(peak)
+    if c < 1 or weight_sum < 0:
+        raise ValueError("target_sqerr: c >= 1 and weight_sum >= 0")
+    if weight_sum == 0:
+        raise ValueError("the weights add up to zero: no PSNR is defined")
+    return float(c * weight_sum) * (peak * peak) / 10.0 ** (db / 10.0)
+
+
+def allocate_target(R, D, target_sqerr, budget_bytes):
+    """R, D: as for allocate; target_sqerr: the squared error of the whole picture to reach; budget_bytes: the cap.
+    -> (bytes per tile, lam, dist, met).
+
+    For a slope s, vertex_t(s) is tile t's last hull vertex over edges of slope >= s, dist(s) = total_distortion of the D_t
+    there (integer D converted with one rounding, _f64) and cost(s) the bytes of those edges.  mu is the largest value of
+    {inf} and the edge slopes with dist(mu) <= target_sqerr; if there is none -- the target is unreachable -- mu is the
+    smallest edge slope (inf without edges).  dist does not rise as s falls (total_distortion is monotone), so the values with
+    dist <= target are the slopes from some slope down, and mu is found by bisection of the descending list.
+      cost(mu) <= budget_bytes: every tile goes to vertex_t(mu) -- edges of equal slope are all taken and none partially, since
+        the error inside an edge was never measured.  lam = mu, dist = dist(mu), met = the target was reachable.
+      otherwise: exactly allocate(R, D, budget_bytes); lam is its lambda*, dist = nan (a partial edge's error is unmeasured),
+        met = False.
+    A target that is NaN or negative is never met (the comparison is false); +inf is met with zero bytes."""
+    budget, target = int(budget_bytes), float(target_sqerr)
+    if budget < 0:
+        raise ValueError("budget_bytes = %d is negative" % budget)
+    hulls = []  # per tile: its edges' slopes (strictly decreasing), its vertices' lengths and distortions
+    for t in range(len(R)):
+        Dt = _f64(D[t])
+        h = lower_hull(R[t], Dt)
+        hulls.append(([slope(R[t], Dt, a, b) for a, b in zip(h, h[1:])], [int(R[t][k]) for k in h], [Dt[k] for k in h]))
+
+    def at(s):
+        ends = [sum(1 for x in sl if x >= s) for sl, _, _ in hulls]
+        return [vR[e] for e, (_, vR, _) in zip(ends, hulls)], total_distortion([vD[e] for e, (_, _, vD) in zip(ends, hulls)])
+
+    cand = sorted({math.inf}.union(*[set(sl) for sl, _, _ in hulls]), reverse=True)
+    lo, hi = 0, len(cand)  # the first candidate, descending, with dist <= target; len(cand): none
+    while lo < hi:
+        m = (lo + hi) // 2
+        if at(cand[m])[1] <= target:
+            hi = m
+        else:
+            lo = m + 1
+    mu = cand[min(lo, len(cand) - 1)]  # unreachable: the smallest slope (cand is [inf] without edges)
+    out, dist = at(mu)
+    if sum(out) <= budget:
+        return out, mu, dist, dist <= target
+    out, lam = allocate(R, D, budget)
+    return out, lam, math.nan, False
+
+
+def allocate_target_layers(R, D, targets, budget_bytes):
+    """targets: Q non-increasing squared errors.  -> (cum, lams, dists, mets): row q is allocate_target(R, D, targets[q],
+    budget_bytes).
+
+    The rows NEST, cum[q][t] <= cum[q + 1][t], and lams does not rise.  Why: dist(s) does not rise as s falls, so mu_q falls
+    as the target falls, and a tile's hull slopes strictly decrease: the vertex it reaches only advances.  cost(s) grows as s
+    falls, so once cost(mu_q) exceeds the budget it does so for every later row, and those rows are all allocate(R, D, budget).
+    lambda*(budget) is the smallest slope whose cost fits, so lambda* <= mu_q for every row that fit: the budget row takes
+    every edge those rows took, whole, and dominates them all.  An unreachable target gives mu = the smallest slope, below
+    every other row's."""
+    targets = [float(v) for v in targets]
+    if any(b > a for a, b in zip(targets, targets[1:])):
+        raise ValueError("the targets must not rise: %r" % (targets,))
+    rows = [allocate_target(R, D, v, budget_bytes) for v in targets]
+    return [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows], [r[3] for r in rows]
+
+
+def target_psnr_arg(target_psnr, N):
+    """the target_psnr= of a one-rate encode of N pictures -> N floats: a number for all pictures or one number per picture"""
+    if isinstance(target_psnr, (str, bytes)):
+        raise TypeError("target_psnr must be a number or a sequence of numbers, not %s" % type(target_psnr).__name__)
+    if isinstance(target_psnr, (list, tuple, np.ndarray)) and np.ndim(target_psnr) > 0:
+        seq = list(target_psnr)
+        if len(seq) != N:
+            raise ValueError("target_psnr holds %d values for %d picture(s)" % (len(seq), N))
+    else:
+        seq = [target_psnr] * N
+    for db in seq:
+        target_sqerr(db, 1.0, 1, 1)  # (its refusals)
+    return [float(db) for db in seq]
+
+
+def layer_targets_arg(target_psnr, layers=None):
+    """the target_psnr= of a layered encode -> Q floats: a sequence of 1 .. MAX_LAYERS strictly increasing finite dB values;
+    layers is then None or Q"""
+    if isinstance(target_psnr, (str, bytes)) or np.ndim(target_psnr) != 1:
+        raise TypeError("the layers' target_psnr must be a sequence of numbers")
+    seq = list(target_psnr)
+    for db in seq:
+        target_sqerr(db, 1.0, 1, 1)
+    out = [float(db) for db in seq]
+    if not 1 <= len(out) <= MAX_LAYERS:
+        raise ValueError("%d layers: 1 .. %d" % (len(out), MAX_LAYERS))
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError("the layers' target PSNRs must strictly increase: %r" % (out,))
+    if layers is not None and (isinstance(layers, bool) or not isinstance(layers, (int, np.integer)) or int(layers) != len(out)):
+        raise ValueError("layers = %r with %d target PSNRs: None or their number" % (layers, len(out)))
+    return out

@@ -4,6 +4,7 @@
 //   k_sse_tiles_f64      per-tile error sum over the tile's valid extent, float64, in a fixed order of additions
 //   k_sse_tiles_px       the same for 8- / 16-bit samples, exact in 64 bits
 //   k_tile_allocate      lower convex hulls, the common slope by bisection, the fill in tile order: one workgroup per picture
+//   k_tile_allocate_target  the same hulls, the steepest common slope at which the picture's error is at or below a target
 // The rule is spiht_amd/alloc.py; the allocation equals it bit for bit.  Compiled with -ffp-contract=off: a term is
 // (p - d) * (p - d) rounded, then added; a slope is one rounded subtraction and one rounded division.  No atomics.
 #include "alloc.h"
@@ -157,16 +158,14 @@ __device__ __forceinline__ uint32_t edges_from(const Hulls &h, uint64_t t, uint3
 
 #define AL_INF_BITS 0x7FF0000000000000ull
 
-// One workgroup per picture; thread i owns the tiles i, i + 256, ... of it in every phase, so a hull is read by the thread that
-// wrote it.  kind: D is float64 (0) or uint64 (1: converted with one rounding).
-__global__ __launch_bounds__(AL_THREADS) void k_tile_allocate(const uint64_t *__restrict__ nbits, const void *__restrict__ D, int kind,
-                                                              uint32_t K, uint32_t T, uint64_t budget, Hulls h,
-                                                              uint64_t *__restrict__ nbits_out, double *__restrict__ lambda) {
-    __shared__ uint64_t sh[2][AL_THREADS / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint64_t t0 = (uint64_t)blockIdx.x * T, NT = h.NT;
+// Both allocation kernels: one workgroup per picture; thread i owns the tiles i, i + 256, ... of it in every phase, so a hull is
+// read by the thread that wrote it.  kind: D is float64 (0) or uint64 (1: converted with one rounding).
 
-    // the hulls (alloc.py: lower_hull), one lane per tile
+// the hulls (alloc.py: lower_hull), one lane per tile
+__device__ __forceinline__ void build_hulls(const uint64_t *__restrict__ nbits, const void *__restrict__ D, int kind, uint32_t K,
+                                            uint32_t T, const Hulls &h) {
+    const uint32_t tid = threadIdx.x;
+    const uint64_t t0 = (uint64_t)blockIdx.x * T, NT = h.NT;
     for (uint32_t tl = tid; tl < T; tl += AL_THREADS) {
         const uint64_t t = t0 + tl;
         const uint64_t n = min((nbits[t] + 7) >> 3, (uint64_t)0x1FFFFFFF);
@@ -194,7 +193,14 @@ __global__ __launch_bounds__(AL_THREADS) void k_tile_allocate(const uint64_t *__
         }
         h.cnt[t] = cnt;
     }
+}
 
+// the cut at a budget (alloc.py: allocate) from the hulls this workgroup built: the common slope by bisection, then the fill in
+// tile order.  sh: no reduction of the caller is still in flight.
+__device__ __forceinline__ void budget_cut(uint32_t T, uint64_t budget, const Hulls &h, uint64_t (*sh)[AL_THREADS / 64],
+                                           uint64_t *__restrict__ nbits_out, double *__restrict__ lambda) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * T, NT = h.NT;
     // x0: the smallest bit pattern x with cost(x) <= budget, cost(x) = the bytes of all edges of slope >= x; cost(inf) = 0
     uint64_t lo = 0, hi = AL_INF_BITS, cost0 = 0;
     int par = 0;
@@ -261,6 +267,97 @@ __global__ __launch_bounds__(AL_THREADS) void k_tile_allocate(const uint64_t *__
     }
 }
 
+__global__ __launch_bounds__(AL_THREADS) void k_tile_allocate(const uint64_t *__restrict__ nbits, const void *__restrict__ D, int kind,
+                                                              uint32_t K, uint32_t T, uint64_t budget, Hulls h,
+                                                              uint64_t *__restrict__ nbits_out, double *__restrict__ lambda) {
+    __shared__ uint64_t sh[2][AL_THREADS / 64];
+    build_hulls(nbits, D, kind, K, T, h);
+    budget_cut(T, budget, h, sh, nbits_out, lambda);
+}
+
+// the workgroup's float64 sum in the order of alloc.py: total_distortion.  v: the thread's own terms, added in ascending order
+// from +0.0; then the butterfly of each wavefront (every lane ends with the same bits) and the four wavefronts in order.
+__device__ __forceinline__ double block_sum_f64(double v, uint64_t *sh) {
+    for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = (uint64_t)__double_as_longlong(v);
+    __syncthreads();
+    double r = __longlong_as_double((long long)sh[0]);
+    for (int i = 1; i < AL_THREADS / 64; i++) r = r + __longlong_as_double((long long)sh[i]);
+    return r;
+}
+
+// The cut at a target squared error (alloc.py: allocate_target).  dist(x) = the total distortion of the vertices the tiles reach
+// over edges of slope >= the double of bit pattern x; it does not fall as x grows.  mu, the largest slope (or inf) with
+// dist(mu) <= target, the smallest slope if there is none: every tile goes to its vertex at mu if that fits the budget;
+// otherwise the workgroup goes on into the cut at the budget.  One launch either way.
+__global__ __launch_bounds__(AL_THREADS) void k_tile_allocate_target(const uint64_t *__restrict__ nbits, const void *__restrict__ D,
+                                                                     int kind, uint32_t K, uint32_t T, uint64_t budget,
+                                                                     const double *__restrict__ targets, Hulls h,
+                                                                     uint64_t *__restrict__ nbits_out, double *__restrict__ lambda,
+                                                                     double *__restrict__ dist_out, uint32_t *__restrict__ met_out) {
+    __shared__ uint64_t sh[2][AL_THREADS / 64];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t t0 = (uint64_t)blockIdx.x * T, NT = h.NT;
+    build_hulls(nbits, D, kind, K, T, h);
+    const double target = targets[blockIdx.x];
+
+    // x1: the largest bit pattern x with dist(x) <= target; 0 if there is none (a NaN or negative target compares false)
+    uint64_t lo = 0, hi = AL_INF_BITS;
+    int par = 0;
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo + 1) >> 1);
+        double mine = 0.0;
+        for (uint32_t tl = tid; tl < T; tl += AL_THREADS) {
+            const uint64_t t = t0 + tl;
+            mine = mine + h.vD[edges_from(h, t, h.cnt[t], mid) * NT + t];
+        }
+        const double d = block_sum_f64(mine, sh[par]);
+        par ^= 1;
+        if (d <= target) lo = mid;
+        else hi = mid - 1;
+    }
+    // mu: the smallest slope >= x1 -- x1 itself where the target is reachable (dist steps only at slopes), inf above every
+    // slope, the smallest slope of all where it is not
+    uint64_t mu = AL_INF_BITS;
+    for (uint32_t tl = tid; tl < T; tl += AL_THREADS) {
+        const uint64_t t = t0 + tl;
+        const uint32_t e = edges_from(h, t, h.cnt[t], lo);
+        if (e >= 1) mu = min(mu, (uint64_t)__double_as_longlong(h.eS[(e - 1) * NT + t]));
+    }
+    __syncthreads();  // the last round's words have been read
+    mu = block_reduce<RED_MIN>(mu, sh[0]);
+    double mine = 0.0;
+    uint64_t cost = 0;
+    for (uint32_t tl = tid; tl < T; tl += AL_THREADS) {
+        const uint64_t t = t0 + tl;
+        const uint32_t e = edges_from(h, t, h.cnt[t], mu);
+        mine = mine + h.vD[e * NT + t];
+        cost += h.vR[e * NT + t];
+    }
+    cost = block_reduce<RED_SUM>(cost, sh[1]);
+    __syncthreads();
+    const double dist = block_sum_f64(mine, sh[0]);
+    __syncthreads();
+    if (cost <= budget) {  // (the same for every thread)
+        for (uint32_t tl = tid; tl < T; tl += AL_THREADS) {
+            const uint64_t t = t0 + tl;
+            nbits_out[t] = 8 * (uint64_t)h.vR[edges_from(h, t, h.cnt[t], mu) * NT + t];
+        }
+        if (tid == 0) {
+            if (lambda) lambda[blockIdx.x] = __longlong_as_double((long long)mu);
+            if (dist_out) dist_out[blockIdx.x] = dist;
+            if (met_out) met_out[blockIdx.x] = dist <= target ? 1u : 0u;
+        }
+        return;
+    }
+    // the budget binds: the cut at the budget, whose partial edges have no measured error
+    if (tid == 0) {
+        if (dist_out) dist_out[blockIdx.x] = __longlong_as_double(0x7FF8000000000000ll);
+        if (met_out) met_out[blockIdx.x] = 0u;
+    }
+    budget_cut(T, budget, h, sh, nbits_out, lambda);
+}
+
 // ---- host launchers ------------------------------------------------------------------------------------------------------------
 
 extern "C" int spiht_launch_tile_prefix_slots(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbits, int64_t NT, int K,
@@ -291,8 +388,10 @@ extern "C" int spiht_launch_sum_tiles(const TileSseArgs *a, int es, uint32_t n, 
     else hipLaunchKernelGGL(k_sum_tiles<uint64_t>, dim3((n + 63) / 64), dim3(64), 0, st, *a, n);
     return (int)hipGetLastError();
 }
+// d_target NULL: the cut at the budget; else [N] squared errors: the cut at a target (d_dist, d_met: its further outputs)
 extern "C" int spiht_launch_tile_allocate(const uint64_t *d_nbits, const void *d_D, int kind, int K, int64_t N, int64_t T,
-                                          uint64_t budget, void *scratch, uint64_t *d_nbits_out, double *d_lambda, hipStream_t st) {
+                                          uint64_t budget, const double *d_target, void *scratch, uint64_t *d_nbits_out,
+                                          double *d_lambda, double *d_dist, uint32_t *d_met, hipStream_t st) {
     const uint64_t NT = (uint64_t)N * T;
     Hulls h;
     h.NT = NT;
@@ -300,7 +399,11 @@ extern "C" int spiht_launch_tile_allocate(const uint64_t *d_nbits, const void *d
     h.eS = h.vD + (size_t)(K + 1) * NT;
     h.vR = (uint32_t *)(h.eS + (size_t)K * NT);
     h.cnt = h.vR + (size_t)(K + 1) * NT;
-    hipLaunchKernelGGL(k_tile_allocate, dim3((uint32_t)N), dim3(AL_THREADS), 0, st, d_nbits, d_D, kind, (uint32_t)K, (uint32_t)T, budget,
-                       h, d_nbits_out, d_lambda);
+    if (d_target)
+        hipLaunchKernelGGL(k_tile_allocate_target, dim3((uint32_t)N), dim3(AL_THREADS), 0, st, d_nbits, d_D, kind, (uint32_t)K,
+                           (uint32_t)T, budget, d_target, h, d_nbits_out, d_lambda, d_dist, d_met);
+    else
+        hipLaunchKernelGGL(k_tile_allocate, dim3((uint32_t)N), dim3(AL_THREADS), 0, st, d_nbits, d_D, kind, (uint32_t)K, (uint32_t)T,
+                           budget, h, d_nbits_out, d_lambda);
     return (int)hipGetLastError();
 }

@@ -73,7 +73,8 @@ int spiht_launch_tile_prefix_slots(const uint8_t *d_slots, uint64_t slot_stride,
 int spiht_launch_sse_tiles(const TileSseArgs *a, int es, int64_t G, hipStream_t st);
 int spiht_launch_sse_tiles_w(const TileSseWArgs *q, int es, int64_t G, hipStream_t st);
 int spiht_launch_tile_allocate(const uint64_t *d_nbits, const void *d_D, int kind, int K, int64_t N, int64_t T, uint64_t budget,
-                               void *scratch, uint64_t *d_nbits_out, double *d_lambda, hipStream_t st);
+                               const double *d_target, void *scratch, uint64_t *d_nbits_out, double *d_lambda, double *d_dist,
+                               uint32_t *d_met, hipStream_t st);
 int spiht_launch_layer_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_cum_bits, int64_t Q, int64_t N, int64_t T,
                             uint64_t *d_off, uint8_t *d_packed, uint64_t cap, uint32_t *d_cum, uint64_t *d_pic_bytes, hipStream_t st);
 int spiht_launch_layer_unpack(const uint8_t *d_layers, uint64_t layers_bytes, const uint32_t *d_cum, int64_t T, int64_t upto,
@@ -2678,19 +2679,32 @@ extern "C" int spiht_sse_tiles_w_u16(spiht_ctx *ctx, const uint16_t *d_tiles, co
                                      const uint8_t *d_w, uint64_t w_stride) {
     return sse_tiles(2, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out, true, d_w, w_stride);
 }
-extern "C" int spiht_tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D, int kind, int64_t K, int64_t N,
-                                   int64_t T, uint64_t budget_bytes, uint64_t *d_nbits_out, double *d_lambda) {
+// both cuts: at the budget (d_target NULL), or at a target squared error per picture under that budget
+static int tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D, int kind, int64_t K, int64_t N, int64_t T,
+                         uint64_t budget_bytes, const double *d_target, uint64_t *d_nbits_out, double *d_lambda, double *d_dist,
+                         uint32_t *d_met) {
     if (!ctx || !d_nbits || !d_D || !d_nbits_out || (kind != 0 && kind != 1) || K < 1 || K > 255 || N < 0 || T < 1)
         return SPIHT_ERR_ARG;
     if ((uintptr_t)d_nbits % 8 || (uintptr_t)d_D % 8 || (uintptr_t)d_nbits_out % 8 || (uintptr_t)d_lambda % 8) return SPIHT_ERR_ARG;
+    if ((uintptr_t)d_target % 8 || (uintptr_t)d_dist % 8 || (uintptr_t)d_met % 4) return SPIHT_ERR_ARG;
     if ((__int128)N * T > 0x7FFFFFFF || budget_bytes > ((uint64_t)1 << 60)) return SPIHT_ERR_TOO_LARGE;
     if (N == 0) return SPIHT_OK;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     CHK(ensure(ctx, ctx->allocscr, al_scratch_bytes((uint64_t)N * T, (uint64_t)K)));
-    LAUNCHCHK(spiht_launch_tile_allocate(d_nbits, d_D, kind, (int)K, N, T, budget_bytes, ctx->allocscr.p, d_nbits_out, d_lambda,
-                                         ctx->stream));
+    LAUNCHCHK(spiht_launch_tile_allocate(d_nbits, d_D, kind, (int)K, N, T, budget_bytes, d_target, ctx->allocscr.p, d_nbits_out,
+                                         d_lambda, d_dist, d_met, ctx->stream));
     return SPIHT_OK;
+}
+extern "C" int spiht_tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D, int kind, int64_t K, int64_t N,
+                                   int64_t T, uint64_t budget_bytes, uint64_t *d_nbits_out, double *d_lambda) {
+    return tile_allocate(ctx, d_nbits, d_D, kind, K, N, T, budget_bytes, nullptr, d_nbits_out, d_lambda, nullptr, nullptr);
+}
+extern "C" int spiht_tile_allocate_target(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D, int kind, int64_t K, int64_t N,
+                                          int64_t T, uint64_t budget_bytes, const double *d_target, uint64_t *d_nbits_out,
+                                          double *d_lambda, double *d_dist, uint32_t *d_met) {
+    if (!d_target) return SPIHT_ERR_ARG;
+    return tile_allocate(ctx, d_nbits, d_D, kind, K, N, T, budget_bytes, d_target, d_nbits_out, d_lambda, d_dist, d_met);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -17,9 +17,9 @@ from .spiht_wrapper import (EncodingResult, SpihtSettings, decode_image, decode_
                             get_slices_and_h_w)
 from .alloc import roi_map
 from .rd import cut_to_psnr, rd_curve
-from .tiles import (decode_image_layered, decode_image_layered_u8, decode_image_layered_window, decode_image_layered_window_u8,
-                    decode_image_tiled, decode_image_tiled_u8, decode_image_window, decode_image_window_u8, encode_image_layered,
-                    encode_image_tiled)
+from .tiles import (_codec_for, decode_image_layered, decode_image_layered_u8, decode_image_layered_window,
+                    decode_image_layered_window_u8, decode_image_tiled, decode_image_tiled_u8, decode_image_window,
+                    decode_image_window_u8, encode_image_layered, encode_image_tiled)
 from .utils import imload, imsave, load_encoding, save_encoding
 
 _ARGS = [  # (flag, type, default, help): the reference tool's options, then ours
@@ -34,7 +34,8 @@ _ARGS = [  # (flag, type, default, help): the reference tool's options, then our
     ("--save", str, None, "also write the encoding to this file"),
     ("--load", str, None, "decode this encoding instead of encoding the image"),
     ("--reduce", int, 0, "decode at 1/2^K size (K pyramid levels below full size) and save that picture"),
-    ("--psnr", float, None, "cut the stream to the shortest prefix found that reaches this PSNR in dB (of the float picture)"),
+    ("--psnr", float, None, "cut the stream to the shortest prefix found that reaches this PSNR in dB (of the float picture); with "
+                            "--tile N --allocate rd: cut the tiles where the picture reaches it, --bpp the cap"),
     ("--rd-curve", int, None, "print N rows of the stream's rate-distortion curve: bytes, bpp, PSNR"),
     ("--tile", int, None, "code the picture as tiles of N x N, one stream per tile (the bit budget is shared equally)"),
     ("--window", str, None, "with --tile: decode only the window Y0,X0,H,W of the picture and save that (with --reduce K: of "
@@ -43,6 +44,8 @@ _ARGS = [  # (flag, type, default, help): the reference tool's options, then our
     ("--points", int, 16, "with --allocate rd: prefixes measured per tile"),
     ("--layers", str, None, "with --tile N --allocate rd: Q quality layers, or their bit budgets b0,b1,... (the last one the "
                             "picture's); decodes after every layer"),
+    ("--layer-psnr", str, None, "with --tile N --allocate rd: quality layers that reach the PSNRs DB0,DB1,... in dB (strictly "
+                                "increasing), --bpp the cap; decodes after every layer"),
 ]
 
 
@@ -123,20 +126,31 @@ def report_encoding(enc: EncodingResult, settings: SpihtSettings, seconds: Optio
 def main_tiled(args, picture):
     """--tile N [--window Y0,X0,H,W] [--reduce K]: the picture as tiles of N x N.  The level is a tile's (--level, or the default
     of an N x N picture); the bit budget of --bpp is shared equally among the tiles, or with --allocate rd [--points K] by
-    their rate-distortion curves, which --roi Y0,X0,H,W[:WEIGHT[:BACKGROUND]] weights per pixel.  --reduce K saves the 8-bit picture at 1/2^K size (the window in its coordinates)."""
+    their rate-distortion curves, which --roi Y0,X0,H,W[:WEIGHT[:BACKGROUND]] weights per pixel.  With --allocate rd, --psnr DB
+    cuts the tiles where the picture reaches DB (weighted by --roi) with --bpp as the cap, and prints the bytes, the PSNR
+    reached and whether the target was met.  --reduce K saves the 8-bit picture at 1/2^K size (the window in its coordinates)."""
     c, h, w = picture.shape
-    if args.load or args.save or args.psnr is not None or args.rd_curve is not None:
-        raise SystemExit("--tile goes with --bpp, --level, the settings, --window, --reduce and --out only")
+    if args.load or args.save or args.rd_curve is not None:
+        raise SystemExit("--tile goes with --bpp, --level, the settings, --window, --reduce, --psnr and --out only")
+    if (args.psnr is not None or args.layer_psnr is not None) and args.allocate != "rd":
+        raise SystemExit("--psnr and --layer-psnr with --tile need --allocate rd")
+    if args.psnr is not None and (args.layer_psnr is not None or args.layers is not None):
+        raise SystemExit("--psnr is one rate; the layers' PSNRs are --layer-psnr DB0,DB1,...")
     p = plan(args, c, h, w)
     level = default_level(args.tile, args.tile) if args.level is None else args.level
     print("encoding %d x %d x %d at %.3f bpp as tiles of %d x %d" % (c, h, w, args.bpp, args.tile, args.tile))
     roi = roi_from_args(args, h, w)
-    if args.layers is not None:
+    if args.layers is not None or args.layer_psnr is not None:
         return main_layered(args, picture, p, level, roi)
     enc, secs = timed(lambda: encode_image_tiled(picture, args.tile, p.settings, level, p.max_bits, args.allocate, args.points,
-                                                 roi=roi))
+                                                 roi=roi, target_psnr=args.psnr))
     gy, gx = enc.grid()
     print("encoded in %.3f s: %d x %d tiles, %.2f KiB" % (secs, gy, gx, len(enc.encoded_bytes) / 1024))
+    if args.psnr is not None:
+        # (the codec of the call above, which keeps its cut)
+        cut = _codec_for(c, h, w, args.tile, p.settings, level, p.max_bits, np.float64, "rd", args.points).last_allocation
+        print("cut to %.2f dB%s: %d bytes, %s" % (args.psnr, " (weighted by --roi)" if roi is not None else "",
+                                                  len(enc.encoded_bytes), reached(cut)))
     if args.reduce:
         # the 8-bit picture of pyramid level K (no distance: there is no original of that size)
         if args.window:
@@ -160,6 +174,15 @@ def main_tiled(args, picture):
     return enc, decoded
 
 
+def reached(cut):
+    """what a TileAllocation of a call with a target PSNR says of it, in words"""
+    if cut.met:
+        return "PSNR %.3f dB, target met" % cut.psnr
+    if cut.psnr is not None:
+        return "PSNR %.3f dB with every tile's whole hull, target not reached" % cut.psnr
+    return "the cut of the --bpp budget, target not reached within it"
+
+
 def _window(args):
     return [int(v) for v in args.window.split(",")]
 
@@ -173,16 +196,33 @@ def save_reduced(args, small, secs):
 
 
 def main_layered(args, picture, p, level, roi=None):
-    """--layers Q | b0,b1,...: the tiled picture in quality layers; the file is cut after every layer and decoded"""
+    """--layers Q | b0,b1,... or --layer-psnr DB0,DB1,...: the tiled picture in quality layers, given as bit budgets or as the
+    PSNRs to reach under the cap of --bpp; the file is cut after every layer and decoded"""
     c, h, w = picture.shape
     if args.allocate != "rd":
-        raise SystemExit("--layers needs --tile N --allocate rd")
-    layers = [int(v) for v in args.layers.split(",")]
-    layers = layers[0] if len(layers) == 1 else layers
-    enc, secs = timed(lambda: encode_image_layered(picture, args.tile, p.settings, level, p.max_bits, layers, args.points,
-                                                   roi=roi))
+        raise SystemExit("--layers and --layer-psnr need --tile N --allocate rd")
+    layers, targets = None, None
+    if args.layers is not None:
+        layers = [int(v) for v in args.layers.split(",")]
+        layers = layers[0] if len(layers) == 1 else layers
+    if args.layer_psnr is not None:
+        try:
+            targets = [float(v) for v in args.layer_psnr.split(",")]
+        except ValueError:
+            raise SystemExit("--layer-psnr %s: DB0,DB1,... in dB" % args.layer_psnr)
+    try:
+        enc, secs = timed(lambda: encode_image_layered(picture, args.tile, p.settings, level, p.max_bits, layers, args.points,
+                                                       roi=roi, target_psnr=targets))
+    except ValueError as e:
+        if targets is None:
+            raise
+        raise SystemExit("--layer-psnr: %s" % e)
     gy, gx = enc.grid()
     print("encoded in %.3f s: %d x %d tiles, %d layers, %.2f KiB" % (secs, gy, gx, enc.layers, len(enc.to_bytes()) / 1024))
+    if targets is not None:
+        cuts = _codec_for(c, h, w, args.tile, p.settings, level, p.max_bits, np.float64, "rd", args.points).last_allocation
+        for q, (db, cut) in enumerate(zip(targets, cuts)):
+            print("  layer %d to %.2f dB: %d bytes, %s" % (q, db, sum(cut.nbytes), reached(cut)))
     window = _window(args) if args.window else None
     if args.reduce:
         # every layer at 1/2^K size; the last one is saved
@@ -212,8 +252,8 @@ def main(args):
     picture = imload(args.image_filename)
     if args.tile is not None:
         return main_tiled(args, picture)
-    if args.window or args.allocate or args.layers or args.roi:
-        raise SystemExit("--window, --allocate, --layers and --roi need --tile")
+    if args.window or args.allocate or args.layers or args.roi or args.layer_psnr:
+        raise SystemExit("--window, --allocate, --layers, --layer-psnr and --roi need --tile")
     c, h, w = picture.shape
     p = plan(args, c, h, w)
     if args.load:

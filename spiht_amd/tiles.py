@@ -26,6 +26,12 @@ cuts the tiles by the squared error weighted with it (alloc.roi_arg is the rule,
 the bytes -- with layers, the first layers -- go where the caller says the picture matters.  Streams, containers and decoders
 are untouched.
 
+Target quality (the encode calls' target_psnr=, the device forms' d_target=): a PSNR in place of a size.  On the same table
+allocate="rd" measures, every tile is cut at the hull vertex of the steepest common slope at which the picture's squared error
+is at or below the target (alloc.allocate_target is the rule, k_tile_allocate_target the kernel); max_bits stays the cap, and
+a target it cannot pay for gives the cut at max_bits.  Layers can be given as PSNRs.  Streams, containers and decoders are
+untouched.
+
 Reduced resolution (every decode call's reduce=k; tiled_reduced_shape): the tiles are decoded at 1/2^k size by the batched
 reduced decode and assembled into the picture at 1/2^k size by one more copy (k_tile_mosaic, spiht_tile_mosaic_*), which takes
 every sample from the centred window of its tile's reduced decode.  It composes with windows (given in the reduced picture's
@@ -309,9 +315,15 @@ class TileCurves:
 @dataclass
 class TileAllocation:
     """the cut of one picture: lam -- lambda*, the drop in squared error per byte every tile was cut at (inf: the budget lies
-    below every tile's first hull edge); nbytes -- the bytes per tile"""
+    below every tile's first hull edge); nbytes -- the bytes per tile.  Of a call with target_psnr: met -- the target was
+    reached within max_bits; dist -- the (weighted) squared error of the picture at the cut, the table's sum in the order of
+    alloc.total_distortion, and psnr -- its PSNR in dB; both None where the budget bound, since a tile cut inside a hull edge
+    was never measured there.  All three are None for a call without a target."""
     lam: float
     nbytes: List[int]
+    dist: Optional[float] = None
+    psnr: Optional[float] = None
+    met: Optional[bool] = None
 
 
 def _alloc_args(allocate, points, spread, max_bits, pixel_dtype):
@@ -421,7 +433,38 @@ class TiledCodec:
         self.ctx.upload(d_roi.ptr, roi)
         return d_roi, 0 if roi.ndim == 2 else self.H * self.W
 
-    def encode_device(self, d_img, N, d_packed, d_lens, d_max_n, strides=None, d_roi=None, roi_stride=0):
+    # ---- target quality ----------------------------------------------------------------------------
+    def _target_check(self, name):
+        if self.allocate is None:
+            raise ValueError('%s: a target quality is reached by allocate="rd"; the codec was not built with it' % name)
+
+    def _weight_sums(self, roi, N):
+        """the sum of the weights of each of the N pictures as Python ints: H * W without a map"""
+        if roi is None:
+            return [self.H * self.W] * N
+        roi = alloc.roi_arg(roi, N, self.H, self.W)
+        if roi.ndim == 2:
+            return [int(roi.sum(dtype=np.int64))] * N
+        return [int(roi[n].sum(dtype=np.int64)) for n in range(N)]
+
+    def _targets_upload(self, rows, sums, dtype):
+        """rows: Q lists of N target PSNRs; sums: the N weight sums -> the device double [Q][N] of squared errors, in the buffer
+        "targets": one upload"""
+        peak = float(np.iinfo(dtype).max) if np.dtype(dtype).kind == "u" else 1.0
+        table = np.array([[alloc.target_sqerr(db, peak, self.c, s) for db, s in zip(row, sums)] for row in rows], dtype=np.float64)
+        d_target = self._buf("targets", table.nbytes)
+        self.ctx.upload(d_target.ptr, table)
+        return d_target
+
+    def _allocation(self, lam, nbytes, dist, met, weight_sum, dtype):
+        """the TileAllocation of a cut at a target: dist is NaN where the budget bound"""
+        from .rd import psnr_of
+        if np.isnan(dist):
+            return TileAllocation(float(lam), nbytes, None, None, bool(met))
+        peak = float(np.iinfo(dtype).max) if np.dtype(dtype).kind == "u" else 1.0
+        return TileAllocation(float(lam), nbytes, float(dist), psnr_of(float(dist) / (self.c * weight_sum), peak), bool(met))
+
+    def encode_device(self, d_img, N, d_packed, d_lens, d_max_n, strides=None, d_roi=None, roi_stride=0, d_target=None):
         """d_img: DeviceArray of N pictures [N, c, H, W] -- float64 (float32 for a float32 codec), or uint8 / uint16 laid out by
         `strides` (bytes (sb, sc, sh, sw); None: dense CHW).  -> d_packed: the N * T streams one behind the other (uint8, at
         least N * T * codec.slot_stride bytes always suffice; nothing is written past the array), d_lens: uint32 [N * T] their
@@ -431,13 +474,20 @@ class TiledCodec:
         the pack takes.  No host wait anywhere.
         d_roi (allocate="rd" codecs; otherwise ValueError): a device weight map, uint8 [H, W] for all pictures (roi_stride 0)
         or [N, H, W] with roi_stride >= H * W bytes from one picture's map to the next, at any address.  The error sums are
-        then the weighted ones (spiht_sse_tiles_w_*; alloc.roi_arg has the rule); nothing else in the path changes."""
+        then the weighted ones (spiht_sse_tiles_w_*; alloc.roi_arg has the rule); nothing else in the path changes.
+        d_target (allocate="rd" codecs; otherwise ValueError): a device double [N], per picture the squared error of the whole
+        picture to reach (alloc.target_sqerr; with a weight map, the weighted error -- a caller with a device map computes its
+        own).  spiht_tile_allocate_target then takes the place of spiht_tile_allocate: one launch for one launch, max_bits the
+        cap (alloc.allocate_target); lambda, the error reached and whether the target was met stay in the buffers "lambda",
+        "tdist" (double [N], NaN where the budget bound) and "tmet" (uint32 [N])."""
         N, vp = int(N), C.c_void_p
+        if d_target is not None:
+            self._target_check("encode_device")
         roi = self._roi_device(d_roi, roi_stride, d_img.dtype, "encode_device")
         dt, d_tiles, d_slots, d_nbits = self._encode_slots(d_img, N, d_max_n, strides, "encode_device")
         NT, stride = N * self.T, self.codec.slot_stride
         if self.allocate is not None:
-            d_nbits = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi)
+            d_nbits = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi, d_target)
         _lib.check(self.L.spiht_tile_pack(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, vp(d_packed.ptr),
                                           d_packed.nbytes, vp(d_lens.ptr)))
 
@@ -471,15 +521,21 @@ class TiledCodec:
             self.codec.encode_device(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
         return dt, d_tiles, d_slots, d_nbits
 
-    def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi=None):
+    def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi=None, d_target=None):
         """the NT full streams in d_slots -> the buffer of the cut lengths in bits (uint64 [NT]); the table of distortions
-        stays in the buffer "D" ([K + 1][NT]) and lambda* in "lambda" ([N]) for the host forms"""
+        stays in the buffer "D" ([K + 1][NT]) and lambda* in "lambda" ([N]) for the host forms.  d_target: the cut at a target
+        squared error per picture, whose further outputs stay in "tdist" and "tmet" ([N] each)"""
         NT, K, vp = N * self.T, self.points, C.c_void_p
         d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi)
         d_cut = self._buf("cut", NT * 8)
         d_lam = self._buf("lambda", N * 8)
-        _lib.check(self.L.spiht_tile_allocate(self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, K, N, self.T,
-                                              int(self.max_bits) // 8, vp(d_cut.ptr), vp(d_lam.ptr)))
+        args = (self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, K, N, self.T, int(self.max_bits) // 8)
+        if d_target is None:
+            _lib.check(self.L.spiht_tile_allocate(*args, vp(d_cut.ptr), vp(d_lam.ptr)))
+        else:
+            d_dist, d_met = self._buf("tdist", N * 8), self._buf("tmet", N * 4)
+            _lib.check(self.L.spiht_tile_allocate_target(*args, vp(_ptr(d_target)), vp(d_cut.ptr), vp(d_lam.ptr), vp(d_dist.ptr),
+                                                         vp(d_met.ptr)))
         return d_cut
 
     def _measure_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi=None):
@@ -514,7 +570,7 @@ class TiledCodec:
         return d_D
 
     def encode_layered_device(self, d_img, N, layers, d_packed, d_cum, d_max_n, d_pic_bytes, strides=None, d_roi=None,
-                              roi_stride=0):
+                              roi_stride=0, target_psnr=None, d_target=None):
         """encode_device in Q quality layers (allocate="rd" codecs; layers: alloc.layer_budgets(max_bits, layers)).  d_img, N,
         d_max_n, strides: as encode_device.  -> d_packed: picture n's layers behind picture n - 1's, inside a picture layer by
         layer and tile by tile (N * T * codec.slot_stride bytes always suffice; nothing is written past the array); d_cum: uint32
@@ -522,20 +578,46 @@ class TiledCodec:
         What encode_device queues up to the table of distortions, then Q spiht_tile_allocate on that one table -- the cuts
         stay in the buffers "cuts" (bits, uint64 [Q][N * T]) and "lambdas" ([Q][N]) -- then one spiht_layer_pack.  No host
         wait anywhere.  The last layer's cut is encode_device's.  Returns Q.
-        d_roi, roi_stride: a device weight map, as encode_device; the first layers then hold the bytes of the tiles it favours."""
+        d_roi, roi_stride: a device weight map, as encode_device; the first layers then hold the bytes of the tiles it favours.
+        target_psnr: the layers as Q strictly increasing PSNRs in dB in place of budgets (layers is then None or Q): layer q is
+        the cut of spiht_tile_allocate_target at target q under the cap max_bits // 8 (alloc.allocate_target_layers: the rows
+        nest), and a layer whose target the cap cannot pay for repeats the cut at the cap.  The squared errors are
+        alloc.target_sqerr of the unweighted picture, uploaded once; or d_target, a device double [Q][N] of them, which a call
+        with d_roi must give (the weights' sums are the caller's).  "tdists" (double [Q][N]) and "tmets" (uint32 [Q][N]) keep
+        the errors reached and whether each target was met."""
         if self.allocate is None:
             raise ValueError('encode_layered: the codec was not built with allocate="rd"')
-        budgets = alloc.layer_budgets(self.max_bits, layers)
-        N, Q, vp = int(N), len(budgets), C.c_void_p
+        N, vp = int(N), C.c_void_p
+        if target_psnr is None:
+            if d_target is not None:
+                raise ValueError("encode_layered_device: d_target goes with target_psnr, the layers' PSNRs")
+            budgets = alloc.layer_budgets(self.max_bits, layers)
+            Q = len(budgets)
+        else:
+            dbs = alloc.layer_targets_arg(target_psnr, layers)
+            Q = len(dbs)
+            if d_target is None and d_roi is not None:
+                raise ValueError("encode_layered_device: with a device weight map, give the weighted squared errors as d_target")
         roi = self._roi_device(d_roi, roi_stride, d_img.dtype, "encode_layered_device")
+        if target_psnr is not None and d_target is None:
+            if N < 1:
+                raise ValueError("encode_layered_device: no pictures")
+            d_target = self._targets_upload([[db] * N for db in dbs], self._weight_sums(None, N), d_img.dtype)
         dt, d_tiles, d_slots, d_nbits = self._encode_slots(d_img, N, d_max_n, strides, "encode_layered_device")
         NT = N * self.T
         d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi)
         d_cuts = self._buf("cuts", Q * NT * 8)
         d_lams = self._buf("lambdas", Q * N * 8)
-        for q, bits in enumerate(budgets):
-            _lib.check(self.L.spiht_tile_allocate(self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, self.points,
-                                                  N, self.T, bits // 8, vp(d_cuts.ptr + 8 * q * NT), vp(d_lams.ptr + 8 * q * N)))
+        args = (self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, self.points, N, self.T)
+        if target_psnr is None:
+            for q, bits in enumerate(budgets):
+                _lib.check(self.L.spiht_tile_allocate(*args, bits // 8, vp(d_cuts.ptr + 8 * q * NT), vp(d_lams.ptr + 8 * q * N)))
+        else:
+            d_dists, d_mets = self._buf("tdists", Q * N * 8), self._buf("tmets", Q * N * 4)
+            for q in range(Q):
+                _lib.check(self.L.spiht_tile_allocate_target(*args, int(self.max_bits) // 8, vp(_ptr(d_target) + 8 * q * N),
+                                                             vp(d_cuts.ptr + 8 * q * NT), vp(d_lams.ptr + 8 * q * N),
+                                                             vp(d_dists.ptr + 8 * q * N), vp(d_mets.ptr + 4 * q * N)))
         _lib.check(self.L.spiht_layer_pack(self.ctx.handle, vp(d_slots.ptr), self.codec.slot_stride, vp(d_cuts.ptr), Q, N, self.T,
                                            vp(_ptr(d_packed)), int(d_packed.nbytes), vp(_ptr(d_cum)), vp(_ptr(d_pic_bytes))))
         return Q
@@ -660,15 +742,21 @@ class TiledCodec:
         self._decode_slots(d_slots, d_nbytes, _ptr(d_max_n), stride, sub, window, d_out, strides, rs, reduce)
 
     # ---- host forms ----------------------------------------------------------------------------------
-    def _encode_host(self, images, dtype, channels_last, name, roi=None):
+    def _encode_host(self, images, dtype, channels_last, name, roi=None, target_psnr=None):
         if roi is not None:
             self._roi_check(dtype, name)
+        if target_psnr is not None:
+            self._target_check(name)
         single, N, d_img_view, strides = self._upload_pictures(images, dtype, channels_last, name)
         NT = N * self.T
         d_packed = self._buf("packed", NT * self.codec.slot_stride)
         d_lens = self._buf("lens", NT * 4)
         d_maxn = self._buf("maxn", NT)
-        self.encode_device(d_img_view, N, d_packed, d_lens, d_maxn, strides, *self._roi_upload(roi, N))
+        d_target = None
+        if target_psnr is not None:
+            sums = self._weight_sums(roi, N)
+            d_target = self._targets_upload([alloc.target_psnr_arg(target_psnr, N)], sums, dtype)
+        self.encode_device(d_img_view, N, d_packed, d_lens, d_maxn, strides, *self._roi_upload(roi, N), d_target)
         self.ctx.synchronize()
         lens = np.empty(NT, dtype=np.uint32)
         maxn = np.empty(NT, dtype=np.uint8)
@@ -682,7 +770,14 @@ class TiledCodec:
         if self.allocate is not None:
             lam = np.empty(N, dtype=np.float64)
             self.ctx.download(lam, self._bufs["lambda"].ptr)
-            cuts = [TileAllocation(float(lam[n]), [int(v) for v in lens[n * self.T:(n + 1) * self.T]]) for n in range(N)]
+            rows = [[int(v) for v in lens[n * self.T:(n + 1) * self.T]] for n in range(N)]
+            if d_target is None:
+                cuts = [TileAllocation(float(lam[n]), rows[n]) for n in range(N)]
+            else:
+                dist, met = np.empty(N, dtype=np.float64), np.empty(N, dtype=np.uint32)
+                self.ctx.download(dist, self._bufs["tdist"].ptr)
+                self.ctx.download(met, self._bufs["tmet"].ptr)
+                cuts = [self._allocation(lam[n], rows[n], dist[n], met[n], sums[n], dtype) for n in range(N)]
             self.last_allocation = cuts[0] if single else cuts
         for n in range(N):
             a, b = n * self.T, (n + 1) * self.T
@@ -690,23 +785,29 @@ class TiledCodec:
                                    [int(v) for v in lens[a:b]], run[int(off[a]):int(off[b])].tobytes()))
         return out[0] if single else out
 
-    def encode(self, image_or_images, roi=None):
+    def encode(self, image_or_images, roi=None, target_psnr=None):
         """one float picture [c, H, W] -> TiledResult; N pictures [N, c, H, W] -> a list of them -- from one cut, one batched
         encode of the N * T tiles and one pack; the packed bytes and the table come back in one download each.
         roi (allocate="rd" codecs; otherwise ValueError): a weight map, bool or uint8 [H, W] for all pictures or [N, H, W]
         (alloc.roi_arg, alloc.roi_map), uploaded once: the tiles share the budget by the squared error weighted per pixel, so
         the bytes go where the map is large and a tile of zero weights gets none.  The streams, the container and every
-        decoder are as without it; last_allocation and tile_curves report the weighted table's numbers."""
-        return self._encode_host(image_or_images, self.pixel_dtype, False, "encode", roi)
+        decoder are as without it; last_allocation and tile_curves report the weighted table's numbers.
+        target_psnr (allocate="rd" codecs; otherwise ValueError): a PSNR in dB, or one per picture, in place of a size.  Every
+        tile is cut at the hull vertex of the steepest common slope at which the picture's squared error -- with roi, the
+        weighted one -- is at or below alloc.target_sqerr(target_psnr, peak, c, H * W or the weights' sum), peak 1.0 / 255 /
+        65535 (alloc.allocate_target).  max_bits stays the ceiling the tiles are coded with and the cap: a target it cannot
+        pay for gives the cut of the call without a target, and one that no cut reaches gives every tile's whole hull if that
+        fits.  last_allocation.met tells (with dist and psnr, the error reached)."""
+        return self._encode_host(image_or_images, self.pixel_dtype, False, "encode", roi, target_psnr)
 
-    def encode_u8(self, image_or_images, channels_last=False, roi=None):
+    def encode_u8(self, image_or_images, channels_last=False, roi=None, target_psnr=None):
         """uint8 pictures [c, H, W] / [N, c, H, W] (or [H, W, c] / [N, H, W, c] with channels_last) -> what encode gives for
         pictures / 255.0"""
-        return self._encode_host(image_or_images, np.uint8, channels_last, "encode_u8", roi)
+        return self._encode_host(image_or_images, np.uint8, channels_last, "encode_u8", roi, target_psnr)
 
-    def encode_u16(self, image_or_images, channels_last=False, roi=None):
+    def encode_u16(self, image_or_images, channels_last=False, roi=None, target_psnr=None):
         """uint16 pictures -> what encode gives for pictures / 65535.0"""
-        return self._encode_host(image_or_images, np.uint16, channels_last, "encode_u16", roi)
+        return self._encode_host(image_or_images, np.uint16, channels_last, "encode_u16", roi, target_psnr)
 
     def _upload_pictures(self, images, dtype, channels_last, name):
         """the host checks of _encode_host and the upload -> (single, N, the device view, strides)"""
@@ -738,19 +839,28 @@ class TiledCodec:
         self.ctx.upload(d_img.ptr, images)
         return single, shape[0], _View(d_img.ptr, dtype), strides
 
-    def _encode_layered_host(self, images, layers, dtype, channels_last, name, roi=None):
+    def _encode_layered_host(self, images, layers, dtype, channels_last, name, roi=None, target_psnr=None):
         if self.allocate is None:
             raise ValueError('%s: the codec was not built with allocate="rd"' % name)
         if roi is not None:
             self._roi_check(dtype, name)
-        Q = len(alloc.layer_budgets(self.max_bits, layers))
+        if target_psnr is None:
+            Q = len(alloc.layer_budgets(self.max_bits, layers))
+        else:
+            dbs = alloc.layer_targets_arg(target_psnr, layers)
+            Q = len(dbs)
         single, N, d_img, strides = self._upload_pictures(images, dtype, channels_last, name)
         T, NT = self.T, N * self.T
         d_packed = self._buf("packed", NT * self.codec.slot_stride)
         d_cum = self._buf("cum", N * Q * T * 4)
         d_maxn = self._buf("maxn", NT)
         d_pic = self._buf("picbytes", N * 8)
-        self.encode_layered_device(d_img, N, layers, d_packed, d_cum, d_maxn, d_pic, strides, *self._roi_upload(roi, N))
+        d_target = None
+        if target_psnr is not None:
+            sums = self._weight_sums(roi, N)
+            d_target = self._targets_upload([[db] * N for db in dbs], sums, dtype)
+        self.encode_layered_device(d_img, N, layers, d_packed, d_cum, d_maxn, d_pic, strides, *self._roi_upload(roi, N),
+                                   target_psnr, d_target)
         self.ctx.synchronize()
         cum = np.empty((N, Q, T), dtype=np.uint32)
         maxn = np.empty(NT, dtype=np.uint8)
@@ -760,6 +870,10 @@ class TiledCodec:
         self.ctx.download(maxn, d_maxn.ptr)
         self.ctx.download(pic, d_pic.ptr)
         self.ctx.download(lam, self._bufs["lambdas"].ptr)
+        if d_target is not None:
+            dist, met = np.empty((Q, N), dtype=np.float64), np.empty((Q, N), dtype=np.uint32)
+            self.ctx.download(dist, self._bufs["tdists"].ptr)
+            self.ctx.download(met, self._bufs["tmets"].ptr)
         off = np.concatenate(([0], np.cumsum(pic.astype(np.int64))))
         run = np.empty(int(off[-1]), dtype=np.uint8)
         if run.size:
@@ -767,27 +881,36 @@ class TiledCodec:
         out, cuts = [], []
         for n in range(N):
             rows = [[int(v) for v in row] for row in cum[n]]
-            cuts.append([TileAllocation(float(lam[q, n]), rows[q]) for q in range(Q)])
+            if d_target is None:
+                cuts.append([TileAllocation(float(lam[q, n]), rows[q]) for q in range(Q)])
+            else:
+                cuts.append([self._allocation(lam[q, n], rows[q], dist[q, n], met[q, n], sums[n], dtype) for q in range(Q)])
             out.append(LayeredResult(self.H, self.W, self.c, self.th, self.tw, self.level, [int(v) for v in maxn[n * T:(n + 1) * T]],
                                      rows, run[int(off[n]):int(off[n + 1])].tobytes()))
         self.last_allocation = cuts[0] if single else cuts
         return out[0] if single else out
 
-    def encode_layered(self, image_or_images, layers, roi=None):
+    def encode_layered(self, image_or_images, layers=None, roi=None, target_psnr=None):
         """encode in quality layers (a codec built with allocate="rd"; otherwise ValueError).  layers: an int Q or the layers'
         bit budgets, the last one max_bits (alloc.layer_budgets).  -> LayeredResult, or a list for [N, c, H, W];
         result.tiled() is what encode gives.  last_allocation: a list of Q TileAllocation, one per layer (a list of such lists
         for several pictures).  roi: a weight map, as encode -- the first layers then hold the bytes of the tiles it favours,
-        so a truncated file shows the region of interest first."""
-        return self._encode_layered_host(image_or_images, layers, self.pixel_dtype, False, "encode_layered", roi)
+        so a truncated file shows the region of interest first.
+        target_psnr: the layers as strictly increasing PSNRs in dB, e.g. [30, 35, 40], in place of budgets (layers is then None
+        or their number).  Layer q ends where encode(..., target_psnr=target_psnr[q]) cuts: result.tiled(q + 1) is that
+        TiledResult.  max_bits stays the cap; a layer whose target it cannot pay for ends at the cut of max_bits, and the layers
+        behind it are empty.  The container is the same SPTQ."""
+        return self._encode_layered_host(image_or_images, layers, self.pixel_dtype, False, "encode_layered", roi, target_psnr)
 
-    def encode_layered_u8(self, image_or_images, layers, channels_last=False, roi=None):
+    def encode_layered_u8(self, image_or_images, layers=None, channels_last=False, roi=None, target_psnr=None):
         """encode_layered of uint8 pictures, as encode_u8"""
-        return self._encode_layered_host(image_or_images, layers, np.uint8, channels_last, "encode_layered_u8", roi)
+        return self._encode_layered_host(image_or_images, layers, np.uint8, channels_last, "encode_layered_u8", roi,
+                                         target_psnr)
 
-    def encode_layered_u16(self, image_or_images, layers, channels_last=False, roi=None):
+    def encode_layered_u16(self, image_or_images, layers=None, channels_last=False, roi=None, target_psnr=None):
         """encode_layered of uint16 pictures, as encode_u16"""
-        return self._encode_layered_host(image_or_images, layers, np.uint16, channels_last, "encode_layered_u16", roi)
+        return self._encode_layered_host(image_or_images, layers, np.uint16, channels_last, "encode_layered_u16", roi,
+                                         target_psnr)
 
     def tile_curves(self, image, dtype=None, roi=None):
         """The curves allocate="rd" cuts by, of one picture [c, H, W] (dtype None: the codec's float pixels; np.uint8 /
@@ -983,7 +1106,7 @@ def _codec_for(c, H, W, tile, settings, level, max_bits, pixel_dtype=np.float64,
 
 
 def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_last, name, allocate=None, points=alloc.POINTS,
-                  spread=alloc.SPREAD, roi=None):
+                  spread=alloc.SPREAD, roi=None, target_psnr=None):
     if not isinstance(image, np.ndarray) or image.ndim != 3:
         raise ValueError('image ndim must be 3: c,h,w')
     c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
@@ -991,31 +1114,34 @@ def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_
         dtype = np.float32 if image.dtype in (np.float32, np.float16) else np.float64
     codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if np.dtype(dtype).kind == "f" else np.float64,
                        allocate, points, spread)
-    return codec._encode_host(image, codec.pixel_dtype if np.dtype(dtype).kind == "f" else dtype, channels_last, name, roi)
+    return codec._encode_host(image, codec.pixel_dtype if np.dtype(dtype).kind == "f" else dtype, channels_last, name, roi,
+                              target_psnr)
 
 
 def encode_image_tiled(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, allocate=None, points=alloc.POINTS,
-                       spread=alloc.SPREAD, roi=None):
+                       spread=alloc.SPREAD, roi=None, target_psnr=None):
     """encode_image of a picture (c, h, w) as tiles of `tile` (an int or (th, tw)) -> TiledResult.  level and max_bits are
     per tile as in TiledCodec: every tile gets max_bits // T bits; float32 pixels run the single-precision transform.
     allocate="rd" (with points, spread): the tiles share max_bits by their rate-distortion curves, as in TiledCodec.
-    roi (with allocate="rd"): a weight map [h, w], bool or uint8 (roi_map), that steers the shares, as in TiledCodec.encode."""
+    roi (with allocate="rd"): a weight map [h, w], bool or uint8 (roi_map), that steers the shares, as in TiledCodec.encode.
+    target_psnr (with allocate="rd"): a PSNR in dB to reach with the fewest bytes the measured curves allow, max_bits the cap, as
+    in TiledCodec.encode."""
     return _encode_tiled(image, tile, spiht_settings, level, max_bits, None, False, "encode_image_tiled", allocate, points, spread,
-                         roi)
+                         roi, target_psnr)
 
 
 def encode_image_tiled_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False,
-                          allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None):
+                          allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None, target_psnr=None):
     """uint8 pixels: the TiledResult of encode_image_tiled(image / 255.0, ...); allocate="rd" measures 8-bit decodes"""
     return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint8, channels_last, "encode_image_tiled_u8", allocate,
-                         points, spread, roi)
+                         points, spread, roi, target_psnr)
 
 
 def encode_image_tiled_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False,
-                           allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None):
+                           allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None, target_psnr=None):
     """uint16 pixels: the TiledResult of encode_image_tiled(image / 65535.0, ...); allocate="rd" measures 16-bit decodes"""
     return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint16, channels_last, "encode_image_tiled_u16", allocate,
-                         points, spread, roi)
+                         points, spread, roi, target_psnr)
 
 
 def _decode_tiled(result, spiht_settings, window, dtype, channels_last, reduce=0):
@@ -1051,34 +1177,40 @@ def decode_image_window_u16(result, spiht_settings, y0, x0, h, w, channels_last=
     return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint16, channels_last, reduce)
 
 
-def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype, channels_last, name, points, spread, roi=None):
+def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype, channels_last, name, points, spread, roi=None,
+                    target_psnr=None):
+    if layers is None and target_psnr is None:
+        layers = 1
     if not isinstance(image, np.ndarray) or image.ndim != 3:
         raise ValueError('image ndim must be 3: c,h,w')
     c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
     codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, np.float64, "rd", points, spread)
-    return codec._encode_layered_host(image, layers, codec.pixel_dtype if dtype is None else dtype, channels_last, name, roi)
+    return codec._encode_layered_host(image, layers, codec.pixel_dtype if dtype is None else dtype, channels_last, name, roi,
+                                      target_psnr)
 
 
-def encode_image_layered(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=1, points=alloc.POINTS,
-                         spread=alloc.SPREAD, roi=None):
+def encode_image_layered(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=None, points=alloc.POINTS,
+                         spread=alloc.SPREAD, roi=None, target_psnr=None):
     """encode_image_tiled(..., allocate="rd") of a float64 picture (c, h, w) in quality layers -> LayeredResult.  layers: an
     int Q or the layers' bit budgets, the last one max_bits (alloc.layer_budgets); result.tiled() is the TiledResult of
     encode_image_tiled, and any prefix of result.to_bytes() that holds the tables is a picture.  roi: a weight map, as
-    encode_image_tiled -- the first layers then hold the region of interest."""
+    encode_image_tiled -- the first layers then hold the region of interest.  layers=None is one layer, or with target_psnr
+    as many as it holds: the layers as strictly increasing PSNRs in dB in place of budgets, max_bits the cap, as in
+    TiledCodec.encode_layered."""
     return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, None, False, "encode_image_layered", points, spread,
-                           roi)
+                           roi, target_psnr)
 
 
-def encode_image_layered_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=1, points=alloc.POINTS,
-                            spread=alloc.SPREAD, channels_last=False, roi=None):
+def encode_image_layered_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=None, points=alloc.POINTS,
+                            spread=alloc.SPREAD, channels_last=False, roi=None, target_psnr=None):
     return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, np.uint8, channels_last, "encode_image_layered_u8",
-                           points, spread, roi)
+                           points, spread, roi, target_psnr)
 
 
-def encode_image_layered_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=1, points=alloc.POINTS,
-                             spread=alloc.SPREAD, channels_last=False, roi=None):
+def encode_image_layered_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=None, points=alloc.POINTS,
+                             spread=alloc.SPREAD, channels_last=False, roi=None, target_psnr=None):
     return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, np.uint16, channels_last, "encode_image_layered_u16",
-                           points, spread, roi)
+                           points, spread, roi, target_psnr)
 
 
 def _decode_layered(result, spiht_settings, window, upto, dtype, channels_last, reduce=0):
