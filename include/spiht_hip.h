@@ -755,6 +755,45 @@ int spiht_layer_unpack(spiht_ctx *ctx, const uint8_t *d_layers, uint64_t layers_
                        int64_t upto, const int32_t *d_sel, int64_t S, uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes);
 
 /* ---------------------------------------------------------------------------------------
+ * Overlapping tiles, cross-faded at the seams (csrc/overlap.hip; the rule is spiht_amd/overlap.py).  Every tile is coded with a
+ * margin of m samples of its neighbours (0 <= m, 2 m <= min(th, tw)), and the decoder blends the decoded tiles over the 2m
+ * samples around each seam.  Additions only: the ABI version stays at 2.  All pointers are DEVICE pointers; asynchronous on the
+ * context's stream; argument errors are returned before anything is queued; no byte outside the stated outputs is written.
+ *   spiht_tile_cut_overlap_*  the arguments, checks and limits of spiht_tile_cut_*, and m -> d_tiles: dense
+ *                      [N * T, c, th + 2m, tw + 2m]; coded tile (i, j)'s sample (y, x) is the picture's at row
+ *                      clamp(i th - m + y, 0, H - 1), column clamp(j tw - m + x, 0, W - 1) (np.pad(mode="edge") on all four
+ *                      sides).  m = 0 gives the bytes of spiht_tile_cut_*.  m < 0 or 2 m > min(th, tw): SPIHT_ERR_ARG.
+ *   spiht_tile_blend_*  d_tiles: float64, dense [(i1-i0) * (j1-j0), c, rh, rw], the decodes of the coded tiles of the sub-grid
+ *                      in row-major order, rh >= th + 2m, rw >= tw + 2m (tile (i, j)'s own samples at (m, m)) -> the window
+ *                      [c, wh, ww] at (y0, x0) of the H x W picture: _f64 dense float64; _u8 / _u16 by out_strides (bytes
+ *                      (sc, sh, sw); NULL = dense CHW; what lies between a view's samples is not written).  Along an axis
+ *                      (core t, g tiles) position P lies in the zone of the seam s = k t, 1 <= k < g, when s - m <= P < s + m;
+ *                      there u = P - (s - m), tile k weighs a = 2u + 1 and tile k - 1 b = 4m - a, and tile k's sample index of
+ *                      P is P - k t + m; elsewhere tile P / t has the whole weight.  In float64, every operation rounded once
+ *                      (no fma), the division IEEE's: columns first, r = (bx L + ax R) / (4m) in a column zone, else the one
+ *                      tile's sample; then rows, out = (by r_top + ay r_bottom) / (4m) in a row zone, else r.  _u8 / _u16:
+ *                      out through the decoders' conversion (clip to [0, 1], times 255 / 65535, truncated, NaN -> 0).
+ *                      SPIHT_ERR_ARG: m < 0 or 2 m > min(th, tw), a window that is empty or leaves the picture, a sub-grid
+ *                      that is not inside the grid or misses a tile with weight in the window, rh / rw too small. */
+int spiht_tile_cut_overlap_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
+                              int64_t W, int64_t th, int64_t tw, int64_t m, uint8_t *d_tiles);
+int spiht_tile_cut_overlap_u16(spiht_ctx *ctx, const uint16_t *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
+                               int64_t W, int64_t th, int64_t tw, int64_t m, uint16_t *d_tiles);
+int spiht_tile_cut_overlap_f32(spiht_ctx *ctx, const float *d_img, int64_t N, int64_t c, int64_t H, int64_t W, int64_t th,
+                               int64_t tw, int64_t m, float *d_tiles);
+int spiht_tile_cut_overlap_f64(spiht_ctx *ctx, const double *d_img, int64_t N, int64_t c, int64_t H, int64_t W, int64_t th,
+                               int64_t tw, int64_t m, double *d_tiles);
+int spiht_tile_blend_u8(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W, int64_t th,
+                        int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0, int64_t wh,
+                        int64_t ww, uint8_t *d_out, const int64_t *out_strides);
+int spiht_tile_blend_u16(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W, int64_t th,
+                         int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0, int64_t wh,
+                         int64_t ww, uint16_t *d_out, const int64_t *out_strides);
+int spiht_tile_blend_f64(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W, int64_t th,
+                         int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0, int64_t wh,
+                         int64_t ww, double *d_out);
+
+/* ---------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, every rank codes its own images (the reference's encode / decode
  * are pure functions of one image, src/lib.rs:24-42 -- nothing is exchanged while coding); the ONE exchange of the
  * path is the gather of the finished streams.  It runs on RCCL (ncclAllGather over xGMI), inside this library, on

@@ -10,7 +10,7 @@ import sys
 
 import spiht_amd as _impl
 
-_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode", "rd", "tiles")
+_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode", "rd", "tiles", "overlap")
 for _name in _SUBMODULES:
     # `spiht.spiht` is the reference's compiled extension (src/lib.rs:58-65); here spiht_amd/spiht.py over the C ABI
     _mod = importlib.import_module("spiht_amd." + _name)
@@ -43,4 +43,6 @@ globals().update({_k: getattr(_impl, _k) for _k in ("tiled_reduced_shape",)})
 globals().update({_k: getattr(_impl, _k) for _k in ("roi_map",)})
 # ... target quality: the squared error that the encode calls' target_psnr= stands for
 globals().update({_k: getattr(_impl, _k) for _k in ("target_sqerr",)})
+# ... overlapping tiles: the tiles a window needs when the decoded tiles are cross-faded at the seams (the encode calls' overlap=)
+globals().update({_k: getattr(_impl, _k) for _k in ("window_tiles_overlap",)})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

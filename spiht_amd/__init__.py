@@ -21,3 +21,4 @@ from .tiles import (TiledCodec, TiledResult, TileCurves, TileAllocation, tile_gr
                     decode_image_layered_u8, decode_image_layered_u16, decode_image_layered_window, decode_image_layered_window_u8,
                     decode_image_layered_window_u16)
 from .alloc import roi_map, target_sqerr  # noqa: E402,F401
+from .overlap import window_tiles_overlap  # noqa: E402,F401

@@ -70,6 +70,8 @@ SYMBOLS = [
     "spiht_layer_pack", "spiht_layer_unpack",
     "spiht_sse_tiles_w_f64", "spiht_sse_tiles_w_u8", "spiht_sse_tiles_w_u16",
     "spiht_tile_allocate_target",
+    "spiht_tile_cut_overlap_u8", "spiht_tile_cut_overlap_u16", "spiht_tile_cut_overlap_f32", "spiht_tile_cut_overlap_f64",
+    "spiht_tile_blend_u8", "spiht_tile_blend_u16", "spiht_tile_blend_f64",
 ]
 
 
@@ -238,6 +240,11 @@ def lib():
         # quality layers of a tiled picture: the streams in layer-major order and back
         L.spiht_layer_pack.argtypes = [vp, vp, u64, vp, i64, i64, i64, vp, u64, vp, vp]
         L.spiht_layer_unpack.argtypes = [vp, vp, u64, vp, i64, i64, i64, vp, i64, vp, u64, vp]
+        # overlapping tiles: the cut with the margin m behind the tile, the blend with m behind the tile of the paste's arguments
+        L.spiht_tile_cut_overlap_u8.argtypes = [vp, vp, vp] + [i64] * 7 + [vp]
+        L.spiht_tile_cut_overlap_f32.argtypes = L.spiht_tile_cut_overlap_f64.argtypes = [vp, vp] + [i64] * 7 + [vp]
+        L.spiht_tile_blend_u8.argtypes = [vp, vp] + [i64] * 16 + [vp, vp]
+        L.spiht_tile_blend_f64.argtypes = [vp, vp] + [i64] * 16 + [vp]
         # 16-bit pixels: every *_u16 call takes what its *_u8 sibling takes
         for name in SYMBOLS:
             if name.endswith("_u16"):

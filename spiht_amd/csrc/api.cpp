@@ -63,6 +63,8 @@ int spiht_launch_sse_px(const PxView *px, const void *d_dec, int K, uint64_t *pa
 int spiht_launch_tile_cut(const TileCutArgs *a, int es, int64_t NT, hipStream_t st);
 int spiht_launch_tile_paste(const TilePasteArgs *a, int es, int64_t ntiles, hipStream_t st);
 int spiht_launch_tile_mosaic(const TileMosaicArgs *a, int es, hipStream_t st);
+int spiht_launch_tile_cut_overlap(const TileCutOverlapArgs *a, int es, int64_t NT, hipStream_t st);
+int spiht_launch_tile_blend(const TileBlendArgs *a, int es, hipStream_t st);
 int spiht_launch_tile_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbytes, int64_t T, uint64_t *d_off,
                            uint8_t *d_packed, uint64_t cap, uint32_t *d_lens, hipStream_t st);
 int spiht_launch_tile_unpack(const uint8_t *d_packed, uint64_t packed_bytes, const uint32_t *d_lens, int64_t T, uint64_t *d_off,
@@ -2383,11 +2385,13 @@ extern "C" int spiht_tile_grid(int64_t H, int64_t W, int64_t th, int64_t tw, int
     return SPIHT_OK;
 }
 // in: the picture batch (dense_pic of a float format, or int_pic's checked view)
+// overlap: NULL, or the margin m of spiht_tile_cut_overlap_* (k_tile_cut_overlap; 0 <= m, 2 m <= min(th, tw))
 static int tile_cut(spiht_ctx *ctx, const Pic &in, int es, int64_t N, int64_t c, int64_t H, int64_t W, int64_t th, int64_t tw,
-                    void *d_tiles) {
+                    void *d_tiles, const int64_t *overlap = nullptr) {
     if (!ctx || !in.p || !d_tiles || N < 0 || c < 1 || (uintptr_t)in.p % es || (uintptr_t)d_tiles % es) return SPIHT_ERR_ARG;
     int64_t gy, gx;
     CHK(spiht_tile_grid(H, W, th, tw, &gy, &gx));
+    if (overlap && (*overlap < 0 || 2 * *overlap > std::min(th, tw))) return SPIHT_ERR_ARG;
     if (c > 65535 || (__int128)N * gy * gx > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
     if (N == 0) return SPIHT_OK;
     TileCutArgs a;
@@ -2402,15 +2406,20 @@ static int tile_cut(spiht_ctx *ctx, const Pic &in, int es, int64_t N, int64_t c,
     a.gy = (int32_t)gy; a.gx = (int32_t)gx; a.rows = 0;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
+    if (overlap) {
+        const TileCutOverlapArgs q = {a, (int32_t)*overlap};
+        LAUNCHCHK(spiht_launch_tile_cut_overlap(&q, es, N * gy * gx, ctx->stream));
+        return SPIHT_OK;
+    }
     LAUNCHCHK(spiht_launch_tile_cut(&a, es, N * gy * gx, ctx->stream));
     return SPIHT_OK;
 }
 static int tile_cut_px(int es, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
-                       int64_t W, int64_t th, int64_t tw, void *d_tiles) {
+                       int64_t W, int64_t th, int64_t tw, void *d_tiles, const int64_t *overlap = nullptr) {
     if (N < 0 || c < 1 || H < 1 || W < 1) return SPIHT_ERR_ARG;
     Pic pic;
     CHK(int_pic(d_img, es, false, strides, 4, std::max<int64_t>(N, 1), c, H, W, &pic));
-    return tile_cut(ctx, pic, es, N, c, H, W, th, tw, d_tiles);
+    return tile_cut(ctx, pic, es, N, c, H, W, th, tw, d_tiles, overlap);
 }
 extern "C" int spiht_tile_cut_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
                                  int64_t W, int64_t th, int64_t tw, uint8_t *d_tiles) {
@@ -2427,6 +2436,23 @@ extern "C" int spiht_tile_cut_f32(spiht_ctx *ctx, const float *d_img, int64_t N,
 extern "C" int spiht_tile_cut_f64(spiht_ctx *ctx, const double *d_img, int64_t N, int64_t c, int64_t H, int64_t W, int64_t th,
                                   int64_t tw, double *d_tiles) {
     return tile_cut(ctx, dense_pic(d_img, PIC_F64), 8, N, c, H, W, th, tw, d_tiles);
+}
+// ... with a margin of m samples around every tile (overlap.hip): d_tiles is [N * T, c, th + 2m, tw + 2m]
+extern "C" int spiht_tile_cut_overlap_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t N, int64_t c,
+                                         int64_t H, int64_t W, int64_t th, int64_t tw, int64_t m, uint8_t *d_tiles) {
+    return tile_cut_px(1, ctx, d_img, strides, N, c, H, W, th, tw, d_tiles, &m);
+}
+extern "C" int spiht_tile_cut_overlap_u16(spiht_ctx *ctx, const uint16_t *d_img, const int64_t *strides, int64_t N, int64_t c,
+                                          int64_t H, int64_t W, int64_t th, int64_t tw, int64_t m, uint16_t *d_tiles) {
+    return tile_cut_px(2, ctx, d_img, strides, N, c, H, W, th, tw, d_tiles, &m);
+}
+extern "C" int spiht_tile_cut_overlap_f32(spiht_ctx *ctx, const float *d_img, int64_t N, int64_t c, int64_t H, int64_t W,
+                                          int64_t th, int64_t tw, int64_t m, float *d_tiles) {
+    return tile_cut(ctx, dense_pic(d_img, PIC_F32), 4, N, c, H, W, th, tw, d_tiles, &m);
+}
+extern "C" int spiht_tile_cut_overlap_f64(spiht_ctx *ctx, const double *d_img, int64_t N, int64_t c, int64_t H, int64_t W,
+                                          int64_t th, int64_t tw, int64_t m, double *d_tiles) {
+    return tile_cut(ctx, dense_pic(d_img, PIC_F64), 8, N, c, H, W, th, tw, d_tiles, &m);
 }
 
 // out: the window (dense_pic of a float format, or int_pic's checked view of [c, wh, ww])
@@ -2565,6 +2591,78 @@ extern "C" int spiht_tile_mosaic_f64(spiht_ctx *ctx, const double *d_tiles, int6
     if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
     return tile_mosaic(ctx, d_tiles, dense_pic(d_out, PIC_F64, true), 8, c, rh, rw, oy, ox, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh,
                        ww);
+}
+
+// overlapping tiles: the cross-fade of the float64 decodes of a sub-grid into a window (k_tile_blend).  The tiles (lo, hi)
+// with weight at position P of an axis of g tiles of t: the two of a seam's zone, else the one that owns P.
+static void blend_axis_tiles(int64_t P, int64_t g, int64_t t, int64_t m, int64_t *lo, int64_t *hi) {
+    const int64_t k = (P + m) / t;
+    if (k >= 1 && k < g && P + m - k * t < 2 * m) {
+        *lo = k - 1; *hi = k;
+    } else {
+        *lo = *hi = P / t;
+    }
+}
+// out: the window (dense_pic of float64, or int_pic's checked view of [c, wh, ww]); es: its bytes per sample
+static int tile_blend(spiht_ctx *ctx, const double *d_tiles, const Pic &out, int es, int64_t c, int64_t rh, int64_t rw, int64_t H,
+                      int64_t W, int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                      int64_t x0, int64_t wh, int64_t ww) {
+    if (!ctx || !d_tiles || !out.p || c < 1 || (uintptr_t)d_tiles % 8 || (uintptr_t)out.p % es) return SPIHT_ERR_ARG;
+    int64_t gy, gx;
+    CHK(spiht_tile_grid(H, W, th, tw, &gy, &gx));
+    if (m < 0 || 2 * m > std::min(th, tw)) return SPIHT_ERR_ARG;
+    if (rh < th + 2 * m || rw < tw + 2 * m || rh > th + (1 << 25) || rw > tw + (1 << 25)) return SPIHT_ERR_ARG;
+    if (i0 < 0 || i1 <= i0 || i1 > gy || j0 < 0 || j1 <= j0 || j1 > gx) return SPIHT_ERR_ARG;
+    // the window lies in the picture, and the sub-grid holds every tile with weight in it
+    if (y0 < 0 || x0 < 0 || wh < 1 || ww < 1 || y0 + wh > H || x0 + ww > W) return SPIHT_ERR_ARG;
+    int64_t lo, hi, unused;
+    blend_axis_tiles(y0, gy, th, m, &lo, &unused);
+    blend_axis_tiles(y0 + wh - 1, gy, th, m, &unused, &hi);
+    if (lo < i0 || hi >= i1) return SPIHT_ERR_ARG;
+    blend_axis_tiles(x0, gx, tw, m, &lo, &unused);
+    blend_axis_tiles(x0 + ww - 1, gx, tw, m, &unused, &hi);
+    if (lo < j0 || hi >= j1) return SPIHT_ERR_ARG;
+    if (c > 65535 || (__int128)(i1 - i0) * (j1 - j0) > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    TileBlendArgs a;
+    a.tiles = d_tiles;
+    a.out = (uint8_t *)out.p;
+    if (out.integer()) {
+        a.sc = out.px.sc; a.sh = out.px.sh; a.sw = out.px.sw;
+    } else {
+        a.sw = es; a.sh = ww * es; a.sc = wh * a.sh;
+    }
+    a.c = (int32_t)c; a.rh = (int32_t)rh; a.rw = (int32_t)rw; a.th = (int32_t)th; a.tw = (int32_t)tw; a.m = (int32_t)m;
+    a.gy = (int32_t)gy; a.gx = (int32_t)gx; a.i0 = (int32_t)i0; a.j0 = (int32_t)j0; a.nj = (int32_t)(j1 - j0);
+    a.y0 = (int32_t)y0; a.x0 = (int32_t)x0; a.wh = (int32_t)wh; a.ww = (int32_t)ww; a.rows = 0;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    LAUNCHCHK(spiht_launch_tile_blend(&a, es, ctx->stream));
+    return SPIHT_OK;
+}
+static int tile_blend_px(int es, spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                         int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
+                         int64_t wh, int64_t ww, void *d_out, const int64_t *out_strides) {
+    if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
+    Pic pic;
+    CHK(int_pic(d_out, es, true, out_strides, 3, 1, c, wh, ww, &pic));
+    return tile_blend(ctx, d_tiles, pic, es, c, rh, rw, H, W, th, tw, m, i0, i1, j0, j1, y0, x0, wh, ww);
+}
+extern "C" int spiht_tile_blend_u8(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                                   int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                                   int64_t x0, int64_t wh, int64_t ww, uint8_t *d_out, const int64_t *out_strides) {
+    return tile_blend_px(1, ctx, d_tiles, c, rh, rw, H, W, th, tw, m, i0, i1, j0, j1, y0, x0, wh, ww, d_out, out_strides);
+}
+extern "C" int spiht_tile_blend_u16(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                                    int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                                    int64_t x0, int64_t wh, int64_t ww, uint16_t *d_out, const int64_t *out_strides) {
+    return tile_blend_px(2, ctx, d_tiles, c, rh, rw, H, W, th, tw, m, i0, i1, j0, j1, y0, x0, wh, ww, d_out, out_strides);
+}
+extern "C" int spiht_tile_blend_f64(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                                    int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                                    int64_t x0, int64_t wh, int64_t ww, double *d_out) {
+    if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
+    return tile_blend(ctx, d_tiles, dense_pic(d_out, PIC_F64, true), 8, c, rh, rw, H, W, th, tw, m, i0, i1, j0, j1, y0, x0, wh,
+                      ww);
 }
 
 // the checks pack and unpack share; the scratch: uint64 [T] byte lengths (pack), uint64 [T] offsets

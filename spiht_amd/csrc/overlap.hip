@@ -1,0 +1,193 @@
+// Overlapping tiles (gfx950): every tile coded with a margin of m samples of its neighbours, the decoded tiles cross-faded
+// over the 2m samples around each seam.  The rule is spiht_amd/overlap.py.
+//   k_tile_cut_overlap  picture batch [N, c, H, W] -> dense tile batch [N * T, c, th + 2m, tw + 2m]; coded tile (i, j)'s sample
+//                       (y, x) is the picture's at row clamp(i th - m + y, 0, H - 1), column clamp(j tw - m + x, 0, W - 1):
+//                       k_tile_cut with an origin and a clamp on all four sides (m = 0 gives its bytes)
+//   k_tile_blend        dense float64 tile batch of a sub-grid -> a window of the picture.  Where k_tile_paste copies, this does
+//                       arithmetic: in the zone of a seam, (b * one tile + a * the other) / 4m, columns first, then rows, every
+//                       operation rounded once (this file is built with -ffp-contract=off) and the division IEEE's;
+//                       elsewhere the one tile's sample.  Output float64, or 8 / 16 bits by the decoder's conversion.
+// Workgroups own rows of the window, as k_tile_mosaic's do: whether a row lies in a zone, its two tile rows and their weights
+// are the same for all lanes of the row; only the column zone is per lane.  Stores follow tiles.hip: 16 bytes at a 16-byte-
+// aligned address wherever the destination is contiguous, element by element in front of the first and behind the last.
+#include "tiles.h"
+
+// ---- cut ---------------------------------------------------------------------------------------------------------------------
+// One row of a coded tile: n elements of ES bytes to the dense dst, element k from picture column clamp(X0 + k, 0, W - 1) of the
+// row at src (stride ss).  The lanes lane, lane + nlanes, ... of the caller share the row.  A 16-byte vector is one 16-byte load
+// where its columns are contiguous in the source, unclamped and aligned.
+template <int ES>
+__device__ __forceinline__ void cut_row(uint8_t *dst, const uint8_t *src, int64_t ss, int n, int X0, int W, int lane, int nlanes) {
+    typedef typename ElemOf<ES>::type T;
+    constexpr int EPV = 16 / ES;
+    auto at = [&](int k) { return src + (int64_t)min(max(X0 + k, 0), W - 1) * ss; };
+    const int a = (int)((uintptr_t)dst & 15), nbytes = n * ES;
+    const int nvec = (a + nbytes + 15) >> 4;
+    for (int v = lane; v < nvec; v += nlanes) {
+        const int p = 16 * v - a;  // bytes from dst; a multiple of ES, negative in the first vector of an unaligned row
+        const int k0 = p / ES;
+        if (p >= 0 && p + 16 <= nbytes) {
+            const int X = X0 + k0;
+            const uint8_t *s = src + (int64_t)X * ss;  // (formed, not read, where X is clamped)
+            uint4 q;
+            if (ss == ES && X >= 0 && X + EPV <= W && ((uintptr_t)s & 15) == 0) {
+                q = *reinterpret_cast<const uint4 *>(s);
+            } else {
+                T e[EPV];
+#pragma unroll
+                for (int i = 0; i < EPV; i++) e[i] = *reinterpret_cast<const T *>(at(k0 + i));
+                __builtin_memcpy(&q, e, 16);
+            }
+            *reinterpret_cast<uint4 *>(dst + p) = q;
+        } else {
+#pragma unroll
+            for (int i = 0; i < EPV; i++) {
+                const int k = k0 + i;
+                if (k >= 0 && k < n) *reinterpret_cast<T *>(dst + (int64_t)k * ES) = *reinterpret_cast<const T *>(at(k));
+            }
+        }
+    }
+}
+
+// grid (N * T, c, row chunks); block (bx, by): bx lanes along a row, by rows at a time
+template <int ES>
+__global__ __launch_bounds__(TL_THREADS) void k_tile_cut_overlap(const TileCutOverlapArgs q) {
+    const TileCutArgs &a = q.cut;
+    const uint32_t nt = blockIdx.x, ch = blockIdx.y, T = (uint32_t)a.gy * (uint32_t)a.gx;
+    const uint32_t n = nt / T, t = nt - n * T;
+    const int i = (int)(t / (uint32_t)a.gx), j = (int)(t - (uint32_t)i * (uint32_t)a.gx);
+    const int ch_h = a.th + 2 * q.m, ch_w = a.tw + 2 * q.m;  // the coded tile
+    const uint8_t *src0 = a.in + (int64_t)n * a.sb + (int64_t)ch * a.sc;
+    uint8_t *dst0 = a.out + ((size_t)nt * a.c + ch) * (size_t)ch_h * ch_w * ES;
+    const int ya = (int)blockIdx.z * a.rows, yb = min(ya + a.rows, ch_h);
+    for (int y = ya + (int)threadIdx.y; y < yb; y += (int)blockDim.y) {
+        const int Y = min(max(i * a.th - q.m + y, 0), a.H - 1);
+        cut_row<ES>(dst0 + (size_t)y * ch_w * ES, src0 + (int64_t)Y * a.sh, a.sw, ch_w, j * a.tw - q.m, a.W, (int)threadIdx.x,
+                    (int)blockDim.x);
+    }
+}
+
+// ---- blend -------------------------------------------------------------------------------------------------------------------
+// what a sample of the window is stored as.  8 / 16 bits: the decoder's conversion of a float64 sample (dwt.hip,
+// px8_store_value / px16_store_value): clip to [0, 1], times 255 / 65535, truncate; NaN -> 0 (fmax / fmin return the number
+// of a pair with a NaN)
+template <int ES> __device__ __forceinline__ typename ElemOf<ES>::type blend_store_value(double v) {
+    if constexpr (ES == 8) {
+        return (uint64_t)__double_as_longlong(v);
+    } else {
+        const double c = fmin(fmax(v, 0.0), 1.0);
+        const double s = c * (ES == 1 ? 255.0 : 65535.0);
+        return (typename ElemOf<ES>::type)(uint32_t)s;
+    }
+}
+
+// grid (row chunks of the window, c); block (bx, by): bx lanes along a window row, by rows at a time
+template <int ES>
+__global__ __launch_bounds__(TL_THREADS) void k_tile_blend(const TileBlendArgs a) {
+    typedef typename ElemOf<ES>::type T;
+    constexpr int EPV = 16 / ES;
+    const uint32_t ch = blockIdx.y;
+    const int m = a.m, lane = (int)threadIdx.x, nlanes = (int)blockDim.x;
+    const size_t plane = (size_t)a.rh * a.rw;
+    const int64_t tstep = (int64_t)((size_t)a.c * plane);  // doubles from a tile to its right neighbour
+    const double fm = (double)(4 * m);
+    const uint32_t tw = (uint32_t)a.tw;
+    const int64_t ya = (int64_t)blockIdx.x * a.rows;
+    const int yb = (int)min(ya + a.rows, (int64_t)a.wh);
+    for (int y = (int)ya + (int)threadIdx.y; y < yb; y += (int)blockDim.y) {
+        // the row: one tile row, or the two around a seam with their weights
+        const int Y = a.y0 + y, ky = (Y + m) / a.th, uy = Y + m - ky * a.th;
+        const bool zy = ky >= 1 && ky < a.gy && uy < 2 * m;
+        const int it = zy ? ky - 1 : (uy >= m ? ky : ky - 1);  // outside a zone: Y / th
+        const double ay = (double)(2 * uy + 1), by = (double)(4 * m - (2 * uy + 1));
+        // the row's sample of tile column j0, first sample of the coded tile
+        const double *top = a.tiles + ((size_t)(it - a.i0) * a.nj * a.c + ch) * plane + (size_t)(Y - it * a.th + m) * a.rw;
+        const double *bot = zy ? a.tiles + ((size_t)(ky - a.i0) * a.nj * a.c + ch) * plane + (size_t)uy * a.rw : top;
+        auto hval = [&](const double *row, int X) -> double {  // the columns' blend of one tile row at picture column X
+            const uint32_t kx = (uint32_t)(X + m) / tw, ux = (uint32_t)(X + m) - kx * tw;
+            if (kx >= 1 && (int)kx < a.gx && (int)ux < 2 * m) {
+                const double L = row[(int64_t)((int)kx - 1 - a.j0) * tstep + (ux + tw)];
+                const double R = row[(int64_t)((int)kx - a.j0) * tstep + ux];
+                const double ax = (double)(2 * ux + 1), bx = (double)(4 * m - (int)(2 * ux + 1));
+                return (bx * L + ax * R) / fm;
+            }
+            const int j = (int)ux >= m ? (int)kx : (int)kx - 1;  // X / tw
+            return row[(int64_t)(j - a.j0) * tstep + (X - j * a.tw + m)];
+        };
+        auto val = [&](int X) -> T {
+            double r = hval(top, X);
+            if (zy) r = (by * r + ay * hval(bot, X)) / fm;
+            return blend_store_value<ES>(r);
+        };
+        uint8_t *dst = a.out + (int64_t)ch * a.sc + (int64_t)y * a.sh;
+        const int n = a.ww;
+        if (a.sw != ES) {  // a strided destination (HWC, RGBA): what lies between the elements is not written
+            for (int k = lane; k < n; k += nlanes) *reinterpret_cast<T *>(dst + (int64_t)k * a.sw) = val(a.x0 + k);
+            continue;
+        }
+        const int al = (int)((uintptr_t)dst & 15);
+        const int64_t nbytes = (int64_t)n * ES;
+        const int nvec = (int)((al + nbytes + 15) >> 4);
+        for (int v = lane; v < nvec; v += nlanes) {
+            const int64_t p = 16 * (int64_t)v - al;  // bytes from dst; negative in the first vector of an unaligned row
+            const int k0 = (int)(p / ES);
+            if (p >= 0 && p + 16 <= nbytes) {
+                T e[EPV];
+#pragma unroll
+                for (int i = 0; i < EPV; i++) e[i] = val(a.x0 + k0 + i);
+                uint4 q;
+                __builtin_memcpy(&q, e, 16);
+                *reinterpret_cast<uint4 *>(dst + p) = q;
+            } else {
+#pragma unroll
+                for (int i = 0; i < EPV; i++) {
+                    const int k = k0 + i;
+                    if (k >= 0 && k < n) *reinterpret_cast<T *>(dst + (int64_t)k * ES) = val(a.x0 + k);
+                }
+            }
+        }
+    }
+}
+
+// ---- host launchers ----------------------------------------------------------------------------------------------------------
+template <int ES>
+static int launch_cut_overlap(TileCutOverlapArgs a, int64_t NT, hipStream_t st) {
+    dim3 block;
+    uint32_t gz;
+    const int64_t cw = (int64_t)a.cut.tw + 2 * a.m, chh = (int64_t)a.cut.th + 2 * a.m;
+    row_blocks((cw * ES + 15) / 16 + 1, cw * ES, chh, &block, &a.cut.rows, &gz);
+    hipLaunchKernelGGL(k_tile_cut_overlap<ES>, dim3((uint32_t)NT, a.cut.c, gz), block, 0, st, a);
+    return (int)hipGetLastError();
+}
+extern "C" int spiht_launch_tile_cut_overlap(const TileCutOverlapArgs *a, int es, int64_t NT, hipStream_t st) {
+    switch (es) {
+    case 1: return launch_cut_overlap<1>(*a, NT, st);
+    case 2: return launch_cut_overlap<2>(*a, NT, st);
+    case 4: return launch_cut_overlap<4>(*a, NT, st);
+    default: return launch_cut_overlap<8>(*a, NT, st);
+    }
+}
+
+template <int ES>
+static int launch_blend(TileBlendArgs a, hipStream_t st) {
+    dim3 block;
+    uint32_t gz;
+    const int64_t n = a.ww;  // a workgroup's rows are the window's
+    row_blocks(a.sw == ES ? (n * ES + 15) / 16 + 1 : n, n * ES, a.wh, &block, &a.rows, &gz);
+    // a small window: fewer rows per workgroup, down to one pass of the block, until there are workgroups for every CU a few
+    // times over (as the mosaic)
+    while ((int64_t)gz * a.c < TL_MOSAIC_WGS && a.rows > (int)block.y) {
+        a.rows = std::max<int>((int)block.y, a.rows / 2 / (int)block.y * (int)block.y);
+        gz = (uint32_t)((a.wh + a.rows - 1) / a.rows);
+    }
+    hipLaunchKernelGGL(k_tile_blend<ES>, dim3(gz, a.c), block, 0, st, a);
+    return (int)hipGetLastError();
+}
+// es: bytes per sample of the OUTPUT: 8 float64, 1 / 2 the 8- / 16-bit conversion
+extern "C" int spiht_launch_tile_blend(const TileBlendArgs *a, int es, hipStream_t st) {
+    switch (es) {
+    case 1: return launch_blend<1>(*a, st);
+    case 2: return launch_blend<2>(*a, st);
+    default: return launch_blend<8>(*a, st);
+    }
+}

@@ -1,6 +1,9 @@
-// Tiled pictures (tiles.hip): the arguments of the four copy kernels, shared with api.cpp, which checks them.
+// Tiled pictures (tiles.hip, overlap.hip): the arguments of the copy kernels and of the blend, shared with api.cpp, which checks
+// them, and what the kernels' files share.
 #pragma once
 #include "common.h"
+
+#include <algorithm>
 
 #define TL_THREADS 256
 #define TL_CHUNK 16384        // pack / unpack: bytes of one stream a workgroup moves (four 16-byte stores per lane)
@@ -36,3 +39,41 @@ struct TileMosaicArgs {
     int32_t c, rh, rw, oy, ox, th, tw, i0, j0, nj, y0, x0, wh, ww;
     int32_t rows;            // window rows per workgroup (a multiple of the workgroup's y extent)
 };
+
+// overlapping tiles (overlap.hip).  cut: TileCutArgs with a margin of m picture samples around every tile, clamped on all
+// four sides -> the dense tile batch [N * gy * gx, c, th + 2m, tw + 2m]
+struct TileCutOverlapArgs {
+    TileCutArgs cut;         // rows: rows of the CODED tile per workgroup
+    int32_t m;
+};
+
+// blend: the dense float64 tile batch [ni * nj, c, rh, rw] of the sub-grid, every tile with its margin of m (its core at
+// (m, m)) -> the window [c, wh, ww] at (y0, x0) of the picture, cross-faded over the 2m samples around each seam; float64, or
+// 8- / 16-bit samples by byte strides.  Workgroups own rows of the window.
+struct TileBlendArgs {
+    const double *tiles;
+    uint8_t *out;
+    int64_t sc, sh, sw;      // bytes
+    int32_t c, rh, rw, th, tw, m, gy, gx, i0, j0, nj, y0, x0, wh, ww;
+    int32_t rows;            // window rows per workgroup (a multiple of the workgroup's y extent)
+};
+
+// the unsigned integer of ES bytes: what a copy moves of an element
+template <int ES> struct ElemOf;
+template <> struct ElemOf<1> { typedef uint8_t type; };
+template <> struct ElemOf<2> { typedef uint16_t type; };
+template <> struct ElemOf<4> { typedef uint32_t type; };
+template <> struct ElemOf<8> { typedef uint64_t type; };
+
+// The workgroup's shape for rows of `units` pieces (16-byte vectors, or elements of a strided row) of row_bytes bytes, `rows`
+// of them: bx lanes along the row (a power of two), 256 / bx rows at a time, about TL_BLOCK_BYTES per workgroup.
+static inline void row_blocks(int64_t units, int64_t row_bytes, int64_t rows, dim3 *block, int *rows_per_wg, uint32_t *gz) {
+    int bx = 1;
+    while (bx < units && bx < TL_THREADS) bx *= 2;
+    const int by = TL_THREADS / bx;
+    int64_t per = (int64_t)by * std::max<int64_t>(1, TL_BLOCK_BYTES / std::max<int64_t>(1, row_bytes * by));
+    if ((rows + per - 1) / per > 65535) per = ((rows + 65534) / 65535 + by - 1) / by * by;
+    *block = dim3(bx, by);
+    *rows_per_wg = (int)per;
+    *gz = (uint32_t)std::max<int64_t>(1, (rows + per - 1) / per);
+}

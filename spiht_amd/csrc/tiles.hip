@@ -15,14 +15,6 @@
 #include "tiles.h"
 #include "copy_bytes.h"
 
-#include <algorithm>
-
-template <int ES> struct ElemOf;
-template <> struct ElemOf<1> { typedef uint8_t type; };
-template <> struct ElemOf<2> { typedef uint16_t type; };
-template <> struct ElemOf<4> { typedef uint32_t type; };
-template <> struct ElemOf<8> { typedef uint64_t type; };
-
 // One row: n elements of ES bytes, element k from src + min(k, nvalid - 1) * ss (replication past nvalid) to dst + k * ds.
 // The lanes lane, lane + nlanes, ... of the caller share the row.  dst, src and the strides are multiples of ES.
 template <int ES>
@@ -228,19 +220,6 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_unpack(const uint8_t *__res
 }
 
 // ---- host launchers ------------------------------------------------------------------------------------------------------
-
-// The workgroup's shape for rows of `units` pieces (16-byte vectors, or elements of a strided row) of row_bytes bytes, `rows`
-// of them: bx lanes along the row (a power of two), 256 / bx rows at a time, about TL_BLOCK_BYTES per workgroup.
-static void row_blocks(int64_t units, int64_t row_bytes, int64_t rows, dim3 *block, int *rows_per_wg, uint32_t *gz) {
-    int bx = 1;
-    while (bx < units && bx < TL_THREADS) bx *= 2;
-    const int by = TL_THREADS / bx;
-    int64_t per = (int64_t)by * std::max<int64_t>(1, TL_BLOCK_BYTES / std::max<int64_t>(1, row_bytes * by));
-    if ((rows + per - 1) / per > 65535) per = ((rows + 65534) / 65535 + by - 1) / by * by;
-    *block = dim3(bx, by);
-    *rows_per_wg = (int)per;
-    *gz = (uint32_t)std::max<int64_t>(1, (rows + per - 1) / per);
-}
 
 template <int ES>
 static int launch_cut(TileCutArgs a, int64_t NT, hipStream_t st) {

@@ -46,6 +46,8 @@ _ARGS = [  # (flag, type, default, help): the reference tool's options, then our
                             "picture's); decodes after every layer"),
     ("--layer-psnr", str, None, "with --tile N --allocate rd: quality layers that reach the PSNRs DB0,DB1,... in dB (strictly "
                                 "increasing), --bpp the cap; decodes after every layer"),
+    ("--overlap", int, 0, "with --tile N: code every tile with a margin of M pixels of its neighbours (2 M <= N) and cross-fade the "
+                          "decoded tiles over the 2 M pixels around each seam; goes with --window, --allocate rd and --layers"),
 ]
 
 
@@ -136,14 +138,19 @@ def main_tiled(args, picture):
         raise SystemExit("--psnr and --layer-psnr with --tile need --allocate rd")
     if args.psnr is not None and (args.layer_psnr is not None or args.layers is not None):
         raise SystemExit("--psnr is one rate; the layers' PSNRs are --layer-psnr DB0,DB1,...")
+    if args.overlap and (args.roi or args.psnr is not None or args.layer_psnr is not None or args.reduce):
+        raise SystemExit("--overlap goes with --window, --allocate rd and --layers; not with --roi, --psnr, --layer-psnr or --reduce")
     p = plan(args, c, h, w)
-    level = default_level(args.tile, args.tile) if args.level is None else args.level
-    print("encoding %d x %d x %d at %.3f bpp as tiles of %d x %d" % (c, h, w, args.bpp, args.tile, args.tile))
+    # (the level is the coded tile's: with --overlap M a picture of N + 2 M)
+    coded = args.tile + 2 * args.overlap
+    level = default_level(coded, coded) if args.level is None else args.level
+    print("encoding %d x %d x %d at %.3f bpp as tiles of %d x %d%s" % (c, h, w, args.bpp, args.tile, args.tile,
+                                                                      ", overlap %d" % args.overlap if args.overlap else ""))
     roi = roi_from_args(args, h, w)
     if args.layers is not None or args.layer_psnr is not None:
         return main_layered(args, picture, p, level, roi)
     enc, secs = timed(lambda: encode_image_tiled(picture, args.tile, p.settings, level, p.max_bits, args.allocate, args.points,
-                                                 roi=roi, target_psnr=args.psnr))
+                                                 roi=roi, target_psnr=args.psnr, overlap=args.overlap))
     gy, gx = enc.grid()
     print("encoded in %.3f s: %d x %d tiles, %.2f KiB" % (secs, gy, gx, len(enc.encoded_bytes) / 1024))
     if args.psnr is not None:
@@ -212,7 +219,7 @@ def main_layered(args, picture, p, level, roi=None):
             raise SystemExit("--layer-psnr %s: DB0,DB1,... in dB" % args.layer_psnr)
     try:
         enc, secs = timed(lambda: encode_image_layered(picture, args.tile, p.settings, level, p.max_bits, layers, args.points,
-                                                       roi=roi, target_psnr=targets))
+                                                       roi=roi, target_psnr=targets, overlap=args.overlap))
     except ValueError as e:
         if targets is None:
             raise
@@ -252,8 +259,8 @@ def main(args):
     picture = imload(args.image_filename)
     if args.tile is not None:
         return main_tiled(args, picture)
-    if args.window or args.allocate or args.layers or args.roi or args.layer_psnr:
-        raise SystemExit("--window, --allocate, --layers, --layer-psnr and --roi need --tile")
+    if args.window or args.allocate or args.layers or args.roi or args.layer_psnr or args.overlap:
+        raise SystemExit("--window, --allocate, --layers, --layer-psnr, --roi and --overlap need --tile")
     c, h, w = picture.shape
     p = plan(args, c, h, w)
     if args.load:

@@ -36,6 +36,12 @@ Reduced resolution (every decode call's reduce=k; tiled_reduced_shape): the tile
 reduced decode and assembled into the picture at 1/2^k size by one more copy (k_tile_mosaic, spiht_tile_mosaic_*), which takes
 every sample from the centred window of its tile's reduced decode.  It composes with windows (given in the reduced picture's
 coordinates) and with quality layers.
+
+Overlapping tiles (the constructor's and the encode calls' overlap=m; overlap.py is the rule, csrc/overlap.hip the kernels): every
+tile is coded with a margin of m samples of its neighbours (spiht_tile_cut_overlap_*), and every decode call decodes the tiles in
+float64 and cross-fades them over the 2m samples around each seam (spiht_tile_blend_*), so the seams of independent tiles do
+not show.  The tile codec is one of slightly larger tiles; the coder, pack / unpack and the layer copies are untouched, results
+carry the overlap (containers SPOL / SPOQ), and overlap=0 is the path without it in every byte.
 """
 import ctypes as C
 import struct
@@ -45,6 +51,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib, alloc
+from . import overlap as _overlap
 from .batch import BatchCodec, DeviceArray
 from .spiht_wrapper import (ENCODER_DECODER_VERSION, EncodingResult, SpihtSettings, _check_aligned, _check_int_view,
                             _check_version, _is_dtype, _wavelet_mode_ids)
@@ -55,6 +62,11 @@ _HEADER = struct.Struct("<4sBBHIIII")
 LAYERED_MAGIC = b"SPTQ"
 LAYERED_VERSION = 1
 _LAYERED_HEADER = struct.Struct("<4sBBHIIIIHH")
+# overlapping tiles (overlap > 0): magics of their own, the same header followed by a u32 overlap, then the same tables and bytes
+OVERLAP_MAGIC = b"SPOL"
+OVERLAP_LAYERED_MAGIC = b"SPOQ"
+OVERLAP_VERSION = 1
+_OVERLAP_FIELD = struct.Struct("<I")
 
 
 def _tile_arg(tile):
@@ -116,10 +128,38 @@ def tiled_reduced_shape(H, W, tile, settings, level, reduce):
     return dict(level=lv.value, **{k: t.value for k, t in zip(_REDUCED_NAMES, v)})
 
 
+def _container_head(header, magic, overlap_magic, version, m, fields):
+    """the header of either container: with overlap = m > 0 the other magic and a u32 m behind the same fields"""
+    m = int(m)
+    if m == 0:
+        return header.pack(magic, version, *fields)
+    if m < 0 or m >= 2 ** 32:
+        raise ValueError("overlap %d does not fit the container" % m)
+    return header.pack(overlap_magic, OVERLAP_VERSION, *fields) + _OVERLAP_FIELD.pack(m)
+
+
+def _container_overlap(data, header, overlapped, version, known, what, th, tw):
+    """the reader's side: the version check of the form the magic named -> (overlap, bytes in front of the tables)"""
+    if not overlapped:
+        if version != known:
+            raise ValueError("%s container version %d, this reader knows %d" % (what, version, known))
+        return 0, header.size
+    if version != OVERLAP_VERSION:
+        raise ValueError("%s container with overlap, version %d, this reader knows %d" % (what, version, OVERLAP_VERSION))
+    if len(data) < header.size + _OVERLAP_FIELD.size:
+        raise ValueError("a %s container with overlap has a %d-byte header; got %d bytes"
+                         % (what, header.size + _OVERLAP_FIELD.size, len(data)))
+    m, = _OVERLAP_FIELD.unpack_from(data, header.size)
+    if m < 1 or 2 * m > min(th, tw):
+        raise ValueError("overlap = %d of tiles of %d x %d: 1 <= overlap and 2 * overlap <= the shorter tile side" % (m, th, tw))
+    return m, header.size + _OVERLAP_FIELD.size
+
+
 @dataclass
 class TiledResult:
     """The streams of one tiled picture.  h, w, c: the PICTURE; th, tw: the tile; max_n, nbytes: one entry per tile,
-    row-major; encoded_bytes: the tiles' streams one behind the other."""
+    row-major; encoded_bytes: the tiles' streams one behind the other.  overlap = m > 0: every tile was coded with a margin of
+    m samples of its neighbours (overlap.py), so a tile's stream is that of a (th + 2m) x (tw + 2m) picture."""
     h: int
     w: int
     c: int
@@ -130,6 +170,7 @@ class TiledResult:
     nbytes: List[int]
     encoded_bytes: bytes
     _encoding_version: str = ENCODER_DECODER_VERSION
+    overlap: int = 0
 
     def grid(self):
         return tile_grid(self.h, self.w, self.th, self.tw)
@@ -138,52 +179,53 @@ class TiledResult:
         return np.concatenate(([0], np.cumsum(np.asarray(self.nbytes, dtype=np.int64))))
 
     def tile(self, i, j):
-        """Tile (i, j) as an ordinary EncodingResult with h = th, w = tw: what encode_image gives for the tile's pixels,
-        and a stream the reference itself decodes."""
+        """Tile (i, j) as an ordinary EncodingResult with h = th + 2 overlap, w = tw + 2 overlap: what encode_image gives for
+        the (coded) tile's pixels, and a stream the reference itself decodes."""
         gy, gx = self.grid()
         if not (0 <= i < gy and 0 <= j < gx):
             raise IndexError("tile (%d, %d) of a %d x %d grid" % (i, j, gy, gx))
         t = i * gx + j
         off = self._offsets()
-        return EncodingResult(self.encoded_bytes[int(off[t]):int(off[t + 1])], self.th, self.tw, self.c, int(self.max_n[t]),
-                              self.level, self._encoding_version)
+        return EncodingResult(self.encoded_bytes[int(off[t]):int(off[t + 1])], self.th + 2 * self.overlap,
+                              self.tw + 2 * self.overlap, self.c, int(self.max_n[t]), self.level, self._encoding_version)
 
     def to_bytes(self):
         """The container, little-endian: b"SPTL", u8 version = 1, u8 level (255 = None), u16 c, u32 H, W, th, tw, then
-        T x u32 nbytes, T x u8 max_n, then the packed streams."""
+        T x u32 nbytes, T x u8 max_n, then the packed streams.  overlap > 0: b"SPOL", version 1, and a u32 overlap behind the
+        header; overlap = 0 writes the bytes it always wrote."""
         T = len(self.nbytes)
         if len(self.max_n) != T or sum(self.nbytes) != len(self.encoded_bytes):
             raise ValueError("the tables do not describe %d tiles of %d bytes" % (T, len(self.encoded_bytes)))
         if self.level is not None and not 0 <= int(self.level) < 255:
             raise ValueError("level %r does not fit the container" % (self.level,))
         level = 255 if self.level is None else int(self.level)
-        return (_HEADER.pack(MAGIC, CONTAINER_VERSION, level, self.c, self.h, self.w, self.th, self.tw)
+        return (_container_head(_HEADER, MAGIC, OVERLAP_MAGIC, CONTAINER_VERSION, self.overlap,
+                                (level, self.c, self.h, self.w, self.th, self.tw))
                 + np.asarray(self.nbytes, dtype="<u4").tobytes() + np.asarray(self.max_n, dtype=np.uint8).tobytes()
                 + bytes(self.encoded_bytes))
 
     @staticmethod
     def from_bytes(data):
-        """Inverse of to_bytes.  ValueError on a wrong magic or version, a short table, or a length sum that is not the
-        remaining byte count."""
+        """Inverse of to_bytes; the magic tells which of the two forms.  ValueError on a wrong magic or version, a short table,
+        a length sum that is not the remaining byte count, or an overlap that is 0 or more than half a tile side."""
         data = bytes(data)
         if len(data) < _HEADER.size:
             raise ValueError("a tiled container has a %d-byte header; got %d bytes" % (_HEADER.size, len(data)))
         magic, version, level, c, h, w, th, tw = _HEADER.unpack_from(data, 0)
-        if magic != MAGIC:
+        if magic not in (MAGIC, OVERLAP_MAGIC):
             raise ValueError("not a tiled container: magic %r" % (magic,))
-        if version != CONTAINER_VERSION:
-            raise ValueError("tiled container version %d, this reader knows %d" % (version, CONTAINER_VERSION))
+        m, head = _container_overlap(data, _HEADER, magic == OVERLAP_MAGIC, version, CONTAINER_VERSION, "tiled", th, tw)
         gy, gx = tile_grid(h, w, th, tw)
         T = gy * gx
-        if len(data) < _HEADER.size + 5 * T:
-            raise ValueError("the tables of %d tiles need %d bytes; %d are left" % (T, 5 * T, len(data) - _HEADER.size))
-        nbytes = np.frombuffer(data, dtype="<u4", count=T, offset=_HEADER.size).astype(np.int64)
-        max_n = np.frombuffer(data, dtype=np.uint8, count=T, offset=_HEADER.size + 4 * T)
-        rest = len(data) - _HEADER.size - 5 * T
+        if len(data) < head + 5 * T:
+            raise ValueError("the tables of %d tiles need %d bytes; %d are left" % (T, 5 * T, len(data) - head))
+        nbytes = np.frombuffer(data, dtype="<u4", count=T, offset=head).astype(np.int64)
+        max_n = np.frombuffer(data, dtype=np.uint8, count=T, offset=head + 4 * T)
+        rest = len(data) - head - 5 * T
         if int(nbytes.sum()) != rest:
             raise ValueError("the table's lengths add up to %d bytes; %d follow it" % (int(nbytes.sum()), rest))
         return TiledResult(h, w, c, th, tw, None if level == 255 else level, [int(v) for v in max_n], [int(v) for v in nbytes],
-                           data[_HEADER.size + 5 * T:])
+                           data[head + 5 * T:], overlap=m)
 
 
 @dataclass
@@ -201,6 +243,7 @@ class LayeredResult:
     cum: List[List[int]]
     encoded_bytes: bytes
     _encoding_version: str = ENCODER_DECODER_VERSION
+    overlap: int = 0
 
     @property
     def layers(self):
@@ -227,7 +270,7 @@ class LayeredResult:
     def layer_ends(self):
         """the Q lengths of to_bytes() at which each layer is complete: where a server cuts the file"""
         cum, lens, _ = self._table()
-        head = _LAYERED_HEADER.size + 4 * cum.size + cum.shape[1]
+        head = _LAYERED_HEADER.size + (_OVERLAP_FIELD.size if self.overlap else 0) + 4 * cum.size + cum.shape[1]
         return [head + int(v) for v in np.cumsum(lens.sum(axis=1))]
 
     def tiled(self, upto=None):
@@ -240,17 +283,19 @@ class LayeredResult:
         parts = [data[int(off[q, t]):int(off[q, t] + lens[q, t])] for t in range(cum.shape[1]) for q in range(upto)]
         run = np.concatenate(parts) if parts else data[:0]
         return TiledResult(self.h, self.w, self.c, self.th, self.tw, self.level, [int(v) for v in self.max_n],
-                           [int(v) for v in cum[upto - 1]], run.tobytes(), self._encoding_version)
+                           [int(v) for v in cum[upto - 1]], run.tobytes(), self._encoding_version, self.overlap)
 
     def to_bytes(self):
         """The container, little-endian: b"SPTQ", u8 version = 1, u8 level (255 = None), u16 c, u32 H, W, th, tw, u16 Q, u16 0
         (28 bytes), then Q x T u32 cum (row q tile-major), T x u8 max_n, then the layers.  Every prefix at least
-        28 + 4 Q T + T bytes long is a picture (from_bytes)."""
+        28 + 4 Q T + T bytes long is a picture (from_bytes).  overlap > 0: b"SPOQ", version 1, and a u32 overlap behind the
+        header (32 bytes in front of the tables); the prefix rule is the same."""
         cum, _, _ = self._table()
         if self.level is not None and not 0 <= int(self.level) < 255:
             raise ValueError("level %r does not fit the container" % (self.level,))
         level = 255 if self.level is None else int(self.level)
-        return (_LAYERED_HEADER.pack(LAYERED_MAGIC, LAYERED_VERSION, level, self.c, self.h, self.w, self.th, self.tw, cum.shape[0], 0)
+        return (_container_head(_LAYERED_HEADER, LAYERED_MAGIC, OVERLAP_LAYERED_MAGIC, LAYERED_VERSION, self.overlap,
+                                (level, self.c, self.h, self.w, self.th, self.tw, cum.shape[0], 0))
                 + cum.astype("<u4").tobytes() + np.asarray(self.max_n, dtype=np.uint8).tobytes() + bytes(self.encoded_bytes))
 
     @staticmethod
@@ -264,19 +309,19 @@ class LayeredResult:
         if len(data) < _LAYERED_HEADER.size:
             raise ValueError("a layered container has a %d-byte header; got %d bytes" % (_LAYERED_HEADER.size, len(data)))
         magic, version, level, c, h, w, th, tw, Q, _ = _LAYERED_HEADER.unpack_from(data, 0)
-        if magic != LAYERED_MAGIC:
+        if magic not in (LAYERED_MAGIC, OVERLAP_LAYERED_MAGIC):
             raise ValueError("not a layered tiled container: magic %r" % (magic,))
-        if version != LAYERED_VERSION:
-            raise ValueError("layered container version %d, this reader knows %d" % (version, LAYERED_VERSION))
+        m, tables = _container_overlap(data, _LAYERED_HEADER, magic == OVERLAP_LAYERED_MAGIC, version, LAYERED_VERSION, "layered",
+                                       th, tw)
         if not 1 <= Q <= alloc.MAX_LAYERS:
             raise ValueError("a layered container has 1 .. %d layers, not %d" % (alloc.MAX_LAYERS, Q))
         gy, gx = tile_grid(h, w, th, tw)
         T = gy * gx
-        head = _LAYERED_HEADER.size + 4 * Q * T + T
+        head = tables + 4 * Q * T + T
         if len(data) < head:
             raise ValueError("header and tables of %d layers of %d tiles are %d bytes; got %d" % (Q, T, head, len(data)))
-        cum = np.frombuffer(data, dtype="<u4", count=Q * T, offset=_LAYERED_HEADER.size).astype(np.int64).reshape(Q, T)
-        max_n = np.frombuffer(data, dtype=np.uint8, count=T, offset=_LAYERED_HEADER.size + 4 * Q * T)
+        cum = np.frombuffer(data, dtype="<u4", count=Q * T, offset=tables).astype(np.int64).reshape(Q, T)
+        max_n = np.frombuffer(data, dtype=np.uint8, count=T, offset=tables + 4 * Q * T)
         lens = np.diff(cum, axis=0, prepend=0)
         if (lens < 0).any():
             raise ValueError("the table falls from a layer to the next")
@@ -288,7 +333,7 @@ class LayeredResult:
             off = np.cumsum(flat) - flat
             cum = np.cumsum(np.clip(a - off, 0, flat).reshape(Q, T), axis=0)
         return LayeredResult(h, w, c, th, tw, None if level == 255 else level, [int(v) for v in max_n],
-                             [[int(v) for v in row] for row in cum], data[head:])
+                             [[int(v) for v in row] for row in cum], data[head:], overlap=m)
 
 
 def _upto_arg(upto, Q):
@@ -354,10 +399,24 @@ class TiledCodec:
     allocate="rd" (max_bits required; not for a float32 codec): the tiles share max_bits by their rate-distortion curves.
     Every tile is coded with the ceiling alloc.ceiling_bits(max_bits, T, spread), measured at `points` prefixes and cut at
     equal slope (alloc.allocate); the lengths add up to max_bits // 8 whenever the tiles' hulls can take that much.
-    max_bytes (an attribute) bounds the device memory of the prefixes decoded at a time; results do not depend on it."""
+    max_bytes (an attribute) bounds the device memory of the prefixes decoded at a time; results do not depend on it.
+
+    overlap = m > 0 (2 m <= min(th, tw); overlap.py is the rule, csrc/overlap.hip the kernels): every tile is coded with a margin
+    of m samples of its neighbours -- coded tile (i, j) is the picture's rows i th - m .. (i + 1) th + m and columns j tw - m ..
+    (j + 1) tw + m, clamped to the picture (np.pad(mode="edge") on all four sides) -- and every decode call cross-fades the
+    decoded tiles over the 2m samples around each seam.  The tile codec is one of (th + 2m) x (tw + 2m) pictures, whose level
+    and refusals hold; a tile's stream is still encode_image of the (coded) tile's pixels, and the budgets are unchanged
+    (max_bits // T per tile, or the ceiling of allocate="rd").  Every decode call decodes the tiles in float64 and blends once;
+    8- and 16-bit output is the decoder's conversion of the blended float64 sample.  A window needs the tiles with weight in
+    it (overlap.window_tiles_overlap): one more row or column of them where it begins or ends inside a seam's zone.
+    allocate="rd" and the layers measure the error of the CODED tiles -- margins and padding included, every tile's whole
+    extent -- not of the blended picture.  Out of scope with overlap > 0, each a ValueError: roi / d_roi, target_psnr /
+    d_target, reduce > 0 and tile_curves(roi=...).  overlap = 0 is the codec without it in every byte."""
+
+    overlap = 0
 
     def __init__(self, c, H, W, tile, settings=None, level=None, max_bits=None, ctx=None, pixel_dtype=np.float64, allocate=None,
-                 points=alloc.POINTS, spread=alloc.SPREAD):
+                 points=alloc.POINTS, spread=alloc.SPREAD, overlap=0):
         self.settings = settings if settings is not None else SpihtSettings()
         if self.settings.color_model not in (None, "RGB"):
             pixel_dtype = np.float64  # as encode_image: colour pictures are coded in float64
@@ -367,13 +426,15 @@ class TiledCodec:
         self.th, self.tw = _tile_arg(tile)
         self.gy, self.gx = tile_grid(self.H, self.W, self.th, self.tw)
         self.T = self.gy * self.gx
+        self.overlap = _overlap.overlap_arg(overlap, self.th, self.tw)
+        self.cth, self.ctw = self.th + 2 * self.overlap, self.tw + 2 * self.overlap  # the coded tile
         self.level = level
         self.max_bits = max_bits
         if allocate is not None:
             tile_bits = alloc.ceiling_bits(max_bits, self.T, self.spread)
         else:
             tile_bits = None if max_bits is None else int(max_bits) // self.T
-        self.codec = BatchCodec(self.c, self.th, self.tw, self.settings, level, tile_bits, ctx, pixel_dtype)
+        self.codec = BatchCodec(self.c, self.cth, self.ctw, self.settings, level, tile_bits, ctx, pixel_dtype)
         self.ctx, self.L = self.codec.ctx, self.codec.L
         self.pixel_dtype = self.codec.pixel_dtype
         self.last_tiles_decoded = 0  # tiles the last decode call ran
@@ -402,6 +463,20 @@ class TiledCodec:
         st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
         _check_int_view(8 * np.dtype(dtype).itemsize, shape, st, output)
         return st, C.c_void_p(st.ctypes.data)
+
+    # ---- overlapping tiles: what is out of scope with them ------------------------------------------
+    def _overlap_refuses(self, name, roi=None, target=None, reduce=0):
+        """ValueError for what a codec of overlapping tiles does not do, before anything is uploaded or queued"""
+        if not self.overlap:
+            return
+        if roi is not None:
+            raise ValueError("%s: a weight map is not supported with overlap > 0: the map is indexed in picture coordinates, and a "
+                             "coded tile's margin lies in its neighbours" % name)
+        if target is not None:
+            raise ValueError("%s: a target quality is not supported with overlap > 0: overlapping tiles count pixels twice, so the "
+                             "sum of the tiles' errors is not the picture's" % name)
+        if not isinstance(reduce, bool) and isinstance(reduce, (int, np.integer)) and reduce > 0:
+            raise ValueError("%s: reduce = %d is not supported with overlap > 0: a reduced decode has no cross-fade" % (name, reduce))
 
     # ---- device-resident forms ---------------------------------------------------------------------
     # ---- region of interest ----------------------------------------------------------------------
@@ -481,6 +556,7 @@ class TiledCodec:
         cap (alloc.allocate_target); lambda, the error reached and whether the target was met stay in the buffers "lambda",
         "tdist" (double [N], NaN where the budget bound) and "tmet" (uint32 [N])."""
         N, vp = int(N), C.c_void_p
+        self._overlap_refuses("encode_device", d_roi, d_target)
         if d_target is not None:
             self._target_check("encode_device")
         roi = self._roi_device(d_roi, roi_stride, d_img.dtype, "encode_device")
@@ -499,17 +575,21 @@ class TiledCodec:
         NT, vp = N * self.T, C.c_void_p
         if N < 1:
             raise ValueError("%s: no pictures" % name)
-        d_tiles = self._buf("tiles", NT * self.c * self.th * self.tw * dt.itemsize)
+        d_tiles = self._buf("tiles", NT * self.c * self.cth * self.ctw * dt.itemsize)
         geom = (N, self.c, self.H, self.W, self.th, self.tw)
+        # overlap > 0: the cut with a margin (spiht_tile_cut_overlap_*: the tile's arguments, then m)
+        stem = "spiht_tile_cut_"
+        if self.overlap:
+            geom, stem = geom + (self.overlap,), "spiht_tile_cut_overlap_"
         if dt.kind == "u":
             st, st_p = self._strides_arg((N, self.c, self.H, self.W), strides, False, dt)
             _check_aligned(d_img.ptr, dt)
-            cut = self.L.spiht_tile_cut_u16 if dt.itemsize == 2 else self.L.spiht_tile_cut_u8
+            cut = getattr(self.L, stem + ("u16" if dt.itemsize == 2 else "u8"))
             _lib.check(cut(self.ctx.handle, vp(d_img.ptr), st_p, *geom, vp(d_tiles.ptr)))
         else:
             if dt != self.pixel_dtype or strides is not None:
                 raise ValueError("%s: %s pictures, the codec's are dense %s" % (name, dt.name, self.pixel_dtype.name))
-            cut = self.L.spiht_tile_cut_f32 if dt.itemsize == 4 else self.L.spiht_tile_cut_f64
+            cut = getattr(self.L, stem + ("f32" if dt.itemsize == 4 else "f64"))
             _lib.check(cut(self.ctx.handle, vp(d_img.ptr), *geom, vp(d_tiles.ptr)))
         stride = self.codec.slot_stride
         d_slots = self._buf("slots", NT * stride)
@@ -540,11 +620,14 @@ class TiledCodec:
 
     def _measure_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi=None):
         """the NT full streams in d_slots -> the buffer "D": float64 / uint64 [K + 1][NT], the error of every tile at its K + 1
-        candidate lengths; roi = (address, stride) of a device weight map: the weighted error"""
+        candidate lengths; roi = (address, stride) of a device weight map: the weighted error.  overlap > 0: the error of the
+        CODED tiles, margins and padding included -- the sums are taken with the geometry of a picture of gy x gx whole coded
+        tiles, in which every tile's valid extent is the whole tile -- not the error of the blended picture"""
         NT, K, vp, c = N * self.T, self.points, C.c_void_p, self.c
         stride = self.codec.slot_stride
         integer = dt.kind == "u"
-        rh, rw = (self.th, self.tw) if integer else (self.codec.geom["rec_h"], self.codec.geom["rec_w"])
+        rh, rw = (self.cth, self.ctw) if integer else (self.codec.geom["rec_h"], self.codec.geom["rec_w"])
+        H, W = (self.gy * self.cth, self.gx * self.ctw) if self.overlap else (self.H, self.W)
         G = max(1, min(K + 1, int(self.max_bytes) // (NT * (stride + c * rh * rw * dt.itemsize + 9))))
         d_pre = self._buf("pre", G * NT * stride)
         d_prebytes = self._buf("prebytes", G * NT * 8)
@@ -565,7 +648,7 @@ class TiledCodec:
             _lib.check(self.L.spiht_tile_prefix_slots(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, K, k0, g,
                                                       vp(d_pre.ptr), stride, vp(d_prebytes.ptr), vp(d_max_n.ptr), vp(d_premaxn.ptr)))
             dec(d_pre.ptr, d_prebytes.ptr, d_premaxn.ptr, g * NT, d_dec.ptr, slot_stride=stride)
-            _lib.check(sse(self.ctx.handle, vp(d_tiles.ptr), vp(d_dec.ptr), g, N, c, self.H, self.W, self.th, self.tw, rh, rw,
+            _lib.check(sse(self.ctx.handle, vp(d_tiles.ptr), vp(d_dec.ptr), g, N, c, H, W, self.cth, self.ctw, rh, rw,
                            vp(d_D.ptr + 8 * k0 * NT), *w_args))
         return d_D
 
@@ -587,6 +670,7 @@ class TiledCodec:
         the errors reached and whether each target was met."""
         if self.allocate is None:
             raise ValueError('encode_layered: the codec was not built with allocate="rd"')
+        self._overlap_refuses("encode_layered_device", d_roi, target_psnr if target_psnr is not None else d_target)
         N, vp = int(N), C.c_void_p
         if target_psnr is None:
             if d_target is not None:
@@ -624,6 +708,10 @@ class TiledCodec:
 
     def reduced_shape(self, reduce):
         """tiled_reduced_shape of the codec's pictures: TypeError / ValueError for a reduce the codec does not decode at"""
+        self._overlap_refuses("decode", reduce=reduce)
+        if self.overlap and isinstance(reduce, (int, np.integer)) and not isinstance(reduce, bool) and reduce == 0:
+            # (full size: the picture and the grid; the levels are the coded tile's, which tiled_reduced_shape does not know)
+            return dict(level=self.level, thk=self.th, twk=self.tw, Hk=self.H, Wk=self.W, gy=self.gy, gx=self.gx)
         rs = self._reduced.get(reduce) if isinstance(reduce, (int, np.integer)) and not isinstance(reduce, bool) else None
         if rs is None:  # (a reduce of another type is refused here, before it becomes a key)
             rs = self._reduced[int(reduce)] = tiled_reduced_shape(self.H, self.W, (self.th, self.tw), self.settings, self.level, reduce)
@@ -633,10 +721,16 @@ class TiledCodec:
         """None: the whole (reduced) picture"""
         return (0, 0, rs["Hk"], rs["Wk"]) if window is None else tuple(int(v) for v in window)
 
+    def _window_tiles(self, rs, y0, x0, h, w):
+        """the sub-grid a window needs: the tiles it meets, or with overlap > 0 those with weight in it"""
+        if self.overlap:
+            return _overlap.window_tiles_overlap(self.H, self.W, self.th, self.tw, self.overlap, y0, x0, h, w)
+        return window_tiles(rs["Hk"], rs["Wk"], rs["thk"], rs["twk"], y0, x0, h, w)
+
     def _sub_window(self, sub, window, rs):
         i0, i1, j0, j1 = [int(v) for v in sub]
         y0, x0, h, w = [int(v) for v in window]
-        need = window_tiles(rs["Hk"], rs["Wk"], rs["thk"], rs["twk"], y0, x0, h, w)
+        need = self._window_tiles(rs, y0, x0, h, w)
         if not (0 <= i0 <= need[0] and need[1] <= i1 <= self.gy and 0 <= j0 <= need[2] and need[3] <= j1 <= self.gx):
             raise ValueError("the sub-grid %s does not hold the tiles %s of the window %s" % ((i0, i1, j0, j1), need, (y0, x0, h, w)))
         return (i0, i1, j0, j1), (y0, x0, h, w)
@@ -674,6 +768,8 @@ class TiledCodec:
         dt = np.dtype(d_out.dtype)
         if reduce:
             return self._decode_slots_reduced(d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, int(reduce))
+        if self.overlap:
+            return self._decode_slots_overlap(d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides)
         grid_args = (self.H, self.W, self.th, self.tw, i0, i1, j0, j1, y0, x0, h, w)
         if dt.kind == "u":
             st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
@@ -690,6 +786,27 @@ class TiledCodec:
             d_dec = self._buf("dec", n * self.c * rh * rw * 8)
             self.codec.decode_device(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, slot_stride=stride)
             _lib.check(self.L.spiht_tile_paste_f64(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *grid_args, vp(d_out.ptr)))
+        self.last_tiles_decoded = n
+
+    def _decode_slots_overlap(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides):
+        """overlap > 0, every element type: one batched float64 decode of the coded tiles, one blend (spiht_tile_blend_*), which
+        converts the blended sample for 8- and 16-bit output"""
+        (i0, i1, j0, j1), (y0, x0, h, w) = sub, window
+        n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
+        dt = np.dtype(d_out.dtype)
+        rh, rw = self.codec.geom["rec_h"], self.codec.geom["rec_w"]
+        args = (self.c, rh, rw, self.H, self.W, self.th, self.tw, self.overlap, i0, i1, j0, j1, y0, x0, h, w)
+        if dt.kind == "u":
+            st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
+            _check_aligned(d_out.ptr, dt)
+            blend, tail = (self.L.spiht_tile_blend_u16 if dt.itemsize == 2 else self.L.spiht_tile_blend_u8), (st_p,)
+        else:
+            if dt != np.float64 or strides is not None:
+                raise ValueError("decode: the float form gives dense float64 pictures")
+            blend, tail = self.L.spiht_tile_blend_f64, ()
+        d_dec = self._buf("dec", n * self.c * rh * rw * 8)
+        self.codec.decode_device(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, slot_stride=stride)
+        _lib.check(blend(self.ctx.handle, vp(d_dec.ptr), *args, vp(d_out.ptr), *tail))
         self.last_tiles_decoded = n
 
     def _decode_slots_reduced(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, k):
@@ -743,6 +860,7 @@ class TiledCodec:
 
     # ---- host forms ----------------------------------------------------------------------------------
     def _encode_host(self, images, dtype, channels_last, name, roi=None, target_psnr=None):
+        self._overlap_refuses(name, roi, target_psnr)
         if roi is not None:
             self._roi_check(dtype, name)
         if target_psnr is not None:
@@ -782,7 +900,7 @@ class TiledCodec:
         for n in range(N):
             a, b = n * self.T, (n + 1) * self.T
             out.append(TiledResult(self.H, self.W, self.c, self.th, self.tw, self.level, [int(v) for v in maxn[a:b]],
-                                   [int(v) for v in lens[a:b]], run[int(off[a]):int(off[b])].tobytes()))
+                                   [int(v) for v in lens[a:b]], run[int(off[a]):int(off[b])].tobytes(), overlap=self.overlap))
         return out[0] if single else out
 
     def encode(self, image_or_images, roi=None, target_psnr=None):
@@ -842,6 +960,7 @@ class TiledCodec:
     def _encode_layered_host(self, images, layers, dtype, channels_last, name, roi=None, target_psnr=None):
         if self.allocate is None:
             raise ValueError('%s: the codec was not built with allocate="rd"' % name)
+        self._overlap_refuses(name, roi, target_psnr)
         if roi is not None:
             self._roi_check(dtype, name)
         if target_psnr is None:
@@ -886,7 +1005,7 @@ class TiledCodec:
             else:
                 cuts.append([self._allocation(lam[q, n], rows[q], dist[q, n], met[q, n], sums[n], dtype) for q in range(Q)])
             out.append(LayeredResult(self.H, self.W, self.c, self.th, self.tw, self.level, [int(v) for v in maxn[n * T:(n + 1) * T]],
-                                     rows, run[int(off[n]):int(off[n + 1])].tobytes()))
+                                     rows, run[int(off[n]):int(off[n + 1])].tobytes(), overlap=self.overlap))
         self.last_allocation = cuts[0] if single else cuts
         return out[0] if single else out
 
@@ -939,6 +1058,8 @@ class TiledCodec:
         if (r.h, r.w, r.c, r.th, r.tw) != (self.H, self.W, self.c, self.th, self.tw):
             raise ValueError("a result of geometry %s, the codec's is %s" % ((r.h, r.w, r.c, r.th, r.tw),
                                                                             (self.H, self.W, self.c, self.th, self.tw)))
+        if r.overlap != self.overlap:
+            raise ValueError("a result of overlap %d, the codec's is %d" % (r.overlap, self.overlap))
         if len(r.nbytes) != self.T or len(r.max_n) != self.T or sum(r.nbytes) != len(r.encoded_bytes):
             raise ValueError("the tables of the result do not describe %d tiles of %d bytes" % (self.T, len(r.encoded_bytes)))
 
@@ -946,7 +1067,7 @@ class TiledCodec:
         self._check_result(result)
         rs = self.reduced_shape(reduce)
         y0, x0, h, w = self._window_arg(window, rs)
-        i0, i1, j0, j1 = sub = window_tiles(rs["Hk"], rs["Wk"], rs["thk"], rs["twk"], y0, x0, h, w)
+        i0, i1, j0, j1 = sub = self._window_tiles(rs, y0, x0, h, w)
         dtype = np.dtype(dtype)
         # the streams of the sub-grid's tiles (a row of it is contiguous in the run), their lengths and start planes: one upload
         off = result._offsets()
@@ -983,11 +1104,13 @@ class TiledCodec:
                 or len(result.max_n) != self.T:
             raise ValueError("a result of geometry %s, the codec's is %s" % ((result.h, result.w, result.c, result.th, result.tw),
                                                                             (self.H, self.W, self.c, self.th, self.tw)))
+        if result.overlap != self.overlap:
+            raise ValueError("a result of overlap %d, the codec's is %d" % (result.overlap, self.overlap))
         cum, lens, off = result._table()
         upto = _upto_arg(upto, cum.shape[0])
         rs = self.reduced_shape(reduce)
         y0, x0, h, w = self._window_arg(window, rs)
-        i0, i1, j0, j1 = sub = window_tiles(rs["Hk"], rs["Wk"], rs["thk"], rs["twk"], y0, x0, h, w)
+        i0, i1, j0, j1 = sub = self._window_tiles(rs, y0, x0, h, w)
         dtype = np.dtype(dtype)
         # the table, the start planes and the pieces of the sub-grid's tiles in the layers below upto -- per layer a row of the
         # sub-grid is contiguous in the file: one upload
@@ -1089,63 +1212,68 @@ _codecs = {}
 
 
 def _codec_for(c, H, W, tile, settings, level, max_bits, pixel_dtype=np.float64, allocate=None, points=alloc.POINTS,
-               spread=alloc.SPREAD):
+               spread=alloc.SPREAD, overlap=0):
     """a TiledCodec per geometry and settings, kept (a few of them) so that repeated calls reuse its device buffers"""
     th, tw = _tile_arg(tile)
     if getattr(settings, "color_model", None) not in (None, "RGB"):
         pixel_dtype = np.float64  # as TiledCodec: colour pictures are coded in float64
     points, spread = _alloc_args(allocate, points, spread, max_bits, pixel_dtype)
+    overlap = _overlap.overlap_arg(overlap, th, tw)
     key = (c, H, W, th, tw, repr(settings), level, max_bits, np.dtype(pixel_dtype).name, allocate, points, spread,
-           id(_lib.default_context()))
+           id(_lib.default_context()), overlap)
     codec = _codecs.get(key)
     if codec is None:
         while len(_codecs) >= 4:
             _codecs.pop(next(iter(_codecs))).close()
-        codec = _codecs[key] = TiledCodec(c, H, W, (th, tw), settings, level, max_bits, None, pixel_dtype, allocate, points, spread)
+        codec = _codecs[key] = TiledCodec(c, H, W, (th, tw), settings, level, max_bits, None, pixel_dtype, allocate, points, spread,
+                                          overlap)
     return codec
 
 
 def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_last, name, allocate=None, points=alloc.POINTS,
-                  spread=alloc.SPREAD, roi=None, target_psnr=None):
+                  spread=alloc.SPREAD, roi=None, target_psnr=None, overlap=0):
     if not isinstance(image, np.ndarray) or image.ndim != 3:
         raise ValueError('image ndim must be 3: c,h,w')
     c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
     if dtype is None:
         dtype = np.float32 if image.dtype in (np.float32, np.float16) else np.float64
     codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if np.dtype(dtype).kind == "f" else np.float64,
-                       allocate, points, spread)
+                       allocate, points, spread, overlap)
     return codec._encode_host(image, codec.pixel_dtype if np.dtype(dtype).kind == "f" else dtype, channels_last, name, roi,
                               target_psnr)
 
 
 def encode_image_tiled(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, allocate=None, points=alloc.POINTS,
-                       spread=alloc.SPREAD, roi=None, target_psnr=None):
+                       spread=alloc.SPREAD, roi=None, target_psnr=None, overlap=0):
     """encode_image of a picture (c, h, w) as tiles of `tile` (an int or (th, tw)) -> TiledResult.  level and max_bits are
     per tile as in TiledCodec: every tile gets max_bits // T bits; float32 pixels run the single-precision transform.
     allocate="rd" (with points, spread): the tiles share max_bits by their rate-distortion curves, as in TiledCodec.
     roi (with allocate="rd"): a weight map [h, w], bool or uint8 (roi_map), that steers the shares, as in TiledCodec.encode.
     target_psnr (with allocate="rd"): a PSNR in dB to reach with the fewest bytes the measured curves allow, max_bits the cap, as
-    in TiledCodec.encode."""
+    in TiledCodec.encode.
+    overlap = m > 0: every tile is coded with a margin of m samples of its neighbours and the decode calls cross-fade the seams,
+    as in TiledCodec (the result carries the overlap; roi and target_psnr are then refused)."""
     return _encode_tiled(image, tile, spiht_settings, level, max_bits, None, False, "encode_image_tiled", allocate, points, spread,
-                         roi, target_psnr)
+                         roi, target_psnr, overlap)
 
 
 def encode_image_tiled_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False,
-                          allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None, target_psnr=None):
+                          allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None, target_psnr=None, overlap=0):
     """uint8 pixels: the TiledResult of encode_image_tiled(image / 255.0, ...); allocate="rd" measures 8-bit decodes"""
     return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint8, channels_last, "encode_image_tiled_u8", allocate,
-                         points, spread, roi, target_psnr)
+                         points, spread, roi, target_psnr, overlap)
 
 
 def encode_image_tiled_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, channels_last=False,
-                           allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None, target_psnr=None):
+                           allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None, target_psnr=None, overlap=0):
     """uint16 pixels: the TiledResult of encode_image_tiled(image / 65535.0, ...); allocate="rd" measures 16-bit decodes"""
     return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint16, channels_last, "encode_image_tiled_u16", allocate,
-                         points, spread, roi, target_psnr)
+                         points, spread, roi, target_psnr, overlap)
 
 
 def _decode_tiled(result, spiht_settings, window, dtype, channels_last, reduce=0):
-    codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None)
+    codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None,
+                       overlap=result.overlap)
     return codec._decode_host(result, window, dtype, channels_last, reduce)
 
 
@@ -1178,43 +1306,44 @@ def decode_image_window_u16(result, spiht_settings, y0, x0, h, w, channels_last=
 
 
 def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype, channels_last, name, points, spread, roi=None,
-                    target_psnr=None):
+                    target_psnr=None, overlap=0):
     if layers is None and target_psnr is None:
         layers = 1
     if not isinstance(image, np.ndarray) or image.ndim != 3:
         raise ValueError('image ndim must be 3: c,h,w')
     c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
-    codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, np.float64, "rd", points, spread)
+    codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, np.float64, "rd", points, spread, overlap)
     return codec._encode_layered_host(image, layers, codec.pixel_dtype if dtype is None else dtype, channels_last, name, roi,
                                       target_psnr)
 
 
 def encode_image_layered(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=None, points=alloc.POINTS,
-                         spread=alloc.SPREAD, roi=None, target_psnr=None):
+                         spread=alloc.SPREAD, roi=None, target_psnr=None, overlap=0):
     """encode_image_tiled(..., allocate="rd") of a float64 picture (c, h, w) in quality layers -> LayeredResult.  layers: an
     int Q or the layers' bit budgets, the last one max_bits (alloc.layer_budgets); result.tiled() is the TiledResult of
     encode_image_tiled, and any prefix of result.to_bytes() that holds the tables is a picture.  roi: a weight map, as
     encode_image_tiled -- the first layers then hold the region of interest.  layers=None is one layer, or with target_psnr
     as many as it holds: the layers as strictly increasing PSNRs in dB in place of budgets, max_bits the cap, as in
-    TiledCodec.encode_layered."""
+    TiledCodec.encode_layered.  overlap: overlapping tiles, as encode_image_tiled (layers as budgets only)."""
     return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, None, False, "encode_image_layered", points, spread,
-                           roi, target_psnr)
+                           roi, target_psnr, overlap)
 
 
 def encode_image_layered_u8(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=None, points=alloc.POINTS,
-                            spread=alloc.SPREAD, channels_last=False, roi=None, target_psnr=None):
+                            spread=alloc.SPREAD, channels_last=False, roi=None, target_psnr=None, overlap=0):
     return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, np.uint8, channels_last, "encode_image_layered_u8",
-                           points, spread, roi, target_psnr)
+                           points, spread, roi, target_psnr, overlap)
 
 
 def encode_image_layered_u16(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=None, points=alloc.POINTS,
-                             spread=alloc.SPREAD, channels_last=False, roi=None, target_psnr=None):
+                             spread=alloc.SPREAD, channels_last=False, roi=None, target_psnr=None, overlap=0):
     return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, np.uint16, channels_last, "encode_image_layered_u16",
-                           points, spread, roi, target_psnr)
+                           points, spread, roi, target_psnr, overlap)
 
 
 def _decode_layered(result, spiht_settings, window, upto, dtype, channels_last, reduce=0):
-    codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None)
+    codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None,
+                       overlap=result.overlap)
     return codec._decode_layered_host(result, window, upto, dtype, channels_last, reduce)
 
 
