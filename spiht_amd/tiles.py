@@ -98,6 +98,13 @@ def window_tiles(H, W, th, tw, y0, x0, h, w):
     return y0 // th, (y0 + h - 1) // th + 1, x0 // tw, (x0 + w - 1) // tw + 1
 
 
+def _reduce_arg(reduce):
+    """reduce as an int; TypeError for what is no integer (a bool is none)"""
+    if isinstance(reduce, bool) or not isinstance(reduce, (int, np.integer)):
+        raise TypeError("reduce must be an integer, not %s" % type(reduce).__name__)
+    return int(reduce)
+
+
 _REDUCED_NAMES = ("thk", "twk", "Hk", "Wk", "gy", "gx", "rec_h", "rec_w", "pic_h", "pic_w", "off_y", "off_x")
 
 
@@ -112,8 +119,7 @@ def tiled_reduced_shape(H, W, tile, settings, level, reduce):
     wid, mid = _wavelet_mode_ids(settings if settings is not None else SpihtSettings())
     if level is not None and level < 0:
         raise ValueError("Level value of %d is too low . Minimum level is 0." % level)
-    if isinstance(reduce, bool) or not isinstance(reduce, (int, np.integer)):
-        raise TypeError("reduce must be an integer, not %s" % type(reduce).__name__)
+    reduce = _reduce_arg(reduce)
     if not 0 <= reduce < 64:
         raise ValueError("reduce = %d" % reduce)
     tile_grid(H, W, th, tw)  # (its own refusals, in its own words)
@@ -128,35 +134,54 @@ def tiled_reduced_shape(H, W, tile, settings, level, reduce):
     return dict(level=lv.value, **{k: t.value for k, t in zip(_REDUCED_NAMES, v)})
 
 
-def _container_head(header, magic, overlap_magic, version, m, fields):
-    """the header of either container: with overlap = m > 0 the other magic and a u32 m behind the same fields"""
-    m = int(m)
-    if m == 0:
-        return header.pack(magic, version, *fields)
-    if m < 0 or m >= 2 ** 32:
-        raise ValueError("overlap %d does not fit the container" % m)
-    return header.pack(overlap_magic, OVERLAP_VERSION, *fields) + _OVERLAP_FIELD.pack(m)
+class _Container:
+    """What TiledResult and LayeredResult share: the grid, and the header of their containers -- the magic of the form, u8 version,
+    u8 level (255 = None), u16 c, u32 H, W, th, tw, then the form's own fields; with overlap = m > 0 the other magic, version
+    OVERLAP_VERSION and a u32 m behind the same fields."""
+
+    def grid(self):
+        return tile_grid(self.h, self.w, self.th, self.tw)
+
+    def _head(self, header, magic, overlap_magic, version, *more):
+        """the writer's side"""
+        if self.level is not None and not 0 <= int(self.level) < 255:
+            raise ValueError("level %r does not fit the container" % (self.level,))
+        fields = (255 if self.level is None else int(self.level), self.c, self.h, self.w, self.th, self.tw) + more
+        m = int(self.overlap)
+        if m == 0:
+            return header.pack(magic, version, *fields)
+        if m < 0 or m >= 2 ** 32:
+            raise ValueError("overlap %d does not fit the container" % m)
+        return header.pack(overlap_magic, OVERLAP_VERSION, *fields) + _OVERLAP_FIELD.pack(m)
 
 
-def _container_overlap(data, header, overlapped, version, known, what, th, tw):
-    """the reader's side: the version check of the form the magic named -> (overlap, bytes in front of the tables)"""
-    if not overlapped:
+def _parse_head(data, header, magic, overlap_magic, known, what):
+    """the reader's side: the magic tells the form, whose version is checked -> (level, c, h, w, th, tw and the form's own
+    fields, overlap, bytes in front of the tables)"""
+    if len(data) < header.size:
+        raise ValueError("a %s container has a %d-byte header; got %d bytes" % (what, header.size, len(data)))
+    found, version, level, *fields = header.unpack_from(data, 0)
+    if found not in (magic, overlap_magic):
+        raise ValueError("not a %s container: magic %r" % (what if what == "tiled" else what + " tiled", found))
+    fields = [None if level == 255 else level] + fields
+    if found == magic:
         if version != known:
             raise ValueError("%s container version %d, this reader knows %d" % (what, version, known))
-        return 0, header.size
+        return fields, 0, header.size
     if version != OVERLAP_VERSION:
         raise ValueError("%s container with overlap, version %d, this reader knows %d" % (what, version, OVERLAP_VERSION))
     if len(data) < header.size + _OVERLAP_FIELD.size:
         raise ValueError("a %s container with overlap has a %d-byte header; got %d bytes"
                          % (what, header.size + _OVERLAP_FIELD.size, len(data)))
     m, = _OVERLAP_FIELD.unpack_from(data, header.size)
+    th, tw = fields[4], fields[5]
     if m < 1 or 2 * m > min(th, tw):
         raise ValueError("overlap = %d of tiles of %d x %d: 1 <= overlap and 2 * overlap <= the shorter tile side" % (m, th, tw))
-    return m, header.size + _OVERLAP_FIELD.size
+    return fields, m, header.size + _OVERLAP_FIELD.size
 
 
 @dataclass
-class TiledResult:
+class TiledResult(_Container):
     """The streams of one tiled picture.  h, w, c: the PICTURE; th, tw: the tile; max_n, nbytes: one entry per tile,
     row-major; encoded_bytes: the tiles' streams one behind the other.  overlap = m > 0: every tile was coded with a margin of
     m samples of its neighbours (overlap.py), so a tile's stream is that of a (th + 2m) x (tw + 2m) picture."""
@@ -171,9 +196,6 @@ class TiledResult:
     encoded_bytes: bytes
     _encoding_version: str = ENCODER_DECODER_VERSION
     overlap: int = 0
-
-    def grid(self):
-        return tile_grid(self.h, self.w, self.th, self.tw)
 
     def _offsets(self):
         return np.concatenate(([0], np.cumsum(np.asarray(self.nbytes, dtype=np.int64))))
@@ -196,25 +218,15 @@ class TiledResult:
         T = len(self.nbytes)
         if len(self.max_n) != T or sum(self.nbytes) != len(self.encoded_bytes):
             raise ValueError("the tables do not describe %d tiles of %d bytes" % (T, len(self.encoded_bytes)))
-        if self.level is not None and not 0 <= int(self.level) < 255:
-            raise ValueError("level %r does not fit the container" % (self.level,))
-        level = 255 if self.level is None else int(self.level)
-        return (_container_head(_HEADER, MAGIC, OVERLAP_MAGIC, CONTAINER_VERSION, self.overlap,
-                                (level, self.c, self.h, self.w, self.th, self.tw))
-                + np.asarray(self.nbytes, dtype="<u4").tobytes() + np.asarray(self.max_n, dtype=np.uint8).tobytes()
-                + bytes(self.encoded_bytes))
+        return (self._head(_HEADER, MAGIC, OVERLAP_MAGIC, CONTAINER_VERSION) + np.asarray(self.nbytes, dtype="<u4").tobytes()
+                + np.asarray(self.max_n, dtype=np.uint8).tobytes() + bytes(self.encoded_bytes))
 
     @staticmethod
     def from_bytes(data):
         """Inverse of to_bytes; the magic tells which of the two forms.  ValueError on a wrong magic or version, a short table,
         a length sum that is not the remaining byte count, or an overlap that is 0 or more than half a tile side."""
         data = bytes(data)
-        if len(data) < _HEADER.size:
-            raise ValueError("a tiled container has a %d-byte header; got %d bytes" % (_HEADER.size, len(data)))
-        magic, version, level, c, h, w, th, tw = _HEADER.unpack_from(data, 0)
-        if magic not in (MAGIC, OVERLAP_MAGIC):
-            raise ValueError("not a tiled container: magic %r" % (magic,))
-        m, head = _container_overlap(data, _HEADER, magic == OVERLAP_MAGIC, version, CONTAINER_VERSION, "tiled", th, tw)
+        (level, c, h, w, th, tw), m, head = _parse_head(data, _HEADER, MAGIC, OVERLAP_MAGIC, CONTAINER_VERSION, "tiled")
         gy, gx = tile_grid(h, w, th, tw)
         T = gy * gx
         if len(data) < head + 5 * T:
@@ -224,12 +236,12 @@ class TiledResult:
         rest = len(data) - head - 5 * T
         if int(nbytes.sum()) != rest:
             raise ValueError("the table's lengths add up to %d bytes; %d follow it" % (int(nbytes.sum()), rest))
-        return TiledResult(h, w, c, th, tw, None if level == 255 else level, [int(v) for v in max_n], [int(v) for v in nbytes],
+        return TiledResult(h, w, c, th, tw, level, [int(v) for v in max_n], [int(v) for v in nbytes],
                            data[head + 5 * T:], overlap=m)
 
 
 @dataclass
-class LayeredResult:
+class LayeredResult(_Container):
     """The streams of one tiled picture in Q quality layers.  h, w, c, th, tw, level, max_n: as TiledResult; cum [Q][T]:
     cum[q][t] the bytes of tile t through layer q, non-decreasing in q; encoded_bytes: the layers one behind the other,
     layer q being, for t = 0 .. T - 1, the bytes [cum[q - 1][t], cum[q][t]) of tile t's stream (cum[-1] = 0)."""
@@ -248,9 +260,6 @@ class LayeredResult:
     @property
     def layers(self):
         return len(self.cum)
-
-    def grid(self):
-        return tile_grid(self.h, self.w, self.th, self.tw)
 
     def _table(self):
         """(cum [Q][T], piece lengths [Q][T], piece offsets in encoded_bytes [Q][T]) as int64; ValueError if the tables do not
@@ -291,11 +300,7 @@ class LayeredResult:
         28 + 4 Q T + T bytes long is a picture (from_bytes).  overlap > 0: b"SPOQ", version 1, and a u32 overlap behind the
         header (32 bytes in front of the tables); the prefix rule is the same."""
         cum, _, _ = self._table()
-        if self.level is not None and not 0 <= int(self.level) < 255:
-            raise ValueError("level %r does not fit the container" % (self.level,))
-        level = 255 if self.level is None else int(self.level)
-        return (_container_head(_LAYERED_HEADER, LAYERED_MAGIC, OVERLAP_LAYERED_MAGIC, LAYERED_VERSION, self.overlap,
-                                (level, self.c, self.h, self.w, self.th, self.tw, cum.shape[0], 0))
+        return (self._head(_LAYERED_HEADER, LAYERED_MAGIC, OVERLAP_LAYERED_MAGIC, LAYERED_VERSION, cum.shape[0], 0)
                 + cum.astype("<u4").tobytes() + np.asarray(self.max_n, dtype=np.uint8).tobytes() + bytes(self.encoded_bytes))
 
     @staticmethod
@@ -306,13 +311,8 @@ class LayeredResult:
         LayeredResult.  ValueError: wrong magic or version, fewer bytes than header and tables, a table that falls from a
         layer to the next, more bytes than the table accounts for."""
         data = bytes(data)
-        if len(data) < _LAYERED_HEADER.size:
-            raise ValueError("a layered container has a %d-byte header; got %d bytes" % (_LAYERED_HEADER.size, len(data)))
-        magic, version, level, c, h, w, th, tw, Q, _ = _LAYERED_HEADER.unpack_from(data, 0)
-        if magic not in (LAYERED_MAGIC, OVERLAP_LAYERED_MAGIC):
-            raise ValueError("not a layered tiled container: magic %r" % (magic,))
-        m, tables = _container_overlap(data, _LAYERED_HEADER, magic == OVERLAP_LAYERED_MAGIC, version, LAYERED_VERSION, "layered",
-                                       th, tw)
+        (level, c, h, w, th, tw, Q, _), m, tables = _parse_head(data, _LAYERED_HEADER, LAYERED_MAGIC, OVERLAP_LAYERED_MAGIC,
+                                                                 LAYERED_VERSION, "layered")
         if not 1 <= Q <= alloc.MAX_LAYERS:
             raise ValueError("a layered container has 1 .. %d layers, not %d" % (alloc.MAX_LAYERS, Q))
         gy, gx = tile_grid(h, w, th, tw)
@@ -332,7 +332,7 @@ class LayeredResult:
             flat = lens.reshape(-1)
             off = np.cumsum(flat) - flat
             cum = np.cumsum(np.clip(a - off, 0, flat).reshape(Q, T), axis=0)
-        return LayeredResult(h, w, c, th, tw, None if level == 255 else level, [int(v) for v in max_n],
+        return LayeredResult(h, w, c, th, tw, level, [int(v) for v in max_n],
                              [[int(v) for v in row] for row in cum], data[head:], overlap=m)
 
 
@@ -386,6 +386,21 @@ def _alloc_args(allocate, points, spread, max_bits, pixel_dtype):
 def _ptr(x):
     """the device address of a DeviceArray, or the integer itself"""
     return int(x.ptr) if hasattr(x, "ptr") else int(x)
+
+
+# the element types of the library's tile entry points, by the suffix of their names
+_SUFFIX = {np.dtype(np.uint8): "u8", np.dtype(np.uint16): "u16", np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
+
+
+def _entry(L, stem, dt):
+    """the library's entry point of that stem for an element type (an np.dtype): (L, "spiht_tile_paste_", uint16) ->
+    L.spiht_tile_paste_u16"""
+    return getattr(L, stem + _SUFFIX[dt])
+
+
+def _peak(dtype):
+    """the largest pixel value: of 8- and 16-bit pixels the type's, of float pixels 1.0"""
+    return float(np.iinfo(dtype).max) if np.dtype(dtype).kind == "u" else 1.0
 
 
 class TiledCodec:
@@ -464,6 +479,24 @@ class TiledCodec:
         _check_int_view(8 * np.dtype(dtype).itemsize, shape, st, output)
         return st, C.c_void_p(st.ctypes.data)
 
+    def _tile_call(self, op, dt):
+        """the tile codec's batched call for an element type (an np.dtype); op: "encode", "decode" or "decode_reduced".  The
+        float form is the one of the codec's own float pixels"""
+        return getattr(self.codec, op + "_device" + ("_" + _SUFFIX[dt] if dt.kind == "u" else ""))
+
+    def _download(self, ptr, shape, dtype):
+        """a host array of that shape, filled from the device address: one download (none of an empty array)"""
+        out = np.empty(shape, dtype=dtype)
+        if out.size:
+            self.ctx.download(out, ptr)
+        return out
+
+    def _download_cuts(self, s, Q, N, target):
+        """what _allocate_device left of the last device encode: [lambda* [Q][N]]; of a cut at a target also the errors reached
+        and whether each was met.  s: as _allocate_device's"""
+        names = ("lambda", np.float64), ("tdist", np.float64), ("tmet", np.uint32)
+        return [self._download(self._bufs[k + s].ptr, (Q, N), t) for k, t in names[:3 if target else 1]]
+
     # ---- overlapping tiles: what is out of scope with them ------------------------------------------
     def _overlap_refuses(self, name, roi=None, target=None, reduce=0):
         """ValueError for what a codec of overlapping tiles does not do, before anything is uploaded or queued"""
@@ -475,7 +508,7 @@ class TiledCodec:
         if target is not None:
             raise ValueError("%s: a target quality is not supported with overlap > 0: overlapping tiles count pixels twice, so the "
                              "sum of the tiles' errors is not the picture's" % name)
-        if not isinstance(reduce, bool) and isinstance(reduce, (int, np.integer)) and reduce > 0:
+        if reduce > 0:
             raise ValueError("%s: reduce = %d is not supported with overlap > 0: a reduced decode has no cross-fade" % (name, reduce))
 
     # ---- device-resident forms ---------------------------------------------------------------------
@@ -525,19 +558,22 @@ class TiledCodec:
     def _targets_upload(self, rows, sums, dtype):
         """rows: Q lists of N target PSNRs; sums: the N weight sums -> the device double [Q][N] of squared errors, in the buffer
         "targets": one upload"""
-        peak = float(np.iinfo(dtype).max) if np.dtype(dtype).kind == "u" else 1.0
+        peak = _peak(dtype)
         table = np.array([[alloc.target_sqerr(db, peak, self.c, s) for db, s in zip(row, sums)] for row in rows], dtype=np.float64)
         d_target = self._buf("targets", table.nbytes)
         self.ctx.upload(d_target.ptr, table)
         return d_target
 
-    def _allocation(self, lam, nbytes, dist, met, weight_sum, dtype):
-        """the TileAllocation of a cut at a target: dist is NaN where the budget bound"""
+    def _allocation(self, lam, nbytes, target=None):
+        """the TileAllocation of a cut; target: (dist, met, the picture's weight sum, pixel dtype) of a cut at a target, dist NaN
+        where the budget bound"""
+        if target is None:
+            return TileAllocation(float(lam), nbytes)
         from .rd import psnr_of
+        dist, met, weight_sum, dtype = target
         if np.isnan(dist):
             return TileAllocation(float(lam), nbytes, None, None, bool(met))
-        peak = float(np.iinfo(dtype).max) if np.dtype(dtype).kind == "u" else 1.0
-        return TileAllocation(float(lam), nbytes, float(dist), psnr_of(float(dist) / (self.c * weight_sum), peak), bool(met))
+        return TileAllocation(float(lam), nbytes, float(dist), psnr_of(float(dist) / (self.c * weight_sum), _peak(dtype)), bool(met))
 
     def encode_device(self, d_img, N, d_packed, d_lens, d_max_n, strides=None, d_roi=None, roi_stride=0, d_target=None):
         """d_img: DeviceArray of N pictures [N, c, H, W] -- float64 (float32 for a float32 codec), or uint8 / uint16 laid out by
@@ -563,7 +599,7 @@ class TiledCodec:
         dt, d_tiles, d_slots, d_nbits = self._encode_slots(d_img, N, d_max_n, strides, "encode_device")
         NT, stride = N * self.T, self.codec.slot_stride
         if self.allocate is not None:
-            d_nbits = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi, d_target)
+            d_nbits = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi, [int(self.max_bits)], d_target)
         _lib.check(self.L.spiht_tile_pack(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, vp(d_packed.ptr),
                                           d_packed.nbytes, vp(d_lens.ptr)))
 
@@ -581,41 +617,39 @@ class TiledCodec:
         stem = "spiht_tile_cut_"
         if self.overlap:
             geom, stem = geom + (self.overlap,), "spiht_tile_cut_overlap_"
+        view = ()  # the integer forms take a view of the pictures: the strides, behind the address
         if dt.kind == "u":
             st, st_p = self._strides_arg((N, self.c, self.H, self.W), strides, False, dt)
             _check_aligned(d_img.ptr, dt)
-            cut = getattr(self.L, stem + ("u16" if dt.itemsize == 2 else "u8"))
-            _lib.check(cut(self.ctx.handle, vp(d_img.ptr), st_p, *geom, vp(d_tiles.ptr)))
-        else:
-            if dt != self.pixel_dtype or strides is not None:
-                raise ValueError("%s: %s pictures, the codec's are dense %s" % (name, dt.name, self.pixel_dtype.name))
-            cut = getattr(self.L, stem + ("f32" if dt.itemsize == 4 else "f64"))
-            _lib.check(cut(self.ctx.handle, vp(d_img.ptr), *geom, vp(d_tiles.ptr)))
-        stride = self.codec.slot_stride
-        d_slots = self._buf("slots", NT * stride)
+            view = (st_p,)
+        elif dt != self.pixel_dtype or strides is not None:
+            raise ValueError("%s: %s pictures, the codec's are dense %s" % (name, dt.name, self.pixel_dtype.name))
+        _lib.check(_entry(self.L, stem, dt)(self.ctx.handle, vp(d_img.ptr), *view, *geom, vp(d_tiles.ptr)))
+        d_slots = self._buf("slots", NT * self.codec.slot_stride)
         d_nbits = self._buf("nbits", NT * 8)
-        if dt.kind == "u":
-            enc = self.codec.encode_device_u16 if dt.itemsize == 2 else self.codec.encode_device_u8
-            enc(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
-        else:
-            self.codec.encode_device(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
+        self._tile_call("encode", dt)(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
         return dt, d_tiles, d_slots, d_nbits
 
-    def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi=None, d_target=None):
-        """the NT full streams in d_slots -> the buffer of the cut lengths in bits (uint64 [NT]); the table of distortions
-        stays in the buffer "D" ([K + 1][NT]) and lambda* in "lambda" ([N]) for the host forms.  d_target: the cut at a target
-        squared error per picture, whose further outputs stay in "tdist" and "tmet" ([N] each)"""
-        NT, K, vp = N * self.T, self.points, C.c_void_p
+    def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi, budgets, d_target=None, s=""):
+        """the NT full streams in d_slots -> the buffer of the cut lengths in bits (uint64 [Q][NT]), one row per budget (in bits)
+        of `budgets`, each row one spiht_tile_allocate on the one table of distortions; the table stays in the buffer "D"
+        ([K + 1][NT]) and the rows' lambda* in "lambda" ([Q][N]) for the host forms.  d_target (double [Q][N]): row q is the cut at
+        the target squared errors of its row q under the cap budgets[q], whose further outputs stay in "tdist" and "tmet"
+        ([Q][N] each).  s = "s" gives the four buffers the layered form's names: "cuts", "lambdas", "tdists" and "tmets"."""
+        NT, Q, vp = N * self.T, len(budgets), C.c_void_p
         d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi)
-        d_cut = self._buf("cut", NT * 8)
-        d_lam = self._buf("lambda", N * 8)
-        args = (self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, K, N, self.T, int(self.max_bits) // 8)
-        if d_target is None:
-            _lib.check(self.L.spiht_tile_allocate(*args, vp(d_cut.ptr), vp(d_lam.ptr)))
-        else:
-            d_dist, d_met = self._buf("tdist", N * 8), self._buf("tmet", N * 4)
-            _lib.check(self.L.spiht_tile_allocate_target(*args, vp(_ptr(d_target)), vp(d_cut.ptr), vp(d_lam.ptr), vp(d_dist.ptr),
-                                                         vp(d_met.ptr)))
+        d_cut = self._buf("cut" + s, Q * NT * 8)
+        d_lam = self._buf("lambda" + s, Q * N * 8)
+        if d_target is not None:
+            d_dist, d_met = self._buf("tdist" + s, Q * N * 8), self._buf("tmet" + s, Q * N * 4)
+        args = (self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, self.points, N, self.T)
+        for q, bits in enumerate(budgets):
+            cut, lam = vp(d_cut.ptr + 8 * q * NT), vp(d_lam.ptr + 8 * q * N)
+            if d_target is None:
+                _lib.check(self.L.spiht_tile_allocate(*args, bits // 8, cut, lam))
+            else:
+                _lib.check(self.L.spiht_tile_allocate_target(*args, bits // 8, vp(_ptr(d_target) + 8 * q * N), cut, lam,
+                                                             vp(d_dist.ptr + 8 * q * N), vp(d_met.ptr + 4 * q * N)))
         return d_cut
 
     def _measure_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi=None):
@@ -634,15 +668,11 @@ class TiledCodec:
         d_premaxn = self._buf("premaxn", G * NT)
         d_dec = self._buf("dec", G * NT * c * rh * rw * dt.itemsize)
         d_D = self._buf("D", (K + 1) * NT * 8)
-        if integer:
-            dec = self.codec.decode_device_u16 if dt.itemsize == 2 else self.codec.decode_device_u8
-            kind = "u16" if dt.itemsize == 2 else "u8"
-        else:
-            dec, kind = self.codec.decode_device, "f64"
+        dec = self._tile_call("decode", dt)
         if roi is None:
-            sse, w_args = getattr(self.L, "spiht_sse_tiles_" + kind), ()
+            sse, w_args = _entry(self.L, "spiht_sse_tiles_", dt), ()
         else:
-            sse, w_args = getattr(self.L, "spiht_sse_tiles_w_" + kind), (vp(roi[0]), roi[1])
+            sse, w_args = _entry(self.L, "spiht_sse_tiles_w_", dt), (vp(roi[0]), roi[1])
         for k0 in range(0, K + 1, G):
             g = min(G, K + 1 - k0)
             _lib.check(self.L.spiht_tile_prefix_slots(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, K, k0, g,
@@ -680,6 +710,7 @@ class TiledCodec:
         else:
             dbs = alloc.layer_targets_arg(target_psnr, layers)
             Q = len(dbs)
+            budgets = [int(self.max_bits)] * Q  # every layer's cap
             if d_target is None and d_roi is not None:
                 raise ValueError("encode_layered_device: with a device weight map, give the weighted squared errors as d_target")
         roi = self._roi_device(d_roi, roi_stride, d_img.dtype, "encode_layered_device")
@@ -688,33 +719,21 @@ class TiledCodec:
                 raise ValueError("encode_layered_device: no pictures")
             d_target = self._targets_upload([[db] * N for db in dbs], self._weight_sums(None, N), d_img.dtype)
         dt, d_tiles, d_slots, d_nbits = self._encode_slots(d_img, N, d_max_n, strides, "encode_layered_device")
-        NT = N * self.T
-        d_D = self._measure_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi)
-        d_cuts = self._buf("cuts", Q * NT * 8)
-        d_lams = self._buf("lambdas", Q * N * 8)
-        args = (self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, self.points, N, self.T)
-        if target_psnr is None:
-            for q, bits in enumerate(budgets):
-                _lib.check(self.L.spiht_tile_allocate(*args, bits // 8, vp(d_cuts.ptr + 8 * q * NT), vp(d_lams.ptr + 8 * q * N)))
-        else:
-            d_dists, d_mets = self._buf("tdists", Q * N * 8), self._buf("tmets", Q * N * 4)
-            for q in range(Q):
-                _lib.check(self.L.spiht_tile_allocate_target(*args, int(self.max_bits) // 8, vp(_ptr(d_target) + 8 * q * N),
-                                                             vp(d_cuts.ptr + 8 * q * NT), vp(d_lams.ptr + 8 * q * N),
-                                                             vp(d_dists.ptr + 8 * q * N), vp(d_mets.ptr + 4 * q * N)))
+        d_cuts = self._allocate_device(dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi, budgets, d_target, "s")
         _lib.check(self.L.spiht_layer_pack(self.ctx.handle, vp(d_slots.ptr), self.codec.slot_stride, vp(d_cuts.ptr), Q, N, self.T,
                                            vp(_ptr(d_packed)), int(d_packed.nbytes), vp(_ptr(d_cum)), vp(_ptr(d_pic_bytes))))
         return Q
 
     def reduced_shape(self, reduce):
         """tiled_reduced_shape of the codec's pictures: TypeError / ValueError for a reduce the codec does not decode at"""
+        reduce = _reduce_arg(reduce)  # (a reduce of another type is refused here, before it becomes a key)
         self._overlap_refuses("decode", reduce=reduce)
-        if self.overlap and isinstance(reduce, (int, np.integer)) and not isinstance(reduce, bool) and reduce == 0:
+        if self.overlap and reduce == 0:
             # (full size: the picture and the grid; the levels are the coded tile's, which tiled_reduced_shape does not know)
             return dict(level=self.level, thk=self.th, twk=self.tw, Hk=self.H, Wk=self.W, gy=self.gy, gx=self.gx)
-        rs = self._reduced.get(reduce) if isinstance(reduce, (int, np.integer)) and not isinstance(reduce, bool) else None
-        if rs is None:  # (a reduce of another type is refused here, before it becomes a key)
-            rs = self._reduced[int(reduce)] = tiled_reduced_shape(self.H, self.W, (self.th, self.tw), self.settings, self.level, reduce)
+        rs = self._reduced.get(reduce)
+        if rs is None:
+            rs = self._reduced[reduce] = tiled_reduced_shape(self.H, self.W, (self.th, self.tw), self.settings, self.level, reduce)
         return rs
 
     def _window_arg(self, window, rs):
@@ -762,74 +781,37 @@ class TiledCodec:
 
     def _decode_slots(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, reduce):
         """the zero-padded slots of the sub-grid's tiles -> the window: one batched decode, one paste (reduce > 0: one batched
-        reduced decode, one mosaic)"""
+        reduced decode, one mosaic; overlap > 0, every element type: one batched float64 decode of the coded tiles, one blend,
+        which converts the blended sample for 8- and 16-bit output)"""
         (i0, i1, j0, j1), (y0, x0, h, w) = sub, window
-        n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
+        n, vp, k = (i1 - i0) * (j1 - j0), C.c_void_p, int(reduce)
         dt = np.dtype(d_out.dtype)
-        if reduce:
-            return self._decode_slots_reduced(d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, int(reduce))
-        if self.overlap:
-            return self._decode_slots_overlap(d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides)
-        grid_args = (self.H, self.W, self.th, self.tw, i0, i1, j0, j1, y0, x0, h, w)
-        if dt.kind == "u":
+        integer = dt.kind == "u"
+        # the plan: the batched decode (with what it takes behind the output) and the element type of its tiles, rh x rw of one
+        # decoded tile, the call that assembles them and the geometry it takes in front of the sub-grid and the window
+        rec = self.codec.geom["rec_h"], self.codec.geom["rec_w"]
+        if k:
+            op, more, tile_dt = "decode_reduced", (k,), dt
+            rh, rw = (rs["pic_h"], rs["pic_w"]) if integer else (rs["rec_h"], rs["rec_w"])
+            stem, geom = "spiht_tile_mosaic_", (rs["off_y"], rs["off_x"], rs["Hk"], rs["Wk"], rs["thk"], rs["twk"])
+        elif self.overlap:
+            op, more, tile_dt, (rh, rw) = "decode", (), np.dtype(np.float64), rec
+            stem, geom = "spiht_tile_blend_", (self.H, self.W, self.th, self.tw, self.overlap)
+        else:
+            op, more, tile_dt = "decode", (), dt
+            rh, rw = (self.th, self.tw) if integer else rec
+            stem, geom = "spiht_tile_paste_", (self.H, self.W, self.th, self.tw)
+        view = ()  # the integer forms write a view of the output: the strides, behind the address
+        if integer:
             st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
             _check_aligned(d_out.ptr, dt)
-            d_dec = self._buf("dec", n * self.c * self.th * self.tw * dt.itemsize)
-            dec = self.codec.decode_device_u16 if dt.itemsize == 2 else self.codec.decode_device_u8
-            dec(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, slot_stride=stride)
-            paste = self.L.spiht_tile_paste_u16 if dt.itemsize == 2 else self.L.spiht_tile_paste_u8
-            _lib.check(paste(self.ctx.handle, vp(d_dec.ptr), self.c, self.th, self.tw, *grid_args, vp(d_out.ptr), st_p))
-        else:
-            if dt != np.float64 or strides is not None:
-                raise ValueError("decode: the float form gives dense float64 pictures")
-            rh, rw = self.codec.geom["rec_h"], self.codec.geom["rec_w"]
-            d_dec = self._buf("dec", n * self.c * rh * rw * 8)
-            self.codec.decode_device(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, slot_stride=stride)
-            _lib.check(self.L.spiht_tile_paste_f64(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *grid_args, vp(d_out.ptr)))
-        self.last_tiles_decoded = n
-
-    def _decode_slots_overlap(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides):
-        """overlap > 0, every element type: one batched float64 decode of the coded tiles, one blend (spiht_tile_blend_*), which
-        converts the blended sample for 8- and 16-bit output"""
-        (i0, i1, j0, j1), (y0, x0, h, w) = sub, window
-        n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
-        dt = np.dtype(d_out.dtype)
-        rh, rw = self.codec.geom["rec_h"], self.codec.geom["rec_w"]
-        args = (self.c, rh, rw, self.H, self.W, self.th, self.tw, self.overlap, i0, i1, j0, j1, y0, x0, h, w)
-        if dt.kind == "u":
-            st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
-            _check_aligned(d_out.ptr, dt)
-            blend, tail = (self.L.spiht_tile_blend_u16 if dt.itemsize == 2 else self.L.spiht_tile_blend_u8), (st_p,)
-        else:
-            if dt != np.float64 or strides is not None:
-                raise ValueError("decode: the float form gives dense float64 pictures")
-            blend, tail = self.L.spiht_tile_blend_f64, ()
-        d_dec = self._buf("dec", n * self.c * rh * rw * 8)
-        self.codec.decode_device(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, slot_stride=stride)
-        _lib.check(blend(self.ctx.handle, vp(d_dec.ptr), *args, vp(d_out.ptr), *tail))
-        self.last_tiles_decoded = n
-
-    def _decode_slots_reduced(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, k):
-        (i0, i1, j0, j1), (y0, x0, h, w) = sub, window
-        n, vp = (i1 - i0) * (j1 - j0), C.c_void_p
-        dt = np.dtype(d_out.dtype)
-        grid_args = (rs["off_y"], rs["off_x"], rs["Hk"], rs["Wk"], rs["thk"], rs["twk"], i0, i1, j0, j1, y0, x0, h, w)
-        if dt.kind == "u":
-            st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
-            _check_aligned(d_out.ptr, dt)
-            rh, rw = rs["pic_h"], rs["pic_w"]
-            d_dec = self._buf("dec", n * self.c * rh * rw * dt.itemsize)
-            dec = self.codec.decode_reduced_device_u16 if dt.itemsize == 2 else self.codec.decode_reduced_device_u8
-            dec(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, k, slot_stride=stride)
-            mosaic = self.L.spiht_tile_mosaic_u16 if dt.itemsize == 2 else self.L.spiht_tile_mosaic_u8
-            _lib.check(mosaic(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *grid_args, vp(d_out.ptr), st_p))
-        else:
-            if dt != np.float64 or strides is not None:
-                raise ValueError("decode: the float form gives dense float64 pictures")
-            rh, rw = rs["rec_h"], rs["rec_w"]
-            d_dec = self._buf("dec", n * self.c * rh * rw * 8)
-            self.codec.decode_reduced_device(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, k, slot_stride=stride)
-            _lib.check(self.L.spiht_tile_mosaic_f64(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *grid_args, vp(d_out.ptr)))
+            view = (st_p,)
+        elif dt != np.float64 or strides is not None:
+            raise ValueError("decode: the float form gives dense float64 pictures")
+        d_dec = self._buf("dec", n * self.c * rh * rw * tile_dt.itemsize)
+        self._tile_call(op, tile_dt)(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, *more, slot_stride=stride)
+        _lib.check(_entry(self.L, stem, dt)(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *geom, i0, i1, j0, j1, y0, x0, h, w,
+                                            vp(d_out.ptr), *view))
         self.last_tiles_decoded = n
 
     def decode_device(self, d_packed, packed_bytes, d_lens, d_max_n, d_out, strides=None, slot_stride=None, reduce=0):
@@ -859,48 +841,67 @@ class TiledCodec:
         self._decode_slots(d_slots, d_nbytes, _ptr(d_max_n), stride, sub, window, d_out, strides, rs, reduce)
 
     # ---- host forms ----------------------------------------------------------------------------------
-    def _encode_host(self, images, dtype, channels_last, name, roi=None, target_psnr=None):
+    def _encode_host(self, images, dtype, channels_last, name, roi=None, target_psnr=None, layered=False, layers=None):
+        """the frame of every host encode: the checks, the uploads (pictures, targets, weight map), the device form, one
+        synchronise, the downloads, and the results with last_allocation.  layered: encode_layered_device and LayeredResult
+        in place of encode_device and TiledResult; the table of lengths is then cum [N][Q][T], otherwise lens [N][1][T]"""
+        if layered and self.allocate is None:
+            raise ValueError('%s: the codec was not built with allocate="rd"' % name)
         self._overlap_refuses(name, roi, target_psnr)
         if roi is not None:
             self._roi_check(dtype, name)
-        if target_psnr is not None:
-            self._target_check(name)
-        single, N, d_img_view, strides = self._upload_pictures(images, dtype, channels_last, name)
-        NT = N * self.T
+        Q = 1
+        if not layered:
+            if target_psnr is not None:
+                self._target_check(name)
+        elif target_psnr is None:
+            Q = len(alloc.layer_budgets(self.max_bits, layers))
+        else:
+            dbs = alloc.layer_targets_arg(target_psnr, layers)
+            Q = len(dbs)
+        single, N, d_img, strides = self._upload_pictures(images, dtype, channels_last, name)
+        T, NT = self.T, N * self.T
         d_packed = self._buf("packed", NT * self.codec.slot_stride)
-        d_lens = self._buf("lens", NT * 4)
+        d_table = self._buf("cum", N * Q * T * 4) if layered else self._buf("lens", NT * 4)
         d_maxn = self._buf("maxn", NT)
+        if layered:
+            d_pic = self._buf("picbytes", N * 8)
         d_target = None
         if target_psnr is not None:
             sums = self._weight_sums(roi, N)
-            d_target = self._targets_upload([alloc.target_psnr_arg(target_psnr, N)], sums, dtype)
-        self.encode_device(d_img_view, N, d_packed, d_lens, d_maxn, strides, *self._roi_upload(roi, N), d_target)
+            rows = [[db] * N for db in dbs] if layered else [alloc.target_psnr_arg(target_psnr, N)]
+            d_target = self._targets_upload(rows, sums, dtype)
+        if layered:
+            self.encode_layered_device(d_img, N, layers, d_packed, d_table, d_maxn, d_pic, strides, *self._roi_upload(roi, N),
+                                       target_psnr, d_target)
+        else:
+            self.encode_device(d_img, N, d_packed, d_table, d_maxn, strides, *self._roi_upload(roi, N), d_target)
         self.ctx.synchronize()
-        lens = np.empty(NT, dtype=np.uint32)
-        maxn = np.empty(NT, dtype=np.uint8)
-        self.ctx.download(lens, d_lens.ptr)   # the table: one download
-        self.ctx.download(maxn, d_maxn.ptr)
-        total = int(lens.sum(dtype=np.int64))
-        run = np.empty(total, dtype=np.uint8)
-        if total:
-            self.ctx.download(run, d_packed.ptr)  # the streams of all pictures: one download
-        out, off = [], np.concatenate(([0], np.cumsum(lens, dtype=np.int64)))
-        if self.allocate is not None:
-            lam = np.empty(N, dtype=np.float64)
-            self.ctx.download(lam, self._bufs["lambda"].ptr)
-            rows = [[int(v) for v in lens[n * self.T:(n + 1) * self.T]] for n in range(N)]
-            if d_target is None:
-                cuts = [TileAllocation(float(lam[n]), rows[n]) for n in range(N)]
-            else:
-                dist, met = np.empty(N, dtype=np.float64), np.empty(N, dtype=np.uint32)
-                self.ctx.download(dist, self._bufs["tdist"].ptr)
-                self.ctx.download(met, self._bufs["tmet"].ptr)
-                cuts = [self._allocation(lam[n], rows[n], dist[n], met[n], sums[n], dtype) for n in range(N)]
-            self.last_allocation = cuts[0] if single else cuts
+        table = self._download(d_table.ptr, (N, Q, T), np.uint32)  # the tables: one download each
+        maxn = self._download(d_maxn.ptr, NT, np.uint8)
+        if layered:
+            pic = self._download(d_pic.ptr, N, np.uint64).astype(np.int64)
+            cuts = self._download_cuts("s", Q, N, d_target is not None)
+        else:
+            pic = table.sum(axis=(1, 2), dtype=np.int64)
+        off = np.concatenate(([0], np.cumsum(pic)))
+        run = self._download(d_packed.ptr, int(off[-1]), np.uint8)  # the streams (layers) of all pictures: one download
+        if not layered and self.allocate is not None:  # (the plain form fetches its cut behind the streams)
+            cuts = self._download_cuts("", Q, N, d_target is not None)
+        out, allocations = [], []
         for n in range(N):
-            a, b = n * self.T, (n + 1) * self.T
-            out.append(TiledResult(self.H, self.W, self.c, self.th, self.tw, self.level, [int(v) for v in maxn[a:b]],
-                                   [int(v) for v in lens[a:b]], run[int(off[a]):int(off[b])].tobytes(), overlap=self.overlap))
+            rows = [[int(v) for v in row] for row in table[n]]
+            head = (self.H, self.W, self.c, self.th, self.tw, self.level, [int(v) for v in maxn[n * T:(n + 1) * T]])
+            data = run[int(off[n]):int(off[n + 1])].tobytes()
+            out.append(LayeredResult(*head, rows, data, overlap=self.overlap) if layered else
+                       TiledResult(*head, list(rows[0]), data, overlap=self.overlap))
+            if self.allocate is not None:
+                target = [None] * Q if d_target is None else [(cuts[1][q, n], cuts[2][q, n], sums[n], dtype) for q in range(Q)]
+                allocations.append([self._allocation(cuts[0][q, n], rows[q], target[q]) for q in range(Q)])
+        if self.allocate is not None:
+            if not layered:
+                allocations = [a[0] for a in allocations]
+            self.last_allocation = allocations[0] if single else allocations
         return out[0] if single else out
 
     def encode(self, image_or_images, roi=None, target_psnr=None):
@@ -957,58 +958,6 @@ class TiledCodec:
         self.ctx.upload(d_img.ptr, images)
         return single, shape[0], _View(d_img.ptr, dtype), strides
 
-    def _encode_layered_host(self, images, layers, dtype, channels_last, name, roi=None, target_psnr=None):
-        if self.allocate is None:
-            raise ValueError('%s: the codec was not built with allocate="rd"' % name)
-        self._overlap_refuses(name, roi, target_psnr)
-        if roi is not None:
-            self._roi_check(dtype, name)
-        if target_psnr is None:
-            Q = len(alloc.layer_budgets(self.max_bits, layers))
-        else:
-            dbs = alloc.layer_targets_arg(target_psnr, layers)
-            Q = len(dbs)
-        single, N, d_img, strides = self._upload_pictures(images, dtype, channels_last, name)
-        T, NT = self.T, N * self.T
-        d_packed = self._buf("packed", NT * self.codec.slot_stride)
-        d_cum = self._buf("cum", N * Q * T * 4)
-        d_maxn = self._buf("maxn", NT)
-        d_pic = self._buf("picbytes", N * 8)
-        d_target = None
-        if target_psnr is not None:
-            sums = self._weight_sums(roi, N)
-            d_target = self._targets_upload([[db] * N for db in dbs], sums, dtype)
-        self.encode_layered_device(d_img, N, layers, d_packed, d_cum, d_maxn, d_pic, strides, *self._roi_upload(roi, N),
-                                   target_psnr, d_target)
-        self.ctx.synchronize()
-        cum = np.empty((N, Q, T), dtype=np.uint32)
-        maxn = np.empty(NT, dtype=np.uint8)
-        pic = np.empty(N, dtype=np.uint64)
-        lam = np.empty((Q, N), dtype=np.float64)
-        self.ctx.download(cum, d_cum.ptr)     # the tables: one download each
-        self.ctx.download(maxn, d_maxn.ptr)
-        self.ctx.download(pic, d_pic.ptr)
-        self.ctx.download(lam, self._bufs["lambdas"].ptr)
-        if d_target is not None:
-            dist, met = np.empty((Q, N), dtype=np.float64), np.empty((Q, N), dtype=np.uint32)
-            self.ctx.download(dist, self._bufs["tdists"].ptr)
-            self.ctx.download(met, self._bufs["tmets"].ptr)
-        off = np.concatenate(([0], np.cumsum(pic.astype(np.int64))))
-        run = np.empty(int(off[-1]), dtype=np.uint8)
-        if run.size:
-            self.ctx.download(run, d_packed.ptr)  # the layers of all pictures: one download
-        out, cuts = [], []
-        for n in range(N):
-            rows = [[int(v) for v in row] for row in cum[n]]
-            if d_target is None:
-                cuts.append([TileAllocation(float(lam[q, n]), rows[q]) for q in range(Q)])
-            else:
-                cuts.append([self._allocation(lam[q, n], rows[q], dist[q, n], met[q, n], sums[n], dtype) for q in range(Q)])
-            out.append(LayeredResult(self.H, self.W, self.c, self.th, self.tw, self.level, [int(v) for v in maxn[n * T:(n + 1) * T]],
-                                     rows, run[int(off[n]):int(off[n + 1])].tobytes(), overlap=self.overlap))
-        self.last_allocation = cuts[0] if single else cuts
-        return out[0] if single else out
-
     def encode_layered(self, image_or_images, layers=None, roi=None, target_psnr=None):
         """encode in quality layers (a codec built with allocate="rd"; otherwise ValueError).  layers: an int Q or the layers'
         bit budgets, the last one max_bits (alloc.layer_budgets).  -> LayeredResult, or a list for [N, c, H, W];
@@ -1019,17 +968,15 @@ class TiledCodec:
         or their number).  Layer q ends where encode(..., target_psnr=target_psnr[q]) cuts: result.tiled(q + 1) is that
         TiledResult.  max_bits stays the cap; a layer whose target it cannot pay for ends at the cut of max_bits, and the layers
         behind it are empty.  The container is the same SPTQ."""
-        return self._encode_layered_host(image_or_images, layers, self.pixel_dtype, False, "encode_layered", roi, target_psnr)
+        return self._encode_host(image_or_images, self.pixel_dtype, False, "encode_layered", roi, target_psnr, True, layers)
 
     def encode_layered_u8(self, image_or_images, layers=None, channels_last=False, roi=None, target_psnr=None):
         """encode_layered of uint8 pictures, as encode_u8"""
-        return self._encode_layered_host(image_or_images, layers, np.uint8, channels_last, "encode_layered_u8", roi,
-                                         target_psnr)
+        return self._encode_host(image_or_images, np.uint8, channels_last, "encode_layered_u8", roi, target_psnr, True, layers)
 
     def encode_layered_u16(self, image_or_images, layers=None, channels_last=False, roi=None, target_psnr=None):
         """encode_layered of uint16 pictures, as encode_u16"""
-        return self._encode_layered_host(image_or_images, layers, np.uint16, channels_last, "encode_layered_u16", roi,
-                                         target_psnr)
+        return self._encode_host(image_or_images, np.uint16, channels_last, "encode_layered_u16", roi, target_psnr, True, layers)
 
     def tile_curves(self, image, dtype=None, roi=None):
         """The curves allocate="rd" cuts by, of one picture [c, H, W] (dtype None: the codec's float pixels; np.uint8 /
@@ -1044,100 +991,72 @@ class TiledCodec:
         dtype = self.pixel_dtype if dtype is None else np.dtype(dtype)
         self._encode_host(image, dtype, False, "tile_curves", roi)
         T, K = self.T, self.points
-        D = np.empty((K + 1, T), dtype=np.uint64 if dtype.kind == "u" else np.float64)
-        nbits = np.empty(T, dtype=np.uint64)
-        maxn = np.empty(T, dtype=np.uint8)
-        self.ctx.download(D, self._bufs["D"].ptr)
-        self.ctx.download(nbits, self._bufs["nbits"].ptr)
-        self.ctx.download(maxn, self._bufs["maxn"].ptr)
+        D = self._download(self._bufs["D"].ptr, (K + 1, T), np.uint64 if dtype.kind == "u" else np.float64)
+        nbits = self._download(self._bufs["nbits"].ptr, T, np.uint64)
+        maxn = self._download(self._bufs["maxn"].ptr, T, np.uint8)
         nbytes = [(int(v) + 7) // 8 for v in nbits]
         return TileCurves([alloc.tile_lengths(n, K) for n in nbytes], np.ascontiguousarray(D.T), nbytes, [int(v) for v in maxn])
 
-    def _check_result(self, r):
+    def _check_result(self, r, layered):
+        """ValueError for a result that is not one of this codec's pictures; a TiledResult's tables are checked here, a
+        LayeredResult's by its own _table()"""
         _check_version(r)
-        if (r.h, r.w, r.c, r.th, r.tw) != (self.H, self.W, self.c, self.th, self.tw):
+        if (r.h, r.w, r.c, r.th, r.tw) != (self.H, self.W, self.c, self.th, self.tw) or (layered and len(r.max_n) != self.T):
             raise ValueError("a result of geometry %s, the codec's is %s" % ((r.h, r.w, r.c, r.th, r.tw),
                                                                             (self.H, self.W, self.c, self.th, self.tw)))
         if r.overlap != self.overlap:
             raise ValueError("a result of overlap %d, the codec's is %d" % (r.overlap, self.overlap))
-        if len(r.nbytes) != self.T or len(r.max_n) != self.T or sum(r.nbytes) != len(r.encoded_bytes):
+        if not layered and (len(r.nbytes) != self.T or len(r.max_n) != self.T or sum(r.nbytes) != len(r.encoded_bytes)):
             raise ValueError("the tables of the result do not describe %d tiles of %d bytes" % (self.T, len(r.encoded_bytes)))
 
-    def _decode_host(self, result, window, dtype, channels_last, reduce=0):
-        self._check_result(result)
+    def _decode_host(self, result, window, dtype, channels_last, reduce=0, layered=False, upto=None):
+        """the frame of every host decode, of a TiledResult or (layered) of the first upto layers of a LayeredResult: the checks,
+        the window and its sub-grid, one upload of a blob -- a u32 table [rows][n] of the sub-grid's n tiles whose last row is
+        their lengths, their start planes padded to a multiple of 4, their bytes -- the device form, one synchronise and one
+        download.  The kinds differ in the table (lens [1][n] / cum [upto][n]), in the byte ranges gathered and in the device form"""
+        self._check_result(result, layered)
+        if layered:
+            cum, lens, off = result._table()
+            upto = _upto_arg(upto, cum.shape[0])
         rs = self.reduced_shape(reduce)
         y0, x0, h, w = self._window_arg(window, rs)
         i0, i1, j0, j1 = sub = self._window_tiles(rs, y0, x0, h, w)
         dtype = np.dtype(dtype)
-        # the streams of the sub-grid's tiles (a row of it is contiguous in the run), their lengths and start planes: one upload
-        off = result._offsets()
         ts = [i * self.gx + j for i in range(i0, i1) for j in range(j0, j1)]
         n = len(ts)
-        lens = np.asarray([result.nbytes[t] for t in ts], dtype=np.uint32)
-        nb = int(lens.sum(dtype=np.int64))
-        head = 4 * n + ((n + 3) & ~3)
+        # a row of the sub-grid, tiles a .. b - 1, is contiguous in the run (per layer, in the file)
+        rows = [(i * self.gx + j0, i * self.gx + j1) for i in range(i0, i1)]
+        if layered:
+            table = np.ascontiguousarray(cum[:upto, ts], dtype=np.uint32)
+            ranges = [(int(off[q, a]), int(off[q, b - 1] + lens[q, b - 1])) for q in range(upto) for a, b in rows]
+        else:
+            table = np.asarray([[result.nbytes[t] for t in ts]], dtype=np.uint32)
+            off = result._offsets()
+            ranges = [(int(off[a]), int(off[b])) for a, b in rows]
+        total = table[-1]  # the tiles' lengths
+        nb = int(total.sum(dtype=np.int64))
+        planes = 4 * table.size
+        head = planes + ((n + 3) & ~3)
         blob = np.zeros(head + max(nb, 1), dtype=np.uint8)
-        blob[:4 * n] = lens.view(np.uint8)
-        blob[4 * n:5 * n] = np.asarray([result.max_n[t] for t in ts], dtype=np.uint8)
+        blob[:planes] = table.reshape(-1).view(np.uint8)
+        blob[planes:planes + n] = np.asarray([result.max_n[t] for t in ts], dtype=np.uint8)
         data = np.frombuffer(result.encoded_bytes, dtype=np.uint8)
         p = head
-        for i in range(i0, i1):
-            a, b = int(off[i * self.gx + j0]), int(off[i * self.gx + j1])
+        for a, b in ranges:
             blob[p:p + b - a] = data[a:b]
             p += b - a
         d_in = self._buf("in", blob.nbytes)
-        self.ctx.upload(d_in.ptr, blob)
+        self.ctx.upload(d_in.ptr, blob)  # the table, the start planes and the streams of the sub-grid's tiles: one upload
         es = dtype.itemsize
         strides = (es, w * self.c * es, self.c * es) if channels_last else None
         d_out = self._buf("out", self.c * h * w * es)
-        stride = max(4, (int(lens.max()) + 3) & ~3)
-        self.decode_window_device(d_in.ptr + head, nb, d_in.ptr, d_in.ptr + 4 * n, sub, (y0, x0, h, w), _View(d_out.ptr, dtype),
-                                  strides, stride, reduce)
-        self.ctx.synchronize()
-        out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w), dtype)
-        self.ctx.download(out, d_out.ptr)
-        return out
-
-    def _decode_layered_host(self, result, window, upto, dtype, channels_last, reduce=0):
-        _check_version(result)
-        if (result.h, result.w, result.c, result.th, result.tw) != (self.H, self.W, self.c, self.th, self.tw) \
-                or len(result.max_n) != self.T:
-            raise ValueError("a result of geometry %s, the codec's is %s" % ((result.h, result.w, result.c, result.th, result.tw),
-                                                                            (self.H, self.W, self.c, self.th, self.tw)))
-        if result.overlap != self.overlap:
-            raise ValueError("a result of overlap %d, the codec's is %d" % (result.overlap, self.overlap))
-        cum, lens, off = result._table()
-        upto = _upto_arg(upto, cum.shape[0])
-        rs = self.reduced_shape(reduce)
-        y0, x0, h, w = self._window_arg(window, rs)
-        i0, i1, j0, j1 = sub = self._window_tiles(rs, y0, x0, h, w)
-        dtype = np.dtype(dtype)
-        # the table, the start planes and the pieces of the sub-grid's tiles in the layers below upto -- per layer a row of the
-        # sub-grid is contiguous in the file: one upload
-        ts = [i * self.gx + j for i in range(i0, i1) for j in range(j0, j1)]
-        n = len(ts)
-        sub_cum = np.ascontiguousarray(cum[:upto, ts], dtype=np.uint32)
-        nb = int(sub_cum[-1].sum(dtype=np.int64))
-        head = 4 * upto * n + ((n + 3) & ~3)
-        blob = np.zeros(head + max(nb, 1), dtype=np.uint8)
-        blob[:4 * upto * n] = sub_cum.reshape(-1).view(np.uint8)
-        blob[4 * upto * n:4 * upto * n + n] = np.asarray([result.max_n[t] for t in ts], dtype=np.uint8)
-        data = np.frombuffer(result.encoded_bytes, dtype=np.uint8)
-        p = head
-        for q in range(upto):
-            for i in range(i0, i1):
-                a = int(off[q, i * self.gx + j0])
-                b = int(off[q, i * self.gx + j1 - 1] + lens[q, i * self.gx + j1 - 1])
-                blob[p:p + b - a] = data[a:b]
-                p += b - a
-        d_in = self._buf("in", blob.nbytes)
-        self.ctx.upload(d_in.ptr, blob)
-        es = dtype.itemsize
-        strides = (es, w * self.c * es, self.c * es) if channels_last else None
-        d_out = self._buf("out", self.c * h * w * es)
-        stride = max(4, (int(sub_cum[-1].max()) + 3) & ~3)
-        self.decode_layers_device(d_in.ptr + head, nb, d_in.ptr, d_in.ptr + 4 * upto * n, upto, upto, sub, (y0, x0, h, w),
-                                  _View(d_out.ptr, dtype), strides, stride, None, reduce)
+        stride = max(4, (int(total.max()) + 3) & ~3)
+        streams = (d_in.ptr + head, nb, d_in.ptr, d_in.ptr + planes)
+        where = (sub, (y0, x0, h, w), _View(d_out.ptr, dtype), strides, stride)
+        if layered:
+            self.decode_layers_device(*streams, upto, upto, *where, None, reduce)
+        else:
+            self.decode_window_device(*streams, *where, reduce)
         self.ctx.synchronize()
         out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w), dtype)
         self.ctx.download(out, d_out.ptr)
@@ -1147,24 +1066,24 @@ class TiledCodec:
         """LayeredResult -> float64 [c, H, W] from its first `upto` layers (None: all): what decode gives for
         result.tiled(upto), with the tiles' pieces gathered on the device -- one upload, one layer-unpack, one batched decode,
         one paste.  A prefix of a file (LayeredResult.from_bytes) decodes like any other result.  reduce: as decode."""
-        return self._decode_layered_host(result, None, upto, np.float64, False, reduce)
+        return self._decode_host(result, None, np.float64, False, reduce, True, upto)
 
     def decode_layered_u8(self, result, upto=None, channels_last=False, reduce=0):
-        return self._decode_layered_host(result, None, upto, np.uint8, channels_last, reduce)
+        return self._decode_host(result, None, np.uint8, channels_last, reduce, True, upto)
 
     def decode_layered_u16(self, result, upto=None, channels_last=False, reduce=0):
-        return self._decode_layered_host(result, None, upto, np.uint16, channels_last, reduce)
+        return self._decode_host(result, None, np.uint16, channels_last, reduce, True, upto)
 
     def decode_layered_window(self, result, y0, x0, h, w, upto=None, reduce=0):
         """-> float64 [c, h, w] = decode_layered(result, upto)[:, y0:y0 + h, x0:x0 + w]; only the pieces of the tiles that meet
         the window, of the layers below upto, are uploaded (last_tiles_decoded tells how many tiles).  reduce: as decode_window."""
-        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.float64, False, reduce)
+        return self._decode_host(result, (y0, x0, h, w), np.float64, False, reduce, True, upto)
 
     def decode_layered_window_u8(self, result, y0, x0, h, w, upto=None, channels_last=False, reduce=0):
-        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.uint8, channels_last, reduce)
+        return self._decode_host(result, (y0, x0, h, w), np.uint8, channels_last, reduce, True, upto)
 
     def decode_layered_window_u16(self, result, y0, x0, h, w, upto=None, channels_last=False, reduce=0):
-        return self._decode_layered_host(result, (y0, x0, h, w), upto, np.uint16, channels_last, reduce)
+        return self._decode_host(result, (y0, x0, h, w), np.uint16, channels_last, reduce, True, upto)
 
     def decode(self, result, reduce=0):
         """TiledResult -> float64 [c, H, W]: one upload, one unpack, one batched decode of all T tiles, one paste.  Unlike
@@ -1230,11 +1149,16 @@ def _codec_for(c, H, W, tile, settings, level, max_bits, pixel_dtype=np.float64,
     return codec
 
 
-def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_last, name, allocate=None, points=alloc.POINTS,
-                  spread=alloc.SPREAD, roi=None, target_psnr=None, overlap=0):
+def _picture_shape(image, channels_last):
+    """(c, h, w) of the one picture a module-level encode call takes"""
     if not isinstance(image, np.ndarray) or image.ndim != 3:
         raise ValueError('image ndim must be 3: c,h,w')
-    c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
+    return (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
+
+
+def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_last, name, allocate=None, points=alloc.POINTS,
+                  spread=alloc.SPREAD, roi=None, target_psnr=None, overlap=0):
+    c, h, w = _picture_shape(image, channels_last)
     if dtype is None:
         dtype = np.float32 if image.dtype in (np.float32, np.float16) else np.float64
     codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if np.dtype(dtype).kind == "f" else np.float64,
@@ -1271,10 +1195,10 @@ def encode_image_tiled_u16(image, tile, spiht_settings=SpihtSettings(), level=No
                          points, spread, roi, target_psnr, overlap)
 
 
-def _decode_tiled(result, spiht_settings, window, dtype, channels_last, reduce=0):
+def _decode_tiled(result, spiht_settings, window, dtype, channels_last, reduce=0, layered=False, upto=None):
     codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None,
                        overlap=result.overlap)
-    return codec._decode_host(result, window, dtype, channels_last, reduce)
+    return codec._decode_host(result, window, dtype, channels_last, reduce, layered, upto)
 
 
 def decode_image_tiled(result, spiht_settings, reduce=0):
@@ -1309,12 +1233,10 @@ def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype,
                     target_psnr=None, overlap=0):
     if layers is None and target_psnr is None:
         layers = 1
-    if not isinstance(image, np.ndarray) or image.ndim != 3:
-        raise ValueError('image ndim must be 3: c,h,w')
-    c, h, w = (image.shape[2], image.shape[0], image.shape[1]) if channels_last else image.shape
+    c, h, w = _picture_shape(image, channels_last)
     codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, np.float64, "rd", points, spread, overlap)
-    return codec._encode_layered_host(image, layers, codec.pixel_dtype if dtype is None else dtype, channels_last, name, roi,
-                                      target_psnr)
+    return codec._encode_host(image, codec.pixel_dtype if dtype is None else dtype, channels_last, name, roi, target_psnr, True,
+                              layers)
 
 
 def encode_image_layered(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=None, points=alloc.POINTS,
@@ -1341,34 +1263,28 @@ def encode_image_layered_u16(image, tile, spiht_settings=SpihtSettings(), level=
                            points, spread, roi, target_psnr, overlap)
 
 
-def _decode_layered(result, spiht_settings, window, upto, dtype, channels_last, reduce=0):
-    codec = _codec_for(result.c, result.h, result.w, (result.th, result.tw), spiht_settings, result.level, None,
-                       overlap=result.overlap)
-    return codec._decode_layered_host(result, window, upto, dtype, channels_last, reduce)
-
-
 def decode_image_layered(result, spiht_settings, upto=None, reduce=0):
     """LayeredResult -> float64 (c, h, w) from its first `upto` layers (None: all), cropped as decode_image_tiled; reduce: as
     decode_image_tiled"""
-    return _decode_layered(result, spiht_settings, None, upto, np.float64, False, reduce)
+    return _decode_tiled(result, spiht_settings, None, np.float64, False, reduce, True, upto)
 
 
 def decode_image_layered_u8(result, spiht_settings, upto=None, channels_last=False, reduce=0):
-    return _decode_layered(result, spiht_settings, None, upto, np.uint8, channels_last, reduce)
+    return _decode_tiled(result, spiht_settings, None, np.uint8, channels_last, reduce, True, upto)
 
 
 def decode_image_layered_u16(result, spiht_settings, upto=None, channels_last=False, reduce=0):
-    return _decode_layered(result, spiht_settings, None, upto, np.uint16, channels_last, reduce)
+    return _decode_tiled(result, spiht_settings, None, np.uint16, channels_last, reduce, True, upto)
 
 
 def decode_image_layered_window(result, spiht_settings, y0, x0, h, w, upto=None, reduce=0):
     """the window of the picture from its first `upto` layers, decoding only the tiles it meets; reduce: as decode_image_window"""
-    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.float64, False, reduce)
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.float64, False, reduce, True, upto)
 
 
 def decode_image_layered_window_u8(result, spiht_settings, y0, x0, h, w, upto=None, channels_last=False, reduce=0):
-    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.uint8, channels_last, reduce)
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint8, channels_last, reduce, True, upto)
 
 
 def decode_image_layered_window_u16(result, spiht_settings, y0, x0, h, w, upto=None, channels_last=False, reduce=0):
-    return _decode_layered(result, spiht_settings, (y0, x0, h, w), upto, np.uint16, channels_last, reduce)
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint16, channels_last, reduce, True, upto)

@@ -10,28 +10,11 @@ import pytest
 
 from alloc_cases import PINNED
 from conftest import synth_image
+from tile_helpers import dev, padded, tile_pixels
 
 pytestmark = pytest.mark.gpu
 
 vp = C.c_void_p
-
-
-def dev(arr):
-    from spiht_amd import _lib
-    from spiht_amd.batch import DeviceArray
-    arr = np.ascontiguousarray(arr)
-    d = DeviceArray(_lib.default_context(), arr.shape, arr.dtype)
-    d.upload(arr)
-    return d
-
-
-def padded(P, th, tw):
-    H, W = P.shape[-2:]
-    return np.pad(P, [(0, 0)] * (P.ndim - 2) + [(0, -H % th), (0, -W % tw)], mode="edge")
-
-
-def tile_pixels(P, th, tw, i, j):
-    return np.ascontiguousarray(padded(P, th, tw)[..., i * th:(i + 1) * th, j * tw:(j + 1) * tw])
 
 
 # ---- prefix slots ---------------------------------------------------------------------------------------------------------

@@ -10,20 +10,12 @@ import numpy as np
 import pytest
 
 from conftest import synth_image
+from tile_helpers import dev, padded
 
 pytestmark = pytest.mark.gpu
 
 vp = C.c_void_p
 GUARD = 0xEE
-
-
-def dev(arr):
-    from spiht_amd import _lib
-    from spiht_amd.batch import DeviceArray
-    arr = np.ascontiguousarray(arr)
-    d = DeviceArray(_lib.default_context(), arr.shape, arr.dtype)
-    d.upload(arr)
-    return d
 
 
 # ---- the two copies against numpy ------------------------------------------------------------------------------------------
@@ -278,11 +270,6 @@ def case(name):
         plain = codec.encode(P)
     curves = codec.tile_curves(P, cfg.get("dtype"))
     return cfg, P, s, codec, res, cuts, plain, curves
-
-
-def padded(P, th, tw):
-    H, W = P.shape[-2:]
-    return np.pad(P, [(0, 0)] * (P.ndim - 2) + [(0, -H % th), (0, -W % tw)], mode="edge")
 
 
 @pytest.mark.parametrize("name", list(CASES))

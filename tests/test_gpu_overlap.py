@@ -8,21 +8,13 @@ import numpy as np
 import pytest
 
 from conftest import synth_image
+from tile_helpers import dev, tile_of
 
 pytestmark = pytest.mark.gpu
 
 vp = C.c_void_p
 DTYPES = {1: np.uint8, 2: np.uint16, 4: np.float32, 8: np.float64}
 SENTINEL = {1: 0xA5, 2: 0xA5A5, 4: -77.5, 8: -77.5}
-
-
-def dev(arr):
-    from spiht_amd import _lib
-    from spiht_amd.batch import DeviceArray
-    arr = np.ascontiguousarray(arr)
-    d = DeviceArray(_lib.default_context(), arr.shape, arr.dtype)
-    d.upload(arr)
-    return d
 
 
 def rand_array(rng, shape, es):
@@ -211,10 +203,6 @@ CASES = {
 def settings(cfg):
     import spiht_amd
     return spiht_amd.SpihtSettings(color_model=cfg.get("color"))
-
-
-def tile_of(tile):
-    return tuple(tile) if isinstance(tile, tuple) else (tile, tile)
 
 
 def rule_decode(result, s, window=None, dtype=np.float64):

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from conftest import synth_image
-from test_gpu_alloc import dev, sse_operands, tile_pixels, valid
+from test_gpu_alloc import sse_operands, valid
+from tile_helpers import dev, tile_pixels
 
 pytestmark = pytest.mark.gpu
 

@@ -12,26 +12,12 @@ import pytest
 
 from conftest import synth_image
 from target_cases import PINNED, all_slopes, dist_at, hulls_of, random_table, same_float
+from tile_helpers import dev, tile_pixels
 
 pytestmark = pytest.mark.gpu
 
 vp = C.c_void_p
 NAN_GUARD = 0x7FF8000000000123  # a NaN that is not the kernel's: an output not written shows
-
-
-def dev(arr):
-    from spiht_amd import _lib
-    from spiht_amd.batch import DeviceArray
-    arr = np.ascontiguousarray(arr)
-    d = DeviceArray(_lib.default_context(), arr.shape, arr.dtype)
-    d.upload(arr)
-    return d
-
-
-def tile_pixels(P, th, tw, i, j):
-    H, W = P.shape[-2:]
-    padded = np.pad(P, [(0, 0)] * (P.ndim - 2) + [(0, -H % th), (0, -W % tw)], mode="edge")
-    return np.ascontiguousarray(padded[..., i * th:(i + 1) * th, j * tw:(j + 1) * tw])
 
 
 def run_target(nbytes, K, D, budget, kind, targets, optional=True):

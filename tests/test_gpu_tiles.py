@@ -8,30 +8,11 @@ import numpy as np
 import pytest
 
 from conftest import synth_image
+from tile_helpers import dev, padded, settings, tile_of, tile_pixels
 
 pytestmark = pytest.mark.gpu
 
 vp = C.c_void_p
-
-
-def settings(cfg):
-    import spiht_amd
-    return spiht_amd.SpihtSettings(wavelet=cfg.get("wavelet", "bior2.2"), mode=cfg.get("mode", "reflect"),
-                                   color_model=cfg.get("color"))
-
-
-def tile_of(tile):
-    return tuple(tile) if isinstance(tile, tuple) else (tile, tile)
-
-
-def padded(P, th, tw):
-    """the picture extended by edge replication to whole tiles"""
-    H, W = P.shape[-2:]
-    return np.pad(P, [(0, 0)] * (P.ndim - 2) + [(0, -H % th), (0, -W % tw)], mode="edge")
-
-
-def tile_pixels(P, th, tw, i, j):
-    return np.ascontiguousarray(padded(P, th, tw)[..., i * th:(i + 1) * th, j * tw:(j + 1) * tw])
 
 
 def same_result(a, b):
@@ -47,15 +28,6 @@ def same_tiled(a, b):
 def to_int(dec, dtype):
     """the contract's formula of the integer decodes: clip, scale, truncate"""
     return (np.clip(dec, 0.0, 1.0) * float(np.iinfo(dtype).max)).astype(dtype)
-
-
-def dev(arr):
-    from spiht_amd import _lib
-    from spiht_amd.batch import DeviceArray
-    arr = np.ascontiguousarray(arr)
-    d = DeviceArray(_lib.default_context(), arr.shape, arr.dtype)
-    d.upload(arr)
-    return d
 
 
 # the smallest shapes at which each thing can go wrong
@@ -518,3 +490,145 @@ def test_command_line_tile_and_window(tmp_path):
     _, win = main(build_parser().parse_args(common + ["--window", "28,30,10,8", "--out", str(tmp_path / "win.png")]))
     assert np.array_equal(win, dec[:, 28:38, 30:38])
     assert imload(str(tmp_path / "win.png")).shape == (3, 10, 8)
+
+
+# ---- refusals: a foreign result, a wrong output or picture array, a reduce that is no level ----------------------------------
+
+PIN = dict(c=1, H=70, W=90, tile=32)
+# one of H, W, c, th, tw changed at a time
+FOREIGN = [dict(H=71), dict(W=91), dict(c=2), dict(tile=(40, 32)), dict(tile=(32, 40))]
+
+
+@functools.lru_cache(maxsize=None)
+def pinned(overlap, **change):
+    """the codecs of PIN (or of PIN with one thing changed) with that overlap: a plain one and an allocate="rd" one, the tiled
+    result of the first and the two-layer result of the second: computed once, shared, never changed"""
+    import spiht_amd
+    g = dict(PIN, **change)
+    P = synth_image(4100 + g["H"] + g["W"] + g["c"], g["c"], g["H"], g["W"])
+    plain = spiht_amd.TiledCodec(g["c"], g["H"], g["W"], g["tile"], None, None, 27005, overlap=overlap)
+    rd = spiht_amd.TiledCodec(g["c"], g["H"], g["W"], g["tile"], None, None, 40000, allocate="rd", overlap=overlap)
+    return plain, rd, plain.encode(P), rd.encode_layered(P, 2)
+
+
+@pytest.mark.parametrize("overlap", [0, 4])
+def test_foreign_result_is_refused_by_every_host_decode(overlap):
+    """a result of another geometry, one whose max_n misses a tile and one whose lengths do not describe its bytes: ValueError
+    from every host decode, and the codec decodes a good result afterwards as it did before"""
+    import dataclasses
+    plain, rd, res, lay = pinned(overlap)
+    calls = [(plain, res, lambda k, r: k.decode(r)),
+             (plain, res, lambda k, r: k.decode_window_u8(r, 28, 30, 10, 8)),
+             (rd, lay, lambda k, r: k.decode_layered(r)),
+             (rd, lay, lambda k, r: k.decode_layered_window_u16(r, 28, 30, 10, 8, upto=1))]
+    for n, (codec, good, call) in enumerate(calls):
+        layered = good is lay
+        before = call(codec, good)
+        bad = [pinned(overlap, **change)[3 if layered else 2] for change in FOREIGN]
+        bad.append(dataclasses.replace(good, max_n=good.max_n[:-1]))
+        if layered:  # the layered result's own tables: its pieces do not add up to its bytes
+            bad.append(dataclasses.replace(good, encoded_bytes=good.encoded_bytes[:-1]))
+        else:
+            bad.append(dataclasses.replace(good, nbytes=[good.nbytes[0] + 1] + good.nbytes[1:]))
+            bad.append(dataclasses.replace(good, nbytes=good.nbytes[:-1]))
+        for r in bad:
+            with pytest.raises(ValueError):
+                call(codec, r)
+        after = call(codec, good)
+        assert after.dtype == before.dtype and after.tobytes() == before.tobytes(), n
+
+
+def device_streams(res):
+    """the streams, lengths and start planes of a TiledResult on the device, as decode_device takes them"""
+    return (dev(np.frombuffer(res.encoded_bytes, np.uint8)), len(res.encoded_bytes), dev(np.array(res.nbytes, np.uint32)),
+            dev(np.array(res.max_n, np.uint8)))
+
+
+@pytest.mark.parametrize("form", ["plain", "reduced", "overlap"])
+def test_decode_device_refuses_an_output_it_does_not_write(form):
+    """a float32 output, a float64 output with strides: ValueError from each of the three assemblers; the output keeps the
+    pattern it was filled with and last_tiles_decoded its value"""
+    from spiht_amd import _lib
+    ctx = _lib.default_context()
+    codec, _, res, _ = pinned(4 if form == "overlap" else 0)
+    reduce = 1 if form == "reduced" else 0
+    rs = codec.reduced_shape(reduce)
+    shape = (1, rs["Hk"], rs["Wk"])
+    assert shape == ((1, 35, 45) if reduce else (1, 70, 90))
+    good = codec.decode(res, reduce=reduce)
+    assert good.shape == shape
+    streams = device_streams(res)
+    codec.last_tiles_decoded = 77
+    for dtype, strides in [(np.float32, None), (np.float64, (8 * shape[1] * shape[2], 8 * shape[2], 8))]:
+        pattern = np.full(shape, -7.25, dtype)
+        d_out = dev(pattern)
+        with pytest.raises(ValueError):
+            codec.decode_device(*streams, d_out, strides=strides, reduce=reduce)
+        ctx.synchronize()
+        assert np.array_equal(d_out.download(), pattern)
+        assert codec.last_tiles_decoded == 77
+    # ... and the good call still writes all of it
+    d_out = dev(np.full(shape, -7.25))
+    codec.decode_device(*streams, d_out, reduce=reduce)
+    ctx.synchronize()
+    assert np.array_equal(d_out.download(), good) and codec.last_tiles_decoded == codec.T
+
+
+def test_encode_device_refuses_no_pictures_and_foreign_arrays():
+    """N = 0; a float32 picture for a float64 codec; a float64 picture with strides: ValueError"""
+    from spiht_amd import _lib
+    from spiht_amd.batch import DeviceArray
+    ctx = _lib.default_context()
+    plain, rd, res, lay = pinned(0)
+    T = plain.T
+    P = synth_image(4261, 1, 70, 90)
+    d_packed = DeviceArray(ctx, (T * rd.codec.slot_stride,), np.uint8)
+    d_lens, d_maxn = DeviceArray(ctx, (2 * T,), np.uint32), DeviceArray(ctx, (T,), np.uint8)
+    d_pic = DeviceArray(ctx, (1,), np.uint64)
+    d_img = dev(P[None])
+    with pytest.raises(ValueError):
+        plain.encode_device(d_img, 0, d_packed, d_lens, d_maxn)
+    with pytest.raises(ValueError):
+        rd.encode_device(d_img, 0, d_packed, d_lens, d_maxn)
+    with pytest.raises(ValueError):
+        rd.encode_layered_device(d_img, 0, 2, d_packed, d_lens, d_maxn, d_pic)
+    for codec in (plain, rd):
+        with pytest.raises(ValueError):
+            codec.encode_device(dev(P[None].astype(np.float32)), 1, d_packed, d_lens, d_maxn)
+        with pytest.raises(ValueError):
+            codec.encode_device(d_img, 1, d_packed, d_lens, d_maxn, strides=(8 * 70 * 90, 8 * 70 * 90, 8 * 90, 8))
+    ctx.synchronize()
+    # the good call, after them
+    plain.encode_device(d_img, 1, d_packed, d_lens, d_maxn)
+    ctx.synchronize()
+    assert d_lens.download()[:T].tolist() == plain.encode(P).nbytes
+
+
+# what a reduce that is no int >= 0 meets, call by call: recorded from the code as it stood before the paths were folded
+REDUCE_PINS = {  # (overlap, the argument's name) -> the exception, words of its message; None: it decodes as reduce=1
+    (0, "True"): (TypeError, "integer"),
+    (0, "1.0"): (TypeError, "integer"),
+    (0, "int64(1)"): None,
+    (0, "-1"): (ValueError, "reduce = -1"),
+    (4, "True"): (TypeError, "integer"),
+    (4, "1.0"): (TypeError, "integer"),
+    (4, "int64(1)"): (ValueError, "overlap"),
+    (4, "-1"): (ValueError, "reduce = -1"),
+}
+REDUCE_ARGS = {"True": True, "1.0": 1.0, "int64(1)": np.int64(1), "-1": -1}
+
+
+@pytest.mark.parametrize("overlap,arg", list(REDUCE_PINS))
+def test_reduce_that_is_no_plain_level(overlap, arg):
+    plain, rd, res, lay = pinned(overlap)
+    reduce, pin = REDUCE_ARGS[arg], REDUCE_PINS[overlap, arg]
+    calls = [lambda r: plain.decode(res, reduce=r), lambda r: rd.decode_layered(lay, reduce=r)]
+    if pin is None:
+        assert plain.reduced_shape(reduce) == plain.reduced_shape(1) and rd.reduced_shape(reduce) == rd.reduced_shape(1)
+        for call in calls:
+            got, want = call(reduce), call(1)
+            assert got.shape == (1, 35, 45) and got.dtype == want.dtype and got.tobytes() == want.tobytes()
+        return
+    for call in calls + [plain.reduced_shape, rd.reduced_shape]:
+        with pytest.raises(pin[0], match=pin[1]):
+            call(reduce)

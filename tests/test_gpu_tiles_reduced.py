@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import synth_image
+from tile_helpers import dev, settings, tile_of
 from test_reduced_cpu import oracle_reduced
 
 pytestmark = pytest.mark.gpu
@@ -35,25 +36,6 @@ def same_bits(a, b):
     if a.dtype == np.float64:
         return np.array_equal(a.view(np.uint64), b.view(np.uint64))
     return np.array_equal(a, b)
-
-
-def settings(cfg):
-    import spiht_amd
-    return spiht_amd.SpihtSettings(wavelet=cfg.get("wavelet", "bior2.2"), mode=cfg.get("mode", "reflect"),
-                                   color_model=cfg.get("color"))
-
-
-def tile_of(tile):
-    return tuple(tile) if isinstance(tile, tuple) else (tile, tile)
-
-
-def dev(arr):
-    from spiht_amd import _lib
-    from spiht_amd.batch import DeviceArray
-    arr = np.ascontiguousarray(arr)
-    d = DeviceArray(_lib.default_context(), arr.shape, arr.dtype)
-    d.upload(arr)
-    return d
 
 
 @functools.lru_cache(maxsize=None)
