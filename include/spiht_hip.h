@@ -48,8 +48,8 @@ typedef struct spiht_ctx spiht_ctx;
 const char *spiht_strerror(int status);
 const char *spiht_last_hip_error(void);
 /* ABI version of this header; bumped on any signature change and on every round that adds entry points (now 2).  The
- * 8-bit and 16-bit pixel entry points (*_u8, *_u16) are additions only -- no existing signature changed -- and the version
- * stays at 2. */
+ * 8-bit and 16-bit pixel entry points (*_u8, *_u16) and the float pixel ones (*_flt) are additions only -- no existing
+ * signature changed -- and the version stays at 2. */
 int spiht_abi_version(void);
 
 /* One context per (process, GPU): device id, streams, scratch.  Thread-safe per context
@@ -64,8 +64,8 @@ void spiht_ctx_destroy(spiht_ctx *ctx);
  * The rule for that latched error: it is reported exactly once, by the first call on the context that waits for its
  * stream.  Those calls are spiht_ctx_synchronize() and the calls that take or return host arrays: spiht_encode_i32,
  * spiht_decode_i32, spiht_decode_with_metadata_i32, spiht_decode_budgets_i32, spiht_decode_budgets_dev_i32 (it waits while
- * it uploads the stream), spiht_encode_image_host_f64 / _f32 / _u8 / _u16, spiht_decode_image_host_f64 / _u8 / _u16,
- * spiht_decode_image_reduced_host_f64 / _u8 / _u16.  (spiht_pipeline_synchronize reports for the pipeline's contexts.)
+ * it uploads the stream), spiht_encode_image_host_f64 / _f32 / _u8 / _u16, spiht_decode_image_host_f64 / _u8 / _u16 / _flt,
+ * spiht_decode_image_reduced_host_f64 / _u8 / _u16 / _flt.  (spiht_pipeline_synchronize reports for the pipeline's contexts.)
  * Such a call looks at the error before it starts its own work: it returns the earlier call's status without running, and
  * the same call made again works normally.  Outputs of the images that tripped no guard are valid either way. */
 int spiht_ctx_synchronize(spiht_ctx *ctx);
@@ -889,6 +889,65 @@ int spiht_dev_upload(spiht_ctx *ctx, void *d_dst, const void *h_src, uint64_t by
 int spiht_dev_download(spiht_ctx *ctx, void *h_dst, const void *d_src, uint64_t bytes);
 int spiht_dev_memset(spiht_ctx *ctx, void *d_dst, int value, uint64_t bytes);
 int spiht_dev_copy(spiht_ctx *ctx, void *d_dst, const void *d_src, uint64_t bytes); /* device to device, asynchronous */
+
+/* ---------------------------------------------------------------------------------------
+ * Float pixels out (*_flt): a decode into float32, float16 or bfloat16 pictures.
+ *
+ *   kind   1 float32, 2 float16, 3 bfloat16 (anything else: SPIHT_ERR_ARG)
+ *
+ * Each call is its *_u16 sibling with a leading `kind` behind the context (in front of everything, where there is none) and
+ * a void picture pointer: the same view by BYTE strides (non-negative multiples of the element size, 4 or 2; the base
+ * aligned to the element; a view that is written does not overlap itself; NULL: dense CHW), the same crop to the picture's
+ * own [c, H, W] (the reduced forms: to [c, hs[reduce], ws[reduce]]), the same statuses, asynchrony and chunking; refusals
+ * happen before any launch.  What is stored differs: sample v of the float64 picture the *_f64 sibling makes, rounded ONCE
+ * to the kind, to nearest, ties to even -- no clip, no scale; overflow gives +-inf, subnormals of the kind are kept, the sign
+ * of zero is kept, NaN gives a NaN.  (Once: float64 -> float32 -> float16 rounds twice and differs on a few dozen samples of
+ * a small bior2.2 picture, whose decoded samples lie a hair off the ties of the narrow kinds.)  The rule in integer
+ * arithmetic: spiht_amd/floatpx.py on the host, csrc/floatpx.h on the device.  A stream does not record the pixel format it
+ * was coded from: streams of float64, float32, 8-bit and 16-bit pictures all decode into the float kinds.
+ * Level 1 of the tiled inverse transform stores the kind itself (one pixel kind of the kernels, PX_FLT, for the three); the
+ * routes without a fused form -- periodization, filters longer than SPIHT_MAX_TAPS -- convert in a pass of their own over
+ * the float64 result, which is what spiht_convert_batch_flt runs alone:
+ *   spiht_convert_batch_flt  d_in: dense float64 [B, c, rec_h, rec_w] on the device -> the view [B, c, H, W] of the kind at
+ *                            d_out (H <= rec_h, W <= rec_w: the crop).  Asynchronous.
+ * Tiles: a tile batch of a 16-bit kind is pasted and assembled by the *_u16 copies, one of float32 by spiht_tile_paste_f32
+ * and spiht_tile_mosaic_f32 (dense), or by the strided copies below; overlapping tiles are decoded as float64, blended in
+ * float64 and rounded at the store (spiht_tile_blend_flt: spiht_tile_blend_u16's arguments). */
+int spiht_check_view_flt(int kind, int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output);
+int spiht_convert_batch_flt(spiht_ctx *ctx, int kind, const double *d_in, int64_t B, int64_t c, int64_t rec_h, int64_t rec_w,
+                            int64_t H, int64_t W, void *d_out, const int64_t *out_strides);
+int spiht_decode_image_batch_flt(spiht_ctx *ctx, int kind, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
+                                 const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
+                                 int level, double q_scale, const double *channel_mults, void *d_img_out,
+                                 const int64_t *out_strides, int32_t *d_rec);
+int spiht_decode_image_host_flt(spiht_ctx *ctx, int kind, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c, int64_t H,
+                                int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                void *img_out, const int64_t *strides);
+int spiht_dequant_idwt_flags_batch_flt(spiht_ctx *ctx, int kind, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
+                                       int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                       const double *channel_mults, void *d_img_out, const int64_t *out_strides);
+int spiht_dequant_idwt_reduced_batch_flt(spiht_ctx *ctx, int kind, const int32_t *d_rec, int64_t B, int64_t c, int64_t H,
+                                         int64_t W, int wavelet, int mode, int level, double q_scale,
+                                         const double *channel_mults, void *d_img_out, const int64_t *out_strides, int reduce);
+int spiht_decode_image_reduced_batch_flt(spiht_ctx *ctx, int kind, const uint8_t *d_data, uint64_t slot_stride,
+                                         const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H,
+                                         int64_t W, int wavelet, int mode, int level, double q_scale,
+                                         const double *channel_mults, void *d_img_out, const int64_t *out_strides,
+                                         int32_t *d_rec, int reduce);
+int spiht_decode_image_reduced_host_flt(spiht_ctx *ctx, int kind, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                        int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                        const double *channel_mults, void *img_out, const int64_t *strides, int reduce);
+/* float32 tile batches by strides (spiht_tile_paste_u16 / spiht_tile_mosaic_u16 with 4-byte elements: out_strides[3] in bytes,
+ * multiples of 4; NULL: dense CHW) */
+int spiht_tile_paste_f32s(spiht_ctx *ctx, const float *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                          int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
+                          int64_t wh, int64_t ww, float *d_out, const int64_t *out_strides);
+int spiht_tile_mosaic_f32(spiht_ctx *ctx, const float *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy, int64_t ox,
+                          int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1,
+                          int64_t y0, int64_t x0, int64_t wh, int64_t ww, float *d_out, const int64_t *out_strides);
+int spiht_tile_blend_flt(spiht_ctx *ctx, int kind, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                         int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
+                         int64_t x0, int64_t wh, int64_t ww, void *d_out, const int64_t *out_strides);
 
 #ifdef __cplusplus
 }

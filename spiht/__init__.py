@@ -10,7 +10,7 @@ import sys
 
 import spiht_amd as _impl
 
-_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode", "rd", "tiles", "overlap")
+_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode", "rd", "tiles", "overlap", "floatpx")
 for _name in _SUBMODULES:
     # `spiht.spiht` is the reference's compiled extension (src/lib.rs:58-65); here spiht_amd/spiht.py over the C ABI
     _mod = importlib.import_module("spiht_amd." + _name)
@@ -45,4 +45,8 @@ globals().update({_k: getattr(_impl, _k) for _k in ("roi_map",)})
 globals().update({_k: getattr(_impl, _k) for _k in ("target_sqerr",)})
 # ... overlapping tiles: the tiles a window needs when the decoded tiles are cross-faded at the seams (the encode calls' overlap=)
 globals().update({_k: getattr(_impl, _k) for _k in ("window_tiles_overlap",)})
+# ... float pixels out: decodes into float32, float16 and bfloat16 pictures
+globals().update({_k: getattr(_impl, _k) for _k in ("decode_image_float", "decode_image_reduced_float", "decode_image_tiled_float",
+                                                    "decode_image_window_float", "decode_image_layered_float",
+                                                    "decode_image_layered_window_float")})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

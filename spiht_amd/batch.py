@@ -10,7 +10,7 @@ import math
 
 import numpy as np
 
-from . import _lib, color_models
+from . import _lib, color_models, floatpx
 from . import spiht as spiht_rs
 from .spiht_wrapper import (EncodingResult, SpihtSettings, _geometry, _metadata_boxes, _mults_arg, _wavelet_mode_ids,
                             check_u8_view, _check_int_view, _check_aligned, _is_dtype, reduced_shape)
@@ -226,6 +226,68 @@ class BatchCodec:
     def decode_u16(self, results, channels_last=False):
         """list of EncodingResult (same geometry) -> uint16 [B, c, H, W] (or [B, H, W, c]), cropped to H x W"""
         return self._decode_int(np.uint16, results, channels_last)
+
+    # ---- float pixels out (include/spiht_hip.h, *_flt; spiht_amd/floatpx.py): float32, float16 or bfloat16 pictures, each
+    # sample of the float64 decode rounded once to the kind.  dtype: what floatpx.kind_arg takes. -----------------------------
+    def _float_strides(self, kind, shape, strides):
+        """byte strides of a [B, c, h, w] view of the kind that is written, as a ctypes argument (None: dense CHW)"""
+        if strides is None:
+            return None, None
+        st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
+        floatpx.check_float_view(kind, shape, st, True)
+        return st, C.c_void_p(st.ctypes.data)
+
+    def decode_device_float(self, d_data, d_nbytes, d_max_n, B, d_img_out, dtype, strides=None, d_rec=None, slot_stride=None):
+        """-> pictures of the kind `dtype` [B, c, H, W] on the device, cropped to H x W: floatpx.convert of what decode_device
+        makes, laid out by `strides` (BYTES, multiples of the element size, as the base; None: dense CHW; what lies between the
+        view's elements -- a fourth channel, row padding -- is not written)"""
+        kind = floatpx.kind_id(dtype)
+        st, st_p = self._float_strides(kind, (int(B), self.c, self.H, self.W), strides)
+        _check_aligned(d_img_out, floatpx.storage_dtype(kind))
+        with self._color():
+            _lib.check(self.L.spiht_decode_image_batch_flt(
+                self.ctx.handle, kind, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
+                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
+                self.c, self.H, self.W, self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
+                C.c_void_p(d_img_out), st_p, C.c_void_p(d_rec) if d_rec else None))
+
+    def decode_float(self, results, dtype=np.float32, channels_last=False):
+        """list of EncodingResult (same geometry) -> [B, c, H, W] (or [B, H, W, c]) of the kind `dtype`, cropped to H x W:
+        spiht_wrapper.decode_image_float of each (float32, float16, or uint16 bit patterns for bfloat16)"""
+        kind = floatpx.kind_arg(dtype)
+        c, H, W, es = self.c, self.H, self.W, floatpx.itemsize(kind)
+        strides = (H * W * c * es, es, W * c * es, c * es) if channels_last else None
+        return self._decode_host(results, (H, W, c) if channels_last else (c, H, W), floatpx.storage_dtype(kind),
+                                 lambda *a, slot_stride: self.decode_device_float(*a, kind, strides, None, slot_stride))
+
+    def decode_reduced_device_float(self, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, dtype, strides=None, d_rec=None,
+                                    slot_stride=None):
+        """-> pictures of the kind `dtype` [B, c, pic_h, pic_w] on the device (reduced_shape), laid out by `strides` (BYTES,
+        multiples of the element size; None: dense CHW): floatpx.convert of decode_reduced_device's, cropped to the band"""
+        kind = floatpx.kind_id(dtype)
+        rs = self.reduced_shape(reduce)
+        st, st_p = self._float_strides(kind, (int(B), self.c, rs["pic_h"], rs["pic_w"]), strides)
+        _check_aligned(d_img_out, floatpx.storage_dtype(kind))
+        with self._color():
+            _lib.check(self.L.spiht_decode_image_reduced_batch_flt(
+                self.ctx.handle, kind, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
+                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
+                self.c, self.H, self.W, self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
+                C.c_void_p(d_img_out), st_p, C.c_void_p(d_rec) if d_rec else None, int(reduce)))
+
+    def decode_reduced_float(self, results, reduce, dtype=np.float32, crop=False, channels_last=False):
+        """list of EncodingResult -> [B, c, pic_h, pic_w] (or [B, pic_h, pic_w, c]) of the kind `dtype`:
+        decode_image_reduced_float of each"""
+        kind = floatpx.kind_arg(dtype)
+        rs = self.reduced_shape(reduce)
+        c, h, w, es = self.c, rs["pic_h"], rs["pic_w"], floatpx.itemsize(kind)
+        strides = (h * w * c * es, es, w * c * es, c * es) if channels_last else None
+        out = self._decode_host(results, (h, w, c) if channels_last else (c, h, w), floatpx.storage_dtype(kind),
+                                lambda *a, slot_stride: self.decode_reduced_device_float(*a, reduce, kind, strides, None, slot_stride))
+        if not crop:
+            return out
+        ys, xs = slice(rs["off_y"], rs["off_y"] + rs["in_h"]), slice(rs["off_x"], rs["off_x"] + rs["in_w"])
+        return out[:, ys, xs, :] if channels_last else out[:, :, ys, xs]
 
     # ---- reduced-resolution decode (include/spiht_hip.h, *_reduced_*): pictures at 1/2^reduce size, 0 <= reduce <= L.
     # What spiht_wrapper.decode_image_reduced* return, for B streams in one queue of kernels. ------------------------------

@@ -16,6 +16,7 @@
 
 #include "alloc.h"
 #include "common.h"
+#include "floatpx.h"
 #include "rd.h"
 #include "tiles.h"
 #include "wavelets.h"
@@ -65,6 +66,7 @@ int spiht_launch_tile_paste(const TilePasteArgs *a, int es, int64_t ntiles, hipS
 int spiht_launch_tile_mosaic(const TileMosaicArgs *a, int es, hipStream_t st);
 int spiht_launch_tile_cut_overlap(const TileCutOverlapArgs *a, int es, int64_t NT, hipStream_t st);
 int spiht_launch_tile_blend(const TileBlendArgs *a, int es, hipStream_t st);
+int spiht_launch_tile_blend_flt(const TileBlendArgs *a, int kind, hipStream_t st);
 int spiht_launch_tile_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbytes, int64_t T, uint64_t *d_off,
                            uint8_t *d_packed, uint64_t cap, uint32_t *d_lens, hipStream_t st);
 int spiht_launch_tile_unpack(const uint8_t *d_packed, uint64_t packed_bytes, const uint32_t *d_lens, int64_t T, uint64_t *d_off,
@@ -1313,13 +1315,21 @@ static int upload_filters(spiht_ctx *ctx, int wavelet, const double **d_filt) {
 // Float pixels: a dense array at p, [B, c, H, W] (the inverse transform's output: [B, c, rec_H, rec_W]).  8- and 16-bit
 // pixels: the view px (common.h: PxView) of a [B, c, H, W] uint8 / uint16 picture batch by byte strides, based at p.  The
 // extern "C" entry points make one; everything behind them passes it on.
-enum PicFmt { PIC_F64, PIC_F32, PIC_U8, PIC_U16 };
+// PIC_FLT: float pixels OUT (floatpx.h), a view like the integer ones whose kind is px.kind.
+enum PicFmt { PIC_F64, PIC_F32, PIC_U8, PIC_U16, PIC_FLT };
+// the element of a view: its bytes and, for float pixels out, the kind (0: integer pixels)
+struct PxElem {
+    int es, kind;
+    PxElem(int es_) : es(es_), kind(0) {}
+    PxElem(int es_, int kind_) : es(es_), kind(kind_) {}
+};
+static PxElem flt_elem(int kind) { return PxElem(flt_itemsize(kind), kind); }  // (es 0: not a kind -- int_pic refuses it)
 struct Pic {
     PicFmt fmt = PIC_F64;
     char *p = nullptr;  // the first picture
     bool out = false;   // the call writes the pixels (else it reads them)
     PxView px = {};     // integer pixels: strides, size and element size (px.in / px.out unset: see view())
-    bool integer() const { return fmt == PIC_U8 || fmt == PIC_U16; }
+    bool integer() const { return fmt == PIC_U8 || fmt == PIC_U16 || fmt == PIC_FLT; }  // a view by strides
     // the view as the integer kernels and the conversion passes take it
     PxView view() const {
         PxView v = px;
@@ -1356,7 +1366,10 @@ static Pic dense_pic(const void *p, PicFmt fmt, bool out = false) {
 // es: bytes per sample, 1 or 2.  strides (in bytes): n == 4: (sb, sc, sh, sw); n == 3: (sc, sh, sw) of one picture;
 // nullptr: dense CHW.  Strides are non-negative and, as the base, multiples of es; a view that is written must not overlap
 // itself: sorted by stride, every dimension longer than 1 must step past the last byte all the smaller ones reach.
-static int int_pic(const void *p, int es, bool out, const int64_t *strides, int n, int64_t B, int64_t c, int64_t h, int64_t w, Pic *v) {
+// A float kind (el.kind): es 4 or 2 by the same rules; such a view is only ever written.
+static int int_pic(const void *p, PxElem el, bool out, const int64_t *strides, int n, int64_t B, int64_t c, int64_t h, int64_t w, Pic *v) {
+    const int es = el.es;
+    if (es < 1 || (el.kind && !out)) return SPIHT_ERR_ARG;
     int64_t st[4] = {c * h * w * es, h * w * es, w * es, es};
     if (strides)
         for (int i = 0; i < n; i++) st[4 - n + i] = strides[i];
@@ -1380,8 +1393,9 @@ static int int_pic(const void *p, int es, bool out, const int64_t *strides, int 
             reach += (ext[i] - 1) * st[i];
         }
     }
-    *v = dense_pic(p, es == 2 ? PIC_U16 : PIC_U8, out);
+    *v = dense_pic(p, el.kind ? PIC_FLT : es == 2 ? PIC_U16 : PIC_U8, out);
     v->px.es = es;
+    v->px.kind = el.kind;
     v->px.sb = st[0]; v->px.sc = st[1]; v->px.sh = st[2]; v->px.sw = st[3];
     v->px.c = (int32_t)c; v->px.h = (int32_t)h; v->px.w = (int32_t)w;
     return SPIHT_OK;
@@ -1761,13 +1775,13 @@ extern "C" int spiht_dequant_idwt_flags_batch_f64(spiht_ctx *ctx, const int32_t 
     return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                               dense_pic(d_img_out, PIC_F64, true));
 }
-static int dequant_idwt_flags_batch_px(int es, spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
+static int dequant_idwt_flags_batch_px(PxElem el, spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
                                        int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                                        double q_scale, const double *channel_mults, void *d_img_out,
                                        const int64_t *out_strides) {
     if (!d_img_out) return SPIHT_ERR_ARG;
     Pic out;
-    CHK(int_pic(d_img_out, es, true, out_strides, 4, B, c, H, W, &out));
+    CHK(int_pic(d_img_out, el, true, out_strides, 4, B, c, H, W, &out));
     return dequant_idwt_batch(ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out);
 }
 extern "C" int spiht_dequant_idwt_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B,
@@ -1997,7 +2011,7 @@ extern "C" int spiht_decode_image_batch_f64(spiht_ctx *ctx, const uint8_t *d_dat
     return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                               dense_pic(d_img_out, PIC_F64, true), d_rec);
 }
-static int decode_image_batch_px(int es, spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+static int decode_image_batch_px(PxElem el, spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
                                  const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
                                  int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                  const double *channel_mults, void *d_img_out, const int64_t *out_strides,
@@ -2005,7 +2019,7 @@ static int decode_image_batch_px(int es, spiht_ctx *ctx, const uint8_t *d_data, 
     if (!d_img_out) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
     Pic out;
-    CHK(int_pic(d_img_out, es, true, out_strides, 4, B, c, H, W, &out));
+    CHK(int_pic(d_img_out, el, true, out_strides, 4, B, c, H, W, &out));
     return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                               out, d_rec);
 }
@@ -2131,13 +2145,14 @@ extern "C" int spiht_decode_image_host_f64(spiht_ctx *ctx, const uint8_t *data, 
     return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                              dense_pic(img_out, PIC_F64, true));
 }
-static int decode_image_host_px(int es, spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+static int decode_image_host_px(PxElem el, spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
                                 int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                 const double *channel_mults, void *img_out, const int64_t *strides) {
+    const int es = el.es;
     if (!img_out) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, 1, c, H, W));
     Pic out;
-    CHK(int_pic(img_out, es, true, strides, 3, 1, c, H, W, &out));
+    CHK(int_pic(img_out, el, true, strides, 3, 1, c, H, W, &out));
     // the copy back is of c*H*W samples: only the two dense layouts, CHW and HWC
     const PxView &px = out.px;
     const bool chw = px.sw == es && px.sh == W * es && px.sc == H * W * es, hwc = px.sc == es && px.sw == c * es && px.sh == W * c * es;
@@ -2211,7 +2226,7 @@ extern "C" int spiht_reduced_shape(int64_t H, int64_t W, int wavelet, int mode, 
     return SPIHT_OK;
 }
 // the integer view of a reduced call: B pictures [c, hs[reduce], ws[reduce]] by n strides
-static int reduced_int_pic(void *p, int es, const int64_t *strides, int n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
+static int reduced_int_pic(void *p, PxElem es, const int64_t *strides, int n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
                            int mode, int level, int reduce, Pic *out) {
     if (!p) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
@@ -2226,11 +2241,11 @@ extern "C" int spiht_dequant_idwt_reduced_batch_f64(spiht_ctx *ctx, const int32_
     return dequant_idwt_batch(ctx, d_rec, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                               dense_pic(d_img_out, PIC_F64, true), reduce);
 }
-static int dequant_idwt_reduced_batch_px(int es, spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H, int64_t W,
+static int dequant_idwt_reduced_batch_px(PxElem el, spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H, int64_t W,
                                          int wavelet, int mode, int level, double q_scale, const double *channel_mults,
                                          void *d_img_out, const int64_t *out_strides, int reduce) {
     Pic out;
-    CHK(reduced_int_pic(d_img_out, es, out_strides, 4, B, c, H, W, wavelet, mode, level, reduce, &out));
+    CHK(reduced_int_pic(d_img_out, el, out_strides, 4, B, c, H, W, wavelet, mode, level, reduce, &out));
     return dequant_idwt_batch(ctx, d_rec, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out, reduce);
 }
 extern "C" int spiht_dequant_idwt_reduced_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H,
@@ -2256,13 +2271,13 @@ extern "C" int spiht_decode_image_reduced_batch_f64(spiht_ctx *ctx, const uint8_
     return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                               dense_pic(d_img_out, PIC_F64, true), d_rec, reduce);
 }
-static int decode_image_reduced_batch_px(int es, spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+static int decode_image_reduced_batch_px(PxElem el, spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
                                          const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H,
                                          int64_t W, int wavelet, int mode, int level, double q_scale,
                                          const double *channel_mults, void *d_img_out, const int64_t *out_strides,
                                          int32_t *d_rec, int reduce) {
     Pic out;
-    CHK(reduced_int_pic(d_img_out, es, out_strides, 4, B, c, H, W, wavelet, mode, level, reduce, &out));
+    CHK(reduced_int_pic(d_img_out, el, out_strides, 4, B, c, H, W, wavelet, mode, level, reduce, &out));
     return decode_image_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                               out, d_rec, reduce);
 }
@@ -2289,11 +2304,12 @@ extern "C" int spiht_decode_image_reduced_host_f64(spiht_ctx *ctx, const uint8_t
     return decode_image_host(ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                              dense_pic(img_out, PIC_F64, true), reduce);
 }
-static int decode_image_reduced_host_px(int es, spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+static int decode_image_reduced_host_px(PxElem el, spiht_ctx *ctx, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
                                         int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                         const double *channel_mults, void *img_out, const int64_t *strides, int reduce) {
+    const int es = el.es;
     Pic out;
-    CHK(reduced_int_pic(img_out, es, strides, 3, 1, c, H, W, wavelet, mode, level, reduce, &out));
+    CHK(reduced_int_pic(img_out, el, strides, 3, 1, c, H, W, wavelet, mode, level, reduce, &out));
     // the copy back is of c * pic_h * pic_w samples: only the two dense layouts, CHW and HWC
     const PxView &px = out.px;
     const int64_t h = px.h, w = px.w;
@@ -2314,6 +2330,77 @@ extern "C" int spiht_decode_image_reduced_host_u16(spiht_ctx *ctx, const uint8_t
                                                    int reduce) {
     return decode_image_reduced_host_px(2, ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults, img_out,
                                         strides, reduce);
+}
+
+// ------------------------------------------------------------------------------------------------
+// float pixels out (include/spiht_hip.h, *_flt): the *_u16 decode calls with the element of a float kind.  The view's rules
+// are int_pic's with 4 or 2 bytes per sample; level 1 of the tiled inverse stores the kind (dwt.hip, PX_FLT), the routes
+// without a fused form convert in a pass of their own (dwt_inverse: conv8), which spiht_convert_batch_flt runs alone.
+// ------------------------------------------------------------------------------------------------
+extern "C" int spiht_check_view_flt(int kind, int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output) {
+    if (B < 1 || c < 1 || H < 1 || W < 1 || !strides) return SPIHT_ERR_ARG;
+    Pic v;
+    // (a view that is read obeys the same rules without the overlap check; int_pic itself only makes views that are written)
+    const PxElem el = flt_elem(kind);
+    if (el.es == 0) return SPIHT_ERR_ARG;
+    if (output) return int_pic(nullptr, el, true, strides, 4, B, c, H, W, &v);
+    return int_pic(nullptr, PxElem(el.es), false, strides, 4, B, c, H, W, &v);
+}
+extern "C" int spiht_convert_batch_flt(spiht_ctx *ctx, int kind, const double *d_in, int64_t B, int64_t c, int64_t rec_h,
+                                       int64_t rec_w, int64_t H, int64_t W, void *d_out, const int64_t *out_strides) {
+    if (!ctx || !d_in || !d_out || B < 0 || c < 1 || H < 1 || W < 1 || rec_h < H || rec_w < W) return SPIHT_ERR_ARG;
+    if (rec_h > (1 << 24) || rec_w > (1 << 24) || (__int128)B * c >= ((__int128)1 << 31)) return SPIHT_ERR_TOO_LARGE;
+    Pic out;
+    CHK(int_pic(d_out, flt_elem(kind), true, out_strides, 4, std::max<int64_t>(B, 1), c, H, W, &out));
+    if (B == 0) return SPIHT_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    const PxView px = out.view();
+    LAUNCHCHK(spiht_launch_f64_to_px(d_in, (int)rec_h, (int)rec_w, &px, B, ctx->stream));
+    return SPIHT_OK;
+}
+extern "C" int spiht_decode_image_batch_flt(spiht_ctx *ctx, int kind, const uint8_t *d_data, uint64_t slot_stride,
+                                            const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H,
+                                            int64_t W, int wavelet, int mode, int level, double q_scale,
+                                            const double *channel_mults, void *d_img_out, const int64_t *out_strides,
+                                            int32_t *d_rec) {
+    return decode_image_batch_px(flt_elem(kind), ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level,
+                                 q_scale, channel_mults, d_img_out, out_strides, d_rec);
+}
+extern "C" int spiht_decode_image_host_flt(spiht_ctx *ctx, int kind, const uint8_t *data, uint64_t nbytes, uint8_t n, int64_t c,
+                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                           const double *channel_mults, void *img_out, const int64_t *strides) {
+    return decode_image_host_px(flt_elem(kind), ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                                img_out, strides);
+}
+extern "C" int spiht_dequant_idwt_flags_batch_flt(spiht_ctx *ctx, int kind, const int32_t *d_rec, const uint32_t *d_flags,
+                                                  int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                                                  double q_scale, const double *channel_mults, void *d_img_out,
+                                                  const int64_t *out_strides) {
+    return dequant_idwt_flags_batch_px(flt_elem(kind), ctx, d_rec, d_flags, B, c, H, W, wavelet, mode, level, q_scale,
+                                       channel_mults, d_img_out, out_strides);
+}
+extern "C" int spiht_dequant_idwt_reduced_batch_flt(spiht_ctx *ctx, int kind, const int32_t *d_rec, int64_t B, int64_t c,
+                                                    int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                    const double *channel_mults, void *d_img_out,
+                                                    const int64_t *out_strides, int reduce) {
+    return dequant_idwt_reduced_batch_px(flt_elem(kind), ctx, d_rec, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                                         d_img_out, out_strides, reduce);
+}
+extern "C" int spiht_decode_image_reduced_batch_flt(spiht_ctx *ctx, int kind, const uint8_t *d_data, uint64_t slot_stride,
+                                                    const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                                    int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                                    const double *channel_mults, void *d_img_out,
+                                                    const int64_t *out_strides, int32_t *d_rec, int reduce) {
+    return decode_image_reduced_batch_px(flt_elem(kind), ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode,
+                                         level, q_scale, channel_mults, d_img_out, out_strides, d_rec, reduce);
+}
+extern "C" int spiht_decode_image_reduced_host_flt(spiht_ctx *ctx, int kind, const uint8_t *data, uint64_t nbytes, uint8_t n,
+                                                   int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                                                   double q_scale, const double *channel_mults, void *img_out,
+                                                   const int64_t *strides, int reduce) {
+    return decode_image_reduced_host_px(flt_elem(kind), ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale,
+                                        channel_mults, img_out, strides, reduce);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2484,12 +2571,13 @@ static int tile_paste(spiht_ctx *ctx, const void *d_tiles, const Pic &out, int e
     LAUNCHCHK(spiht_launch_tile_paste(&a, es, (i1 - i0) * (j1 - j0), ctx->stream));
     return SPIHT_OK;
 }
-static int tile_paste_px(int es, spiht_ctx *ctx, const void *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+static int tile_paste_px(PxElem el, spiht_ctx *ctx, const void *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
                          int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0, int64_t wh,
                          int64_t ww, void *d_out, const int64_t *out_strides) {
+    const int es = el.es;
     if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
     Pic pic;
-    CHK(int_pic(d_out, es, true, out_strides, 3, 1, c, wh, ww, &pic));
+    CHK(int_pic(d_out, el, true, out_strides, 3, 1, c, wh, ww, &pic));
     return tile_paste(ctx, d_tiles, pic, es, c, rh, rw, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww);
 }
 extern "C" int spiht_tile_paste_u8(spiht_ctx *ctx, const uint8_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
@@ -2565,12 +2653,13 @@ static int tile_mosaic(spiht_ctx *ctx, const void *d_tiles, const Pic &out, int 
     LAUNCHCHK(spiht_launch_tile_mosaic(&a, es, ctx->stream));
     return SPIHT_OK;
 }
-static int tile_mosaic_px(int es, spiht_ctx *ctx, const void *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy, int64_t ox,
+static int tile_mosaic_px(PxElem el, spiht_ctx *ctx, const void *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy, int64_t ox,
                           int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
                           int64_t x0, int64_t wh, int64_t ww, void *d_out, const int64_t *out_strides) {
+    const int es = el.es;
     if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
     Pic pic;
-    CHK(int_pic(d_out, es, true, out_strides, 3, 1, c, wh, ww, &pic));
+    CHK(int_pic(d_out, el, true, out_strides, 3, 1, c, wh, ww, &pic));
     return tile_mosaic(ctx, d_tiles, pic, es, c, rh, rw, oy, ox, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww);
 }
 extern "C" int spiht_tile_mosaic_u8(spiht_ctx *ctx, const uint8_t *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy,
@@ -2636,15 +2725,17 @@ static int tile_blend(spiht_ctx *ctx, const double *d_tiles, const Pic &out, int
     a.y0 = (int32_t)y0; a.x0 = (int32_t)x0; a.wh = (int32_t)wh; a.ww = (int32_t)ww; a.rows = 0;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    LAUNCHCHK(spiht_launch_tile_blend(&a, es, ctx->stream));
+    if (out.fmt == PIC_FLT) LAUNCHCHK(spiht_launch_tile_blend_flt(&a, out.px.kind, ctx->stream));
+    else LAUNCHCHK(spiht_launch_tile_blend(&a, es, ctx->stream));
     return SPIHT_OK;
 }
-static int tile_blend_px(int es, spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+static int tile_blend_px(PxElem el, spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
                          int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
                          int64_t wh, int64_t ww, void *d_out, const int64_t *out_strides) {
+    const int es = el.es;
     if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
     Pic pic;
-    CHK(int_pic(d_out, es, true, out_strides, 3, 1, c, wh, ww, &pic));
+    CHK(int_pic(d_out, el, true, out_strides, 3, 1, c, wh, ww, &pic));
     return tile_blend(ctx, d_tiles, pic, es, c, rh, rw, H, W, th, tw, m, i0, i1, j0, j1, y0, x0, wh, ww);
 }
 extern "C" int spiht_tile_blend_u8(spiht_ctx *ctx, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
@@ -2663,6 +2754,27 @@ extern "C" int spiht_tile_blend_f64(spiht_ctx *ctx, const double *d_tiles, int64
     if (c < 1 || wh < 1 || ww < 1) return SPIHT_ERR_ARG;
     return tile_blend(ctx, d_tiles, dense_pic(d_out, PIC_F64, true), 8, c, rh, rw, H, W, th, tw, m, i0, i1, j0, j1, y0, x0, wh,
                       ww);
+}
+
+// float pixels out: the blend rounded to a float kind at the store; float32 tile batches pasted / assembled by strides (a copy
+// of 4-byte elements -- the 16-bit kinds go through the *_u16 copies)
+extern "C" int spiht_tile_blend_flt(spiht_ctx *ctx, int kind, const double *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H,
+                                    int64_t W, int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1,
+                                    int64_t y0, int64_t x0, int64_t wh, int64_t ww, void *d_out, const int64_t *out_strides) {
+    return tile_blend_px(flt_elem(kind), ctx, d_tiles, c, rh, rw, H, W, th, tw, m, i0, i1, j0, j1, y0, x0, wh, ww, d_out, out_strides);
+}
+extern "C" int spiht_tile_paste_f32s(spiht_ctx *ctx, const float *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t H, int64_t W,
+                                     int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0, int64_t x0,
+                                     int64_t wh, int64_t ww, float *d_out, const int64_t *out_strides) {
+    return tile_paste_px(flt_elem(SPIHT_FLT_F32), ctx, d_tiles, c, rh, rw, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww, d_out,
+                         out_strides);
+}
+extern "C" int spiht_tile_mosaic_f32(spiht_ctx *ctx, const float *d_tiles, int64_t c, int64_t rh, int64_t rw, int64_t oy,
+                                     int64_t ox, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t i0, int64_t i1, int64_t j0,
+                                     int64_t j1, int64_t y0, int64_t x0, int64_t wh, int64_t ww, float *d_out,
+                                     const int64_t *out_strides) {
+    return tile_mosaic_px(flt_elem(SPIHT_FLT_F32), ctx, d_tiles, c, rh, rw, oy, ox, H, W, th, tw, i0, i1, j0, j1, y0, x0, wh, ww,
+                          d_out, out_strides);
 }
 
 // the checks pack and unpack share; the scratch: uint64 [T] byte lengths (pack), uint64 [T] offsets

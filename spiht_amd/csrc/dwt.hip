@@ -22,6 +22,7 @@
 // so GPU and oracle agree bit for bit and both agree with pywt to a few ulp.
 // HBM-bound: per level, 8 B per input sample + 8 B (LL) + 3*4 B (details) per output position.
 #include "common.h"
+#include "floatpx.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -162,8 +163,18 @@ __device__ __forceinline__ uint16_t px16_store_value(double v) {
 }
 // The pixel kind of a level-1 kernel (template parameter PX): PX_F64 reads / writes the dense float64 planes a.in / a.out,
 // the integer kinds the strided view a.px (common.h: PxView; byte strides, so a sample's address is formed in bytes for
-// both) -- the value of an integer kind is its element size.
-enum PxKind : int { PX_F64 = 0, PX_U8 = 1, PX_U16 = 2 };
+// both) -- the value of an integer kind is its element size.  PX_FLT: the inverse kernels' float32 / float16 / bfloat16
+// store (floatpx.h) through the same view; which of the three is the view's `kind`, uniform over the launch, so the one
+// instantiation serves them all (every kind multiplies the level-1 inverse kernels by the wavelet instantiations).
+enum PxKind : int { PX_F64 = 0, PX_U8 = 1, PX_U16 = 2, PX_FLT = 3 };
+// the pixel kind of a launch into / out of the view px
+static inline int px_kind_of(const PxView &px) { return px.kind ? PX_FLT : px.es == 2 ? PX_U16 : PX_U8; }
+// a float sample at its byte address: 4 bytes of float32, else the 2 of float16 / bfloat16
+__device__ __forceinline__ void flt_store(uint8_t *p, double v, int kind) {
+    const uint32_t b = flt_store_value(v, kind);
+    if (kind == SPIHT_FLT_F32) *reinterpret_cast<uint32_t *>(p) = b;
+    else *reinterpret_cast<uint16_t *>(p) = (uint16_t)b;
+}
 template <int PX> __device__ __forceinline__ uint32_t px_load(const uint8_t *p) {  // the raw sample, not yet converted
     if constexpr (PX == PX_U16) return *reinterpret_cast<const uint16_t *>(p);
     else return *p;
@@ -174,9 +185,11 @@ template <int PX> __device__ __forceinline__ double px_value(uint32_t raw) {
 }
 // p[o] = the stored form of v.  The 8-bit statement is the one the kernels held before there was a second integer kind,
 // as a statement of its own: their instruction order stays what it was.
-#define PX_STORE(PX, p, o, v)                                                               \
+// (kind: the view's, read by PX_FLT alone)
+#define PX_STORE(PX, p, o, v, kind)                                                         \
     do {                                                                                    \
-        if constexpr ((PX) == PX_U16) *reinterpret_cast<uint16_t *>((p) + (o)) = px16_store_value(v); \
+        if constexpr ((PX) == PX_FLT) flt_store((p) + (o), v, kind);                        \
+        else if constexpr ((PX) == PX_U16) *reinterpret_cast<uint16_t *>((p) + (o)) = px16_store_value(v); \
         else (p)[o] = px8_store_value(v);                                                   \
     } while (0)
 
@@ -1248,7 +1261,7 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
                 }
                 const double sacc = (0.0 + sa) + sd;
                 if (PX) {
-                    if (m + mp < a.px.h && n < a.px.w) PX_STORE(PX, out8, (int64_t)(m + mp) * a.px.sh + (int64_t)n * a.px.sw, sacc);
+                    if (m + mp < a.px.h && n < a.px.w) PX_STORE(PX, out8, (int64_t)(m + mp) * a.px.sh + (int64_t)n * a.px.sw, sacc, a.px.kind);
                 } else {
                     if (m + mp < a.out_h && n < a.out_w) out[(size_t)(m + mp) * a.out_w + n] = sacc;
                 }
@@ -1392,7 +1405,7 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
         // for the next tile's samples at the top of the loop becomes a wait for these stores as well.
         const uint32_t row_bytes = (uint32_t)a.out_w * 8u;
         const __amdgpu_buffer_rsrc_t orsrc = PX ? plane_rsrc(a.px.out + (int64_t)(plane / (uint32_t)a.c) * a.px.sb + (int64_t)(plane % (uint32_t)a.c) * a.px.sc,
-                                                             (uint32_t)((int64_t)(a.px.h - 1) * a.px.sh + (int64_t)(a.px.w - 1) * a.px.sw + PX))
+                                                             (uint32_t)((int64_t)(a.px.h - 1) * a.px.sh + (int64_t)(a.px.w - 1) * a.px.sw + (PX == PX_FLT ? a.px.es : PX)))
                                                 : plane_rsrc(a.out + (size_t)plane * a.out_h * a.out_w, (uint32_t)a.out_h * row_bytes);
         const uint32_t voff0 = n < a.out_w ? (uint32_t)(2 * (kh0 + rbase)) * row_bytes + (uint32_t)n * 8u : BUF_OOB;
         // (integer pixels) the crop: columns x >= w by an offset beyond the descriptor, rows y >= h by a compare per store
@@ -1441,6 +1454,14 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
                         const int dy = 2 * (rr - (HF - 1)) + mp;
                         __builtin_amdgcn_raw_buffer_store_b16(px16_store_value(sacc), orsrc,
                                                               y0 + dy < a.px.h ? voff8 + (uint32_t)dy * (uint32_t)a.px.sh : BUF_OOB, 0, 0);
+                    } else if constexpr (PX == PX_FLT) {
+                        // both widths stand in the straight line, the one the kind does not use at an offset beyond the
+                        // descriptor (dropped without a trip to memory): a branch around a store is what the kernel avoids
+                        const int dy = 2 * (rr - (HF - 1)) + mp;
+                        const uint32_t b = flt_store_value(sacc, a.px.kind);
+                        const uint32_t vo = y0 + dy < a.px.h ? voff8 + (uint32_t)dy * (uint32_t)a.px.sh : BUF_OOB;
+                        __builtin_amdgcn_raw_buffer_store_b32(b, orsrc, a.px.kind == SPIHT_FLT_F32 ? vo : BUF_OOB, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b16((uint16_t)b, orsrc, a.px.kind == SPIHT_FLT_F32 ? BUF_OOB : vo, 0, 0);
                     } else {
                         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, sacc), orsrc,
                                                               voff0 + (uint32_t)(2 * (rr - (HF - 1)) + mp) * row_bytes, 0, 0);
@@ -1588,9 +1609,9 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
                     color3_px(a.col, s_pw, px[0], px[1], px[2], w0, w1, w2);
                     if (PX) {
                         const int64_t o = (int64_t)(m + mp) * a.px.sh + (int64_t)n * a.px.sw;
-                        PX_STORE(PX, out8, o, w0);
-                        PX_STORE(PX, out8, o + a.px.sc, w1);
-                        PX_STORE(PX, out8, o + 2 * a.px.sc, w2);
+                        PX_STORE(PX, out8, o, w0, a.px.kind);
+                        PX_STORE(PX, out8, o + a.px.sc, w1, a.px.kind);
+                        PX_STORE(PX, out8, o + 2 * a.px.sc, w2, a.px.kind);
                     } else {
                         const size_t o = (size_t)(m + mp) * a.out_w + n;
                         out[o] = w0;
@@ -1673,10 +1694,11 @@ static void launch_idwt_pf(IdwtKArgs &a, uint32_t G, uint32_t pad, hipStream_t s
 template <int F, uint32_t LOM, uint32_t HIM>
 static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) {
     a.planes = planes;
-    const int px = a.px.out == nullptr ? PX_F64 : a.px.es == 2 ? PX_U16 : PX_U8;
+    const int px = a.px.out == nullptr ? PX_F64 : px_kind_of(a.px);
     if (a.color) {  // level 1 of a 3-channel image, colour model change on the stores
         uint32_t ntc = (uint32_t)((a.out_w + IW_TW - 1) / IW_TW) * (uint32_t)((a.out_h + IWC_TH - 1) / IWC_TH) * (uint32_t)(planes / 3);
-        if (px == PX_U16) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, PX_U16>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
+        if (px == PX_FLT) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, PX_FLT>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
+        else if (px == PX_U16) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, PX_U16>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
         else if (px == PX_U8) hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM, PX_U8>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
         else hipLaunchKernelGGL((k_idwt1_color<F, LOM, HIM>), dim3(ntc), dim3(DW_BLOCK), 0, st, a);
         return (int)hipGetLastError();
@@ -1689,7 +1711,7 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) 
     const int num_cu = tc ? tc->num_cu : 0;
     // (the persistent kernel addresses a plane with 32-bit offsets: float64 planes by their size, the 8- / 16-bit output by
     // the byte span of its strides)
-    const bool off32 = px ? (uint64_t)((a.px.h - 1) * a.px.sh + (a.px.w - 1) * a.px.sw) + (uint64_t)px < (1ull << 31)
+    const bool off32 = px ? (uint64_t)((a.px.h - 1) * a.px.sh + (a.px.w - 1) * a.px.sw) + (uint64_t)a.px.es < (1ull << 31)
                           : (uint64_t)(a.out_h + IW_TH) * a.out_w * 8u < (1ull << 31);
     if (tc && tc->dev && num_cu >= 2 && nt >= pf_min && off32) {  // (>= 8 workgroups: one per tile range at least)
         const int g = tc->wg_per_cu > 0 ? tc->wg_per_cu : IWP_WG;
@@ -1715,7 +1737,8 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) 
             tc->base[x] += (nt >> 3) + (x < (nt & 7u) ? 1u : 0u) + 2u * ((G + 7u - x) >> 3);
         }
         tc->started += G;
-        if (px == PX_U16) launch_idwt_pf<F, LOM, HIM, PX_U16>(a, G, pad, st, gx, gy, ctr, cb);
+        if (px == PX_FLT) launch_idwt_pf<F, LOM, HIM, PX_FLT>(a, G, pad, st, gx, gy, ctr, cb);
+        else if (px == PX_U16) launch_idwt_pf<F, LOM, HIM, PX_U16>(a, G, pad, st, gx, gy, ctr, cb);
         else if (px == PX_U8) launch_idwt_pf<F, LOM, HIM, PX_U8>(a, G, pad, st, gx, gy, ctr, cb);
         else launch_idwt_pf<F, LOM, HIM, PX_F64>(a, G, pad, st, gx, gy, ctr, cb);
         const hipError_t e = hipGetLastError();
@@ -1726,7 +1749,8 @@ static int launch_idwt_FM(IdwtKArgs a, int planes, hipStream_t st, TileCtr *tc) 
         }
         return (int)e;
     }
-    if (px == PX_U16) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, PX_U16>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
+    if (px == PX_FLT) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, PX_FLT>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
+    else if (px == PX_U16) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, PX_U16>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
     else if (px == PX_U8) hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM, PX_U8>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
     else hipLaunchKernelGGL((k_idwt_level<F, LOM, HIM>), dim3(nt), dim3(DW_BLOCK), 0, st, a);
     return (int)hipGetLastError();
@@ -1824,7 +1848,7 @@ __global__ __launch_bounds__(256) void k_f64_to_px(const double *__restrict__ in
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
         const int64_t p = t / hw, r = t - p * hw, y = r / px.w, x = r - y * px.w;
         const int64_t o = (p / px.c) * px.sb + (p % px.c) * px.sc + y * px.sh + x * px.sw;
-        PX_STORE(PX, px.out, o, in[(p * rec_h + y) * rec_w + x]);
+        PX_STORE(PX, px.out, o, in[(p * rec_h + y) * rec_w + x], px.kind);
     }
 }
 static unsigned pass_grid(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 8192); }
@@ -1838,7 +1862,8 @@ extern "C" int spiht_launch_px_to_f64(const PxView *px, int64_t B, double *out, 
 extern "C" int spiht_launch_f64_to_px(const double *in, int rec_h, int rec_w, const PxView *px, int64_t B, hipStream_t st) {
     const int64_t n = B * px->c * (int64_t)px->h * px->w;
     if (n <= 0) return 0;
-    if (px->es == 2) hipLaunchKernelGGL(k_f64_to_px<PX_U16>, dim3(pass_grid(n)), dim3(256), 0, st, in, rec_h, rec_w, *px, n);
+    if (px->kind) hipLaunchKernelGGL(k_f64_to_px<PX_FLT>, dim3(pass_grid(n)), dim3(256), 0, st, in, rec_h, rec_w, *px, n);
+    else if (px->es == 2) hipLaunchKernelGGL(k_f64_to_px<PX_U16>, dim3(pass_grid(n)), dim3(256), 0, st, in, rec_h, rec_w, *px, n);
     else hipLaunchKernelGGL(k_f64_to_px<PX_U8>, dim3(pass_grid(n)), dim3(256), 0, st, in, rec_h, rec_w, *px, n);
     return (int)hipGetLastError();
 }
@@ -1879,7 +1904,7 @@ __global__ __launch_bounds__(256) void k_ll_to_pic(LlPicArgs a) {
         for (int ch = 0; ch < nch; ch++) {
             const int plane = plane0 + ch;
             uint8_t *p = a.px.out + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc;
-            PX_STORE(PX, p, (int64_t)y * a.px.sh + (int64_t)x * a.px.sw, v[ch]);
+            PX_STORE(PX, p, (int64_t)y * a.px.sh + (int64_t)x * a.px.sw, v[ch], a.px.kind);
         }
     } else {
         for (int ch = 0; ch < nch; ch++) a.out[(size_t)(plane0 + ch) * opl + t] = v[ch];
@@ -1893,6 +1918,7 @@ extern "C" int spiht_launch_ll_to_pic(const LlPicArgs *a, int planes, hipStream_
     if (npix >= (1ll << 31) - 256 || units > 65535) return -1;
     const dim3 grid((unsigned)((npix + 255) / 256), (unsigned)units);
     if (a->px.out == nullptr) hipLaunchKernelGGL(k_ll_to_pic<PX_F64>, grid, dim3(256), 0, st, *a);
+    else if (a->px.kind) hipLaunchKernelGGL(k_ll_to_pic<PX_FLT>, grid, dim3(256), 0, st, *a);
     else if (a->px.es == 2) hipLaunchKernelGGL(k_ll_to_pic<PX_U16>, grid, dim3(256), 0, st, *a);
     else hipLaunchKernelGGL(k_ll_to_pic<PX_U8>, grid, dim3(256), 0, st, *a);
     return (int)hipGetLastError();

@@ -11,6 +11,7 @@
 // are the same for all lanes of the row; only the column zone is per lane.  Stores follow tiles.hip: 16 bytes at a 16-byte-
 // aligned address wherever the destination is contiguous, element by element in front of the first and behind the last.
 #include "tiles.h"
+#include "floatpx.h"
 
 // ---- cut ---------------------------------------------------------------------------------------------------------------------
 // One row of a coded tile: n elements of ES bytes to the dense dst, element k from picture column clamp(X0 + k, 0, W - 1) of the
@@ -70,9 +71,12 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_cut_overlap(const TileCutOv
 // ---- blend -------------------------------------------------------------------------------------------------------------------
 // what a sample of the window is stored as.  8 / 16 bits: the decoder's conversion of a float64 sample (dwt.hip,
 // px8_store_value / px16_store_value): clip to [0, 1], times 255 / 65535, truncate; NaN -> 0 (fmax / fmin return the number
-// of a pair with a NaN)
-template <int ES> __device__ __forceinline__ typename ElemOf<ES>::type blend_store_value(double v) {
-    if constexpr (ES == 8) {
+// of a pair with a NaN).  FK != 0: a float kind (floatpx.h: 1 float32, 2 float16, 3 bfloat16) -- the blended float64 sample
+// rounded once to the kind, as the decoder's float store does
+template <int ES, int FK = 0> __device__ __forceinline__ typename ElemOf<ES>::type blend_store_value(double v) {
+    if constexpr (FK != 0) {
+        return (typename ElemOf<ES>::type)flt_store_value(v, FK);
+    } else if constexpr (ES == 8) {
         return (uint64_t)__double_as_longlong(v);
     } else {
         const double c = fmin(fmax(v, 0.0), 1.0);
@@ -82,7 +86,7 @@ template <int ES> __device__ __forceinline__ typename ElemOf<ES>::type blend_sto
 }
 
 // grid (row chunks of the window, c); block (bx, by): bx lanes along a window row, by rows at a time
-template <int ES>
+template <int ES, int FK = 0>
 __global__ __launch_bounds__(TL_THREADS) void k_tile_blend(const TileBlendArgs a) {
     typedef typename ElemOf<ES>::type T;
     constexpr int EPV = 16 / ES;
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_blend(const TileBlendArgs a
         auto val = [&](int X) -> T {
             double r = hval(top, X);
             if (zy) r = (by * r + ay * hval(bot, X)) / fm;
-            return blend_store_value<ES>(r);
+            return blend_store_value<ES, FK>(r);
         };
         uint8_t *dst = a.out + (int64_t)ch * a.sc + (int64_t)y * a.sh;
         const int n = a.ww;
@@ -168,7 +172,7 @@ extern "C" int spiht_launch_tile_cut_overlap(const TileCutOverlapArgs *a, int es
     }
 }
 
-template <int ES>
+template <int ES, int FK = 0>
 static int launch_blend(TileBlendArgs a, hipStream_t st) {
     dim3 block;
     uint32_t gz;
@@ -180,7 +184,7 @@ static int launch_blend(TileBlendArgs a, hipStream_t st) {
         a.rows = std::max<int>((int)block.y, a.rows / 2 / (int)block.y * (int)block.y);
         gz = (uint32_t)((a.wh + a.rows - 1) / a.rows);
     }
-    hipLaunchKernelGGL(k_tile_blend<ES>, dim3(gz, a.c), block, 0, st, a);
+    hipLaunchKernelGGL((k_tile_blend<ES, FK>), dim3(gz, a.c), block, 0, st, a);
     return (int)hipGetLastError();
 }
 // es: bytes per sample of the OUTPUT: 8 float64, 1 / 2 the 8- / 16-bit conversion
@@ -189,5 +193,14 @@ extern "C" int spiht_launch_tile_blend(const TileBlendArgs *a, int es, hipStream
     case 1: return launch_blend<1>(*a, st);
     case 2: return launch_blend<2>(*a, st);
     default: return launch_blend<8>(*a, st);
+    }
+}
+// ... into a float kind (floatpx.h)
+extern "C" int spiht_launch_tile_blend_flt(const TileBlendArgs *a, int kind, hipStream_t st) {
+    switch (kind) {
+    case SPIHT_FLT_F32: return launch_blend<4, SPIHT_FLT_F32>(*a, st);
+    case SPIHT_FLT_F16: return launch_blend<2, SPIHT_FLT_F16>(*a, st);
+    case SPIHT_FLT_BF16: return launch_blend<2, SPIHT_FLT_BF16>(*a, st);
+    default: return -1;
     }
 }

@@ -275,6 +275,7 @@ extern "C" int spiht_launch_tile_mosaic(const TileMosaicArgs *a, int es, hipStre
     switch (es) {
     case 1: return launch_mosaic<1>(*a, st);
     case 2: return launch_mosaic<2>(*a, st);
+    case 4: return launch_mosaic<4>(*a, st);
     default: return launch_mosaic<8>(*a, st);
     }
 }

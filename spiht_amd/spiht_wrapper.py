@@ -13,8 +13,9 @@ from typing import Any, List, Optional, Tuple, Union
 
 import numpy as np
 
-from . import _lib, color_models
+from . import _lib, color_models, floatpx
 from . import spiht as spiht_rs
+from .floatpx import check_float_view  # noqa: F401  (the float kinds' view rule, beside check_u8_view / check_u16_view)
 
 
 def quantize(arr, q_scale=10.):
@@ -301,7 +302,8 @@ def _encode_image_int(image, spiht_settings, level, max_bits, channels_last, dty
                         spiht_settings, mults_p, max_bits)
 
 
-def _decode_image_int(encoding_result, spiht_settings, channels_last, dtype, fn_name):
+def _decode_image_int(encoding_result, spiht_settings, channels_last, dtype, fn_name, kind=()):
+    """kind: () for the integer calls, (kind id,) for the *_flt ones -- the argument behind the context"""
     _check_version(encoding_result)
     h, w, c = encoding_result.h, encoding_result.w, encoding_result.c
     if spiht_settings.color_model is not None and c != 3:
@@ -311,7 +313,8 @@ def _decode_image_int(encoding_result, spiht_settings, channels_last, dtype, fn_
     strides = np.array((1, w * c, c) if channels_last else (h * w, w, 1), dtype=np.int64) * np.dtype(dtype).itemsize
     ctx = _lib.default_context()
     with color_models.fused(ctx, spiht_settings.color_model):
-        _lib.check(getattr(_lib.lib(), fn_name)(ctx.handle, *args, C.c_void_p(out.ctypes.data), C.c_void_p(strides.ctypes.data)))
+        _lib.check(getattr(_lib.lib(), fn_name)(ctx.handle, *kind, *args, C.c_void_p(out.ctypes.data),
+                                                C.c_void_p(strides.ctypes.data)))
     return out
 
 
@@ -344,6 +347,22 @@ def decode_image_u16(encoding_result: EncodingResult, spiht_settings: SpihtSetti
     with the conversion done on the device.  Returns a new uint16 array (c, h, w), or (h, w, c) with channels_last.  The
     stream may come from any pixel format."""
     return _decode_image_int(encoding_result, spiht_settings, channels_last, np.uint16, "spiht_decode_image_host_u16")
+
+
+def decode_image_float(encoding_result: EncodingResult, spiht_settings: SpihtSettings, dtype=np.float32,
+                       channels_last: bool = False) -> np.ndarray:
+    """Float pixels out: floatpx.convert(decode_image(r, s)[:, :h, :w], dtype) in every bit -- each float64 sample rounded ONCE
+    to the kind (nearest, ties to even; no clip, no scale: what lies outside [0, 1] stays, overflow gives inf), cropped to the
+    encoded picture's h x w -- with the conversion done on the device, so that 4 or 2 bytes per sample cross the link.
+    dtype: np.float32, np.float16, "bfloat16", or a torch dtype (floatpx.kind_arg).  Returns a new array (c, h, w), or
+    (h, w, c) with channels_last: float32, float16, or for bfloat16 the uint16 bit patterns (numpy has no such type) --
+
+        torch.from_numpy(a.view(np.int16)).view(torch.bfloat16)
+
+    The stream may come from any pixel format."""
+    kind = floatpx.kind_arg(dtype)
+    return _decode_image_int(encoding_result, spiht_settings, channels_last, floatpx.storage_dtype(kind),
+                             "spiht_decode_image_host_flt", (kind,))
 
 
 def reduced_shape(h: int, w: int, spiht_settings: SpihtSettings, level: Optional[int], reduce: int):
@@ -411,7 +430,7 @@ def decode_image_reduced(encoding_result: EncodingResult, spiht_settings: SpihtS
     return _crop_window(out, rs, crop)
 
 
-def _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, dtype, fn_name):
+def _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, dtype, fn_name, kind=()):
     _check_version(encoding_result)
     er = encoding_result
     rs = reduced_shape(er.h, er.w, spiht_settings, er.level, reduce)
@@ -423,8 +442,8 @@ def _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, cha
     strides = np.array((1, w * c, c) if channels_last else (h * w, w, 1), dtype=np.int64) * np.dtype(dtype).itemsize
     ctx = _lib.default_context()
     with color_models.fused(ctx, spiht_settings.color_model):
-        _lib.check(getattr(_lib.lib(), fn_name)(ctx.handle, *args, C.c_void_p(out.ctypes.data), C.c_void_p(strides.ctypes.data),
-                                                int(reduce)))
+        _lib.check(getattr(_lib.lib(), fn_name)(ctx.handle, *kind, *args, C.c_void_p(out.ctypes.data),
+                                                C.c_void_p(strides.ctypes.data), int(reduce)))
     return _crop_window(out, rs, crop, channels_last)
 
 
@@ -442,6 +461,16 @@ def decode_image_reduced_u16(encoding_result: EncodingResult, spiht_settings: Sp
     """16-bit pixels at 1/2^reduce size: as decode_image_reduced_u8 with 65535 for 255."""
     return _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, np.uint16,
                                      "spiht_decode_image_reduced_host_u16")
+
+
+def decode_image_reduced_float(encoding_result: EncodingResult, spiht_settings: SpihtSettings, reduce: int, dtype=np.float32,
+                               crop: bool = False, channels_last: bool = False) -> np.ndarray:
+    """Float pixels at 1/2^reduce size: floatpx.convert(decode_image_reduced(r, s, reduce), dtype) cropped to the band size
+    (c, pic_h, pic_w) (reduced_shape), as the integer forms are -- the rule of decode_image_float one pyramid level up --,
+    converted on the device; (pic_h, pic_w, c) with channels_last.  crop=True: the centred window, as decode_image_reduced."""
+    kind = floatpx.kind_arg(dtype)
+    return _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, floatpx.storage_dtype(kind),
+                                     "spiht_decode_image_reduced_host_flt", (kind,))
 
 
 def _band_sizes(h, w, wavelet, levels, mode="reflect"):

@@ -50,7 +50,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import _lib, alloc
+from . import _lib, alloc, floatpx
 from . import overlap as _overlap
 from .batch import BatchCodec, DeviceArray
 from .spiht_wrapper import (ENCODER_DECODER_VERSION, EncodingResult, SpihtSettings, _check_aligned, _check_int_view,
@@ -392,9 +392,35 @@ def _ptr(x):
 _SUFFIX = {np.dtype(np.uint8): "u8", np.dtype(np.uint16): "u16", np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
 
 
+class _FloatKind:
+    """the element type of float pixels OUT (floatpx: float32, float16, bfloat16), where the others are an np.dtype: the kind's
+    id, its bytes per sample and the numpy type its pictures come in (bfloat16: uint16 bit patterns)"""
+    kind = "F"  # (np.dtype.kind of the others: "u", "f")
+
+    def __init__(self, dtype):
+        self.id = floatpx.kind_id(dtype)
+        self.itemsize = floatpx.itemsize(self.id)
+        self.storage = floatpx.storage_dtype(self.id)
+
+
+def _elem(dtype):
+    """an element type as the tile calls name it: a _FloatKind as it is, anything else as an np.dtype"""
+    return dtype if isinstance(dtype, _FloatKind) else np.dtype(dtype)
+
+
+# float pixels out: a tile batch of a kind is copied as elements of its size -- both 16-bit kinds by the uint16 copies, float32
+# by the strided 4-byte ones; the blend rounds to the kind at its store
+_FLOAT_COPY = {("spiht_tile_paste_", 2): "spiht_tile_paste_u16", ("spiht_tile_paste_", 4): "spiht_tile_paste_f32s",
+               ("spiht_tile_mosaic_", 2): "spiht_tile_mosaic_u16", ("spiht_tile_mosaic_", 4): "spiht_tile_mosaic_f32"}
+
+
 def _entry(L, stem, dt):
     """the library's entry point of that stem for an element type (an np.dtype): (L, "spiht_tile_paste_", uint16) ->
-    L.spiht_tile_paste_u16"""
+    L.spiht_tile_paste_u16; for a _FloatKind the copy of its element size, or the blend into the kind"""
+    if isinstance(dt, _FloatKind):
+        if stem == "spiht_tile_blend_":
+            return lambda ctx, *a: L.spiht_tile_blend_flt(ctx, dt.id, *a)
+        return getattr(L, _FLOAT_COPY[stem, dt.itemsize])
     return getattr(L, stem + _SUFFIX[dt])
 
 
@@ -476,12 +502,18 @@ class TiledCodec:
         if strides is None:
             return None, None
         st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
-        _check_int_view(8 * np.dtype(dtype).itemsize, shape, st, output)
+        if isinstance(dtype, _FloatKind):
+            floatpx.check_float_view(dtype.id, shape, st, output)
+        else:
+            _check_int_view(8 * np.dtype(dtype).itemsize, shape, st, output)
         return st, C.c_void_p(st.ctypes.data)
 
     def _tile_call(self, op, dt):
         """the tile codec's batched call for an element type (an np.dtype); op: "encode", "decode" or "decode_reduced".  The
-        float form is the one of the codec's own float pixels"""
+        float form is the one of the codec's own float pixels; a _FloatKind: the *_float decode, which takes the kind behind the
+        output (behind `reduce`)"""
+        if isinstance(dt, _FloatKind):
+            return getattr(self.codec, op + "_device_float")
         return getattr(self.codec, op + "_device" + ("_" + _SUFFIX[dt] if dt.kind == "u" else ""))
 
     def _download(self, ptr, shape, dtype):
@@ -759,7 +791,8 @@ class TiledCodec:
         """d_packed / d_lens / d_max_n: the streams, lengths (uint32) and start planes (uint8) of the tiles of the sub-grid
         sub = (i0, i1, j0, j1) in row-major order -- only those are unpacked and decoded.  window = (y0, x0, h, w) inside the
         picture and inside the sub-grid.  -> d_out: DeviceArray [c, h, w], float64, or uint8 / uint16 laid out by `strides`
-        (bytes (sc, sh, sw); None: dense CHW; what lies between the view's samples is not written).  slot_stride: bytes per
+        (bytes (sc, sh, sw); None: dense CHW; what lies between the view's samples is not written); float pixels out: an
+        object with .ptr and .dtype = float_elem(dtype), laid out by `strides` the same way.  slot_stride: bytes per
         stream slot the streams are unpacked into, a multiple of 4 no stream is longer than (None: the codec's bound).
         One unpack, one batched decode, one paste, queued on the codec's context.
         Streams of an allocate="rd" encoder: a tile may be longer than the bound of an equal-split codec, and
@@ -782,11 +815,12 @@ class TiledCodec:
     def _decode_slots(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, reduce):
         """the zero-padded slots of the sub-grid's tiles -> the window: one batched decode, one paste (reduce > 0: one batched
         reduced decode, one mosaic; overlap > 0, every element type: one batched float64 decode of the coded tiles, one blend,
-        which converts the blended sample for 8- and 16-bit output)"""
+        which converts the blended sample for 8- and 16-bit output and rounds it for a float kind).  A float kind (_FloatKind) goes
+        the integer kinds' way: the tiles' *_float decode into a dense tile batch of the kind, cropped as theirs, then a copy"""
         (i0, i1, j0, j1), (y0, x0, h, w) = sub, window
         n, vp, k = (i1 - i0) * (j1 - j0), C.c_void_p, int(reduce)
-        dt = np.dtype(d_out.dtype)
-        integer = dt.kind == "u"
+        dt = _elem(d_out.dtype)
+        integer = dt.kind in "uF"  # (a view of the output, tiles cropped to the picture's samples)
         # the plan: the batched decode (with what it takes behind the output) and the element type of its tiles, rh x rw of one
         # decoded tile, the call that assembles them and the geometry it takes in front of the sub-grid and the window
         rec = self.codec.geom["rec_h"], self.codec.geom["rec_w"]
@@ -804,8 +838,10 @@ class TiledCodec:
         view = ()  # the integer forms write a view of the output: the strides, behind the address
         if integer:
             st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
-            _check_aligned(d_out.ptr, dt)
+            _check_aligned(d_out.ptr, dt.storage if isinstance(dt, _FloatKind) else dt)
             view = (st_p,)
+            if isinstance(dt, _FloatKind) and tile_dt is dt:
+                more = more + (dt.id,)
         elif dt != np.float64 or strides is not None:
             raise ValueError("decode: the float form gives dense float64 pictures")
         d_dec = self._buf("dec", n * self.c * rh * rw * tile_dt.itemsize)
@@ -1021,7 +1057,7 @@ class TiledCodec:
         rs = self.reduced_shape(reduce)
         y0, x0, h, w = self._window_arg(window, rs)
         i0, i1, j0, j1 = sub = self._window_tiles(rs, y0, x0, h, w)
-        dtype = np.dtype(dtype)
+        dtype = _elem(dtype)
         ts = [i * self.gx + j for i in range(i0, i1) for j in range(j0, j1)]
         n = len(ts)
         # a row of the sub-grid, tiles a .. b - 1, is contiguous in the run (per layer, in the file)
@@ -1058,7 +1094,8 @@ class TiledCodec:
         else:
             self.decode_window_device(*streams, *where, reduce)
         self.ctx.synchronize()
-        out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w), dtype)
+        out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w),
+                                dtype.storage if isinstance(dtype, _FloatKind) else dtype)
         self.ctx.download(out, d_out.ptr)
         return out
 
@@ -1118,12 +1155,31 @@ class TiledCodec:
         """decode_window into uint16 [c, h, w] (or [h, w, c])"""
         return self._decode_host(result, (y0, x0, h, w), np.uint16, channels_last, reduce)
 
+    # ---- float pixels out (floatpx): floatpx.convert(<the float64 call>, dtype) in every bit, each sample rounded once, with
+    # the conversion on the device -- in the tiles' decode, or with overlap > 0 at the blend's store.  dtype: np.float32,
+    # np.float16, "bfloat16" or a torch dtype; bfloat16 comes as uint16 bit patterns.
+    def decode_float(self, result, dtype=np.float32, channels_last=False, reduce=0):
+        """-> [c, H, W] (or [H, W, c]) of the kind: floatpx.convert(decode(result, reduce), dtype)"""
+        return self._decode_host(result, None, _FloatKind(dtype), channels_last, reduce)
+
+    def decode_window_float(self, result, y0, x0, h, w, dtype=np.float32, channels_last=False, reduce=0):
+        """-> [c, h, w] (or [h, w, c]) of the kind: floatpx.convert(decode_window(result, y0, x0, h, w, reduce), dtype)"""
+        return self._decode_host(result, (y0, x0, h, w), _FloatKind(dtype), channels_last, reduce)
+
+    def decode_layered_float(self, result, upto=None, dtype=np.float32, channels_last=False, reduce=0):
+        """floatpx.convert(decode_layered(result, upto, reduce), dtype)"""
+        return self._decode_host(result, None, _FloatKind(dtype), channels_last, reduce, True, upto)
+
+    def decode_layered_window_float(self, result, y0, x0, h, w, upto=None, dtype=np.float32, channels_last=False, reduce=0):
+        """floatpx.convert(decode_layered_window(result, y0, x0, h, w, upto, reduce), dtype)"""
+        return self._decode_host(result, (y0, x0, h, w), _FloatKind(dtype), channels_last, reduce, True, upto)
+
 
 class _View:
     """a device address with an element type (what the device forms need of a DeviceArray), owning nothing"""
 
     def __init__(self, ptr, dtype):
-        self.ptr, self.dtype = int(ptr), np.dtype(dtype)
+        self.ptr, self.dtype = int(ptr), _elem(dtype)
 
 
 # ---- top-level conveniences, after the single-image calls -------------------------------------------------------------
@@ -1227,6 +1283,34 @@ def decode_image_window_u8(result, spiht_settings, y0, x0, h, w, channels_last=F
 
 def decode_image_window_u16(result, spiht_settings, y0, x0, h, w, channels_last=False, reduce=0):
     return _decode_tiled(result, spiht_settings, (y0, x0, h, w), np.uint16, channels_last, reduce)
+
+
+def decode_image_tiled_float(result, spiht_settings, dtype=np.float32, channels_last=False, reduce=0):
+    """TiledResult -> the picture in a float kind (np.float32, np.float16, "bfloat16", a torch dtype; bfloat16 as uint16 bit
+    patterns): floatpx.convert(decode_image_tiled(result, spiht_settings, reduce), dtype) in every bit, converted on the device"""
+    return _decode_tiled(result, spiht_settings, None, _FloatKind(dtype), channels_last, reduce)
+
+
+def decode_image_window_float(result, spiht_settings, y0, x0, h, w, dtype=np.float32, channels_last=False, reduce=0):
+    """floatpx.convert(decode_image_window(result, spiht_settings, y0, x0, h, w, reduce), dtype)"""
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), _FloatKind(dtype), channels_last, reduce)
+
+
+def decode_image_layered_float(result, spiht_settings, upto=None, dtype=np.float32, channels_last=False, reduce=0):
+    """floatpx.convert(decode_image_layered(result, spiht_settings, upto, reduce), dtype)"""
+    return _decode_tiled(result, spiht_settings, None, _FloatKind(dtype), channels_last, reduce, True, upto)
+
+
+def decode_image_layered_window_float(result, spiht_settings, y0, x0, h, w, upto=None, dtype=np.float32, channels_last=False,
+                                      reduce=0):
+    """floatpx.convert(decode_image_layered_window(result, spiht_settings, y0, x0, h, w, upto, reduce), dtype)"""
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), _FloatKind(dtype), channels_last, reduce, True, upto)
+
+
+def float_elem(dtype):
+    """the element type the device forms (decode_window_device, decode_device, decode_layers_device) take as d_out.dtype for
+    float pixels out"""
+    return _FloatKind(dtype)
 
 
 def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype, channels_last, name, points, spread, roi=None,
