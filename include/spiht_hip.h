@@ -28,7 +28,7 @@ enum {
     SPIHT_ERR_ARG = 6,       /* null pointer / negative size / unknown wavelet or mode */
     SPIHT_ERR_MAGNITUDE = 7, /* max|x| >= 2^30: outside the range the reference handles */
     SPIHT_ERR_INTERNAL = 8,  /* device-side list overflow guard tripped (a bug, never expected) */
-    SPIHT_ERR_TOO_LARGE = 9, /* c*h*w >= 2^30 or stream >= 2^32 bits */
+    SPIHT_ERR_TOO_LARGE = 9, /* c*h*w >= 2^30, stream >= 2^32 bits, or a picture of more than 65535 planes */
     SPIHT_ERR_NOMEM = 10
 };
 
@@ -198,7 +198,13 @@ int spiht_geometry(int64_t H, int64_t W, int wavelet, int level, int *level_used
 int spiht_geometry_mode(int64_t H, int64_t W, int wavelet, int mode, int level, int *level_used, int64_t *ll_h, int64_t *ll_w,
                         int64_t *enc_h, int64_t *enc_w, int64_t *rec_H, int64_t *rec_W);
 
-/* d_img: float64 [B,c,H,W] (device).  channel_mults: HOST array of c doubles or NULL
+/* Every image call below -- batched or host, any pixel format, forward, inverse, fused, two-part, reduced -- takes at most
+ * 65535 planes per picture: c > 65535 is SPIHT_ERR_TOO_LARGE before anything is queued and before the geometry is looked
+ * at.  A batch is cut into launches of at most 65535 planes between pictures, never inside one, and a launch carries its
+ * planes in grid.y / grid.z.  spiht_encode_batch_i32 has the same limit and the same status; spiht_pyramid_batch_i32
+ * takes at most 65535 planes in the whole call (SPIHT_ERR_ARG beyond).
+ *
+ * d_img: float64 [B,c,H,W] (device).  channel_mults: HOST array of c doubles or NULL
  * (SpihtSettings.per_channel_quant_scales); q_scale: SpihtSettings.quantization_scale.
  * Outputs as spiht_encode_batch_i32.  d_coeffs: optional device int32 [B,c,enc_h,enc_w] that receives the
  * quantised coefficient array handed to the coder (NULL to keep it in scratch). */

@@ -435,7 +435,7 @@ extern "C" const char *spiht_strerror(int s) {
     case SPIHT_ERR_ARG: return "invalid argument";
     case SPIHT_ERR_MAGNITUDE: return "coefficient magnitude >= 2^30 is outside the supported range";
     case SPIHT_ERR_INTERNAL: return "internal list capacity guard tripped";
-    case SPIHT_ERR_TOO_LARGE: return "array or stream too large (c*h*w must be < 2^30, stream < 2^32 bits)";
+    case SPIHT_ERR_TOO_LARGE: return "array or stream too large (c*h*w must be < 2^30, stream < 2^32 bits, a picture at most 65535 planes)";
     case SPIHT_ERR_NOMEM: return "out of device memory";
     default: return "unknown status";
     }
@@ -1112,6 +1112,7 @@ extern "C" int spiht_encode_batch_i32(spiht_ctx *ctx, const int32_t *d_x, int64_
     if (!ctx || !d_x || !d_out || !d_nbits || !d_max_n || B < 0) return SPIHT_ERR_ARG;
     Geom g;
     CHK(make_geom(c, h, w, ll_h, ll_w, &g));
+    if (c > 65535) return SPIHT_ERR_TOO_LARGE;  // (one array's planes go into grid.z of the pyramid's launches)
     if (B == 0) return SPIHT_OK;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
@@ -1680,6 +1681,9 @@ static int check_img_args(int wavelet, int mode, int64_t B, int64_t c, int64_t H
     if (wavelet < 0 || wavelet >= SPIHT_NWAVELETS || mode < 0 || mode > SPIHT_MODE_PERIODIZATION) return SPIHT_ERR_ARG;
     if (B < 0 || c < 1 || H < 1 || W < 1) return SPIHT_ERR_ARG;
     if (H > (1 << 24) || W > (1 << 24)) return SPIHT_ERR_TOO_LARGE;
+    // one picture is never split: batch_chunks hands all its c planes to one launch, and the launchers put the planes of a
+    // launch into grid.y / grid.z (k_dwt_edge, k_zero_pads, k_pyr_ll, k_ll_to_pic), which end at 65535
+    if (c > 65535) return SPIHT_ERR_TOO_LARGE;
     return SPIHT_OK;
 }
 

@@ -142,6 +142,168 @@ def flags_reference(O):
     return cached("flags_reference", make)
 
 
+# ---- the seam once more, at a geometry whose sizes all differ ------------------------------------------------------
+# At CHUNK every per-picture size is 3 * 64 (H W = rec_H rec_W = enc_h enc_w, the reduced picture is the root block), and at
+# FLAGS rec_H = H: a launch that stepped its pictures by the wrong one of them would land on the right picture all the same.
+# SEAM2: hs = [17, 11, 8], ws = [25, 15, 10]; the array is 27 x 35, the float64 picture 18 x 26, the approximation plane of
+# the two-part inverse 12 x 16 (which is also the float64 picture at reduce = 1: the same number by definition), the root
+# block 8 x 10 (the float64 picture at reduce = 2 = L), the reduced integer pictures 11 x 15 and 8 x 10.  The budget cuts
+# every stream short.  127 pictures in turn: 21845 % 127 = 1.
+SEAM2 = dict(c=3, H=17, W=25, wavelet="bior2.2", mode="reflect", level=2, q=50.0, max_bits=4000)
+SEAM2_DISTINCT = 127
+# the two-pass route (k_dwt_axis_ext / k_dwt_pack_ext, k_idwt_axis_per, and the conversion passes k_px_to_f64 / k_f64_to_px
+# around them for integer and float-kind pixels): periodization, hs = [9, 5], ws = [13, 7], array and float64 picture 10 x 14
+SEAM_PER = dict(c=3, H=9, W=13, wavelet="db2", mode="periodization", level=1, q=50.0, max_bits=900)
+SEAM_PER_DISTINCT = 127
+
+
+def seam_pictures(k, distinct):
+    """uint8 [distinct, c, H, W]: the pictures that take turns through the batch of case k (picture b is b % distinct)"""
+    def make():
+        p = np.random.default_rng(20261020 + k["H"]).integers(0, 256, (distinct, k["c"], k["H"], k["W"]), dtype=np.uint8)
+        p.flags.writeable = False
+        return p
+    return cached(("seam_pictures", k["H"], k["W"], distinct), make)
+
+
+def in_turn(distinct, B=None):
+    """which of the distinct pictures stands at each place of the batch"""
+    return np.arange(CHUNK_B if B is None else B) % distinct
+
+
+def seam2_sizes(O):
+    """the per-picture element counts the offsets of a chunk are multiples of (api.cpp; each times b0), from the oracle's
+    geometry -> dict"""
+    k = SEAM2
+    g = O.geometry(k["H"], k["W"], k["wavelet"], k["level"], k["mode"])
+    F = len(O.wavelet_filters(k["wavelet"])[0])
+    c, L = k["c"], g["level"]
+    rec = lambda n: 2 * n - F + 2  # noqa: E731  (what one inverse level returns for a band of n)
+    return dict(picture=c * k["H"] * k["W"], rec=c * rec(g["hs"][1]) * rec(g["ws"][1]), array=c * g["enc_h"] * g["enc_w"],
+                approx=c * rec(g["hs"][2]) * rec(g["ws"][2]), reduced1=c * rec(g["hs"][2]) * rec(g["ws"][2]),
+                reduced2=c * g["hs"][L] * g["ws"][L], reduced1_int=c * g["hs"][1] * g["ws"][1])
+
+
+def _reduced(O, D, k, g, r):
+    """R_r of a dequantised array [c, enc_h, enc_w] (tests/test_gpu_reduced.py: want_reduced; tests/test_reduced_cpu.py:
+    oracle_reduced): the corner of the array is the array of the hs[r] x ws[r] picture at L - r levels; its inverse transform
+    times 2^-r; at r = L the root block times 2^-L"""
+    L = g["level"]
+    if r == L:
+        return np.ascontiguousarray(D[:, :g["ll_h"], :g["ll_w"]]) * 2.0 ** -L
+    gk = O.geometry(g["hs"][r], g["ws"][r], k["wavelet"], L - r, k["mode"])
+    sub = np.ascontiguousarray(D[:, :gk["enc_h"], :gk["enc_w"]])
+    return O.waverec2_array(sub, g["hs"][r], g["ws"][r], k["wavelet"], L - r, k["mode"]) * 2.0 ** -r
+
+
+def _frozen(out):
+    for v in out.values():
+        if isinstance(v, np.ndarray):
+            v.flags.writeable = False
+    return out
+
+
+def seam_reference(O, k, distinct):
+    """the oracle on the distinct pictures of case k (/ 255) -> dict of arrays over them, read-only (picture b of the batch is
+    b % distinct): coeffs int32 [D, c, enc_h, enc_w] with dcode / lcode, the masks d_where / l_where and maxabs as
+    chunk_reference has them; coeffs_f32 (the single-precision transform of float32(P / 255)); streams, nbits, max_n of
+    coeffs, and streams_f32, nbits_f32, max_n_f32 of coeffs_f32; rec (the decoded arrays); pics float64 [D, c, rec_h, rec_w];
+    geom (the oracle's geometry).  With two levels or more also: red[r] for r = 1 .. L (the reduced pictures, float64,
+    uncropped); approx = 2 red[1], what the coarse half of the two-part inverse leaves; rec_fl, a copy of rec with the level-1
+    detail bands of about half the (plane, tile) pairs emptied, its occupancy words (dwt_sweep_tables.occupancy_words) and
+    its pictures pics_fl.  Host time, once per process: 0.5 s for SEAM2's 127 pictures, under 0.1 s for SEAM_PER's."""
+    def make():
+        P = seam_pictures(k, distinct)
+        c, H, W, wv, md, lv, q = k["c"], k["H"], k["W"], k["wavelet"], k["mode"], k["level"], k["q"]
+        g = O.geometry(H, W, wv, lv, md)
+        F = len(O.wavelet_filters(wv)[0])
+        eh, ew, lh, lw = g["enc_h"], g["enc_w"], g["ll_h"], g["ll_w"]
+        out = dict(coeffs=[], coeffs_f32=[], dcode=[], lcode=[], streams=[], nbits=[], max_n=[], streams_f32=[], nbits_f32=[],
+                   max_n_f32=[], rec=[], pics=[])
+        two = g["level"] >= 2
+        if two:
+            out.update(rec_fl=[], pics_fl=[])
+            red = {r: [] for r in range(1, g["level"] + 1)}
+        has = None
+        for i in range(distinct):
+            co = O.quantize(O.wavedec2_array(P[i] / 255, wv, md, lv)[0], q, None)
+            co32 = O.quantize_f32(O.wavedec2_array_f32((P[i] / 255).astype(np.float32), wv, md, lv)[0], q, None)
+            dc, lc, has = O.set_codes(co, lh, lw)
+            d, n, nb = O.encode_nbits(co, lh, lw, k["max_bits"])
+            d32, n32, nb32 = O.encode_nbits(co32, lh, lw, k["max_bits"])
+            rec = O.decode(d, n, c, eh, ew, lh, lw)
+            D = O.dequantize(rec, q, None)
+            for name, v in (("coeffs", co), ("coeffs_f32", co32), ("dcode", dc), ("lcode", lc), ("streams", d), ("nbits", nb),
+                            ("max_n", n), ("streams_f32", d32), ("nbits_f32", nb32), ("max_n_f32", n32), ("rec", rec),
+                            ("pics", O.waverec2_array(D, H, W, wv, lv, md))):
+                out[name].append(v)
+            if two:
+                for r in red:
+                    red[r].append(_reduced(O, D, k, g, r))
+                fl = T.empty_some_tiles(rec.copy(), H, W, F, 70 + i)
+                out["rec_fl"].append(fl)
+                out["pics_fl"].append(O.waverec2_array(O.dequantize(fl, q, None), H, W, wv, lv, md))
+        for name, dt in (("nbits", np.uint64), ("max_n", np.uint8), ("nbits_f32", np.uint64), ("max_n_f32", np.uint8)):
+            out[name] = np.array(out[name], dt)
+        for name in out:
+            if isinstance(out[name], list) and not name.startswith("streams"):
+                out[name] = np.stack(out[name])
+        I, J = np.arange(eh)[:, None], np.arange(ew)[None, :]
+        out.update(d_where=has, l_where=has & ((4 * I + 3 < eh) & (4 * J + 3 < ew))[None], geom=g,
+                   maxabs=np.abs(out["coeffs"].astype(np.int64)).max(axis=(1, 2, 3)).astype(np.uint32))
+        if two:
+            out["red"] = {r: np.stack(v) for r, v in red.items()}
+            for v in out["red"].values():
+                v.flags.writeable = False
+            out["approx"] = out["red"][1] * 2.0  # (exact: the reduced picture is the approximation times 2^-1)
+            out["words"] = T.occupancy_words(out["rec_fl"], H, W, F)
+        return _frozen(out)
+    return cached(("seam_reference", k["H"], k["W"], k["mode"], distinct), make)
+
+
+def seam2_reference(O):
+    return seam_reference(O, SEAM2, SEAM2_DISTINCT)
+
+
+def seam_per_reference(O):
+    return seam_reference(O, SEAM_PER, SEAM_PER_DISTINCT)
+
+
+# ---- padded views: every stride differs from the dense one ---------------------------------------------------------
+PAD_BYTE = 0x7F  # (the guard byte of tests/test_gpu_coder_edges.py)
+
+
+def padded_strides(c, H, W, es):
+    """byte strides (sb, sc, sh, sw) of a channels-last view with one spare sample behind the c of every pixel (RGBA-like),
+    three spare samples behind every row and two spare rows behind every picture: none of sb, sh, sw is the dense HWC one"""
+    sw = (c + 1) * es
+    sh = W * sw + 3 * es
+    return np.array([(H + 2) * sh, es, sh, sw], np.int64)
+
+
+def padded_buffer(B, c, H, W, dtype):
+    """-> (host buffer [B, sb / es] of dtype, every byte the guard byte; its view [B, c, H, W] of the samples; the strides).
+    For a float kind take the unsigned integer of its size (the guard pattern is a NaN in float16)."""
+    dtype = np.dtype(dtype)
+    st = padded_strides(c, H, W, dtype.itemsize)
+    buf = np.full((B, int(st[0])), PAD_BYTE, np.uint8).view(dtype)
+    return buf, samples_of(buf, c, H, W), st
+
+
+def samples_of(buf, c, H, W):
+    """the [B, c, H, W] view of the samples in a buffer [B, sb / es] laid out by padded_strides"""
+    st = padded_strides(c, H, W, buf.dtype.itemsize)
+    assert buf.ndim == 2 and buf.flags.c_contiguous and buf.shape[1] * buf.dtype.itemsize == st[0]
+    return np.lib.stride_tricks.as_strided(buf, (len(buf), c, H, W), tuple(int(v) for v in st))
+
+
+def padding_untouched(buf, c, H, W):
+    """every byte of the buffer that is no sample still holds the guard byte"""
+    b = np.array(buf.view(np.dtype("u%d" % buf.dtype.itemsize)), copy=True)
+    samples_of(b, c, H, W)[...] = int.from_bytes(bytes([PAD_BYTE]) * b.dtype.itemsize, "little")
+    return bool((b.view(np.uint8) == PAD_BYTE).all())
+
+
 # =================================================================================== B. what a call leaves behind
 # the probe: one small fused round trip whose answers the oracle gives
 PROBE = dict(B=2, c=3, H=70, W=90, wavelet="bior2.2", mode="reflect", level=None, q=50.0, max_bits=int(70 * 90 * 0.5))

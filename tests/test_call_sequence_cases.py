@@ -72,6 +72,133 @@ def test_the_occupancy_words_of_the_seam_case(oracle):
     assert len(np.unique(R["rec"].reshape(K.FLAGS_DISTINCT, -1), axis=0)) == K.FLAGS_DISTINCT
 
 
+def _library_sizes(k):
+    """what the library says of case k: (rec_h, rec_w), (enc_h, enc_w), the approximation plane, {r: (dense reduced picture,
+    the picture of an integer or float-kind view)} for r = 1 .. L, and the occupancy words per picture"""
+    import ctypes as C
+    from spiht_amd import _lib
+    L = _lib.lib()
+    wid, mid, lv = L.spiht_wavelet_id(k["wavelet"].encode()), L.spiht_mode_id(k["mode"].encode()), k["level"]
+    i64 = [C.c_int64() for _ in range(8)]
+    used = C.c_int()
+    assert L.spiht_geometry_mode(k["H"], k["W"], wid, mid, lv, C.byref(used), *[C.byref(v) for v in i64[:6]]) == 0
+    enc, rec = (i64[2].value, i64[3].value), (i64[4].value, i64[5].value)
+    ah, aw = C.c_int64(), C.c_int64()
+    assert L.spiht_idwt_approx_shape(k["H"], k["W"], wid, lv, C.byref(ah), C.byref(aw)) == 0
+    red = {}
+    for r in range(1, used.value + 1):
+        assert L.spiht_reduced_shape(k["H"], k["W"], wid, mid, lv, r, C.byref(used), *[C.byref(v) for v in i64]) == 0
+        red[r] = ((i64[0].value, i64[1].value), (i64[2].value, i64[3].value))
+    words = C.c_uint64()
+    assert L.spiht_l1_flags_words(k["c"], k["H"], k["W"], wid, mid, lv, C.byref(words)) == 0
+    return rec, enc, (ah.value, aw.value), red, int(words.value)
+
+
+def test_no_two_sizes_of_the_second_seam_case_agree(oracle):
+    """SEAM2 exists so that a launch which stepped one of its arrays by another array's size lands on another picture.  The
+    per-picture element counts -- each is the multiplier of b0 somewhere in api.cpp -- are pairwise different, with one
+    exception that no geometry can avoid: the approximation plane of the two-part inverse IS the float64 picture at
+    reduce = 1 (2 hs[2] - F + 2 by 2 ws[2] - F + 2, both), so c a_plane and that dense size are one number, and are
+    asserted to be.  The integer / float-kind picture at reduce = 1 (hs[1] x ws[1]) stands in the list as well."""
+    k = K.SEAM2
+    S = K.seam2_sizes(oracle)
+    g = oracle.geometry(k["H"], k["W"], k["wavelet"], k["level"], k["mode"])
+    assert (g["level"], g["hs"], g["ws"]) == (2, [17, 11, 8], [25, 15, 10])
+    rec, enc, approx, red, words = _library_sizes(k)
+    c = k["c"]
+    # the oracle's geometry and the library's say the same
+    assert enc == (g["enc_h"], g["enc_w"]) == (27, 35) and rec == (18, 26) and approx == (12, 16)
+    assert red[1] == ((12, 16), (11, 15)) and red[2] == ((8, 10), (8, 10)) and (g["ll_h"], g["ll_w"]) == (8, 10)
+    assert S == dict(picture=c * 17 * 25, rec=c * rec[0] * rec[1], array=c * enc[0] * enc[1], approx=c * approx[0] * approx[1],
+                     reduced1=c * red[1][0][0] * red[1][0][1], reduced2=c * red[2][0][0] * red[2][0][1],
+                     reduced1_int=c * red[1][1][0] * red[1][1][1])
+    assert S["approx"] == S["reduced1"]  # (one quantity by definition: see above)
+    different = [S[n] for n in ("picture", "rec", "array", "approx", "reduced2", "reduced1_int")]
+    assert len(set(different)) == len(different), S
+    assert len({S[n] for n in ("picture", "rec", "array", "reduced1", "reduced2", "reduced1_int")}) == 6, S
+    assert words > 0 and words == c  # one inverse tile per plane
+    # the batch, and the pictures that take turns in it
+    for distinct in (K.SEAM2_DISTINCT, K.SEAM_PER_DISTINCT):
+        assert _prime(distinct) and distinct >= 100 and (K.SEAM // 3) % distinct != 0 and 21845 % distinct != 0
+    assert K.chunks(K.CHUNK_B, c) == [(0, 21845), (21845, 7)]
+    which = K.in_turn(K.SEAM2_DISTINCT)
+    assert len(which) == K.CHUNK_B and which[21845] == 1 and which[0] == 0
+
+
+def test_the_second_seam_reference(oracle):
+    k, R = K.SEAM2, K.seam2_reference(oracle)
+    D, c = K.SEAM2_DISTINCT, k["c"]
+    P = K.seam_pictures(k, D)
+    assert P.shape == (D, c, 17, 25) and len(np.unique(P.reshape(D, -1), axis=0)) == D
+    assert R["coeffs"].shape == R["rec"].shape == R["coeffs_f32"].shape == (D, c, 27, 35)
+    assert R["pics"].shape == R["pics_fl"].shape == (D, c, 18, 26)
+    assert R["red"][1].shape == R["approx"].shape == (D, c, 12, 16) and R["red"][2].shape == (D, c, 8, 10)
+    assert all(not v.flags.writeable for v in list(R.values()) + list(R["red"].values()) if isinstance(v, np.ndarray))
+    # the budget cuts every stream short of lossless; distinct pictures give distinct streams
+    assert (R["nbits"] == k["max_bits"]).all() and (R["rec"] != R["coeffs"]).any(axis=(1, 2, 3)).all()
+    assert len(set(R["streams"])) == D and len(set(R["streams_f32"])) == D and (R["nbits_f32"] == k["max_bits"]).all()
+    # the single-precision transform is a reference of its own
+    assert (R["coeffs_f32"] != R["coeffs"]).any()
+    # about half the occupancy words are zero, and the pictures behind the seam need words the pictures at the front lack
+    assert R["words"].shape == (D, c, 1, 1)
+    zero = float((R["words"] == 0).mean())
+    assert 0.3 <= zero <= 0.7, zero
+    b0 = K.SEAM // 3
+    behind, front = K.in_turn(D)[b0:], K.in_turn(D)[:K.CHUNK_B - b0]
+    assert ((R["words"][behind] != 0) & (R["words"][front] == 0)).any()
+    assert (R["pics_fl"] != R["pics"]).any()  # (emptying the tiles changed pictures: the decoded arrays had level-1 details)
+    # the reduced pictures are not crops or copies of one another
+    assert np.array_equal(R["approx"], R["red"][1] * 2) and R["red"][1].std() > 0 and R["red"][2].std() > 0
+
+
+def test_the_two_pass_seam_reference(oracle):
+    k, R = K.SEAM_PER, K.seam_per_reference(oracle)
+    g = R["geom"]
+    taps = len(oracle.wavelet_filters(k["wavelet"])[0])
+    assert k["mode"] == "periodization" and 2 < taps <= 20  # the two-pass route of a filter the tiled kernels would take
+    assert (g["level"], g["hs"], g["ws"], g["enc_h"], g["enc_w"]) == (1, [9, 5], [13, 7], 10, 14)
+    rec, enc, approx, red, words = _library_sizes(k)
+    assert rec == (10, 14) and enc == (10, 14) and words == 0
+    assert k["H"] * k["W"] != rec[0] * rec[1]  # (the pixels and the array step by different sizes)
+    assert R["pics"].shape == (K.SEAM_PER_DISTINCT, 3, 10, 14) and "red" not in R
+    assert len(set(R["streams"])) == K.SEAM_PER_DISTINCT and (R["nbits"] == k["max_bits"]).all()
+
+
+def test_the_padded_views_differ_from_the_dense_ones_and_are_taken():
+    """every stride of K.padded_strides differs from dense HWC (what strided_hwc makes) and from dense CHW, and the library
+    takes the view as an output of every kind, for the full and for the reduced pictures"""
+    import ctypes as C
+    from spiht_amd import _lib, floatpx
+    L = _lib.lib()
+    B, c = K.CHUNK_B, 3
+    for H, W in ((17, 25), (11, 15), (8, 10), (9, 13)):
+        for es in (1, 2, 4):
+            st = K.padded_strides(c, H, W, es)
+            sb, sc, sh, sw = (int(v) for v in st)
+            assert sc == es and sw not in (c * es, es) and sh not in (W * c * es, W * es, W * sw) and sb not in (H * W * c * es, H * sh)
+            assert sw > c * es and sh > W * sw and sb > H * sh and all(v % es == 0 for v in (sb, sh, sw))
+            p = C.c_void_p(st.ctypes.data)
+            if es == 1:
+                assert L.spiht_check_view_u8(B, c, H, W, p, 1) == 0 and L.spiht_check_view_u8(B, c, H, W, p, 0) == 0
+            if es == 2:
+                assert L.spiht_check_view_u16(B, c, H, W, p, 1) == 0 and L.spiht_check_view_u16(B, c, H, W, p, 0) == 0
+            for kind in floatpx.KINDS:
+                if floatpx.itemsize(kind) == es:
+                    assert L.spiht_check_view_flt(kind, B, c, H, W, p, 1) == 0
+    # the buffer helpers: samples go where the strides say, and a byte written into the padding shows
+    buf, view, st = K.padded_buffer(5, 3, 4, 6, np.uint16)
+    assert buf.shape == (5, int(st[0]) // 2) and (buf.view(np.uint8) == K.PAD_BYTE).all() and K.padding_untouched(buf, 3, 4, 6)
+    view[...] = np.arange(5 * 3 * 4 * 6, dtype=np.uint16).reshape(5, 3, 4, 6)
+    flat = buf.reshape(-1)
+    for b, ch, y, x in ((0, 0, 0, 0), (4, 2, 3, 5), (1, 1, 2, 3)):
+        assert flat[(b * st[0] + ch * st[1] + y * st[2] + x * st[3]) // 2] == view[b, ch, y, x] == ((b * 3 + ch) * 4 + y) * 6 + x
+    assert K.padding_untouched(buf, 3, 4, 6)
+    for off in (3, int(st[3]) // 2 * 6, int(st[2]) // 2 * 4, buf.shape[1] - 1):  # alpha, row padding, spare row, last sample
+        bad = buf.copy()
+        bad[2, off] ^= 1
+        assert not K.padding_untouched(bad, 3, 4, 6), off
+
+
 def test_the_probe_and_the_dense_decode(oracle):
     imgs, streams, ns, pics, recs = K.probe_reference(oracle)
     assert imgs.shape == (2, 3, 70, 90) and pics.shape[:2] == (2, 3) and streams[0] != streams[1]
