@@ -955,6 +955,13 @@ int spiht_tile_blend_flt(spiht_ctx *ctx, int kind, const double *d_tiles, int64_
                          int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
                          int64_t x0, int64_t wh, int64_t ww, void *d_out, const int64_t *out_strides);
 
+/* How the tiled forward transform kernel addresses a level (host only, no device call): 1 when every plane the level reads or
+ * writes -- its float64 input in_h x in_w (px_es == 0) or the byte span of an 8- / 16-bit view with element size px_es and
+ * byte strides px_sh, px_sw; the packed array enc_h x enc_w; the approximation out_h x out_w -- is under 2^30 bytes, so that the
+ * kernel may use 32-bit offsets into per-plane buffer descriptors; 0: 64-bit addresses.  The results are the same bits. */
+int spiht_dwt_addr32(int64_t in_h, int64_t in_w, int64_t out_h, int64_t out_w, int64_t enc_h, int64_t enc_w, int px_es,
+                     int64_t px_sh, int64_t px_sw);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,7 @@ SYMBOLS = [
     "spiht_check_view_flt", "spiht_convert_batch_flt", "spiht_decode_image_batch_flt", "spiht_decode_image_host_flt",
     "spiht_dequant_idwt_flags_batch_flt", "spiht_dequant_idwt_reduced_batch_flt", "spiht_decode_image_reduced_batch_flt",
     "spiht_decode_image_reduced_host_flt", "spiht_tile_blend_flt", "spiht_tile_paste_f32s", "spiht_tile_mosaic_f32",
+    "spiht_dwt_addr32",
 ]
 
 

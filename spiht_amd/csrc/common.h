@@ -32,6 +32,35 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv &f) {
 }
 #endif
 
+// The same for any divisor d >= 1 (the general Granlund-Montgomery form: two shifts, so that d == 1 needs no case of its own):
+//   q = (t + ((n - t) >> s1)) >> s2,  t = mulhi(m, n);  exact for every 32-bit n
+struct FastDivU {
+    uint32_t m, s1, s2, d;
+};
+
+static inline FastDivU fastdivu_make(uint32_t d) {
+    FastDivU f;
+    if (d < 1) d = 1;
+    f.d = d;
+    uint32_t l = 0;
+    while ((1ull << l) < d) l++;  // ceil(log2 d), 0 ... 32
+    f.m = (uint32_t)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
+    f.s1 = l < 1 ? l : 1;
+    f.s2 = l < 1 ? 0 : l - 1;
+    return f;
+}
+static inline uint32_t fastdivu_host(uint32_t n, const FastDivU &f) {  // what fdivu computes, on the host (tools/fastdiv_check.cpp)
+    const uint32_t t = (uint32_t)(((uint64_t)f.m * n) >> 32);
+    return (t + ((n - t) >> f.s1)) >> f.s2;
+}
+
+#ifdef __HIPCC__
+__device__ __forceinline__ uint32_t fdivu(uint32_t n, const FastDivU &f) {
+    const uint32_t t = __umulhi(f.m, n);
+    return (t + ((n - t) >> f.s1)) >> f.s2;
+}
+#endif
+
 // Geometry of one coefficient array [c,h,w] with an ll_h x ll_w root block.
 struct Geom {
     int32_t c, h, w, ll_h, ll_w;
@@ -235,7 +264,37 @@ struct DwtKArgs {
     int32_t color, pad2;   // level 1 of a 3-channel image with the colour model change on its loads (k_dwt1_color)
     Color3 col;
     PxView px;             // level 1 of an 8- / 16-bit picture: the kernels' integer instantiations read it instead of `in`
+    // Launch-time constants of the tiled kernel k_dwt_level (set by its launcher, dwt.hip: dwt_set_launch_consts)
+    FastDivU dv_gx, dv_gy, dv_c;  // tile -> (bx, by, plane), plane -> (image, channel) without a division in the kernel
+    uint32_t gx, gy, nt;   // tiles per row, per column, in all
+    int32_t narrow;        // every plane the kernel touches spans less than 2^30 bytes: 32-bit offsets into plane descriptors
+    uint32_t in_pb;        // narrow: bytes per input plane (float64 input), per row, per column; an 8- / 16-bit view: its span and
+    uint32_t in_rb, in_cb; // its byte strides sh and sw
+    uint32_t co_pb, co_rb; // ... per plane and row of `coeffs`
+    uint32_t ll_pb, ll_rb; // ... of `ll_out`
+    uint32_t pad3;
 };
+
+// Whether k_dwt_level may address with 32-bit offsets (DwtKArgs::narrow): each plane it reads or writes -- the input (float64
+// in_h x in_w, or the byte span of an 8- / 16-bit view), the packed array, the approximation -- stays under 2^30 bytes, so that
+// the sum of a row offset and a column offset, either of which may be an out-of-range mark (2^31 for a row, 2^30 for a column),
+// neither wraps nor lands inside the plane.  Larger pictures take the 64-bit addressing.
+static inline bool dwt_narrow_ok(int64_t in_h, int64_t in_w, int64_t out_h, int64_t out_w, int64_t enc_h, int64_t enc_w, int px_es,
+                                 int64_t px_sh, int64_t px_sw) {
+    const int64_t lim = (int64_t)1 << 30;
+    if (in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || enc_h < 1 || enc_w < 1) return false;
+    if (in_h >= lim || in_w >= lim || out_h >= lim / 16 || out_w >= lim / 16 || enc_h >= lim || enc_w >= lim) return false;  // (no overflow below)
+    if (px_es) {
+        if (px_sh < 0 || px_sw < 0 || px_sh >= lim || px_sw >= lim) return false;
+        if ((in_h - 1) * px_sh + (in_w - 1) * px_sw + px_es >= lim) return false;
+    } else if (in_h * in_w * 8 >= lim) return false;
+    if (enc_h * enc_w * 4 >= lim) return false;
+    if (out_h * out_w * 8 >= lim) return false;
+    // a tile's rows below the last output row (at most DW_TH - 1 <= 64 of them) are addressed and dropped by the range check:
+    // their offsets, and an out-of-range mark advanced over a tile's rows, stay below 2^32
+    if ((out_h + 64) * enc_w * 4 >= 2 * lim || (out_h + 64) * out_w * 8 >= 2 * lim) return false;
+    return true;
+}
 
 // One inverse DWT level (dwt.hip)
 // Tile hand-out of the persistent inverse-transform kernel (k_idwt_level_pf): one counter per XCD in device memory,

@@ -36,8 +36,12 @@
 #define DW_TW 64      // output cols per tile
 #endif
 #define DW_BLOCK 256
+#ifndef DWF_STRAY
+#define DWF_STRAY 1    // k_dwt_level: the few input columns beyond the last full wavefront as (column, output row) items (dwt_tile)
+#endif
 #ifndef DWF_BLOCK
-#define DWF_BLOCK 192  // threads of a forward-transform workgroup (k_dwt_level); 132 of them hold an input column each.  Three
+#define DWF_BLOCK 192  // threads of a forward-transform workgroup (k_dwt_level); 132 input columns: 128 threads hold one each, the
+                       // other four are the third wavefront's items (DWF_STRAY).  Three
                        // wavefronts instead of four: beside a list-decoder workgroup (192 of a SIMD's 512 registers) FIVE of these
                        // workgroups fit a CU instead of four -- level 1 inside the pipelined step 6.3 instead of 6.55 ms, the step
                        // 16.4 instead of 16.7; alone 4.2 instead of 4.05 ms (round 4)
@@ -73,9 +77,23 @@ __device__ __forceinline__ void xcd_tile(uint32_t gx, uint32_t gy, uint32_t gz, 
 // front of this launch, so a look can return an OLD value of this launch's epoch (lower: a spare atomic) but never one
 // from before the zero-fill (higher: a lost maximum).  tests/test_gpu_dwt.py::test_maxabs_small_batch_after_large_batch
 // runs exactly the case that would show it: large magnitudes, then small ones, same context and buffer.
+// The wavefront's maximum, in its lane 63, by data-parallel-primitive moves inside the vector unit (six ds_bpermute round
+// trips, with their address arithmetic, were 64 instructions): neighbours, pairs, mirrored halves and rows leave every lane
+// of a row of 16 with the row's maximum; lane 15 of each row is then handed to the next row, lane 31 to the upper half.
+// All 64 lanes must be active.
+#define DPP_MAX_STEP(v, ctrl, rows) v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, rows, 0xF, false))
+__device__ __forceinline__ uint32_t wave_max_lane63(uint32_t v) {
+    DPP_MAX_STEP(v, 0xB1, 0xF);   // quad_perm [1,0,3,2]
+    DPP_MAX_STEP(v, 0x4E, 0xF);   // quad_perm [2,3,0,1]
+    DPP_MAX_STEP(v, 0x141, 0xF);  // row_half_mirror
+    DPP_MAX_STEP(v, 0x140, 0xF);  // row_mirror
+    DPP_MAX_STEP(v, 0x142, 0xA);  // row_bcast:15 into rows 1 and 3 (a row left out takes 0: no change)
+    DPP_MAX_STEP(v, 0x143, 0xC);  // row_bcast:31 into rows 2 and 3
+    return v;
+}
 __device__ __forceinline__ void block_raise_max(uint32_t *p, uint32_t v, uint32_t *s_m) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-    if ((threadIdx.x & 63) == 0 && v) atomicMax(s_m, v);
+    v = wave_max_lane63(v);
+    if ((threadIdx.x & 63) == 63 && v) atomicMax(s_m, v);
     __syncthreads();
     if (threadIdx.x == 0) {
         const uint32_t m = *s_m;
@@ -99,23 +117,33 @@ __device__ __forceinline__ void wave_raise_max(uint32_t *maxabs, int img, uint32
     }
 }
 
+// i mod P for P > 0, in [0, P).  An index within one period either side of [0, P) -- every index a tile asks for when the
+// picture is at least as long as the filter -- takes an add or a subtract; the software division runs only for the rest
+// (pictures shorter than the filter, the unused rows of a tile far below a short picture).
+__device__ __forceinline__ int ext_mod(int i, int P) {
+    int m = i < 0 ? i + P : i;
+    if (m >= P) m -= P;
+    if ((unsigned)m >= (unsigned)P) {
+        m = i % P; if (m < 0) m += P;
+    }
+    return m;
+}
 __device__ __forceinline__ int ext_index(int i, int N, int mode) {
     if (i >= 0 && i < N) return i;
     switch (mode) {
     case 0: {  // reflect (whole-sample symmetric)
         if (N == 1) return 0;
         int P = 2 * (N - 1);
-        int m = i % P; if (m < 0) m += P;
+        int m = ext_mod(i, P);
         return m < N ? m : P - m;
     }
     case 1: {  // symmetric (half-sample)
         int P = 2 * N;
-        int m = i % P; if (m < 0) m += P;
+        int m = ext_mod(i, P);
         return m < N ? m : P - 1 - m;
     }
     case 2: {  // periodic
-        int m = i % N; if (m < 0) m += N;
-        return m;
+        return ext_mod(i, N);
     }
     case 4: return i < 0 ? 0 : N - 1;  // constant
     default: return -1;                 // zero
@@ -193,40 +221,118 @@ template <int PX> __device__ __forceinline__ double px_value(uint32_t raw) {
         else (p)[o] = px8_store_value(v);                                                   \
     } while (0)
 
+// ---- plane descriptors and LDS barrier of the tiled forward kernel and the persistent inverse kernel -----------------
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// a barrier that waits for LDS traffic only: __syncthreads() would wait for the global loads in flight as well
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+#define BUF_OOB 0x80000000u  // an offset no plane reaches (the launcher checks): dropped by the descriptor's range check
+// Buffer descriptor of `bytes` bytes at p.  p and bytes are workgroup-uniform, but a value that went through a VALU
+// division is a VGPR to the instruction selector, and a descriptor in VGPRs costs a waterfall loop per memory
+// instruction: its words are read back as scalars here, once.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void *p, uint32_t bytes) {
+    const uint64_t v = (uint64_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, (int)__builtin_amdgcn_readfirstlane(bytes),
+                                             0x00020000);
+}
+
+// ---- the tiled forward level ---------------------------------------------------------------------------------------
+// Tile -> (bx, by, plane) of k_dwt_level in the XCD order of xcd_tile_at, with the launcher's multipliers instead of the
+// two divisions (DwtKArgs::dv_gx, dv_gy: exact for every 32-bit tile index, so the same coordinates for every grid).
+__device__ __forceinline__ void xcd_tile_fd(uint32_t L, const DwtKArgs &a, uint32_t &bx, uint32_t &by, uint32_t &bz) {
+    const uint32_t q = a.nt >> 3, r = a.nt & 7u, x = L & 7u, j = L >> 3;
+    const uint32_t T = x * q + (x < r ? x : r) + j;
+    const uint32_t t2 = fdivu(T, a.dv_gx);
+    bx = T - t2 * a.gx;
+    bz = fdivu(t2, a.dv_gy);
+    by = t2 - bz * a.gy;
+}
+#define OOB_ROW BUF_OOB      // row offset of a row of zeros (zero padding) ...
+#define OOB_COL 0x40000000u  // ... column offset of a column of zeros: with planes under 2^30 bytes (dwt_narrow_ok) the sum
+                             // of a row and a column offset is past the plane's end as soon as one of the two is a mark,
+                             // and the load returns zero
+
 // grid: (ceil(out_w/TW), ceil(out_h/TH), planes).  LOM / HIM: bit j set = tap j of dec_lo / dec_hi is non-zero;
 // a zero tap contributes exactly nothing (0*x added to the running sum), so skipping it changes no bit and
 // removes a third (bior2.2) to a fifth of the float64 arithmetic.
 // One tile of k_dwt_level.
 // PX != PX_F64: the level's input is the strided 8- or 16-bit picture a.px (common.h: PxView), converted on the loads.
-template <int F, uint32_t LOM, uint32_t HIM, int PS, int NR, int PX = PX_F64>
+// WIDE == false (the launcher's choice, dwt_narrow_ok: every plane under 2^30 bytes): the input plane, the packed array's
+// plane and the approximation's plane are addressed through buffer descriptors with 32-bit byte offsets -- a load is one LDS
+// word (the row's offset) + the lane's column offset, a store is an offset advanced by a launch-time constant, and rows and
+// columns outside the level fall to the descriptors' range check.  WIDE == true: 64-bit addresses formed per access, for
+// planes of any size.
+template <int F, uint32_t LOM, uint32_t HIM, int PS, int NR, int PX = PX_F64, bool WIDE = false>
 __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS], double (&s_hi)[2][PS], uint32_t tbx, uint32_t tby,
                                          uint32_t tbz) {
     constexpr int NC = 2 * DW_TW + F - 2;  // input columns needed by the tile
     constexpr int HC = (NC + 1) / 2;       // columns per parity plane
     static_assert(NC <= DWF_BLOCK, "one thread per input column");
     static_assert(NR == 2 * DW_TH + F - 2, "input rows needed");
+    static_assert(DW_TH <= 64, "dwt_narrow_ok allows for 64 rows below the level's last");
     constexpr int RS = HC + 1;
-    const int plane = (int)tbz;
+    constexpr int NRP = (NR + 3) & ~3;     // row offsets in LDS, read four at a time
+    const uint32_t plane = tbz;
+    const uint32_t img = fdivu(plane, a.dv_c), k = plane - img * (uint32_t)a.c;
     const int oh0 = (int)tby * DW_TH, ow0 = (int)tbx * DW_TW;
-    const double *__restrict__ in = PX ? nullptr : a.in + (size_t)plane * a.in_h * a.in_w;
-    // (the plane base in 64 bits, from the tile coordinates in vector registers: see below)
-    const uint8_t *__restrict__ in8 = PX ? a.px.in + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
     const int tid = threadIdx.x;
 
     // input row needed for output row o, tap j: 2*o + 1 - j ; first needed row r0 = 2*oh0 + 1 - (F-1)
     const int r0 = 2 * oh0 + 2 - F, c0 = 2 * ow0 + 2 - F;
-    // the rows' element offsets (row index * in_w; -1: a row of zeros), worked out once per tile by NR threads
-    __shared__ long long s_off[NR];
+    // the rows' offsets, worked out once per tile by NR threads.  Narrow: bytes from the plane's start (OOB_ROW: a row of
+    // zeros); wide: elements / bytes as 64-bit numbers (-1: a row of zeros)
+    __shared__ __attribute__((aligned(16))) uint32_t s_off[WIDE ? 4 : NRP];
+    __shared__ long long s_off64[WIDE ? NR : 1];
     if (tid < NR) {
         const int gr = ext_index(r0 + tid, a.in_h, a.mode);
-        s_off[tid] = gr < 0 ? -1ll : (long long)gr * (PX ? a.px.sh : (long long)a.in_w);
+        if constexpr (WIDE) s_off64[tid] = gr < 0 ? -1ll : (long long)gr * (PX ? a.px.sh : (long long)a.in_w);
+        else s_off[tid] = gr < 0 ? OOB_ROW : (uint32_t)gr * a.in_rb;
     }
     __shared__ uint32_t s_amax;
     if (tid == 0) s_amax = 0;
     __syncthreads();
 
     // ---- axis -2: thread <-> input column; all loads first, then the filter ----
-    if (tid < NC) {
+    // The columns beyond the last full wavefront (NC - 128 = F - 2 of them) would have a wavefront issue the whole phase for a
+    // few live lanes.  Where they fit (DWF_STRAY), that wavefront instead spreads them over its lanes as (column, output row)
+    // items: an item loads its own F rows and adds the same taps in the same ascending order -- the same bits.
+    constexpr int NFULL = NC / 64 * 64, NS = NC - NFULL;
+    constexpr bool STRAY = DWF_STRAY && !WIDE && NS > 0 && NS * DW_TH <= 64;
+    if constexpr (STRAY) {
+        const int it = tid - NFULL;
+        if (it >= 0 && it < NS * DW_TH) {
+            const int o = it / NS, sc = NFULL + it % NS;
+            const int gc = ext_index(c0 + sc, a.in_w, a.mode);
+            const uint8_t *pb = PX ? a.px.in + (int64_t)img * a.px.sb + (int64_t)k * a.px.sc
+                                   : reinterpret_cast<const uint8_t *>(a.in) + (uint64_t)plane * a.in_pb;
+            const __amdgpu_buffer_rsrc_t rs_in = plane_rsrc(pb, a.in_pb);
+            const uint32_t cb = gc < 0 ? OOB_COL : (uint32_t)gc * (PX ? a.in_cb : 8u);
+            double x[F];
+            if constexpr (PX != PX_F64) {
+                uint32_t raw[F];
+#pragma unroll
+                for (int t = 0; t < F; t++) {
+                    if constexpr (PX == PX_U16) raw[t] = __builtin_amdgcn_raw_buffer_load_b16(rs_in, s_off[2 * o + t] + cb, 0, 0);
+                    else raw[t] = __builtin_amdgcn_raw_buffer_load_b8(rs_in, s_off[2 * o + t] + cb, 0, 0);
+                }
+#pragma unroll
+                for (int t = 0; t < F; t++) x[t] = px_value<PX>(raw[t]);
+            } else {
+#pragma unroll
+                for (int t = 0; t < F; t++)
+                    x[t] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs_in, s_off[2 * o + t] + cb, 0, 0));
+            }
+            double sl = 0.0, shh = 0.0;
+#pragma unroll
+            for (int j = 0; j < F; j++) {
+                if ((LOM >> j) & 1u) sl += a.lo[j] * x[F - 1 - j];
+                if ((HIM >> j) & 1u) shh += a.hi[j] * x[F - 1 - j];
+            }
+            s_lo[sc & 1][o * RS + (sc >> 1)] = sl;
+            s_hi[sc & 1][o * RS + (sc >> 1)] = shh;
+        }
+    }
+    if (tid < (STRAY ? NFULL : NC)) {
         const int gc = ext_index(c0 + tid, a.in_w, a.mode);
         double x[NR];
         // Nothing of the address arithmetic on the scalar unit: a list-coding workgroup on the same CU keeps that unit busy
@@ -236,32 +342,72 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
         // through an index the compiler cannot prove uniform, so that they stay in vector registers.
         int lz = 0;
         asm volatile("" : "+v"(lz));
-        if (PX) {  // byte / 16-bit loads at the same row offsets, ALL of them first (converted one by one behind its load,
-                   // the compiler waited for each load before it issued the next: level 1 took 7.1 instead of 4.3 ms),
-                   // then k -> k / 255.0 (k / 65535.0)
-            const long long co8 = gc < 0 ? 0 : (long long)gc * a.px.sw;
-            uint32_t raw[NR];
-            static_assert(NR <= 64, "one bit per row");
-            uint64_t okm = 0;  // bit r: row r is inside the picture (zero padding: a zero sample otherwise)
+        if constexpr (!WIDE) {
+            // the plane's base in 64 bits once (from the tile coordinates in vector registers, read back as scalars into the
+            // descriptor); per row one add of two 32-bit offsets.  Zero padding needs no case of its own: a marked row or
+            // column is out of the descriptor's range and loads as 0, which is 0.0 (and the pixel 0 / 255 = 0.0).
+            const uint8_t *pb = PX ? a.px.in + (int64_t)img * a.px.sb + (int64_t)k * a.px.sc
+                                   : reinterpret_cast<const uint8_t *>(a.in) + (uint64_t)plane * a.in_pb;
+            const __amdgpu_buffer_rsrc_t rs_in = plane_rsrc(pb, a.in_pb);
+            const uint32_t cb = gc < 0 ? OOB_COL : (uint32_t)gc * (PX ? a.in_cb : 8u);
+            const uint4 *so = reinterpret_cast<const uint4 *>(s_off) + lz;
+            if constexpr (PX != PX_F64) {  // byte / 16-bit loads, ALL of them first (converted one by one behind its load, the
+                                           // compiler waited for each load before it issued the next: level 1 took 7.1
+                                           // instead of 4.3 ms), then k -> k / 255.0 (k / 65535.0)
+                uint32_t raw[NRP];
 #pragma unroll
-            for (int r = 0; r < NR; r++) {
-                const long long off = s_off[r + lz];
-                const bool ok = a.mode != 3 || (gc >= 0 && off >= 0);
-                okm |= (ok ? 1ull : 0ull) << r;
-                raw[r] = px_load<PX>(in8 + (ok ? off + co8 : 0));
+                for (int q = 0; q < NRP / 4; q++) {
+                    const uint4 o4 = so[q];
+                    const uint32_t o[4] = {o4.x, o4.y, o4.z, o4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        if (4 * q + e >= NR) continue;
+                        if constexpr (PX == PX_U16) raw[4 * q + e] = __builtin_amdgcn_raw_buffer_load_b16(rs_in, o[e] + cb, 0, 0);
+                        else raw[4 * q + e] = __builtin_amdgcn_raw_buffer_load_b8(rs_in, o[e] + cb, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < NR; r++) x[r] = px_value<PX>(raw[r]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < NRP / 4; q++) {
+                    const uint4 o4 = so[q];
+                    const uint32_t o[4] = {o4.x, o4.y, o4.z, o4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        if (4 * q + e >= NR) continue;
+                        x[4 * q + e] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs_in, o[e] + cb, 0, 0));
+                    }
+                }
             }
-#pragma unroll
-            for (int r = 0; r < NR; r++) x[r] = ((okm >> r) & 1ull) ? px_value<PX>(raw[r]) : 0.0;
-        } else if (a.mode != 3) {  // not zero padding: every index is inside the picture
-#pragma unroll
-            for (int r = 0; r < NR; r++) x[r] = in[s_off[r + lz] + gc];
         } else {
+            const double *__restrict__ in = PX ? nullptr : a.in + (size_t)plane * a.in_h * a.in_w;
+            const uint8_t *__restrict__ in8 = PX ? a.px.in + (int64_t)img * a.px.sb + (int64_t)k * a.px.sc : nullptr;
+            if (PX) {
+                const long long co8 = gc < 0 ? 0 : (long long)gc * a.px.sw;
+                uint32_t raw[NR];
+                static_assert(NR <= 64, "one bit per row");
+                uint64_t okm = 0;  // bit r: row r is inside the picture (zero padding: a zero sample otherwise)
 #pragma unroll
-            for (int r = 0; r < NR; r++) {
-                const long long off = s_off[r + lz];
-                const bool ok = gc >= 0 && off >= 0;
-                const double v = in[ok ? off + gc : 0];
-                x[r] = ok ? v : 0.0;
+                for (int r = 0; r < NR; r++) {
+                    const long long off = s_off64[r + lz];
+                    const bool ok = a.mode != 3 || (gc >= 0 && off >= 0);
+                    okm |= (ok ? 1ull : 0ull) << r;
+                    raw[r] = px_load<PX>(in8 + (ok ? off + co8 : 0));
+                }
+#pragma unroll
+                for (int r = 0; r < NR; r++) x[r] = ((okm >> r) & 1ull) ? px_value<PX>(raw[r]) : 0.0;
+            } else if (a.mode != 3) {  // not zero padding: every index is inside the picture
+#pragma unroll
+                for (int r = 0; r < NR; r++) x[r] = in[s_off64[r + lz] + gc];
+            } else {
+#pragma unroll
+                for (int r = 0; r < NR; r++) {
+                    const long long off = s_off64[r + lz];
+                    const bool ok = gc >= 0 && off >= 0;
+                    const double v = in[ok ? off + gc : 0];
+                    x[r] = ok ? v : 0.0;
+                }
             }
         }
         const int par = tid & 1, hc = tid >> 1;
@@ -281,50 +427,103 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
     __syncthreads();
 
     // ---- axis -1 from LDS; 4 sub-bands per output position ----
-    const int k = plane % a.c;
     const bool has_m = a.mults != nullptr;
     const double mk = has_m ? a.mults[k] : 1.0;
-    int32_t *__restrict__ co = a.coeffs + (size_t)plane * a.enc_h * a.enc_w;
-    double *__restrict__ llo = a.last ? nullptr : a.ll_out + (size_t)plane * a.out_h * a.out_w;
     uint32_t amax = 0;
     constexpr int NU = (DW_TH * DW_TW + DWF_BLOCK - 1) / DWF_BLOCK;  // output positions per thread
-#pragma unroll
-    for (int u = 0; u < NU; u++) {
-        const int p = tid + u * DWF_BLOCK;
-        const int o = p / DW_TW, wcol = p % DW_TW;
-        const int oh = oh0 + o, ow = ow0 + wcol;
-        if (o >= DW_TH || oh >= a.out_h || ow >= a.out_w) continue;
-        // x~ index 2*ow+1-j  ->  tile column 2*wcol + F-1-j  ->  parity (F-1-j)&1, half-column wcol + (F-1-j)/2
-        double aa = 0.0, ad = 0.0, da = 0.0, dd = 0.0;
-#pragma unroll
-        for (int j = 0; j < F; j++) {
-            const double vl = s_lo[(F - 1 - j) & 1][o * RS + wcol + ((F - 1 - j) >> 1)];
-            const double vh = s_hi[(F - 1 - j) & 1][o * RS + wcol + ((F - 1 - j) >> 1)];
-            if ((LOM >> j) & 1u) { aa += a.lo[j] * vl; da += a.lo[j] * vh; }
-            if ((HIM >> j) & 1u) { ad += a.hi[j] * vl; dd += a.hi[j] * vh; }
-        }
-        const int32_t qad = quant(ad, mk, a.q, has_m), qda = quant(da, mk, a.q, has_m), qdd = quant(dd, mk, a.q, has_m);
+    if constexpr (!WIDE) {
+        // A thread's outputs lie in one column, DWF_BLOCK / DW_TW rows apart: the offset of the first is worked out once (the
+        // same offset serves the top and the bottom bands: their descriptors start off_h rows apart, and the 'ad' / 'dd'
+        // column offset is the instruction's scalar offset), the others follow by a constant.  The descriptors end with the
+        // level's last row, so a tile's rows below it are dropped by the range check; a thread right of the last column
+        // starts from the out-of-range mark and stays out of range.
+        static_assert(DWF_BLOCK % DW_TW == 0 && (DW_TH * DW_TW) % DWF_BLOCK == 0, "a thread keeps its column; whole steps");
+        constexpr int RSTEP = DWF_BLOCK / DW_TW;
+        const int o0 = tid / DW_TW, wcol = tid % DW_TW;
+        const int oh = oh0 + o0, ow = ow0 + wcol;
+        const bool colok = ow < a.out_w;
+        uint32_t vco = colok ? (uint32_t)oh * a.co_rb + (uint32_t)ow * 4u : BUF_OOB;
+        uint32_t vll = colok ? (uint32_t)oh * a.ll_rb + (uint32_t)ow * 8u : BUF_OOB;
+        uint8_t *cob = reinterpret_cast<uint8_t *>(a.coeffs) + (uint64_t)plane * a.co_pb;
+        const uint32_t band_bytes = (uint32_t)a.out_h * a.co_rb;
+        const __amdgpu_buffer_rsrc_t rs_top = plane_rsrc(cob, band_bytes);
+        const __amdgpu_buffer_rsrc_t rs_bot = plane_rsrc(cob + (uint64_t)(uint32_t)a.off_h * a.co_rb, band_bytes);
+        const __amdgpu_buffer_rsrc_t rs_ll =
+            plane_rsrc(reinterpret_cast<uint8_t *>(a.ll_out) + (uint64_t)plane * a.ll_pb, a.last ? 0u : (uint32_t)a.out_h * a.ll_rb);
+        const uint32_t so_w = (uint32_t)a.off_w * 4u;
         // the few outputs of the bottom / right overhang whose sum depends on PyWavelets' tap order are computed again
-        // by k_dwt_edge, which overwrites them and accounts for their magnitude
-        const bool mine = oh < a.ov_h && ow < a.ov_w;
-        if (a.last) {
-            const int32_t qaa = quant(aa, mk, a.q, has_m);
-            co[(size_t)oh * a.enc_w + ow] = qaa;
-            if (mine) amax = max(amax, iabs_u(qaa));
-        } else {
-            llo[(size_t)oh * a.out_w + ow] = aa;
+        // by k_dwt_edge, which overwrites them and accounts for their magnitude (ov_h <= out_h, ov_w <= out_w: an output
+        // counted here is inside the level)
+        const int mine_rows = ow < a.ov_w ? a.ov_h - oh : 0;  // output u is this kernel's to account for: u * RSTEP < mine_rows
+#pragma unroll
+        for (int u = 0; u < NU; u++) {
+            const int o = o0 + u * RSTEP;
+            // x~ index 2*ow+1-j  ->  tile column 2*wcol + F-1-j  ->  parity (F-1-j)&1, half-column wcol + (F-1-j)/2
+            double aa = 0.0, ad = 0.0, da = 0.0, dd = 0.0;
+#pragma unroll
+            for (int j = 0; j < F; j++) {
+                const double vl = s_lo[(F - 1 - j) & 1][o * RS + wcol + ((F - 1 - j) >> 1)];
+                const double vh = s_hi[(F - 1 - j) & 1][o * RS + wcol + ((F - 1 - j) >> 1)];
+                if ((LOM >> j) & 1u) { aa += a.lo[j] * vl; da += a.lo[j] * vh; }
+                if ((HIM >> j) & 1u) { ad += a.hi[j] * vl; dd += a.hi[j] * vh; }
+            }
+            // (the channel scale is multiplied in whether there is one or not: without one mk is 1.0 and 1.0 * v is v in every
+            // bit -- the product was computed either way, and picking between v and mk * v cost two selects a value)
+            const int32_t qad = quant(ad, mk, a.q, true), qda = quant(da, mk, a.q, true), qdd = quant(dd, mk, a.q, true);
+            uint32_t m = max(iabs_u(qad), max(iabs_u(qda), iabs_u(qdd)));
+            if (a.last) {
+                const int32_t qaa = quant(aa, mk, a.q, true);
+                __builtin_amdgcn_raw_buffer_store_b32((uint32_t)qaa, rs_top, vco, 0, 0);
+                m = max(m, iabs_u(qaa));
+            } else {
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, aa), rs_ll, vll, 0, 0);
+            }
+            __builtin_amdgcn_raw_buffer_store_b32((uint32_t)qad, rs_top, vco, so_w, 0);  // 'ad' top-right
+            __builtin_amdgcn_raw_buffer_store_b32((uint32_t)qda, rs_bot, vco, 0, 0);     // 'da' bottom-left
+            __builtin_amdgcn_raw_buffer_store_b32((uint32_t)qdd, rs_bot, vco, so_w, 0);  // 'dd' bottom-right
+            amax = max(amax, u * RSTEP < mine_rows ? m : 0u);
+            vco += (uint32_t)RSTEP * a.co_rb;
+            vll += (uint32_t)RSTEP * a.ll_rb;
         }
-        co[(size_t)oh * a.enc_w + a.off_w + ow] = qad;                 // 'ad' top-right
-        co[(size_t)(a.off_h + oh) * a.enc_w + ow] = qda;               // 'da' bottom-left
-        co[(size_t)(a.off_h + oh) * a.enc_w + a.off_w + ow] = qdd;     // 'dd' bottom-right
-        if (mine) amax = max(amax, max(iabs_u(qad), max(iabs_u(qda), iabs_u(qdd))));
+    } else {
+        int32_t *__restrict__ co = a.coeffs + (size_t)plane * a.enc_h * a.enc_w;
+        double *__restrict__ llo = a.last ? nullptr : a.ll_out + (size_t)plane * a.out_h * a.out_w;
+#pragma unroll
+        for (int u = 0; u < NU; u++) {
+            const int p = tid + u * DWF_BLOCK;
+            const int o = p / DW_TW, wcol = p % DW_TW;
+            const int oh = oh0 + o, ow = ow0 + wcol;
+            if (o >= DW_TH || oh >= a.out_h || ow >= a.out_w) continue;
+            double aa = 0.0, ad = 0.0, da = 0.0, dd = 0.0;
+#pragma unroll
+            for (int j = 0; j < F; j++) {
+                const double vl = s_lo[(F - 1 - j) & 1][o * RS + wcol + ((F - 1 - j) >> 1)];
+                const double vh = s_hi[(F - 1 - j) & 1][o * RS + wcol + ((F - 1 - j) >> 1)];
+                if ((LOM >> j) & 1u) { aa += a.lo[j] * vl; da += a.lo[j] * vh; }
+                if ((HIM >> j) & 1u) { ad += a.hi[j] * vl; dd += a.hi[j] * vh; }
+            }
+            const int32_t qad = quant(ad, mk, a.q, has_m), qda = quant(da, mk, a.q, has_m), qdd = quant(dd, mk, a.q, has_m);
+            const bool mine = oh < a.ov_h && ow < a.ov_w;
+            if (a.last) {
+                const int32_t qaa = quant(aa, mk, a.q, has_m);
+                co[(size_t)oh * a.enc_w + ow] = qaa;
+                if (mine) amax = max(amax, iabs_u(qaa));
+            } else {
+                llo[(size_t)oh * a.out_w + ow] = aa;
+            }
+            co[(size_t)oh * a.enc_w + a.off_w + ow] = qad;                 // 'ad' top-right
+            co[(size_t)(a.off_h + oh) * a.enc_w + ow] = qda;               // 'da' bottom-left
+            co[(size_t)(a.off_h + oh) * a.enc_w + a.off_w + ow] = qdd;     // 'dd' bottom-right
+            if (mine) amax = max(amax, max(iabs_u(qad), max(iabs_u(qda), iabs_u(qdd))));
+        }
     }
     if (a.maxabs != nullptr) {
-        block_raise_max(&a.maxabs[plane / a.c], amax, &s_amax);
+        block_raise_max(&a.maxabs[img], amax, &s_amax);
     }
 }
 
-template <int F, uint32_t LOM, uint32_t HIM, int PX = PX_F64>  // PX_U8 / PX_U16: level 1 of an 8- / 16-bit picture (a.px; a.in unused)
+// PX_U8 / PX_U16: level 1 of an 8- / 16-bit picture (a.px; a.in unused).  WIDE: see dwt_tile
+template <int F, uint32_t LOM, uint32_t HIM, int PX = PX_F64, bool WIDE = false>
 __global__ __launch_bounds__(DWF_BLOCK) void k_dwt_level(DwtKArgs a) {
     constexpr int NC = 2 * DW_TW + F - 2, NR = 2 * DW_TH + F - 2, HC = (NC + 1) / 2;
     // two column-parity planes; the padding makes the plane stride an odd multiple of 16 banks, so the even and odd
@@ -333,27 +532,12 @@ __global__ __launch_bounds__(DWF_BLOCK) void k_dwt_level(DwtKArgs a) {
     __shared__ double s_lo[2][PS];
     __shared__ double s_hi[2][PS];
     uint32_t tbx, tby, tbz;
-    // the tile's coordinates worked out in vector registers (every lane the same values): the two divisions and everything
-    // that follows from them -- plane, origin, the base pointers -- then cost the scalar unit nothing (see dwt_tile)
+    // the tile's coordinates worked out in vector registers (every lane the same values): they and everything that follows
+    // from them -- plane, origin, the base pointers -- then cost the scalar unit nothing (see dwt_tile)
     uint32_t lin = blockIdx.x;
     asm volatile("" : "+v"(lin));
-    xcd_tile_at(lin, (a.out_w + DW_TW - 1) / DW_TW, (a.out_h + DW_TH - 1) / DW_TH, a.planes, tbx, tby, tbz);
-    dwt_tile<F, LOM, HIM, PS, NR, PX>(a, s_lo, s_hi, tbx, tby, tbz);
-}
-
-// ---- helpers of the persistent inverse-transform kernel (k_idwt_level_pf) -------------------------------------------
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-// a barrier that waits for LDS traffic only: __syncthreads() would wait for the global loads in flight as well
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#define BUF_OOB 0x80000000u  // an offset no plane reaches (the launcher checks): dropped by the descriptor's range check
-// Buffer descriptor of `bytes` bytes at p.  p and bytes are workgroup-uniform, but a value that went through a VALU
-// division is a VGPR to the instruction selector, and a descriptor in VGPRs costs a waterfall loop per memory
-// instruction: its words are read back as scalars here, once.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void *p, uint32_t bytes) {
-    const uint64_t v = (uint64_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, (int)__builtin_amdgcn_readfirstlane(bytes),
-                                             0x00020000);
+    xcd_tile_fd(lin, a, tbx, tby, tbz);
+    dwt_tile<F, LOM, HIM, PS, NR, PX, WIDE>(a, s_lo, s_hi, tbx, tby, tbz);
 }
 
 // ---- the bottom / right overhang of a float64 level, in PyWavelets' summation order -----------------------------
@@ -1626,6 +1810,36 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
 
 // ---- host launchers -----------------------------------------------------------------------------
 
+// The launch-time constants of k_dwt_level (common.h: DwtKArgs): the tile grid with its division multipliers, and the choice
+// of addressing -- 32-bit offsets into plane descriptors where every plane is small enough for them (dwt_narrow_ok), the 64-bit
+// addressing otherwise (or when SPIHT_DWT_ADDR64 is set to a non-zero number: the tests run small pictures through it).
+// Returns the number of tiles.
+extern "C" int spiht_dwt_addr32(int64_t in_h, int64_t in_w, int64_t out_h, int64_t out_w, int64_t enc_h, int64_t enc_w, int px_es,
+                                int64_t px_sh, int64_t px_sw) {
+    return dwt_narrow_ok(in_h, in_w, out_h, out_w, enc_h, enc_w, px_es, px_sh, px_sw) ? 1 : 0;
+}
+static uint32_t dwt_set_launch_consts(DwtKArgs &a, int planes, int px) {
+    a.gx = (uint32_t)((a.out_w + DW_TW - 1) / DW_TW);
+    a.gy = (uint32_t)((a.out_h + DW_TH - 1) / DW_TH);
+    a.nt = a.gx * a.gy * (uint32_t)planes;
+    a.dv_gx = fastdivu_make(a.gx);
+    a.dv_gy = fastdivu_make(a.gy);
+    a.dv_c = fastdivu_make((uint32_t)a.c);
+    const char *force = getenv("SPIHT_DWT_ADDR64");
+    a.narrow = spiht_dwt_addr32(a.in_h, a.in_w, a.out_h, a.out_w, a.enc_h, a.enc_w, px ? a.px.es : 0, a.px.sh, a.px.sw) &&
+               !(force && atoi(force) != 0);
+    if (a.narrow) {
+        a.in_pb = px ? (uint32_t)((a.in_h - 1) * a.px.sh + (a.in_w - 1) * a.px.sw + a.px.es) : (uint32_t)a.in_h * (uint32_t)a.in_w * 8u;
+        a.in_rb = px ? (uint32_t)a.px.sh : (uint32_t)a.in_w * 8u;
+        a.in_cb = px ? (uint32_t)a.px.sw : 8u;
+        a.co_pb = (uint32_t)a.enc_h * (uint32_t)a.enc_w * 4u;
+        a.co_rb = (uint32_t)a.enc_w * 4u;
+        a.ll_pb = (uint32_t)a.out_h * (uint32_t)a.out_w * 8u;
+        a.ll_rb = (uint32_t)a.out_w * 8u;
+    }
+    return a.nt;
+}
+
 // a.px.in set: level 1 of an 8- or 16-bit picture (the kernels of the kind a.px.es names; a.in unused)
 template <int F, uint32_t LOM, uint32_t HIM>
 static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
@@ -1659,10 +1873,16 @@ static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
     while (z < F && a.lo[z] == 0.0 && a.hi[z] == 0.0) z++;
     if (a.mode != 4) a.ov_h = min(a.out_h, (a.in_h + z + 2) / 2);
     if (a.mode != 4) a.ov_w = min(a.out_w, (a.in_w + z + 2) / 2);
-    const uint32_t nt = (uint32_t)((a.out_w + DW_TW - 1) / DW_TW) * (uint32_t)((a.out_h + DW_TH - 1) / DW_TH) * (uint32_t)planes;
-    if (px == PX_U16) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U16>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
-    else if (px == PX_U8) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U8>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+    const uint32_t nt = dwt_set_launch_consts(a, planes, px);
+    if (a.narrow) {
+        if (px == PX_U16) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U16>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+        else if (px == PX_U8) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U8>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+    } else {
+        if (px == PX_U16) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U16, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+        else if (px == PX_U8) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U8, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_F64, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+    }
     const int n_edge = (a.out_h - a.ov_h) * a.out_w + a.ov_h * (a.out_w - a.ov_w);
     if (n_edge > 0) {
         if (px == PX_U16) hipLaunchKernelGGL((k_dwt_edge<F, PX_U16>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
