@@ -955,8 +955,60 @@ int spiht_tile_blend_flt(spiht_ctx *ctx, int kind, const double *d_tiles, int64_
                          int64_t th, int64_t tw, int64_t m, int64_t i0, int64_t i1, int64_t j0, int64_t j1, int64_t y0,
                          int64_t x0, int64_t wh, int64_t ww, void *d_out, const int64_t *out_strides);
 
+/* ---------------------------------------------------------------------------------------
+ * Float pixels in (*_flt, the encode side): float32, float16 or bfloat16 pictures coded as they lie, by the float64 codec.
+ *
+ * Each call is its *_u16 sibling with `kind` (as above) behind the context and a void picture pointer: the same view by BYTE
+ * strides (non-negative multiples of the element size, 4 or 2; the base aligned to the element; NULL: dense CHW), the same
+ * statuses, asynchrony and chunking at 65535 planes; refusals (spiht_check_view_flt(kind, .., 0), an unaligned base, an
+ * unknown kind) happen before any launch.  Every sample is WIDENED EXACTLY to float64 on the loads of forward level 1 --
+ * float32 by the hardware's conversion, float16 as half -> float -> double, bfloat16 as the upper half of a float32; nothing
+ * is scaled and nothing is clipped, subnormals of every kind keep their value -- and everything behind the loads is the
+ * float64 path.  So every call returns, field by field and bit for bit, what its *_f64 sibling returns for the widened
+ * picture (spiht_amd/floatpx.py: to_float64; csrc/floatpx.h: flt_load_value), with every feature of the float64 codec: the
+ * colour model, every mode and wavelet, tiles, allocation, region of interest, target PSNR, layers, overlap.
+ * This is NOT spiht_encode_image_*_f32: a float32 picture given to the *_f32 calls keeps the reference's single-precision
+ * transform (and its limits: dense CHW, no colour model); the same picture given to the *_flt calls is transformed in
+ * float64.  The two streams differ as soon as the quantiser step is fine enough to see float32's rounding.
+ * Non-finite samples are outside the contract of the encode calls, as they are for the *_f64 calls; the widening pass alone
+ * is specified on them (infinities stay, a NaN gives a NaN).
+ * Level 1 of the tiled forward transform loads the kind itself (one pixel kind of the kernels, PX_FLT, for the three; all loads
+ * of a thread first, then the widenings); the routes without a fused form -- the modes that compute their extension,
+ * periodization, filters longer than SPIHT_MAX_TAPS -- widen in a pass of their own in front, which is what
+ * spiht_widen_batch_flt runs alone (the mirror of spiht_convert_batch_flt):
+ *   spiht_widen_batch_flt    the view [B, c, H, W] of the kind at d_in (strides[4] in bytes; NULL: dense) -> dense float64
+ *                            [B, c, H, W] at d_out on the device.  Asynchronous.
+ * Error sums of the allocation: spiht_sse_tiles_flt / spiht_sse_tiles_w_flt are spiht_sse_tiles_f64 / _w_f64 with ORIGINAL
+ * tiles of the kind (d_tiles aligned to the element), widened on the load; the decodes stay float64, the partition and the
+ * order of additions are the same, so the sums are the bits of the _f64 calls on the widened tiles.
+ * Tiles: a picture of a 16-bit kind is cut by the *_u16 copies, as bit patterns; one of float32 by the strided copies
+ * spiht_tile_cut_f32s / spiht_tile_cut_overlap_f32s (spiht_tile_cut_u16 / spiht_tile_cut_overlap_u16 with 4-byte elements;
+ * the dense *_f32 calls are unchanged). */
+int spiht_widen_batch_flt(spiht_ctx *ctx, int kind, const void *d_in, const int64_t *strides, int64_t B, int64_t c, int64_t H,
+                          int64_t W, double *d_out);
+int spiht_encode_image_batch_flt(spiht_ctx *ctx, int kind, const void *d_img, const int64_t *strides, int64_t B, int64_t c,
+                                 int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                 const double *channel_mults, uint64_t max_bits, uint8_t *d_out, uint64_t slot_stride,
+                                 uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs);
+int spiht_encode_image_host_flt(spiht_ctx *ctx, int kind, const void *img, const int64_t *strides, int64_t c, int64_t H, int64_t W,
+                                int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                uint64_t max_bits, uint8_t *out, uint64_t out_cap, uint64_t *out_nbits, uint8_t *max_n);
+int spiht_dwt_pyramid_batch_flt(spiht_ctx *ctx, int kind, const void *d_img, const int64_t *strides, int64_t B, int64_t c, int64_t H,
+                                int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                                int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb, uint32_t *d_maxabs);
+int spiht_sse_tiles_flt(spiht_ctx *ctx, int kind, const void *d_tiles, const double *d_dec, int64_t G, int64_t N, int64_t c,
+                        int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, double *d_out);
+int spiht_sse_tiles_w_flt(spiht_ctx *ctx, int kind, const void *d_tiles, const double *d_dec, int64_t G, int64_t N, int64_t c,
+                          int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, double *d_out, const uint8_t *d_w,
+                          uint64_t w_stride);
+int spiht_tile_cut_f32s(spiht_ctx *ctx, const float *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H, int64_t W,
+                        int64_t th, int64_t tw, float *d_tiles);
+int spiht_tile_cut_overlap_f32s(spiht_ctx *ctx, const float *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
+                                int64_t W, int64_t th, int64_t tw, int64_t m, float *d_tiles);
+
 /* How the tiled forward transform kernel addresses a level (host only, no device call): 1 when every plane the level reads or
- * writes -- its float64 input in_h x in_w (px_es == 0) or the byte span of an 8- / 16-bit view with element size px_es and
+ * writes -- its float64 input in_h x in_w (px_es == 0) or the byte span of an 8- / 16-bit or float view with element size px_es
+ * (1, 2 or 4) and
  * byte strides px_sh, px_sw; the packed array enc_h x enc_w; the approximation out_h x out_w -- is under 2^30 bytes, so that the
  * kernel may use 32-bit offsets into per-plane buffer descriptors; 0: 64-bit addresses.  The results are the same bits. */
 int spiht_dwt_addr32(int64_t in_h, int64_t in_w, int64_t out_h, int64_t out_w, int64_t enc_h, int64_t enc_w, int px_es,

@@ -49,4 +49,6 @@ globals().update({_k: getattr(_impl, _k) for _k in ("window_tiles_overlap",)})
 globals().update({_k: getattr(_impl, _k) for _k in ("decode_image_float", "decode_image_reduced_float", "decode_image_tiled_float",
                                                     "decode_image_window_float", "decode_image_layered_float",
                                                     "decode_image_layered_window_float")})
+# ... float pixels in: float32, float16 and bfloat16 pictures coded as they lie, by the float64 codec
+globals().update({_k: getattr(_impl, _k) for _k in ("encode_image_float", "encode_image_tiled_float", "encode_image_layered_float")})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

@@ -10,7 +10,8 @@ _lib_mod.lib()  # fail at import time, not at first use, when the HIP library ha
 from .spiht_wrapper import (encode_image, decode_image, EncodingResult, SpihtSettings,  # noqa: E402,F401
                             ENCODER_DECODER_VERSION, encode_image_u8, decode_image_u8,
                             encode_image_u16, decode_image_u16, decode_image_reduced, decode_image_reduced_u8,
-                            decode_image_reduced_u16, reduced_shape, decode_image_float, decode_image_reduced_float)
+                            decode_image_reduced_u16, reduced_shape, decode_image_float, decode_image_reduced_float,
+                            encode_image_float)
 from . import floatpx  # noqa: E402,F401
 from .spiht import encode, decode  # noqa: E402,F401
 from .rd import (RDCurve, rd_curve, rd_curve_u8, rd_curve_u16, cut_to_psnr, cut_to_psnr_u8,  # noqa: E402,F401
@@ -21,6 +22,7 @@ from .tiles import (TiledCodec, TiledResult, TileCurves, TileAllocation, tile_gr
                     LayeredResult, encode_image_layered, encode_image_layered_u8, encode_image_layered_u16, decode_image_layered,
                     decode_image_layered_u8, decode_image_layered_u16, decode_image_layered_window, decode_image_layered_window_u8,
                     decode_image_layered_window_u16, decode_image_tiled_float, decode_image_window_float,
-                    decode_image_layered_float, decode_image_layered_window_float)
+                    decode_image_layered_float, decode_image_layered_window_float, encode_image_tiled_float,
+                    encode_image_layered_float)
 from .alloc import roi_map, target_sqerr  # noqa: E402,F401
 from .overlap import window_tiles_overlap  # noqa: E402,F401

@@ -76,6 +76,8 @@ SYMBOLS = [
     "spiht_dequant_idwt_flags_batch_flt", "spiht_dequant_idwt_reduced_batch_flt", "spiht_decode_image_reduced_batch_flt",
     "spiht_decode_image_reduced_host_flt", "spiht_tile_blend_flt", "spiht_tile_paste_f32s", "spiht_tile_mosaic_f32",
     "spiht_dwt_addr32",
+    "spiht_widen_batch_flt", "spiht_encode_image_batch_flt", "spiht_encode_image_host_flt", "spiht_dwt_pyramid_batch_flt",
+    "spiht_sse_tiles_flt", "spiht_sse_tiles_w_flt", "spiht_tile_cut_f32s", "spiht_tile_cut_overlap_f32s",
 ]
 
 
@@ -254,14 +256,17 @@ def lib():
             if name.endswith("_u16"):
                 getattr(L, name).argtypes = getattr(L, name[:-2] + "8").argtypes
                 getattr(L, name).restype = getattr(L, name[:-2] + "8").restype
-        # float pixels out: every *_flt call takes what its *_u8 sibling takes, with the kind behind the context (in front of
-        # everything where there is none); the conversion pass alone; float32 tile batches by strides
+        # float pixels out and in: every *_flt call takes what its *_u8 sibling takes, with the kind behind the context (in front
+        # of everything where there is none); the conversion and the widening pass alone; float32 tile batches by strides
         for name in SYMBOLS:
-            if name.endswith("_flt") and name != "spiht_convert_batch_flt":
+            if name.endswith("_flt") and name not in ("spiht_convert_batch_flt", "spiht_widen_batch_flt"):
                 a = getattr(L, name[:-3] + "u8").argtypes
                 getattr(L, name).argtypes = [i32] + a if name == "spiht_check_view_flt" else a[:1] + [i32] + a[1:]
         L.spiht_convert_batch_flt.argtypes = [vp, i32, vp] + [i64] * 6 + [vp, vp]
+        L.spiht_widen_batch_flt.argtypes = [vp, i32, vp, vp] + [i64] * 4 + [vp]
         L.spiht_tile_paste_f32s.argtypes = L.spiht_tile_paste_u8.argtypes
+        L.spiht_tile_cut_f32s.argtypes = L.spiht_tile_cut_u8.argtypes
+        L.spiht_tile_cut_overlap_f32s.argtypes = L.spiht_tile_cut_overlap_u8.argtypes
         L.spiht_tile_mosaic_f32.argtypes = L.spiht_tile_mosaic_u8.argtypes
         L.spiht_ctx_lock.argtypes = [vp]
         L.spiht_ctx_unlock.argtypes = [vp]

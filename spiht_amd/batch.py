@@ -289,6 +289,40 @@ class BatchCodec:
         ys, xs = slice(rs["off_y"], rs["off_y"] + rs["in_h"]), slice(rs["off_x"], rs["off_x"] + rs["in_w"])
         return out[:, ys, xs, :] if channels_last else out[:, :, ys, xs]
 
+    # ---- float pixels in (include/spiht_hip.h, the encode side of *_flt): float32, float16 or bfloat16 pictures, each sample
+    # widened exactly on the loads of level 1; whatever pixel_dtype says, the float64 arithmetic -- what encode() of a float64
+    # codec gives for floatpx.to_float64 of the pictures.  NOT the single-precision transform of a pixel_dtype=float32 codec.
+    def encode_device_float(self, d_img, B, d_out, d_nbits, d_max_n, dtype, strides=None, d_coeffs=None):
+        """d_img: pictures of the kind `dtype` [B, c, H, W] on the device, laid out by `strides` (BYTES, non-negative multiples
+        of the element size, as the base; None: dense CHW)"""
+        kind = floatpx.kind_id(dtype)
+        st = st_p = None
+        if strides is not None:
+            st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
+            floatpx.check_float_view(kind, (int(B), self.c, self.H, self.W), st, False)
+            st_p = C.c_void_p(st.ctypes.data)
+        _check_aligned(d_img, floatpx.storage_dtype(kind))
+        with self._color():
+            _lib.check(self.L.spiht_encode_image_batch_flt(
+                self.ctx.handle, kind, C.c_void_p(d_img), st_p, int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
+                float(self.settings.quantization_scale), self._mults_p, self.max_bits, C.c_void_p(d_out), self.slot_stride,
+                C.c_void_p(d_nbits), C.c_void_p(d_max_n), C.c_void_p(d_coeffs) if d_coeffs else None))
+
+    def encode_float(self, images, dtype=None, channels_last=False):
+        """images: [B, c, H, W] (or [B, H, W, c] with channels_last) float32 or float16, or uint16 bit patterns with
+        dtype="bfloat16" -> list of EncodingResult: spiht_wrapper.encode_image_float of each"""
+        images = np.asarray(images)
+        kind = floatpx.input_kind(images, dtype, "encode_float")
+        sd = floatpx.storage_dtype(kind)
+        if images.ndim != 4:
+            raise ValueError("encode_float takes a %s array [B, c, H, W]" % sd.name)
+        if channels_last:
+            images = images.transpose(0, 3, 1, 2)
+        images = np.ascontiguousarray(images, dtype=sd)
+        if images.shape[1:] != (self.c, self.H, self.W):
+            raise ValueError("encode_float: pictures of shape %s, the codec's are %s" % (images.shape[1:], (self.c, self.H, self.W)))
+        return self._encode_host(images, lambda d_img, *a: self.encode_device_float(d_img, *a, kind))
+
     # ---- reduced-resolution decode (include/spiht_hip.h, *_reduced_*): pictures at 1/2^reduce size, 0 <= reduce <= L.
     # What spiht_wrapper.decode_image_reduced* return, for B streams in one queue of kernels. ------------------------------
     def reduced_shape(self, reduce):

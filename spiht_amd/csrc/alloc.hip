@@ -2,6 +2,7 @@
 // decoded and measured, and every tile is cut where one more byte buys the same drop in distortion.
 //   k_tile_prefix_slots  NT stream slots -> G * NT slots holding the prefixes of candidates k0 .. k0 + G - 1, zero behind
 //   k_sse_tiles_f64      per-tile error sum over the tile's valid extent, float64, in a fixed order of additions
+//   k_sse_tiles_flt      k_sse_tiles_f64 with original tiles of a float kind, widened on the load (float pixels in)
 //   k_sse_tiles_px       the same for 8- / 16-bit samples, exact in 64 bits
 //   k_tile_allocate      lower convex hulls, the common slope by bisection, the fill in tile order: one workgroup per picture
 //   k_tile_allocate_target  the same hulls, the steepest common slope at which the picture's error is at or below a target
@@ -9,6 +10,7 @@
 // (p - d) * (p - d) rounded, then added; a slope is one rounded subtraction and one rounded division.  No atomics.
 #include "alloc.h"
 #include "copy_bytes.h"
+#include "floatpx.h"
 
 // ---- prefix slots ----------------------------------------------------------------------------------------------------------
 
@@ -58,6 +60,51 @@ __global__ __launch_bounds__(AL_THREADS) void k_sse_tiles_f64(const TileSseArgs 
                 acc += t1 * t1;
             } else {
                 const double t0 = pr[x] - dr[x];
+                acc += t0 * t0;
+            }
+        }
+    }
+    for (int off = 32; off; off >>= 1) acc += __shfl_down(acc, off);
+    __shared__ double sh[AL_THREADS / 64];
+    if (lane == 0) sh[wv] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        for (int i = 1; i < AL_THREADS / 64; i++) acc += sh[i];
+        ((double *)a.part)[((size_t)s * a.c + ch) * a.chunks + chunk] = acc;
+    }
+}
+
+// Float pixels in: the ORIGINAL tiles are float32 (T = uint32_t) or float16 / bfloat16 (T = uint16_t) bit patterns of kind
+// `kind` (uniform over the launch), each widened exactly on the load (floatpx.h); the decodes are float64.  The partition, the
+// pairing of columns and the order of additions are k_sse_tiles_f64's, so the sums are its bits on the widened tiles.  A tile
+// row is only element-aligned (tw may be odd): the pair of the original is two loads of one element; the decode keeps the
+// paired load of the float64 kernel.
+template <typename T>
+__global__ __launch_bounds__(AL_THREADS) void k_sse_tiles_flt(const TileSseArgs a, int kind) {
+    const uint32_t s = blockIdx.x, chunk = blockIdx.y, ch = blockIdx.z, tid = threadIdx.x;
+    const uint32_t t = s % a.NT;
+    int vh, vw;
+    valid_extent(a, t, vh, vw);
+    if ((int)chunk * AL_TILE_ROWS >= vh) return;
+    const int wv = tid >> 6, lane = tid & 63;
+    const T *p = (const T *)a.tiles + ((size_t)t * a.c + ch) * (size_t)a.th * a.tw;
+    const double *d = (const double *)a.dec + ((size_t)s * a.c + ch) * (size_t)a.rh * a.rw;
+    double acc = 0.0;
+    for (int r = wv; r < AL_TILE_ROWS; r += AL_THREADS / 64) {
+        const int y = (int)chunk * AL_TILE_ROWS + r;
+        if (y >= vh) break;
+        const T *pr = p + (size_t)y * a.tw;
+        const double *dr = d + (size_t)y * a.rw;
+#pragma unroll 4
+        for (int x = 2 * lane; x < vw; x += 128) {
+            if (x + 1 < vw) {
+                const uint32_t r0 = pr[x], r1 = pr[x + 1];
+                const F64x2 dv = *reinterpret_cast<const F64x2 *>(dr + x);
+                const double t0 = flt_load_value(r0, kind) - dv.a, t1 = flt_load_value(r1, kind) - dv.b;
+                acc += t0 * t0;
+                acc += t1 * t1;
+            } else {
+                const double t0 = flt_load_value(pr[x], kind) - dr[x];
                 acc += t0 * t0;
             }
         }
@@ -380,6 +427,15 @@ extern "C" int spiht_launch_sse_tiles(const TileSseArgs *a, int es, int64_t G, h
         else hipLaunchKernelGGL(k_sse_tiles_px<uint8_t>, grid, dim3(AL_THREADS), 0, st, *a);
         hipLaunchKernelGGL(k_sum_tiles<uint64_t>, dim3((n + 63) / 64), dim3(64), 0, st, *a, n);
     }
+    return (int)hipGetLastError();
+}
+// float pixels in: originals of a float kind against float64 decodes, float64 sums
+extern "C" int spiht_launch_sse_tiles_flt(const TileSseArgs *a, int kind, int64_t G, hipStream_t st) {
+    const uint32_t n = (uint32_t)(G * a->NT);
+    const dim3 grid(n, a->chunks, a->c);
+    if (flt_itemsize(kind) == 4) hipLaunchKernelGGL(k_sse_tiles_flt<uint32_t>, grid, dim3(AL_THREADS), 0, st, *a, kind);
+    else hipLaunchKernelGGL(k_sse_tiles_flt<uint16_t>, grid, dim3(AL_THREADS), 0, st, *a, kind);
+    hipLaunchKernelGGL(k_sum_tiles<double>, dim3((n + 63) / 64), dim3(64), 0, st, *a, n);
     return (int)hipGetLastError();
 }
 // the second launch alone, for the weighted forms (roi.hip), whose partials it adds: n sums, float64 (es 8) or uint64

@@ -76,6 +76,8 @@ int spiht_launch_tile_prefix_slots(const uint8_t *d_slots, uint64_t slot_stride,
                                    uint8_t *d_max_n_out, hipStream_t st);
 int spiht_launch_sse_tiles(const TileSseArgs *a, int es, int64_t G, hipStream_t st);
 int spiht_launch_sse_tiles_w(const TileSseWArgs *q, int es, int64_t G, hipStream_t st);
+int spiht_launch_sse_tiles_flt(const TileSseArgs *a, int kind, int64_t G, hipStream_t st);
+int spiht_launch_sse_tiles_w_flt(const TileSseWArgs *q, int kind, int64_t G, hipStream_t st);
 int spiht_launch_tile_allocate(const uint64_t *d_nbits, const void *d_D, int kind, int K, int64_t N, int64_t T, uint64_t budget,
                                const double *d_target, void *scratch, uint64_t *d_nbits_out, double *d_lambda, double *d_dist,
                                uint32_t *d_met, hipStream_t st);
@@ -1316,9 +1318,9 @@ static int upload_filters(spiht_ctx *ctx, int wavelet, const double **d_filt) {
 // Float pixels: a dense array at p, [B, c, H, W] (the inverse transform's output: [B, c, rec_H, rec_W]).  8- and 16-bit
 // pixels: the view px (common.h: PxView) of a [B, c, H, W] uint8 / uint16 picture batch by byte strides, based at p.  The
 // extern "C" entry points make one; everything behind them passes it on.
-// PIC_FLT: float pixels OUT (floatpx.h), a view like the integer ones whose kind is px.kind.
+// PIC_FLT: float pixels in or out (floatpx.h), a view like the integer ones whose kind is px.kind.
 enum PicFmt { PIC_F64, PIC_F32, PIC_U8, PIC_U16, PIC_FLT };
-// the element of a view: its bytes and, for float pixels out, the kind (0: integer pixels)
+// the element of a view: its bytes and, for float pixels in or out, the kind (0: integer pixels)
 struct PxElem {
     int es, kind;
     PxElem(int es_) : es(es_), kind(0) {}
@@ -1367,10 +1369,10 @@ static Pic dense_pic(const void *p, PicFmt fmt, bool out = false) {
 // es: bytes per sample, 1 or 2.  strides (in bytes): n == 4: (sb, sc, sh, sw); n == 3: (sc, sh, sw) of one picture;
 // nullptr: dense CHW.  Strides are non-negative and, as the base, multiples of es; a view that is written must not overlap
 // itself: sorted by stride, every dimension longer than 1 must step past the last byte all the smaller ones reach.
-// A float kind (el.kind): es 4 or 2 by the same rules; such a view is only ever written.
+// A float kind (el.kind): es 4 or 2 by the same rules, read (float pixels in) or written (float pixels out).
 static int int_pic(const void *p, PxElem el, bool out, const int64_t *strides, int n, int64_t B, int64_t c, int64_t h, int64_t w, Pic *v) {
     const int es = el.es;
-    if (es < 1 || (el.kind && !out)) return SPIHT_ERR_ARG;
+    if (es < 1) return SPIHT_ERR_ARG;
     int64_t st[4] = {c * h * w * es, h * w * es, w * es, es};
     if (strides)
         for (int i = 0; i < n; i++) st[4 - n + i] = strides[i];
@@ -1417,7 +1419,8 @@ extern "C" int spiht_check_view_u16(int64_t B, int64_t c, int64_t H, int64_t W, 
 // must then be at least as long as the filter: SPIHT_ERR_ARG otherwise), at a level >= 1 and without the colour model.
 // 8- and 16-bit pixels need a level >= 1 (no entry point gets here with level 0: SPIHT refuses that geometry -- the root block's
 // offspring fall outside the array -- before anything is transformed, on the float64 path as well); the tiled level 1
-// reads them itself, the two-pass levels get their float64 form from a conversion pass first.
+// reads them itself, the two-pass levels get their float64 form from a conversion pass first.  Float pixels in (PIC_FLT) go
+// the integer kinds' way in everything: the same view, the same two routes; their conversion is the exact widening.
 static int dwt_forward(spiht_ctx *ctx, const Pic &in, int planes, int c, const ImgGeom &ig, int wavelet, int mode,
                        double q, const double *d_mults, int32_t *d_coeffs, uint32_t *d_maxabs = nullptr) {
     const WaveletDef &wv = SPIHT_WAVELETS[wavelet];
@@ -1931,14 +1934,14 @@ extern "C" int spiht_encode_image_batch_f32(spiht_ctx *ctx, const float *d_img, 
     return encode_image_batch(ctx, dense_pic(d_img, PIC_F32), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
                               d_out, slot_stride, d_nbits, d_max_n, d_coeffs);
 }
-static int encode_image_batch_px(int es, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t B, int64_t c,
+static int encode_image_batch_px(PxElem el, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t B, int64_t c,
                                  int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                  const double *channel_mults, uint64_t max_bits, uint8_t *d_out,
                                  uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs) {
     if (!d_img) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
     Pic in;
-    CHK(int_pic(d_img, es, false, strides, 4, B, c, H, W, &in));
+    CHK(int_pic(d_img, el, false, strides, 4, B, c, H, W, &in));
     return encode_image_batch(ctx, in, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, d_out, slot_stride,
                               d_nbits, d_max_n, d_coeffs);
 }
@@ -2091,14 +2094,14 @@ extern "C" int spiht_encode_image_host_f32(spiht_ctx *ctx, const float *img, int
     return encode_image_host(ctx, dense_pic(img, PIC_F32), c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out,
                              out_cap, out_nbits, max_n);
 }
-static int encode_image_host_px(int es, spiht_ctx *ctx, const void *img, const int64_t *strides, int64_t c, int64_t H,
+static int encode_image_host_px(PxElem el, spiht_ctx *ctx, const void *img, const int64_t *strides, int64_t c, int64_t H,
                                 int64_t W, int wavelet, int mode, int level, double q_scale,
                                 const double *channel_mults, uint64_t max_bits, uint8_t *out, uint64_t out_cap,
                                 uint64_t *out_nbits, uint8_t *max_n) {
     if (!img) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, 1, c, H, W));
     Pic in;
-    CHK(int_pic(img, es, false, strides, 3, 1, c, H, W, &in));
+    CHK(int_pic(img, el, false, strides, 3, 1, c, H, W, &in));
     return encode_image_host(ctx, in, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits, out, out_cap, out_nbits,
                              max_n);
 }
@@ -2344,11 +2347,8 @@ extern "C" int spiht_decode_image_reduced_host_u16(spiht_ctx *ctx, const uint8_t
 extern "C" int spiht_check_view_flt(int kind, int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output) {
     if (B < 1 || c < 1 || H < 1 || W < 1 || !strides) return SPIHT_ERR_ARG;
     Pic v;
-    // (a view that is read obeys the same rules without the overlap check; int_pic itself only makes views that are written)
-    const PxElem el = flt_elem(kind);
-    if (el.es == 0) return SPIHT_ERR_ARG;
-    if (output) return int_pic(nullptr, el, true, strides, 4, B, c, H, W, &v);
-    return int_pic(nullptr, PxElem(el.es), false, strides, 4, B, c, H, W, &v);
+    // (a view that is read obeys the same rules without the overlap check)
+    return int_pic(nullptr, flt_elem(kind), output != 0, strides, 4, B, c, H, W, &v);
 }
 extern "C" int spiht_convert_batch_flt(spiht_ctx *ctx, int kind, const double *d_in, int64_t B, int64_t c, int64_t rec_h,
                                        int64_t rec_w, int64_t H, int64_t W, void *d_out, const int64_t *out_strides) {
@@ -2405,6 +2405,40 @@ extern "C" int spiht_decode_image_reduced_host_flt(spiht_ctx *ctx, int kind, con
                                                    const int64_t *strides, int reduce) {
     return decode_image_reduced_host_px(flt_elem(kind), ctx, data, nbytes, n, c, H, W, wavelet, mode, level, q_scale,
                                         channel_mults, img_out, strides, reduce);
+}
+
+// ------------------------------------------------------------------------------------------------
+// float pixels in (include/spiht_hip.h, *_flt): the *_u16 encode calls with the element of a float kind.  Every sample is
+// widened exactly on the loads of forward level 1 (dwt.hip, PX_FLT: flt_load_value), and everything behind that is the
+// float64 path -- NOT the single-precision transform of the *_f32 calls.  The routes without a fused form widen in a pass of
+// their own (dwt_forward: k_px_to_f64), which spiht_widen_batch_flt runs alone.
+// ------------------------------------------------------------------------------------------------
+extern "C" int spiht_widen_batch_flt(spiht_ctx *ctx, int kind, const void *d_in, const int64_t *strides, int64_t B, int64_t c,
+                                     int64_t H, int64_t W, double *d_out) {
+    if (!ctx || !d_in || !d_out || B < 0 || c < 1 || H < 1 || W < 1) return SPIHT_ERR_ARG;
+    if (H > (1 << 24) || W > (1 << 24) || (__int128)B * c >= ((__int128)1 << 31)) return SPIHT_ERR_TOO_LARGE;
+    Pic in;
+    CHK(int_pic(d_in, flt_elem(kind), false, strides, 4, std::max<int64_t>(B, 1), c, H, W, &in));
+    if (B == 0) return SPIHT_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    const PxView px = in.view();
+    LAUNCHCHK(spiht_launch_px_to_f64(&px, B, d_out, ctx->stream));
+    return SPIHT_OK;
+}
+extern "C" int spiht_encode_image_batch_flt(spiht_ctx *ctx, int kind, const void *d_img, const int64_t *strides, int64_t B,
+                                            int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                            const double *channel_mults, uint64_t max_bits, uint8_t *d_out,
+                                            uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs) {
+    return encode_image_batch_px(flt_elem(kind), ctx, d_img, strides, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                                 max_bits, d_out, slot_stride, d_nbits, d_max_n, d_coeffs);
+}
+extern "C" int spiht_encode_image_host_flt(spiht_ctx *ctx, int kind, const void *img, const int64_t *strides, int64_t c, int64_t H,
+                                           int64_t W, int wavelet, int mode, int level, double q_scale,
+                                           const double *channel_mults, uint64_t max_bits, uint8_t *out, uint64_t out_cap,
+                                           uint64_t *out_nbits, uint8_t *max_n) {
+    return encode_image_host_px(flt_elem(kind), ctx, img, strides, c, H, W, wavelet, mode, level, q_scale, channel_mults, max_bits,
+                                out, out_cap, out_nbits, max_n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2505,12 +2539,12 @@ static int tile_cut(spiht_ctx *ctx, const Pic &in, int es, int64_t N, int64_t c,
     LAUNCHCHK(spiht_launch_tile_cut(&a, es, N * gy * gx, ctx->stream));
     return SPIHT_OK;
 }
-static int tile_cut_px(int es, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
+static int tile_cut_px(PxElem el, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
                        int64_t W, int64_t th, int64_t tw, void *d_tiles, const int64_t *overlap = nullptr) {
     if (N < 0 || c < 1 || H < 1 || W < 1) return SPIHT_ERR_ARG;
     Pic pic;
-    CHK(int_pic(d_img, es, false, strides, 4, std::max<int64_t>(N, 1), c, H, W, &pic));
-    return tile_cut(ctx, pic, es, N, c, H, W, th, tw, d_tiles, overlap);
+    CHK(int_pic(d_img, el, false, strides, 4, std::max<int64_t>(N, 1), c, H, W, &pic));
+    return tile_cut(ctx, pic, el.es, N, c, H, W, th, tw, d_tiles, overlap);
 }
 extern "C" int spiht_tile_cut_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
                                  int64_t W, int64_t th, int64_t tw, uint8_t *d_tiles) {
@@ -2528,6 +2562,11 @@ extern "C" int spiht_tile_cut_f64(spiht_ctx *ctx, const double *d_img, int64_t N
                                   int64_t tw, double *d_tiles) {
     return tile_cut(ctx, dense_pic(d_img, PIC_F64), 8, N, c, H, W, th, tw, d_tiles);
 }
+// ... from a float32 view by byte strides (float pixels in: the 16-bit kinds go through the *_u16 copies, as bit patterns)
+extern "C" int spiht_tile_cut_f32s(spiht_ctx *ctx, const float *d_img, const int64_t *strides, int64_t N, int64_t c, int64_t H,
+                                   int64_t W, int64_t th, int64_t tw, float *d_tiles) {
+    return tile_cut_px(flt_elem(SPIHT_FLT_F32), ctx, d_img, strides, N, c, H, W, th, tw, d_tiles);
+}
 // ... with a margin of m samples around every tile (overlap.hip): d_tiles is [N * T, c, th + 2m, tw + 2m]
 extern "C" int spiht_tile_cut_overlap_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t N, int64_t c,
                                          int64_t H, int64_t W, int64_t th, int64_t tw, int64_t m, uint8_t *d_tiles) {
@@ -2536,6 +2575,10 @@ extern "C" int spiht_tile_cut_overlap_u8(spiht_ctx *ctx, const uint8_t *d_img, c
 extern "C" int spiht_tile_cut_overlap_u16(spiht_ctx *ctx, const uint16_t *d_img, const int64_t *strides, int64_t N, int64_t c,
                                           int64_t H, int64_t W, int64_t th, int64_t tw, int64_t m, uint16_t *d_tiles) {
     return tile_cut_px(2, ctx, d_img, strides, N, c, H, W, th, tw, d_tiles, &m);
+}
+extern "C" int spiht_tile_cut_overlap_f32s(spiht_ctx *ctx, const float *d_img, const int64_t *strides, int64_t N, int64_t c,
+                                           int64_t H, int64_t W, int64_t th, int64_t tw, int64_t m, float *d_tiles) {
+    return tile_cut_px(flt_elem(SPIHT_FLT_F32), ctx, d_img, strides, N, c, H, W, th, tw, d_tiles, &m);
 }
 extern "C" int spiht_tile_cut_overlap_f32(spiht_ctx *ctx, const float *d_img, int64_t N, int64_t c, int64_t H, int64_t W,
                                           int64_t th, int64_t tw, int64_t m, float *d_tiles) {
@@ -2833,12 +2876,14 @@ extern "C" int spiht_tile_prefix_slots(spiht_ctx *ctx, const uint8_t *d_slots, u
 }
 // es: bytes per sample (8: float64).  d_tiles [N * T, c, th, tw], d_dec [G, N * T, c, rh, rw] -> d_out [G][N * T].  weighted:
 // every term times d_w [N or 1][H][W] (roi.hip)
+// kind: 0, or the float kind of the ORIGINAL tiles (float pixels in; es is then 8: the decodes and the sums are float64)
 static int sse_tiles(int es, spiht_ctx *ctx, const void *d_tiles, const void *d_dec, int64_t G, int64_t N, int64_t c, int64_t H,
                      int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, void *d_out, bool weighted = false,
-                     const uint8_t *d_w = nullptr, uint64_t w_stride = 0) {
+                     const uint8_t *d_w = nullptr, uint64_t w_stride = 0, int kind = 0) {
     if (!ctx || !d_tiles || !d_dec || !d_out || G < 1 || G > 65535 || N < 1 || c < 1) return SPIHT_ERR_ARG;
     if (weighted && !d_w) return SPIHT_ERR_ARG;
-    if ((uintptr_t)d_tiles % es || (uintptr_t)d_dec % es || (uintptr_t)d_out % 8) return SPIHT_ERR_ARG;
+    if (kind && flt_itemsize(kind) == 0) return SPIHT_ERR_ARG;
+    if ((uintptr_t)d_tiles % (kind ? flt_itemsize(kind) : es) || (uintptr_t)d_dec % es || (uintptr_t)d_out % 8) return SPIHT_ERR_ARG;
     int64_t gy, gx;
     CHK(spiht_tile_grid(H, W, th, tw, &gy, &gx));
     if (rh < th || rw < tw) return SPIHT_ERR_ARG;
@@ -2860,9 +2905,11 @@ static int sse_tiles(int es, spiht_ctx *ctx, const void *d_tiles, const void *d_
     if (weighted) {
         TileSseWArgs q;
         q.a = a; q.w = d_w; q.w_stride = w_stride;
-        LAUNCHCHK(spiht_launch_sse_tiles_w(&q, es, G, ctx->stream));
+        if (kind) LAUNCHCHK(spiht_launch_sse_tiles_w_flt(&q, kind, G, ctx->stream));
+        else LAUNCHCHK(spiht_launch_sse_tiles_w(&q, es, G, ctx->stream));
     } else {
-        LAUNCHCHK(spiht_launch_sse_tiles(&a, es, G, ctx->stream));
+        if (kind) LAUNCHCHK(spiht_launch_sse_tiles_flt(&a, kind, G, ctx->stream));
+        else LAUNCHCHK(spiht_launch_sse_tiles(&a, es, G, ctx->stream));
     }
     return SPIHT_OK;
 }
@@ -2892,6 +2939,19 @@ extern "C" int spiht_sse_tiles_w_u16(spiht_ctx *ctx, const uint16_t *d_tiles, co
                                      int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, uint64_t *d_out,
                                      const uint8_t *d_w, uint64_t w_stride) {
     return sse_tiles(2, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out, true, d_w, w_stride);
+}
+// float pixels in: the original tiles of a float kind, widened on the load; the decodes float64 -- the bits of the _f64 calls
+// on the widened tiles
+extern "C" int spiht_sse_tiles_flt(spiht_ctx *ctx, int kind, const void *d_tiles, const double *d_dec, int64_t G, int64_t N,
+                                   int64_t c, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, double *d_out) {
+    if (flt_itemsize(kind) == 0) return SPIHT_ERR_ARG;
+    return sse_tiles(8, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out, false, nullptr, 0, kind);
+}
+extern "C" int spiht_sse_tiles_w_flt(spiht_ctx *ctx, int kind, const void *d_tiles, const double *d_dec, int64_t G, int64_t N,
+                                     int64_t c, int64_t H, int64_t W, int64_t th, int64_t tw, int64_t rh, int64_t rw, double *d_out,
+                                     const uint8_t *d_w, uint64_t w_stride) {
+    if (flt_itemsize(kind) == 0) return SPIHT_ERR_ARG;
+    return sse_tiles(8, ctx, d_tiles, d_dec, G, N, c, H, W, th, tw, rh, rw, d_out, true, d_w, w_stride, kind);
 }
 // both cuts: at the budget (d_target NULL), or at a target squared error per picture under that budget
 static int tile_allocate(spiht_ctx *ctx, const uint64_t *d_nbits, const void *d_D, int kind, int64_t K, int64_t N, int64_t T,
@@ -2991,14 +3051,14 @@ extern "C" int spiht_dwt_pyramid_batch_f64(spiht_ctx *ctx, const double *d_img, 
     return dwt_pyramid_batch(ctx, dense_pic(d_img, PIC_F64), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs,
                              d_dmsb, d_lmsb, d_maxabs);
 }
-static int dwt_pyramid_batch_px(int es, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t B, int64_t c,
+static int dwt_pyramid_batch_px(PxElem el, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t B, int64_t c,
                                 int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                 const double *channel_mults, int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb,
                                 uint32_t *d_maxabs) {
     if (!d_img) return SPIHT_ERR_ARG;
     CHK(check_img_args(wavelet, mode, B, c, H, W));
     Pic in;
-    CHK(int_pic(d_img, es, false, strides, 4, B, c, H, W, &in));
+    CHK(int_pic(d_img, el, false, strides, 4, B, c, H, W, &in));
     return dwt_pyramid_batch(ctx, in, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs, d_dmsb, d_lmsb, d_maxabs);
 }
 extern "C" int spiht_dwt_pyramid_batch_u8(spiht_ctx *ctx, const uint8_t *d_img, const int64_t *strides, int64_t B, int64_t c,
@@ -3014,6 +3074,13 @@ extern "C" int spiht_dwt_pyramid_batch_u16(spiht_ctx *ctx, const uint16_t *d_img
                                            uint32_t *d_maxabs) {
     return dwt_pyramid_batch_px(2, ctx, d_img, strides, B, c, H, W, wavelet, mode, level, q_scale, channel_mults, d_coeffs,
                                 d_dmsb, d_lmsb, d_maxabs);
+}
+extern "C" int spiht_dwt_pyramid_batch_flt(spiht_ctx *ctx, int kind, const void *d_img, const int64_t *strides, int64_t B, int64_t c,
+                                           int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                                           const double *channel_mults, int32_t *d_coeffs, uint8_t *d_dmsb, uint8_t *d_lmsb,
+                                           uint32_t *d_maxabs) {
+    return dwt_pyramid_batch_px(flt_elem(kind), ctx, d_img, strides, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+                                d_coeffs, d_dmsb, d_lmsb, d_maxabs);
 }
 
 extern "C" int spiht_encode_lists_batch_i32(spiht_ctx *ctx, const int32_t *d_x, const uint8_t *d_dmsb,

@@ -238,8 +238,9 @@ struct PxView {
     int64_t sb, sc, sh, sw;
     int32_t c, h, w;
     int32_t es;            // element size in bytes: 1 or 2 (the launchers pick the kernels' pixel kind from it); a float kind: 4 or 2
-    int32_t kind;          // 0: integer pixels.  Inverse only, floatpx.h: 1 float32, 2 float16, 3 bfloat16 -- the value is stored
-    int32_t pad;           // rounded once to the kind, no clip and no scale, through the same strides and the same crop
+    int32_t kind;          // 0: integer pixels.  floatpx.h: 1 float32, 2 float16, 3 bfloat16.  Inverse: the value is stored rounded
+    int32_t pad;           // once to the kind, no clip and no scale, through the same strides and the same crop.  Forward: the
+                           // sample is loaded as the double of the same value (exact), through the same strides
 };
 
 // One forward DWT level (dwt.hip)

@@ -191,9 +191,10 @@ __device__ __forceinline__ uint16_t px16_store_value(double v) {
 }
 // The pixel kind of a level-1 kernel (template parameter PX): PX_F64 reads / writes the dense float64 planes a.in / a.out,
 // the integer kinds the strided view a.px (common.h: PxView; byte strides, so a sample's address is formed in bytes for
-// both) -- the value of an integer kind is its element size.  PX_FLT: the inverse kernels' float32 / float16 / bfloat16
-// store (floatpx.h) through the same view; which of the three is the view's `kind`, uniform over the launch, so the one
-// instantiation serves them all (every kind multiplies the level-1 inverse kernels by the wavelet instantiations).
+// both) -- the value of an integer kind is its element size.  PX_FLT: float32 / float16 / bfloat16 samples (floatpx.h)
+// through the same view, stored by the inverse kernels (rounded once) and loaded by the forward ones (widened exactly);
+// which of the three is the view's `kind`, uniform over the launch, so the one instantiation serves them all (every kind
+// multiplies the level-1 kernels by the wavelet instantiations).
 enum PxKind : int { PX_F64 = 0, PX_U8 = 1, PX_U16 = 2, PX_FLT = 3 };
 // the pixel kind of a launch into / out of the view px
 static inline int px_kind_of(const PxView &px) { return px.kind ? PX_FLT : px.es == 2 ? PX_U16 : PX_U8; }
@@ -203,12 +204,15 @@ __device__ __forceinline__ void flt_store(uint8_t *p, double v, int kind) {
     if (kind == SPIHT_FLT_F32) *reinterpret_cast<uint32_t *>(p) = b;
     else *reinterpret_cast<uint16_t *>(p) = (uint16_t)b;
 }
-template <int PX> __device__ __forceinline__ uint32_t px_load(const uint8_t *p) {  // the raw sample, not yet converted
-    if constexpr (PX == PX_U16) return *reinterpret_cast<const uint16_t *>(p);
+// (kind: the view's, read by PX_FLT alone -- 4 bytes of float32, else the 2 of float16 / bfloat16; widened exactly, floatpx.h)
+template <int PX> __device__ __forceinline__ uint32_t px_load(const uint8_t *p, int kind = 0) {  // the raw sample, not yet converted
+    if constexpr (PX == PX_FLT) return kind == SPIHT_FLT_F32 ? *reinterpret_cast<const uint32_t *>(p) : (uint32_t)*reinterpret_cast<const uint16_t *>(p);
+    else if constexpr (PX == PX_U16) return *reinterpret_cast<const uint16_t *>(p);
     else return *p;
 }
-template <int PX> __device__ __forceinline__ double px_value(uint32_t raw) {
-    if constexpr (PX == PX_U16) return px16_value((uint16_t)raw);
+template <int PX> __device__ __forceinline__ double px_value(uint32_t raw, int kind = 0) {
+    if constexpr (PX == PX_FLT) return flt_load_value(raw, kind);
+    else if constexpr (PX == PX_U16) return px16_value((uint16_t)raw);
     else return px8_value((uint8_t)raw);
 }
 // p[o] = the stored form of v.  The 8-bit statement is the one the kernels held before there was a second integer kind,
@@ -256,7 +260,8 @@ __device__ __forceinline__ void xcd_tile_fd(uint32_t L, const DwtKArgs &a, uint3
 // a zero tap contributes exactly nothing (0*x added to the running sum), so skipping it changes no bit and
 // removes a third (bior2.2) to a fifth of the float64 arithmetic.
 // One tile of k_dwt_level.
-// PX != PX_F64: the level's input is the strided 8- or 16-bit picture a.px (common.h: PxView), converted on the loads.
+// PX != PX_F64: the level's input is the strided 8- or 16-bit picture a.px (common.h: PxView), converted on the loads;
+// PX_FLT: the strided float32 / float16 / bfloat16 picture of kind a.px.kind, widened on the loads (nothing scaled).
 // WIDE == false (the launcher's choice, dwt_narrow_ok: every plane under 2^30 bytes): the input plane, the packed array's
 // plane and the approximation's plane are addressed through buffer descriptors with 32-bit byte offsets -- a load is one LDS
 // word (the row's offset) + the lane's column offset, a store is an offset advanced by a launch-time constant, and rows and
@@ -310,13 +315,18 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
             double x[F];
             if constexpr (PX != PX_F64) {
                 uint32_t raw[F];
+                if (PX == PX_FLT && a.px.kind == SPIHT_FLT_F32) {  // (the kind is uniform over the launch: one branch around the item's loads)
 #pragma unroll
-                for (int t = 0; t < F; t++) {
-                    if constexpr (PX == PX_U16) raw[t] = __builtin_amdgcn_raw_buffer_load_b16(rs_in, s_off[2 * o + t] + cb, 0, 0);
-                    else raw[t] = __builtin_amdgcn_raw_buffer_load_b8(rs_in, s_off[2 * o + t] + cb, 0, 0);
+                    for (int t = 0; t < F; t++) raw[t] = __builtin_amdgcn_raw_buffer_load_b32(rs_in, s_off[2 * o + t] + cb, 0, 0);
+                } else {
+#pragma unroll
+                    for (int t = 0; t < F; t++) {
+                        if constexpr (PX == PX_U8) raw[t] = __builtin_amdgcn_raw_buffer_load_b8(rs_in, s_off[2 * o + t] + cb, 0, 0);
+                        else raw[t] = __builtin_amdgcn_raw_buffer_load_b16(rs_in, s_off[2 * o + t] + cb, 0, 0);
+                    }
                 }
 #pragma unroll
-                for (int t = 0; t < F; t++) x[t] = px_value<PX>(raw[t]);
+                for (int t = 0; t < F; t++) x[t] = px_value<PX>(raw[t], a.px.kind);
             } else {
 #pragma unroll
                 for (int t = 0; t < F; t++)
@@ -355,19 +365,34 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
                                            // compiler waited for each load before it issued the next: level 1 took 7.1
                                            // instead of 4.3 ms), then k -> k / 255.0 (k / 65535.0)
                 uint32_t raw[NRP];
+                if (PX == PX_FLT && a.px.kind == SPIHT_FLT_F32) {  // a float kind: the same order -- every load, then the widening.
+                                                                   // The kind is uniform over the launch, so the one branch stands
+                                                                   // around all of a thread's loads, not between them
 #pragma unroll
-                for (int q = 0; q < NRP / 4; q++) {
-                    const uint4 o4 = so[q];
-                    const uint32_t o[4] = {o4.x, o4.y, o4.z, o4.w};
+                    for (int q = 0; q < NRP / 4; q++) {
+                        const uint4 o4 = so[q];
+                        const uint32_t o[4] = {o4.x, o4.y, o4.z, o4.w};
 #pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        if (4 * q + e >= NR) continue;
-                        if constexpr (PX == PX_U16) raw[4 * q + e] = __builtin_amdgcn_raw_buffer_load_b16(rs_in, o[e] + cb, 0, 0);
-                        else raw[4 * q + e] = __builtin_amdgcn_raw_buffer_load_b8(rs_in, o[e] + cb, 0, 0);
+                        for (int e = 0; e < 4; e++) {
+                            if (4 * q + e >= NR) continue;
+                            raw[4 * q + e] = __builtin_amdgcn_raw_buffer_load_b32(rs_in, o[e] + cb, 0, 0);
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < NRP / 4; q++) {
+                        const uint4 o4 = so[q];
+                        const uint32_t o[4] = {o4.x, o4.y, o4.z, o4.w};
+#pragma unroll
+                        for (int e = 0; e < 4; e++) {
+                            if (4 * q + e >= NR) continue;
+                            if constexpr (PX == PX_U8) raw[4 * q + e] = __builtin_amdgcn_raw_buffer_load_b8(rs_in, o[e] + cb, 0, 0);
+                            else raw[4 * q + e] = __builtin_amdgcn_raw_buffer_load_b16(rs_in, o[e] + cb, 0, 0);
+                        }
                     }
                 }
 #pragma unroll
-                for (int r = 0; r < NR; r++) x[r] = px_value<PX>(raw[r]);
+                for (int r = 0; r < NR; r++) x[r] = px_value<PX>(raw[r], a.px.kind);
             } else {
 #pragma unroll
                 for (int q = 0; q < NRP / 4; q++) {
@@ -393,10 +418,10 @@ __device__ __forceinline__ void dwt_tile(const DwtKArgs &a, double (&s_lo)[2][PS
                     const long long off = s_off64[r + lz];
                     const bool ok = a.mode != 3 || (gc >= 0 && off >= 0);
                     okm |= (ok ? 1ull : 0ull) << r;
-                    raw[r] = px_load<PX>(in8 + (ok ? off + co8 : 0));
+                    raw[r] = px_load<PX>(in8 + (ok ? off + co8 : 0), a.px.kind);
                 }
 #pragma unroll
-                for (int r = 0; r < NR; r++) x[r] = ((okm >> r) & 1ull) ? px_value<PX>(raw[r]) : 0.0;
+                for (int r = 0; r < NR; r++) x[r] = ((okm >> r) & 1ull) ? px_value<PX>(raw[r], a.px.kind) : 0.0;
             } else if (a.mode != 3) {  // not zero padding: every index is inside the picture
 #pragma unroll
                 for (int r = 0; r < NR; r++) x[r] = in[s_off64[r + lz] + gc];
@@ -585,7 +610,7 @@ __global__ __launch_bounds__(256) void k_dwt_edge(DwtKArgs a) {
             double xv[F];
 #pragma unroll
             for (int r = 0; r < F; r++) {
-                if (PX) xv[r] = (gc < 0 || gr[r] < 0) ? 0.0 : px_value<PX>(px_load<PX>(in8 + ((int64_t)gr[r] * a.px.sh + (int64_t)gc * a.px.sw)));
+                if (PX) xv[r] = (gc < 0 || gr[r] < 0) ? 0.0 : px_value<PX>(px_load<PX>(in8 + ((int64_t)gr[r] * a.px.sh + (int64_t)gc * a.px.sw), a.px.kind), a.px.kind);
                 else xv[r] = (gc < 0 || gr[r] < 0) ? 0.0 : in[(size_t)gr[r] * a.in_w + gc];
             }
             double tl = 0.0, th = 0.0;
@@ -859,8 +884,14 @@ void k_dwt1_color(DwtKArgs a, uint32_t gx, uint32_t gy) {                       
         const bool z = gc < 0 || gr < 0;
         if (PX) {  // (the pixel's three channels sc bytes apart: neighbours in an interleaved picture)
             const int64_t o = z ? 0 : (int64_t)gr * a.px.sh + (int64_t)gc * a.px.sw;
-            u0 = px_value<PX>(px_load<PX>(in8 + o)); u1 = px_value<PX>(px_load<PX>(in8 + (o + a.px.sc)));
-            u2 = px_value<PX>(px_load<PX>(in8 + (o + 2 * a.px.sc)));
+            if constexpr (PX == PX_FLT) {  // the three loads, then the widenings (the kind is uniform over the launch)
+                const uint32_t r0 = px_load<PX>(in8 + o, a.px.kind), r1 = px_load<PX>(in8 + (o + a.px.sc), a.px.kind);
+                const uint32_t r2 = px_load<PX>(in8 + (o + 2 * a.px.sc), a.px.kind);
+                u0 = px_value<PX>(r0, a.px.kind); u1 = px_value<PX>(r1, a.px.kind); u2 = px_value<PX>(r2, a.px.kind);
+            } else {
+                u0 = px_value<PX>(px_load<PX>(in8 + o)); u1 = px_value<PX>(px_load<PX>(in8 + (o + a.px.sc)));
+                u2 = px_value<PX>(px_load<PX>(in8 + (o + 2 * a.px.sc)));
+            }
         } else {
             const size_t o = z ? 0 : (size_t)gr * a.in_w + gc;
             u0 = in[o]; u1 = in[o + npl]; u2 = in[o + 2 * npl];
@@ -1844,7 +1875,7 @@ static uint32_t dwt_set_launch_consts(DwtKArgs &a, int planes, int px) {
 template <int F, uint32_t LOM, uint32_t HIM>
 static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
     a.planes = planes;
-    const int px = a.px.in == nullptr ? PX_F64 : a.px.es == 2 ? PX_U16 : PX_U8;
+    const int px = a.px.in == nullptr ? PX_F64 : px_kind_of(a.px);
     a.ov_h = a.out_h;
     a.ov_w = a.out_w;
     if (a.f32) {
@@ -1859,7 +1890,8 @@ static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
         if (a.mode != 4) a.ov_h = min(a.out_h, (a.in_h + z + 2) / 2);
         if (a.mode != 4) a.ov_w = min(a.out_w, (a.in_w + z + 2) / 2);
         const uint32_t gx = (uint32_t)((a.out_w + SW - 1) / SW), gy = (uint32_t)((a.out_h + C1_ROWS - 1) / C1_ROWS);
-        if (px == PX_U16) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, PX_U16>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
+        if (px == PX_FLT) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, PX_FLT>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
+        else if (px == PX_U16) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, PX_U16>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
         else if (px == PX_U8) hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM, PX_U8>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
         else hipLaunchKernelGGL((k_dwt1_color<F, LOM, HIM>), dim3(gx * gy * (uint32_t)(planes / 3)), dim3(256), 0, st, a, gx, gy);
         return (int)hipGetLastError();
@@ -1875,17 +1907,20 @@ static int launch_dwt_FM(DwtKArgs a, int planes, hipStream_t st) {
     if (a.mode != 4) a.ov_w = min(a.out_w, (a.in_w + z + 2) / 2);
     const uint32_t nt = dwt_set_launch_consts(a, planes, px);
     if (a.narrow) {
-        if (px == PX_U16) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U16>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+        if (px == PX_FLT) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_FLT>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+        else if (px == PX_U16) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U16>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
         else if (px == PX_U8) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U8>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
         else hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
     } else {
-        if (px == PX_U16) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U16, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+        if (px == PX_FLT) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_FLT, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
+        else if (px == PX_U16) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U16, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
         else if (px == PX_U8) hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_U8, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
         else hipLaunchKernelGGL((k_dwt_level<F, LOM, HIM, PX_F64, true>), dim3(nt), dim3(DWF_BLOCK), 0, st, a);
     }
     const int n_edge = (a.out_h - a.ov_h) * a.out_w + a.ov_h * (a.out_w - a.ov_w);
     if (n_edge > 0) {
-        if (px == PX_U16) hipLaunchKernelGGL((k_dwt_edge<F, PX_U16>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
+        if (px == PX_FLT) hipLaunchKernelGGL((k_dwt_edge<F, PX_FLT>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
+        else if (px == PX_U16) hipLaunchKernelGGL((k_dwt_edge<F, PX_U16>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
         else if (px == PX_U8) hipLaunchKernelGGL((k_dwt_edge<F, PX_U8>), dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_dwt_edge<F>, dim3((n_edge + 255) / 256, planes), dim3(256), 0, st, a);
     }
@@ -2052,14 +2087,15 @@ extern "C" int spiht_launch_dequant_plain(const int32_t *in, double *out, size_t
 
 // ---- 8- and 16-bit pixels to and from dense float64, for the routes whose level 1 has no integer form ------------------------
 // (level 0, the two-pass levels, the colour model change in front of a two-pass level).  One thread per sample, the same
-// conversions as the fused kernels (px_value / PX_STORE); the kind is the view's element size.
+// conversions as the fused kernels (px_value / PX_STORE); the kind is the view's element size, or its float kind (both ways:
+// k_px_to_f64<PX_FLT> is the exact widening of float pixels in, spiht_widen_batch_flt runs it alone).
 template <int PX>
 __global__ __launch_bounds__(256) void k_px_to_f64(PxView px, double *__restrict__ out, int64_t n) {  // out [B*c, h, w]
     const int64_t hw = (int64_t)px.h * px.w;
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
         const int64_t p = t / hw, r = t - p * hw, y = r / px.w, x = r - y * px.w;
         const int64_t o = (p / px.c) * px.sb + (p % px.c) * px.sc + y * px.sh + x * px.sw;
-        out[t] = px_value<PX>(px_load<PX>(px.in + o));
+        out[t] = px_value<PX>(px_load<PX>(px.in + o, px.kind), px.kind);
     }
 }
 template <int PX>
@@ -2075,7 +2111,8 @@ static unsigned pass_grid(int64_t n) { return (unsigned)std::min<int64_t>(std::m
 extern "C" int spiht_launch_px_to_f64(const PxView *px, int64_t B, double *out, hipStream_t st) {
     const int64_t n = B * px->c * (int64_t)px->h * px->w;
     if (n <= 0) return 0;
-    if (px->es == 2) hipLaunchKernelGGL(k_px_to_f64<PX_U16>, dim3(pass_grid(n)), dim3(256), 0, st, *px, out, n);
+    if (px->kind) hipLaunchKernelGGL(k_px_to_f64<PX_FLT>, dim3(pass_grid(n)), dim3(256), 0, st, *px, out, n);
+    else if (px->es == 2) hipLaunchKernelGGL(k_px_to_f64<PX_U16>, dim3(pass_grid(n)), dim3(256), 0, st, *px, out, n);
     else hipLaunchKernelGGL(k_px_to_f64<PX_U8>, dim3(pass_grid(n)), dim3(256), 0, st, *px, out, n);
     return (int)hipGetLastError();
 }

@@ -50,3 +50,14 @@ FLT_HD uint32_t flt_store_value(double v, int kind) {
     if (v != v) return (b >> 16) | 0x40u;                 // NaN: the quiet one of its sign (the rounding below could carry out of it)
     return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;        // nearest even on the float32 bits; a carry runs up to infinity by itself
 }
+
+// Float pixels in (include/spiht_hip.h, the encode side of *_flt): the bit pattern of a sample of the kind (in the low 16 bits
+// for the two 16-bit kinds) as the double of the same value -- the rule of spiht_amd/floatpx.py: to_float64.  Every step is
+// exact: float32 -> float64 is the hardware's conversion, float16 goes half -> float -> double (each type holds every value
+// of the one before it), and a bfloat16 is the upper half of the float32 of the same value.  Subnormals keep their value (no
+// flush, see above), the sign of zero is kept, infinities stay, a NaN gives a NaN.  `kind` is uniform wherever this is called.
+FLT_HD double flt_load_value(uint32_t raw, int kind) {
+    if (kind == SPIHT_FLT_F32) return (double)__builtin_bit_cast(float, raw);
+    if (kind == SPIHT_FLT_F16) return (double)(float)__builtin_bit_cast(_Float16, (uint16_t)raw);
+    return (double)__builtin_bit_cast(float, raw << 16);
+}

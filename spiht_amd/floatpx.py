@@ -1,4 +1,4 @@
-"""Float pixels out: the host rule the device conversion equals (csrc/floatpx.h: flt_store_value).
+"""Float pixels out and in: the host rules the device conversions equal (csrc/floatpx.h: flt_store_value, flt_load_value).
 
 A decode into a float kind -- float32, float16 or bfloat16 -- returns, bit for bit,
 
@@ -14,6 +14,15 @@ patterns, and the rule is written out below in integer arithmetic on the float64
 torch is NOT the yardstick for the narrowing direction: its CPU conversion from float64 goes through float32 and so rounds
 twice.  1 + 2^-8 + 2^-40 becomes 0x3F80 there, where one rounding gives 0x3F81, and 1 + 2^-11 + 2^-40 becomes the float16
 0x3C00, where numpy gives 0x3C01.  The widening direction (bfloat16_to_float64) is exact everywhere.
+
+Float pixels IN go the other way: an encode of a picture P of a float kind returns, field by field and bit for bit, what
+the float64 call returns for
+
+    to_float64(P, kind)
+
+the exact widening of every sample -- nothing scaled, nothing clipped, subnormals of every kind keep their value.  This is
+NOT encode_image(P32): a float32 array given to encode_image keeps the reference's single-precision transform, the same
+array given to encode_image_float is transformed in float64.
 
 This module is to the kernels what overlap.py and alloc.py are: no device, no library, numpy only.
 """
@@ -105,6 +114,40 @@ def convert(a, kind):
         return bfloat16_bits(a)
     with np.errstate(over="ignore", under="ignore", invalid="ignore"):
         return a.astype(storage_dtype(kind))
+
+
+def to_float64(a, kind):
+    """array of the kind (storage_dtype: float32, float16, or uint16 bit patterns for bfloat16) -> float64, exact: the rule of
+    float pixels in.  Subnormals keep their value, the sign of zero is kept, infinities stay, a NaN gives a NaN."""
+    kind = kind_id(kind)
+    if kind == BFLOAT16:
+        return bfloat16_to_float64(a).reshape(np.shape(a))
+    a = np.asarray(a)
+    if a.dtype.newbyteorder("=") != storage_dtype(kind):
+        raise TypeError("a %s picture comes as a %s array, not %s" % (kind_name(kind), storage_dtype(kind).name, a.dtype))
+    with np.errstate(invalid="ignore"):
+        return a.astype(np.float64)
+
+
+def input_kind(a, dtype, name):
+    """The kind of the picture `a` given to the encode call `name` with dtype=`dtype`: inferred from a float32 / float16 array
+    (a dtype, if given, must say the same); uint16 bit patterns need dtype="bfloat16" or torch.bfloat16.  ValueError for an
+    array that is no float picture or does not match its dtype, TypeError for a dtype that is no float kind."""
+    if not isinstance(a, np.ndarray):
+        raise ValueError("%s takes a float32, float16 or (bfloat16 bit patterns) uint16 array, not %s" % (name, type(a)))
+    have = a.dtype.newbyteorder("=")
+    if dtype is None:
+        if have == np.float32:
+            return FLOAT32
+        if have == np.float16:
+            return FLOAT16
+        if have == np.uint16:
+            raise TypeError("%s: a uint16 array of bit patterns needs dtype=\"bfloat16\"" % name)
+        raise ValueError("%s takes a float32, float16 or (bfloat16 bit patterns) uint16 array, not %s" % (name, a.dtype))
+    kind = kind_id(dtype)
+    if have != storage_dtype(kind):
+        raise ValueError("%s takes a %s array for dtype=%s, not %s" % (name, storage_dtype(kind).name, kind_name(kind), a.dtype))
+    return kind
 
 
 def check_float_view(dtype, shape, strides, output):

@@ -283,7 +283,8 @@ def _u8_picture(image, spiht_settings):
     return _int_picture(image, spiht_settings, np.uint8, "encode_image_u8")
 
 
-def _encode_image_int(image, spiht_settings, level, max_bits, channels_last, dtype, name, fn_name):
+def _encode_image_int(image, spiht_settings, level, max_bits, channels_last, dtype, name, fn_name, kind=()):
+    """kind: () for the integer calls, (kind id,) for the *_flt ones -- the argument behind the context"""
     if _is_dtype(image, dtype) and image.ndim == 3 and channels_last:
         image = image.transpose(2, 0, 1)
     image = _int_picture(image, spiht_settings, dtype, name)
@@ -295,10 +296,13 @@ def _encode_image_int(image, spiht_settings, level, max_bits, channels_last, dty
         max_bits = 99999999999999999
     max_bits = spiht_rs._as_usize(max_bits, "max_bits")
     strides = np.array(image.strides, dtype=np.int64)
-    _check_int_view(8 * np.dtype(dtype).itemsize, image.shape, strides, False)
+    if kind:
+        floatpx.check_float_view(kind[0], image.shape, strides, False)
+    else:
+        _check_int_view(8 * np.dtype(dtype).itemsize, image.shape, strides, False)
     _check_aligned(image.ctypes.data, dtype)
     return _encode_host(_lib.default_context(), getattr(_lib.lib(), fn_name),
-                        (C.c_void_p(image.ctypes.data), C.c_void_p(strides.ctypes.data)), (c, h, w), g, wid, mid, level,
+                        (*kind, C.c_void_p(image.ctypes.data), C.c_void_p(strides.ctypes.data)), (c, h, w), g, wid, mid, level,
                         spiht_settings, mults_p, max_bits)
 
 
@@ -347,6 +351,22 @@ def decode_image_u16(encoding_result: EncodingResult, spiht_settings: SpihtSetti
     with the conversion done on the device.  Returns a new uint16 array (c, h, w), or (h, w, c) with channels_last.  The
     stream may come from any pixel format."""
     return _decode_image_int(encoding_result, spiht_settings, channels_last, np.uint16, "spiht_decode_image_host_u16")
+
+
+def encode_image_float(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSettings(), level: Optional[int] = None,
+                       max_bits: Optional[int] = None, dtype=None, channels_last: bool = False):
+    """Float pixels in: the EncodingResult of encode_image(floatpx.to_float64(image, kind), ...), field by field -- every
+    sample widened EXACTLY to float64 on the device (nothing scaled, nothing clipped, subnormals kept), then the float64
+    codec with all it has (colour model, every mode and wavelet) -- so that 4 or 2 bytes per sample cross the link.
+    This is NOT encode_image(image): a float32 array given to encode_image keeps the reference's single-precision
+    transform; given to this call it is transformed in float64.
+    image: float32 or float16 (c, h, w), or (h, w, c) with channels_last -- any non-negative strides (a four-sample buffer's
+    [..., :3] view goes as it is; a negative stride or the other byte order is copied first); for bfloat16 the uint16 bit
+    patterns with dtype="bfloat16" or torch.bfloat16 (floatpx.kind_arg).  The kind is inferred from a float32 / float16
+    array.  Non-finite samples are outside the contract, as they are for encode_image."""
+    kind = floatpx.input_kind(image, dtype, "encode_image_float")
+    return _encode_image_int(image, spiht_settings, level, max_bits, channels_last, floatpx.storage_dtype(kind),
+                             "encode_image_float", "spiht_encode_image_host_flt", (kind,))
 
 
 def decode_image_float(encoding_result: EncodingResult, spiht_settings: SpihtSettings, dtype=np.float32,

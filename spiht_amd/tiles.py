@@ -393,8 +393,8 @@ _SUFFIX = {np.dtype(np.uint8): "u8", np.dtype(np.uint16): "u16", np.dtype(np.flo
 
 
 class _FloatKind:
-    """the element type of float pixels OUT (floatpx: float32, float16, bfloat16), where the others are an np.dtype: the kind's
-    id, its bytes per sample and the numpy type its pictures come in (bfloat16: uint16 bit patterns)"""
+    """the element type of float pixels out and in (floatpx: float32, float16, bfloat16), where the others are an np.dtype: the
+    kind's id, its bytes per sample and the numpy type its pictures come in (bfloat16: uint16 bit patterns)"""
     kind = "F"  # (np.dtype.kind of the others: "u", "f")
 
     def __init__(self, dtype):
@@ -408,25 +408,31 @@ def _elem(dtype):
     return dtype if isinstance(dtype, _FloatKind) else np.dtype(dtype)
 
 
-# float pixels out: a tile batch of a kind is copied as elements of its size -- both 16-bit kinds by the uint16 copies, float32
-# by the strided 4-byte ones; the blend rounds to the kind at its store
+# float pixels out and in: a tile batch of a kind is copied as elements of its size -- both 16-bit kinds by the uint16 copies,
+# float32 by the strided 4-byte ones; the blend rounds to the kind at its store, the error sums widen the original's samples
 _FLOAT_COPY = {("spiht_tile_paste_", 2): "spiht_tile_paste_u16", ("spiht_tile_paste_", 4): "spiht_tile_paste_f32s",
-               ("spiht_tile_mosaic_", 2): "spiht_tile_mosaic_u16", ("spiht_tile_mosaic_", 4): "spiht_tile_mosaic_f32"}
+               ("spiht_tile_mosaic_", 2): "spiht_tile_mosaic_u16", ("spiht_tile_mosaic_", 4): "spiht_tile_mosaic_f32",
+               ("spiht_tile_cut_", 2): "spiht_tile_cut_u16", ("spiht_tile_cut_", 4): "spiht_tile_cut_f32s",
+               ("spiht_tile_cut_overlap_", 2): "spiht_tile_cut_overlap_u16",
+               ("spiht_tile_cut_overlap_", 4): "spiht_tile_cut_overlap_f32s"}
+_FLOAT_KIND_CALL = ("spiht_tile_blend_", "spiht_sse_tiles_", "spiht_sse_tiles_w_")  # entry points that take the kind
 
 
 def _entry(L, stem, dt):
     """the library's entry point of that stem for an element type (an np.dtype): (L, "spiht_tile_paste_", uint16) ->
-    L.spiht_tile_paste_u16; for a _FloatKind the copy of its element size, or the blend into the kind"""
+    L.spiht_tile_paste_u16; for a _FloatKind the copy of its element size, or the *_flt call with the kind behind the context
+    (the blend into the kind, the error sums of tiles of the kind)"""
     if isinstance(dt, _FloatKind):
-        if stem == "spiht_tile_blend_":
-            return lambda ctx, *a: L.spiht_tile_blend_flt(ctx, dt.id, *a)
+        if stem in _FLOAT_KIND_CALL:
+            fn = getattr(L, stem + "flt")
+            return lambda ctx, *a: fn(ctx, dt.id, *a)
         return getattr(L, _FLOAT_COPY[stem, dt.itemsize])
     return getattr(L, stem + _SUFFIX[dt])
 
 
 def _peak(dtype):
     """the largest pixel value: of 8- and 16-bit pixels the type's, of float pixels 1.0"""
-    return float(np.iinfo(dtype).max) if np.dtype(dtype).kind == "u" else 1.0
+    return float(np.iinfo(dtype).max) if _elem(dtype).kind == "u" else 1.0
 
 
 class TiledCodec:
@@ -510,8 +516,8 @@ class TiledCodec:
 
     def _tile_call(self, op, dt):
         """the tile codec's batched call for an element type (an np.dtype); op: "encode", "decode" or "decode_reduced".  The
-        float form is the one of the codec's own float pixels; a _FloatKind: the *_float decode, which takes the kind behind the
-        output (behind `reduce`)"""
+        float form is the one of the codec's own float pixels; a _FloatKind: the *_float call, which takes the kind behind the
+        output (behind `reduce`; an encode: behind d_max_n)"""
         if isinstance(dt, _FloatKind):
             return getattr(self.codec, op + "_device_float")
         return getattr(self.codec, op + "_device" + ("_" + _SUFFIX[dt] if dt.kind == "u" else ""))
@@ -549,7 +555,7 @@ class TiledCodec:
         """what a call with a weight map needs of the codec, before anything is uploaded or queued"""
         if self.allocate is None:
             raise ValueError('%s: a weight map steers allocate="rd"; the codec was not built with it' % name)
-        if np.dtype(dtype).kind == "u" and self.c * self.th * self.tw > alloc.ROI_MAX_TILE_SAMPLES:
+        if _elem(dtype).kind == "u" and self.c * self.th * self.tw > alloc.ROI_MAX_TILE_SAMPLES:
             raise ValueError("%s: the exact weighted sum of integer pixels takes tiles of c * th * tw <= 2^24 samples, not %d"
                              % (name, self.c * self.th * self.tw))
 
@@ -639,7 +645,8 @@ class TiledCodec:
         """the cut and the batched encode of the N * T tiles -> (element type, the buffers of the tiles, the stream slots and
         the streams' lengths in bits)"""
         N = int(N)
-        dt = np.dtype(d_img.dtype)
+        dt = _elem(d_img.dtype)
+        flt = isinstance(dt, _FloatKind)  # float pixels in: a view of the kind, cut as elements of its size
         NT, vp = N * self.T, C.c_void_p
         if N < 1:
             raise ValueError("%s: no pictures" % name)
@@ -650,16 +657,16 @@ class TiledCodec:
         if self.overlap:
             geom, stem = geom + (self.overlap,), "spiht_tile_cut_overlap_"
         view = ()  # the integer forms take a view of the pictures: the strides, behind the address
-        if dt.kind == "u":
+        if dt.kind == "u" or flt:
             st, st_p = self._strides_arg((N, self.c, self.H, self.W), strides, False, dt)
-            _check_aligned(d_img.ptr, dt)
+            _check_aligned(d_img.ptr, dt.storage if flt else dt)
             view = (st_p,)
         elif dt != self.pixel_dtype or strides is not None:
             raise ValueError("%s: %s pictures, the codec's are dense %s" % (name, dt.name, self.pixel_dtype.name))
         _lib.check(_entry(self.L, stem, dt)(self.ctx.handle, vp(d_img.ptr), *view, *geom, vp(d_tiles.ptr)))
         d_slots = self._buf("slots", NT * self.codec.slot_stride)
         d_nbits = self._buf("nbits", NT * 8)
-        self._tile_call("encode", dt)(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
+        self._tile_call("encode", dt)(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr, *((dt.id,) if flt else ()))
         return dt, d_tiles, d_slots, d_nbits
 
     def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi, budgets, d_target=None, s=""):
@@ -688,9 +695,13 @@ class TiledCodec:
         """the NT full streams in d_slots -> the buffer "D": float64 / uint64 [K + 1][NT], the error of every tile at its K + 1
         candidate lengths; roi = (address, stride) of a device weight map: the weighted error.  overlap > 0: the error of the
         CODED tiles, margins and padding included -- the sums are taken with the geometry of a picture of gy x gx whole coded
-        tiles, in which every tile's valid extent is the whole tile -- not the error of the blended picture"""
+        tiles, in which every tile's valid extent is the whole tile -- not the error of the blended picture.  Tiles of a float
+        kind (float pixels in) are measured against float64 decodes, their samples widened in the sums (spiht_sse_tiles_flt)"""
         NT, K, vp, c = N * self.T, self.points, C.c_void_p, self.c
         stride = self.codec.slot_stride
+        tile_dt = dt
+        if isinstance(dt, _FloatKind):
+            dt = np.dtype(np.float64)  # (the decodes' element)
         integer = dt.kind == "u"
         rh, rw = (self.cth, self.ctw) if integer else (self.codec.geom["rec_h"], self.codec.geom["rec_w"])
         H, W = (self.gy * self.cth, self.gx * self.ctw) if self.overlap else (self.H, self.W)
@@ -702,9 +713,9 @@ class TiledCodec:
         d_D = self._buf("D", (K + 1) * NT * 8)
         dec = self._tile_call("decode", dt)
         if roi is None:
-            sse, w_args = _entry(self.L, "spiht_sse_tiles_", dt), ()
+            sse, w_args = _entry(self.L, "spiht_sse_tiles_", tile_dt), ()
         else:
-            sse, w_args = _entry(self.L, "spiht_sse_tiles_w_", dt), (vp(roi[0]), roi[1])
+            sse, w_args = _entry(self.L, "spiht_sse_tiles_w_", tile_dt), (vp(roi[0]), roi[1])
         for k0 in range(0, K + 1, G):
             g = min(G, K + 1 - k0)
             _lib.check(self.L.spiht_tile_prefix_slots(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, K, k0, g,
@@ -964,6 +975,32 @@ class TiledCodec:
         """uint16 pictures -> what encode gives for pictures / 65535.0"""
         return self._encode_host(image_or_images, np.uint16, channels_last, "encode_u16", roi, target_psnr)
 
+    # ---- float pixels in (floatpx): what the float64 call gives for floatpx.to_float64 of the pictures, every sample widened
+    # exactly on the device -- the float64 arithmetic of a float64 codec, NOT the single-precision transform of a float32 codec.
+    # dtype: None (inferred from a float32 / float16 array) or what floatpx.kind_arg takes ("bfloat16" for uint16 bit patterns).
+    def encode_float(self, image_or_images, dtype=None, channels_last=False, roi=None, target_psnr=None):
+        """pictures of a float kind [c, H, W] / [N, c, H, W] (or [H, W, c] / [N, H, W, c] with channels_last) -> what encode gives
+        for floatpx.to_float64(pictures, kind): allocate="rd", roi and target_psnr as there, with the same ValueErrors"""
+        kind = floatpx.input_kind(np.asarray(image_or_images), dtype, "encode_float")
+        return self._encode_host(image_or_images, _FloatKind(kind), channels_last, "encode_float", roi, target_psnr)
+
+    def encode_layered_float(self, image_or_images, layers=None, dtype=None, channels_last=False, roi=None, target_psnr=None):
+        """encode_layered of pictures of a float kind, as encode_float"""
+        kind = floatpx.input_kind(np.asarray(image_or_images), dtype, "encode_layered_float")
+        return self._encode_host(image_or_images, _FloatKind(kind), channels_last, "encode_layered_float", roi, target_psnr, True,
+                                 layers)
+
+    def encode_device_float(self, d_img, N, d_packed, d_lens, d_max_n, dtype, strides=None, d_roi=None, roi_stride=0,
+                            d_target=None):
+        """encode_device of N pictures of the kind `dtype` on the device (a DeviceArray or an address), laid out by `strides`
+        (BYTES (sb, sc, sh, sw), non-negative multiples of the element size, as the base; None: dense CHW)"""
+        self.encode_device(_View(_ptr(d_img), _FloatKind(dtype)), N, d_packed, d_lens, d_max_n, strides, d_roi, roi_stride, d_target)
+
+    def tile_curves_float(self, image, dtype=None, roi=None):
+        """tile_curves of one picture of a float kind: the curves of tile_curves(floatpx.to_float64(image, kind))"""
+        image = np.asarray(image)
+        return self.tile_curves(image, _FloatKind(floatpx.input_kind(image, dtype, "tile_curves_float")), roi)
+
     def _upload_pictures(self, images, dtype, channels_last, name):
         """the host checks of _encode_host and the upload -> (single, N, the device view, strides)"""
         images = np.asarray(images)
@@ -972,15 +1009,16 @@ class TiledCodec:
             images = images[None]
         if images.ndim != 4:
             raise ValueError("%s takes a picture [c, H, W] or pictures [N, c, H, W]" % name)
-        dtype = np.dtype(dtype)
+        dtype = _elem(dtype)
         strides = None
-        if dtype.kind == "u":
-            if not _is_dtype(images, dtype):
-                raise ValueError("%s takes a %s array, not %s" % (name, dtype.name, images.dtype))
-            images = np.ascontiguousarray(images, dtype=dtype.newbyteorder("="))
+        if dtype.kind == "u" or isinstance(dtype, _FloatKind):  # (a float kind goes in as its storage type: bit patterns)
+            sd = dtype.storage if isinstance(dtype, _FloatKind) else dtype
+            if not _is_dtype(images, sd):
+                raise ValueError("%s takes a %s array, not %s" % (name, sd.name, images.dtype))
+            images = np.ascontiguousarray(images, dtype=sd.newbyteorder("="))
             if channels_last:
                 N, H, W, c = images.shape
-                es = dtype.itemsize
+                es = sd.itemsize
                 strides = (H * W * c * es, es, W * c * es, c * es)
                 shape = (N, c, H, W)
             else:
@@ -1024,7 +1062,7 @@ class TiledCodec:
         image = np.asarray(image)
         if image.ndim != 3:
             raise ValueError("tile_curves takes one picture [c, H, W]")
-        dtype = self.pixel_dtype if dtype is None else np.dtype(dtype)
+        dtype = self.pixel_dtype if dtype is None else _elem(dtype)
         self._encode_host(image, dtype, False, "tile_curves", roi)
         T, K = self.T, self.points
         D = self._download(self._bufs["D"].ptr, (K + 1, T), np.uint64 if dtype.kind == "u" else np.float64)
@@ -1217,10 +1255,10 @@ def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_
     c, h, w = _picture_shape(image, channels_last)
     if dtype is None:
         dtype = np.float32 if image.dtype in (np.float32, np.float16) else np.float64
-    codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if np.dtype(dtype).kind == "f" else np.float64,
-                       allocate, points, spread, overlap)
-    return codec._encode_host(image, codec.pixel_dtype if np.dtype(dtype).kind == "f" else dtype, channels_last, name, roi,
-                              target_psnr)
+    own = _elem(dtype).kind == "f"  # the codec's own float pixels (integer pixels and the float kinds: a float64 codec)
+    codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if own else np.float64, allocate, points, spread,
+                       overlap)
+    return codec._encode_host(image, codec.pixel_dtype if own else dtype, channels_last, name, roi, target_psnr)
 
 
 def encode_image_tiled(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, allocate=None, points=alloc.POINTS,
@@ -1249,6 +1287,16 @@ def encode_image_tiled_u16(image, tile, spiht_settings=SpihtSettings(), level=No
     """uint16 pixels: the TiledResult of encode_image_tiled(image / 65535.0, ...); allocate="rd" measures 16-bit decodes"""
     return _encode_tiled(image, tile, spiht_settings, level, max_bits, np.uint16, channels_last, "encode_image_tiled_u16", allocate,
                          points, spread, roi, target_psnr, overlap)
+
+
+def encode_image_tiled_float(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, dtype=None, channels_last=False,
+                             allocate=None, points=alloc.POINTS, spread=alloc.SPREAD, roi=None, target_psnr=None, overlap=0):
+    """float pixels in (float32, float16, or uint16 bit patterns with dtype="bfloat16"): the TiledResult of
+    encode_image_tiled(floatpx.to_float64(image, kind), ...), every sample widened exactly on the device -- the float64
+    transform, not the single-precision one encode_image_tiled runs for a float32 array"""
+    kind = floatpx.input_kind(image, dtype, "encode_image_tiled_float")
+    return _encode_tiled(image, tile, spiht_settings, level, max_bits, _FloatKind(kind), channels_last, "encode_image_tiled_float",
+                         allocate, points, spread, roi, target_psnr, overlap)
 
 
 def _decode_tiled(result, spiht_settings, window, dtype, channels_last, reduce=0, layered=False, upto=None):
@@ -1345,6 +1393,14 @@ def encode_image_layered_u16(image, tile, spiht_settings=SpihtSettings(), level=
                              spread=alloc.SPREAD, channels_last=False, roi=None, target_psnr=None, overlap=0):
     return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, np.uint16, channels_last, "encode_image_layered_u16",
                            points, spread, roi, target_psnr, overlap)
+
+
+def encode_image_layered_float(image, tile, spiht_settings=SpihtSettings(), level=None, max_bits=None, layers=None, dtype=None,
+                               points=alloc.POINTS, spread=alloc.SPREAD, channels_last=False, roi=None, target_psnr=None, overlap=0):
+    """float pixels in: the LayeredResult of encode_image_layered(floatpx.to_float64(image, kind), ...)"""
+    kind = floatpx.input_kind(image, dtype, "encode_image_layered_float")
+    return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, _FloatKind(kind), channels_last,
+                           "encode_image_layered_float", points, spread, roi, target_psnr, overlap)
 
 
 def decode_image_layered(result, spiht_settings, upto=None, reduce=0):
