@@ -39,3 +39,17 @@ struct __attribute__((aligned(8))) F64x2 {
 
 // spiht_tile_allocate's scratch, per tile: K + 1 hull vertices (float64 distortion, uint32 length), K edge slopes, a count
 static inline size_t al_scratch_bytes(uint64_t NT, uint64_t K) { return (size_t)(NT * ((K + 1) * 12 + K * 8 + 4)); }
+
+// the launchers of alloc.hip and roi.hip (called from api.cpp)
+extern "C" {
+int spiht_launch_tile_prefix_slots(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbits, int64_t NT, int K, int k0,
+                                   int G, uint8_t *d_out, uint64_t out_stride, uint64_t *d_nbytes, const uint8_t *d_max_n,
+                                   uint8_t *d_max_n_out, hipStream_t st);
+int spiht_launch_sse_tiles(const TileSseArgs *a, int es, int64_t G, hipStream_t st);
+int spiht_launch_sse_tiles_w(const TileSseWArgs *q, int es, int64_t G, hipStream_t st);
+int spiht_launch_sse_tiles_flt(const TileSseArgs *a, int kind, int64_t G, hipStream_t st);
+int spiht_launch_sse_tiles_w_flt(const TileSseWArgs *q, int kind, int64_t G, hipStream_t st);
+int spiht_launch_tile_allocate(const uint64_t *d_nbits, const void *d_D, int kind, int K, int64_t N, int64_t T, uint64_t budget,
+                               const double *d_target, void *scratch, uint64_t *d_nbits_out, double *d_lambda, double *d_dist,
+                               uint32_t *d_met, hipStream_t st);
+}

@@ -346,3 +346,45 @@ struct LlPicArgs {
     PxView px;             // integer pictures
     Color3 col;
 };
+
+// The launchers of pyramid.hip, encode.hip, encode_wide.hip, decode.hip (built twice: 12 and 8 wavefronts), dwt.hip and
+// metadata.hip, as the host side (api.cpp, api_*.cpp) calls them: declared here so that the compiler holds every definition to its callers.
+extern "C" {
+int spiht_launch_absmax(const int32_t *d_x, int B, uint32_t n, uint32_t *d_maxabs, hipStream_t st);
+int spiht_launch_pyramid(const Geom *g, int B, const int32_t *d_x, uint8_t *d_dmsb, uint8_t *d_lmsb, hipStream_t st);
+int spiht_launch_encode(const EncArgs *a, hipStream_t st);
+int spiht_launch_encode_wide(const EncArgs *a, const WideArgs *w, int groups, hipStream_t st);
+int spiht_wide_groups_per_cu(void);
+int spiht_launch_decode(const DecArgs *a, hipStream_t st);
+int spiht_launch_decode_w8(const DecArgs *a, hipStream_t st);  // the 8-wavefront build of decode.hip
+int spiht_launch_unscatter(const DecArgs *a, hipStream_t st);
+int spiht_meta_sort_temp_bytes(uint64_t rows, size_t *bytes);
+int spiht_launch_metadata(const MetaArgs *a, uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
+                          void *temp, size_t temp_bytes, hipStream_t st);
+int spiht_launch_budget_fold(const MetaArgs *a, uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
+                             void *temp, size_t temp_bytes, const uint64_t *d_budgets, int K, int32_t *d_out, hipStream_t st);
+int spiht_meta_batch_sort_temp_bytes(const MetaBatchArgs *a, size_t *bytes);
+int spiht_launch_metadata_batch(const MetaBatchArgs *a, uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_out,
+                                uint32_t *vals_out, void *temp, size_t temp_bytes, hipStream_t st);
+int spiht_launch_nbits_to_nbytes(const uint64_t *d_nbits, int B, uint64_t *d_nbytes, hipStream_t st);
+int spiht_launch_color3(const double *d_in, double *d_out, int B, size_t npix, const double *A, const double *M, double p,
+                        hipStream_t st);
+int spiht_launch_dwt_level(const DwtKArgs *a, int planes, hipStream_t st);
+int spiht_launch_dwt_level_ext(const DwtKArgs *a, int planes, void *t_lo, void *t_hi, void *b_aa, void *b_ad, void *b_da,
+                               void *b_dd, const double *d_filt, hipStream_t st);
+int spiht_launch_idwt_level_per(const IdwtKArgs *a, int planes, double *t_lo, double *t_hi, const double *d_filt, int per,
+                                hipStream_t st);
+int spiht_launch_idwt_level(const IdwtKArgs *a, int planes, hipStream_t st, TileCtr *tc);
+int spiht_launch_px_to_f64(const PxView *px, int64_t B, double *out, hipStream_t st);
+int spiht_launch_f64_to_px(const double *in, int rec_h, int rec_w, const PxView *px, int64_t B, hipStream_t st);
+int spiht_launch_quant_plain(const double *in, int32_t *out, size_t n_per_plane, int planes, int c, const double *mults,
+                             double q, uint32_t *maxabs, hipStream_t st);
+int spiht_launch_zero_pads(int L, const int64_t *hs, const int64_t *ws, const int64_t *offh, const int64_t *offw, int enc_h,
+                           int enc_w, int32_t *coeffs, int planes, hipStream_t st);
+int spiht_launch_ll_to_pic(const LlPicArgs *a, int planes, hipStream_t st);
+int spiht_launch_dequant_plain(const int32_t *in, double *out, size_t n_per_plane, int planes, int c,
+                               const double *mults, double q, hipStream_t st);
+int spiht_launch_gate(const uint32_t *counter, uint32_t target, uint64_t ticks, hipStream_t st);
+int spiht_launch_spin(int blocks, int threads, uint64_t ticks, uint32_t lds_bytes, uint32_t *sink, hipStream_t st);  // (SPIHT_DIAG builds)
+int spiht_launch_spin_kind(int blocks, int threads, uint64_t ticks, uint32_t lds_bytes, uint32_t *sink, int mode, hipStream_t st);
+}

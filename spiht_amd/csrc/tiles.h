@@ -77,3 +77,22 @@ static inline void row_blocks(int64_t units, int64_t row_bytes, int64_t rows, di
     *rows_per_wg = (int)per;
     *gz = (uint32_t)std::max<int64_t>(1, (rows + per - 1) / per);
 }
+
+// the launchers of tiles.hip, layers.hip and overlap.hip (called from api.cpp)
+extern "C" {
+int spiht_launch_tile_cut(const TileCutArgs *a, int es, int64_t NT, hipStream_t st);
+int spiht_launch_tile_paste(const TilePasteArgs *a, int es, int64_t ntiles, hipStream_t st);
+int spiht_launch_tile_mosaic(const TileMosaicArgs *a, int es, hipStream_t st);
+int spiht_launch_tile_cut_overlap(const TileCutOverlapArgs *a, int es, int64_t NT, hipStream_t st);
+int spiht_launch_tile_blend(const TileBlendArgs *a, int es, hipStream_t st);
+int spiht_launch_tile_blend_flt(const TileBlendArgs *a, int kind, hipStream_t st);
+int spiht_launch_tile_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbytes, int64_t T, uint64_t *d_off,
+                           uint8_t *d_packed, uint64_t cap, uint32_t *d_lens, hipStream_t st);
+int spiht_launch_tile_unpack(const uint8_t *d_packed, uint64_t packed_bytes, const uint32_t *d_lens, int64_t T, uint64_t *d_off,
+                             uint8_t *d_slots, uint64_t slot_stride, uint64_t *d_nbytes, hipStream_t st);
+int spiht_launch_layer_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_cum_bits, int64_t Q, int64_t N, int64_t T,
+                            uint64_t *d_off, uint8_t *d_packed, uint64_t cap, uint32_t *d_cum, uint64_t *d_pic_bytes, hipStream_t st);
+int spiht_launch_layer_unpack(const uint8_t *d_layers, uint64_t layers_bytes, const uint32_t *d_cum, int64_t T, int64_t upto,
+                              const int32_t *d_sel, int64_t S, uint64_t *d_off, uint32_t *d_M, uint8_t *d_slots, uint64_t slot_stride,
+                              uint64_t *d_nbytes, hipStream_t st);
+}

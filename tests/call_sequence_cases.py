@@ -7,7 +7,7 @@ import numpy as np
 import dwt_sweep_tables as T
 from conftest import synth_coeffs, synth_image
 
-SEAM = 65535  # api.cpp: batch_chunks -- planes per launch (grid.y, and the decoder's slot limit)
+SEAM = 65535  # api_internal.h: batch_chunks -- planes per launch (grid.y, and the decoder's slot limit)
 UNLIMITED = 99999999999999999
 _CACHE = {}
 
@@ -172,7 +172,7 @@ def in_turn(distinct, B=None):
 
 
 def seam2_sizes(O):
-    """the per-picture element counts the offsets of a chunk are multiples of (api.cpp; each times b0), from the oracle's
+    """the per-picture element counts the offsets of a chunk are multiples of (api.cpp, api_coder.cpp; each times b0), from the oracle's
     geometry -> dict"""
     k = SEAM2
     g = O.geometry(k["H"], k["W"], k["wavelet"], k["level"], k["mode"])

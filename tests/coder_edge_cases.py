@@ -8,7 +8,7 @@ import numpy as np
 from conftest import synth_coeffs
 
 UNLIMITED = 99999999999999999
-CHUNK_SLACK = 16384           # api.cpp: list_caps(), chunk_slack
+CHUNK_SLACK = 16384           # api_coder.cpp: list_caps(), chunk_slack
 SMALL_GEOMS = [(1, 8, 8, 2, 2), (3, 13, 17, 3, 5)]   # c, h, w, ll_h, ll_w; the second has duplicated tree nodes
 ODD_GEOM = (3, 13, 17, 3, 5)
 MID_GEOM = (2, 26, 38, 13, 19)
@@ -71,7 +71,7 @@ def parents_of_cells(oracle, h, w, lh, lw):
 
 
 def node_instances(oracle, h, w, lh, lw):
-    """tree-node instances of one channel, duplicates counted as the coder's lists hold them (api.cpp: instance_counts)"""
+    """tree-node instances of one channel, duplicates counted as the coder's lists hold them (api_coder.cpp: instance_counts)"""
     frontier = {(i, j): 1 for i in range(lh) for j in range(lw)}
     total = 0
     while frontier:

@@ -56,7 +56,7 @@ def test_size_lists_sit_on_the_tile_seams():
     assert T.pf_tile_count() >= T.PF_MIN
     # ... and its 32-bit plane offsets hold (launch_idwt_FM: off32), or the launcher falls back to k_idwt_level
     assert (T.PF_REC[0] + T.INV_TH) * T.PF_REC[1] * 8 < 2 ** 31
-    assert T.PF_PICTURES * 3 <= 65535  # one launch: batch_chunks of api.cpp does not split the batch
+    assert T.PF_PICTURES * 3 <= 65535  # one launch: batch_chunks of api_internal.h does not split the batch
 
 
 def _dense(arr, H, W, F):

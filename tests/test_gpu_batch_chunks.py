@@ -1,4 +1,4 @@
-"""Both sides of the 65535-plane seam: batch_chunks (api.cpp) cuts every batched call into launches of at most 65535 planes,
+"""Both sides of the 65535-plane seam: batch_chunks (api_internal.h) cuts every batched call into launches of at most 65535 planes,
 and before this module no test passed more, so no launch had b0 != 0, none had exactly 65535 planes in grid.y.  Here every
 chunked entry point runs once through the seam -- 21852 distinct pictures of 3 planes: 65535 planes in the first launch, 21
 in the second -- and the raw coder calls also with one plane per picture, where the chunk is 65535 pictures.  Every image of

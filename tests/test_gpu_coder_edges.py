@@ -202,7 +202,7 @@ def _slots(streams, slot=None):
 
 @pytest.mark.parametrize("part", ["narrow", "wide2", "wide5", "batch", "image"])
 def test_start_plane_at_every_threshold(oracle, part):
-    """`(max as f32).log2() as u8` through the device's threshold table (encode_common.h: start_plane(), api.cpp:
+    """`(max as f32).log2() as u8` through the device's threshold table (encode_common.h: start_plane(), api_ctx.cpp:
     log2_thresh): every maximum around a power of two and around the step of the band below 2^21 .. 2^30, in the root block,
     in a leaf, in the last cell and on a duplicated node, both signs, alone and among small values.  A band maximum starts a
     plane above its top bit: that first plane holds no significant coefficient, and budgets cut inside and just behind it.
@@ -449,7 +449,7 @@ CAP_PARTS = ["enc-%d-%s" % (g, cd) for g in (0, 1) for cd in ("narrow", "wide5")
 
 @pytest.mark.parametrize("part", CAP_PARTS)
 def test_lists_at_their_capacity(oracle, part):
-    """list_caps() (api.cpp) sizes LIP, LSP and LIS from the stream length -- roots + mb + 16384, mb/2 + 1 + 16384,
+    """list_caps() (api_coder.cpp) sizes LIP, LSP and LIS from the stream length -- roots + mb + 16384, mb/2 + 1 + 16384,
     roots + 4 mb + 16384 -- or from the tree's node count, whichever is smaller.  Arrays that are significant everywhere,
     only in the finest level, or in one far cell, at budgets on either side of the points where the two terms meet; streams
     of ones (the LSP bound mb/2 + 1 is tight), of zeros and of every short period through the decoder.  A cap too small

@@ -576,7 +576,7 @@ def test_wide_encoder_beside_a_kernel_that_holds_the_cus(oracle, tmp_path):
 def test_wide_encoder_from_two_contexts_at_once(oracle):
     """Two threads, a context each, 160 workgroups per image: the two grids together exceed the CUs, and the workgroups of
     a grid wait for one another -- half-resident twins would wait for ever.  The library chains such launches one at a
-    time per device (api.cpp: encode_lists_device); every stream must come out right, no spin limit hit."""
+    time per device (api_coder.cpp: encode_lists_device); every stream must come out right, no spin limit hit."""
     import ctypes as C
     import threading
     from spiht_amd import _lib
