@@ -334,7 +334,7 @@ static int dwt_forward(spiht_ctx *ctx, const Pic &in, int planes, int c, const I
         memcpy(a.lo_f, wv.dec_lo_f, sizeof(float) * Fc);
         memcpy(a.hi_f, wv.dec_hi_f, sizeof(float) * Fc);
         if (twopass) {
-            // smooth / antisymmetric / antireflect / periodization / long filters: two plain passes through an intermediate (dwt.hip:
+            // smooth / antisymmetric / antireflect / periodization / long filters: two plain passes through an intermediate (dwt_plain.hip:
             // k_dwt_axis_ext), a few planes at a time so that the intermediates stay under a gigabyte; in the pixels' precision
             StageTimer t(ctx, l == 1 ? ST_DWT_L1 : ST_DWT_REST);
             const size_t esz = f32 ? 4 : 8;
@@ -459,7 +459,7 @@ static int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, 
             a.out = (double *)ctx->pix.p;
         }
         if (ig.per || F > SPIHT_MAX_TAPS) {
-            // periodization / a filter longer than the tiled kernels take: two plain passes through an intermediate (dwt.hip:
+            // periodization / a filter longer than the tiled kernels take: two plain passes through an intermediate (dwt_plain.hip:
             // k_idwt_axis_per), a few planes at a time; the colour model of the picture as a pass of its own behind level 1
             const double *d_filt;
             CHK(upload_filters(ctx, wavelet, &d_filt));
@@ -1075,7 +1075,7 @@ extern "C" int spiht_decode_image_reduced_host_u16(spiht_ctx *ctx, const uint8_t
 
 // ------------------------------------------------------------------------------------------------
 // float pixels out (include/spiht_hip.h, *_flt): the *_u16 decode calls with the element of a float kind.  The view's rules
-// are view_pic's with 4 or 2 bytes per sample; level 1 of the tiled inverse stores the kind (dwt.hip, PX_FLT), the routes
+// are view_pic's with 4 or 2 bytes per sample; level 1 of the tiled inverse stores the kind (dwt_inv.hip, PX_FLT), the routes
 // without a fused form convert in a pass of their own (dwt_inverse: conv8), which spiht_convert_batch_flt runs alone.
 // ------------------------------------------------------------------------------------------------
 extern "C" int spiht_check_view_flt(int kind, int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output) {
@@ -1154,7 +1154,7 @@ extern "C" int spiht_decode_image_reduced_host_flt(spiht_ctx *ctx, int kind, con
 
 // ------------------------------------------------------------------------------------------------
 // float pixels in (include/spiht_hip.h, *_flt): the *_u16 encode calls with the element of a float kind.  Every sample is
-// widened exactly on the loads of forward level 1 (dwt.hip, PX_FLT: flt_load_value), and everything behind that is the
+// widened exactly on the loads of forward level 1 (dwt_fwd.hip, PX_FLT: flt_load_value), and everything behind that is the
 // float64 path -- NOT the single-precision transform of the *_f32 calls.  The routes without a fused form widen in a pass of
 // their own (dwt_forward: k_px_to_f64), which spiht_widen_batch_flt runs alone.
 // ------------------------------------------------------------------------------------------------

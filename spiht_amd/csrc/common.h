@@ -124,7 +124,7 @@ struct EncArgs {
     float log2_thresh[32];   // log2_thresh[k]: smallest float m < 2^k with (u8)log2f(m) == k (host libm), or 2^k
 };
 
-// Tile of the inverse level-1 kernels (dwt.hip), in output positions; in band positions half of it.
+// Tile of the inverse level-1 kernels (dwt_inv.hip), in output positions; in band positions half of it.
 #define IW_TH 24    // output rows per tile (two halves, one per half of the workgroup; a multiple of 4)
 #define IW_TW 128   // output cols per tile, one thread per column per half
 
@@ -220,13 +220,13 @@ struct PyrArgs {
     uint32_t *maxabs;
 };
 
-// Colour model change fused into level 1 of the transform (dwt.hip): per pixel w = M * spow(A * u, p), spow(x, p) =
+// Colour model change fused into level 1 of the transform (dwt_device.h: color3_px): per pixel w = M * spow(A * u, p), spow(x, p) =
 // sign(x)|x|^p -- the shape of RGB <-> IPT (spiht/color_models.py:6-13 -> colour-science; here the published matrices)
 struct Color3 {
     double A[9], M[9], p;
 };
 
-// 8- and 16-bit pixels at level 1 of the transforms (dwt.hip, the PX_U8 / PX_U16 kernels): a [B, c, h, w] uint8 or uint16
+// 8- and 16-bit pixels at level 1 of the transforms (dwt_fwd.hip, dwt_inv.hip: the PX_U8 / PX_U16 kernels): a [B, c, h, w] uint8 or uint16
 // view given by BYTE strides (both kinds: the pointers stay byte pointers, a 16-bit sample is read / written at its byte
 // address, which is even -- the entry points check base and strides).  With D = 255 (es == 1) or 65535 (es == 2):
 // Forward: sample k is loaded as the double k / D (IEEE division: exactly numpy's P / D).  Inverse: a value v is
@@ -243,7 +243,7 @@ struct PxView {
                            // sample is loaded as the double of the same value (exact), through the same strides
 };
 
-// One forward DWT level (dwt.hip)
+// One forward DWT level (dwt_fwd.hip)
 struct DwtKArgs {
     int32_t c;             // channels (plane index = b*c + k)
     int32_t F, mode;
@@ -265,7 +265,7 @@ struct DwtKArgs {
     int32_t color, pad2;   // level 1 of a 3-channel image with the colour model change on its loads (k_dwt1_color)
     Color3 col;
     PxView px;             // level 1 of an 8- / 16-bit picture: the kernels' integer instantiations read it instead of `in`
-    // Launch-time constants of the tiled kernel k_dwt_level (set by its launcher, dwt.hip: dwt_set_launch_consts)
+    // Launch-time constants of the tiled kernel k_dwt_level (set by its launcher, dwt_fwd.hip: dwt_set_launch_consts)
     FastDivU dv_gx, dv_gy, dv_c;  // tile -> (bx, by, plane), plane -> (image, channel) without a division in the kernel
     uint32_t gx, gy, nt;   // tiles per row, per column, in all
     int32_t narrow;        // every plane the kernel touches spans less than 2^30 bytes: 32-bit offsets into plane descriptors
@@ -297,7 +297,7 @@ static inline bool dwt_narrow_ok(int64_t in_h, int64_t in_w, int64_t out_h, int6
     return true;
 }
 
-// One inverse DWT level (dwt.hip)
+// One inverse DWT level (dwt_inv.hip)
 // Tile hand-out of the persistent inverse-transform kernel (k_idwt_level_pf): one counter per XCD in device memory,
 // never reset -- the launcher knows how many numbers a launch draws from each (tiles + 2 per workgroup) and hands the
 // kernel the counter values it starts from (all arithmetic modulo 2^32).
@@ -335,7 +335,7 @@ struct IdwtKArgs {
     PxView px;                 // level 1 into an 8- / 16-bit picture: the kernels' integer instantiations write it instead of `out`
 };
 
-// The root block as a picture (dwt.hip: k_ll_to_pic): a reduced-resolution decode that runs no synthesis level
+// The root block as a picture (dwt_plain.hip: k_ll_to_pic): a reduced-resolution decode that runs no synthesis level
 struct LlPicArgs {
     const int32_t *rec;    // [planes, enc_h, enc_w]
     int32_t enc_h, enc_w, ll_h, ll_w;
@@ -347,7 +347,7 @@ struct LlPicArgs {
     Color3 col;
 };
 
-// The launchers of pyramid.hip, encode.hip, encode_wide.hip, decode.hip (built twice: 12 and 8 wavefronts), dwt.hip and
+// The launchers of pyramid.hip, encode.hip, encode_wide.hip, decode.hip (built twice: 12 and 8 wavefronts), dwt_fwd.hip, dwt_inv.hip, dwt_plain.hip and
 // metadata.hip, as the host side (api.cpp, api_*.cpp) calls them: declared here so that the compiler holds every definition to its callers.
 extern "C" {
 int spiht_launch_absmax(const int32_t *d_x, int B, uint32_t n, uint32_t *d_maxabs, hipStream_t st);

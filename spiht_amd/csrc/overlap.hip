@@ -69,7 +69,7 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_cut_overlap(const TileCutOv
 }
 
 // ---- blend -------------------------------------------------------------------------------------------------------------------
-// what a sample of the window is stored as.  8 / 16 bits: the decoder's conversion of a float64 sample (dwt.hip,
+// what a sample of the window is stored as.  8 / 16 bits: the decoder's conversion of a float64 sample (dwt_device.h,
 // px8_store_value / px16_store_value): clip to [0, 1], times 255 / 65535, truncate; NaN -> 0 (fmax / fmin return the number
 // of a pair with a NaN).  FK != 0: a float kind (floatpx.h: 1 float32, 2 float16, 3 bfloat16) -- the blended float64 sample
 // rounded once to the kind, as the decoder's float store does

@@ -310,7 +310,7 @@ static int submit_impl(spiht_pipeline *p, const StepPics &in, const StepPics &ou
         CHK(queue_inverse_level1(p, p->pending_slot, p->pending_out));
         p->pending = false;
         // ... L: this batch's decoder not before the coarse levels are through, and not before level 1's persistent workgroups
-        // (three per CU, too large for a fourth: dwt.hip) are on the CUs: a CU serves its older wavefronts first, the inverse
+        // (three per CU, too large for a fourth: dwt_inv.hip) are on the CUs: a CU serves its older wavefronts first, the inverse
         // level 1 beside a decoder that got there first takes 4.4 instead of 3.7 ms, and decoder workgroups that arrive
         // TOGETHER with it land unevenly (12.5 instead of 8.8 ms for the decoder, round 4).  The wait is for that fact, not for
         // a time: a one-wavefront kernel on L that watches the count of started workgroups (spiht_ctx_wait_resident).

@@ -1,4 +1,4 @@
-// x^p for x > 0 in float64, for the colour kernels (dwt.hip).  (The CPU checker oracle/color_oracle.c does not include this
+// x^p for x > 0 in float64, for the colour kernels (dwt_device.h).  (The CPU checker oracle/color_oracle.c does not include this
 // file: it uses the C library's pow(); tests/native/spow_probe.c measures this function against 60-digit arithmetic.)
 //
 // The colour model change (RGB <-> IPT: spiht/color_models.py:6-13 -> colour-science) takes three signed powers per

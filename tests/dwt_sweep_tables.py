@@ -7,7 +7,7 @@ import numpy as np
 from conftest import synth_image
 
 # One name per (filter length, zero-tap mask instantiation, leading joint zero taps) of spiht_launch_dwt_level /
-# spiht_launch_idwt_level (dwt.hip: launch_dwt_F, launch_idwt_F, launch_dwt_FM's z); test_dwt_sweep_tables.py recomputes
+# spiht_launch_idwt_level (dwt_fwd.hip: launch_dwt_F, launch_dwt_FM's z; dwt_inv.hip: launch_idwt_F); test_dwt_sweep_tables.py recomputes
 # the grouping from the filters.
 WAVELETS = ["haar", "db2", "bior2.2", "db3", "rbio1.3", "db4", "bior3.3", "bior4.4", "db5", "bior2.4", "db6", "rbio5.5", "db7",
             "bior2.6", "db8", "bior3.7", "bior6.8", "db9", "bior2.8", "db10", "bior3.9"]
@@ -15,23 +15,23 @@ WAVELETS = ["haar", "db2", "bior2.2", "db3", "rbio1.3", "db4", "bior3.3", "bior4
 INVERSE_MASK_WAVELETS = ["haar", "db2", "bior2.2", "db3", "db4", "bior4.4", "db5", "db6", "db7", "db8", "bior6.8", "db9", "db10"]
 MODES = ["reflect", "symmetric", "periodic", "zero", "constant"]  # the index maps: the modes the tiled kernels take
 
-# the switch of spiht_launch_dwt_level / spiht_launch_idwt_level (dwt.hip): F -> (mask of the low-pass, of the high-pass
+# the switch of spiht_launch_dwt_level / spiht_launch_idwt_level (dwt_fwd.hip, dwt_inv.hip): F -> (mask of the low-pass, of the high-pass
 # filter) of the bank that length is specialised for; any other bank of that length takes the all-taps instantiation
 FWD_SPECIALISED = {2: (0x3, 0x3), 6: (0x3E, 0x0E), 10: (0x3FE, 0x0FE), 18: (0x3FFFE, 0x3FF8)}
 INV_SPECIALISED = {2: (0x3, 0x3), 6: (0x0E, 0x3E), 10: (0x0FE, 0x3FE), 18: (0x3FF8, 0x3FFFE)}
 FILTER_LENGTHS = [2, 4, 6, 8, 10, 12, 14, 16, 18, 20]
 
 # tile constants of the kernels, mirrored
-FWD_TH, FWD_TW = 12, 64    # dwt.hip:31, :35  DW_TH, DW_TW: output rows / columns per tile of k_dwt_level
-FWD32_TH = 16              # dwt.hip:33  DW32_TH: output rows per tile of k_dwt_level_f32
-C1_ROWS = 136              # dwt.hip:634  output rows a workgroup of k_dwt1_color marches down
-INV_TH, INV_TW = 24, 128   # common.h:99, :100  IW_TH, IW_TW: output rows / columns per tile of k_idwt_level(_pf)
-INVC_TH = 8                # dwt.hip:1484  IWC_TH: output rows per tile of k_idwt1_color
-PF_MIN = 20000             # dwt.hip:1688  pf_min: tiles of a level from which launch_idwt_FM takes k_idwt_level_pf
+FWD_TH, FWD_TW = 12, 64    # dwt_device.h  DW_TH, DW_TW: output rows / columns per tile of k_dwt_level
+FWD32_TH = 16              # dwt_device.h  DW32_TH: output rows per tile of k_dwt_level_f32
+C1_ROWS = 136              # dwt_fwd.hip  C1_ROWS: output rows a workgroup of k_dwt1_color marches down
+INV_TH, INV_TW = 24, 128   # common.h  IW_TH, IW_TW: output rows / columns per tile of k_idwt_level(_pf)
+INVC_TH = 8                # dwt_inv.hip  IWC_TH: output rows per tile of k_idwt1_color
+PF_MIN = 20000             # dwt_inv.hip  launch_idwt_FM's pf_min: tiles of a level from which launch_idwt_FM takes k_idwt_level_pf
 
 
 def c1_sw(F):
-    """dwt.hip:641  SW: output columns per strip of k_dwt1_color"""
+    """dwt_fwd.hip  k_dwt1_color's SW: output columns per strip of k_dwt1_color"""
     return (256 - (F - 2)) // 2
 
 
@@ -81,7 +81,7 @@ def forward_sizes_reduced(F):
 
 
 def f32_level(F, H, W):
-    """The single-precision kernel takes no level input shorter than the filter (dwt.hip, above k_dwt_level_f32): two levels
+    """The single-precision kernel takes no level input shorter than the filter (dwt_fwd.hip, above k_dwt_level_f32): two levels
     where both levels' inputs are long enough, one where only the picture is, None (left out) otherwise."""
     if min(H, W) < F:
         return None
@@ -161,7 +161,7 @@ def level1_detail_bands(arr, H, W, F):
 
 def staged(ty, tx, F):
     """band rows and columns tile (ty, tx) of the inverse level stages: its own INV_TH/2 x INV_TW/2 band positions and the
-    halo of F/2 - 1 behind them (dwt.hip: KH, KW)"""
+    halo of F/2 - 1 behind them (dwt_inv.hip: KH, KW)"""
     hf1 = F // 2 - 1
     return slice(INV_TH // 2 * ty, INV_TH // 2 * ty + INV_TH // 2 + hf1), slice(INV_TW // 2 * tx, INV_TW // 2 * tx + INV_TW // 2 + hf1)
 

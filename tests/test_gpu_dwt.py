@@ -321,7 +321,7 @@ def test_pads_persist_tells_layouts_of_one_array_apart(oracle):
 
 def test_maxabs_small_batch_after_large_batch(oracle):
     """max|coefficient| of an image is raised by one atomic per workgroup, left out when a cached look at the word shows
-    it holds as much already (dwt.hip: block_raise_max, MAXLOOK 1).  That look must never see a value from BEFORE the
+    it holds as much already (dwt_device.h: block_raise_max, MAXLOOK 1).  That look must never see a value from BEFORE the
     word was last zeroed: a large-magnitude batch and then a small-magnitude one go through the same context and the
     same buffer, several times over; start plane and stream of every image must be the oracle's."""
     import spiht_amd
@@ -491,7 +491,7 @@ def test_every_wavelet_up_to_20_taps(oracle):
 
 def test_computed_extension_modes(oracle):
     """smooth / antisymmetric / antireflect / periodization (the reference passes SpihtSettings.mode to PyWavelets as it is):
-    the two-pass forward level (dwt.hip: k_dwt_axis_ext) and, for periodization -- another length rule, ceil(n / 2) -- the
+    the two-pass forward level (dwt_plain.hip: k_dwt_axis_ext) and, for periodization -- another length rule, ceil(n / 2) -- the
     two-pass inverse level (k_idwt_axis_per) against PyWavelets 1.1.1 (tests/golden/modes_pywt.npz) and, on a batch of
     pictures larger than a tile with channel scales and a colour model, against the oracle; the coder behind it included."""
     import spiht_amd
@@ -611,7 +611,7 @@ def test_single_precision_computed_modes_and_coiflets(oracle):
 
 def test_wavelets_above_20_taps(oracle):
     """db11-38, sym11-20, coif4-17, dmey (22 to 102 taps; the reference takes any PyWavelets name, spiht_wrapper.py:163, :276)
-    go through the two-pass levels with the filters read from device memory (dwt.hip: k_dwt_axis_ext / k_idwt_axis_per):
+    go through the two-pass levels with the filters read from device memory (dwt_plain.hip: k_dwt_axis_ext / k_idwt_axis_per):
     the int32 array and the picture back against PyWavelets 1.1.1 (tests/golden/long_pywt.npz), all nine modes, float64 and
     float32; then pictures larger than a tile with channel scales and a colour model against the oracle, the coder included."""
     import spiht_amd

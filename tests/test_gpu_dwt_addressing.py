@@ -1,4 +1,4 @@
-"""The addressing of the tiled forward transform kernel (spiht_amd/csrc/dwt.hip: k_dwt_level): one plane descriptor and 32-bit
+"""The addressing of the tiled forward transform kernel (spiht_amd/csrc/dwt_fwd.hip: k_dwt_level): one plane descriptor and 32-bit
 offsets per tile, store offsets advanced by launch-time constants, tile -> (column, row, plane) and plane -> (image, channel)
 by multipliers, extension indices without a division.  The smallest shapes at which each of these can go wrong, every
 quantised array and every max|coefficient| word (the start plane max_n is its bit length) equal to the oracle's, bit for bit.

@@ -1,4 +1,4 @@
-"""Every tiled transform kernel of spiht_amd/csrc/dwt.hip against the plain loops of oracle/dwt_oracle.c, over the product the
+"""Every tiled transform kernel of spiht_amd/csrc/dwt_fwd.hip and dwt_inv.hip against the plain loops of oracle/dwt_oracle.c, over the product the
 launchers dispatch on: filter length x zero-tap mask x pixel kind x kernel family x extension mode, at picture sizes that
 put the tile seams of each kernel where they can go wrong (tests/dwt_sweep_tables.py; tests/test_dwt_sweep_tables.py holds
 that grid to its purpose without a GPU).  Through the C ABI; every comparison is equality of bits."""

@@ -342,7 +342,7 @@ def _batch_u8_images(B, c, H, W, seed):
 
 
 # 40 RGB pictures of 541 x 961: level 1 of the inverse has 8 x 23 tiles of 128 x 24 per plane, 22 080 in all -- above the
-# 20 000 from which the launcher takes the persistent inverse kernel (dwt.hip: k_idwt_level_pf) -- and odd sizes, so that
+# 20 000 from which the launcher takes the persistent inverse kernel (dwt_inv.hip: k_idwt_level_pf) -- and odd sizes, so that
 # its crop of the extra row and column is exercised
 BIG = (40, 3, 541, 961)
 

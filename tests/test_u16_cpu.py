@@ -182,7 +182,7 @@ def test_u16_byte_order_and_negative_strides_are_copied():
 
 
 def test_u16_sample_value_is_the_quotient_for_every_value():
-    """A proof of the algorithm of dwt.hip's px16_value, restated here, not a run of the device code (which the GPU parity
+    """A proof of the algorithm of dwt_device.h's px16_value, restated here, not a run of the device code (which the GPU parity
     tests cover): q = k * (1/65535), corrected once by its residual through two fused multiply-adds, is the IEEE quotient
     k / 65535.0 (numpy's P / 65535) for all 65536 values -- and the product alone is not (88 of them differ).  fma
     emulated exactly: the exact sum, rounded once."""
@@ -205,7 +205,7 @@ def test_u16_sample_value_is_the_quotient_for_every_value():
 
 
 def test_u16_store_returns_every_value():
-    """dwt.hip's px16_store_value, restated: (uint16)(clip(v, 0, 1) * 65535.0), truncated, gives k back for v = k / 65535.0
+    """dwt_device.h's px16_store_value, restated: (uint16)(clip(v, 0, 1) * 65535.0), truncated, gives k back for v = k / 65535.0
     for all 65536 k -- a picture that survives the codec unquantised survives the store -- and clips and drops NaN."""
     def store(v):
         c = min(max(v, 0.0), 1.0) if v == v else 0.0  # (fmax / fmin return the number of a NaN pair: fmax(NaN, 0) = 0)

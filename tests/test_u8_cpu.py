@@ -82,7 +82,7 @@ def test_u8_view_rule(no_context):
 
 
 def test_u8_sample_value_is_the_quotient_for_every_byte():
-    """A proof of the algorithm of dwt.hip's px8_value, restated here, not a run of the device code (which the GPU parity
+    """A proof of the algorithm of dwt_device.h's px8_value, restated here, not a run of the device code (which the GPU parity
     tests cover): q = k * (1/255), corrected once by its residual through two fused multiply-adds, is the IEEE quotient
     k / 255.0 (numpy's P / 255) for all 256 bytes.  fma emulated exactly: the exact sum, rounded once."""
     from fractions import Fraction

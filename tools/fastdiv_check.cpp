@@ -16,7 +16,7 @@
 
 #include "common.h"
 
-#define TH 12  // dwt.hip: DW_TH, DW_TW
+#define TH 12  // dwt_device.h: DW_TH, DW_TW
 #define TW 64
 
 static uint64_t n_cmp = 0, n_bad = 0;

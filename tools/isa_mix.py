@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """isa_mix.py -- what a kernel issues, by instruction class, from the assembly of one translation unit.
 
-    hipcc <the Makefile's flags of the file> --cuda-device-only -S dwt.hip -o dwt.s
-    python3 tools/isa_mix.py dwt.s 'k_dwt_level<6, 62u, 14u, 0, false>'
+    hipcc <the Makefile's flags of the file> --cuda-device-only -S dwt_fwd.hip -o dwt_fwd.s
+    python3 tools/isa_mix.py dwt_fwd.s 'k_dwt_level<6, 62u, 14u, 0, false>'
 
 The kernel is named by its mangled symbol, or by a piece of its demangled name (c++filt / llvm-cxxfilt is asked when one
 is there; every kernel whose name contains the piece is reported).  Per kernel one line of static counts:
