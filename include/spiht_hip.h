@@ -1014,6 +1014,97 @@ int spiht_tile_cut_overlap_f32s(spiht_ctx *ctx, const float *d_img, const int64_
 int spiht_dwt_addr32(int64_t in_h, int64_t in_w, int64_t out_h, int64_t out_w, int64_t enc_h, int64_t enc_w, int px_es,
                      int64_t px_sh, int64_t px_sw);
 
+/* ---------------------------------------------------------------------------------------
+ * Host-fed streams (csrc/hoststream.cpp): batches of HOST pictures encoded, or batches of HOST streams decoded, with the
+ * transfers overlapped -- step i+1's upload, step i's coding and step i-1's download run at the same time.  The reference's
+ * interface is host arrays in and out, one picture per call (spiht_wrapper.py:142-216); this is the schedule for a caller
+ * with a folder of pictures or a loader with thousands of streams.  One-directional: a stream encodes or it decodes.
+ * Additions only: the ABI version stays at 2.
+ *
+ * A stream lives on a caller's context, which must outlive it.  The first one gives the context two more HIP streams,
+ * one for the copies in and one for the copies out; every later host-fed stream on the context shares them and the last
+ * one destroyed takes them along, so a context carries three HIP streams in all however many encoders and decoders it
+ * feeds (a process has four hardware queues, and two HIP streams on one queue run one after the other).  No graphs, no
+ * threads, no new context; it is driven by the caller's thread.
+ * It holds a ring of `depth` slots (2 .. 4), each with page-locked input staging and page-locked output staging from the pool behind spiht_host_alloc, its device buffers and its events.  The coding is the
+ * batched entry point of the stream's element -- spiht_encode_image_batch_f64 / _u8 / _u16 / _flt or its decode sibling --
+ * so every wavelet, mode, level, channel scale and the context's colour model (spiht_ctx_set_color3: the setting at the
+ * moment of _submit) mean what they mean there, and the bits are those calls' bits.
+ *
+ *   elem      SPIHT_HS_F64, _U8, _U16, or a float kind of the *_flt calls: SPIHT_HS_FLT32, _FLT16, _BF16
+ *   strides   the view [B, c, H, W] of the staged pictures in BYTES, as the batched calls take it (NULL: dense CHW); float64
+ *             pictures are dense.  An encoder reads the view, a decoder writes it (the rules of spiht_check_view_*).
+ *             A float64 decoder's pictures are dense [n, c, rec_H, rec_W], uncropped as spiht_decode_image_batch_f64 leaves
+ *             them; every other element's are cropped to H x W as its batch call crops them.
+ *   max_bits  encoder: the budget per picture (0 or SPIHT_MAX_BITS_UNLIMITED: none).  decoder: the longest stream it takes,
+ *             in bits (0: the bound of the geometry).  Either way it sizes the staging: slot_bytes per picture
+ *             (spiht_hstream_info).
+ *
+ * Encode step:
+ *   _input(s, &h)    the next slot's page-locked picture buffer (B pictures by `strides`), to be filled by the caller -- a
+ *                    decoder library can write straight into it.  Asked again before the submit: the same buffer.
+ *   _submit(s, n, 0) 1 <= n <= B pictures of it.  Queues, without waiting for anything: the upload on the copy-in stream; on
+ *                    the context's stream, behind an event, the batched encode, spiht_tile_pack of the n streams into one
+ *                    run and the download of the n lengths and start planes; an event.
+ *   _next(s, ms, &o) the OLDEST submitted step: waits for that event, queues the download of exactly the packed bytes on
+ *                    the copy-out stream -- with no wait in front of it: it never stands behind a later step -- and waits
+ *                    for it.
+ *                    o.bytes: the n streams one behind the other, o.nbytes of them; o.lens[n]; o.max_n[n].
+ * Decode step:
+ *   _input(s, &h)    page-locked room for a step's input; spiht_hstream_decode_input gives its three parts: packed bytes
+ *                    (B * slot_bytes), lens uint32 [B], max_n uint8 [B].  (*h is the packed bytes.)
+ *   _submit(s, n, d) the n streams of lens[0 .. n), one behind the other.  Queues the upload of exactly those bytes,
+ *                    spiht_tile_unpack into slots (of the longest stream's size, rounded up to 4), the batched decode, and
+ *                    the download of the pictures.  d != NULL: a DEVICE destination for the pictures (the view by `strides`,
+ *                    or dense) -- they stay in HBM and nothing is downloaded; d must stay valid until _next has returned
+ *                    the step.  (An encoder takes d == NULL only.)
+ *   _next(s, ms, &o) o.pictures: the n pictures in the slot's page-locked output (NULL with a device destination, which is
+ *                    complete when _next returns), o.nbytes the bytes they span.
+ * What _next hands out is valid until _input hands that slot out again -- after `depth` - 1 further steps at the earliest.
+ *
+ * No call waits without bound.  _input and _submit never block: with no free slot they return SPIHT_ERR_BUSY and change
+ * nothing (_submit without an _input before it: SPIHT_ERR_BUSY when the ring is full, else SPIHT_ERR_ARG).  _next polls the
+ * step's event for at most timeout_ms milliseconds (0: one look), then returns SPIHT_ERR_TIMEOUT and leaves the stream as it
+ * was -- the same call made again goes on waiting; with nothing submitted it returns SPIHT_ERR_IDLE at once.  Results leave
+ * in the order of submission.  A failed HIP call latches: every later call returns that first status (destroy the stream).
+ * The device-side guards of the batched calls (SPIHT_ERR_MAGNITUDE ...) stay the context's: spiht_ctx_synchronize reports
+ * them, as for every batched call.  The first step of a stream may wait while the context's scratch grows to the batch's
+ * size; later steps do not.  _destroy waits for what is queued, at most SPIHT_HS_DESTROY_MS, then frees; when that time runs
+ * out it gives its events back but leaves the buffers to the process (a transfer may still be writing them) and
+ * returns SPIHT_ERR_TIMEOUT.  Calls on one stream come from one thread at a time.
+ * Page-locked footprint: depth * (one batch of pictures + B * slot_bytes + 5 B) bytes; when the pool refuses (4 GiB handed
+ * out, or the system says no) _create fails with SPIHT_ERR_NOMEM and nothing is left allocated. */
+enum { SPIHT_ERR_BUSY = 11,    /* a host-fed stream's ring is full: take a result (spiht_hstream_next) first */
+       SPIHT_ERR_TIMEOUT = 12, /* the step did not complete within the time given; the call may be made again */
+       SPIHT_ERR_IDLE = 13 };  /* spiht_hstream_next with nothing submitted */
+enum { SPIHT_HS_ENCODE = 0, SPIHT_HS_DECODE = 1 };
+enum { SPIHT_HS_F64 = 0, SPIHT_HS_U8 = 1, SPIHT_HS_U16 = 2,
+       SPIHT_HS_FLT32 = 3, SPIHT_HS_FLT16 = 4, SPIHT_HS_BF16 = 5 /* the float kinds 1, 2, 3 of the *_flt calls */ };
+#define SPIHT_HS_DESTROY_MS 10000
+typedef struct spiht_hstream spiht_hstream;
+typedef struct spiht_hstream_result {
+    int64_t n;              /* pictures of the step */
+    uint64_t nbytes;        /* encoder: bytes at `bytes`; decoder: bytes the n pictures span at `pictures` */
+    const uint8_t *bytes;   /* encoder: the n streams, one behind the other */
+    const uint32_t *lens;   /* encoder: their n lengths in bytes */
+    const uint8_t *max_n;   /* encoder: their n start planes */
+    void *pictures;         /* decoder: the n pictures (NULL: they went to the device destination of the submit) */
+    uint64_t step;          /* the step's number, from 0 in the order of submission */
+} spiht_hstream_result;
+int spiht_hstream_create(spiht_ctx *ctx, int direction, int elem, int64_t B, int depth, int64_t c, int64_t H, int64_t W,
+                         int wavelet, int mode, int level, double q_scale, const double *channel_mults, uint64_t max_bits,
+                         const int64_t *strides, spiht_hstream **out);
+int spiht_hstream_destroy(spiht_hstream *s);
+/* slot_bytes: the stream slot per picture; pic_bytes: bytes one step's B pictures span in the staging; rec_H x rec_W: the
+ * size of a decoder's pictures (float64: spiht_geometry's; else H x W).  Output pointers may be NULL. */
+int spiht_hstream_info(spiht_hstream *s, uint64_t *slot_bytes, uint64_t *pic_bytes, int64_t *rec_H, int64_t *rec_W);
+int spiht_hstream_input(spiht_hstream *s, void **h_ptr);
+int spiht_hstream_decode_input(spiht_hstream *s, uint8_t **h_packed, uint32_t **h_lens, uint8_t **h_max_n);
+int spiht_hstream_submit(spiht_hstream *s, int64_t n, void *d_dst);
+int spiht_hstream_next(spiht_hstream *s, int timeout_ms, spiht_hstream_result *out);
+/* steps submitted and not yet taken (0 .. depth) */
+int spiht_hstream_pending(spiht_hstream *s, int *steps);
+
 #ifdef __cplusplus
 }
 #endif

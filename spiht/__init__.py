@@ -10,7 +10,8 @@ import sys
 
 import spiht_amd as _impl
 
-_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode", "rd", "tiles", "overlap", "floatpx")
+_SUBMODULES = ("spiht_wrapper", "spiht", "utils", "color_models", "spiht_py", "encode_decode", "rd", "tiles", "overlap", "floatpx",
+               "hoststream")
 for _name in _SUBMODULES:
     # `spiht.spiht` is the reference's compiled extension (src/lib.rs:58-65); here spiht_amd/spiht.py over the C ABI
     _mod = importlib.import_module("spiht_amd." + _name)
@@ -51,4 +52,9 @@ globals().update({_k: getattr(_impl, _k) for _k in ("decode_image_float", "decod
                                                     "decode_image_layered_window_float")})
 # ... float pixels in: float32, float16 and bfloat16 pictures coded as they lie, by the float64 codec
 globals().update({_k: getattr(_impl, _k) for _k in ("encode_image_float", "encode_image_tiled_float", "encode_image_layered_float")})
+# ... host-fed streams: batches of host pictures encoded / streams decoded with the transfers overlapped
+globals().update({_k: getattr(_impl, _k) for _k in ("StreamEncoder", "StreamDecoder", "StreamBusy", "StreamTimeout", "StreamIdle",
+                                                    "encode_images", "encode_images_u8", "encode_images_u16",
+                                                    "encode_images_float", "decode_images", "decode_images_u8",
+                                                    "decode_images_u16", "decode_images_float")})
 __all__ = ["encode_image", "decode_image", "EncodingResult", "SpihtSettings", "ENCODER_DECODER_VERSION", "encode", "decode"]

@@ -26,3 +26,6 @@ from .tiles import (TiledCodec, TiledResult, TileCurves, TileAllocation, tile_gr
                     encode_image_layered_float)
 from .alloc import roi_map, target_sqerr  # noqa: E402,F401
 from .overlap import window_tiles_overlap  # noqa: E402,F401
+from .hoststream import (StreamEncoder, StreamDecoder, StreamBusy, StreamTimeout, StreamIdle, encode_images,  # noqa: E402,F401
+                         encode_images_u8, encode_images_u16, encode_images_float, decode_images, decode_images_u8,
+                         decode_images_u16, decode_images_float)

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SPIHT_HIP_LIB") or os.path.join(_HERE, "libspiht_hip.
 
 OK, ERR_LL, ERR_EMPTY, ERR_SHAPE, ERR_CAPACITY, ERR_HIP, ERR_ARG, ERR_MAGNITUDE, ERR_INTERNAL, ERR_TOO_LARGE, \
     ERR_NOMEM = range(11)
+ERR_BUSY, ERR_TIMEOUT, ERR_IDLE = 11, 12, 13   # host-fed streams (spiht_hstream_*)
 
 MODES = {"reflect": 0, "symmetric": 1, "periodic": 2, "zero": 3, "constant": 4}
 
@@ -78,7 +79,15 @@ SYMBOLS = [
     "spiht_dwt_addr32",
     "spiht_widen_batch_flt", "spiht_encode_image_batch_flt", "spiht_encode_image_host_flt", "spiht_dwt_pyramid_batch_flt",
     "spiht_sse_tiles_flt", "spiht_sse_tiles_w_flt", "spiht_tile_cut_f32s", "spiht_tile_cut_overlap_f32s",
+    "spiht_hstream_create", "spiht_hstream_destroy", "spiht_hstream_info", "spiht_hstream_input", "spiht_hstream_decode_input",
+    "spiht_hstream_submit", "spiht_hstream_next", "spiht_hstream_pending",
 ]
+
+
+class HStreamResult(C.Structure):
+    """spiht_hstream_result"""
+    _fields_ = [("n", C.c_int64), ("nbytes", C.c_uint64), ("bytes", C.c_void_p), ("lens", C.c_void_p), ("max_n", C.c_void_p),
+                ("pictures", C.c_void_p), ("step", C.c_uint64)]
 
 
 def lib():
@@ -270,6 +279,15 @@ def lib():
         L.spiht_tile_mosaic_f32.argtypes = L.spiht_tile_mosaic_u8.argtypes
         L.spiht_ctx_lock.argtypes = [vp]
         L.spiht_ctx_unlock.argtypes = [vp]
+        # host-fed streams: context, direction, element, B, depth, then the geometry and settings of the batched image calls
+        L.spiht_hstream_create.argtypes = [vp, i32, i32, i64, i32, i64, i64, i64, i32, i32, i32, C.c_double, vp, u64, vp, C.POINTER(vp)]
+        L.spiht_hstream_destroy.argtypes = [vp]
+        L.spiht_hstream_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i64), C.POINTER(i64)]
+        L.spiht_hstream_input.argtypes = [vp, C.POINTER(vp)]
+        L.spiht_hstream_decode_input.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.spiht_hstream_submit.argtypes = [vp, i64, vp]
+        L.spiht_hstream_next.argtypes = [vp, i32, C.POINTER(HStreamResult)]
+        L.spiht_hstream_pending.argtypes = [vp, C.POINTER(i32)]
         _lib = L
         return _lib
 

@@ -72,6 +72,9 @@ extern "C" const char *spiht_strerror(int s) {
     case SPIHT_ERR_INTERNAL: return "internal list capacity guard tripped";
     case SPIHT_ERR_TOO_LARGE: return "array or stream too large (c*h*w must be < 2^30, stream < 2^32 bits, a picture at most 65535 planes)";
     case SPIHT_ERR_NOMEM: return "out of device memory";
+    case SPIHT_ERR_BUSY: return "the stream's ring is full: take a result first";
+    case SPIHT_ERR_TIMEOUT: return "the step did not complete within the time given";
+    case SPIHT_ERR_IDLE: return "nothing is submitted";
     default: return "unknown status";
     }
 }
@@ -148,6 +151,8 @@ extern "C" void spiht_ctx_destroy(spiht_ctx *ctx) {
         if (b->p) (void)hipFree(b->p);
     for (auto &r : ctx->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : ctx->pool) (void)hipEventDestroy(e);
+    if (ctx->copy_in) (void)hipStreamDestroy(ctx->copy_in);
+    if (ctx->copy_out) (void)hipStreamDestroy(ctx->copy_out);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

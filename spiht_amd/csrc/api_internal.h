@@ -61,6 +61,11 @@ struct spiht_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::recursive_mutex mu;  // recursive: the host-array entry points call the batched ones
+    // host-fed streams (hoststream.cpp): the copy-in and the copy-out stream beside `stream`, made for the first spiht_hstream of
+    // the context, shared by all of them and given back with the last -- three HIP streams per context however many host-fed
+    // streams it carries, and one when it carries none
+    hipStream_t copy_in = nullptr, copy_out = nullptr;
+    int copy_users = 0;
     int num_cu = 256;
     float log2_thresh[32];
     // grow-only scratch
