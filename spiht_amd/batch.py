@@ -10,10 +10,10 @@ import math
 
 import numpy as np
 
-from . import _lib, color_models, floatpx
+from . import _lib, color_models, floatpx, px
 from . import spiht as spiht_rs
-from .spiht_wrapper import (EncodingResult, SpihtSettings, _geometry, _metadata_boxes, _mults_arg, _wavelet_mode_ids,
-                            check_u8_view, _check_int_view, _check_aligned, _is_dtype, reduced_shape)
+from .spiht_wrapper import (EncodingResult, SpihtSettings, _crop_window, _geometry, _metadata_boxes, _mults_arg,
+                            _wavelet_mode_ids, reduced_shape)
 
 
 class DeviceArray:
@@ -91,21 +91,43 @@ class BatchCodec:
         return color_models.fused(self.ctx, self.settings.color_model)
 
     # ---- raw device-pointer API (ints) -------------------------------------------------------
-    def encode_device(self, d_img, B, d_out, d_nbits, d_max_n, d_coeffs=None):
-        fn = self.L.spiht_encode_image_batch_f32 if self.pixel_dtype == np.float32 else self.L.spiht_encode_image_batch_f64
+    # One implementation by the element type (px.Elem); the public names pick it.  The checks of a view -- its strides, its
+    # base -- come before anything of the codec but c, H, W is read: they need no context.
+    def _encode_device(self, elem, d_img, B, d_out, d_nbits, d_max_n, strides=None, d_coeffs=None):
+        view = ()  # the elements that come as a view take the strides behind the address
+        if elem.view:
+            st, st_p = elem.strides_arg((int(B), self.c, self.H, self.W), strides, False)
+            elem.check_aligned(d_img)
+            view = (st_p,)
+        args = (C.c_void_p(d_img), *view, int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
+                float(self.settings.quantization_scale), self._mults_p, self.max_bits, C.c_void_p(d_out), self.slot_stride,
+                C.c_void_p(d_nbits), C.c_void_p(d_max_n), C.c_void_p(d_coeffs) if d_coeffs else None)
         with self._color():
-            _lib.check(fn(
-                self.ctx.handle, C.c_void_p(d_img), int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
-                float(self.settings.quantization_scale), self._mults_p, self.max_bits, C.c_void_p(d_out),
-                self.slot_stride, C.c_void_p(d_nbits), C.c_void_p(d_max_n), C.c_void_p(d_coeffs) if d_coeffs else None))
+            _lib.check(elem.entry(self.L, "spiht_encode_image_batch_")(self.ctx.handle, *args))
+
+    def _decode_device(self, elem, d_data, d_nbytes, d_max_n, B, d_img_out, strides=None, d_rec=None, slot_stride=None, reduce=None):
+        """reduce=None: the full-size entry point; otherwise the *_reduced_* one, whose pictures are reduced_shape(reduce)'s"""
+        stem, h, w, tail = "spiht_decode_image_batch_", self.H, self.W, ()
+        if reduce is not None:
+            rs = self.reduced_shape(reduce)
+            stem, h, w, tail = "spiht_decode_image_reduced_batch_", rs["pic_h"], rs["pic_w"], (int(reduce),)
+        view = ()
+        if elem.view:
+            st, st_p = elem.strides_arg((int(B), self.c, h, w), strides, True)
+            elem.check_aligned(d_img_out)
+            view = (st_p,)
+        args = (C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride), C.c_void_p(d_nbytes),
+                C.c_void_p(d_max_n), int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
+                float(self.settings.quantization_scale), self._mults_p, C.c_void_p(d_img_out), *view,
+                C.c_void_p(d_rec) if d_rec else None, *tail)
+        with self._color():
+            _lib.check(elem.entry(self.L, stem)(self.ctx.handle, *args))
+
+    def encode_device(self, d_img, B, d_out, d_nbits, d_max_n, d_coeffs=None):
+        self._encode_device(px.of_dtype(self.pixel_dtype), d_img, B, d_out, d_nbits, d_max_n, None, d_coeffs)
 
     def decode_device(self, d_data, d_nbytes, d_max_n, B, d_img_out, d_rec=None, slot_stride=None):
-        with self._color():
-            _lib.check(self.L.spiht_decode_image_batch_f64(
-                self.ctx.handle, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
-                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
-                float(self.settings.quantization_scale), self._mults_p, C.c_void_p(d_img_out),
-                C.c_void_p(d_rec) if d_rec else None))
+        self._decode_device(px.F64, d_data, d_nbytes, d_max_n, B, d_img_out, None, d_rec, slot_stride)
 
     def decode_with_metadata_device(self, d_data, d_nbytes, d_max_n, B, d_meta, meta_rows, d_img_out=None, d_rec=None,
                                     slot_stride=None):
@@ -141,153 +163,92 @@ class BatchCodec:
 
     # ---- 8- and 16-bit pixels (include/spiht_hip.h, *_u8 / *_u16): whatever pixel_dtype says, the float64 arithmetic on
     # k / 255 (k / 65535).  One implementation by the element type; the public names pick it. -------------------------------
-    def _int_strides(self, B, strides, output, dtype=np.uint8):
-        """byte strides (sb, sc, sh, sw) of a [B, c, H, W] uint8 / uint16 view as a ctypes argument (None: dense CHW)"""
-        if strides is None:
-            return None, None
-        st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
-        _check_int_view(8 * np.dtype(dtype).itemsize, (int(B), self.c, self.H, self.W), st, output)
-        return st, C.c_void_p(st.ctypes.data)
-
-    def _u8_strides(self, B, strides, output):
-        return self._int_strides(B, strides, output, np.uint8)
-
-    def _encode_device_int(self, dtype, d_img, B, d_out, d_nbits, d_max_n, strides, d_coeffs=None):
-        st, st_p = self._int_strides(B, strides, False, dtype)
-        _check_aligned(d_img, dtype)
-        fn = self.L.spiht_encode_image_batch_u16 if np.dtype(dtype).itemsize == 2 else self.L.spiht_encode_image_batch_u8
-        with self._color():
-            _lib.check(fn(
-                self.ctx.handle, C.c_void_p(d_img), st_p, int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
-                float(self.settings.quantization_scale), self._mults_p, self.max_bits, C.c_void_p(d_out), self.slot_stride,
-                C.c_void_p(d_nbits), C.c_void_p(d_max_n), C.c_void_p(d_coeffs) if d_coeffs else None))
-
-    def _decode_device_int(self, dtype, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride):
-        st, st_p = self._int_strides(B, strides, True, dtype)
-        _check_aligned(d_img_out, dtype)
-        fn = self.L.spiht_decode_image_batch_u16 if np.dtype(dtype).itemsize == 2 else self.L.spiht_decode_image_batch_u8
-        with self._color():
-            _lib.check(fn(
-                self.ctx.handle, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
-                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
-                self.c, self.H, self.W, self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
-                C.c_void_p(d_img_out), st_p, C.c_void_p(d_rec) if d_rec else None))
-
-    def _encode_int(self, dtype, name, images, channels_last):
+    def _encode_pixels(self, elem, name, images, channels_last):
+        """host pictures [B, c, H, W] (or [B, H, W, c]) of a view element -> EncodingResults"""
         images = np.asarray(images)
-        if not _is_dtype(images, dtype) or images.ndim != 4:
-            raise ValueError("%s takes a %s array [B, c, H, W]" % (name, np.dtype(dtype).name))
+        if not px._is_dtype(images, elem.storage) or images.ndim != 4:
+            raise ValueError("%s takes a %s array [B, c, H, W]" % (name, elem.storage.name))
         if channels_last:
             images = images.transpose(0, 3, 1, 2)
-        images = np.ascontiguousarray(images, dtype=np.dtype(dtype).newbyteorder("="))
+        images = np.ascontiguousarray(images, dtype=elem.storage)
         if images.shape[1:] != (self.c, self.H, self.W):
             raise ValueError("%s: pictures of shape %s, the codec's are %s" % (name, images.shape[1:], (self.c, self.H, self.W)))
-        return self._encode_host(images, lambda d_img, *a: self._encode_device_int(dtype, d_img, *a, None))
+        return self._encode_host(elem, images)
 
-    def _decode_int(self, dtype, results, channels_last):
-        c, H, W, es = self.c, self.H, self.W, np.dtype(dtype).itemsize
-        strides = (H * W * c * es, es, W * c * es, c * es) if channels_last else None
-        return self._decode_host(results, (H, W, c) if channels_last else (c, H, W), dtype,
-                                 lambda *a, slot_stride: self._decode_device_int(dtype, *a, strides, None, slot_stride))
+    def _decode_pixels(self, elem, results, channels_last=False, reduce=None, crop=False):
+        """EncodingResults -> host pictures [B, c, h, w] (or [B, h, w, c]) of the element: the uncropped float64 ones, or a view
+        element's, cropped to the picture (reduce: to the band); crop: the centred window of a reduced decode"""
+        rs = None if reduce is None else self.reduced_shape(reduce)
+        if not elem.view:
+            g = self.geom if rs is None else rs
+            h, w = g["rec_h"], g["rec_w"]
+        else:
+            h, w = (self.H, self.W) if rs is None else (rs["pic_h"], rs["pic_w"])
+        shape = (len(results), self.c, h, w)
+        out = self._decode_host(elem, results, (h, w, self.c) if channels_last else shape[1:],
+                                elem.channels_last_strides(shape) if channels_last else None, reduce)
+        return _crop_window(out, rs, crop, channels_last)
 
     def encode_device_u8(self, d_img, B, d_out, d_nbits, d_max_n, strides=None):
         """d_img: uint8 [B, c, H, W] on the device, laid out by `strides` (bytes; None: dense CHW)"""
-        self._encode_device_int(np.uint8, d_img, B, d_out, d_nbits, d_max_n, strides)
+        self._encode_device(px.U8, d_img, B, d_out, d_nbits, d_max_n, strides)
 
     def decode_device_u8(self, d_data, d_nbytes, d_max_n, B, d_img_out, strides=None, d_rec=None, slot_stride=None):
         """-> uint8 [B, c, H, W] on the device, cropped to H x W, laid out by `strides` (bytes; None: dense CHW; the bytes
         between the view's elements -- an RGBA buffer's alpha, row padding -- are not written)"""
-        self._decode_device_int(np.uint8, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride)
+        self._decode_device(px.U8, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride)
 
     def encode_u8(self, images, channels_last=False):
         """images: uint8 [B, c, H, W] (or [B, H, W, c] with channels_last) -> list of EncodingResult (those of
         encode(images / 255.0))"""
-        return self._encode_int(np.uint8, "encode_u8", images, channels_last)
+        return self._encode_pixels(px.U8, "encode_u8", images, channels_last)
 
     def decode_u8(self, results, channels_last=False):
         """list of EncodingResult (same geometry) -> uint8 [B, c, H, W] (or [B, H, W, c]), cropped to H x W"""
-        return self._decode_int(np.uint8, results, channels_last)
+        return self._decode_pixels(px.U8, results, channels_last)
 
     def encode_device_u16(self, d_img, B, d_out, d_nbits, d_max_n, strides=None):
         """d_img: uint16 [B, c, H, W] on the device (native byte order, even address), laid out by `strides` (BYTES, all
         even; None: dense CHW)"""
-        self._encode_device_int(np.uint16, d_img, B, d_out, d_nbits, d_max_n, strides)
+        self._encode_device(px.U16, d_img, B, d_out, d_nbits, d_max_n, strides)
 
     def decode_device_u16(self, d_data, d_nbytes, d_max_n, B, d_img_out, strides=None, d_rec=None, slot_stride=None):
         """-> uint16 [B, c, H, W] on the device, cropped to H x W, laid out by `strides` (BYTES, all even; None: dense CHW;
         what lies between the view's elements -- a 16-bit RGBA buffer's alpha, row padding -- is not written)"""
-        self._decode_device_int(np.uint16, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride)
+        self._decode_device(px.U16, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride)
 
     def encode_u16(self, images, channels_last=False):
         """images: uint16 [B, c, H, W] (or [B, H, W, c] with channels_last) -> list of EncodingResult (those of
         encode(images / 65535.0))"""
-        return self._encode_int(np.uint16, "encode_u16", images, channels_last)
+        return self._encode_pixels(px.U16, "encode_u16", images, channels_last)
 
     def decode_u16(self, results, channels_last=False):
         """list of EncodingResult (same geometry) -> uint16 [B, c, H, W] (or [B, H, W, c]), cropped to H x W"""
-        return self._decode_int(np.uint16, results, channels_last)
+        return self._decode_pixels(px.U16, results, channels_last)
 
     # ---- float pixels out (include/spiht_hip.h, *_flt; spiht_amd/floatpx.py): float32, float16 or bfloat16 pictures, each
     # sample of the float64 decode rounded once to the kind.  dtype: what floatpx.kind_arg takes. -----------------------------
-    def _float_strides(self, kind, shape, strides):
-        """byte strides of a [B, c, h, w] view of the kind that is written, as a ctypes argument (None: dense CHW)"""
-        if strides is None:
-            return None, None
-        st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
-        floatpx.check_float_view(kind, shape, st, True)
-        return st, C.c_void_p(st.ctypes.data)
-
     def decode_device_float(self, d_data, d_nbytes, d_max_n, B, d_img_out, dtype, strides=None, d_rec=None, slot_stride=None):
         """-> pictures of the kind `dtype` [B, c, H, W] on the device, cropped to H x W: floatpx.convert of what decode_device
         makes, laid out by `strides` (BYTES, multiples of the element size, as the base; None: dense CHW; what lies between the
         view's elements -- a fourth channel, row padding -- is not written)"""
-        kind = floatpx.kind_id(dtype)
-        st, st_p = self._float_strides(kind, (int(B), self.c, self.H, self.W), strides)
-        _check_aligned(d_img_out, floatpx.storage_dtype(kind))
-        with self._color():
-            _lib.check(self.L.spiht_decode_image_batch_flt(
-                self.ctx.handle, kind, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
-                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
-                self.c, self.H, self.W, self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
-                C.c_void_p(d_img_out), st_p, C.c_void_p(d_rec) if d_rec else None))
+        self._decode_device(px.of_kind_id(dtype), d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride)
 
     def decode_float(self, results, dtype=np.float32, channels_last=False):
         """list of EncodingResult (same geometry) -> [B, c, H, W] (or [B, H, W, c]) of the kind `dtype`, cropped to H x W:
         spiht_wrapper.decode_image_float of each (float32, float16, or uint16 bit patterns for bfloat16)"""
-        kind = floatpx.kind_arg(dtype)
-        c, H, W, es = self.c, self.H, self.W, floatpx.itemsize(kind)
-        strides = (H * W * c * es, es, W * c * es, c * es) if channels_last else None
-        return self._decode_host(results, (H, W, c) if channels_last else (c, H, W), floatpx.storage_dtype(kind),
-                                 lambda *a, slot_stride: self.decode_device_float(*a, kind, strides, None, slot_stride))
+        return self._decode_pixels(px.of_kind(dtype), results, channels_last)
 
     def decode_reduced_device_float(self, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, dtype, strides=None, d_rec=None,
                                     slot_stride=None):
         """-> pictures of the kind `dtype` [B, c, pic_h, pic_w] on the device (reduced_shape), laid out by `strides` (BYTES,
         multiples of the element size; None: dense CHW): floatpx.convert of decode_reduced_device's, cropped to the band"""
-        kind = floatpx.kind_id(dtype)
-        rs = self.reduced_shape(reduce)
-        st, st_p = self._float_strides(kind, (int(B), self.c, rs["pic_h"], rs["pic_w"]), strides)
-        _check_aligned(d_img_out, floatpx.storage_dtype(kind))
-        with self._color():
-            _lib.check(self.L.spiht_decode_image_reduced_batch_flt(
-                self.ctx.handle, kind, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
-                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
-                self.c, self.H, self.W, self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
-                C.c_void_p(d_img_out), st_p, C.c_void_p(d_rec) if d_rec else None, int(reduce)))
+        self._decode_device(px.of_kind_id(dtype), d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride, reduce)
 
     def decode_reduced_float(self, results, reduce, dtype=np.float32, crop=False, channels_last=False):
         """list of EncodingResult -> [B, c, pic_h, pic_w] (or [B, pic_h, pic_w, c]) of the kind `dtype`:
         decode_image_reduced_float of each"""
-        kind = floatpx.kind_arg(dtype)
-        rs = self.reduced_shape(reduce)
-        c, h, w, es = self.c, rs["pic_h"], rs["pic_w"], floatpx.itemsize(kind)
-        strides = (h * w * c * es, es, w * c * es, c * es) if channels_last else None
-        out = self._decode_host(results, (h, w, c) if channels_last else (c, h, w), floatpx.storage_dtype(kind),
-                                lambda *a, slot_stride: self.decode_reduced_device_float(*a, reduce, kind, strides, None, slot_stride))
-        if not crop:
-            return out
-        ys, xs = slice(rs["off_y"], rs["off_y"] + rs["in_h"]), slice(rs["off_x"], rs["off_x"] + rs["in_w"])
-        return out[:, ys, xs, :] if channels_last else out[:, :, ys, xs]
+        return self._decode_pixels(px.of_kind(dtype), results, channels_last, reduce, crop)
 
     # ---- float pixels in (include/spiht_hip.h, the encode side of *_flt): float32, float16 or bfloat16 pictures, each sample
     # widened exactly on the loads of level 1; whatever pixel_dtype says, the float64 arithmetic -- what encode() of a float64
@@ -295,33 +256,14 @@ class BatchCodec:
     def encode_device_float(self, d_img, B, d_out, d_nbits, d_max_n, dtype, strides=None, d_coeffs=None):
         """d_img: pictures of the kind `dtype` [B, c, H, W] on the device, laid out by `strides` (BYTES, non-negative multiples
         of the element size, as the base; None: dense CHW)"""
-        kind = floatpx.kind_id(dtype)
-        st = st_p = None
-        if strides is not None:
-            st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
-            floatpx.check_float_view(kind, (int(B), self.c, self.H, self.W), st, False)
-            st_p = C.c_void_p(st.ctypes.data)
-        _check_aligned(d_img, floatpx.storage_dtype(kind))
-        with self._color():
-            _lib.check(self.L.spiht_encode_image_batch_flt(
-                self.ctx.handle, kind, C.c_void_p(d_img), st_p, int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
-                float(self.settings.quantization_scale), self._mults_p, self.max_bits, C.c_void_p(d_out), self.slot_stride,
-                C.c_void_p(d_nbits), C.c_void_p(d_max_n), C.c_void_p(d_coeffs) if d_coeffs else None))
+        self._encode_device(px.of_kind_id(dtype), d_img, B, d_out, d_nbits, d_max_n, strides, d_coeffs)
 
     def encode_float(self, images, dtype=None, channels_last=False):
         """images: [B, c, H, W] (or [B, H, W, c] with channels_last) float32 or float16, or uint16 bit patterns with
         dtype="bfloat16" -> list of EncodingResult: spiht_wrapper.encode_image_float of each"""
         images = np.asarray(images)
-        kind = floatpx.input_kind(images, dtype, "encode_float")
-        sd = floatpx.storage_dtype(kind)
-        if images.ndim != 4:
-            raise ValueError("encode_float takes a %s array [B, c, H, W]" % sd.name)
-        if channels_last:
-            images = images.transpose(0, 3, 1, 2)
-        images = np.ascontiguousarray(images, dtype=sd)
-        if images.shape[1:] != (self.c, self.H, self.W):
-            raise ValueError("encode_float: pictures of shape %s, the codec's are %s" % (images.shape[1:], (self.c, self.H, self.W)))
-        return self._encode_host(images, lambda d_img, *a: self.encode_device_float(d_img, *a, kind))
+        elem = px.of_kind_id(floatpx.input_kind(images, dtype, "encode_float"))
+        return self._encode_pixels(elem, "encode_float", images, channels_last)
 
     # ---- reduced-resolution decode (include/spiht_hip.h, *_reduced_*): pictures at 1/2^reduce size, 0 <= reduce <= L.
     # What spiht_wrapper.decode_image_reduced* return, for B streams in one queue of kernels. ------------------------------
@@ -331,70 +273,31 @@ class BatchCodec:
 
     def decode_reduced_device(self, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, d_rec=None, slot_stride=None):
         """decode_device at 1/2^reduce size -> float64 [B, c, rec_h, rec_w] on the device (reduced_shape)"""
-        self.reduced_shape(reduce)
-        with self._color():
-            _lib.check(self.L.spiht_decode_image_reduced_batch_f64(
-                self.ctx.handle, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
-                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B), self.c, self.H, self.W, self.wid, self.mid, self._lv,
-                float(self.settings.quantization_scale), self._mults_p, C.c_void_p(d_img_out),
-                C.c_void_p(d_rec) if d_rec else None, int(reduce)))
-
-    def _decode_reduced_device_int(self, dtype, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides, d_rec, slot_stride):
-        rs = self.reduced_shape(reduce)
-        st = st_p = None
-        if strides is not None:
-            st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
-            _check_int_view(8 * np.dtype(dtype).itemsize, (int(B), self.c, rs["pic_h"], rs["pic_w"]), st, True)
-            st_p = C.c_void_p(st.ctypes.data)
-        _check_aligned(d_img_out, dtype)
-        fn = (self.L.spiht_decode_image_reduced_batch_u16 if np.dtype(dtype).itemsize == 2
-              else self.L.spiht_decode_image_reduced_batch_u8)
-        with self._color():
-            _lib.check(fn(
-                self.ctx.handle, C.c_void_p(d_data), self.slot_stride if slot_stride is None else int(slot_stride),
-                C.c_void_p(d_nbytes), C.c_void_p(d_max_n), int(B),
-                self.c, self.H, self.W, self.wid, self.mid, self._lv, float(self.settings.quantization_scale), self._mults_p,
-                C.c_void_p(d_img_out), st_p, C.c_void_p(d_rec) if d_rec else None, int(reduce)))
+        self._decode_device(px.F64, d_data, d_nbytes, d_max_n, B, d_img_out, None, d_rec, slot_stride, reduce)
 
     def decode_reduced_device_u8(self, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides=None, d_rec=None,
                                  slot_stride=None):
         """-> uint8 [B, c, pic_h, pic_w] on the device (reduced_shape), laid out by `strides` (bytes; None: dense CHW; what
         lies between the view's elements is not written)"""
-        self._decode_reduced_device_int(np.uint8, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides, d_rec, slot_stride)
+        self._decode_device(px.U8, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride, reduce)
 
     def decode_reduced_device_u16(self, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides=None, d_rec=None,
                                   slot_stride=None):
         """-> uint16 [B, c, pic_h, pic_w] on the device, laid out by `strides` (BYTES, all even; None: dense CHW)"""
-        self._decode_reduced_device_int(np.uint16, d_data, d_nbytes, d_max_n, B, d_img_out, reduce, strides, d_rec, slot_stride)
+        self._decode_device(px.U16, d_data, d_nbytes, d_max_n, B, d_img_out, strides, d_rec, slot_stride, reduce)
 
     def decode_reduced(self, results, reduce, crop=False):
         """list of EncodingResult (same geometry) -> float64 [B, c, rec_h, rec_w]: decode_image_reduced of each; crop=True:
         the centred in_h x in_w window (a view)"""
-        rs = self.reduced_shape(reduce)
-        out = self._decode_host(results, (self.c, rs["rec_h"], rs["rec_w"]), np.float64,
-                                lambda *a, slot_stride: self.decode_reduced_device(*a, reduce, slot_stride=slot_stride))
-        if not crop:
-            return out
-        return out[:, :, rs["off_y"]:rs["off_y"] + rs["in_h"], rs["off_x"]:rs["off_x"] + rs["in_w"]]
-
-    def _decode_reduced_int(self, dtype, results, reduce, crop, channels_last):
-        rs = self.reduced_shape(reduce)
-        c, h, w, es = self.c, rs["pic_h"], rs["pic_w"], np.dtype(dtype).itemsize
-        strides = (h * w * c * es, es, w * c * es, c * es) if channels_last else None
-        out = self._decode_host(results, (h, w, c) if channels_last else (c, h, w), dtype,
-                                lambda *a, slot_stride: self._decode_reduced_device_int(dtype, *a, reduce, strides, None, slot_stride))
-        if not crop:
-            return out
-        ys, xs = slice(rs["off_y"], rs["off_y"] + rs["in_h"]), slice(rs["off_x"], rs["off_x"] + rs["in_w"])
-        return out[:, ys, xs, :] if channels_last else out[:, :, ys, xs]
+        return self._decode_pixels(px.F64, results, False, reduce, crop)
 
     def decode_reduced_u8(self, results, reduce, crop=False, channels_last=False):
         """list of EncodingResult -> uint8 [B, c, pic_h, pic_w] (or [B, pic_h, pic_w, c]): decode_image_reduced_u8 of each"""
-        return self._decode_reduced_int(np.uint8, results, reduce, crop, channels_last)
+        return self._decode_pixels(px.U8, results, channels_last, reduce, crop)
 
     def decode_reduced_u16(self, results, reduce, crop=False, channels_last=False):
         """list of EncodingResult -> uint16 [B, c, pic_h, pic_w] (or [B, pic_h, pic_w, c]): decode_image_reduced_u16 of each"""
-        return self._decode_reduced_int(np.uint16, results, reduce, crop, channels_last)
+        return self._decode_pixels(px.U16, results, channels_last, reduce, crop)
 
     # ---- rate-distortion curve and cut (spiht_amd/rd.py; include/spiht_hip.h: spiht_sqerr_i32, spiht_sse_*) ---------------
     def rd_curve(self, image, result=None, byte_lengths=None, points=32, max_bytes=2 ** 31):
@@ -409,23 +312,23 @@ class BatchCodec:
         and compared with the picture (spiht_sse_f64); the K rows come back.  A group holds as many lengths as keep
         K_g c (enc_h enc_w 4 + rec_h rec_w 8) bytes within max_bytes, at least one; the numbers do not depend on it."""
         from . import rd
-        return rd.codec_rd_curve(self, image, result, byte_lengths, points, max_bytes)[0]
+        return rd.codec_rd_curve(self, image, result, byte_lengths, points, max_bytes, px.F64)[0]
 
     def rd_curve_u8(self, image, result=None, byte_lengths=None, points=32, max_bytes=2 ** 31):
         """rd_curve of a uint8 picture (c, H, W): the distances are those between 8-bit pictures (decode_image_u8 of the
         prefix against `image`), exact integers; peak 255"""
         from . import rd
-        return rd.codec_rd_curve(self, image, result, byte_lengths, points, max_bytes, np.uint8)[0]
+        return rd.codec_rd_curve(self, image, result, byte_lengths, points, max_bytes, px.U8)[0]
 
     def rd_curve_u16(self, image, result=None, byte_lengths=None, points=32, max_bytes=2 ** 31):
         """rd_curve of a uint16 picture (c, H, W); peak 65535"""
         from . import rd
-        return rd.codec_rd_curve(self, image, result, byte_lengths, points, max_bytes, np.uint16)[0]
+        return rd.codec_rd_curve(self, image, result, byte_lengths, points, max_bytes, px.U16)[0]
 
-    def _cut_to_psnr(self, image, result, target_db, points, dtype):
+    def _cut_to_psnr(self, image, result, target_db, points, elem):
         from . import rd
         target = rd._target_arg(target_db, "target_db")
-        return rd.codec_cut(self, image, result, points, dtype, "psnr", lambda v: v >= target)
+        return rd.codec_cut(self, image, result, points, elem, "psnr", lambda v: v >= target)
 
     def cut_to_psnr(self, image, result, target_db, points=32):
         """A prefix of `result` (a stream of the float picture `image`) that reaches target_db -> (EncodingResult, psnr, met).
@@ -435,15 +338,15 @@ class BatchCodec:
         search -- at most `points` lengths per round, evenly spaced between a length that fails and one that passes, one
         rd_curve call per round, at most ceil(log(n + 1) / log(points + 1)) rounds after the look at the whole stream --
         ends at one place where the curve crosses the target."""
-        return self._cut_to_psnr(image, result, target_db, points, None)
+        return self._cut_to_psnr(image, result, target_db, points, px.F64)
 
     def cut_to_psnr_u8(self, image, result, target_db, points=32):
         """cut_to_psnr on the 8-bit curve (rd_curve_u8)"""
-        return self._cut_to_psnr(image, result, target_db, points, np.uint8)
+        return self._cut_to_psnr(image, result, target_db, points, px.U8)
 
     def cut_to_psnr_u16(self, image, result, target_db, points=32):
         """cut_to_psnr on the 16-bit curve (rd_curve_u16)"""
-        return self._cut_to_psnr(image, result, target_db, points, np.uint16)
+        return self._cut_to_psnr(image, result, target_db, points, px.U16)
 
     def cut_to_sqerr(self, image, result, max_sqerr, points=32):
         """A prefix of `result` whose coefficient error E = sum (X - X_L)^2 is at most max_sqerr -> (EncodingResult, E, met);
@@ -457,7 +360,7 @@ class BatchCodec:
         from . import rd
         if isinstance(max_sqerr, float) and math.isnan(max_sqerr):
             raise ValueError("max_sqerr is NaN")
-        return rd.codec_cut(self, image, result, points, None, "coef_sqerr", lambda v: v <= max_sqerr)
+        return rd.codec_cut(self, image, result, points, px.F64, "coef_sqerr", lambda v: v <= max_sqerr)
 
     def nbits_to_nbytes(self, d_nbits, B, d_nbytes):
         _lib.check(self.L.spiht_nbits_to_nbytes(self.ctx.handle, C.c_void_p(d_nbits), int(B), C.c_void_p(d_nbytes)))
@@ -467,11 +370,11 @@ class BatchCodec:
         """images: float array [B,c,H,W] -> list of EncodingResult"""
         images = np.ascontiguousarray(images, dtype=self.pixel_dtype)
         assert images.shape[1:] == (self.c, self.H, self.W)
-        return self._encode_host(images, self.encode_device)
+        return self._encode_host(px.of_dtype(self.pixel_dtype), images)
 
     def decode(self, results):
         """list of EncodingResult (same geometry) -> float64 [B,c,H',W']"""
-        return self._decode_host(results, (self.c, self.geom["rec_h"], self.geom["rec_w"]), np.float64, self.decode_device)
+        return self._decode_pixels(px.F64, results)
 
     def decode_with_metadata(self, results):
         """list of EncodingResult (same geometry) -> (float64 [B,c,H',W'], [metadata_b]): the pictures of decode(results)
@@ -495,8 +398,8 @@ class BatchCodec:
                 d.free()
         return images, [meta[b, :8 * len(r.encoded_bytes) + 1] for b, r in enumerate(results)]
 
-    def _encode_host(self, images, encode_device):
-        """host pictures [B, ...] -> their device copy -> encode_device(d_img, B, d_out, d_nbits, d_max_n) -> EncodingResults"""
+    def _encode_host(self, elem, images):
+        """host pictures [B, c, H, W] of the element, dense -> their device copy -> _encode_device -> EncodingResults"""
         B = images.shape[0]
         ctx = self.ctx
         d_img = DeviceArray(ctx, images.shape, images.dtype)
@@ -505,7 +408,7 @@ class BatchCodec:
         d_maxn = DeviceArray(ctx, (B,), np.uint8)
         try:
             d_img.upload(images)
-            encode_device(d_img.ptr, B, d_out.ptr, d_nbits.ptr, d_maxn.ptr)
+            self._encode_device(elem, d_img.ptr, B, d_out.ptr, d_nbits.ptr, d_maxn.ptr)
             ctx.synchronize()
             out, nbits, maxn = d_out.download(), d_nbits.download(), d_maxn.download()
         finally:
@@ -514,14 +417,14 @@ class BatchCodec:
         return [EncodingResult(out[b, :(int(nbits[b]) + 7) // 8].tobytes(), self.H, self.W, self.c, int(maxn[b]),
                                self.level) for b in range(B)]
 
-    def _decode_host(self, results, shape, dtype, decode_device):
-        """the streams of `results` on the device, in slots of the longest one's size -> decode_device(d_data, d_nbytes,
-        d_max_n, B, d_img_out, slot_stride=...) into `dtype` pictures of `shape` -> host array [B, *shape]"""
+    def _decode_host(self, elem, results, shape, strides, reduce):
+        """the streams of `results` on the device, in slots of the longest one's size -> _decode_device into pictures of the
+        element, `shape` each as the host sees them, laid out by `strides` -> host array [B, *shape]"""
         B = len(results)
         stride, (d_data, d_nbytes, d_maxn) = self._streams_on_device(results)
-        d_img = DeviceArray(self.ctx, (B,) + tuple(shape), dtype)
+        d_img = DeviceArray(self.ctx, (B,) + tuple(shape), elem.storage)
         try:
-            decode_device(d_data.ptr, d_nbytes.ptr, d_maxn.ptr, B, d_img.ptr, slot_stride=stride)
+            self._decode_device(elem, d_data.ptr, d_nbytes.ptr, d_maxn.ptr, B, d_img.ptr, strides, None, stride, reduce)
             self.ctx.synchronize()
             return d_img.download()
         finally:
@@ -635,24 +538,25 @@ class Pipeline:
             _lib.check(self.L.spiht_pipeline_submit_gather(self.handle, vp(d_img), vp(d_out), vp(d_nbits), vp(d_max_n), vp(d_img_out),
                                                            comm.handle, vp(gathered[0]), vp(gathered[1]), vp(gathered[2]), int(rank)))
 
-    def _submit_int(self, dtype, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides, out_strides):
+    def _submit(self, elem, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides, out_strides):
         vp = C.c_void_p
-        st_in, p_in = self.codec._int_strides(self.B, in_strides, False, dtype)
-        st_out, p_out = self.codec._int_strides(self.B, out_strides, True, dtype)
-        _check_aligned(d_img, dtype)
-        _check_aligned(d_img_out, dtype)
-        fn = self.L.spiht_pipeline_submit_u16 if np.dtype(dtype).itemsize == 2 else self.L.spiht_pipeline_submit_u8
-        _lib.check(fn(self.handle, vp(d_img), p_in, vp(d_out), vp(d_nbits), vp(d_max_n), vp(d_img_out), p_out))
+        shape = (int(self.B), self.codec.c, self.codec.H, self.codec.W)
+        st_in, p_in = elem.strides_arg(shape, in_strides, False)
+        st_out, p_out = elem.strides_arg(shape, out_strides, True)
+        elem.check_aligned(d_img)
+        elem.check_aligned(d_img_out)
+        _lib.check(elem.entry(self.L, "spiht_pipeline_submit_")(self.handle, vp(d_img), p_in, vp(d_out), vp(d_nbits), vp(d_max_n),
+                                                                vp(d_img_out), p_out))
 
     def submit_u8(self, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides=None, out_strides=None):
         """queue one step of 8-bit pictures (device pointers as ints): uint8 [B, c, H, W] in and out, laid out by byte strides
         (None: dense CHW), the output cropped to H x W.  Float64, 8-bit and 16-bit steps may alternate."""
-        self._submit_int(np.uint8, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides, out_strides)
+        self._submit(px.U8, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides, out_strides)
 
     def submit_u16(self, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides=None, out_strides=None):
         """queue one step of 16-bit pictures (device pointers as ints): uint16 [B, c, H, W] in and out, laid out by BYTE
         strides (all even; None: dense CHW), the output cropped to H x W."""
-        self._submit_int(np.uint16, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides, out_strides)
+        self._submit(px.U16, d_img, d_out, d_nbits, d_max_n, d_img_out, in_strides, out_strides)
 
     def flush(self):
         _lib.check(self.L.spiht_pipeline_flush(self.handle))

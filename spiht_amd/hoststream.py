@@ -25,7 +25,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, color_models, floatpx
+from . import _lib, color_models, px
 from .spiht_wrapper import EncodingResult, SpihtSettings, _geometry, _mults_arg, _wavelet_mode_ids
 
 ENCODE, DECODE = 0, 1
@@ -55,18 +55,18 @@ def _check(status):
 
 
 def _element(dtype):
-    """dtype as BatchCodec's pixel calls name it -> (element id of the C ABI, numpy dtype the pictures are stored in)"""
+    """dtype as BatchCodec's pixel calls name it -> its px.Elem: float64, uint8 and uint16 by dtype, everything else a float
+    kind (np.float32 is the kind here, not the codec's own single-precision pixels)"""
     d = None
     if type(dtype).__module__.split(".")[0] != "torch" and dtype is not None:
         try:
             d = np.dtype(dtype)
         except TypeError:   # ("bfloat16": numpy has no such type)
             d = None
-    for elem, t in enumerate((np.float64, np.uint8, np.uint16)):
-        if d == t:
-            return elem, np.dtype(t)
-    kind = floatpx.kind_arg(dtype)
-    return 2 + kind, floatpx.storage_dtype(kind)
+    for elem in (px.F64, px.U8, px.U16):
+        if d is not None and d == elem.storage:  # (a dtype compares equal to None as to float64)
+            return elem
+    return px.of_kind(dtype)
 
 
 def _view(ptr, nbytes, dtype, shape):
@@ -78,16 +78,15 @@ def _view(ptr, nbytes, dtype, shape):
 class _NativeBackend:
     """spiht_hstream behind the three calls; what a fake backend of the tests stands in for"""
 
-    def __init__(self, direction, elem, store, B, depth, c, H, W, wid, mid, lv, q, mults_p, max_bits, ctx, channels_last=False):
+    def __init__(self, direction, elem, B, depth, c, H, W, wid, mid, lv, q, mults_p, max_bits, ctx, channels_last=False):
         self.L = _lib.lib()
-        self.direction, self.store, self.B, self.depth, self.c = direction, store, int(B), int(depth), int(c)
+        self.direction, self.store, self.B, self.depth, self.c = direction, elem.storage, int(B), int(depth), int(c)
         self.channels_last = bool(channels_last)
         h = C.c_void_p()
         st = None
         if self.channels_last:   # the view [B, c, H, W] of dense [B, H, W, c] pictures, in bytes
-            es = store.itemsize
-            st = np.ascontiguousarray([int(H) * int(W) * self.c * es, es, int(W) * self.c * es, self.c * es], dtype=np.int64)
-        _check(self.L.spiht_hstream_create(ctx.handle, direction, elem, self.B, self.depth, self.c, int(H), int(W), wid, mid, lv,
+            st = np.ascontiguousarray(elem.channels_last_strides((self.B, self.c, int(H), int(W))), dtype=np.int64)
+        _check(self.L.spiht_hstream_create(ctx.handle, direction, elem.stream_id, self.B, self.depth, self.c, int(H), int(W), wid, mid, lv,
                                            float(q), mults_p, int(max_bits), C.c_void_p(st.ctypes.data) if st is not None else None,
                                            C.byref(h)))
         self.handle = h
@@ -144,9 +143,10 @@ class _Stream:
             raise ValueError("batch must be at least 1")
         if not 2 <= self.depth <= 4:
             raise ValueError("depth must be 2, 3 or 4")
-        self.elem, self.store = _element(dtype)
+        self.elem = _element(dtype)
+        self.store = self.elem.storage
         self.channels_last = bool(channels_last)
-        if self.channels_last and self.elem == 0:
+        if self.channels_last and not self.elem.view:
             raise ValueError("float64 pictures are dense (c, H, W); channels_last is for the integer and float kinds")
         self.pic_shape = (self.H, self.W, self.c) if self.channels_last else (self.c, self.H, self.W)
         cm = self.settings.color_model
@@ -164,7 +164,7 @@ class _Stream:
         self.geom = _geometry(self.H, self.W, wid, level, mid)
         self._mults, mults_p = _mults_arg(self.settings.per_channel_quant_scales, self.c)
         self.ctx = ctx if ctx is not None else _lib.default_context()
-        self._be = _NativeBackend(direction, self.elem, self.store, self.batch, self.depth, self.c, self.H, self.W, wid, mid,
+        self._be = _NativeBackend(direction, self.elem, self.batch, self.depth, self.c, self.H, self.W, wid, mid,
                                   -1 if level is None else int(level), self.settings.quantization_scale, mults_p, max_bits, self.ctx,
                                   self.channels_last)
 
@@ -366,7 +366,7 @@ def _batched(items, batch):
 def _encode_stream(images, settings, level, max_bits, batch, depth, ctx, dtype, name, _backend):
     """the generator behind encode_images*: the first picture says the shape; every picture is written straight into the
     staging of the step it belongs to (one copy); the stream is closed when the generator ends"""
-    store = _element(dtype)[1]
+    store = _element(dtype).storage
     enc, buf, n = None, None, 0
     try:
         for i, im in enumerate(images):

@@ -15,10 +15,10 @@ from typing import Any, List
 
 import numpy as np
 
-from . import _lib
-from .spiht_wrapper import (EncodingResult, SpihtSettings, _check_aligned, _check_version, _int_picture)
+from . import _lib, px
+from .spiht_wrapper import EncodingResult, SpihtSettings, _check_version, _int_picture
 
-PEAK = {None: 1.0, np.dtype(np.uint8): 255, np.dtype(np.uint16): 65535}
+PEAK = {None: 1.0, px.U8.storage: int(px.U8.peak), px.U16.storage: int(px.U16.peak)}  # by dtype; None: float pixels
 
 
 @dataclass
@@ -141,22 +141,21 @@ def _prefix(result, length):
                           result._encoding_version)
 
 
-def _picture(codec, image, dtype):
-    """the checks on `image`: one picture of the codec's geometry, float (dtype None) or of the integer `dtype`"""
-    if dtype is None:
+def _picture(codec, image, elem):
+    """the checks on `image`: one picture of the codec's geometry, float (px.F64) or of the integer element"""
+    if not elem.integer:
         if codec.pixel_dtype != np.float64:
             raise ValueError("rd_curve takes the pictures of a float64 codec")
         image = np.ascontiguousarray(image, dtype=np.float64)
     else:
-        name = "rd_curve_u%d" % (8 * np.dtype(dtype).itemsize)
-        image = np.ascontiguousarray(_int_picture(image, codec.settings, dtype, name))
+        image = np.ascontiguousarray(_int_picture(image, codec.settings, elem.storage, "rd_curve_" + elem.suffix))
     if image.shape != (codec.c, codec.H, codec.W):
         raise ValueError("a picture of shape %s, the codec's are %s" % (image.shape, (codec.c, codec.H, codec.W)))
     return image
 
 
-def codec_rd_curve(codec, image, result=None, byte_lengths=None, points=32, max_bytes=2 ** 31, dtype=None, kept=None):
-    """BatchCodec.rd_curve / rd_curve_u8 / rd_curve_u16 (dtype None / uint8 / uint16); returns (RDCurve, result).
+def codec_rd_curve(codec, image, result=None, byte_lengths=None, points=32, max_bytes=2 ** 31, elem=px.F64, kept=None):
+    """BatchCodec.rd_curve / rd_curve_u8 / rd_curve_u16 (elem px.F64 / px.U8 / px.U16); returns (RDCurve, result).
     kept: a list, empty at first, in which the picture and X stay on the device from one call to the next of the same
     picture and stream (the rounds of a search: codec_cut, which frees them)"""
     from .batch import DeviceArray
@@ -165,12 +164,12 @@ def codec_rd_curve(codec, image, result=None, byte_lengths=None, points=32, max_
         byte_lengths = _lengths_arg(byte_lengths)
     if isinstance(max_bytes, bool) or not isinstance(max_bytes, (int, np.integer)) or max_bytes < 0:
         raise ValueError("max_bytes must be a non-negative integer")
-    image = _picture(codec, image, dtype)
+    image = _picture(codec, image, elem)
+    view = (None,) if elem.view else ()  # the integer calls take a view: dense here, no strides
     if result is not None:
         _check_version(result)
         if (result.c, result.h, result.w, result.level) != (codec.c, codec.H, codec.W, codec.level):
             raise ValueError("the stream is not of the codec's geometry")
-    es = 8 if dtype is None else np.dtype(dtype).itemsize
     ctx, L, g, c, H, W = codec.ctx, codec.L, codec.geom, codec.c, codec.H, codec.W
     vp = C.c_void_p
     q = float(codec.settings.quantization_scale)
@@ -187,7 +186,7 @@ def codec_rd_curve(codec, image, result=None, byte_lengths=None, points=32, max_
             d_x = DeviceArray(ctx, (c, g["enc_h"], g["enc_w"]), np.int32)
             (held if kept is None else kept).extend((d_pic, d_x))
             d_pic.upload(image)
-            _check_aligned(d_pic.ptr, image.dtype)
+            elem.check_aligned(d_pic.ptr)
         else:
             d_pic, d_x = kept
         if not fresh:
@@ -195,10 +194,7 @@ def codec_rd_curve(codec, image, result=None, byte_lengths=None, points=32, max_
         elif result is None:
             # a batch of one: X is the array the encoder handed to the list coder
             d_out, d_nbits, d_maxn = dev((1, codec.slot_stride), np.uint8), dev((1,), np.uint64), dev((1,), np.uint8)
-            if dtype is None:
-                codec.encode_device(d_pic.ptr, 1, d_out.ptr, d_nbits.ptr, d_maxn.ptr, d_coeffs=d_x.ptr)
-            else:
-                codec._encode_device_int(dtype, d_pic.ptr, 1, d_out.ptr, d_nbits.ptr, d_maxn.ptr, None, d_coeffs=d_x.ptr)
+            codec._encode_device(elem, d_pic.ptr, 1, d_out.ptr, d_nbits.ptr, d_maxn.ptr, None, d_x.ptr)
             ctx.synchronize()
             nbits = int(d_nbits.download()[0])
             result = EncodingResult(d_out.download()[0, :(nbits + 7) // 8].tobytes(), H, W, c, int(d_maxn.download()[0]),
@@ -206,26 +202,25 @@ def codec_rd_curve(codec, image, result=None, byte_lengths=None, points=32, max_
         else:
             # the forward transform of the picture with the codec's settings (the pyramid left out)
             d_maxabs = dev((1,), np.uint32)
-            fwd = {8: (L.spiht_dwt_pyramid_batch_f64, ()), 1: (L.spiht_dwt_pyramid_batch_u8, (None,)),
-                   2: (L.spiht_dwt_pyramid_batch_u16, (None,))}[es]
             with codec._color():
-                _lib.check(fwd[0](ctx.handle, vp(d_pic.ptr), *fwd[1], 1, c, H, W, codec.wid, codec.mid, codec._lv, q,
-                                  codec._mults_p, vp(d_x.ptr), None, None, vp(d_maxabs.ptr)))
+                _lib.check(elem.entry(L, "spiht_dwt_pyramid_batch_")(ctx.handle, vp(d_pic.ptr), *view, 1, c, H, W, codec.wid, codec.mid,
+                                                                     codec._lv, q, codec._mults_p, vp(d_x.ptr), None, None,
+                                                                     vp(d_maxabs.ptr)))
         n = len(result.encoded_bytes)
         lens = default_lengths(n, points) if byte_lengths is None else byte_lengths
         K = len(lens)
         if K == 0:
-            return curve_from_sums([], n, [], [], c, H, W, PEAK[None if dtype is None else np.dtype(dtype)]), result
+            return curve_from_sums([], n, [], [], c, H, W, elem.peak), result
         # one row per distinct number of bits read, ascending (what the walk wants); the caller's rows point into them
         uniq = sorted({min(k, n) for k in lens})
         row = {k: i for i, k in enumerate(uniq)}
         U = len(uniq)
-        rec_h, rec_w = (g["rec_h"], g["rec_w"]) if dtype is None else (H, W)
+        rec_h, rec_w = (H, W) if elem.integer else (g["rec_h"], g["rec_w"])
         Kg = min(U, group_size(c, g["enc_h"], g["enc_w"], g["rec_h"], g["rec_w"], max_bytes), 65535)
         d_rec = dev((Kg, c, g["enc_h"], g["enc_w"]), np.int32)
         d_dec = dev((Kg, c, rec_h, rec_w), image.dtype)
         d_e = dev((U, 2), np.uint64)
-        d_s = dev((U, c), np.float64 if dtype is None else np.uint64)
+        d_s = dev((U, c), np.uint64 if elem.integer else np.float64)
         data = np.frombuffer(result.encoded_bytes[:uniq[-1]], dtype=np.uint8)
         for k0 in range(0, U, Kg):
             kg = min(Kg, U - k0)
@@ -235,41 +230,38 @@ def codec_rd_curve(codec, image, result=None, byte_lengths=None, points=32, max_
                 g["ll_h"], g["ll_w"], vp(bud.ctypes.data), kg, vp(d_rec.ptr)))
             _lib.check(L.spiht_sqerr_i32(ctx.handle, vp(d_x.ptr), vp(d_rec.ptr), kg, c, g["enc_h"], g["enc_w"],
                                          vp(d_e.ptr + 16 * k0)))
-            idwt = (ctx.handle, vp(d_rec.ptr)) + (() if dtype is None else (None,)) + \
-                (kg, c, H, W, codec.wid, codec.mid, codec._lv, q, codec._mults_p, vp(d_dec.ptr))
+            idwt = (kg, c, H, W, codec.wid, codec.mid, codec._lv, q, codec._mults_p, vp(d_dec.ptr))
+            sse = elem.entry(L, "spiht_sse_")
             with codec._color():
-                if dtype is None:
-                    _lib.check(L.spiht_dequant_idwt_batch_f64(*idwt))
-                    _lib.check(L.spiht_sse_f64(ctx.handle, vp(d_pic.ptr), vp(d_dec.ptr), kg, c, H, W, rec_h, rec_w,
-                                               vp(d_s.ptr + 8 * c * k0)))
+                if elem.integer:  # (the flags form with no flags; both pictures dense)
+                    _lib.check(elem.entry(L, "spiht_dequant_idwt_flags_batch_")(ctx.handle, vp(d_rec.ptr), None, *idwt, *view))
+                    _lib.check(sse(ctx.handle, vp(d_pic.ptr), *view, vp(d_dec.ptr), kg, c, H, W, vp(d_s.ptr + 8 * c * k0)))
                 else:
-                    inv, sse = ((L.spiht_dequant_idwt_flags_batch_u16, L.spiht_sse_u16) if es == 2 else
-                                (L.spiht_dequant_idwt_flags_batch_u8, L.spiht_sse_u8))
-                    _lib.check(inv(*idwt, None))
-                    _lib.check(sse(ctx.handle, vp(d_pic.ptr), None, vp(d_dec.ptr), kg, c, H, W, vp(d_s.ptr + 8 * c * k0)))
+                    _lib.check(L.spiht_dequant_idwt_batch_f64(ctx.handle, vp(d_rec.ptr), *idwt))
+                    _lib.check(sse(ctx.handle, vp(d_pic.ptr), vp(d_dec.ptr), kg, c, H, W, rec_h, rec_w, vp(d_s.ptr + 8 * c * k0)))
         ctx.synchronize()
         e, s = d_e.download(), d_s.download()
     finally:
         for d in held:
             d.free()
     coef = [int(e[row[min(k, n)], 0]) | (int(e[row[min(k, n)], 1]) << 64) for k in lens]
-    if dtype is None:
+    if elem.integer:
+        sse_rows = sums = [[int(v) for v in s[row[min(k, n)]]] for k in lens]
+    else:
         sse_rows = np.ascontiguousarray(s[[row[min(k, n)] for k in lens]])
         sums = [[float(v) for v in r] for r in sse_rows]
-    else:
-        sse_rows = sums = [[int(v) for v in s[row[min(k, n)]]] for k in lens]
-    curve = curve_from_sums(lens, n, coef, sums, c, H, W, PEAK[None if dtype is None else np.dtype(dtype)])
+    curve = curve_from_sums(lens, n, coef, sums, c, H, W, elem.peak)
     curve.sse = sse_rows
     return curve, result
 
 
-def codec_cut(codec, image, result, points, dtype, field, passes):
+def codec_cut(codec, image, result, points, elem, field, passes):
     """the search on one field of the curve -> (EncodingResult of the cut stream, the field's value there, met)"""
     points = _points_arg(points)
     kept = []  # the picture and X on the device, uploaded and transformed once for all rounds
 
     def evaluate(lengths):
-        curve, _ = codec_rd_curve(codec, image, result, lengths, points, dtype=dtype, kept=kept)
+        curve, _ = codec_rd_curve(codec, image, result, lengths, points, elem=elem, kept=kept)
         return getattr(curve, field)
 
     try:

@@ -13,9 +13,10 @@ from typing import Any, List, Optional, Tuple, Union
 
 import numpy as np
 
-from . import _lib, color_models, floatpx
+from . import _lib, color_models, floatpx, px
 from . import spiht as spiht_rs
 from .floatpx import check_float_view  # noqa: F401  (the float kinds' view rule, beside check_u8_view / check_u16_view)
+from .px import _check_aligned, _check_int_view, _is_dtype  # noqa: F401  (the rules by dtype; px.Elem has them by element)
 
 
 def quantize(arr, q_scale=10.):
@@ -189,16 +190,7 @@ def decode_image(encoding_result: EncodingResult, spiht_settings: SpihtSettings,
         image = decode_from_rec_arr(**d, spiht_settings=spiht_settings)
         return image, spiht_metadata
     # decode_rec_array + decode_from_rec_arr (wrapper:218-281) as one C call: the coefficient array never leaves HBM
-    _check_version(encoding_result)
-    c = encoding_result.c
-    g, keep, args = _decode_args(encoding_result, spiht_settings)
-    out = _lib.result_array((c, g["rec_h"], g["rec_w"]), np.float64)  # (page-locked: the copy back is one DMA)
-    ctx = _lib.default_context()
-    if spiht_settings.color_model is not None and c != 3:
-        raise ValueError("colour conversion needs 3 channels")
-    with color_models.fused(ctx, spiht_settings.color_model):  # wrapper:278-279, inside the last level of the inverse transform
-        _lib.check(_lib.lib().spiht_decode_image_host_f64(ctx.handle, *args, C.c_void_p(out.ctypes.data)))
-    return out
+    return _decode_image_px(encoding_result, spiht_settings, px.F64)
 
 
 def _check_version(encoding_result):
@@ -221,23 +213,6 @@ def _decode_args(encoding_result, spiht_settings):
                float(spiht_settings.quantization_scale), mults_p)
 
 
-def _check_int_view(bits, shape, strides, output):
-    """check_u8_view / check_u16_view: `bits` 8 or 16"""
-    shape, strides = [int(x) for x in shape], [int(x) for x in strides]
-    if len(shape) != len(strides) or len(shape) not in (3, 4):
-        raise ValueError("%d strides for a %d-dimensional picture" % (len(strides), len(shape)))
-    if len(shape) == 3:
-        shape, strides = [1] + shape, [0] + strides
-    if min(shape) < 1:
-        raise ValueError("empty %d-bit picture %s" % (bits, shape))
-    st = np.ascontiguousarray(strides, dtype=np.int64)
-    fn = _lib.lib().spiht_check_view_u16 if bits == 16 else _lib.lib().spiht_check_view_u8
-    if fn(shape[0], shape[1], shape[2], shape[3], C.c_void_p(st.ctypes.data), int(bool(output))):
-        raise ValueError("the strides %s of the %d-bit %s %s are not supported (negative%s%s)"
-                         % (strides, bits, "output" if output else "input", shape, ", odd" if bits == 16 else "",
-                            ", or overlapping" if output else ""))
-
-
 def check_u8_view(shape, strides, output):
     """The library's rule for an 8-bit view (include/spiht_hip.h, *_u8; spiht_check_view_u8): byte strides of a (B, c, h, w)
     or (c, h, w) `shape` are non-negative, and a view that is written does not overlap itself -- sorted by stride, every
@@ -249,17 +224,6 @@ def check_u16_view(shape, strides, output):
     """The library's rule for a 16-bit view (include/spiht_hip.h, *_u16; spiht_check_view_u16): as check_u8_view, the strides
     still in BYTES (numpy's .strides as they are) and all of them even; the overlap rule counts a sample's two bytes."""
     _check_int_view(16, shape, strides, output)
-
-
-def _check_aligned(ptr, dtype):
-    """a uint16 picture starts at an even address (the 16-bit loads and stores of the device)"""
-    if int(ptr) % np.dtype(dtype).itemsize:
-        raise ValueError("the %d-bit picture at address %#x is not aligned to its samples" % (8 * np.dtype(dtype).itemsize, int(ptr)))
-
-
-def _is_dtype(a, dtype):
-    """a numpy array of `dtype` in either byte order"""
-    return isinstance(a, np.ndarray) and a.dtype.newbyteorder("=") == np.dtype(dtype)
 
 
 def _int_picture(image, spiht_settings, dtype, name):
@@ -279,15 +243,11 @@ def _int_picture(image, spiht_settings, dtype, name):
     return image
 
 
-def _u8_picture(image, spiht_settings):
-    return _int_picture(image, spiht_settings, np.uint8, "encode_image_u8")
-
-
-def _encode_image_int(image, spiht_settings, level, max_bits, channels_last, dtype, name, fn_name, kind=()):
-    """kind: () for the integer calls, (kind id,) for the *_flt ones -- the argument behind the context"""
-    if _is_dtype(image, dtype) and image.ndim == 3 and channels_last:
+def _encode_image_px(image, spiht_settings, level, max_bits, channels_last, elem, name):
+    """the encode calls of the elements that come as a view: the picture goes as it lies, by its own strides"""
+    if _is_dtype(image, elem.storage) and image.ndim == 3 and channels_last:
         image = image.transpose(2, 0, 1)
-    image = _int_picture(image, spiht_settings, dtype, name)
+    image = _int_picture(image, spiht_settings, elem.storage, name)
     c, h, w = image.shape
     wid, mid = _wavelet_mode_ids(spiht_settings)
     g = _geometry(h, w, wid, level, mid)
@@ -296,30 +256,38 @@ def _encode_image_int(image, spiht_settings, level, max_bits, channels_last, dty
         max_bits = 99999999999999999
     max_bits = spiht_rs._as_usize(max_bits, "max_bits")
     strides = np.array(image.strides, dtype=np.int64)
-    if kind:
-        floatpx.check_float_view(kind[0], image.shape, strides, False)
-    else:
-        _check_int_view(8 * np.dtype(dtype).itemsize, image.shape, strides, False)
-    _check_aligned(image.ctypes.data, dtype)
-    return _encode_host(_lib.default_context(), getattr(_lib.lib(), fn_name),
-                        (*kind, C.c_void_p(image.ctypes.data), C.c_void_p(strides.ctypes.data)), (c, h, w), g, wid, mid, level,
+    elem.check_view(image.shape, strides, False)
+    elem.check_aligned(image.ctypes.data)
+    return _encode_host(_lib.default_context(), elem.entry(_lib.lib(), "spiht_encode_image_host_"),
+                        (C.c_void_p(image.ctypes.data), C.c_void_p(strides.ctypes.data)), (c, h, w), g, wid, mid, level,
                         spiht_settings, mults_p, max_bits)
 
 
-def _decode_image_int(encoding_result, spiht_settings, channels_last, dtype, fn_name, kind=()):
-    """kind: () for the integer calls, (kind id,) for the *_flt ones -- the argument behind the context"""
+def _decode_image_px(encoding_result, spiht_settings, elem, channels_last=False, reduce=None, crop=False):
+    """every decode call that returns a picture: float64 pictures are the uncropped rec_h x rec_w of the inverse transform,
+    dense; a view element's are cropped to the picture (reduce: to the band) and written by strides.  reduce=None: the
+    full-size entry point"""
     _check_version(encoding_result)
-    h, w, c = encoding_result.h, encoding_result.w, encoding_result.c
-    if spiht_settings.color_model is not None and c != 3:
+    er = encoding_result
+    rs = None if reduce is None else reduced_shape(er.h, er.w, spiht_settings, er.level, reduce)
+    if spiht_settings.color_model is not None and er.c != 3:
         raise ValueError("colour conversion needs 3 channels")
-    _, keep, args = _decode_args(encoding_result, spiht_settings)
-    out = _lib.result_array((h, w, c) if channels_last else (c, h, w), dtype)
-    strides = np.array((1, w * c, c) if channels_last else (h * w, w, 1), dtype=np.int64) * np.dtype(dtype).itemsize
+    g, keep, args = _decode_args(er, spiht_settings)
+    if elem.view:
+        h, w = (er.h, er.w) if rs is None else (rs["pic_h"], rs["pic_w"])
+    else:
+        h, w = (g if rs is None else rs)["rec_h"], (g if rs is None else rs)["rec_w"]
+    c, es = er.c, elem.itemsize
+    out = _lib.result_array((h, w, c) if channels_last else (c, h, w), elem.storage)
+    view = ()
+    if elem.view:
+        strides = np.array(elem.channels_last_strides((c, h, w)) if channels_last else (h * w * es, w * es, es), dtype=np.int64)
+        view = (C.c_void_p(strides.ctypes.data),)
+    stem, tail = ("spiht_decode_image_host_", ()) if reduce is None else ("spiht_decode_image_reduced_host_", (int(reduce),))
     ctx = _lib.default_context()
-    with color_models.fused(ctx, spiht_settings.color_model):
-        _lib.check(getattr(_lib.lib(), fn_name)(ctx.handle, *kind, *args, C.c_void_p(out.ctypes.data),
-                                                C.c_void_p(strides.ctypes.data)))
-    return out
+    with color_models.fused(ctx, spiht_settings.color_model):  # wrapper:278-279, inside the last level of the inverse transform
+        _lib.check(elem.entry(_lib.lib(), stem)(ctx.handle, *args, C.c_void_p(out.ctypes.data), *view, *tail))
+    return _crop_window(out, rs, crop, channels_last)
 
 
 def encode_image_u8(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSettings(), level: Optional[int] = None,
@@ -327,14 +295,13 @@ def encode_image_u8(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSett
     """8-bit pixels: the EncodingResult of encode_image(image / 255.0, ...), field by field, with the conversion done on the
     device (only the bytes cross the link).  image: uint8 (c, h, w), or (h, w, c) with channels_last -- any strides (an
     RGBA buffer's rgba[..., :3] view goes as it is)."""
-    return _encode_image_int(image, spiht_settings, level, max_bits, channels_last, np.uint8, "encode_image_u8",
-                             "spiht_encode_image_host_u8")
+    return _encode_image_px(image, spiht_settings, level, max_bits, channels_last, px.U8, "encode_image_u8")
 
 
 def decode_image_u8(encoding_result: EncodingResult, spiht_settings: SpihtSettings, channels_last: bool = False) -> np.ndarray:
     """8-bit pixels: (np.clip(decode_image(r, s), 0, 1) * 255).astype(np.uint8) cropped to the encoded picture's h x w, with
     the conversion done on the device.  Returns a new uint8 array (c, h, w), or (h, w, c) with channels_last."""
-    return _decode_image_int(encoding_result, spiht_settings, channels_last, np.uint8, "spiht_decode_image_host_u8")
+    return _decode_image_px(encoding_result, spiht_settings, px.U8, channels_last)
 
 
 def encode_image_u16(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSettings(), level: Optional[int] = None,
@@ -342,15 +309,14 @@ def encode_image_u16(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSet
     """16-bit pixels: the EncodingResult of encode_image(image / 65535.0, ...), field by field, with the conversion done on
     the device (two bytes per sample cross the link).  image: uint16 (c, h, w), or (h, w, c) with channels_last -- any
     non-negative strides (a 16-bit RGBA buffer's rgba[..., :3] view goes as it is); the other byte order is copied."""
-    return _encode_image_int(image, spiht_settings, level, max_bits, channels_last, np.uint16, "encode_image_u16",
-                             "spiht_encode_image_host_u16")
+    return _encode_image_px(image, spiht_settings, level, max_bits, channels_last, px.U16, "encode_image_u16")
 
 
 def decode_image_u16(encoding_result: EncodingResult, spiht_settings: SpihtSettings, channels_last: bool = False) -> np.ndarray:
     """16-bit pixels: (np.clip(decode_image(r, s), 0, 1) * 65535).astype(np.uint16) cropped to the encoded picture's h x w,
     with the conversion done on the device.  Returns a new uint16 array (c, h, w), or (h, w, c) with channels_last.  The
     stream may come from any pixel format."""
-    return _decode_image_int(encoding_result, spiht_settings, channels_last, np.uint16, "spiht_decode_image_host_u16")
+    return _decode_image_px(encoding_result, spiht_settings, px.U16, channels_last)
 
 
 def encode_image_float(image: np.ndarray, spiht_settings: SpihtSettings = SpihtSettings(), level: Optional[int] = None,
@@ -364,9 +330,8 @@ def encode_image_float(image: np.ndarray, spiht_settings: SpihtSettings = SpihtS
     [..., :3] view goes as it is; a negative stride or the other byte order is copied first); for bfloat16 the uint16 bit
     patterns with dtype="bfloat16" or torch.bfloat16 (floatpx.kind_arg).  The kind is inferred from a float32 / float16
     array.  Non-finite samples are outside the contract, as they are for encode_image."""
-    kind = floatpx.input_kind(image, dtype, "encode_image_float")
-    return _encode_image_int(image, spiht_settings, level, max_bits, channels_last, floatpx.storage_dtype(kind),
-                             "encode_image_float", "spiht_encode_image_host_flt", (kind,))
+    elem = px.of_kind_id(floatpx.input_kind(image, dtype, "encode_image_float"))
+    return _encode_image_px(image, spiht_settings, level, max_bits, channels_last, elem, "encode_image_float")
 
 
 def decode_image_float(encoding_result: EncodingResult, spiht_settings: SpihtSettings, dtype=np.float32,
@@ -380,9 +345,7 @@ def decode_image_float(encoding_result: EncodingResult, spiht_settings: SpihtSet
         torch.from_numpy(a.view(np.int16)).view(torch.bfloat16)
 
     The stream may come from any pixel format."""
-    kind = floatpx.kind_arg(dtype)
-    return _decode_image_int(encoding_result, spiht_settings, channels_last, floatpx.storage_dtype(kind),
-                             "spiht_decode_image_host_flt", (kind,))
+    return _decode_image_px(encoding_result, spiht_settings, px.of_kind(dtype), channels_last)
 
 
 def reduced_shape(h: int, w: int, spiht_settings: SpihtSettings, level: Optional[int], reduce: int):
@@ -414,11 +377,11 @@ def _reduce_arg(reduce, levels):
 
 
 def _crop_window(picture, rs, crop, channels_last=False):
-    """crop=True: the centred in_h x in_w window of a reduced picture (a view)"""
+    """crop=True: the centred in_h x in_w window of a reduced picture, or of a batch of them (a view)"""
     if not crop:
         return picture
     ys, xs = slice(rs["off_y"], rs["off_y"] + rs["in_h"]), slice(rs["off_x"], rs["off_x"] + rs["in_w"])
-    return picture[ys, xs, :] if channels_last else picture[:, ys, xs]
+    return picture[..., ys, xs, :] if channels_last else picture[..., ys, xs]
 
 
 def decode_image_reduced(encoding_result: EncodingResult, spiht_settings: SpihtSettings, reduce: int,
@@ -437,34 +400,7 @@ def decode_image_reduced(encoding_result: EncodingResult, spiht_settings: SpihtS
     approaches four samples a side).  crop=True returns the centred ceil(h / 2^reduce) x ceil(w / 2^reduce) window of it, as
     a view: offset (hs[reduce] - ceil(h / 2^reduce)) // 2 per axis, 0 under periodization.  That window is the downsampled
     picture to within a sample: the sampling phase of an even-length filter is not an integer."""
-    _check_version(encoding_result)
-    er = encoding_result
-    rs = reduced_shape(er.h, er.w, spiht_settings, er.level, reduce)
-    if spiht_settings.color_model is not None and er.c != 3:
-        raise ValueError("colour conversion needs 3 channels")
-    _, keep, args = _decode_args(er, spiht_settings)
-    out = _lib.result_array((er.c, rs["rec_h"], rs["rec_w"]), np.float64)
-    ctx = _lib.default_context()
-    with color_models.fused(ctx, spiht_settings.color_model):
-        _lib.check(_lib.lib().spiht_decode_image_reduced_host_f64(ctx.handle, *args, C.c_void_p(out.ctypes.data), int(reduce)))
-    return _crop_window(out, rs, crop)
-
-
-def _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, dtype, fn_name, kind=()):
-    _check_version(encoding_result)
-    er = encoding_result
-    rs = reduced_shape(er.h, er.w, spiht_settings, er.level, reduce)
-    c, h, w = er.c, rs["pic_h"], rs["pic_w"]
-    if spiht_settings.color_model is not None and c != 3:
-        raise ValueError("colour conversion needs 3 channels")
-    _, keep, args = _decode_args(er, spiht_settings)
-    out = _lib.result_array((h, w, c) if channels_last else (c, h, w), dtype)
-    strides = np.array((1, w * c, c) if channels_last else (h * w, w, 1), dtype=np.int64) * np.dtype(dtype).itemsize
-    ctx = _lib.default_context()
-    with color_models.fused(ctx, spiht_settings.color_model):
-        _lib.check(getattr(_lib.lib(), fn_name)(ctx.handle, *kind, *args, C.c_void_p(out.ctypes.data),
-                                                C.c_void_p(strides.ctypes.data), int(reduce)))
-    return _crop_window(out, rs, crop, channels_last)
+    return _decode_image_px(encoding_result, spiht_settings, px.F64, False, reduce, crop)
 
 
 def decode_image_reduced_u8(encoding_result: EncodingResult, spiht_settings: SpihtSettings, reduce: int, crop: bool = False,
@@ -472,15 +408,13 @@ def decode_image_reduced_u8(encoding_result: EncodingResult, spiht_settings: Spi
     """8-bit pixels at 1/2^reduce size: (np.clip(decode_image_reduced(r, s, reduce), 0, 1) * 255).astype(np.uint8) cropped to
     the band size (c, pic_h, pic_w) (reduced_shape) -- the rule of decode_image_u8 one pyramid level up --, converted on the
     device; (pic_h, pic_w, c) with channels_last.  crop=True: the centred window, as decode_image_reduced."""
-    return _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, np.uint8,
-                                     "spiht_decode_image_reduced_host_u8")
+    return _decode_image_px(encoding_result, spiht_settings, px.U8, channels_last, reduce, crop)
 
 
 def decode_image_reduced_u16(encoding_result: EncodingResult, spiht_settings: SpihtSettings, reduce: int, crop: bool = False,
                              channels_last: bool = False) -> np.ndarray:
     """16-bit pixels at 1/2^reduce size: as decode_image_reduced_u8 with 65535 for 255."""
-    return _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, np.uint16,
-                                     "spiht_decode_image_reduced_host_u16")
+    return _decode_image_px(encoding_result, spiht_settings, px.U16, channels_last, reduce, crop)
 
 
 def decode_image_reduced_float(encoding_result: EncodingResult, spiht_settings: SpihtSettings, reduce: int, dtype=np.float32,
@@ -488,9 +422,7 @@ def decode_image_reduced_float(encoding_result: EncodingResult, spiht_settings: 
     """Float pixels at 1/2^reduce size: floatpx.convert(decode_image_reduced(r, s, reduce), dtype) cropped to the band size
     (c, pic_h, pic_w) (reduced_shape), as the integer forms are -- the rule of decode_image_float one pyramid level up --,
     converted on the device; (pic_h, pic_w, c) with channels_last.  crop=True: the centred window, as decode_image_reduced."""
-    kind = floatpx.kind_arg(dtype)
-    return _decode_image_reduced_int(encoding_result, spiht_settings, reduce, crop, channels_last, floatpx.storage_dtype(kind),
-                                     "spiht_decode_image_reduced_host_flt", (kind,))
+    return _decode_image_px(encoding_result, spiht_settings, px.of_kind(dtype), channels_last, reduce, crop)
 
 
 def _band_sizes(h, w, wavelet, levels, mode="reflect"):

@@ -50,11 +50,10 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import _lib, alloc, floatpx
+from . import _lib, alloc, floatpx, px
 from . import overlap as _overlap
 from .batch import BatchCodec, DeviceArray
-from .spiht_wrapper import (ENCODER_DECODER_VERSION, EncodingResult, SpihtSettings, _check_aligned, _check_int_view,
-                            _check_version, _is_dtype, _wavelet_mode_ids)
+from .spiht_wrapper import ENCODER_DECODER_VERSION, EncodingResult, SpihtSettings, _check_version, _wavelet_mode_ids
 
 MAGIC = b"SPTL"
 CONTAINER_VERSION = 1
@@ -388,26 +387,7 @@ def _ptr(x):
     return int(x.ptr) if hasattr(x, "ptr") else int(x)
 
 
-# the element types of the library's tile entry points, by the suffix of their names
-_SUFFIX = {np.dtype(np.uint8): "u8", np.dtype(np.uint16): "u16", np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
-
-
-class _FloatKind:
-    """the element type of float pixels out and in (floatpx: float32, float16, bfloat16), where the others are an np.dtype: the
-    kind's id, its bytes per sample and the numpy type its pictures come in (bfloat16: uint16 bit patterns)"""
-    kind = "F"  # (np.dtype.kind of the others: "u", "f")
-
-    def __init__(self, dtype):
-        self.id = floatpx.kind_id(dtype)
-        self.itemsize = floatpx.itemsize(self.id)
-        self.storage = floatpx.storage_dtype(self.id)
-
-
-def _elem(dtype):
-    """an element type as the tile calls name it: a _FloatKind as it is, anything else as an np.dtype"""
-    return dtype if isinstance(dtype, _FloatKind) else np.dtype(dtype)
-
-
+# the element type of a tile call is a px.Elem: of_dtype of a DeviceArray's dtype, float_elem(dtype) for the float kinds.
 # float pixels out and in: a tile batch of a kind is copied as elements of its size -- both 16-bit kinds by the uint16 copies,
 # float32 by the strided 4-byte ones; the blend rounds to the kind at its store, the error sums widen the original's samples
 _FLOAT_COPY = {("spiht_tile_paste_", 2): "spiht_tile_paste_u16", ("spiht_tile_paste_", 4): "spiht_tile_paste_f32s",
@@ -419,20 +399,12 @@ _FLOAT_KIND_CALL = ("spiht_tile_blend_", "spiht_sse_tiles_", "spiht_sse_tiles_w_
 
 
 def _entry(L, stem, dt):
-    """the library's entry point of that stem for an element type (an np.dtype): (L, "spiht_tile_paste_", uint16) ->
-    L.spiht_tile_paste_u16; for a _FloatKind the copy of its element size, or the *_flt call with the kind behind the context
-    (the blend into the kind, the error sums of tiles of the kind)"""
-    if isinstance(dt, _FloatKind):
-        if stem in _FLOAT_KIND_CALL:
-            fn = getattr(L, stem + "flt")
-            return lambda ctx, *a: fn(ctx, dt.id, *a)
+    """the library's entry point of a tile stem for an element type (px.Elem.entry: (L, "spiht_tile_paste_", px.U16) ->
+    L.spiht_tile_paste_u16), with the one rule that is the tiles' own: a tile batch of a float kind is copied by its element
+    size; only the blend into the kind and the error sums of tiles of the kind are *_flt calls"""
+    if dt.kind is not None and stem not in _FLOAT_KIND_CALL:
         return getattr(L, _FLOAT_COPY[stem, dt.itemsize])
-    return getattr(L, stem + _SUFFIX[dt])
-
-
-def _peak(dtype):
-    """the largest pixel value: of 8- and 16-bit pixels the type's, of float pixels 1.0"""
-    return float(np.iinfo(dtype).max) if _elem(dtype).kind == "u" else 1.0
+    return dt.entry(L, stem)
 
 
 class TiledCodec:
@@ -504,24 +476,6 @@ class TiledCodec:
             b.free()
         self._bufs = {}
 
-    def _strides_arg(self, shape, strides, output, dtype):
-        if strides is None:
-            return None, None
-        st = np.ascontiguousarray([int(x) for x in strides], dtype=np.int64)
-        if isinstance(dtype, _FloatKind):
-            floatpx.check_float_view(dtype.id, shape, st, output)
-        else:
-            _check_int_view(8 * np.dtype(dtype).itemsize, shape, st, output)
-        return st, C.c_void_p(st.ctypes.data)
-
-    def _tile_call(self, op, dt):
-        """the tile codec's batched call for an element type (an np.dtype); op: "encode", "decode" or "decode_reduced".  The
-        float form is the one of the codec's own float pixels; a _FloatKind: the *_float call, which takes the kind behind the
-        output (behind `reduce`; an encode: behind d_max_n)"""
-        if isinstance(dt, _FloatKind):
-            return getattr(self.codec, op + "_device_float")
-        return getattr(self.codec, op + "_device" + ("_" + _SUFFIX[dt] if dt.kind == "u" else ""))
-
     def _download(self, ptr, shape, dtype):
         """a host array of that shape, filled from the device address: one download (none of an empty array)"""
         out = np.empty(shape, dtype=dtype)
@@ -555,7 +509,7 @@ class TiledCodec:
         """what a call with a weight map needs of the codec, before anything is uploaded or queued"""
         if self.allocate is None:
             raise ValueError('%s: a weight map steers allocate="rd"; the codec was not built with it' % name)
-        if _elem(dtype).kind == "u" and self.c * self.th * self.tw > alloc.ROI_MAX_TILE_SAMPLES:
+        if px.of_dtype(dtype).integer and self.c * self.th * self.tw > alloc.ROI_MAX_TILE_SAMPLES:
             raise ValueError("%s: the exact weighted sum of integer pixels takes tiles of c * th * tw <= 2^24 samples, not %d"
                              % (name, self.c * self.th * self.tw))
 
@@ -596,7 +550,7 @@ class TiledCodec:
     def _targets_upload(self, rows, sums, dtype):
         """rows: Q lists of N target PSNRs; sums: the N weight sums -> the device double [Q][N] of squared errors, in the buffer
         "targets": one upload"""
-        peak = _peak(dtype)
+        peak = px.of_dtype(dtype).peak
         table = np.array([[alloc.target_sqerr(db, peak, self.c, s) for db, s in zip(row, sums)] for row in rows], dtype=np.float64)
         d_target = self._buf("targets", table.nbytes)
         self.ctx.upload(d_target.ptr, table)
@@ -611,7 +565,8 @@ class TiledCodec:
         dist, met, weight_sum, dtype = target
         if np.isnan(dist):
             return TileAllocation(float(lam), nbytes, None, None, bool(met))
-        return TileAllocation(float(lam), nbytes, float(dist), psnr_of(float(dist) / (self.c * weight_sum), _peak(dtype)), bool(met))
+        return TileAllocation(float(lam), nbytes, float(dist), psnr_of(float(dist) / (self.c * weight_sum), px.of_dtype(dtype).peak),
+                              bool(met))
 
     def encode_device(self, d_img, N, d_packed, d_lens, d_max_n, strides=None, d_roi=None, roi_stride=0, d_target=None):
         """d_img: DeviceArray of N pictures [N, c, H, W] -- float64 (float32 for a float32 codec), or uint8 / uint16 laid out by
@@ -645,8 +600,7 @@ class TiledCodec:
         """the cut and the batched encode of the N * T tiles -> (element type, the buffers of the tiles, the stream slots and
         the streams' lengths in bits)"""
         N = int(N)
-        dt = _elem(d_img.dtype)
-        flt = isinstance(dt, _FloatKind)  # float pixels in: a view of the kind, cut as elements of its size
+        dt = px.of_dtype(d_img.dtype)  # (float pixels in: a view of the kind, cut as elements of its size)
         NT, vp = N * self.T, C.c_void_p
         if N < 1:
             raise ValueError("%s: no pictures" % name)
@@ -656,17 +610,17 @@ class TiledCodec:
         stem = "spiht_tile_cut_"
         if self.overlap:
             geom, stem = geom + (self.overlap,), "spiht_tile_cut_overlap_"
-        view = ()  # the integer forms take a view of the pictures: the strides, behind the address
-        if dt.kind == "u" or flt:
-            st, st_p = self._strides_arg((N, self.c, self.H, self.W), strides, False, dt)
-            _check_aligned(d_img.ptr, dt.storage if flt else dt)
+        view = ()  # the integer forms and the float kinds take a view of the pictures: the strides, behind the address
+        if dt.view:
+            st, st_p = dt.strides_arg((N, self.c, self.H, self.W), strides, False)
+            dt.check_aligned(d_img.ptr)
             view = (st_p,)
-        elif dt != self.pixel_dtype or strides is not None:
-            raise ValueError("%s: %s pictures, the codec's are dense %s" % (name, dt.name, self.pixel_dtype.name))
+        elif dt.storage != self.pixel_dtype or strides is not None:
+            raise ValueError("%s: %s pictures, the codec's are dense %s" % (name, dt.storage.name, self.pixel_dtype.name))
         _lib.check(_entry(self.L, stem, dt)(self.ctx.handle, vp(d_img.ptr), *view, *geom, vp(d_tiles.ptr)))
         d_slots = self._buf("slots", NT * self.codec.slot_stride)
         d_nbits = self._buf("nbits", NT * 8)
-        self._tile_call("encode", dt)(d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr, *((dt.id,) if flt else ()))
+        self.codec._encode_device(dt, d_tiles.ptr, NT, d_slots.ptr, d_nbits.ptr, d_max_n.ptr)
         return dt, d_tiles, d_slots, d_nbits
 
     def _allocate_device(self, dt, N, d_tiles, d_slots, d_nbits, d_max_n, roi, budgets, d_target=None, s=""):
@@ -681,7 +635,7 @@ class TiledCodec:
         d_lam = self._buf("lambda" + s, Q * N * 8)
         if d_target is not None:
             d_dist, d_met = self._buf("tdist" + s, Q * N * 8), self._buf("tmet" + s, Q * N * 4)
-        args = (self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.kind == "u" else 0, self.points, N, self.T)
+        args = (self.ctx.handle, vp(d_nbits.ptr), vp(d_D.ptr), 1 if dt.integer else 0, self.points, N, self.T)
         for q, bits in enumerate(budgets):
             cut, lam = vp(d_cut.ptr + 8 * q * NT), vp(d_lam.ptr + 8 * q * N)
             if d_target is None:
@@ -700,9 +654,9 @@ class TiledCodec:
         NT, K, vp, c = N * self.T, self.points, C.c_void_p, self.c
         stride = self.codec.slot_stride
         tile_dt = dt
-        if isinstance(dt, _FloatKind):
-            dt = np.dtype(np.float64)  # (the decodes' element)
-        integer = dt.kind == "u"
+        if dt.kind is not None:
+            dt = px.F64  # (the decodes' element)
+        integer = dt.integer
         rh, rw = (self.cth, self.ctw) if integer else (self.codec.geom["rec_h"], self.codec.geom["rec_w"])
         H, W = (self.gy * self.cth, self.gx * self.ctw) if self.overlap else (self.H, self.W)
         G = max(1, min(K + 1, int(self.max_bytes) // (NT * (stride + c * rh * rw * dt.itemsize + 9))))
@@ -711,7 +665,6 @@ class TiledCodec:
         d_premaxn = self._buf("premaxn", G * NT)
         d_dec = self._buf("dec", G * NT * c * rh * rw * dt.itemsize)
         d_D = self._buf("D", (K + 1) * NT * 8)
-        dec = self._tile_call("decode", dt)
         if roi is None:
             sse, w_args = _entry(self.L, "spiht_sse_tiles_", tile_dt), ()
         else:
@@ -720,7 +673,7 @@ class TiledCodec:
             g = min(G, K + 1 - k0)
             _lib.check(self.L.spiht_tile_prefix_slots(self.ctx.handle, vp(d_slots.ptr), stride, vp(d_nbits.ptr), NT, K, k0, g,
                                                       vp(d_pre.ptr), stride, vp(d_prebytes.ptr), vp(d_max_n.ptr), vp(d_premaxn.ptr)))
-            dec(d_pre.ptr, d_prebytes.ptr, d_premaxn.ptr, g * NT, d_dec.ptr, slot_stride=stride)
+            self.codec._decode_device(dt, d_pre.ptr, d_prebytes.ptr, d_premaxn.ptr, g * NT, d_dec.ptr, slot_stride=stride)
             _lib.check(sse(self.ctx.handle, vp(d_tiles.ptr), vp(d_dec.ptr), g, N, c, H, W, self.cth, self.ctw, rh, rw,
                            vp(d_D.ptr + 8 * k0 * NT), *w_args))
         return d_D
@@ -826,37 +779,34 @@ class TiledCodec:
     def _decode_slots(self, d_slots, d_nbytes, max_n, stride, sub, window, d_out, strides, rs, reduce):
         """the zero-padded slots of the sub-grid's tiles -> the window: one batched decode, one paste (reduce > 0: one batched
         reduced decode, one mosaic; overlap > 0, every element type: one batched float64 decode of the coded tiles, one blend,
-        which converts the blended sample for 8- and 16-bit output and rounds it for a float kind).  A float kind (_FloatKind) goes
+        which converts the blended sample for 8- and 16-bit output and rounds it for a float kind).  A float kind goes
         the integer kinds' way: the tiles' *_float decode into a dense tile batch of the kind, cropped as theirs, then a copy"""
         (i0, i1, j0, j1), (y0, x0, h, w) = sub, window
         n, vp, k = (i1 - i0) * (j1 - j0), C.c_void_p, int(reduce)
-        dt = _elem(d_out.dtype)
-        integer = dt.kind in "uF"  # (a view of the output, tiles cropped to the picture's samples)
-        # the plan: the batched decode (with what it takes behind the output) and the element type of its tiles, rh x rw of one
-        # decoded tile, the call that assembles them and the geometry it takes in front of the sub-grid and the window
+        dt = px.of_dtype(d_out.dtype)
+        integer = dt.view  # (a view of the output, tiles cropped to the picture's samples)
+        # the plan: the element type of the batched decode's tiles, rh x rw of one decoded tile, the call that assembles them
+        # and the geometry it takes in front of the sub-grid and the window
         rec = self.codec.geom["rec_h"], self.codec.geom["rec_w"]
+        tile_dt = dt
         if k:
-            op, more, tile_dt = "decode_reduced", (k,), dt
             rh, rw = (rs["pic_h"], rs["pic_w"]) if integer else (rs["rec_h"], rs["rec_w"])
             stem, geom = "spiht_tile_mosaic_", (rs["off_y"], rs["off_x"], rs["Hk"], rs["Wk"], rs["thk"], rs["twk"])
         elif self.overlap:
-            op, more, tile_dt, (rh, rw) = "decode", (), np.dtype(np.float64), rec
+            tile_dt, (rh, rw) = px.F64, rec
             stem, geom = "spiht_tile_blend_", (self.H, self.W, self.th, self.tw, self.overlap)
         else:
-            op, more, tile_dt = "decode", (), dt
             rh, rw = (self.th, self.tw) if integer else rec
             stem, geom = "spiht_tile_paste_", (self.H, self.W, self.th, self.tw)
         view = ()  # the integer forms write a view of the output: the strides, behind the address
         if integer:
-            st, st_p = self._strides_arg((self.c, h, w), strides, True, dt)
-            _check_aligned(d_out.ptr, dt.storage if isinstance(dt, _FloatKind) else dt)
+            st, st_p = dt.strides_arg((self.c, h, w), strides, True)
+            dt.check_aligned(d_out.ptr)
             view = (st_p,)
-            if isinstance(dt, _FloatKind) and tile_dt is dt:
-                more = more + (dt.id,)
-        elif dt != np.float64 or strides is not None:
+        elif dt is not px.F64 or strides is not None:
             raise ValueError("decode: the float form gives dense float64 pictures")
         d_dec = self._buf("dec", n * self.c * rh * rw * tile_dt.itemsize)
-        self._tile_call(op, tile_dt)(d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, *more, slot_stride=stride)
+        self.codec._decode_device(tile_dt, d_slots.ptr, d_nbytes.ptr, max_n, n, d_dec.ptr, slot_stride=stride, reduce=k or None)
         _lib.check(_entry(self.L, stem, dt)(self.ctx.handle, vp(d_dec.ptr), self.c, rh, rw, *geom, i0, i1, j0, j1, y0, x0, h, w,
                                             vp(d_out.ptr), *view))
         self.last_tiles_decoded = n
@@ -982,24 +932,24 @@ class TiledCodec:
         """pictures of a float kind [c, H, W] / [N, c, H, W] (or [H, W, c] / [N, H, W, c] with channels_last) -> what encode gives
         for floatpx.to_float64(pictures, kind): allocate="rd", roi and target_psnr as there, with the same ValueErrors"""
         kind = floatpx.input_kind(np.asarray(image_or_images), dtype, "encode_float")
-        return self._encode_host(image_or_images, _FloatKind(kind), channels_last, "encode_float", roi, target_psnr)
+        return self._encode_host(image_or_images, px.of_kind_id(kind), channels_last, "encode_float", roi, target_psnr)
 
     def encode_layered_float(self, image_or_images, layers=None, dtype=None, channels_last=False, roi=None, target_psnr=None):
         """encode_layered of pictures of a float kind, as encode_float"""
         kind = floatpx.input_kind(np.asarray(image_or_images), dtype, "encode_layered_float")
-        return self._encode_host(image_or_images, _FloatKind(kind), channels_last, "encode_layered_float", roi, target_psnr, True,
+        return self._encode_host(image_or_images, px.of_kind_id(kind), channels_last, "encode_layered_float", roi, target_psnr, True,
                                  layers)
 
     def encode_device_float(self, d_img, N, d_packed, d_lens, d_max_n, dtype, strides=None, d_roi=None, roi_stride=0,
                             d_target=None):
         """encode_device of N pictures of the kind `dtype` on the device (a DeviceArray or an address), laid out by `strides`
         (BYTES (sb, sc, sh, sw), non-negative multiples of the element size, as the base; None: dense CHW)"""
-        self.encode_device(_View(_ptr(d_img), _FloatKind(dtype)), N, d_packed, d_lens, d_max_n, strides, d_roi, roi_stride, d_target)
+        self.encode_device(_View(_ptr(d_img), px.of_kind_id(dtype)), N, d_packed, d_lens, d_max_n, strides, d_roi, roi_stride, d_target)
 
     def tile_curves_float(self, image, dtype=None, roi=None):
         """tile_curves of one picture of a float kind: the curves of tile_curves(floatpx.to_float64(image, kind))"""
         image = np.asarray(image)
-        return self.tile_curves(image, _FloatKind(floatpx.input_kind(image, dtype, "tile_curves_float")), roi)
+        return self.tile_curves(image, px.of_kind_id(floatpx.input_kind(image, dtype, "tile_curves_float")), roi)
 
     def _upload_pictures(self, images, dtype, channels_last, name):
         """the host checks of _encode_host and the upload -> (single, N, the device view, strides)"""
@@ -1009,23 +959,16 @@ class TiledCodec:
             images = images[None]
         if images.ndim != 4:
             raise ValueError("%s takes a picture [c, H, W] or pictures [N, c, H, W]" % name)
-        dtype = _elem(dtype)
+        dtype = px.of_dtype(dtype)
         strides = None
-        if dtype.kind == "u" or isinstance(dtype, _FloatKind):  # (a float kind goes in as its storage type: bit patterns)
-            sd = dtype.storage if isinstance(dtype, _FloatKind) else dtype
-            if not _is_dtype(images, sd):
-                raise ValueError("%s takes a %s array, not %s" % (name, sd.name, images.dtype))
-            images = np.ascontiguousarray(images, dtype=sd.newbyteorder("="))
-            if channels_last:
-                N, H, W, c = images.shape
-                es = sd.itemsize
-                strides = (H * W * c * es, es, W * c * es, c * es)
-                shape = (N, c, H, W)
-            else:
-                shape = images.shape
-        else:
-            images = np.ascontiguousarray(images, dtype=dtype)
-            shape = images.shape
+        if dtype.view and not px._is_dtype(images, dtype.storage):  # (a float kind goes in as its storage type: bit patterns)
+            raise ValueError("%s takes a %s array, not %s" % (name, dtype.storage.name, images.dtype))
+        images = np.ascontiguousarray(images, dtype=dtype.storage)
+        shape = images.shape
+        if dtype.view and channels_last:
+            N, H, W, c = shape
+            shape = (N, c, H, W)
+            strides = dtype.channels_last_strides(shape)
         if tuple(shape[1:]) != (self.c, self.H, self.W):
             raise ValueError("%s: pictures of shape %s, the codec's are %s" % (name, tuple(shape[1:]), (self.c, self.H, self.W)))
         d_img = self._buf("img", images.nbytes)
@@ -1062,10 +1005,10 @@ class TiledCodec:
         image = np.asarray(image)
         if image.ndim != 3:
             raise ValueError("tile_curves takes one picture [c, H, W]")
-        dtype = self.pixel_dtype if dtype is None else _elem(dtype)
+        dtype = px.of_dtype(self.pixel_dtype if dtype is None else dtype)
         self._encode_host(image, dtype, False, "tile_curves", roi)
         T, K = self.T, self.points
-        D = self._download(self._bufs["D"].ptr, (K + 1, T), np.uint64 if dtype.kind == "u" else np.float64)
+        D = self._download(self._bufs["D"].ptr, (K + 1, T), np.uint64 if dtype.integer else np.float64)
         nbits = self._download(self._bufs["nbits"].ptr, T, np.uint64)
         maxn = self._download(self._bufs["maxn"].ptr, T, np.uint8)
         nbytes = [(int(v) + 7) // 8 for v in nbits]
@@ -1095,7 +1038,7 @@ class TiledCodec:
         rs = self.reduced_shape(reduce)
         y0, x0, h, w = self._window_arg(window, rs)
         i0, i1, j0, j1 = sub = self._window_tiles(rs, y0, x0, h, w)
-        dtype = _elem(dtype)
+        dtype = px.of_dtype(dtype)
         ts = [i * self.gx + j for i in range(i0, i1) for j in range(j0, j1)]
         n = len(ts)
         # a row of the sub-grid, tiles a .. b - 1, is contiguous in the run (per layer, in the file)
@@ -1121,9 +1064,8 @@ class TiledCodec:
             p += b - a
         d_in = self._buf("in", blob.nbytes)
         self.ctx.upload(d_in.ptr, blob)  # the table, the start planes and the streams of the sub-grid's tiles: one upload
-        es = dtype.itemsize
-        strides = (es, w * self.c * es, self.c * es) if channels_last else None
-        d_out = self._buf("out", self.c * h * w * es)
+        strides = dtype.channels_last_strides((self.c, h, w)) if channels_last else None
+        d_out = self._buf("out", self.c * h * w * dtype.itemsize)
         stride = max(4, (int(total.max()) + 3) & ~3)
         streams = (d_in.ptr + head, nb, d_in.ptr, d_in.ptr + planes)
         where = (sub, (y0, x0, h, w), _View(d_out.ptr, dtype), strides, stride)
@@ -1132,8 +1074,7 @@ class TiledCodec:
         else:
             self.decode_window_device(*streams, *where, reduce)
         self.ctx.synchronize()
-        out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w),
-                                dtype.storage if isinstance(dtype, _FloatKind) else dtype)
+        out = _lib.result_array((h, w, self.c) if channels_last else (self.c, h, w), dtype.storage)
         self.ctx.download(out, d_out.ptr)
         return out
 
@@ -1198,26 +1139,26 @@ class TiledCodec:
     # np.float16, "bfloat16" or a torch dtype; bfloat16 comes as uint16 bit patterns.
     def decode_float(self, result, dtype=np.float32, channels_last=False, reduce=0):
         """-> [c, H, W] (or [H, W, c]) of the kind: floatpx.convert(decode(result, reduce), dtype)"""
-        return self._decode_host(result, None, _FloatKind(dtype), channels_last, reduce)
+        return self._decode_host(result, None, px.of_kind_id(dtype), channels_last, reduce)
 
     def decode_window_float(self, result, y0, x0, h, w, dtype=np.float32, channels_last=False, reduce=0):
         """-> [c, h, w] (or [h, w, c]) of the kind: floatpx.convert(decode_window(result, y0, x0, h, w, reduce), dtype)"""
-        return self._decode_host(result, (y0, x0, h, w), _FloatKind(dtype), channels_last, reduce)
+        return self._decode_host(result, (y0, x0, h, w), px.of_kind_id(dtype), channels_last, reduce)
 
     def decode_layered_float(self, result, upto=None, dtype=np.float32, channels_last=False, reduce=0):
         """floatpx.convert(decode_layered(result, upto, reduce), dtype)"""
-        return self._decode_host(result, None, _FloatKind(dtype), channels_last, reduce, True, upto)
+        return self._decode_host(result, None, px.of_kind_id(dtype), channels_last, reduce, True, upto)
 
     def decode_layered_window_float(self, result, y0, x0, h, w, upto=None, dtype=np.float32, channels_last=False, reduce=0):
         """floatpx.convert(decode_layered_window(result, y0, x0, h, w, upto, reduce), dtype)"""
-        return self._decode_host(result, (y0, x0, h, w), _FloatKind(dtype), channels_last, reduce, True, upto)
+        return self._decode_host(result, (y0, x0, h, w), px.of_kind_id(dtype), channels_last, reduce, True, upto)
 
 
 class _View:
     """a device address with an element type (what the device forms need of a DeviceArray), owning nothing"""
 
     def __init__(self, ptr, dtype):
-        self.ptr, self.dtype = int(ptr), _elem(dtype)
+        self.ptr, self.dtype = int(ptr), px.of_dtype(dtype)
 
 
 # ---- top-level conveniences, after the single-image calls -------------------------------------------------------------
@@ -1255,7 +1196,7 @@ def _encode_tiled(image, tile, spiht_settings, level, max_bits, dtype, channels_
     c, h, w = _picture_shape(image, channels_last)
     if dtype is None:
         dtype = np.float32 if image.dtype in (np.float32, np.float16) else np.float64
-    own = _elem(dtype).kind == "f"  # the codec's own float pixels (integer pixels and the float kinds: a float64 codec)
+    own = not px.of_dtype(dtype).view  # the codec's own float pixels (integer pixels and the float kinds: a float64 codec)
     codec = _codec_for(c, h, w, tile, spiht_settings, level, max_bits, dtype if own else np.float64, allocate, points, spread,
                        overlap)
     return codec._encode_host(image, codec.pixel_dtype if own else dtype, channels_last, name, roi, target_psnr)
@@ -1295,7 +1236,7 @@ def encode_image_tiled_float(image, tile, spiht_settings=SpihtSettings(), level=
     encode_image_tiled(floatpx.to_float64(image, kind), ...), every sample widened exactly on the device -- the float64
     transform, not the single-precision one encode_image_tiled runs for a float32 array"""
     kind = floatpx.input_kind(image, dtype, "encode_image_tiled_float")
-    return _encode_tiled(image, tile, spiht_settings, level, max_bits, _FloatKind(kind), channels_last, "encode_image_tiled_float",
+    return _encode_tiled(image, tile, spiht_settings, level, max_bits, px.of_kind_id(kind), channels_last, "encode_image_tiled_float",
                          allocate, points, spread, roi, target_psnr, overlap)
 
 
@@ -1336,29 +1277,29 @@ def decode_image_window_u16(result, spiht_settings, y0, x0, h, w, channels_last=
 def decode_image_tiled_float(result, spiht_settings, dtype=np.float32, channels_last=False, reduce=0):
     """TiledResult -> the picture in a float kind (np.float32, np.float16, "bfloat16", a torch dtype; bfloat16 as uint16 bit
     patterns): floatpx.convert(decode_image_tiled(result, spiht_settings, reduce), dtype) in every bit, converted on the device"""
-    return _decode_tiled(result, spiht_settings, None, _FloatKind(dtype), channels_last, reduce)
+    return _decode_tiled(result, spiht_settings, None, px.of_kind_id(dtype), channels_last, reduce)
 
 
 def decode_image_window_float(result, spiht_settings, y0, x0, h, w, dtype=np.float32, channels_last=False, reduce=0):
     """floatpx.convert(decode_image_window(result, spiht_settings, y0, x0, h, w, reduce), dtype)"""
-    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), _FloatKind(dtype), channels_last, reduce)
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), px.of_kind_id(dtype), channels_last, reduce)
 
 
 def decode_image_layered_float(result, spiht_settings, upto=None, dtype=np.float32, channels_last=False, reduce=0):
     """floatpx.convert(decode_image_layered(result, spiht_settings, upto, reduce), dtype)"""
-    return _decode_tiled(result, spiht_settings, None, _FloatKind(dtype), channels_last, reduce, True, upto)
+    return _decode_tiled(result, spiht_settings, None, px.of_kind_id(dtype), channels_last, reduce, True, upto)
 
 
 def decode_image_layered_window_float(result, spiht_settings, y0, x0, h, w, upto=None, dtype=np.float32, channels_last=False,
                                       reduce=0):
     """floatpx.convert(decode_image_layered_window(result, spiht_settings, y0, x0, h, w, upto, reduce), dtype)"""
-    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), _FloatKind(dtype), channels_last, reduce, True, upto)
+    return _decode_tiled(result, spiht_settings, (y0, x0, h, w), px.of_kind_id(dtype), channels_last, reduce, True, upto)
 
 
 def float_elem(dtype):
     """the element type the device forms (decode_window_device, decode_device, decode_layers_device) take as d_out.dtype for
     float pixels out"""
-    return _FloatKind(dtype)
+    return px.of_kind_id(dtype)
 
 
 def _encode_layered(image, tile, spiht_settings, level, max_bits, layers, dtype, channels_last, name, points, spread, roi=None,
@@ -1399,7 +1340,7 @@ def encode_image_layered_float(image, tile, spiht_settings=SpihtSettings(), leve
                                points=alloc.POINTS, spread=alloc.SPREAD, channels_last=False, roi=None, target_psnr=None, overlap=0):
     """float pixels in: the LayeredResult of encode_image_layered(floatpx.to_float64(image, kind), ...)"""
     kind = floatpx.input_kind(image, dtype, "encode_image_layered_float")
-    return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, _FloatKind(kind), channels_last,
+    return _encode_layered(image, tile, spiht_settings, level, max_bits, layers, px.of_kind_id(kind), channels_last,
                            "encode_image_layered_float", points, spread, roi, target_psnr, overlap)
 
 

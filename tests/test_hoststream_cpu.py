@@ -165,7 +165,7 @@ def test_decoder_run_keeps_order(dtype):
     from spiht_amd import hoststream as hs
     from spiht_amd import EncodingResult
     B, depth, shape = 3, 2, (3, 4, 6)
-    store = hs._element(dtype)[1]
+    store = hs._element(dtype).storage
     be = FakeBackend(1, store, B, depth, shape)
     dec = hs.StreamDecoder(*shape, level=1, dtype=dtype, batch=B, depth=depth, _backend=be)
     res = [EncodingResult(bytes(range(1 + k % 9)), 4, 6, 3, k % 20, 1) for k in range(19)]
