@@ -1,6 +1,6 @@
-// What the files of the host side (api.cpp and api_*.cpp: the C ABI of libspiht_hip.so, include/spiht_hip.h) share: the status macros, the
-// context and its scratch, the geometry and the pictures of an image call, and the helpers that cross files.  Nothing declared
-// here is exported: the whole header has hidden visibility.
+// What the files of the host side (api_*.cpp and hoststream.cpp: the C ABI of libspiht_hip.so, include/spiht_hip.h) share: the
+// status macros, the context and its scratch, the geometry and the pictures of an image call, and the helpers that cross files.
+// Nothing declared here is exported: the whole header has hidden visibility.
 #pragma once
 #include "../../include/spiht_hip.h"
 
@@ -167,7 +167,7 @@ template <class Fn> static int batch_chunks(int64_t B, int64_t c, Fn fn) {
     return SPIHT_OK;
 }
 
-// ---- api.cpp ---------------------------------------------------------------------------------------------------------
+// ---- api_dwt.cpp: the geometry of an image, the pictures of a call, the two transform drivers ---------------------------------
 struct ImgGeom {
     int L;
     int64_t hs[SPIHT_MAX_LEVELS + 1], ws[SPIHT_MAX_LEVELS + 1];      // band sizes, [0] = image
@@ -176,8 +176,12 @@ struct ImgGeom {
     bool per;  // periodization: ceil(n / 2) coefficients per level and 2 n samples back (the rule below with a two-tap filter)
     int l0;    // levels dropped below level 1 of this geometry (reduced_geometry; 0: level 1 is the picture's own)
 };
+int img_geometry(int64_t H, int64_t W, int F_real, int level, ImgGeom *g, int mode = SPIHT_MODE_REFLECT);
+// ... of a stream (ig) and of its picture at 1/2^reduce size (pig); refuses a reduce outside 0 .. L
+int reduced_open(int64_t H, int64_t W, int wavelet, int mode, int level, int reduce, ImgGeom *ig, ImgGeom *pig);
 // Geometry of the L1Flags words of an image geometry (common.h): false when they do not apply
 bool l1flags_geometry(const ImgGeom &ig, int F, L1Flags *fl);
+int check_img_args(int wavelet, int mode, int64_t B, int64_t c, int64_t H, int64_t W);
 
 // ---- the pictures of an image call -------------------------------------------------------------------------------------------
 // The element of a picture, said once.  Float64 and float32 pictures are transformed in their own precision (EL_F32: the
@@ -191,6 +195,10 @@ static inline int el_size(PicElem el) {
 // the float kind as the kernels want it (PxView.kind; 0: no float kind), and back (EL_NONE: not a kind -- view_pic refuses it)
 static inline int el_flt_kind(PicElem el) { return el >= EL_FLT_F32 && el <= EL_FLT_BF16 ? el - EL_FLT_F32 + SPIHT_FLT_F32 : 0; }
 static inline PicElem el_of_kind(int kind) { return flt_itemsize(kind) ? (PicElem)(EL_FLT_F32 + kind - SPIHT_FLT_F32) : EL_NONE; }
+static inline PicElem el_of_hs(int elem) {  // the element of a host-fed stream: SPIHT_HS_F64 .. SPIHT_HS_BF16, checked by the caller
+    static const PicElem els[] = {EL_F64, EL_U8, EL_U16, EL_FLT_F32, EL_FLT_F16, EL_FLT_BF16};
+    return els[elem];
+}
 
 // A batch of pictures [B, c, h, w] at p: a dense array, or (strided) a view by byte strides that view_pic has checked.  The
 // extern "C" entry points make one; everything behind them passes it on.
@@ -255,6 +263,8 @@ static inline Pic dense_pic(const void *p, PicElem el, bool out = false) {
 enum { PIC_NULL_FIRST = 1, PIC_IMG_ARGS = 2, PIC_EMPTY_OK = 4 };
 int view_pic(Pic *v, const void *p, PicElem el, bool out, const int64_t *strides, int n, int64_t B, int64_t c, int64_t h,
              int64_t w, int rules = 0, int wavelet = 0, int mode = 0);
+// spiht_check_view_*: would view_pic take these four strides of B pictures [c, H, W] of element el (output: as a view that is written)
+int check_view(PicElem el, int64_t B, int64_t c, int64_t H, int64_t W, const int64_t *strides, int output);
 
 // The set-up of an image call on B pictures [c, H, W].  open(): the arguments and the geometry (coded: the coefficient
 // array's Geom for the list coder too); false ends the call with *st -- an error, or SPIHT_OK for an empty batch, whose
@@ -295,5 +305,28 @@ struct ImgCall {
         return v.at(b0, c, h, w);
     }
 };
+
+// the transform drivers: pictures -> quantised packed array [planes, enc_h, enc_w], and back (levels l_hi .. l_lo: all of them)
+int dwt_forward(spiht_ctx *ctx, const Pic &in, int planes, int c, const ImgGeom &ig, int wavelet, int mode, double q,
+                const double *d_mults, int32_t *d_coeffs, uint32_t *d_maxabs = nullptr);
+int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, const ImgGeom &ig, int wavelet, double q,
+                const double *d_mults, const Pic &out, int l_hi = -1, int l_lo = 1, const double *d_a_in = nullptr,
+                const uint32_t *d_flags = nullptr);
+
+// ---- api_image.cpp: what a host-fed stream queues -- the batched coded calls on a picture, and on a view of element el -----------
+int encode_image_batch(spiht_ctx *ctx, const Pic &in, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                       double q_scale, const double *channel_mults, uint64_t max_bits, uint8_t *d_out, uint64_t slot_stride,
+                       uint64_t *d_nbits, uint8_t *d_max_n, int32_t *d_coeffs);
+int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes, const uint8_t *d_max_n,
+                       int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
+                       const double *channel_mults, const Pic &out, int32_t *d_rec, int reduce = 0);
+int encode_image_batch_view(PicElem el, spiht_ctx *ctx, const void *d_img, const int64_t *strides, int64_t B, int64_t c, int64_t H,
+                            int64_t W, int wavelet, int mode, int level, double q_scale, const double *channel_mults,
+                            uint64_t max_bits, uint8_t *d_out, uint64_t slot_stride, uint64_t *d_nbits, uint8_t *d_max_n,
+                            int32_t *d_coeffs);
+int decode_image_batch_view(PicElem el, spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
+                            const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                            double q_scale, const double *channel_mults, void *d_img_out, const int64_t *out_strides,
+                            int32_t *d_rec);
 
 #pragma GCC visibility pop

@@ -1,6 +1,6 @@
 // Host-fed streams behind the C ABI (include/spiht_hip.h: spiht_hstream_*): batches of host pictures encoded, or batches of
-// host streams decoded, with the transfers overlapped.  The coding is the batched entry point of the stream's element on the
-// caller's context; what is new here is the schedule over three queues -- the copies in, the context's stream, the copies out --
+// host streams decoded, with the transfers overlapped.  The coding is the batched call of api_image.cpp with the stream's element
+// on the caller's context; what is new here is the schedule over three queues -- copies in, the context's stream, copies out --
 // ordered with events, and a ring of slots (hstream_ring.h) whose staging is page-locked on both sides:
 //
 //     copy-in :  U(i+1)                      U(i+2)
@@ -45,7 +45,8 @@ struct HsSlot {
 
 struct spiht_hstream {
     spiht_ctx *ctx = nullptr;
-    int dir = SPIHT_HS_ENCODE, elem = SPIHT_HS_F64, kind = 0, es = 8;
+    int dir = SPIHT_HS_ENCODE;
+    PicElem el = EL_F64;  // the staged pictures' element (el_of_hs of _create's elem)
     int64_t B = 0, c = 0, H = 0, W = 0;
     int wavelet = 0, mode = 0, level = -1;
     double q = 1.0;
@@ -64,7 +65,7 @@ struct spiht_hstream {
     const double *mp() const { return mults.empty() ? nullptr : mults.data(); }
     const int64_t *strides() const { return strided ? st : nullptr; }
     uint64_t span(int64_t n) const {  // bytes from the first sample of n staged pictures to one past the last
-        return (uint64_t)es + (uint64_t)(n - 1) * st[0] + (uint64_t)(c - 1) * st[1] + (uint64_t)(pic_h - 1) * st[2] +
+        return (uint64_t)el_size(el) + (uint64_t)(n - 1) * st[0] + (uint64_t)(c - 1) * st[1] + (uint64_t)(pic_h - 1) * st[2] +
                (uint64_t)(pic_w - 1) * st[3];
     }
     // the parts of a slot's stream staging: packed bytes | lens (uint32 [B]) | max_n (uint8 [B])
@@ -176,48 +177,22 @@ int alloc_slot(spiht_hstream *s, HsSlot &k) {
     return SPIHT_OK;
 }
 
-int check_view(const spiht_hstream *s, const int64_t *strides, int output) {
-    if (s->elem == SPIHT_HS_U8) return spiht_check_view_u8(s->B, s->c, s->H, s->W, strides, output);
-    if (s->elem == SPIHT_HS_U16) return spiht_check_view_u16(s->B, s->c, s->H, s->W, strides, output);
-    return spiht_check_view_flt(s->kind, s->B, s->c, s->H, s->W, strides, output);
-}
-
-// the batched encode of the stream's element: n pictures at d_pic -> slots, bit counts, start planes
+// the batched encode: n pictures at d_pic (float64: a dense array; else a view) -> slots, bit counts, start planes
 int queue_encode(spiht_hstream *s, HsSlot &k) {
-    spiht_ctx *ctx = s->ctx;
-    switch (s->elem) {
-    case SPIHT_HS_F64:
-        return spiht_encode_image_batch_f64(ctx, (const double *)k.d_pic, k.n, s->c, s->H, s->W, s->wavelet, s->mode, s->level, s->q,
-                                            s->mp(), s->max_bits, k.d_slots, s->slot_bytes, k.d_n64, k.d_maxn, nullptr);
-    case SPIHT_HS_U8:
-        return spiht_encode_image_batch_u8(ctx, (const uint8_t *)k.d_pic, s->strides(), k.n, s->c, s->H, s->W, s->wavelet, s->mode,
-                                           s->level, s->q, s->mp(), s->max_bits, k.d_slots, s->slot_bytes, k.d_n64, k.d_maxn, nullptr);
-    case SPIHT_HS_U16:
-        return spiht_encode_image_batch_u16(ctx, (const uint16_t *)k.d_pic, s->strides(), k.n, s->c, s->H, s->W, s->wavelet, s->mode,
-                                            s->level, s->q, s->mp(), s->max_bits, k.d_slots, s->slot_bytes, k.d_n64, k.d_maxn, nullptr);
-    default:
-        return spiht_encode_image_batch_flt(ctx, s->kind, k.d_pic, s->strides(), k.n, s->c, s->H, s->W, s->wavelet, s->mode, s->level,
-                                            s->q, s->mp(), s->max_bits, k.d_slots, s->slot_bytes, k.d_n64, k.d_maxn, nullptr);
-    }
+    if (s->el == EL_F64)
+        return encode_image_batch(s->ctx, dense_pic(k.d_pic, EL_F64), k.n, s->c, s->H, s->W, s->wavelet, s->mode, s->level, s->q,
+                                  s->mp(), s->max_bits, k.d_slots, s->slot_bytes, k.d_n64, k.d_maxn, nullptr);
+    return encode_image_batch_view(s->el, s->ctx, k.d_pic, s->strides(), k.n, s->c, s->H, s->W, s->wavelet, s->mode, s->level, s->q,
+                                   s->mp(), s->max_bits, k.d_slots, s->slot_bytes, k.d_n64, k.d_maxn, nullptr);
 }
 
 // the batched decode of the stream's element: n slots of `stride` bytes -> pictures at d_dst
 int queue_decode(spiht_hstream *s, HsSlot &k, uint64_t stride, void *d_dst) {
-    spiht_ctx *ctx = s->ctx;
-    switch (s->elem) {
-    case SPIHT_HS_F64:
-        return spiht_decode_image_batch_f64(ctx, k.d_slots, stride, k.d_n64, k.d_maxn, k.n, s->c, s->H, s->W, s->wavelet, s->mode,
-                                            s->level, s->q, s->mp(), (double *)d_dst, nullptr);
-    case SPIHT_HS_U8:
-        return spiht_decode_image_batch_u8(ctx, k.d_slots, stride, k.d_n64, k.d_maxn, k.n, s->c, s->H, s->W, s->wavelet, s->mode,
-                                           s->level, s->q, s->mp(), (uint8_t *)d_dst, s->strides(), nullptr);
-    case SPIHT_HS_U16:
-        return spiht_decode_image_batch_u16(ctx, k.d_slots, stride, k.d_n64, k.d_maxn, k.n, s->c, s->H, s->W, s->wavelet, s->mode,
-                                            s->level, s->q, s->mp(), (uint16_t *)d_dst, s->strides(), nullptr);
-    default:
-        return spiht_decode_image_batch_flt(ctx, s->kind, k.d_slots, stride, k.d_n64, k.d_maxn, k.n, s->c, s->H, s->W, s->wavelet,
-                                            s->mode, s->level, s->q, s->mp(), d_dst, s->strides(), nullptr);
-    }
+    if (s->el == EL_F64)
+        return decode_image_batch(s->ctx, k.d_slots, stride, k.d_n64, k.d_maxn, k.n, s->c, s->H, s->W, s->wavelet, s->mode, s->level,
+                                  s->q, s->mp(), dense_pic(d_dst, EL_F64, true), nullptr);
+    return decode_image_batch_view(s->el, s->ctx, k.d_slots, stride, k.d_n64, k.d_maxn, k.n, s->c, s->H, s->W, s->wavelet, s->mode,
+                                   s->level, s->q, s->mp(), d_dst, s->strides(), nullptr);
 }
 
 int submit_encode(spiht_hstream *s, HsSlot &k) {
@@ -290,9 +265,7 @@ extern "C" int spiht_hstream_create(spiht_ctx *ctx, int direction, int elem, int
     spiht_hstream *s = new (std::nothrow) spiht_hstream();
     if (!s) return SPIHT_ERR_NOMEM;
     s->ctx = ctx;
-    s->dir = direction; s->elem = elem;
-    s->kind = elem >= SPIHT_HS_FLT32 ? elem - SPIHT_HS_FLT32 + SPIHT_FLT_F32 : 0;
-    s->es = elem == SPIHT_HS_F64 ? 8 : elem == SPIHT_HS_U8 ? 1 : elem == SPIHT_HS_U16 ? 2 : flt_itemsize(s->kind);
+    s->dir = direction; s->el = el_of_hs(elem);
     s->B = B; s->c = c; s->H = H; s->W = W;
     s->wavelet = wavelet; s->mode = mode; s->level = level; s->q = q_scale;
     if (channel_mults) s->mults.assign(channel_mults, channel_mults + c);
@@ -302,16 +275,16 @@ extern "C" int spiht_hstream_create(spiht_ctx *ctx, int direction, int elem, int
     int st = spiht_geometry_mode(H, W, wavelet, mode, level, nullptr, &ll_h, &ll_w, &enc_h, &enc_w, &rec_H, &rec_W);
     if (st == SPIHT_OK)
         st = spiht_encode_bound(c, enc_h, enc_w, ll_h, ll_w, 0x3FFFFFFFu, max_bits == SPIHT_MAX_BITS_UNLIMITED ? 0 : max_bits, &s->slot_bytes);
-    if (st == SPIHT_OK && elem != SPIHT_HS_F64 && strides) st = check_view(s, strides, direction == SPIHT_HS_DECODE);
+    if (st == SPIHT_OK && s->el != EL_F64 && strides) st = check_view(s->el, B, c, H, W, strides, direction == SPIHT_HS_DECODE);
     if (st != SPIHT_OK) { delete s; return st; }
     s->slot_bytes = std::max<uint64_t>(4, (s->slot_bytes + 3) & ~(uint64_t)3);
     if (s->slot_bytes > ((uint64_t)1 << 29)) { delete s; return SPIHT_ERR_TOO_LARGE; }  // (spiht_tile_pack's limit)
-    const bool rec = direction == SPIHT_HS_DECODE && elem == SPIHT_HS_F64;
+    const bool rec = direction == SPIHT_HS_DECODE && s->el == EL_F64;
     s->pic_h = rec ? rec_H : H;
     s->pic_w = rec ? rec_W : W;
     s->strided = strides != nullptr;
     if (strides) memcpy(s->st, strides, sizeof(s->st));
-    else { s->st[3] = s->es; s->st[2] = s->pic_w * s->st[3]; s->st[1] = s->pic_h * s->st[2]; s->st[0] = c * s->st[1]; }
+    else { s->st[3] = el_size(s->el); s->st[2] = s->pic_w * s->st[3]; s->st[1] = s->pic_h * s->st[2]; s->st[0] = c * s->st[1]; }
     s->pic_bytes = s->span(B);
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     // the two copy streams are the context's: shared by every host-fed stream on it, gone with the last of them
@@ -389,7 +362,8 @@ extern "C" int spiht_hstream_submit(spiht_hstream *s, int64_t n, void *d_dst) {
     if (s->poisoned != SPIHT_OK) return s->poisoned;
     const int i = s->ring.handed_slot();
     if (i < 0) return s->ring.full() ? SPIHT_ERR_BUSY : SPIHT_ERR_ARG;
-    if (n < 1 || n > s->B || (d_dst && s->dir == SPIHT_HS_ENCODE) || (d_dst && (uintptr_t)d_dst % (uintptr_t)s->es)) return SPIHT_ERR_ARG;
+    if (n < 1 || n > s->B || (d_dst && s->dir == SPIHT_HS_ENCODE) || (d_dst && (uintptr_t)d_dst % (uintptr_t)el_size(s->el)))
+        return SPIHT_ERR_ARG;
     HsSlot &k = s->slot[i];
     k.n = n;
     k.bytes_queued = false;

@@ -172,7 +172,7 @@ def in_turn(distinct, B=None):
 
 
 def seam2_sizes(O):
-    """the per-picture element counts the offsets of a chunk are multiples of (api.cpp, api_coder.cpp; each times b0), from the oracle's
+    """the per-picture element counts the offsets of a chunk are multiples of (api_image.cpp, api_coder.cpp; each times b0), from the oracle's
     geometry -> dict"""
     k = SEAM2
     g = O.geometry(k["H"], k["W"], k["wavelet"], k["level"], k["mode"])

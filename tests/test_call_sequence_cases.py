@@ -96,7 +96,7 @@ def _library_sizes(k):
 
 def test_no_two_sizes_of_the_second_seam_case_agree(oracle):
     """SEAM2 exists so that a launch which stepped one of its arrays by another array's size lands on another picture.  The
-    per-picture element counts -- each is the multiplier of b0 somewhere in api.cpp or api_coder.cpp -- are pairwise different, with one
+    per-picture element counts -- each is the multiplier of b0 somewhere in api_image.cpp or api_coder.cpp -- are pairwise different, with one
     exception that no geometry can avoid: the approximation plane of the two-part inverse IS the float64 picture at
     reduce = 1 (2 hs[2] - F + 2 by 2 ws[2] - F + 2, both), so c a_plane and that dense size are one number, and are
     asserted to be.  The integer / float-kind picture at reduce = 1 (hs[1] x ws[1]) stands in the list as well."""

@@ -5,7 +5,7 @@ pictures, level 2, bior2.2, reflect; tiles of 8 x 8 on a 16 x 24 picture, overla
 that hold the operands of these shapes many times over -- and spoils what its name says.  Only arguments the host code refuses
 before it queues anything are spoiled (rules(): which spoil applies to which family), so nothing here ever runs a kernel on a
 bad pointer.  The expected statuses (tests/golden/api_status.json) were recorded by running this table on the GPU at the commit
-before api.cpp was split by topic; rows that returned SPIHT_OK there are not in the table (NOT_REFUSED).
+before the one api.cpp of then was split by topic (today: csrc/api_*.cpp); rows that returned SPIHT_OK there are not in the table (NOT_REFUSED).
 
     python tests/test_gpu_api_status.py record FILE     writes the JSON from the library that is built (GPU)
 """

@@ -1,8 +1,17 @@
 """GPU tests of the host-fed streams (spiht_amd/hoststream.py over include/spiht_hip.h: spiht_hstream_*): every result of a
 stream equals the single-picture call's, field by field and bit for bit; the ring's rules hold on the device as they do in the
 model.  Shapes are the smallest that still reuse slots (7 steps on 2 or 3 slots), end on a short batch (n = 1) and have an odd
-geometry.  No test asserts a time."""
+geometry.  No test asserts a time.
+
+What a stream answers to ONE bad argument at _create or _submit is a table (hs_rules) against tests/golden/hstream_status.json:
+
+    python tests/test_gpu_hoststream.py record FILE     writes the JSON from the library that is loaded (GPU; SPIHT_HIP_LIB)
+"""
+import ctypes as C
 import functools
+import json
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -346,4 +355,157 @@ def test_strided_staging_channels_last(dtype, geom, depth):
     for d, w in zip(on_dev[:2], dec_want[:2]):
         assert np.array_equal(d.view(np.uint8), np.ascontiguousarray(w).view(np.uint8))
     assert np.array_equal(on_dev[2].view(np.uint8), np.full((H, W, C3), 7, dec_want[0].dtype).view(np.uint8))   # not written
+
+
+# ---- what a stream answers to one bad argument ------------------------------------------------------------------------------
+# A row is (call, element, direction, spoil) -> status.  Every row starts from a spiht_hstream_create that passes -- B = 2, depth 2,
+# c = 3, 16 x 16, level 2, bior2.2, reflect -- and spoils what its name says; the _submit rows spoil that call's own arguments on
+# a stream that has handed out a slot.  Nothing spoiled lets work be queued: every row is refused before the first copy.  The
+# expected statuses (tests/golden/hstream_status.json) were recorded by running this table on the GPU against the library of the
+# commit before the stream kept its element as a PicElem; rows that library did not refuse are not in the table (HS_NOT_REFUSED).
+HS_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hstream_status.json")
+HS_ELEMS = {"f64": (0, 8), "u8": (1, 1), "u16": (2, 2), "flt32": (3, 4), "flt16": (4, 2), "bf16": (5, 2)}   # SPIHT_HS_*: id, bytes
+HS_DIRS = {"enc": 0, "dec": 1}
+HS_B, HS_DEPTH, HS_C, HS_H, HS_W, HS_LEVEL = 2, 2, 3, 16, 16, 2
+HS_CREATE = ["elem", "f64_strides", "neg_stride", "odd_stride", "overlap", "c0", "B65536", "wavelet", "mode", "depth_lo", "depth_hi"]
+HS_SUBMIT = ["n0", "n_over", "dst_on_encoder", "dst_misaligned"]
+HS_NOT_REFUSED = set()
+
+
+def hs_spoils(call, elem, d):
+    es, out = HS_ELEMS[elem][1], []
+    for s in (HS_CREATE if call == "create" else HS_SUBMIT):
+        if s == "f64_strides" and elem != "f64":
+            continue  # (dense strides are a valid view of every other element)
+        if s in ("neg_stride", "odd_stride", "overlap") and elem == "f64":
+            continue  # (float64 takes no strides at all: f64_strides)
+        if s == "odd_stride" and es == 1:
+            continue
+        if s == "overlap" and d != "dec":
+            continue  # (an encoder only reads its view)
+        if s == "dst_on_encoder" and d != "enc":
+            continue
+        if s == "dst_misaligned" and (d != "dec" or es == 1):
+            continue  # (a byte is always aligned)
+        out.append(s)
+    return out
+
+
+def hs_row_id(row):
+    return "%s[%s,%s] %s" % row
+
+
+def hs_rules():
+    rows = [(call, e, d, s) for call in ("create", "submit") for e in HS_ELEMS for d in HS_DIRS for s in hs_spoils(call, e, d)]
+    return [r for r in rows if hs_row_id(r) not in HS_NOT_REFUSED]
+
+
+class HsBench:
+    def __init__(self, ctx):
+        from spiht_amd import _lib
+        self.ctx, self.L = ctx, _lib.lib()
+        self.wv, self.md = self.L.spiht_wavelet_id(b"bior2.2"), self.L.spiht_mode_id(b"reflect")
+        self.dst = ctx.alloc(1 << 16)   # a device destination: four times the largest step (float64 [2, 3, 18, 18])
+
+    def close(self):
+        self.ctx.free(self.dst)
+
+    def create(self, elem, d, spoil=None, dense_strides=False):
+        eid, es = HS_ELEMS[elem]
+        a = dict(elem=eid, B=HS_B, depth=HS_DEPTH, c=HS_C, wavelet=self.wv, mode=self.md)
+        st = None
+        if dense_strides or spoil in ("f64_strides", "neg_stride", "odd_stride", "overlap"):
+            st = (C.c_int64 * 4)(HS_C * HS_H * HS_W * es, HS_H * HS_W * es, HS_W * es, es)
+        if spoil == "neg_stride":
+            st[3] = -es
+        elif spoil == "odd_stride":
+            st[2] += 1
+        elif spoil == "overlap":
+            st[2] = es   # rows on top of one another
+        elif spoil and spoil != "f64_strides":
+            key, bad = {"elem": ("elem", 6), "c0": ("c", 0), "B65536": ("B", 65536), "wavelet": ("wavelet", 1000), "mode": ("mode", 9),
+                        "depth_lo": ("depth", 1), "depth_hi": ("depth", 5)}[spoil]
+            a[key] = bad
+        h = C.c_void_p()
+        status = self.L.spiht_hstream_create(self.ctx.handle, HS_DIRS[d], a["elem"], a["B"], a["depth"], a["c"], HS_H, HS_W, a["wavelet"],
+                                             a["mode"], HS_LEVEL, 50.0, None, 16384, C.addressof(st) if st else None, C.byref(h))
+        return int(status), h
+
+    def create_row(self, elem, d, spoil):
+        status, h = self.create(elem, d, spoil)
+        if h.value:   # (not refused: the stream exists)
+            self.L.spiht_hstream_destroy(h)
+        return status
+
+    def submit_rows(self, elem, d, spoils, base):
+        """the statuses of the spoiled submits of one stream; into base: the valid calls around them, and what is queued after"""
+        L, key = self.L, "[%s,%s]" % (elem, d)
+        base["create" + key], h = self.create(elem, d)
+        if base["create" + key] != 0:
+            return {}
+        if d == "dec":   # (no lengths of a stream that were never written, should a row not be refused)
+            ln, mx = C.c_void_p(), C.c_void_p()
+            base["input" + key] = int(L.spiht_hstream_decode_input(h, None, C.byref(ln), C.byref(mx)))
+            C.memset(ln, 0, HS_B * 4)
+            C.memset(mx, 0, HS_B)
+        else:
+            p = C.c_void_p()
+            base["input" + key] = int(L.spiht_hstream_input(h, C.byref(p)))
+        args = {"n0": (0, None), "n_over": (HS_B + 1, None), "dst_on_encoder": (HS_B, self.dst), "dst_misaligned": (HS_B, self.dst + 1)}
+        out = {s: int(L.spiht_hstream_submit(h, *args[s])) for s in spoils}
+        pending = C.c_int(-1)
+        L.spiht_hstream_pending(h, C.byref(pending))
+        base["pending" + key] = pending.value   # nothing was queued
+        base["destroy" + key] = int(L.spiht_hstream_destroy(h))
+        return out
+
+
+def hs_run_table(ctx):
+    b = HsBench(ctx)
+    try:
+        base, got = {}, {}
+        for e in HS_ELEMS:
+            for d in HS_DIRS:
+                if e != "f64":   # the valid view the stride rows are spoiled from
+                    st, h = b.create(e, d, dense_strides=True)
+                    base["create[%s,%s] dense_strides" % (e, d)] = st
+                    if h.value:
+                        b.L.spiht_hstream_destroy(h)
+                sub = b.submit_rows(e, d, [r[3] for r in hs_rules() if r[:3] == ("submit", e, d)], base)
+                got.update({hs_row_id(("submit", e, d, s)): v for s, v in sub.items()})
+        for r in hs_rules():
+            if r[0] == "create":
+                got[hs_row_id(r)] = b.create_row(*r[1:])
+    finally:
+        b.close()
+    return base, got
+
+
+def test_status_of_every_refused_create_and_submit():
+    from spiht_amd import _lib
+    with open(HS_GOLDEN) as fh:  # {"call[element,direction]": {"spoil": status}}, one line per call and stream
+        want = {"%s %s" % (k, sp): v for k, m in json.load(fh).items() for sp, v in m.items()}
+    base, got = hs_run_table(_lib.default_context())
+    assert {k: v for k, v in base.items() if v != 0} == {}, "a valid call was refused, or a refused submit queued a step"
+    assert sorted(got) == sorted(want), "the table and the recorded rows differ"
+    assert all(v != 0 for v in want.values())
+    assert 4 * len(HS_NOT_REFUSED) <= len(HS_NOT_REFUSED) + len(want)   # at most a quarter of the rows is left out
+    diff = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    for k, (g, w) in sorted(diff.items()):
+        print("%s: returned %d, recorded %d" % (k, g, w))
+    assert not diff
+
+
+if __name__ == "__main__" and sys.argv[1:2] == ["record"]:
+    from spiht_amd import _lib as _l
+    base_, got_ = hs_run_table(_l.default_context())
+    print("library:", _l.LIB_PATH)
+    print("valid calls refused / steps queued:", {k: v for k, v in base_.items() if v})
+    print("not refused:", sorted(k for k, v in got_.items() if v == 0))
+    rows_ = {}
+    for k_, v_ in sorted(got_.items()):
+        if v_ != 0:
+            rows_.setdefault(k_.split(" ")[0], {})[k_.split(" ")[1]] = v_
+    with open(sys.argv[2], "w") as fh:
+        fh.write("{\n" + ",\n".join("%s: %s" % (json.dumps(s_), json.dumps(m_, separators=(",", ":"))) for s_, m_ in rows_.items()) + "\n}\n")
 
