@@ -1105,6 +1105,49 @@ int spiht_hstream_next(spiht_hstream *s, int timeout_ms, spiht_hstream_result *o
 /* steps submitted and not yet taken (0 .. depth) */
 int spiht_hstream_pending(spiht_hstream *s, int *steps);
 
+/* ---------------------------------------------------------------------------------------
+ * Picture sets (csrc/tileset.hip): pictures of DIFFERENT sizes as one dense tile batch, and one dense batch of decoded tiles
+ * into many windows of many pictures -- the cut and the paste of the tiled pictures above, for a whole set in one launch.  All
+ * tiles of a set have one shape th x tw, so the tiles of pictures of any sizes share one batch of the batched calls; the
+ * grid of every picture, the order of its tiles and the edge replication are those of spiht_tile_grid and spiht_tile_cut_*.
+ * One call per kernel, by the element's size es = 1, 2, 4 or 8 bytes and not by the pixel type: both are copies.
+ * Additions only: the ABI version stays at 2.
+ * The tables (pics, items) are HOST memory, one plain row per picture (item); every other pointer, those inside the rows
+ * included, is a DEVICE pointer.  The tables are checked completely before anything is queued -- argument errors are returned
+ * before anything is queued --, then copied to device memory of the library's own on the context's stream: the caller may free
+ * or rewrite them as soon as the call returns, and calls queued back to back without a synchronisation each see their own.
+ * The calls are asynchronous on the context's stream like the *_batch_* calls, and no byte outside the stated output is written.
+ *   spiht_tile_cut_set    pics: P >= 1 rows.  Picture p is [c, H, W] at d_img by the byte strides (sc, sh, sw), under the rules
+ *                         of spiht_check_view_* for a view that is read (non-negative multiples of es, the base aligned to es)
+ *                         -> d_tiles: dense [NT, c, th, tw], NT the sum of the pictures' gy * gx; picture p's tiles lie at
+ *                         rows [tile0_p, tile0_p + T_p), tile0_p the sum of the tile counts in front of it, in row-major
+ *                         order.  H, W >= 1, th, tw >= 8 and the limits of spiht_tile_grid; NT < 2^31, c <= 65535.
+ *   spiht_tile_paste_set  items: B >= 1 rows.  d_tiles: dense [S, c, rh, rw], rh >= th, rw >= tw; item b owns the tiles
+ *                         [s0_b, s0_b + (i1-i0) * (j1-j0)), s0_b the sum of the sub-grid sizes in front of it: the sub-grid
+ *                         [i0, i1) x [j0, j1) of its H x W picture in row-major order.  -> d_out of item b: the window
+ *                         [c, wh, ww] of that picture whose first sample is picture sample (y0, x0), by the byte strides
+ *                         (sc, sh, sw) under the rule for a view that is WRITTEN.  Every output sample comes from the one
+ *                         tile that owns it; a tile that does not meet its item's window gives nothing; rows / columns >= th /
+ *                         tw of a tile are never read.  Every window must lie in its picture and every sub-grid must hold the
+ *                         tiles its window meets; S must be the sum of the sub-grid sizes (SPIHT_ERR_ARG); S < 2^31,
+ *                         c <= 65535.  The views of two DIFFERENT items may overlap: which of the two is left is not said. */
+typedef struct spiht_tileset_pic {
+    const void *d_img;      /* device: the picture's first sample */
+    int64_t sc, sh, sw;     /* bytes */
+    int64_t H, W;
+} spiht_tileset_pic;
+typedef struct spiht_tileset_item {
+    void *d_out;            /* device: the window's first sample */
+    int64_t sc, sh, sw;     /* bytes */
+    int64_t H, W;           /* the picture the window lies in */
+    int64_t i0, i1, j0, j1; /* the sub-grid of its tiles in the batch */
+    int64_t y0, x0, wh, ww; /* the window */
+} spiht_tileset_item;
+int spiht_tile_cut_set(spiht_ctx *ctx, int es, int64_t P, int64_t c, int64_t th, int64_t tw, const spiht_tileset_pic *pics,
+                       void *d_tiles);
+int spiht_tile_paste_set(spiht_ctx *ctx, int es, int64_t B, int64_t c, int64_t rh, int64_t rw, int64_t th, int64_t tw,
+                         const spiht_tileset_item *items, const void *d_tiles, int64_t S);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,3 +29,4 @@ from .overlap import window_tiles_overlap  # noqa: E402,F401
 from .hoststream import (StreamEncoder, StreamDecoder, StreamBusy, StreamTimeout, StreamIdle, encode_images,  # noqa: E402,F401
                          encode_images_u8, encode_images_u16, encode_images_float, decode_images, decode_images_u8,
                          decode_images_u16, decode_images_float)
+from .tileset import TileSetCodec, cut_rule, paste_rule, set_tables  # noqa: E402,F401

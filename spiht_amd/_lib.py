@@ -81,6 +81,7 @@ SYMBOLS = [
     "spiht_sse_tiles_flt", "spiht_sse_tiles_w_flt", "spiht_tile_cut_f32s", "spiht_tile_cut_overlap_f32s",
     "spiht_hstream_create", "spiht_hstream_destroy", "spiht_hstream_info", "spiht_hstream_input", "spiht_hstream_decode_input",
     "spiht_hstream_submit", "spiht_hstream_next", "spiht_hstream_pending",
+    "spiht_tile_cut_set", "spiht_tile_paste_set",
 ]
 
 
@@ -88,6 +89,18 @@ class HStreamResult(C.Structure):
     """spiht_hstream_result"""
     _fields_ = [("n", C.c_int64), ("nbytes", C.c_uint64), ("bytes", C.c_void_p), ("lens", C.c_void_p), ("max_n", C.c_void_p),
                 ("pictures", C.c_void_p), ("step", C.c_uint64)]
+
+
+class TileSetPic(C.Structure):
+    """spiht_tileset_pic: one picture of spiht_tile_cut_set"""
+    _fields_ = [("d_img", C.c_void_p), ("sc", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64), ("H", C.c_int64), ("W", C.c_int64)]
+
+
+class TileSetItem(C.Structure):
+    """spiht_tileset_item: one window of spiht_tile_paste_set"""
+    _fields_ = [("d_out", C.c_void_p), ("sc", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64), ("H", C.c_int64), ("W", C.c_int64),
+                ("i0", C.c_int64), ("i1", C.c_int64), ("j0", C.c_int64), ("j1", C.c_int64),
+                ("y0", C.c_int64), ("x0", C.c_int64), ("wh", C.c_int64), ("ww", C.c_int64)]
 
 
 def lib():
@@ -288,6 +301,9 @@ def lib():
         L.spiht_hstream_submit.argtypes = [vp, i64, vp]
         L.spiht_hstream_next.argtypes = [vp, i32, C.POINTER(HStreamResult)]
         L.spiht_hstream_pending.argtypes = [vp, C.POINTER(i32)]
+        # picture sets: the element's size, the rows' count, c, the tile (the decoded tile and the tile), the host table, the batch
+        L.spiht_tile_cut_set.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp]
+        L.spiht_tile_paste_set.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, vp, vp, i64]
         _lib = L
         return _lib
 

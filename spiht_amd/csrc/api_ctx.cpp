@@ -146,9 +146,13 @@ extern "C" void spiht_ctx_destroy(spiht_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->widebuf, &ctx->filt, &ctx->exttmp, &ctx->l1flags, &ctx->x, &ctx->dmsb, &ctx->lmsb, &ctx->maxabs, &ctx->out, &ctx->nbits, &ctx->maxn, &ctx->err,
                       &ctx->lists, &ctx->coeffs, &ctx->a0, &ctx->a1, &ctx->data, &ctx->nbytes, &ctx->rec, &ctx->mults,
                       &ctx->img, &ctx->trace, &ctx->meta, &ctx->recz, &ctx->lspcnt, &ctx->himg, &ctx->hrec, &ctx->tilebuf,
-                      &ctx->pix, &ctx->hpix8, &ctx->rdpart, &ctx->tilescr, &ctx->allocscr, &ctx->layerscr};
+                      &ctx->pix, &ctx->hpix8, &ctx->rdpart, &ctx->tilescr, &ctx->allocscr, &ctx->layerscr, &ctx->tsettab};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
+    for (TableStage &s : ctx->tstages) {
+        if (s.copied) (void)hipEventDestroy(s.copied);
+        if (s.host) (void)hipHostFree(s.host);
+    }
     for (auto &r : ctx->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : ctx->pool) (void)hipEventDestroy(e);
     if (ctx->copy_in) (void)hipStreamDestroy(ctx->copy_in);

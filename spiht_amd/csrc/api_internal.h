@@ -20,6 +20,7 @@
 #include "floatpx.h"
 #include "rd.h"
 #include "tiles.h"
+#include "tileset.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -104,6 +105,8 @@ struct spiht_ctx {
     DevBuf tilescr;             // tiled pictures (tiles.hip): byte lengths and offsets of the streams pack / unpack move
     DevBuf allocscr;            // rate allocation across tiles (alloc.hip): the tiles' hulls
     DevBuf layerscr;            // quality layers (layers.hip): the pieces' offsets in the run, the table's running maximum
+    DevBuf tsettab;             // picture sets (tileset.hip): the tables of the call queued last; the next call's copy is behind its kernel
+    std::vector<TableStage> tstages;  // ... and the page-locked stages the tables are copied from, one per call in flight
     bool recz_clean = false;
     // spiht_decode_lists_batch_i32 -> spiht_unscatter_lists_batch_i32: the launch whose scatter can still be undone
     DecArgs last_dec;

@@ -407,3 +407,141 @@ extern "C" int spiht_layer_unpack(spiht_ctx *ctx, const uint8_t *d_layers, uint6
                                         slot_stride, d_nbytes, ctx->stream));
     return SPIHT_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// picture sets (tileset.hip): pictures of different sizes as one tile batch, one tile batch into many windows
+// ------------------------------------------------------------------------------------------------
+static PicElem el_of_es(int es) {  // a copy moves elements of a size: any element of that size has its rules of a view
+    switch (es) {
+    case 1: return EL_U8;
+    case 2: return EL_U16;
+    case 4: return EL_FLT_F32;
+    case 8: return EL_F64;
+    default: return EL_NONE;
+    }
+}
+static size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+// The tables of one call, `bytes` at h, into ctx->tsettab by a copy on the context's stream.  The copy reads a page-locked stage
+// that belongs to this call until the copy is done (the stage's event): the next call takes another stage, so two calls queued
+// back to back each see their own tables.  The device side needs no such care: the next copy is queued behind this call's
+// kernel.  No wait unless all TS_MAX_STAGES copies are still in flight; called with the context's lock held.
+static int upload_tables(spiht_ctx *ctx, const void *h, size_t bytes) {
+    CHK(ensure(ctx, ctx->tsettab, bytes));
+    int k = -1;
+    for (size_t i = 0; i < ctx->tstages.size() && k < 0; i++) {
+        if (hipEventQuery(ctx->tstages[i].copied) == hipSuccess) k = (int)i;
+        else (void)hipGetLastError();  // (not ready: no error of ours)
+    }
+    if (k < 0 && ctx->tstages.size() < TS_MAX_STAGES) {
+        TableStage s;
+        HIPCHK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+        ctx->tstages.push_back(s);
+        k = (int)ctx->tstages.size() - 1;
+    }
+    if (k < 0) {
+        k = 0;
+        HIPCHK(hipEventSynchronize(ctx->tstages[0].copied));
+    }
+    TableStage &s = ctx->tstages[k];
+    if (s.cap < bytes) {  // (its last copy is done: nothing reads it)
+        if (s.host) HIPCHK(hipHostFree(s.host));
+        s.host = nullptr;
+        s.cap = 0;
+        HIPCHK(hipHostMalloc(&s.host, bytes + bytes / 4 + 4096, hipHostMallocDefault));
+        s.cap = bytes + bytes / 4 + 4096;
+    }
+    memcpy(s.host, h, bytes);
+    HIPCHK(hipMemcpyAsync(ctx->tsettab.p, s.host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipEventRecord(s.copied, ctx->stream));
+    return SPIHT_OK;
+}
+extern "C" int spiht_tile_cut_set(spiht_ctx *ctx, int es, int64_t P, int64_t c, int64_t th, int64_t tw, const spiht_tileset_pic *pics,
+                                  void *d_tiles) {
+    const PicElem el = el_of_es(es);
+    if (!ctx || el == EL_NONE || !pics || !d_tiles || P < 1 || c < 1 || (uintptr_t)d_tiles % es) return SPIHT_ERR_ARG;
+    if (c > 65535 || P > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    // the whole table is checked before anything is queued
+    int64_t NT = 0;
+    for (int64_t p = 0; p < P; p++) {
+        const spiht_tileset_pic &q = pics[p];
+        int64_t gy, gx;
+        if (!q.d_img) return SPIHT_ERR_ARG;
+        CHK(spiht_tile_grid(q.H, q.W, th, tw, &gy, &gx));
+        const int64_t st[3] = {q.sc, q.sh, q.sw};
+        Pic v;
+        CHK(view_pic(&v, q.d_img, el, false, st, 3, 1, c, q.H, q.W));
+        NT += gy * gx;
+        if (NT > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    }
+    const size_t tab = align16((size_t)P * sizeof(TileSetPic)), bytes = tab + align16((size_t)NT * 4);
+    std::vector<char> h(bytes, 0);
+    TileSetPic *rows = (TileSetPic *)h.data();
+    uint32_t *pic_of_tile = (uint32_t *)(h.data() + tab);
+    uint32_t tile0 = 0;
+    for (int64_t p = 0; p < P; p++) {
+        const spiht_tileset_pic &q = pics[p];
+        const int64_t gy = (q.H + th - 1) / th, gx = (q.W + tw - 1) / tw;
+        rows[p] = {(const uint8_t *)q.d_img, q.sc, q.sh, q.sw, (int32_t)q.H, (int32_t)q.W, (int32_t)gx, tile0};
+        std::fill(pic_of_tile + tile0, pic_of_tile + tile0 + gy * gx, (uint32_t)p);
+        tile0 += (uint32_t)(gy * gx);
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(upload_tables(ctx, h.data(), bytes));
+    TileSetCutArgs a;
+    a.pics = (const TileSetPic *)ctx->tsettab.p;
+    a.pic_of_tile = (const uint32_t *)((const char *)ctx->tsettab.p + tab);
+    a.out = (uint8_t *)d_tiles;
+    a.c = (int32_t)c; a.th = (int32_t)th; a.tw = (int32_t)tw; a.rows = 0;
+    LAUNCHCHK(spiht_launch_tile_cut_set(&a, es, NT, ctx->stream));
+    return SPIHT_OK;
+}
+extern "C" int spiht_tile_paste_set(spiht_ctx *ctx, int es, int64_t B, int64_t c, int64_t rh, int64_t rw, int64_t th, int64_t tw,
+                                    const spiht_tileset_item *items, const void *d_tiles, int64_t S) {
+    const PicElem el = el_of_es(es);
+    if (!ctx || el == EL_NONE || !items || !d_tiles || B < 1 || c < 1 || S < 0 || (uintptr_t)d_tiles % es) return SPIHT_ERR_ARG;
+    if (c > 65535 || B > 0x7FFFFFFF || S > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    // the whole table is checked before anything is queued
+    int64_t sum = 0, n = 1, nrows = 1;
+    int strided = 0;
+    for (int64_t b = 0; b < B; b++) {
+        const spiht_tileset_item &q = items[b];
+        int64_t gy, gx;
+        if (!q.d_out) return SPIHT_ERR_ARG;
+        CHK(spiht_tile_grid(q.H, q.W, th, tw, &gy, &gx));
+        if (rh < th || rw < tw || rh > th + (1 << 24) || rw > tw + (1 << 24)) return SPIHT_ERR_ARG;
+        CHK(check_window(c, gy, gx, q.H, q.W, th, tw, 0, q.i0, q.i1, q.j0, q.j1, q.y0, q.x0, q.wh, q.ww));
+        const int64_t st[3] = {q.sc, q.sh, q.sw};
+        Pic v;
+        CHK(window_view(&v, q.d_out, el, st, c, q.wh, q.ww));
+        sum += (q.i1 - q.i0) * (q.j1 - q.j0);
+        if (sum > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+        n = std::max(n, std::min(tw, q.ww));
+        nrows = std::max(nrows, std::min(th, q.wh));
+        strided |= q.sw != es;
+    }
+    if (sum != S) return SPIHT_ERR_ARG;
+    const size_t tab = align16((size_t)B * sizeof(TileSetItem)), bytes = tab + align16((size_t)S * 4);
+    std::vector<char> h(bytes, 0);
+    TileSetItem *rows = (TileSetItem *)h.data();
+    uint32_t *item_of_tile = (uint32_t *)(h.data() + tab);
+    uint32_t s0 = 0;
+    for (int64_t b = 0; b < B; b++) {
+        const spiht_tileset_item &q = items[b];
+        const int64_t cnt = (q.i1 - q.i0) * (q.j1 - q.j0);
+        rows[b] = {(uint8_t *)q.d_out, q.sc, q.sh, q.sw, (int32_t)q.i0, (int32_t)q.j0, (int32_t)(q.j1 - q.j0), s0,
+                   (int32_t)q.y0, (int32_t)q.x0, (int32_t)q.wh, (int32_t)q.ww};
+        std::fill(item_of_tile + s0, item_of_tile + s0 + cnt, (uint32_t)b);
+        s0 += (uint32_t)cnt;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(upload_tables(ctx, h.data(), bytes));
+    TileSetPasteArgs a;
+    a.items = (const TileSetItem *)ctx->tsettab.p;
+    a.item_of_tile = (const uint32_t *)((const char *)ctx->tsettab.p + tab);
+    a.tiles = (const uint8_t *)d_tiles;
+    a.c = (int32_t)c; a.rh = (int32_t)rh; a.rw = (int32_t)rw; a.th = (int32_t)th; a.tw = (int32_t)tw; a.rows = 0;
+    LAUNCHCHK(spiht_launch_tile_paste_set(&a, es, S, n, nrows, strided, ctx->stream));
+    return SPIHT_OK;
+}
