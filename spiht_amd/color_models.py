@@ -156,8 +156,9 @@ def device_convert(ctx, d_ptr, B, npix, src, dest):
     """The same conversion on the GPU as a pass of its own, in place, for B images [B,3,npix] (float64) at device
     pointer d_ptr: one elementwise kernel on the context's stream (spiht_color3_batch_f64).  The codec itself does not
     use it (the change is fused into the transform, `fused`): it is the checker of the fused kernels -- same function,
-    same bits -- and a utility.  Same matrices as above; the power function is the device library's, so results agree
-    with convert() to a few ulp, not bit for bit."""
+    same bits -- and a utility.  Same matrices as above; the power function is csrc/spow.h's (under 4 ulp), so results agree
+    with convert() to a few ulp, not bit for bit -- and bit for bit with the host build of that header inside the same sums
+    (tests/test_gpu_colour.py)."""
     import ctypes as C
     from . import _lib
     if src not in SUPPORTED_MODELS:

@@ -286,9 +286,12 @@ __device__ __forceinline__ void spow_lds_fill(SpowLds &t, int tid) {  // needs a
 }
 
 // One pixel of the colour model change.  Shared by the stand-alone kernel (k_color3) and the fused level-1 kernels, and
-// every unit that includes this is compiled without multiply-add contraction: the three produce the same bits.  (The CPU checker,
-// oracle/color_oracle.c, is an arithmetic of its own with the C library's pow(): the device is held to it within a
-// tolerance, tests/test_gpu_image.py.)  numpy's dot order.
+// every unit that includes this is compiled without multiply-add contraction: the three produce the same bits.  Every operation
+// here and in spow.h is a correctly rounded IEEE one in a fixed order, so the device gives, bit for bit, what the same header
+// gives on the host inside the same sums: tests/test_gpu_colour.py holds k_color3 to that (tests/colour_cases.py: color3_rule),
+// and tests/test_colour_cases.py holds the host build to 60-digit arithmetic.  (The CPU checker, oracle/color_oracle.c, is an
+// arithmetic of its own with the C library's pow(): the device is held to it within a tolerance besides,
+// tests/test_gpu_image.py.)  numpy's dot order.
 __device__ __forceinline__ void color3_px(const Color3 &c, const SpowLds &t, double u0, double u1, double u2, double &w0,
                                           double &w1, double &w2) {
     double v[3];

@@ -1,5 +1,8 @@
 // x^p for x > 0 in float64, for the colour kernels (dwt_device.h).  (The CPU checker oracle/color_oracle.c does not include this
-// file: it uses the C library's pow(); tests/native/spow_probe.c measures this function against 60-digit arithmetic.)
+// file: it uses the C library's pow().)  Every operation below is a correctly rounded IEEE one in a fixed order -- add, multiply,
+// fma, rint, ldexp, integer work -- so, built without multiply-add contraction, the host and the device give the same bits:
+// tests/native/spow_probe.c is this file built for the host, tests/test_colour_cases.py measures that build against 60-digit
+// arithmetic, and tests/test_gpu_colour.py holds the device kernel to it in every bit, subnormal inputs and results included.
 //
 // The colour model change (RGB <-> IPT: spiht/color_models.py:6-13 -> colour-science) takes three signed powers per
 // pixel and is arithmetic-bound: the device library's pow() costs about 250 float64 instruction slots (it carries the
@@ -8,8 +11,10 @@
 //            r = m / c_i - 1 by ONE fma with the tabulated reciprocal (|r| <= 2^-7), degree-8 Taylor polynomial;
 //   2^y    = 2^q 2^(j/64) e^u,  y = (64 q + j) / 64 + t,  u = t ln 2 (|u| <= 0.0055), degree-6 Taylor polynomial.
 // Error: under 4 units in the last place whatever the magnitudes (the integer part of p log2 x is handled exactly;
-// checked against 60-digit arithmetic in tests/test_oracle.py); numpy's pow, which colour-science calls, stays under 1.  The reference's own arithmetic for this step cannot be
-// consulted (colour-science is not installable here): colour parity is unpinned with any power function.
+// checked against 60-digit arithmetic in tests/test_oracle.py and tests/test_colour_cases.py -- measured worst 1.14 ulp for
+// p = 0.43, 3.18 for p = 1 / 0.43, half an ulp of the subnormal spacing on subnormal results); numpy's pow, which
+// colour-science calls, stays under 1.  The reference's own arithmetic for this step cannot be consulted (colour-science is
+// not installable here): colour parity is unpinned with any power function.
 #ifndef SPIHT_SPOW_H
 #define SPIHT_SPOW_H
 #include <stdint.h>

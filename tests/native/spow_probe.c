@@ -11,3 +11,7 @@
 #include "../../spiht_amd/csrc/spow_tables.h"
 #include "../../spiht_amd/csrc/spow.h"
 double probe_spow(double x, double p) { return spow_signed(x, p, SPOW_INV, SPOW_LOG2C, SPOW_EXP2); }
+/* the same over an array (tests/colour_cases.py: the host restatement the device kernel is held to, bit for bit) */
+void probe_spow_n(const double *x, double p, double *out, long n) {
+    for (long k = 0; k < n; k++) out[k] = spow_signed(x[k], p, SPOW_INV, SPOW_LOG2C, SPOW_EXP2);
+}
