@@ -1,7 +1,9 @@
 """Every tiled transform kernel of spiht_amd/csrc/dwt_fwd.hip and dwt_inv.hip against the plain loops of oracle/dwt_oracle.c, over the product the
 launchers dispatch on: filter length x zero-tap mask x pixel kind x kernel family x extension mode, at picture sizes that
 put the tile seams of each kernel where they can go wrong (tests/dwt_sweep_tables.py; tests/test_dwt_sweep_tables.py holds
-that grid to its purpose without a GPU).  Through the C ABI; every comparison is equality of bits."""
+that grid to its purpose without a GPU).  Through the C ABI; every comparison is equality of bits.  The max|coefficient| word
+(maxabs_of) is compared in every forward case, but these pictures keep their largest coefficient in the root block:
+tests/test_gpu_maxabs.py moves it through the bands, overhang cells, tiles and threads."""
 import ctypes as C
 
 import numpy as np
