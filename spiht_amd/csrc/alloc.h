@@ -1,5 +1,5 @@
 // Rate allocation across tiles (alloc.hip, roi.hip): how the launchers cut the work, shared with api.cpp, which checks the
-// arguments and sizes the context's buffers from it, and what the error-sum kernels of both files share.
+// arguments and sizes the context's buffers from it.  The device code of the error sums is sse_tiles.h.
 #pragma once
 #include "common.h"
 
@@ -31,11 +31,6 @@ __device__ __forceinline__ void valid_extent(const TileSseArgs &a, uint32_t t, i
     vh = min(a.th, a.H - i * a.th);
     vw = min(a.tw, a.W - j * a.tw);
 }
-
-// two float64 at an address that is only 8-byte aligned: which samples a lane adds must not depend on where the tile lies
-struct __attribute__((aligned(8))) F64x2 {
-    double a, b;
-};
 
 // spiht_tile_allocate's scratch, per tile: K + 1 hull vertices (float64 distortion, uint32 length), K edge slopes, a count
 static inline size_t al_scratch_bytes(uint64_t NT, uint64_t K) { return (size_t)(NT * ((K + 1) * 12 + K * 8 + 4)); }

@@ -8,9 +8,8 @@
 //   k_tile_allocate_target  the same hulls, the steepest common slope at which the picture's error is at or below a target
 // The rule is spiht_amd/alloc.py; the allocation equals it bit for bit.  Compiled with -ffp-contract=off: a term is
 // (p - d) * (p - d) rounded, then added; a slope is one rounded subtraction and one rounded division.  No atomics.
-#include "alloc.h"
+#include "sse_tiles.h"
 #include "copy_bytes.h"
-#include "floatpx.h"
 
 // ---- prefix slots ----------------------------------------------------------------------------------------------------------
 
@@ -34,123 +33,18 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_prefix_slots(const uint8_t 
 
 // ---- per-tile error sums -----------------------------------------------------------------------------------------------------
 
-// grid (G * NT, chunks, c).  The partition is a function of (th, vh, vw) alone: a workgroup takes AL_TILE_ROWS rows of one
-// channel, wavefront wv the rows wv, wv + 4, ... of them, lane l the columns 2 l, 2 l + 1, then 128 further on; a lane adds
-// its terms in that order, the wavefront by the __shfl_down tree, thread 0 the four wavefronts in order.
+// grid (G * NT, chunks, c), one body (sse_tiles.h, where the partition and the order of additions are stated).  _flt: the
+// ORIGINAL tiles are bit patterns of a float kind, each widened exactly on the load, so the sums are k_sse_tiles_f64's bits on
+// the widened tiles.  _px: a term is at most 65535^2 < 2^32; any order is exact.
 __global__ __launch_bounds__(AL_THREADS) void k_sse_tiles_f64(const TileSseArgs a) {
-    const uint32_t s = blockIdx.x, chunk = blockIdx.y, ch = blockIdx.z, tid = threadIdx.x;
-    const uint32_t t = s % a.NT;
-    int vh, vw;
-    valid_extent(a, t, vh, vw);
-    if ((int)chunk * AL_TILE_ROWS >= vh) return;
-    const int wv = tid >> 6, lane = tid & 63;
-    const double *p = (const double *)a.tiles + ((size_t)t * a.c + ch) * (size_t)a.th * a.tw;
-    const double *d = (const double *)a.dec + ((size_t)s * a.c + ch) * (size_t)a.rh * a.rw;
-    double acc = 0.0;
-    for (int r = wv; r < AL_TILE_ROWS; r += AL_THREADS / 64) {
-        const int y = (int)chunk * AL_TILE_ROWS + r;
-        if (y >= vh) break;
-        const double *pr = p + (size_t)y * a.tw, *dr = d + (size_t)y * a.rw;
-#pragma unroll 4
-        for (int x = 2 * lane; x < vw; x += 128) {
-            if (x + 1 < vw) {
-                const F64x2 pv = *reinterpret_cast<const F64x2 *>(pr + x), dv = *reinterpret_cast<const F64x2 *>(dr + x);
-                const double t0 = pv.a - dv.a, t1 = pv.b - dv.b;
-                acc += t0 * t0;
-                acc += t1 * t1;
-            } else {
-                const double t0 = pr[x] - dr[x];
-                acc += t0 * t0;
-            }
-        }
-    }
-    for (int off = 32; off; off >>= 1) acc += __shfl_down(acc, off);
-    __shared__ double sh[AL_THREADS / 64];
-    if (lane == 0) sh[wv] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        for (int i = 1; i < AL_THREADS / 64; i++) acc += sh[i];
-        ((double *)a.part)[((size_t)s * a.c + ch) * a.chunks + chunk] = acc;
-    }
+    sse_tiles_body<SSE_F64, double, false>(a, nullptr, 0);
 }
-
-// Float pixels in: the ORIGINAL tiles are float32 (T = uint32_t) or float16 / bfloat16 (T = uint16_t) bit patterns of kind
-// `kind` (uniform over the launch), each widened exactly on the load (floatpx.h); the decodes are float64.  The partition, the
-// pairing of columns and the order of additions are k_sse_tiles_f64's, so the sums are its bits on the widened tiles.  A tile
-// row is only element-aligned (tw may be odd): the pair of the original is two loads of one element; the decode keeps the
-// paired load of the float64 kernel.
 template <typename T>
 __global__ __launch_bounds__(AL_THREADS) void k_sse_tiles_flt(const TileSseArgs a, int kind) {
-    const uint32_t s = blockIdx.x, chunk = blockIdx.y, ch = blockIdx.z, tid = threadIdx.x;
-    const uint32_t t = s % a.NT;
-    int vh, vw;
-    valid_extent(a, t, vh, vw);
-    if ((int)chunk * AL_TILE_ROWS >= vh) return;
-    const int wv = tid >> 6, lane = tid & 63;
-    const T *p = (const T *)a.tiles + ((size_t)t * a.c + ch) * (size_t)a.th * a.tw;
-    const double *d = (const double *)a.dec + ((size_t)s * a.c + ch) * (size_t)a.rh * a.rw;
-    double acc = 0.0;
-    for (int r = wv; r < AL_TILE_ROWS; r += AL_THREADS / 64) {
-        const int y = (int)chunk * AL_TILE_ROWS + r;
-        if (y >= vh) break;
-        const T *pr = p + (size_t)y * a.tw;
-        const double *dr = d + (size_t)y * a.rw;
-#pragma unroll 4
-        for (int x = 2 * lane; x < vw; x += 128) {
-            if (x + 1 < vw) {
-                const uint32_t r0 = pr[x], r1 = pr[x + 1];
-                const F64x2 dv = *reinterpret_cast<const F64x2 *>(dr + x);
-                const double t0 = flt_load_value(r0, kind) - dv.a, t1 = flt_load_value(r1, kind) - dv.b;
-                acc += t0 * t0;
-                acc += t1 * t1;
-            } else {
-                const double t0 = flt_load_value(pr[x], kind) - dr[x];
-                acc += t0 * t0;
-            }
-        }
-    }
-    for (int off = 32; off; off >>= 1) acc += __shfl_down(acc, off);
-    __shared__ double sh[AL_THREADS / 64];
-    if (lane == 0) sh[wv] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        for (int i = 1; i < AL_THREADS / 64; i++) acc += sh[i];
-        ((double *)a.part)[((size_t)s * a.c + ch) * a.chunks + chunk] = acc;
-    }
+    sse_tiles_body<SSE_FLT, T, false>(a, nullptr, kind);
 }
-
-// the same partition of rows; lane l the columns l, l + 64, ...  A term is at most 65535^2 < 2^32; any order is exact.
 template <typename T>
-__global__ __launch_bounds__(AL_THREADS) void k_sse_tiles_px(const TileSseArgs a) {
-    const uint32_t s = blockIdx.x, chunk = blockIdx.y, ch = blockIdx.z, tid = threadIdx.x;
-    const uint32_t t = s % a.NT;
-    int vh, vw;
-    valid_extent(a, t, vh, vw);
-    if ((int)chunk * AL_TILE_ROWS >= vh) return;
-    const int wv = tid >> 6, lane = tid & 63;
-    const T *p = (const T *)a.tiles + ((size_t)t * a.c + ch) * (size_t)a.th * a.tw;
-    const T *d = (const T *)a.dec + ((size_t)s * a.c + ch) * (size_t)a.rh * a.rw;
-    uint64_t acc = 0;
-    for (int r = wv; r < AL_TILE_ROWS; r += AL_THREADS / 64) {
-        const int y = (int)chunk * AL_TILE_ROWS + r;
-        if (y >= vh) break;
-        const T *pr = p + (size_t)y * a.tw, *dr = d + (size_t)y * a.rw;
-#pragma unroll 4
-        for (int x = lane; x < vw; x += 64) {
-            const int32_t e = (int32_t)pr[x] - (int32_t)dr[x];
-            const uint32_t u = (uint32_t)(e < 0 ? -e : e);
-            acc += (uint64_t)(u * u);
-        }
-    }
-    for (int off = 32; off; off >>= 1) acc += __shfl_down(acc, off);
-    __shared__ uint64_t sh[AL_THREADS / 64];
-    if (lane == 0) sh[wv] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        for (int i = 1; i < AL_THREADS / 64; i++) acc += sh[i];
-        ((uint64_t *)a.part)[((size_t)s * a.c + ch) * a.chunks + chunk] = acc;
-    }
-}
+__global__ __launch_bounds__(AL_THREADS) void k_sse_tiles_px(const TileSseArgs a) { sse_tiles_body<SSE_PX, T, false>(a, nullptr, 0); }
 
 // part [G * NT, c, chunks] -> out [G * NT]: one thread per sum; the channels in order, of each the chunks that hold valid rows
 // in order (the others were not written)
@@ -410,8 +304,7 @@ __global__ __launch_bounds__(AL_THREADS) void k_tile_allocate_target(const uint6
 extern "C" int spiht_launch_tile_prefix_slots(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbits, int64_t NT, int K,
                                               int k0, int G, uint8_t *d_out, uint64_t out_stride, uint64_t *d_nbytes,
                                               const uint8_t *d_max_n, uint8_t *d_max_n_out, hipStream_t st) {
-    const uint32_t chunks = (uint32_t)((out_stride + 15 + TL_CHUNK - 1) / TL_CHUNK);
-    hipLaunchKernelGGL(k_tile_prefix_slots, dim3((uint32_t)(G * NT), chunks), dim3(TL_THREADS), 0, st, d_slots, slot_stride, d_nbits,
+    hipLaunchKernelGGL(k_tile_prefix_slots, dim3((uint32_t)(G * NT), slot_chunks(out_stride)), dim3(TL_THREADS), 0, st, d_slots, slot_stride, d_nbits,
                        (uint32_t)NT, (uint32_t)K, (uint32_t)k0, d_out, out_stride, d_nbytes, d_max_n, d_max_n_out);
     return (int)hipGetLastError();
 }

@@ -8,7 +8,7 @@
 //   k_layer_unpack  the run -> zero-padded slots: the pieces of layers < upto of a tile one behind the other, zeros behind
 // Both copies are copy_bytes per piece (copy_bytes.h): chunks cut at 16-byte-aligned destination addresses, the ragged ends
 // byte by byte, so neighbouring pieces write disjoint bytes.  Plain vector and byte stores; no atomics.
-#include "tiles.h"
+#include "tiles_device.h"
 #include "copy_bytes.h"
 
 // grid over the N * T tiles, one thread each.  bits [Q][NT] -> cum [N][Q][T]
@@ -43,30 +43,15 @@ __device__ __forceinline__ uint32_t piece_len(const uint32_t *__restrict__ B, ui
 }
 
 // B [P][Q][T] -> off [P * Q * T]: the sum of the pieces before e in file order.  One workgroup: 256 pieces per round, a carry
-// between rounds (k_tile_scan's scheme).
+// between rounds (tiles_device.h: block_scan_exclusive, as k_tile_scan).
 __global__ __launch_bounds__(TL_THREADS) void k_layer_scan(const uint32_t *__restrict__ B, uint32_t n, uint32_t Q, uint32_t T,
                                                            uint64_t *__restrict__ off) {
     __shared__ uint64_t wsum[TL_THREADS / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     uint64_t carry = 0;
     for (uint32_t base = 0; base < n; base += TL_THREADS) {
-        const uint32_t idx = base + tid;
-        uint64_t v = 0;
-        if (idx < n) v = piece_len(B, idx, Q, T);
-        uint64_t x = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = __shfl_up(x, o);
-            if ((int)lane >= o) x += y;
-        }
-        if (lane == 63) wsum[wv] = x;
-        __syncthreads();
-        uint64_t pre = 0, total = 0;
-        for (uint32_t k = 0; k < TL_THREADS / 64; k++) {
-            if (k < wv) pre += wsum[k];
-            total += wsum[k];
-        }
-        if (idx < n) off[idx] = carry + pre + x - v;
-        carry += total;
+        const uint32_t idx = base + threadIdx.x;
+        const uint64_t before = block_scan_exclusive(idx < n ? piece_len(B, idx, Q, T) : 0, carry, wsum);
+        if (idx < n) off[idx] = before;
         __syncthreads();
     }
 }
@@ -117,8 +102,6 @@ __global__ __launch_bounds__(TL_THREADS) void k_layer_unpack(const uint8_t *__re
 }
 
 // ---- host launchers ------------------------------------------------------------------------------------------------------
-
-static uint32_t slot_chunks(uint64_t slot_stride) { return (uint32_t)((slot_stride + 15 + TL_CHUNK - 1) / TL_CHUNK); }
 
 // d_off: uint64 [N * Q * T] (scratch)
 extern "C" int spiht_launch_layer_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_cum_bits, int64_t Q, int64_t N,

@@ -8,9 +8,9 @@
 //                       operation rounded once (this file is built with -ffp-contract=off) and the division IEEE's;
 //                       elsewhere the one tile's sample.  Output float64, or 8 / 16 bits by the decoder's conversion.
 // Workgroups own rows of the window, as k_tile_mosaic's do: whether a row lies in a zone, its two tile rows and their weights
-// are the same for all lanes of the row; only the column zone is per lane.  Stores follow tiles.hip: 16 bytes at a 16-byte-
-// aligned address wherever the destination is contiguous, element by element in front of the first and behind the last.
-#include "tiles.h"
+// are the same for all lanes of the row; only the column zone is per lane.  Both kernels store their rows by store_row
+// (tiles_device.h).
+#include "tiles_device.h"
 #include "floatpx.h"
 
 // ---- cut ---------------------------------------------------------------------------------------------------------------------
@@ -20,34 +20,13 @@
 template <int ES>
 __device__ __forceinline__ void cut_row(uint8_t *dst, const uint8_t *src, int64_t ss, int n, int X0, int W, int lane, int nlanes) {
     typedef typename ElemOf<ES>::type T;
-    constexpr int EPV = 16 / ES;
-    auto at = [&](int k) { return src + (int64_t)min(max(X0 + k, 0), W - 1) * ss; };
-    const int a = (int)((uintptr_t)dst & 15), nbytes = n * ES;
-    const int nvec = (a + nbytes + 15) >> 4;
-    for (int v = lane; v < nvec; v += nlanes) {
-        const int p = 16 * v - a;  // bytes from dst; a multiple of ES, negative in the first vector of an unaligned row
-        const int k0 = p / ES;
-        if (p >= 0 && p + 16 <= nbytes) {
-            const int X = X0 + k0;
-            const uint8_t *s = src + (int64_t)X * ss;  // (formed, not read, where X is clamped)
-            uint4 q;
-            if (ss == ES && X >= 0 && X + EPV <= W && ((uintptr_t)s & 15) == 0) {
-                q = *reinterpret_cast<const uint4 *>(s);
-            } else {
-                T e[EPV];
-#pragma unroll
-                for (int i = 0; i < EPV; i++) e[i] = *reinterpret_cast<const T *>(at(k0 + i));
-                __builtin_memcpy(&q, e, 16);
-            }
-            *reinterpret_cast<uint4 *>(dst + p) = q;
-        } else {
-#pragma unroll
-            for (int i = 0; i < EPV; i++) {
-                const int k = k0 + i;
-                if (k >= 0 && k < n) *reinterpret_cast<T *>(dst + (int64_t)k * ES) = *reinterpret_cast<const T *>(at(k));
-            }
-        }
-    }
+    auto elem = [&](int k) { return *reinterpret_cast<const T *>(src + (int64_t)min(max(X0 + k, 0), W - 1) * ss); };
+    store_row<ES, int>(dst, ES, n, lane, nlanes, elem, [&](int k0) {
+        const int X = X0 + k0;
+        const uint8_t *s = src + (int64_t)X * ss;  // (formed, not read, where X is clamped)
+        if (ss == ES && X >= 0 && X + 16 / ES <= W && ((uintptr_t)s & 15) == 0) return *reinterpret_cast<const Vec16 *>(s);
+        return gather_vec<ES>(k0, elem);
+    });
 }
 
 // grid (N * T, c, row chunks); block (bx, by): bx lanes along a row, by rows at a time
@@ -89,7 +68,6 @@ template <int ES, int FK = 0> __device__ __forceinline__ typename ElemOf<ES>::ty
 template <int ES, int FK = 0>
 __global__ __launch_bounds__(TL_THREADS) void k_tile_blend(const TileBlendArgs a) {
     typedef typename ElemOf<ES>::type T;
-    constexpr int EPV = 16 / ES;
     const uint32_t ch = blockIdx.y;
     const int m = a.m, lane = (int)threadIdx.x, nlanes = (int)blockDim.x;
     const size_t plane = (size_t)a.rh * a.rw;
@@ -123,77 +101,38 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_blend(const TileBlendArgs a
             if (zy) r = (by * r + ay * hval(bot, X)) / fm;
             return blend_store_value<ES, FK>(r);
         };
-        uint8_t *dst = a.out + (int64_t)ch * a.sc + (int64_t)y * a.sh;
-        const int n = a.ww;
-        if (a.sw != ES) {  // a strided destination (HWC, RGBA): what lies between the elements is not written
-            for (int k = lane; k < n; k += nlanes) *reinterpret_cast<T *>(dst + (int64_t)k * a.sw) = val(a.x0 + k);
-            continue;
-        }
-        const int al = (int)((uintptr_t)dst & 15);
-        const int64_t nbytes = (int64_t)n * ES;
-        const int nvec = (int)((al + nbytes + 15) >> 4);
-        for (int v = lane; v < nvec; v += nlanes) {
-            const int64_t p = 16 * (int64_t)v - al;  // bytes from dst; negative in the first vector of an unaligned row
-            const int k0 = (int)(p / ES);
-            if (p >= 0 && p + 16 <= nbytes) {
-                T e[EPV];
-#pragma unroll
-                for (int i = 0; i < EPV; i++) e[i] = val(a.x0 + k0 + i);
-                uint4 q;
-                __builtin_memcpy(&q, e, 16);
-                *reinterpret_cast<uint4 *>(dst + p) = q;
-            } else {
-#pragma unroll
-                for (int i = 0; i < EPV; i++) {
-                    const int k = k0 + i;
-                    if (k >= 0 && k < n) *reinterpret_cast<T *>(dst + (int64_t)k * ES) = val(a.x0 + k);
-                }
-            }
-        }
+        auto elem = [&](int k) { return val(a.x0 + k); };
+        store_row<ES, int64_t>(a.out + (int64_t)ch * a.sc + (int64_t)y * a.sh, a.sw, a.ww, lane, nlanes, elem,
+                      [&](int k0) { return gather_vec<ES>(k0, elem); });
     }
 }
 
 // ---- host launchers ----------------------------------------------------------------------------------------------------------
-template <int ES>
-static int launch_cut_overlap(TileCutOverlapArgs a, int64_t NT, hipStream_t st) {
-    dim3 block;
-    uint32_t gz;
-    const int64_t cw = (int64_t)a.cut.tw + 2 * a.m, chh = (int64_t)a.cut.th + 2 * a.m;
-    row_blocks((cw * ES + 15) / 16 + 1, cw * ES, chh, &block, &a.cut.rows, &gz);
-    hipLaunchKernelGGL(k_tile_cut_overlap<ES>, dim3((uint32_t)NT, a.cut.c, gz), block, 0, st, a);
-    return (int)hipGetLastError();
-}
-extern "C" int spiht_launch_tile_cut_overlap(const TileCutOverlapArgs *a, int es, int64_t NT, hipStream_t st) {
-    switch (es) {
-    case 1: return launch_cut_overlap<1>(*a, NT, st);
-    case 2: return launch_cut_overlap<2>(*a, NT, st);
-    case 4: return launch_cut_overlap<4>(*a, NT, st);
-    default: return launch_cut_overlap<8>(*a, NT, st);
-    }
+extern "C" int spiht_launch_tile_cut_overlap(const TileCutOverlapArgs *p, int es, int64_t NT, hipStream_t st) {
+    return dispatch_es(es, [&](auto e) {
+        constexpr int ES = decltype(e)::value;
+        TileCutOverlapArgs a = *p;
+        dim3 block;
+        uint32_t gz;
+        const int64_t cw = (int64_t)a.cut.tw + 2 * a.m, chh = (int64_t)a.cut.th + 2 * a.m;
+        row_blocks((cw * ES + 15) / 16 + 1, cw * ES, chh, &block, &a.cut.rows, &gz);
+        hipLaunchKernelGGL(k_tile_cut_overlap<ES>, dim3((uint32_t)NT, a.cut.c, gz), block, 0, st, a);
+        return (int)hipGetLastError();
+    });
 }
 
 template <int ES, int FK = 0>
 static int launch_blend(TileBlendArgs a, hipStream_t st) {
     dim3 block;
     uint32_t gz;
-    const int64_t n = a.ww;  // a workgroup's rows are the window's
-    row_blocks(a.sw == ES ? (n * ES + 15) / 16 + 1 : n, n * ES, a.wh, &block, &a.rows, &gz);
-    // a small window: fewer rows per workgroup, down to one pass of the block, until there are workgroups for every CU a few
-    // times over (as the mosaic)
-    while ((int64_t)gz * a.c < TL_MOSAIC_WGS && a.rows > (int)block.y) {
-        a.rows = std::max<int>((int)block.y, a.rows / 2 / (int)block.y * (int)block.y);
-        gz = (uint32_t)((a.wh + a.rows - 1) / a.rows);
-    }
+    window_blocks(a.sw == ES, a.ww, ES, a.wh, a.c, &block, &a.rows, &gz);  // a workgroup's rows are the window's
     hipLaunchKernelGGL((k_tile_blend<ES, FK>), dim3(gz, a.c), block, 0, st, a);
     return (int)hipGetLastError();
 }
 // es: bytes per sample of the OUTPUT: 8 float64, 1 / 2 the 8- / 16-bit conversion
 extern "C" int spiht_launch_tile_blend(const TileBlendArgs *a, int es, hipStream_t st) {
-    switch (es) {
-    case 1: return launch_blend<1>(*a, st);
-    case 2: return launch_blend<2>(*a, st);
-    default: return launch_blend<8>(*a, st);
-    }
+    // (4-byte samples are a float kind: spiht_launch_tile_blend_flt)
+    return dispatch_es(es, [&](auto e) { return launch_blend<decltype(e)::value == 4 ? 8 : decltype(e)::value>(*a, st); });
 }
 // ... into a float kind (floatpx.h)
 extern "C" int spiht_launch_tile_blend_flt(const TileBlendArgs *a, int kind, hipStream_t st) {

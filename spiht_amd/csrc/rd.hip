@@ -7,6 +7,7 @@
 // No atomics: the integer sums do not need them and the float64 sum must not depend on arrival order.
 // Compiled with -ffp-contract=off: a float64 term is (P - D) * (P - D) rounded, then added -- never a fused multiply-add.
 #include "rd.h"
+#include "sse_tiles.h"
 
 struct U128 {
     uint64_t lo, hi;
@@ -20,10 +21,6 @@ __device__ __forceinline__ void sq_i32(U128 &a, int32_t x, int32_t y) {
     const int64_t d = (int64_t)x - (int64_t)y;
     const uint64_t u = (uint64_t)(d < 0 ? -d : d);
     add128(a, u * u, 0);
-}
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-    for (int off = 32; off; off >>= 1) v += __shfl_down(v, off);
-    return v;
 }
 
 // a 16-byte load from an address that is only 4-byte aligned (X, when the planes of X and Y are not congruent modulo 16)
@@ -101,19 +98,14 @@ __global__ __launch_bounds__(64) void k_sum_u64(const uint64_t *__restrict__ par
     const uint64_t *p = part + (size_t)blockIdx.x * per;
     uint64_t a = 0;
     for (uint32_t i = threadIdx.x; i < per; i += 64) a += p[i];
-    a = wave_sum_u64(a);
+    a = wave_sum(a);
     if (threadIdx.x == 0) out[blockIdx.x] = a;
 }
 
-// two float64 at an address that is only 8-byte aligned: which samples a lane adds must not depend on where the picture lies
-struct __attribute__((aligned(8))) F64x2 {
-    double a, b;
-};
-
 // P [c, H, W], D [K, c, rec_h, rec_w] (the window is D[..., :H, :W]) -> part [K, c, tiles].  The partition is a function of
-// (H, W) alone: a workgroup takes RD_TILE_ROWS rows, wavefront wv the rows wv, wv + 4, ... of them, lane l the columns
-// 2 l, 2 l + 1, then 128 further on; a lane adds its terms in that order, the wavefront by the __shfl_down tree, thread 0
-// the four wavefronts in order.  So S[k, ch] is the same bits whatever K is and wherever picture k lies.
+// (H, W) alone and the order of additions is the per-tile sums' (sse_tiles.h: a workgroup takes RD_TILE_ROWS rows), so
+// S[k, ch] is the same bits whatever K is and wherever picture k lies.
+static_assert(RD_TILE_ROWS == AL_TILE_ROWS && RD_THREADS == AL_THREADS, "sse_lane_sum cuts the rows by alloc.h's constants");
 __global__ __launch_bounds__(RD_THREADS) void k_sse_f64(const double *__restrict__ P, const double *__restrict__ D, int32_t H,
                                                         int32_t W, int32_t rec_h, int32_t rec_w, uint32_t c, uint32_t tiles,
                                                         double *__restrict__ part) {
@@ -121,32 +113,9 @@ __global__ __launch_bounds__(RD_THREADS) void k_sse_f64(const double *__restrict
     const int wv = tid >> 6, lane = tid & 63;
     const double *p = P + (size_t)ch * H * W;
     const double *d = D + ((size_t)k * c + ch) * rec_h * rec_w;
-    double acc = 0.0;
-    for (int r = wv; r < RD_TILE_ROWS; r += RD_THREADS / 64) {
-        const int y = (int)tile * RD_TILE_ROWS + r;
-        if (y >= H) break;
-        const double *pr = p + (size_t)y * W, *dr = d + (size_t)y * rec_w;
-#pragma unroll 4
-        for (int x = 2 * lane; x < W; x += 128) {
-            if (x + 1 < W) {
-                const F64x2 pv = *reinterpret_cast<const F64x2 *>(pr + x), dv = *reinterpret_cast<const F64x2 *>(dr + x);
-                const double t0 = pv.a - dv.a, t1 = pv.b - dv.b;
-                acc += t0 * t0;
-                acc += t1 * t1;
-            } else {
-                const double t0 = pr[x] - dr[x];
-                acc += t0 * t0;
-            }
-        }
-    }
-    for (int off = 32; off; off >>= 1) acc += __shfl_down(acc, off);
-    __shared__ double sh[RD_THREADS / 64];
-    if (lane == 0) sh[wv] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        for (int i = 1; i < RD_THREADS / 64; i++) acc += sh[i];
-        part[((size_t)k * c + ch) * tiles + tile] = acc;
-    }
+    const double mine = sse_lane_sum<SSE_F64, double, false>(p, W, d, rec_w, nullptr, 0, tile, H, W, 0, wv, lane);
+    const double acc = block_sum_ordered<double, RD_THREADS>(mine, tid, wv, lane);
+    if (tid == 0) part[((size_t)k * c + ch) * tiles + tile] = acc;
 }
 // part [n, tiles] -> out [n]: one thread per sum, the partials in index order
 __global__ __launch_bounds__(64) void k_sum_f64(const double *__restrict__ part, uint32_t n, uint32_t tiles, double *__restrict__ out) {
@@ -211,14 +180,8 @@ __global__ __launch_bounds__(RD_THREADS) void k_sse_px(const PxView px, const T 
             }
         }
     }
-    a = wave_sum_u64(a);
-    __shared__ uint64_t sh[RD_THREADS / 64];
-    if ((tid & 63) == 0) sh[tid >> 6] = a;
-    __syncthreads();
-    if (tid == 0) {
-        for (int i = 1; i < RD_THREADS / 64; i++) a += sh[i];
-        part[((size_t)k * c + ch) * tiles + tile] = a;
-    }
+    a = block_sum_ordered<uint64_t, RD_THREADS>(a, tid, tid >> 6, tid & 63);
+    if (tid == 0) part[((size_t)k * c + ch) * tiles + tile] = a;
 }
 
 // ---- host launchers: `part` holds K * c * tiles partials (rd.h: rd_tiles) of 16, 8 and 8 bytes -------------------------

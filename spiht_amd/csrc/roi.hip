@@ -8,106 +8,20 @@
 // by byte: a row of the map starts at any address (W may be odd), and it is 1/8 .. 1/16 of the bytes a lane reads anyway.
 // The partials go to the context's buffer and are added by alloc.hip's second launch.  Compiled with -ffp-contract=off: the
 // subtraction, the square and the product with the weight are each rounded once.  No atomics.
-#include "alloc.h"
-#include "floatpx.h"
+#include "sse_tiles.h"
 
-// the map's first byte for tile t: picture t / T (or the one map), row i th, column j tw
-__device__ __forceinline__ const uint8_t *map_of(const TileSseWArgs &q, uint32_t t) {
-    const uint32_t n = t / q.a.T, tl = t - n * q.a.T;
-    const uint32_t i = tl / (uint32_t)q.a.gx, j = tl - i * (uint32_t)q.a.gx;
-    return q.w + (size_t)n * q.w_stride + (size_t)i * q.a.th * q.a.W + (size_t)j * q.a.tw;
-}
-
-// grid (G * NT, chunks, c): the partition and the order of additions of k_sse_tiles_f64.  A map of ones gives its bits.
+// grid (G * NT, chunks, c): alloc.hip's kernels with q.w, one body (sse_tiles.h).  A map of ones gives their bits.
 __global__ __launch_bounds__(AL_THREADS) void k_sse_tiles_w_f64(const TileSseWArgs q) {
-    const TileSseArgs &a = q.a;
-    const uint32_t s = blockIdx.x, chunk = blockIdx.y, ch = blockIdx.z, tid = threadIdx.x;
-    const uint32_t t = s % a.NT;
-    int vh, vw;
-    valid_extent(a, t, vh, vw);
-    if ((int)chunk * AL_TILE_ROWS >= vh) return;
-    const int wv = tid >> 6, lane = tid & 63;
-    const double *p = (const double *)a.tiles + ((size_t)t * a.c + ch) * (size_t)a.th * a.tw;
-    const double *d = (const double *)a.dec + ((size_t)s * a.c + ch) * (size_t)a.rh * a.rw;
-    const uint8_t *w = map_of(q, t);
-    double acc = 0.0;
-    for (int r = wv; r < AL_TILE_ROWS; r += AL_THREADS / 64) {
-        const int y = (int)chunk * AL_TILE_ROWS + r;
-        if (y >= vh) break;
-        const double *pr = p + (size_t)y * a.tw, *dr = d + (size_t)y * a.rw;
-        const uint8_t *wr = w + (size_t)y * a.W;
-#pragma unroll 4
-        for (int x = 2 * lane; x < vw; x += 128) {
-            if (x + 1 < vw) {
-                const F64x2 pv = *reinterpret_cast<const F64x2 *>(pr + x), dv = *reinterpret_cast<const F64x2 *>(dr + x);
-                const double w0 = (double)wr[x], w1 = (double)wr[x + 1];
-                const double t0 = pv.a - dv.a, t1 = pv.b - dv.b;
-                acc += w0 * (t0 * t0);
-                acc += w1 * (t1 * t1);
-            } else {
-                const double t0 = pr[x] - dr[x];
-                acc += (double)wr[x] * (t0 * t0);
-            }
-        }
-    }
-    for (int off = 32; off; off >>= 1) acc += __shfl_down(acc, off);
-    __shared__ double sh[AL_THREADS / 64];
-    if (lane == 0) sh[wv] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        for (int i = 1; i < AL_THREADS / 64; i++) acc += sh[i];
-        ((double *)a.part)[((size_t)s * a.c + ch) * a.chunks + chunk] = acc;
-    }
+    sse_tiles_body<SSE_F64, double, true>(q.a, &q, 0);
 }
-
-// Float pixels in: the weighted form of alloc.hip's k_sse_tiles_flt -- original tiles of float32 (T = uint32_t) or float16 /
-// bfloat16 (T = uint16_t) bit patterns of kind `kind`, widened exactly on the load; the partition and the order of additions
-// of k_sse_tiles_w_f64, so its bits on the widened tiles.  A map of ones gives the bits of k_sse_tiles_flt.
 template <typename T>
 __global__ __launch_bounds__(AL_THREADS) void k_sse_tiles_w_flt(const TileSseWArgs q, int kind) {
-    const TileSseArgs &a = q.a;
-    const uint32_t s = blockIdx.x, chunk = blockIdx.y, ch = blockIdx.z, tid = threadIdx.x;
-    const uint32_t t = s % a.NT;
-    int vh, vw;
-    valid_extent(a, t, vh, vw);
-    if ((int)chunk * AL_TILE_ROWS >= vh) return;
-    const int wv = tid >> 6, lane = tid & 63;
-    const T *p = (const T *)a.tiles + ((size_t)t * a.c + ch) * (size_t)a.th * a.tw;
-    const double *d = (const double *)a.dec + ((size_t)s * a.c + ch) * (size_t)a.rh * a.rw;
-    const uint8_t *w = map_of(q, t);
-    double acc = 0.0;
-    for (int r = wv; r < AL_TILE_ROWS; r += AL_THREADS / 64) {
-        const int y = (int)chunk * AL_TILE_ROWS + r;
-        if (y >= vh) break;
-        const T *pr = p + (size_t)y * a.tw;
-        const double *dr = d + (size_t)y * a.rw;
-        const uint8_t *wr = w + (size_t)y * a.W;
-#pragma unroll 4
-        for (int x = 2 * lane; x < vw; x += 128) {
-            if (x + 1 < vw) {
-                const uint32_t r0 = pr[x], r1 = pr[x + 1];
-                const F64x2 dv = *reinterpret_cast<const F64x2 *>(dr + x);
-                const double w0 = (double)wr[x], w1 = (double)wr[x + 1];
-                const double t0 = flt_load_value(r0, kind) - dv.a, t1 = flt_load_value(r1, kind) - dv.b;
-                acc += w0 * (t0 * t0);
-                acc += w1 * (t1 * t1);
-            } else {
-                const double t0 = flt_load_value(pr[x], kind) - dr[x];
-                acc += (double)wr[x] * (t0 * t0);
-            }
-        }
-    }
-    for (int off = 32; off; off >>= 1) acc += __shfl_down(acc, off);
-    __shared__ double sh[AL_THREADS / 64];
-    if (lane == 0) sh[wv] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        for (int i = 1; i < AL_THREADS / 64; i++) acc += sh[i];
-        ((double *)a.part)[((size_t)s * a.c + ch) * a.chunks + chunk] = acc;
-    }
+    sse_tiles_body<SSE_FLT, T, true>(q.a, &q, kind);
 }
 
-// the partition of k_sse_tiles_px.  A term is at most 255 * 65535^2 < 2^40, a tile has at most 2^24 of them: exact in any order.
+// The partition of k_sse_tiles_px.  A term is at most 255 * 65535^2 < 2^40, a tile has at most 2^24 of them: exact in any order.
+// Written out, not a call of the body: on the body the 8-bit sum of one measured shape lay above the spread of this text's own
+// runs (profiles/tile_kernels_fold.txt).
 template <typename T>
 __global__ __launch_bounds__(AL_THREADS) void k_sse_tiles_w_px(const TileSseWArgs q) {
     const TileSseArgs &a = q.a;

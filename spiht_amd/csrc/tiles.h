@@ -1,9 +1,10 @@
 // Tiled pictures (tiles.hip, overlap.hip): the arguments of the copy kernels and of the blend, shared with api.cpp, which checks
-// them, and what the kernels' files share.
+// them, and what the launchers of the kernels' files share (their device code: tiles_device.h).
 #pragma once
 #include "common.h"
 
 #include <algorithm>
+#include <type_traits>
 
 #define TL_THREADS 256
 #define TL_CHUNK 16384        // pack / unpack: bytes of one stream a workgroup moves (four 16-byte stores per lane)
@@ -76,6 +77,32 @@ static inline void row_blocks(int64_t units, int64_t row_bytes, int64_t rows, di
     *block = dim3(bx, by);
     *rows_per_wg = (int)per;
     *gz = (uint32_t)std::max<int64_t>(1, (rows + per - 1) / per);
+}
+
+// ... for workgroups that own rows of a window [c, rows, n] of es-byte elements (mosaic, blend); dense: the elements of a row
+// are contiguous.  A small (reduced) window: fewer rows per workgroup, down to one pass of the block, until there are
+// workgroups for every CU a few times over.
+static inline void window_blocks(bool dense, int64_t n, int es, int64_t rows, int c, dim3 *block, int *rows_per_wg, uint32_t *gz) {
+    row_blocks(dense ? (n * es + 15) / 16 + 1 : n, n * es, rows, block, rows_per_wg, gz);
+    const int by = (int)block->y;
+    while ((int64_t)*gz * c < TL_MOSAIC_WGS && *rows_per_wg > by) {
+        *rows_per_wg = std::max<int>(by, *rows_per_wg / 2 / by * by);
+        *gz = (uint32_t)((rows + *rows_per_wg - 1) / *rows_per_wg);
+    }
+}
+
+// pack / unpack and their kin: the grid's chunks of a slot (a chunk may start up to 15 bytes into it)
+static inline uint32_t slot_chunks(uint64_t slot_stride) { return (uint32_t)((slot_stride + 15 + TL_CHUNK - 1) / TL_CHUNK); }
+
+// The element-size dispatch of every copy launcher: f(std::integral_constant<int, ES>()) for es = 1, 2, 4; anything else is 8.
+template <typename F>
+static inline int dispatch_es(int es, F f) {
+    switch (es) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, 8>());
+    }
 }
 
 // the launchers of tiles.hip, layers.hip and overlap.hip (called from api.cpp)

@@ -12,48 +12,8 @@
 // stream) goes element by element (byte by byte).  The source side: cut / paste load 16 bytes where the source address is
 // aligned as well and element by element where it is not; pack / unpack, whose two sides are never aligned to one another,
 // load the aligned 32-bit words around the bytes and shift them into place.
-#include "tiles.h"
+#include "tiles_device.h"
 #include "copy_bytes.h"
-
-// One row: n elements of ES bytes, element k from src + min(k, nvalid - 1) * ss (replication past nvalid) to dst + k * ds.
-// The lanes lane, lane + nlanes, ... of the caller share the row.  dst, src and the strides are multiples of ES.
-template <int ES>
-__device__ __forceinline__ void copy_row(uint8_t *dst, int64_t ds, const uint8_t *src, int64_t ss, int n, int nvalid, int lane,
-                                         int nlanes) {
-    typedef typename ElemOf<ES>::type T;
-    constexpr int EPV = 16 / ES;
-    if (ds != ES) {  // a strided destination (HWC, RGBA): what lies between the elements is not written
-        for (int k = lane; k < n; k += nlanes)
-            *reinterpret_cast<T *>(dst + (int64_t)k * ds) = *reinterpret_cast<const T *>(src + (int64_t)min(k, nvalid - 1) * ss);
-        return;
-    }
-    const int a = (int)((uintptr_t)dst & 15), nbytes = n * ES;
-    const int nvec = (a + nbytes + 15) >> 4;
-    for (int v = lane; v < nvec; v += nlanes) {
-        const int p = 16 * v - a;  // bytes from dst; a multiple of ES, negative in the first vector of an unaligned row
-        const int k0 = p / ES;
-        if (p >= 0 && p + 16 <= nbytes) {
-            const uint8_t *s = src + (int64_t)k0 * ss;
-            uint4 q;
-            if (ss == ES && k0 + EPV <= nvalid && ((uintptr_t)s & 15) == 0) {
-                q = *reinterpret_cast<const uint4 *>(s);
-            } else {
-                T e[EPV];
-#pragma unroll
-                for (int i = 0; i < EPV; i++) e[i] = *reinterpret_cast<const T *>(src + (int64_t)min(k0 + i, nvalid - 1) * ss);
-                __builtin_memcpy(&q, e, 16);
-            }
-            *reinterpret_cast<uint4 *>(dst + p) = q;
-        } else {
-#pragma unroll
-            for (int i = 0; i < EPV; i++) {
-                const int k = k0 + i;
-                if (k >= 0 && k < n)
-                    *reinterpret_cast<T *>(dst + (int64_t)k * ES) = *reinterpret_cast<const T *>(src + (int64_t)min(k, nvalid - 1) * ss);
-            }
-        }
-    }
-}
 
 // grid (N * T, c, row chunks); block (bx, by): bx lanes along a row, by rows at a time
 template <int ES>
@@ -100,49 +60,25 @@ __device__ __forceinline__ void mosaic_row(uint8_t *dst, int64_t ds, const uint8
                                            int n, int lane, int nlanes) {
     typedef typename ElemOf<ES>::type T;
     constexpr int EPV = 16 / ES;
-    auto src = [&](int X) {  // picture column X >= 0
-        const uint32_t j = (uint32_t)X / tw, tx = (uint32_t)X - j * tw;
-        return row + (int64_t)((int)j - j0) * tstep + (size_t)tx * ES;
+    auto elem = [&](int k) {
+        const uint32_t X = (uint32_t)(x0 + k), j = X / tw, tx = X - j * tw;  // picture column X >= 0
+        return *reinterpret_cast<const T *>(row + (int64_t)((int)j - j0) * tstep + (size_t)tx * ES);
     };
-    if (ds != ES) {  // a strided destination (HWC, RGBA): what lies between the elements is not written
-        for (int k = lane; k < n; k += nlanes) *reinterpret_cast<T *>(dst + (int64_t)k * ds) = *reinterpret_cast<const T *>(src(x0 + k));
-        return;
-    }
-    const int a = (int)((uintptr_t)dst & 15);
-    const int64_t nbytes = (int64_t)n * ES;
-    const int nvec = (int)((a + nbytes + 15) >> 4);
-    for (int v = lane; v < nvec; v += nlanes) {
-        const int64_t p = 16 * (int64_t)v - a;  // bytes from dst; a multiple of ES, negative in the first vector of an unaligned row
-        const int k0 = (int)(p / ES);
-        if (p >= 0 && p + 16 <= nbytes) {
-            const uint32_t X = (uint32_t)(x0 + k0), j = X / tw;
-            uint32_t tx = X - j * tw;
-            const uint8_t *s = row + (int64_t)((int)j - j0) * tstep + (size_t)tx * ES;
-            uint4 q;
-            if (tx + EPV <= tw && ((uintptr_t)s & 15) == 0) {
-                q = *reinterpret_cast<const uint4 *>(s);
-            } else {
-                T e[EPV];
-#pragma unroll
-                for (int i = 0; i < EPV; i++) {
-                    e[i] = *reinterpret_cast<const T *>(s);
-                    s += ES;
-                    if (++tx == tw) {  // the seam: the same row of the next tile
-                        tx = 0;
-                        s += tstep - (int64_t)tw * ES;
-                    }
-                }
-                __builtin_memcpy(&q, e, 16);
+    store_row<ES, int64_t>(dst, ds, n, lane, nlanes, elem, [&](int k0) {
+        const uint32_t X = (uint32_t)(x0 + k0), j = X / tw;
+        uint32_t tx = X - j * tw;
+        const uint8_t *s = row + (int64_t)((int)j - j0) * tstep + (size_t)tx * ES;
+        if (tx + EPV <= tw && ((uintptr_t)s & 15) == 0) return *reinterpret_cast<const Vec16 *>(s);
+        return gather_vec<ES>(0, [&](int) {
+            const T e = *reinterpret_cast<const T *>(s);
+            s += ES;
+            if (++tx == tw) {  // the seam: the same row of the next tile
+                tx = 0;
+                s += tstep - (int64_t)tw * ES;
             }
-            *reinterpret_cast<uint4 *>(dst + p) = q;
-        } else {
-#pragma unroll
-            for (int i = 0; i < EPV; i++) {
-                const int k = k0 + i;
-                if (k >= 0 && k < n) *reinterpret_cast<T *>(dst + (int64_t)k * ES) = *reinterpret_cast<const T *>(src(x0 + k));
-            }
-        }
-    }
+            return e;
+        });
+    });
 }
 
 // grid (row chunks of the window, c); block (bx, by): bx lanes along a window row, by rows at a time.  Picture-centric: a
@@ -168,29 +104,15 @@ template <typename TIN, typename TOUT>
 __global__ __launch_bounds__(TL_THREADS) void k_tile_scan(const TIN *__restrict__ in, uint32_t T, uint64_t lim,
                                                           uint64_t *__restrict__ off, TOUT *__restrict__ out) {
     __shared__ uint64_t wsum[TL_THREADS / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     uint64_t carry = 0;
     for (uint32_t base = 0; base < T; base += TL_THREADS) {
-        const uint32_t idx = base + tid;
-        uint64_t v = 0;
-        if (idx < T) v = min((uint64_t)in[idx], lim);
-        uint64_t x = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = __shfl_up(x, o);
-            if ((int)lane >= o) x += y;
-        }
-        if (lane == 63) wsum[wv] = x;
-        __syncthreads();
-        uint64_t pre = 0, total = 0;
-        for (uint32_t k = 0; k < TL_THREADS / 64; k++) {
-            if (k < wv) pre += wsum[k];
-            total += wsum[k];
-        }
+        const uint32_t idx = base + threadIdx.x;
+        const uint64_t v = idx < T ? min((uint64_t)in[idx], lim) : 0;
+        const uint64_t before = block_scan_exclusive(v, carry, wsum);
         if (idx < T) {
-            off[idx] = carry + pre + x - v;
+            off[idx] = before;
             out[idx] = (TOUT)v;
         }
-        carry += total;
         __syncthreads();
     }
 }
@@ -221,66 +143,42 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_unpack(const uint8_t *__res
 
 // ---- host launchers ------------------------------------------------------------------------------------------------------
 
-template <int ES>
-static int launch_cut(TileCutArgs a, int64_t NT, hipStream_t st) {
-    dim3 block;
-    uint32_t gz;
-    row_blocks(((int64_t)a.tw * ES + 15) / 16 + 1, (int64_t)a.tw * ES, a.th, &block, &a.rows, &gz);
-    hipLaunchKernelGGL(k_tile_cut<ES>, dim3((uint32_t)NT, a.c, gz), block, 0, st, a);
-    return (int)hipGetLastError();
-}
-extern "C" int spiht_launch_tile_cut(const TileCutArgs *a, int es, int64_t NT, hipStream_t st) {
-    switch (es) {
-    case 1: return launch_cut<1>(*a, NT, st);
-    case 2: return launch_cut<2>(*a, NT, st);
-    case 4: return launch_cut<4>(*a, NT, st);
-    default: return launch_cut<8>(*a, NT, st);
-    }
+extern "C" int spiht_launch_tile_cut(const TileCutArgs *p, int es, int64_t NT, hipStream_t st) {
+    return dispatch_es(es, [&](auto e) {
+        constexpr int ES = decltype(e)::value;
+        TileCutArgs a = *p;
+        dim3 block;
+        uint32_t gz;
+        row_blocks(((int64_t)a.tw * ES + 15) / 16 + 1, (int64_t)a.tw * ES, a.th, &block, &a.rows, &gz);
+        hipLaunchKernelGGL(k_tile_cut<ES>, dim3((uint32_t)NT, a.c, gz), block, 0, st, a);
+        return (int)hipGetLastError();
+    });
 }
 
-template <int ES>
-static int launch_paste(TilePasteArgs a, int64_t ntiles, hipStream_t st) {
-    dim3 block;
-    uint32_t gz;
-    const int64_t n = std::min<int64_t>(a.tw, a.ww);  // the longest row piece a tile gives
-    row_blocks(a.sw == ES ? (n * ES + 15) / 16 + 1 : n, n * ES, std::min<int64_t>(a.th, a.wh), &block, &a.rows, &gz);
-    hipLaunchKernelGGL(k_tile_paste<ES>, dim3((uint32_t)ntiles, a.c, gz), block, 0, st, a);
-    return (int)hipGetLastError();
-}
-extern "C" int spiht_launch_tile_paste(const TilePasteArgs *a, int es, int64_t ntiles, hipStream_t st) {
-    switch (es) {
-    case 1: return launch_paste<1>(*a, ntiles, st);
-    case 2: return launch_paste<2>(*a, ntiles, st);
-    case 4: return launch_paste<4>(*a, ntiles, st);
-    default: return launch_paste<8>(*a, ntiles, st);
-    }
+extern "C" int spiht_launch_tile_paste(const TilePasteArgs *p, int es, int64_t ntiles, hipStream_t st) {
+    return dispatch_es(es, [&](auto e) {
+        constexpr int ES = decltype(e)::value;
+        TilePasteArgs a = *p;
+        dim3 block;
+        uint32_t gz;
+        const int64_t n = std::min<int64_t>(a.tw, a.ww);  // the longest row piece a tile gives
+        row_blocks(a.sw == ES ? (n * ES + 15) / 16 + 1 : n, n * ES, std::min<int64_t>(a.th, a.wh), &block, &a.rows, &gz);
+        hipLaunchKernelGGL(k_tile_paste<ES>, dim3((uint32_t)ntiles, a.c, gz), block, 0, st, a);
+        return (int)hipGetLastError();
+    });
 }
 
-template <int ES>
-static int launch_mosaic(TileMosaicArgs a, hipStream_t st) {
-    dim3 block;
-    uint32_t gz;
-    const int64_t n = a.ww;  // a workgroup's rows are the window's
-    row_blocks(a.sw == ES ? (n * ES + 15) / 16 + 1 : n, n * ES, a.wh, &block, &a.rows, &gz);
-    // a small (reduced) picture: fewer rows per workgroup, down to one pass of the block, until there are workgroups for
-    // every CU a few times over
-    while ((int64_t)gz * a.c < TL_MOSAIC_WGS && a.rows > (int)block.y) {
-        a.rows = std::max<int>((int)block.y, a.rows / 2 / (int)block.y * (int)block.y);
-        gz = (uint32_t)((a.wh + a.rows - 1) / a.rows);
-    }
-    hipLaunchKernelGGL(k_tile_mosaic<ES>, dim3(gz, a.c), block, 0, st, a);
-    return (int)hipGetLastError();
+extern "C" int spiht_launch_tile_mosaic(const TileMosaicArgs *p, int es, hipStream_t st) {
+    return dispatch_es(es, [&](auto e) {
+        constexpr int ES = decltype(e)::value;
+        TileMosaicArgs a = *p;
+        dim3 block;
+        uint32_t gz;
+        window_blocks(a.sw == ES, a.ww, ES, a.wh, a.c, &block, &a.rows, &gz);  // a workgroup's rows are the window's
+        hipLaunchKernelGGL(k_tile_mosaic<ES>, dim3(gz, a.c), block, 0, st, a);
+        return (int)hipGetLastError();
+    });
 }
-extern "C" int spiht_launch_tile_mosaic(const TileMosaicArgs *a, int es, hipStream_t st) {
-    switch (es) {
-    case 1: return launch_mosaic<1>(*a, st);
-    case 2: return launch_mosaic<2>(*a, st);
-    case 4: return launch_mosaic<4>(*a, st);
-    default: return launch_mosaic<8>(*a, st);
-    }
-}
-
-static uint32_t slot_chunks(uint64_t slot_stride) { return (uint32_t)((slot_stride + 15 + TL_CHUNK - 1) / TL_CHUNK); }
 
 // d_nbytes [T] (scratch: the streams' byte lengths) -> d_off [T] (scratch), d_lens [T]; then the gather
 extern "C" int spiht_launch_tile_pack(const uint8_t *d_slots, uint64_t slot_stride, const uint64_t *d_nbytes, int64_t T,

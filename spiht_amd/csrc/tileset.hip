@@ -8,50 +8,9 @@
 // picture's (item's) row.  Both addresses depend on blockIdx alone, so both reads are scalar loads -- one dependent pair in
 // front of the rows -- and nothing but the tiles (the windows) is written.  A table of the tile's picture costs 4 bytes a tile
 // and one load; the search over tile0 it replaces would be log2(P) dependent loads in every workgroup.
-// copy_row is tiles.hip's, restated: tiles.o stays built from what it was built from.
+// The rows are copied by tiles.hip's copy_row (tiles_device.h).
 #include "tileset.h"
-
-// One row: n elements of ES bytes, element k from src + min(k, nvalid - 1) * ss (replication past nvalid) to dst + k * ds.
-// The lanes lane, lane + nlanes, ... of the caller share the row.  dst, src and the strides are multiples of ES.  A lane
-// stores 16 bytes at a 16-byte-aligned address wherever the destination is contiguous, element by element in front of the
-// first and behind the last such address; it loads 16 bytes where the source is contiguous and aligned as well.
-template <int ES>
-__device__ __forceinline__ void copy_row(uint8_t *dst, int64_t ds, const uint8_t *src, int64_t ss, int n, int nvalid, int lane,
-                                         int nlanes) {
-    typedef typename ElemOf<ES>::type T;
-    constexpr int EPV = 16 / ES;
-    if (ds != ES) {  // a strided destination (HWC, RGBA): what lies between the elements is not written
-        for (int k = lane; k < n; k += nlanes)
-            *reinterpret_cast<T *>(dst + (int64_t)k * ds) = *reinterpret_cast<const T *>(src + (int64_t)min(k, nvalid - 1) * ss);
-        return;
-    }
-    const int a = (int)((uintptr_t)dst & 15), nbytes = n * ES;
-    const int nvec = (a + nbytes + 15) >> 4;
-    for (int v = lane; v < nvec; v += nlanes) {
-        const int p = 16 * v - a;  // bytes from dst; a multiple of ES, negative in the first vector of an unaligned row
-        const int k0 = p / ES;
-        if (p >= 0 && p + 16 <= nbytes) {
-            const uint8_t *s = src + (int64_t)k0 * ss;
-            uint4 q;
-            if (ss == ES && k0 + EPV <= nvalid && ((uintptr_t)s & 15) == 0) {
-                q = *reinterpret_cast<const uint4 *>(s);
-            } else {
-                T e[EPV];
-#pragma unroll
-                for (int i = 0; i < EPV; i++) e[i] = *reinterpret_cast<const T *>(src + (int64_t)min(k0 + i, nvalid - 1) * ss);
-                __builtin_memcpy(&q, e, 16);
-            }
-            *reinterpret_cast<uint4 *>(dst + p) = q;
-        } else {
-#pragma unroll
-            for (int i = 0; i < EPV; i++) {
-                const int k = k0 + i;
-                if (k >= 0 && k < n)
-                    *reinterpret_cast<T *>(dst + (int64_t)k * ES) = *reinterpret_cast<const T *>(src + (int64_t)min(k, nvalid - 1) * ss);
-            }
-        }
-    }
-}
+#include "tiles_device.h"
 
 // grid (NT, c, row chunks); block (bx, by): bx lanes along a row, by rows at a time
 template <int ES>
@@ -92,37 +51,27 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_paste_set(const TileSetPast
 
 // ---- host launchers ------------------------------------------------------------------------------------------------------
 
-template <int ES>
-static int launch_cut_set(TileSetCutArgs a, int64_t NT, hipStream_t st) {
-    dim3 block;
-    uint32_t gz;
-    row_blocks(((int64_t)a.tw * ES + 15) / 16 + 1, (int64_t)a.tw * ES, a.th, &block, &a.rows, &gz);
-    hipLaunchKernelGGL(k_tile_cut_set<ES>, dim3((uint32_t)NT, a.c, gz), block, 0, st, a);
-    return (int)hipGetLastError();
-}
-extern "C" int spiht_launch_tile_cut_set(const TileSetCutArgs *a, int es, int64_t NT, hipStream_t st) {
-    switch (es) {
-    case 1: return launch_cut_set<1>(*a, NT, st);
-    case 2: return launch_cut_set<2>(*a, NT, st);
-    case 4: return launch_cut_set<4>(*a, NT, st);
-    default: return launch_cut_set<8>(*a, NT, st);
-    }
+extern "C" int spiht_launch_tile_cut_set(const TileSetCutArgs *p, int es, int64_t NT, hipStream_t st) {
+    return dispatch_es(es, [&](auto e) {
+        constexpr int ES = decltype(e)::value;
+        TileSetCutArgs a = *p;
+        dim3 block;
+        uint32_t gz;
+        row_blocks(((int64_t)a.tw * ES + 15) / 16 + 1, (int64_t)a.tw * ES, a.th, &block, &a.rows, &gz);
+        hipLaunchKernelGGL(k_tile_cut_set<ES>, dim3((uint32_t)NT, a.c, gz), block, 0, st, a);
+        return (int)hipGetLastError();
+    });
 }
 
-template <int ES>
-static int launch_paste_set(TileSetPasteArgs a, int64_t S, int64_t n, int64_t rows, int strided, hipStream_t st) {
-    dim3 block;
-    uint32_t gz;
-    row_blocks(strided ? n : (n * ES + 15) / 16 + 1, n * ES, rows, &block, &a.rows, &gz);
-    hipLaunchKernelGGL(k_tile_paste_set<ES>, dim3((uint32_t)S, a.c, gz), block, 0, st, a);
-    return (int)hipGetLastError();
-}
-extern "C" int spiht_launch_tile_paste_set(const TileSetPasteArgs *a, int es, int64_t S, int64_t n, int64_t rows, int strided,
+extern "C" int spiht_launch_tile_paste_set(const TileSetPasteArgs *p, int es, int64_t S, int64_t n, int64_t rows, int strided,
                                            hipStream_t st) {
-    switch (es) {
-    case 1: return launch_paste_set<1>(*a, S, n, rows, strided, st);
-    case 2: return launch_paste_set<2>(*a, S, n, rows, strided, st);
-    case 4: return launch_paste_set<4>(*a, S, n, rows, strided, st);
-    default: return launch_paste_set<8>(*a, S, n, rows, strided, st);
-    }
+    return dispatch_es(es, [&](auto e) {
+        constexpr int ES = decltype(e)::value;
+        TileSetPasteArgs a = *p;
+        dim3 block;
+        uint32_t gz;
+        row_blocks(strided ? n : (n * ES + 15) / 16 + 1, n * ES, rows, &block, &a.rows, &gz);
+        hipLaunchKernelGGL(k_tile_paste_set<ES>, dim3((uint32_t)S, a.c, gz), block, 0, st, a);
+        return (int)hipGetLastError();
+    });
 }
