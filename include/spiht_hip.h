@@ -346,6 +346,17 @@ int spiht_l1_flags_words(int64_t c, int64_t H, int64_t W, int wavelet, int mode,
 int spiht_decode_lists_flags_batch_i32(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
                                        const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
                                        int mode, int level, int32_t *d_out_zeroed, uint32_t *d_flags);
+/* Row words: a second array of the same size and geometry as the words (spiht_l1_flags_words x B, [planes, gy, gx]).  Bit r
+ * of a tile's row word, 0 <= r < 12 + F/2 - 1, is set when band row r of the region that tile stages (its 12 band rows and
+ * the F/2 - 1 halo rows behind them, every staged column, any of the three level-1 detail bands) holds a decoded cell.  A few
+ * hundred scattered cells per plane set 40 % of the words but under 5 % of the rows; spiht_idwt_level1_rows_batch_* neither
+ * reads nor filters the detail rows whose bit is clear (same bits: a clear row is +0.0 throughout, and y + 0.0 == y).  The
+ * words themselves stay 0 / 1.  d_rows is zero-filled by the call -- in one fill with the words when d_rows == d_flags +
+ * the words' count, so lay them out as one buffer.  d_rows NULL: spiht_decode_lists_flags_batch_i32; ignored without d_flags.
+ * Additions only: the version stays at 2. */
+int spiht_decode_lists_rows_batch_i32(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride, const uint64_t *d_nbytes,
+                                      const uint8_t *d_max_n, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
+                                      int mode, int level, int32_t *d_out_zeroed, uint32_t *d_flags, uint32_t *d_rows);
 int spiht_dequant_idwt_flags_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, const uint32_t *d_flags, int64_t B, int64_t c,
                                        int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                        const double *channel_mults, double *d_img_out);
@@ -402,6 +413,20 @@ int spiht_idwt_level1_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const
 int spiht_idwt_level1_flags_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
                                       int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
                                       const double *channel_mults, uint16_t *d_img_out, const int64_t *out_strides);
+/* ... and the decoder's row words (spiht_decode_lists_rows_batch_i32): per tile the mask of staged detail rows to read and to
+ * filter is its row word; d_rows NULL: the _flags_ call (a set word: every row); ignored without d_flags.  The same pictures,
+ * bit for bit, whatever bits are set beyond the rows that hold a cell. */
+int spiht_idwt_level1_rows_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                     const uint32_t *d_rows, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
+                                     int level, double q_scale, const double *channel_mults, double *d_img_out);
+int spiht_idwt_level1_rows_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                    const uint32_t *d_rows, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
+                                    int level, double q_scale, const double *channel_mults, uint8_t *d_img_out,
+                                    const int64_t *out_strides);
+int spiht_idwt_level1_rows_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                     const uint32_t *d_rows, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode,
+                                     int level, double q_scale, const double *channel_mults, uint16_t *d_img_out,
+                                     const int64_t *out_strides);
 
 /* Colour model change on the device (the reference converts on the host through colour-science, color_models.py:6-13,
  * called from spiht_wrapper.py:158-160 and :278-279): B three-channel float64 images [B,3,npix]; per pixel

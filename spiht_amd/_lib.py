@@ -82,6 +82,8 @@ SYMBOLS = [
     "spiht_hstream_create", "spiht_hstream_destroy", "spiht_hstream_info", "spiht_hstream_input", "spiht_hstream_decode_input",
     "spiht_hstream_submit", "spiht_hstream_next", "spiht_hstream_pending",
     "spiht_tile_cut_set", "spiht_tile_paste_set",
+    "spiht_decode_lists_rows_batch_i32", "spiht_idwt_level1_rows_batch_f64", "spiht_idwt_level1_rows_batch_u8",
+    "spiht_idwt_level1_rows_batch_u16",
 ]
 
 
@@ -183,6 +185,7 @@ def lib():
         L.spiht_idwt_coarse_batch_f64.argtypes = [vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp]
         L.spiht_idwt_level1_batch_f64.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp]
         L.spiht_idwt_level1_flags_batch_f64.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp]
+        L.spiht_idwt_level1_rows_batch_f64.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp]
         L.spiht_idwt_approx_shape.argtypes = [i64, i64, i32, i32, C.POINTER(i64), C.POINTER(i64)]
         L.spiht_encode_image_host_f64.argtypes = [vp, vp, i64, i64, i64, i32, i32, i32, C.c_double, vp, u64, vp, u64,
                                                   C.POINTER(u64), C.POINTER(u8)]
@@ -207,6 +210,7 @@ def lib():
         L.spiht_ctx_wide_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.spiht_l1_flags_words.argtypes = [i64, i64, i64, i32, i32, i32, C.POINTER(u64)]
         L.spiht_decode_lists_flags_batch_i32.argtypes = [vp, vp, u64, vp, vp, i64, i64, i64, i64, i32, i32, i32, vp, vp]
+        L.spiht_decode_lists_rows_batch_i32.argtypes = L.spiht_decode_lists_flags_batch_i32.argtypes + [vp]
         L.spiht_geometry_mode.argtypes = [i64, i64, i32, i32, i32, C.POINTER(i32)] + [C.POINTER(i64)] * 6
         L.spiht_dequant_idwt_flags_batch_f64.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp]
         L.spiht_pipeline_create.argtypes = [i32, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, u64, C.POINTER(vp)]
@@ -231,6 +235,7 @@ def lib():
         L.spiht_dwt_pyramid_batch_u8.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp]
         L.spiht_dequant_idwt_flags_batch_u8.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp]
         L.spiht_idwt_level1_flags_batch_u8.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp]
+        L.spiht_idwt_level1_rows_batch_u8.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, C.c_double, vp, vp, vp]
         L.spiht_pipeline_submit_u8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         L.spiht_check_view_u8.argtypes = [i64, i64, i64, i64, vp, i32]
         # reduced-resolution decode: the full-size call's arguments, then `reduce`

@@ -273,7 +273,10 @@ int decode_device(spiht_ctx *ctx, const Geom &g, const uint8_t *d_data, uint64_t
     a.tr_ent = d_tr_ent; a.tr_act = d_tr_act; a.tr_stride = tr_stride;
     if (fl && fl->p) {  // (zero-filled here: the decoder only ever sets words)
         a.fl = *fl;
-        HIPCHK(hipMemsetAsync(fl->p, 0, (size_t)B * g.c * fl->gy * fl->gx * 4, ctx->stream));
+        const size_t wb = (size_t)B * g.c * fl->gy * fl->gx * 4;
+        const bool one = fl->rows == fl->p + wb / 4;  // words and row words laid out as one buffer: one fill
+        HIPCHK(hipMemsetAsync(fl->p, 0, one ? 2 * wb : wb, ctx->stream));
+        if (fl->rows && !one) HIPCHK(hipMemsetAsync(fl->rows, 0, wb, ctx->stream));
     }
     if (args_out) {  // the caller wants to undo the scatter later: one LSP length per slot
         CHK(ensure(ctx, ctx->lspcnt, (size_t)nslots * 4));
@@ -755,6 +758,16 @@ extern "C" int spiht_decode_lists_flags_batch_i32(spiht_ctx *ctx, const uint8_t 
                                                   const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
                                                   int64_t H, int64_t W, int wavelet, int mode, int level, int32_t *d_out_zeroed,
                                                   uint32_t *d_flags) {
+    return spiht_decode_lists_rows_batch_i32(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, c, H, W, wavelet, mode, level,
+                                             d_out_zeroed, d_flags, nullptr);
+}
+// ... and in d_rows (as many words again, zero-filled by this call; one fill when d_rows == d_flags + the words' count) the
+// row words of those tiles for spiht_idwt_level1_rows_batch_*: bit r of a tile's word is set when its staged band row r holds
+// a decoded cell.  d_rows == NULL: as spiht_decode_lists_flags_batch_i32; without d_flags d_rows is ignored.
+extern "C" int spiht_decode_lists_rows_batch_i32(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stride,
+                                                 const uint64_t *d_nbytes, const uint8_t *d_max_n, int64_t B, int64_t c,
+                                                 int64_t H, int64_t W, int wavelet, int mode, int level, int32_t *d_out_zeroed,
+                                                 uint32_t *d_flags, uint32_t *d_rows) {
     if (!ctx || !d_data || !d_nbytes || !d_max_n || !d_out_zeroed || B < 0) return SPIHT_ERR_ARG;
     ImgCall k;
     int st;
@@ -762,7 +775,7 @@ extern "C" int spiht_decode_lists_flags_batch_i32(spiht_ctx *ctx, const uint8_t 
     if (!k.open(&st, ctx, 1, c, H, W, wavelet, mode, level, true)) return st;
     L1Flags fl;
     const bool flagged = d_flags && l1flags_geometry(k.ig, k.F, &fl);
-    if (flagged) fl.p = d_flags;
+    if (flagged) { fl.p = d_flags; fl.rows = d_rows; }
     return decode_lists_batch(ctx, d_data, slot_stride, d_nbytes, d_max_n, B, k.g, d_out_zeroed, flagged ? &fl : nullptr);
 }
 

@@ -426,13 +426,15 @@ extern "C" int spiht_l1_flags_words(int64_t c, int64_t H, int64_t W, int wavelet
 // l_hi .. l_lo: the levels to run, coarsest first (ig.L .. 1 = all).  A run that stops above level 1 leaves its last
 // approximation in d_out ([planes, 2*hs[l_lo]-F+2, 2*ws[l_lo]-F+2]); a run that starts below ig.L takes that array as d_a_in.
 // d_flags: L1Flags words [planes, gy, gx] the decoder of d_rec left (nullptr: every level-1 tile reads its detail bands)
+// d_rows: their row words (nullptr: a tile whose word is set reads every row)
 // 8- / 16-bit output (l_lo == 1, a level >= 1: see dwt_forward): cropped to the picture's size; the tiled level 1 writes it
 // itself, the two-pass level goes through a conversion pass behind it.
 // A reduced geometry (reduced_geometry: ig.l0 = k levels dropped) runs the same way: its level 1 is level k + 1 of the
 // stream and makes the picture of that size -- integer store, crop, colour change, conversion pass; also as the coarsest
 // level (l == ig.L) -- and q is the caller's q * 2^k (reduced_q).  No d_flags then: the words belong to the stream's level 1.
 int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, const ImgGeom &ig, int wavelet, double q,
-                const double *d_mults, const Pic &out, int l_hi, int l_lo, const double *d_a_in, const uint32_t *d_flags) {
+                const double *d_mults, const Pic &out, int l_hi, int l_lo, const double *d_a_in, const uint32_t *d_flags,
+                const uint32_t *d_rows) {
     const WaveletDef &wv = SPIHT_WAVELETS[wavelet];
     const int F = wv.F;
     if (l_hi < 0) l_hi = ig.L;
@@ -491,7 +493,7 @@ int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, const I
         a.mults = d_mults;
         a.q = q;
         if (color && l == 1) { a.color = 1; a.col = ctx->col_inv; }
-        if (l == 1 && !a.first && !a.color) a.flags = d_flags;
+        if (l == 1 && !a.first && !a.color) { a.flags = d_flags; a.rows = d_flags ? d_rows : nullptr; }
         memcpy(a.lo, wv.rec_lo, sizeof(double) * std::min(F, SPIHT_MAX_TAPS));
         memcpy(a.hi, wv.rec_hi, sizeof(double) * std::min(F, SPIHT_MAX_TAPS));
         const bool conv8 = strided && l == 1 && (ig.per || F > SPIHT_MAX_TAPS);  // a view's output through a pass of its own

@@ -91,7 +91,7 @@ extern "C" int spiht_dequant_idwt_flags_batch_flt(spiht_ctx *ctx, int kind, cons
 //   level1: d_rec + d_approx -> pixels.  With fewer than two levels the coarse part does nothing and d_approx is not read.
 static int idwt_part(spiht_ctx *ctx, const int32_t *d_rec, double *d_approx, int64_t B, int64_t c, int64_t H, int64_t W,
                      int wavelet, int mode, int level, double q_scale, const double *channel_mults, const Pic &out,
-                     const uint32_t *d_flags = nullptr) {
+                     const uint32_t *d_flags = nullptr, const uint32_t *d_rows = nullptr) {
     if (!ctx || !d_rec || (!d_approx && !out.p)) return SPIHT_ERR_ARG;
     ImgCall k;
     int st;
@@ -112,8 +112,9 @@ static int idwt_part(spiht_ctx *ctx, const int32_t *d_rec, double *d_approx, int
         if (coarse)
             return dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, k.d_mults, dense_pic(ap, EL_F64, true), ig.L, 2,
                                nullptr);
+        const size_t w0 = flagged ? (size_t)b0 * c * fl.gy * fl.gx : 0;  // (the chunk's words, and its row words)
         return dwt_inverse(ctx, rec, nb * (int)c, (int)c, ig, wavelet, q_scale, k.d_mults, k.at(out, b0), std::min(ig.L, 1), 1,
-                           ig.L >= 2 ? ap : nullptr, flagged ? d_flags + (size_t)b0 * c * fl.gy * fl.gx : nullptr);
+                           ig.L >= 2 ? ap : nullptr, flagged ? d_flags + w0 : nullptr, flagged && d_rows ? d_rows + w0 : nullptr);
     });
 }
 extern "C" int spiht_idwt_coarse_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, int64_t B, int64_t c, int64_t H, int64_t W,
@@ -131,30 +132,51 @@ extern "C" int spiht_idwt_level1_batch_f64(spiht_ctx *ctx, const int32_t *d_rec,
 extern "C" int spiht_idwt_level1_flags_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
                                                  int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                                                  double q_scale, const double *channel_mults, double *d_img_out) {
+    return spiht_idwt_level1_rows_batch_f64(ctx, d_rec, d_approx, d_flags, nullptr, B, c, H, W, wavelet, mode, level, q_scale,
+                                            channel_mults, d_img_out);
+}
+// ... and its row words (spiht_decode_lists_rows_batch_i32; NULL: a set word means every row)
+extern "C" int spiht_idwt_level1_rows_batch_f64(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                                const uint32_t *d_rows, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
+                                                int mode, int level, double q_scale, const double *channel_mults, double *d_img_out) {
     if (!d_img_out) return SPIHT_ERR_ARG;
     return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
-                     dense_pic(d_img_out, EL_F64, true), d_flags);
+                     dense_pic(d_img_out, EL_F64, true), d_flags, d_rows);
 }
-static int idwt_level1_flags_view(PicElem el, spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
-                                  int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level, double q_scale,
-                                  const double *channel_mults, void *d_img_out, const int64_t *out_strides) {
+static int idwt_level1_rows_view(PicElem el, spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                 const uint32_t *d_rows, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
+                                 double q_scale, const double *channel_mults, void *d_img_out, const int64_t *out_strides) {
     Pic out;
     CHK(view_pic(&out, d_img_out, el, true, out_strides, 4, B, c, H, W, PIC_NULL_FIRST));
     return idwt_part(ctx, d_rec, const_cast<double *>(d_approx), B, c, H, W, wavelet, mode, level, q_scale, channel_mults, out,
-                     d_flags);
+                     d_flags, d_rows);
+}
+extern "C" int spiht_idwt_level1_rows_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                               const uint32_t *d_rows, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
+                                               int mode, int level, double q_scale, const double *channel_mults, uint8_t *d_img_out,
+                                               const int64_t *out_strides) {
+    return idwt_level1_rows_view(EL_U8, ctx, d_rec, d_approx, d_flags, d_rows, B, c, H, W, wavelet, mode, level, q_scale,
+                                 channel_mults, d_img_out, out_strides);
+}
+extern "C" int spiht_idwt_level1_rows_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
+                                                const uint32_t *d_rows, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet,
+                                                int mode, int level, double q_scale, const double *channel_mults,
+                                                uint16_t *d_img_out, const int64_t *out_strides) {
+    return idwt_level1_rows_view(EL_U16, ctx, d_rec, d_approx, d_flags, d_rows, B, c, H, W, wavelet, mode, level, q_scale,
+                                 channel_mults, d_img_out, out_strides);
 }
 extern "C" int spiht_idwt_level1_flags_batch_u8(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
                                                 int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                                                 double q_scale, const double *channel_mults, uint8_t *d_img_out,
                                                 const int64_t *out_strides) {
-    return idwt_level1_flags_view(EL_U8, ctx, d_rec, d_approx, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+    return idwt_level1_rows_view(EL_U8, ctx, d_rec, d_approx, d_flags, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                                   d_img_out, out_strides);
 }
 extern "C" int spiht_idwt_level1_flags_batch_u16(spiht_ctx *ctx, const int32_t *d_rec, const double *d_approx, const uint32_t *d_flags,
                                                  int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,
                                                  double q_scale, const double *channel_mults, uint16_t *d_img_out,
                                                  const int64_t *out_strides) {
-    return idwt_level1_flags_view(EL_U16, ctx, d_rec, d_approx, d_flags, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
+    return idwt_level1_rows_view(EL_U16, ctx, d_rec, d_approx, d_flags, nullptr, B, c, H, W, wavelet, mode, level, q_scale, channel_mults,
                                   d_img_out, out_strides);
 }
 
@@ -243,14 +265,16 @@ int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stri
         // (a reduced decode never reaches the stream's level 1: it asks for no words and passes none)
         const bool flagged = ctx->opt_l1_flags && reduce == 0 && !(ctx->color_on && c == 3) && l1flags_geometry(k.ig, k.F, &fl);
         if (flagged) {
-            CHK(ensure(ctx, ctx->l1flags, (size_t)nb * c * fl.gy * fl.gx * 4));
+            const size_t nw = (size_t)nb * c * fl.gy * fl.gx;  // words, and as many row words behind them: one buffer, one fill
+            CHK(ensure(ctx, ctx->l1flags, 2 * nw * 4));
             fl.p = (uint32_t *)ctx->l1flags.p;
+            fl.rows = fl.p + nw;
         }
         if (rec) {
             CHK(decode_device(ctx, g, d_data + (size_t)b0 * slot_stride, slot_stride, d_nbytes + b0, d_max_n + b0, nb, rec,
                               nullptr, nullptr, 0, true, nullptr, flagged ? &fl : nullptr));
             return dwt_inverse(ctx, rec, nb * (int)c, (int)c, k.pig, wavelet, k.q, k.d_mults, k.at(out, b0), -1, 1, nullptr,
-                               flagged ? fl.p : nullptr);
+                               flagged ? fl.p : nullptr, flagged ? fl.rows : nullptr);
         }
         // Internal coefficient array: it is all zero on entry and is left all zero -- after the inverse transform the
         // cells the decoder wrote are cleared again through its own LSP lists (about 1 % of the array) instead of
@@ -268,7 +292,7 @@ int decode_image_batch(spiht_ctx *ctx, const uint8_t *d_data, uint64_t slot_stri
                           nullptr, 0, false, &da, flagged ? &fl : nullptr));
         // (a reduced inverse reads a corner of the array only; the decoder wrote all over it: its whole LSP is cleared)
         CHK(dwt_inverse(ctx, rec, nb * (int)c, (int)c, k.pig, wavelet, k.q, k.d_mults, k.at(out, b0), -1, 1, nullptr,
-                        flagged ? fl.p : nullptr));
+                        flagged ? fl.p : nullptr, flagged ? fl.rows : nullptr));
         if (da.nslots >= nb) {
             StageTimer t(ctx, ST_MEMSET);
             LAUNCHCHK(spiht_launch_unscatter(&da, ctx->stream));

@@ -314,7 +314,7 @@ int dwt_forward(spiht_ctx *ctx, const Pic &in, int planes, int c, const ImgGeom 
                 const double *d_mults, int32_t *d_coeffs, uint32_t *d_maxabs = nullptr);
 int dwt_inverse(spiht_ctx *ctx, const int32_t *d_rec, int planes, int c, const ImgGeom &ig, int wavelet, double q,
                 const double *d_mults, const Pic &out, int l_hi = -1, int l_lo = 1, const double *d_a_in = nullptr,
-                const uint32_t *d_flags = nullptr);
+                const uint32_t *d_flags = nullptr, const uint32_t *d_rows = nullptr);
 
 // ---- api_image.cpp: what a host-fed stream queues -- the batched coded calls on a picture, and on a view of element el -----------
 int encode_image_batch(spiht_ctx *ctx, const Pic &in, int64_t B, int64_t c, int64_t H, int64_t W, int wavelet, int mode, int level,

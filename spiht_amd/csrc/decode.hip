@@ -431,6 +431,10 @@ __device__ __forceinline__ void tr_put(const Trace &tr, uint32_t pos, uint32_t a
 // The cell idx of the image's coefficient array gets a value: if it is a cell of a level-1 detail band, the words of the
 // inverse-transform tiles that stage it are set (the tile it lies in and, within F/2 - 1 band rows / columns of that
 // tile's start, the tile before: a tile stages its halo behind itself).  Plain stores of 1: racing writers agree.
+// With row words (f.rows), the bit of the staged row the cell lies in is set in the same tiles' row words: row bi - ty*TR of
+// the tile it lies in and of the one to its left, row TR + that of the tiles above (their halo).  About a thousand cells of
+// a 1080p image at 0.5 bpp come here.
+static_assert(IW_TH / 2 + IW_TH / 2 <= 32, "a tile's staged rows (IW_TH/2 + hf1, hf1 <= IW_TH/2) are the bits of one word");
 __device__ __forceinline__ void l1_mark(const Geom &g, const L1Flags &f, uint32_t plane0, uint32_t idx) {
     uint32_t k, i, j;
     decomp(g, idx, k, i, j);
@@ -446,6 +450,13 @@ __device__ __forceinline__ void l1_mark(const Geom &g, const L1Flags &f, uint32_
     if (up && ty - 1u < gy && tx < gx) p[(ty - 1u) * gx + tx] = 1u;
     if (lf && ty < gy && tx - 1u < gx) p[ty * gx + tx - 1u] = 1u;
     if (up && lf && ty - 1u < gy && tx - 1u < gx) p[(ty - 1u) * gx + tx - 1u] = 1u;
+    if (f.rows == nullptr) return;
+    uint32_t *rw = f.rows + (size_t)(plane0 + k) * gy * gx;
+    const uint32_t own = 1u << (bi - ty * TR), above = own << TR;
+    if (ty < gy && tx < gx) atomicOr(rw + ty * gx + tx, own);
+    if (up && ty - 1u < gy && tx < gx) atomicOr(rw + (ty - 1u) * gx + tx, above);
+    if (lf && ty < gy && tx - 1u < gx) atomicOr(rw + ty * gx + tx - 1u, own);
+    if (up && lf && ty - 1u < gy && tx - 1u < gx) atomicOr(rw + (ty - 1u) * gx + tx - 1u, above);
 }
 
 // ---- duplicated cells ----

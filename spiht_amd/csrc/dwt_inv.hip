@@ -6,8 +6,81 @@
 // 4.02 ms, 20: 4.05, 24: 4.03, 32: 4.19, 12: 4.22, 40: 4.67, 8: 4.74; persistent kernel beside the list decoder (the
 // pipelined schedule): 16 rows 7.3 ms, 20: 7.0, 24: 6.5-6.7, 28: 8.1, 32: 7.6
 
-// grid: (ceil(out_w/TW), ceil(out_h/TH), planes).  LOM / HIM: non-zero taps of rec_lo / rec_hi (a product with a
-// zero tap adds exactly nothing to `ca*lo + cd*hi`, so it is skipped).
+// ---- the filter of a thread, shared by k_idwt_level and k_idwt_level_pf -------------------------------------------------
+// LOM / HIM: non-zero taps of rec_lo / rec_hi (a product with a zero tap adds exactly nothing to `ca*lo + cd*hi`, so it
+// is skipped).
+// `full` (wave-uniform) false: the caller knows the detail part of the sums to be +0.0 and it is not computed.  That is the
+// case for a staged band row whose bit in the tile's row word (common.h: L1Flags) is clear, in a plane whose zeros
+// dequantise to +0.0 (zero_ok): the row is +0.0 in the three detail bands, over every staged column, halo included.  An
+// accumulator that starts at the literal 0.0 and adds products (+0.0) * tap = +-0.0 stays +0.0, so td, ua and ud are +0.0,
+// th = (0.0 + 0.0) + 0.0 is +0.0, and tl = (0.0 + ta) + 0.0 is 0.0 + ta: 0.0 + ta is never -0.0, and y + 0.0 == y in every
+// bit for every other y, NaN and the infinities included.  A window of such rows holds th = +0.0 only: sd is +0.0 and the
+// output (0.0 + sa) + 0.0 likewise.  So skipping changes no bit, whatever further bits the word has set.
+//
+// IDWT_ROW: axis -1 synthesis of band row r at the thread's output column (cl: its first contributing staged column; tlo /
+// thi: the taps of its parity).  Order of the additions as in pywt's upsampling_convolution_valid_sf: the approximation and
+// the detail contribution are separate sums, each over j = 0..F/2-1 (tap 2j+parity against band column i-j, i.e. DEscending
+// band column), and the detail sum is added to the finished approximation sum -- the result is then bit-identical to
+// pywt.waverec2's.
+// (A macro, not a function: through a function's reference parameters the filters of 12 taps and more come out with a quarter
+// more registers -- 186 instead of 147 for 14 taps -- and a workgroup fewer per CU.)  In scope: s_b, cl, tlo, thi; F, LOM, HIM.
+#define IDWT_ROW(tl, th, r, full)                                                                             \
+    double tl, th;                                                                                            \
+    {                                                                                                         \
+        constexpr uint32_t PAIR_ = 3u; /* taps F-2-2s (even columns) and F-1-2s (odd columns): skip a product when both are zero */ \
+        double ta_ = 0.0, td_ = 0.0, ua_ = 0.0, ud_ = 0.0;                                                    \
+        if (full) {                                                                                           \
+            _Pragma("unroll") for (int j_ = 0; j_ < F / 2; j_++) {                                            \
+                const int s_ = F / 2 - 1 - j_;                                                                \
+                if (((LOM >> (F - 2 - 2 * s_)) & PAIR_) != 0) {                                               \
+                    ta_ += s_b[0][r][cl + s_] * tlo[s_];                                                      \
+                    ua_ += s_b[2][r][cl + s_] * tlo[s_];                                                      \
+                }                                                                                             \
+                if (((HIM >> (F - 2 - 2 * s_)) & PAIR_) != 0) {                                               \
+                    td_ += s_b[1][r][cl + s_] * thi[s_];                                                      \
+                    ud_ += s_b[3][r][cl + s_] * thi[s_];                                                      \
+                }                                                                                             \
+            }                                                                                                 \
+        } else {                                                                                              \
+            _Pragma("unroll") for (int j_ = 0; j_ < F / 2; j_++) {                                            \
+                const int s_ = F / 2 - 1 - j_;                                                                \
+                if (((LOM >> (F - 2 - 2 * s_)) & PAIR_) != 0) ta_ += s_b[0][r][cl + s_] * tlo[s_];            \
+            }                                                                                                 \
+        }                                                                                                     \
+        tl = (0.0 + ta_) + td_;                                                                               \
+        th = (0.0 + ua_) + ud_;                                                                               \
+    }
+// idwt_col: output row 2kb + mp of a window wl / wh that holds band rows kb..kb+F/2-1 (index F/2-1 = newest); the same order
+// along axis -2
+template <int F, uint32_t LOM, uint32_t HIM>
+__device__ __forceinline__ double idwt_col(const double (&wl)[F / 2], const double (&wh)[F / 2], const double *lo, const double *hi,
+                                           int mp, bool full) {
+    constexpr int HF = F / 2;
+    double sa = 0.0, sd = 0.0;
+    if (full) {
+#pragma unroll
+        for (int j = 0; j < HF; j++) {
+            const int s = HF - 1 - j;
+            if ((LOM >> (mp + F - 2 - 2 * s)) & 1u) sa += wl[s] * lo[mp + F - 2 - 2 * s];
+            if ((HIM >> (mp + F - 2 - 2 * s)) & 1u) sd += wh[s] * hi[mp + F - 2 - 2 * s];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < HF; j++) {
+            const int s = HF - 1 - j;
+            if ((LOM >> (mp + F - 2 - 2 * s)) & 1u) sa += wl[s] * lo[mp + F - 2 - 2 * s];
+        }
+    }
+    return (0.0 + sa) + sd;
+}
+// The filters up to 10 taps take the two paths.  The longer ones hold their windows and taps in 170 registers with one path and
+// spill with two: their row words steer the loads only, and every row is filtered in full.
+template <int F> constexpr bool IDWT_ROW_SKIP = F <= 10;
+// The rows a thread's half of the tile walks, as a wave-uniform mask with the half's first row at bit 0: a half-tile is two
+// whole wavefronts, which the compiler cannot know -- said so, the tests of the bits are scalar.
+__device__ __forceinline__ uint32_t half_rows(uint32_t mask, int rbase) { return __builtin_amdgcn_readfirstlane(mask >> rbase); }
+
+// grid: (ceil(out_w/TW), ceil(out_h/TH), planes).
 template <int F, uint32_t LOM, uint32_t HIM, int PX = PX_F64>  // PX_U8 / PX_U16: level 1 into an 8- / 16-bit picture (a.px; a.out unused)
 __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
     // band index k contributes to output n with tap t = n + F - 2 - 2k in [0,F):  k in [n/2, n/2 + F/2 - 1]
@@ -28,16 +101,18 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
     const int32_t *__restrict__ rec = a.rec + (size_t)plane * a.enc_h * a.enc_w;
     const double *__restrict__ ain = a.first ? nullptr : a.a_in + (size_t)plane * a.a_h * a.a_w;
     const int tid = threadIdx.x;
-    // L1Flags word of this tile still zero: the decoder wrote nothing into the detail bands it stages -- they are not
-    // read (a zero goes through the same arithmetic: same bits)
-    const bool occupied = a.flags == nullptr ||
-        a.flags[((size_t)plane * ((a.out_h + IW_TH - 1) / IW_TH) + tby) * ((a.out_w + IW_TW - 1) / IW_TW) + tbx] != 0u;
+    // The mask of this tile's staged band rows that may hold a cell of a detail band: its row word; without row words every
+    // row when its L1Flags word is set, none when that is still zero.  The detail bands of the other rows are not read (a zero
+    // goes through the same arithmetic: same bits) and, where zeros dequantise to +0.0, not filtered either (IDWT_ROW)
+    const size_t ti = ((size_t)plane * ((a.out_h + IW_TH - 1) / IW_TH) + tby) * ((a.out_w + IW_TW - 1) / IW_TW) + tbx;
+    const uint32_t mask = a.flags == nullptr ? ~0u : a.rows != nullptr ? a.rows[ti] : a.flags[ti] != 0u ? ~0u : 0u;
 
     for (int p = tid; p < KH * KW; p += DW_BLOCK) {
         const int r = p / KW, cidx = p - r * KW;
         const int bi = kh0 + r, bj = kw0 + cidx;
         double vaa = 0.0, vad = 0.0, vda = 0.0, vdd = 0.0;
         if (bi < a.band_h && bj < a.band_w) {
+            const bool occupied = (mask >> r) & 1u;
             const int32_t rad = occupied ? rec[(size_t)bi * a.enc_w + a.off_w + bj] : 0;
             const int32_t rda = occupied ? rec[(size_t)(a.off_h + bi) * a.enc_w + bj] : 0;
             const int32_t rdd = occupied ? rec[(size_t)(a.off_h + bi) * a.enc_w + a.off_w + bj] : 0;
@@ -73,30 +148,12 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
     double *__restrict__ out = PX ? nullptr : a.out + (size_t)plane * a.out_h * a.out_w;
     uint8_t *__restrict__ out8 = PX ? a.px.out + (int64_t)(plane / a.c) * a.px.sb + (int64_t)(plane % a.c) * a.px.sc : nullptr;
     const int rbase = half * (IW_TH / 4);  // first band row (tile-relative) of this half
+    // (a zero that dequantises to -0.0 or NaN: every row in full)
+    const uint32_t fm = IDWT_ROW_SKIP<F> ? half_rows(zero_ok ? mask : ~0u, rbase) : ~0u;
 #pragma unroll
     for (int rr = 0; rr < KHH; rr++) {
         const int r = rbase + rr;
-        // axis -1 synthesis of band row r at output column n.  Order of the additions as in pywt's
-        // upsampling_convolution_valid_sf: the approximation and the detail contribution are separate sums, each over
-        // j = 0..F/2-1 (tap 2j+parity against band column i-j, i.e. DEscending band column), and the detail sum is
-        // added to the finished approximation sum -- the result is then bit-identical to pywt.waverec2's.
-        double ta = 0.0, td = 0.0, ua = 0.0, ud = 0.0;
-#pragma unroll
-        for (int j = 0; j < HF; j++) {
-            const int s = HF - 1 - j;
-            // taps F-2-2s (even columns) and F-1-2s (odd columns): skip a product when both are zero
-            constexpr uint32_t PAIR = 3u;
-            const bool lnz = ((LOM >> (F - 2 - 2 * s)) & PAIR) != 0, hnz = ((HIM >> (F - 2 - 2 * s)) & PAIR) != 0;
-            if (lnz) {
-                ta += s_b[0][r][cl + s] * tlo[s];
-                ua += s_b[2][r][cl + s] * tlo[s];
-            }
-            if (hnz) {
-                td += s_b[1][r][cl + s] * thi[s];
-                ud += s_b[3][r][cl + s] * thi[s];
-            }
-        }
-        const double tl = (0.0 + ta) + td, th = (0.0 + ua) + ud;
+        IDWT_ROW(tl, th, r, (fm >> rr) & 1u)
 #pragma unroll
         for (int s = 0; s < HF - 1; s++) { wl[s] = wl[s + 1]; wh[s] = wh[s + 1]; }
         wl[HF - 1] = tl;
@@ -104,17 +161,10 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
         if (rr >= HF - 1) {
             // window holds band rows kb..kb+HF-1 with kb = kh0 + r - (HF-1): output rows 2kb, 2kb+1
             const int m = 2 * (kh0 + r - (HF - 1));
+            const bool wfull = ((fm >> (rr - (HF - 1))) & ((1u << HF) - 1u)) != 0u;  // a row of the window holds a cell
 #pragma unroll
             for (int mp = 0; mp < 2; mp++) {
-                double sa = 0.0, sd = 0.0;  // same order along axis -2
-#pragma unroll
-                for (int j = 0; j < HF; j++) {
-                    const int s = HF - 1 - j;
-                    const bool lnz = (LOM >> (mp + F - 2 - 2 * s)) & 1u, hnz = (HIM >> (mp + F - 2 - 2 * s)) & 1u;
-                    if (lnz) sa += wl[s] * a.lo[mp + F - 2 - 2 * s];
-                    if (hnz) sd += wh[s] * a.hi[mp + F - 2 - 2 * s];
-                }
-                const double sacc = (0.0 + sa) + sd;
+                const double sacc = idwt_col<F, LOM, HIM>(wl, wh, a.lo, a.hi, mp, wfull);
                 if (PX) {
                     if (m + mp < a.px.h && n < a.px.w) PX_STORE(PX, out8, (int64_t)(m + mp) * a.px.sh + (int64_t)n * a.px.sw, sacc, a.px.kind);
                 } else {
@@ -138,8 +188,9 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level(IdwtKArgs a) {
 #define IWP_WG 4
 #endif
 
-// FLAGS: a.flags holds one word per tile (common.h: L1Flags); the detail bands of a tile whose word is zero are all zero
-// and are not read.  The loads stay unconditional -- a branch around them would make every later wait a wait for
+// FLAGS: a.flags holds one word per tile (common.h: L1Flags), a.rows -- if given -- one row word; the detail bands of a tile
+// whose word is zero, and with row words those of every staged row whose bit is clear, are all zero: they are not read and,
+// where a zero dequantises to +0.0, neither staged nor filtered (IDWT_ROW, idwt_col).  The loads stay unconditional -- a branch around them would make every later wait a wait for
 // everything -- and go through a buffer descriptor of the plane instead: an offset beyond it returns 0 without a trip
 // to memory.  The word of a tile is fetched when the tile's number becomes known, a tile of work ahead of its use.
 // PX_U8 / PX_U16: the output is the strided 8- / 16-bit picture a.px (common.h: PxView); the launcher sees to it that a
@@ -183,7 +234,12 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
         double vaa[NE];
         double mk;  // the plane's channel scale (a load as well: it must not be waited for on its own)
     };
-    auto request = [&](Stage &g, uint32_t T, uint32_t occ) {  // the loads of tile T (nothing waits for them here)
+    // What occupancy() below loaded for a tile -> the mask of its staged detail rows: its row word, or, without row words,
+    // every row when its L1Flags word is set.  Made where the mask is used, a tile of work behind the load: made at the load
+    // it would wait for it there -- for everything, the stores of the tile before included.
+    auto rows_of = [&](uint32_t w) -> uint32_t { return !FLAGS ? ~0u : a.rows != nullptr ? w : w != 0u ? ~0u : 0u; };
+    auto request = [&](Stage &g, uint32_t T, uint32_t occw) {  // the loads of tile T (nothing waits for them here)
+        const uint32_t occ = rows_of(occw);
         const uint32_t bx = T % gx, t2 = T / gx, by = t2 % gy, plane = t2 / gy;
         const int kh0 = (int)(by * IW_TH) / 2, kw0 = (int)(bx * IW_TW) / 2;
         const int32_t *__restrict__ rec = a.rec + (size_t)plane * a.enc_h * a.enc_w;
@@ -199,9 +255,10 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
             if (FLAGS) {
                 const uint32_t o_ad = ((uint32_t)bi * (uint32_t)a.enc_w + (uint32_t)(a.off_w + bj)) * 4u;
                 const uint32_t o_da = ((uint32_t)(a.off_h + bi) * (uint32_t)a.enc_w + (uint32_t)bj) * 4u;
-                g.rad[e] = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, occ ? o_ad : BUF_OOB, 0, 0);
-                g.rda[e] = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, occ ? o_da : BUF_OOB, 0, 0);
-                g.rdd[e] = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, occ ? o_da + (uint32_t)a.off_w * 4u : BUF_OOB, 0, 0);
+                const bool rd = __builtin_amdgcn_ubfe(occ, (uint32_t)rr, 1u) != 0u;  // the row's bit in the tile's mask (one v_bfe_u32)
+                g.rad[e] = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, rd ? o_ad : BUF_OOB, 0, 0);
+                g.rda[e] = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, rd ? o_da : BUF_OOB, 0, 0);
+                g.rdd[e] = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, rd ? o_da + (uint32_t)a.off_w * 4u : BUF_OOB, 0, 0);
             } else {
                 g.rad[e] = rec[(size_t)bi * a.enc_w + a.off_w + bj];
                 g.rda[e] = rec[(size_t)(a.off_h + bi) * a.enc_w + bj];
@@ -222,12 +279,15 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
     }
     const bool has_m = a.mults != nullptr;
     // one tile: its samples (in g) -> LDS, then g is free and takes the loads of the next tile; filter; store
-    auto tile = [&](Stage &g, uint32_t kk, uint32_t knext, uint32_t occ_next) {
+    auto tile = [&](Stage &g, uint32_t kk, uint32_t knext, uint32_t occw, uint32_t occ_next) {
         const uint32_t T = base + kk;
         const uint32_t bx = T % gx, t2 = T / gx, by = t2 % gy, plane = t2 / gy;
         const int kh0s = (int)(by * IW_TH) / 2, kw0s = (int)(bx * IW_TW) / 2;
         const double mk = g.mk;
         const bool zero_ok = (!has_m || mk > 0.0) && a.q > 0.0;  // 0/m/q == +0.0 exactly: skip the divisions
+        // the rows whose detail bands the filter reads: the tile's mask, or all of them where a zero is not +0.0.  The others
+        // are not written to LDS either (what an earlier tile left there is never read)
+        const uint32_t fmask = !FLAGS || !IDWT_ROW_SKIP<F> || !zero_ok ? ~0u : rows_of(occw);
 #pragma unroll
         for (int e = 0; e < NE; e++) {
             const int p = tid + e * DW_BLOCK;
@@ -236,9 +296,11 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
                 const bool in = kh0s + rr < a.band_h && kw0s + cidx < a.band_w;
                 const double va = FIRST ? ((g.raa[e] == 0 && zero_ok) ? 0.0 : dequant(g.raa[e], mk, a.q, has_m)) : g.vaa[e];
                 s_b[0][rr][cidx] = in ? va : 0.0;
-                s_b[1][rr][cidx] = (!in || (g.rad[e] == 0 && zero_ok)) ? 0.0 : dequant(g.rad[e], mk, a.q, has_m);
-                s_b[2][rr][cidx] = (!in || (g.rda[e] == 0 && zero_ok)) ? 0.0 : dequant(g.rda[e], mk, a.q, has_m);
-                s_b[3][rr][cidx] = (!in || (g.rdd[e] == 0 && zero_ok)) ? 0.0 : dequant(g.rdd[e], mk, a.q, has_m);
+                if (!FLAGS || !IDWT_ROW_SKIP<F> || __builtin_amdgcn_ubfe(fmask, (uint32_t)rr, 1u) != 0u) {
+                    s_b[1][rr][cidx] = (!in || (g.rad[e] == 0 && zero_ok)) ? 0.0 : dequant(g.rad[e], mk, a.q, has_m);
+                    s_b[2][rr][cidx] = (!in || (g.rda[e] == 0 && zero_ok)) ? 0.0 : dequant(g.rda[e], mk, a.q, has_m);
+                    s_b[3][rr][cidx] = (!in || (g.rdd[e] == 0 && zero_ok)) ? 0.0 : dequant(g.rdd[e], mk, a.q, has_m);
+                }
             }
         }
         // the tile after `knext` is drawn here -- behind the wait for this tile's samples, ahead of the next tile's
@@ -254,6 +316,7 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
 #pragma unroll
         for (int s2 = 0; s2 < HF; s2++) { wl[s2] = 0.0; wh[s2] = 0.0; }
         const int rbase = half * (IW_TH / 4);
+        const uint32_t fm = FLAGS && IDWT_ROW_SKIP<F> ? half_rows(fmask, rbase) : ~0u;
         // Stores through a buffer descriptor of the plane: what falls outside the picture (rows past the plane's end by
         // the descriptor's range check, columns past out_w by an offset beyond it) is dropped by the hardware, so the
         // stores stand in straight-line code.  With branches around them the compiler cannot count them, and the wait
@@ -269,38 +332,17 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
 #pragma unroll
         for (int rr = 0; rr < KHH; rr++) {
             const int r = rbase + rr;
-            double ta = 0.0, td = 0.0, ua = 0.0, ud = 0.0;
-#pragma unroll
-            for (int j = 0; j < HF; j++) {
-                const int s2 = HF - 1 - j;
-                constexpr uint32_t PAIR = 3u;
-                const bool lnz = ((LOM >> (F - 2 - 2 * s2)) & PAIR) != 0, hnz = ((HIM >> (F - 2 - 2 * s2)) & PAIR) != 0;
-                if (lnz) {
-                    ta += s_b[0][r][cl + s2] * tlo[s2];
-                    ua += s_b[2][r][cl + s2] * tlo[s2];
-                }
-                if (hnz) {
-                    td += s_b[1][r][cl + s2] * thi[s2];
-                    ud += s_b[3][r][cl + s2] * thi[s2];
-                }
-            }
-            const double tl = (0.0 + ta) + td, th = (0.0 + ua) + ud;
+            // (the branches on the mask's bits go around LDS reads and arithmetic only: the stores below stay in the straight line)
+            IDWT_ROW(tl, th, r, (fm >> rr) & 1u)
 #pragma unroll
             for (int s2 = 0; s2 < HF - 1; s2++) { wl[s2] = wl[s2 + 1]; wh[s2] = wh[s2 + 1]; }
             wl[HF - 1] = tl;
             wh[HF - 1] = th;
             if (rr >= HF - 1) {
+                const bool wfull = ((fm >> (rr - (HF - 1))) & ((1u << HF) - 1u)) != 0u;  // a row of the window holds a cell
 #pragma unroll
                 for (int mp = 0; mp < 2; mp++) {
-                    double sa = 0.0, sd = 0.0;
-#pragma unroll
-                    for (int j = 0; j < HF; j++) {
-                        const int s2 = HF - 1 - j;
-                        const bool lnz = (LOM >> (mp + F - 2 - 2 * s2)) & 1u, hnz = (HIM >> (mp + F - 2 - 2 * s2)) & 1u;
-                        if (lnz) sa += wl[s2] * a.lo[mp + F - 2 - 2 * s2];
-                        if (hnz) sd += wh[s2] * a.hi[mp + F - 2 - 2 * s2];
-                    }
-                    const double sacc = (0.0 + sa) + sd;
+                    const double sacc = idwt_col<F, LOM, HIM>(wl, wh, a.lo, a.hi, mp, wfull);
                     if constexpr (PX == PX_U8) {
                         const int dy = 2 * (rr - (HF - 1)) + mp;
                         __builtin_amdgcn_raw_buffer_store_b8(px8_store_value(sacc), orsrc,
@@ -331,23 +373,27 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt_level_pf(IdwtKArgs a, uint32_
     // a decoder instead of two and was slower there: 9.2-10.6 instead of 7.2 ms for level 1.)
     Stage g0;
     if (k >= cnt) return;
-    auto occupancy = [&](uint32_t kk) -> uint32_t {  // the L1Flags word of position kk of this XCD's range (clamped as the request is)
-        return FLAGS ? a.flags[base + min(kk, cnt - 1u)] : 1u;
-    };
-    request(g0, base + k, occupancy(k));
+    // the row word of position kk of this XCD's range (clamped as the request is), or without row words its L1Flags word: one
+    // load per tile either way, not looked at here (rows_of)
+    const uint32_t *const mw = FLAGS ? (a.rows != nullptr ? a.rows : a.flags) : nullptr;
+    auto occupancy = [&](uint32_t kk) -> uint32_t { return FLAGS ? mw[base + min(kk, cnt - 1u)] : 1u; };
+    uint32_t occ = occupancy(k);
+    request(g0, base + k, occ);
     uint32_t occ_n = occupancy(kn);
     // The first tile stands outside the loop: inside it the wait for a tile's samples can then be "all but the stores
     // issued since" on every path into the loop head (with the first trip inside, nothing follows the samples' loads on
     // the path from above, and the compiler has to make it a wait for everything -- the stores of the tile before).
-    tile(g0, k, kn, occ_n);
+    tile(g0, k, kn, occ, occ_n);
     k = kn;
     kn = __builtin_amdgcn_readfirstlane(s_next[0]);  // (s_next[0] is written again only behind the
                                                                          // next tile's first barrier)
+    occ = occ_n;
     occ_n = occupancy(kn);
     while (k < cnt) {
-        tile(g0, k, kn, occ_n);
+        tile(g0, k, kn, occ, occ_n);
         k = kn;
         kn = __builtin_amdgcn_readfirstlane(s_next[0]);
+        occ = occ_n;
         occ_n = occupancy(kn);
     }
 }
@@ -484,9 +530,9 @@ __global__ __launch_bounds__(DW_BLOCK) void k_idwt1_color(IdwtKArgs a) {
 template <int F, uint32_t LOM, uint32_t HIM, int PX>
 static void launch_idwt_pf(IdwtKArgs &a, uint32_t G, uint32_t pad, hipStream_t st, uint32_t gx, uint32_t gy, uint32_t *ctr, const TileBase &cb) {
     if (a.first) hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, true, false, PX>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
-    else if (a.flags && (uint64_t)a.enc_h * a.enc_w * 4u < (1ull << 31))
+    else if (a.flags && (uint64_t)a.enc_h * a.enc_w * 4u < (1ull << 31))  // (with a.rows or without: one kernel)
         hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, true, PX>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb);
-    else { a.flags = nullptr; hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, false, PX>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb); }
+    else { a.flags = nullptr; a.rows = nullptr; hipLaunchKernelGGL((k_idwt_level_pf<F, LOM, HIM, false, false, PX>), dim3(G), dim3(DW_BLOCK), pad, st, a, gx, gy, ctr, cb); }
 }
 // a.px.out set: level 1 into an 8- or 16-bit picture (the kernels of the kind a.px.es names; a.out unused)
 template <int F, uint32_t LOM, uint32_t HIM>

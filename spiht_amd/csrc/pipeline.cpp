@@ -72,6 +72,8 @@ struct spiht_pipeline {
     double cAf[9], cMf[9], cAi[9], cMi[9], cpf = 1.0, cpi = 1.0;
     int poisoned = SPIHT_OK;   // a call failed half-way: the schedule's state is void, every later call returns this
     const double *mp() const { return mults.empty() ? nullptr : mults.data(); }
+    // the row words of buffer set s: behind its occupancy words, in the same allocation (the decoder zero-fills both at once)
+    uint32_t *rows(int s) const { return flags[s] ? flags[s] + (uint64_t)B * flag_words : nullptr; }
 };
 
 // The H context may be the caller's (spiht_pipeline_create_on): nothing of the pipeline's stays on it between calls.  While a
@@ -161,7 +163,7 @@ static int pipeline_create(spiht_ctx *h_ctx, int device, int64_t B, int64_t c, i
             {(void **)&p->coeffs[s], (uint64_t)B * n * 4}, {(void **)&p->rec[s], (uint64_t)B * n * 4},
             {(void **)&p->dmsb[s], (uint64_t)B * n},       {(void **)&p->lmsb[s], (uint64_t)B * n},
             {(void **)&p->maxabs[s], (uint64_t)B * 4},     {(void **)&p->nbytes[s], (uint64_t)B * 8},
-            {(void **)&p->flags[s], (uint64_t)B * p->flag_words * 4}};
+            {(void **)&p->flags[s], 2 * (uint64_t)B * p->flag_words * 4}};  // words, and the row words behind them (rows())
         for (auto &a : al) {
             if (a.bytes == 0) continue;
             if ((st = spiht_dev_alloc(p->Hc, a.bytes, a.ptr)) != SPIHT_OK) break;
@@ -239,20 +241,20 @@ static int queue_inverse_coarse(spiht_pipeline *p, int s) {
 static int queue_inverse_level1(spiht_pipeline *p, int s, const StepPics &out) {
     if (out.es == 2) {
         if (p->approx)
-            CHK(spiht_idwt_level1_flags_batch_u16(p->Hc, p->rec[s], p->approx, p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode,
+            CHK(spiht_idwt_level1_rows_batch_u16(p->Hc, p->rec[s], p->approx, p->flags[s], p->rows(s), p->B, p->c, p->H, p->W, p->wavelet, p->mode,
                                                   p->level, p->q, p->mp(), (uint16_t *)out.p, out.strides()));
         else
             CHK(spiht_dequant_idwt_flags_batch_u16(p->Hc, p->rec[s], p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
                                                    p->q, p->mp(), (uint16_t *)out.p, out.strides()));
     } else if (out.es == 1) {
         if (p->approx)
-            CHK(spiht_idwt_level1_flags_batch_u8(p->Hc, p->rec[s], p->approx, p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode,
+            CHK(spiht_idwt_level1_rows_batch_u8(p->Hc, p->rec[s], p->approx, p->flags[s], p->rows(s), p->B, p->c, p->H, p->W, p->wavelet, p->mode,
                                                  p->level, p->q, p->mp(), (uint8_t *)out.p, out.strides()));
         else
             CHK(spiht_dequant_idwt_flags_batch_u8(p->Hc, p->rec[s], p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
                                                   p->q, p->mp(), (uint8_t *)out.p, out.strides()));
     } else if (p->approx)
-        CHK(spiht_idwt_level1_flags_batch_f64(p->Hc, p->rec[s], p->approx, p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode,
+        CHK(spiht_idwt_level1_rows_batch_f64(p->Hc, p->rec[s], p->approx, p->flags[s], p->rows(s), p->B, p->c, p->H, p->W, p->wavelet, p->mode,
                                               p->level, p->q, p->mp(), (double *)out.p));
     else
         CHK(spiht_dequant_idwt_flags_batch_f64(p->Hc, p->rec[s], p->flags[s], p->B, p->c, p->H, p->W, p->wavelet, p->mode, p->level,
@@ -320,8 +322,8 @@ static int submit_impl(spiht_pipeline *p, const StepPics &in, const StepPics &ou
         CHK(spiht_ctx_wait_event(L, p->ev_c));
         CHK(spiht_ctx_wait_resident(L, ctr, target, 1000));
     }
-    CHK(spiht_decode_lists_flags_batch_i32(L, x_out, p->slot_stride, p->nbytes[s], x_maxn, p->B, p->c, p->H, p->W, p->wavelet,
-                                           p->mode, p->level, p->rec[s], p->flags[s]));
+    CHK(spiht_decode_lists_rows_batch_i32(L, x_out, p->slot_stride, p->nbytes[s], x_maxn, p->B, p->c, p->H, p->W, p->wavelet,
+                                          p->mode, p->level, p->rec[s], p->flags[s], p->rows(s)));
     CHK(spiht_event_record(p->ev_d[s], L));
     p->used[s] = true;
     p->pending = true;

@@ -70,7 +70,7 @@ if ONLY == "idwtf":
     assert other["images_per_launch"] == B
     other["idwt_level1_with_occupancy_words"] = {}
     for bpp in (0.1, 0.5, 1.0):
-        c = counters("idwtf", "false, true>", bpp)
+        c = counters("idwtf", "false, true, 0>", bpp)
         rd, wr = bytes_of(c, level1(c))
         other["idwt_level1_with_occupancy_words"]["%g bpp" % bpp] = {
             "occupied_tiles_fraction": OCC.get(("idwtf", bpp)), "read_bytes_per_image": rd / B, "write_bytes_per_image": wr / B,
@@ -103,7 +103,7 @@ other["idwt_level1"] = {"read_bytes_per_image": rd / B, "write_bytes_per_image":
 # read, so the read side depends on the bit rate
 other["idwt_level1_with_occupancy_words"] = {}
 for bpp in (0.1, 0.5, 1.0):
-    c = counters("idwtf", "false, true>", bpp)  # the instantiation of the persistent kernel that reads the words: level 1 only
+    c = counters("idwtf", "false, true, 0>", bpp)  # the instantiation of the persistent kernel that reads the words: level 1 only
     rd, wr = bytes_of(c, level1(c))
     other["idwt_level1_with_occupancy_words"]["%g bpp" % bpp] = {
         "occupied_tiles_fraction": OCC.get(("idwtf", bpp)), "read_bytes_per_image": rd / B, "write_bytes_per_image": wr / B,

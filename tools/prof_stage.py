@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Run one stage of the hot path in a loop (for rocprofv3 --pmc / --kernel-trace runs).
 usage: prof_stage.py {dwt|idwt|idwtf|pyramid|encode|decode|all} [batch] [iters]
-idwtf: the inverse transform reading the decoder's level-1 occupancy words (the default of the image-level calls); PROF_BPP
-in the environment: bits per pixel of the streams (default: the bench's)."""
+idwtf: the inverse transform reading the decoder's level-1 occupancy words and row words (the default of the image-level calls:
+coarse levels, then level 1 by spiht_idwt_level1_rows_batch_f64); PROF_BPP in the environment: bits per pixel of the streams
+(default: the bench's)."""
 import sys, os
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -45,12 +46,21 @@ d_fl = None
 if stage == "idwtf":
     nw = C.c_uint64()
     _lib.check(L.spiht_l1_flags_words(C_IMG, H, W, codec.wid, codec.mid, LEVEL, C.byref(nw)))
-    d_fl = DeviceArray(ctx, (B, nw.value), np.uint32)
+    d_fl = DeviceArray(ctx, (2, B, nw.value), np.uint32)  # words, then row words: one buffer
+    d_rows = d_fl.ptr + 4 * B * nw.value
     ctx.memset(d_rec.ptr, 0, d_rec.nbytes)
-    _lib.check(L.spiht_decode_lists_flags_batch_i32(ctx.handle, vp(d_out.ptr), codec.slot_stride, vp(d_nbytes.ptr), vp(d_maxn.ptr), B,
-                                                    C_IMG, H, W, codec.wid, codec.mid, LEVEL, vp(d_rec.ptr), vp(d_fl.ptr)))
+    _lib.check(L.spiht_decode_lists_rows_batch_i32(ctx.handle, vp(d_out.ptr), codec.slot_stride, vp(d_nbytes.ptr), vp(d_maxn.ptr), B,
+                                                   C_IMG, H, W, codec.wid, codec.mid, LEVEL, vp(d_rec.ptr), vp(d_fl.ptr), vp(d_rows)))
     ctx.synchronize()
-    print("occupied_tiles_fraction %.5f" % float(d_fl.download().mean()))
+    a_h, a_w = C.c_int64(), C.c_int64()
+    _lib.check(L.spiht_idwt_approx_shape(H, W, codec.wid, LEVEL, C.byref(a_h), C.byref(a_w)))
+    d_ap = DeviceArray(ctx, (B * C_IMG, a_h.value, a_w.value), np.float64)
+    fl = d_fl.download()
+    print("occupied_tiles_fraction %.5f" % float(fl[0].mean()))
+    # bior2.2 stages 14 band rows per tile: the share of them whose bit is set, and of the 3-row windows that hold one
+    bits = (fl[1][..., None] >> np.arange(14, dtype=np.uint32)) & 1
+    wins = (bits[..., :-2] | bits[..., 1:-1] | bits[..., 2:])
+    print("occupied_rows_fraction %.5f occupied_windows_fraction %.5f" % (float(bits.mean()), float(wins.mean())))
 for _ in range(iters):
     if stage in ("dwt", "all"):
         _lib.check(L.spiht_dwt_quant_batch_f64(ctx.handle, vp(d_img.ptr), B, C_IMG, H, W, codec.wid, codec.mid, LEVEL, 50.0, None, vp(d_co.ptr)))
@@ -61,7 +71,9 @@ for _ in range(iters):
     if stage in ("decode", "all"):
         _lib.check(L.spiht_decode_batch_i32(ctx.handle, vp(d_out.ptr), codec.slot_stride, vp(d_nbytes.ptr), vp(d_maxn.ptr), B, C_IMG, g["enc_h"], g["enc_w"], g["ll_h"], g["ll_w"], vp(d_rec.ptr)))
     if stage == "idwtf":
-        _lib.check(L.spiht_dequant_idwt_flags_batch_f64(ctx.handle, vp(d_rec.ptr), vp(d_fl.ptr), B, C_IMG, H, W, codec.wid, codec.mid, LEVEL, 50.0, None, vp(d_img2.ptr)))
+        _lib.check(L.spiht_idwt_coarse_batch_f64(ctx.handle, vp(d_rec.ptr), B, C_IMG, H, W, codec.wid, codec.mid, LEVEL, 50.0, None, vp(d_ap.ptr)))
+        _lib.check(L.spiht_idwt_level1_rows_batch_f64(ctx.handle, vp(d_rec.ptr), vp(d_ap.ptr), vp(d_fl.ptr), vp(d_rows), B, C_IMG, H, W,
+                                                      codec.wid, codec.mid, LEVEL, 50.0, None, vp(d_img2.ptr)))
     if stage in ("idwt", "all"):
         _lib.check(L.spiht_dequant_idwt_batch_f64(ctx.handle, vp(d_rec.ptr), B, C_IMG, H, W, codec.wid, codec.mid, LEVEL, 50.0, None, vp(d_img2.ptr)))
 ctx.synchronize()
