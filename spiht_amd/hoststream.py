@@ -28,7 +28,7 @@ import numpy as np
 from . import _lib, color_models, px
 from .spiht_wrapper import EncodingResult, SpihtSettings, _geometry, _mults_arg, _wavelet_mode_ids
 
-ENCODE, DECODE = 0, 1
+ENCODE, DECODE = _lib.ENUMS["SPIHT_HS_ENCODE"], _lib.ENUMS["SPIHT_HS_DECODE"]
 DEFAULT_TIMEOUT = 30.0  # seconds a generator waits for one step before it gives up (StreamTimeout)
 
 

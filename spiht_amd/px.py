@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import floatpx
+from . import _lib, floatpx
 
 
 @dataclass(frozen=True)
@@ -75,11 +75,13 @@ class Elem:
         return (es, w * c * es, c * es) if len(shape) == 3 else (h * w * c * es, es, w * c * es, c * es)
 
 
-F64 = Elem("f64", np.dtype(np.float64), "f64", None, 0)
+_lib.lib()  # (ENUMS is the header's, read with the library)
+F64 = Elem("f64", np.dtype(np.float64), "f64", None, _lib.ENUMS["SPIHT_HS_F64"])
 F32 = Elem("f32", np.dtype(np.float32), "f32", None, None)
-U8 = Elem("u8", np.dtype(np.uint8), "u8", None, 1)
-U16 = Elem("u16", np.dtype(np.uint16), "u16", None, 2)
-_KINDS = {k: Elem(floatpx.kind_name(k), floatpx.storage_dtype(k), "flt", k, 2 + k) for k in floatpx.KINDS}
+U8 = Elem("u8", np.dtype(np.uint8), "u8", None, _lib.ENUMS["SPIHT_HS_U8"])
+U16 = Elem("u16", np.dtype(np.uint16), "u16", None, _lib.ENUMS["SPIHT_HS_U16"])
+_KINDS = {k: Elem(floatpx.kind_name(k), floatpx.storage_dtype(k), "flt", k, _lib.ENUMS["SPIHT_HS_" + hs])
+          for k, hs in zip(floatpx.KINDS, ("FLT32", "FLT16", "BF16"))}
 _BY_DTYPE = {e.storage: e for e in (F64, F32, U8, U16)}
 
 
@@ -106,7 +108,6 @@ def of_kind_id(kind):
 # ---- the rules of an integer view and of a base address, by dtype (spiht_wrapper re-exports them) ------------------------------
 def _check_int_view(bits, shape, strides, output):
     """check_u8_view / check_u16_view: `bits` 8 or 16"""
-    from . import _lib
     shape, strides = [int(x) for x in shape], [int(x) for x in strides]
     if len(shape) != len(strides) or len(shape) not in (3, 4):
         raise ValueError("%d strides for a %d-dimensional picture" % (len(strides), len(shape)))

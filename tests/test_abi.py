@@ -30,6 +30,146 @@ def test_library_exports_every_declared_symbol():
         assert not hasattr(L, s), "libspiht_hip.so is a diagnostic build (%s)" % s
 
 
+def _header_text():
+    """the header without its comments"""
+    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "spiht_hip.h")).read(), flags=re.S)
+
+
+def _ctypes_class(t):
+    """a ctypes argument or result type in the words of the probe below"""
+    import ctypes as C
+    if t is None:
+        return "void"
+    if t is C.c_char_p:
+        return "str"
+    if t is C.c_void_p:
+        return "ptr"
+    if t in (C.c_float, C.c_double, C.c_longdouble):
+        return "f%d" % C.sizeof(t)
+    return "%s%d" % ("i" if t(-1).value < 0 else "u", C.sizeof(t))
+
+
+PROBE = r"""
+#include <cstddef>
+#include <cstdio>
+#include <type_traits>
+#include "spiht_hip.h"
+template <class T> void cls() {
+    if constexpr (std::is_void<T>::value) printf(" void");
+    else if constexpr (std::is_pointer<T>::value)
+        printf(std::is_same<typename std::remove_cv<typename std::remove_pointer<T>::type>::type, char>::value ? " str" : " ptr");
+    else if constexpr (std::is_floating_point<T>::value) printf(" f%zu", sizeof(T));
+    else if constexpr (std::is_integral<T>::value) printf(" %c%zu", std::is_signed<T>::value ? 'i' : 'u', sizeof(T));
+    else printf(" other");
+}
+template <class R, class... A> void sig(const char *name, R (*)(A...)) {
+    printf("%s", name);
+    cls<R>();
+    (cls<A>(), ...);
+    printf("\n");
+}
+#define FIELD(S, F) printf(" %s:%zu:%zu", #F, offsetof(S, F), sizeof(((S *)0)->F))
+int main() {
+@BODY@
+    return 0;
+}
+"""
+
+
+def test_binding_is_the_compilers_view_of_the_header(tmp_path):
+    """Every entry point's argtypes and restype, and the three Structure classes, against what a C++ compiler makes of the header:
+    a host program deduces each prototype's result and parameters (pointer to char; other pointer; floating point or signed /
+    unsigned integer of a size; void) and prints each struct's size and its fields' offsets and sizes.  It takes the address of
+    every entry point, so it links against the library; it calls none."""
+    import ctypes as C
+    import shutil
+    import subprocess
+    from spiht_amd import _lib
+    L = _lib.lib()
+    declared = _declared_symbols()
+    body = ['    sig("%s", &%s);' % (s, s) for s in declared]
+    for name, cls in _lib.STRUCTS.items():
+        body.append('    printf("struct %s %%zu", sizeof(%s));' % (name, name))
+        body += ["    FIELD(%s, %s);" % (name, f) for f, _ in cls._fields_]
+        body.append('    printf("\\n");')
+    src = tmp_path / "probe.cpp"
+    src.write_text(PROBE.replace("@BODY@", "\n".join(body)))
+    cxx = shutil.which("c++") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+    libdir = os.path.dirname(os.path.abspath(_lib.LIB_PATH))
+    subprocess.check_call([cxx, "-std=c++17", "-O0", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "probe"),
+                           os.path.abspath(_lib.LIB_PATH), "-Wl,-rpath," + libdir, "-Wl,--allow-shlib-undefined"])
+    lines = subprocess.check_output([str(tmp_path / "probe")], text=True).splitlines()
+    seen = {ln.split()[0]: ln.split()[1:] for ln in lines if not ln.startswith("struct ")}
+    assert sorted(seen) == declared and len(declared) >= 192
+    for s in declared:
+        fn = getattr(L, s)
+        assert [_ctypes_class(fn.restype)] + [_ctypes_class(t) for t in fn.argtypes] == seen[s], s
+    structs = {ln.split()[1]: ln.split()[2:] for ln in lines if ln.startswith("struct ")}
+    assert sorted(structs) == sorted(_lib.STRUCTS)
+    for name, cls in _lib.STRUCTS.items():
+        here = [str(C.sizeof(cls))] + ["%s:%d:%d" % (f, getattr(cls, f).offset, getattr(cls, f).size) for f, _ in cls._fields_]
+        assert here == structs[name], name
+
+
+def test_no_entry_point_is_left_unbound():
+    """a function without argtypes takes every Python integer as a 32-bit int: every declared name has a list, empty exactly for
+    the (void) functions, and the result type its prototype says"""
+    import ctypes as C
+    from spiht_amd import _lib
+    L = _lib.lib()
+    text = _header_text()
+    for s in _lib.SYMBOLS:
+        ret, params = re.search(r"(\bconst\s+char\s*\*|\bvoid\b|\bint\b)\s*%s\s*\(([^)]*)\)" % s, text).groups()
+        fn = getattr(L, s)
+        assert isinstance(fn.argtypes, list), s
+        assert (len(fn.argtypes) == 0) == (params.strip() == "void"), s
+        assert len(fn.argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), s
+        assert fn.restype is {"void": None, "int": C.c_int}.get(ret, C.c_char_p), s
+
+
+def test_structures_match_the_header():
+    from spiht_amd import _header, _lib
+    text = open(_lib.HEADER_PATH).read()
+    structs = _header.parse(text)[1]
+    assert sorted(structs) == sorted(_lib.STRUCTS) and len(structs) == 3
+    for name, cls in _lib.STRUCTS.items():
+        assert cls._fields_ == structs[name], name
+        body = re.search(r"typedef\s+struct\s+%s\s*\{([^}]*)\}" % name, _header_text()).group(1)
+        assert [f for f, _ in cls._fields_] == re.findall(r"(\w+)\s*[,;]", body), name
+    _lib.check_structs(structs)
+    # two fields of one struct swapped, in a copy of the text: the check lib() makes refuses the library
+    swapped = text.replace("int64_t n; ", "@").replace("uint64_t nbytes;", "int64_t n;").replace("@", "uint64_t nbytes; ")
+    assert swapped != text and len(swapped) == len(text)
+    with pytest.raises(ImportError, match="HStreamResult"):
+        _lib.check_structs(_header.parse(swapped)[1])
+
+
+def test_constants_are_the_headers_enumerators():
+    from spiht_amd import _lib
+    L = _lib.lib()
+    found = re.findall(r"\b(SPIHT_(?:OK|ERR_\w+|MODE_\w+|HS_\w+))\s*=\s*(\d+)", _header_text())
+    assert len(found) >= 31 and len(set(n for n, _ in found)) == len(found)
+    for name, value in found:
+        assert _lib.ENUMS[name] == int(value), name
+        if name == "SPIHT_OK" or name.startswith("SPIHT_ERR_"):
+            assert getattr(_lib, name[len("SPIHT_"):]) == int(value), name
+    assert len(_lib.ENUMS) == len(found)
+    modes = {n[len("SPIHT_MODE_"):].lower(): int(v) for n, v in found if n.startswith("SPIHT_MODE_")}
+    assert _lib.MODES == modes and len(modes) == 9
+    for name in modes:
+        assert L.spiht_mode_id(name.encode()) == _lib.MODES[name], name
+
+
+def test_parser_refuses_a_type_it_does_not_know():
+    from spiht_amd import _header
+    ok = "int spiht_fine(int64_t n, const char *name, spiht_ctx **out);\n"
+    assert list(_header.parse(ok)[0]) == ["spiht_fine"]
+    for bad in ("int spiht_odd(int64_t n, long double q);", "int spiht_odd(int64_t n, size_t q);", "int spiht_odd(float);",
+                "long double spiht_odd(int n);", "int spiht_odd(unsigned n);"):
+        with pytest.raises(ValueError, match="spiht_odd"):
+            _header.parse(ok + bad)
+
+
 def test_package_surface_matches_reference_init():
     import spiht_amd
     # /root/reference/spiht/__init__.py:1-2

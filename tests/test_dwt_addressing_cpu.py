@@ -1,15 +1,10 @@
 """CPU test: the forward transform launcher's choice between 32-bit offsets into plane descriptors and 64-bit addresses
 (include/spiht_hip.h: spiht_dwt_addr32; common.h: dwt_narrow_ok).  Host arithmetic only -- nothing is allocated."""
-import ctypes as C
 
 
 def _addr32():
     from spiht_amd import _lib
-    L = _lib.lib()
-    i64 = C.c_int64
-    L.spiht_dwt_addr32.argtypes = [i64, i64, i64, i64, i64, i64, C.c_int, i64, i64]
-    L.spiht_dwt_addr32.restype = C.c_int
-    return L.spiht_dwt_addr32
+    return _lib.lib().spiht_dwt_addr32
 
 
 def test_launcher_picks_wide_addressing_where_offsets_do_not_fit():
