@@ -72,7 +72,8 @@ struct Geom {
 
 // List entry: bit 31 = type A (1) / type B (0) for LIS entries; bit 30 = "leaf": a type-A entry whose node
 // has no offspring (the reference still queues it when its parent's B entry fires; it emits a 0 in every
-// plane and can never fire, encoder_decoder.rs:229-239); low 30 bits = linear index k*hw + i*w + j.
+// plane and can never fire, encoder_decoder.rs:229-239); low 30 bits = linear index k*hw + i*w + j.  The rules on these
+// entries -- tree geometry, tokens, appends -- stand once, in list_coder.h (device code: both encoders, the decoder's tree).
 #define ENT_A 0x80000000u
 #define ENT_LEAF 0x40000000u
 #define ENT_IDX 0x3FFFFFFFu

@@ -28,6 +28,7 @@
 // recoverable from the private values -- are replayed in stream order: exact for any byte string, not only for
 // encoder-produced streams.
 #include "common.h"
+#include "list_coder.h"  // the tree rules and the 64-bit shuffle, shared with the encoders
 
 #ifndef DEC_NW
 #define DEC_NW 12           // wavefronts per workgroup
@@ -193,28 +194,6 @@ __device__ __forceinline__ int32_t set_bit_i32(int32_t x, uint32_t n, uint32_t b
     return -(int32_t)a;
 }
 
-__device__ __forceinline__ void decomp(const Geom &g, uint32_t idx, uint32_t &k, uint32_t &i, uint32_t &j) {
-    k = fdiv(idx, g.div_hw);
-    uint32_t r = idx - k * g.hw;
-    i = fdiv(r, g.div_w);
-    j = r - i * (uint32_t)g.w;
-}
-
-__device__ __forceinline__ uint32_t child_base(const Geom &g, uint32_t k, uint32_t i, uint32_t j, uint32_t &r, uint32_t &cc) {
-    if (i < (uint32_t)g.ll_h && j < (uint32_t)g.ll_w) {
-        r = (i & 1u) * (uint32_t)g.ll_h + (i & ~1u);
-        cc = (j & 1u) * (uint32_t)g.ll_w + (j & ~1u);
-    } else {
-        r = 2 * i;
-        cc = 2 * j;
-    }
-    return k * g.hw + r * (uint32_t)g.w + cc;
-}
-
-__device__ __forceinline__ uint32_t make_a_entry(uint32_t idx, uint32_t ci, uint32_t cj, uint32_t H, uint32_t W) {
-    return idx | ENT_A | ((2 * ci + 1 < H && 2 * cj + 1 < W) ? 0u : ENT_LEAF);
-}
-
 // Token-start mask of a LIP-pass window (tokens '0' | '1 s').  The pass owns bits >= pos of the window.
 // cin: bit `pos` is the pending sign bit of the previous window's last token.  cout: the token starting at
 // bit 63 is '1' and its sign bit is the next window's bit 0.  Runs of ones pair up from their first bit, so
@@ -318,13 +297,6 @@ __device__ __forceinline__ uint32_t stream_word(const BitSrc &bs, uint32_t wi) {
 // 64-bit stream word `w64` (two 32-bit words), zero at and past nbits
 __device__ __forceinline__ uint64_t stream_word64(const BitSrc &bs, uint32_t w64) {
     return (uint64_t)stream_word(bs, 2 * w64) | ((uint64_t)stream_word(bs, 2 * w64 + 1) << 32);
-}
-
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int o) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = (uint32_t)__shfl_up((int)lo, o);
-    hi = (uint32_t)__shfl_up((int)hi, o);
-    return ((uint64_t)hi << 32) | lo;
 }
 
 // exclusive prefix sum of a packed 64-bit value over the whole workgroup (two barriers)
@@ -696,7 +668,7 @@ __device__ __forceinline__ void work_lis(DecShared &sh, const DecArgs &a, const 
                 lipm = ~sigm & 15u;
                 nLSP = (uint32_t)__popc(sigm);
                 nLIP = 4u - nLSP;
-                nQ = (4 * ii + 3 < H && 4 * jj + 3 < W) ? 1u : 0u;  // :411-414
+                nQ = has_grandchildren(ii, jj, H, W) ? 1u : 0u;  // :411-414
             } else {
                 bool stop = false;
                 uint32_t o = 1;
@@ -704,7 +676,7 @@ __device__ __forceinline__ void work_lis(DecShared &sh, const DecArgs &a, const 
                 for (int q = 0; q < 4; q++) {
                     if (!stop) {
                         if (META) {
-                            const uint32_t ch = (cb + (q >> 1) * W + (q & 1)) | cf;
+                            const uint32_t ch = offspring(cb, q, W) | cf;
                             tr_put(tr, mypos + o, 3, n, ch);                                            // action 3 (:745)
                             if (o < avail && ((bits >> o) & 1u)) tr_put(tr, mypos + o + 1, 4, n, ch);  // action 4 (:749)
                         }
@@ -724,7 +696,7 @@ __device__ __forceinline__ void work_lis(DecShared &sh, const DecArgs &a, const 
                 }
                 nLSP = (uint32_t)__popc(sigm);
                 nLIP = (uint32_t)__popc(lipm);
-                if (!stop) nQ = (4 * ii + 3 < H && 4 * jj + 3 < W) ? 1u : 0u;  // :411-414
+                if (!stop) nQ = has_grandchildren(ii, jj, H, W) ? 1u : 0u;  // :411-414
             }
         }
     }
@@ -773,6 +745,7 @@ __device__ __forceinline__ void work_lis(DecShared &sh, const DecArgs &a, const 
             // fired leaf: dropped
         } else if (!isA) {
             const uint32_t oq = b_nxt + mbcnt(mQ1) + 4u * mbcnt(mQ4);
+            // list_coder.h's store_a_entries, written out: through it one s_and_b64 of k_decode gets its operands swapped
             nxt[oq] = make_a_entry(cb, cr, ccol, H, W) | cf;
             nxt[oq + 1] = make_a_entry(cb + 1, cr, ccol + 1, H, W) | cf;
             nxt[oq + 2] = make_a_entry(cb + W, cr + 1, ccol, H, W) | cf;
@@ -784,7 +757,7 @@ __device__ __forceinline__ void work_lis(DecShared &sh, const DecArgs &a, const 
                 // every offspring goes to one of the two lists: one store of its index to the address picked, the value behind it
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
-                    const uint32_t ci = cb + (q >> 1) * W + (q & 1);
+                    const uint32_t ci = offspring(cb, q, W);
                     const bool sg = (sigm >> q) & 1u;
                     uint32_t *dst = sg ? lsp_idx + os : lip + ol;
                     *dst = ci;
@@ -795,7 +768,7 @@ __device__ __forceinline__ void work_lis(DecShared &sh, const DecArgs &a, const 
             } else
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                const uint32_t ci = (cb + (q >> 1) * W + (q & 1)) | cf;
+                const uint32_t ci = offspring(cb, q, W) | cf;
                 if (sigm & (1u << q)) {
                     lsp_idx[os] = ci;
                     lsp_val[os] = ((signm >> q) & 1u) ? base_val : -base_val;

@@ -26,6 +26,7 @@
 #pragma once
 #include "common.h"
 #include "floatpx.h"
+#include "list_coder.h"  // iabs_u
 #include <stdlib.h>
 #include <string.h>
 
@@ -159,7 +160,6 @@ __device__ __forceinline__ int32_t quant(double v, double m, double q, bool has_
     v = v * q;
     return (int32_t)v;
 }
-__device__ __forceinline__ uint32_t iabs_u(int32_t x) { return (uint32_t)(x < 0 ? -x : x); }
 __device__ __forceinline__ double dequant(int32_t r, double m, double q, bool has_m) {
     double v = (double)r;
     if (has_m) v = v / m;

@@ -13,48 +13,18 @@
 //
 // Integer/bit work, latency- and LDS-bound; no roofline claim.
 #include "common.h"
-#include "encode_common.h"
+#include "list_coder.h"
 
 #ifndef ENC_BLOCK
 #define ENC_BLOCK 1024
 #endif
 
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int o) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = (uint32_t)__shfl_up((int)lo, o);
-    hi = (uint32_t)__shfl_up((int)hi, o);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 template <int BLOCK>
 struct EncShared {
     static constexpr int WB = (9 * BLOCK + 31) / 32 + 2;
     uint32_t wbuf[2][WB];
-    uint64_t part[2][BLOCK / 64];
+    uint64_t part[2][BLOCK / 64];  // block_exscan_packed
 };
-
-// packed exclusive scan over the block; one __syncthreads; `par` alternates the partial buffer
-template <int BLOCK>
-__device__ __forceinline__ uint64_t block_exscan(uint64_t v, uint64_t &total, EncShared<BLOCK> &sh, int par) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint64_t t = shfl_up_u64(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) sh.part[par][wave] = inc;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int wv = 0; wv < BLOCK / 64; wv++) {
-        uint64_t p = sh.part[par][wv];
-        if (wv < wave) pre += p;
-        tot += p;
-    }
-    total = tot;
-    return pre + inc - v;
-}
 
 // Emit this thread's `nb` bits (LSB first) at block-relative bit offset `off`; `tot` = bits of the whole
 // block this iteration.  Stream position `bitpos` is advanced; bits at or past max_bits are dropped.
@@ -66,16 +36,7 @@ __device__ __forceinline__ void emit_bits(uint32_t bits, uint32_t nb, uint32_t o
     const uint32_t shft = (uint32_t)(bitpos & 31);
     const uint64_t rem = max_bits - bitpos;  // bitpos < max_bits on entry
     const uint32_t totv = (uint64_t)tot < rem ? tot : (uint32_t)rem;
-    if (nb && off < totv) {
-        uint32_t nbv = (off + nb <= totv) ? nb : (totv - off);
-        uint32_t v = bits & ((1u << nbv) - 1u);
-        uint32_t p = shft + off;
-        uint32_t wi = p >> 5, bo = p & 31;
-        if (v) {
-            atomicOr(&sh.wbuf[par][wi], v << bo);
-            if (bo + nbv > 32) atomicOr(&sh.wbuf[par][wi + 1], v >> (32 - bo));
-        }
-    }
+    stage_bits(sh.wbuf[par], bits, nb, off, totv, shft);
     __syncthreads();
     const uint32_t endb = shft + totv;
     const uint32_t nfull = endb >> 5;
@@ -120,19 +81,18 @@ void k_encode(EncArgs a) {
             for (uint64_t t = tid; t < a.slot_stride / 4; t += BLOCK) zw[t] = 0;
             __syncthreads();
         }
-        const int32_t *__restrict__ X = a.x + (size_t)b * g.n;
-        const uint8_t *__restrict__ DM = a.dmsb + (size_t)b * g.n;
-        const uint8_t *__restrict__ LM = a.lmsb + (size_t)b * g.n;
-        uint32_t *__restrict__ outw = reinterpret_cast<uint32_t *>(a.out + (size_t)b * a.slot_stride);
-        const uint64_t capb = a.slot_stride * 8;  // never write past the slot
-        const uint64_t max_bits = a.max_bits < capb ? a.max_bits : capb;
+        const EncImage im = enc_image(a, b);
+        const int32_t *__restrict__ X = im.X;
+        const uint8_t *__restrict__ DM = im.DM;
+        const uint8_t *__restrict__ LM = im.LM;
+        uint32_t *__restrict__ outw = im.outw;
+        const uint64_t max_bits = im.max_bits;
 
         for (uint32_t t = tid; t < (uint32_t)EncShared<BLOCK>::WB; t += BLOCK) { sh.wbuf[0][t] = 0; sh.wbuf[1][t] = 0; }
         __syncthreads();
 
-        const uint32_t maxabs = a.maxabs[b];
-        const int max_n = start_plane(maxabs, a.log2_thresh);
-        bool bad = maxabs >= (1u << 30);
+        uint32_t maxabs; bool bad;
+        const int max_n = enc_first_plane(a, b, maxabs, bad);
 
         uint32_t *lip = lipA, *lipn = lipB;
         uint32_t *lis = q0, *qa = q1, *qb = q2;
@@ -141,29 +101,12 @@ void k_encode(EncArgs a) {
         int par = 0;     // scan partial buffer parity
         int wpar = 0;    // bit staging buffer parity
 
-        // ---- initial LIP / LIS (encoder_decoder.rs:169-190): i, j, then channel innermost ----
-        const uint32_t nroot = (uint32_t)(g.ll_h * g.ll_w * g.c);
-        for (uint32_t base = 0; base < nroot; base += BLOCK) {
-            uint32_t t = base + tid;
-            bool act = t < nroot;
-            uint32_t k = 0, i = 0, j = 0;
-            if (act) {
-                uint32_t ij = t / (uint32_t)g.c;
-                k = t - ij * (uint32_t)g.c;
-                i = ij / (uint32_t)g.ll_w;
-                j = ij - i * (uint32_t)g.ll_w;
-            }
-            uint32_t idx = k * g.hw + i * W + j;
-            bool inlis = act && (((i | j) & 1u) != 0);
-            uint64_t tot;
-            uint64_t ex = block_exscan<BLOCK>(inlis ? 1ull : 0ull, tot, sh, par);
-            par ^= 1;
-            if (act && t < a.caps.lip) lip[t] = idx;
-            if (inlis && lis_len + (uint32_t)ex < a.caps.lis) lis[lis_len + (uint32_t)ex] = idx | ENT_A;
-            lis_len += (uint32_t)tot;
-        }
-        lip_len = nroot;
-        if (lip_len > a.caps.lip || lis_len > a.caps.lis) bad = true;
+        // ---- initial LIP / LIS (encoder_decoder.rs:169-190) ----
+        if (!seed_lists<BLOCK>(g, a.caps, lip, lis, lip_len, lis_len, [&](uint64_t v, uint64_t &tot) {
+                const uint64_t ex = block_exscan_packed(v, tot, sh, par);
+                par ^= 1;
+                return ex;
+            })) bad = true;
 
         bool done = bad || (max_bits == 0);
         for (int n = max_n; !done; --n) {
@@ -185,14 +128,15 @@ void k_encode(EncArgs a) {
                     e0 = lip[r];
                 }
                 const int32_t x0 = act0 ? X[e0] : 0, x1 = act1 ? X[e1] : 0;
-                const bool sig0 = act0 && iabs_u(x0) >= T, sig1 = act1 && iabs_u(x1) >= T;
-                const uint32_t b0 = sig0 ? (1u | ((x0 >= 0) ? 2u : 0u)) : 0u, b1 = sig1 ? (1u | ((x1 >= 0) ? 2u : 0u)) : 0u;
+                const bool s0 = is_sig(x0, T), s1 = is_sig(x1, T);  // (act0 && is_sig(x0, T): two SGPR spills fewer, so not that wording)
+                const bool sig0 = act0 && s0, sig1 = act1 && s1;
+                const uint32_t b0 = sig0 ? sig_token(x0) : 0u, b1 = sig1 ? sig_token(x1) : 0u;
                 const uint32_t nb0 = act0 ? (sig0 ? 2u : 1u) : 0u, nb1 = act1 ? (sig1 ? 2u : 1u) : 0u;
                 const uint32_t ns = (sig0 ? 1u : 0u) + (sig1 ? 1u : 0u);
                 const uint32_t nn = ((act0 && !sig0) ? 1u : 0u) + ((act1 && !sig1) ? 1u : 0u);
                 uint64_t pk = (uint64_t)(nb0 + nb1) | ((uint64_t)ns << 16) | ((uint64_t)nn << 32);
                 uint64_t tot;
-                uint64_t ex = block_exscan<BLOCK>(pk, tot, sh, par);
+                uint64_t ex = block_exscan_packed(pk, tot, sh, par);
                 par ^= 1;
                 uint32_t totLSP = (uint32_t)(tot >> 16) & 0xffffu;
                 if (lsp_len + totLSP > a.caps.lsp) { bad = true; done = true; break; }
@@ -233,23 +177,10 @@ void k_encode(EncArgs a) {
                         if (isA) {
                             int32_t xc[4];
                             xc[0] = X[cb]; xc[1] = X[cb + 1]; xc[2] = X[cb + W]; xc[3] = X[cb + W + 1];
-                            uint32_t o = 1;
-#pragma unroll
-                            for (int q = 0; q < 4; q++) {
-                                bool s = iabs_u(xc[q]) >= T;
-                                if (s) {
-                                    bits |= (1u << o) | ((xc[q] >= 0 ? 1u : 0u) << (o + 1));
-                                    o += 2;
-                                    sigm |= 1u << q;
-                                } else {
-                                    o += 1;
-                                }
-                            }
-                            nb = o;
+                            bits = token_a(xc, T, nb, sigm);
                             nLSP = (uint32_t)__popc(sigm);
                             nLIP = 4 - nLSP;
-                            // has_descendents_past_offspring (encoder_decoder.rs:7-12), raw coordinates
-                            nQ = (4 * i + 3 < H && 4 * j + 3 < W) ? 1u : 0u;
+                            nQ = has_grandchildren(i, j, H, W) ? 1u : 0u;
                         } else {
                             nQ = 4;
                         }
@@ -259,7 +190,7 @@ void k_encode(EncArgs a) {
                     uint64_t pk = (uint64_t)nb | ((uint64_t)nQ << 14) | ((uint64_t)nR << 27) | ((uint64_t)nLIP << 38) |
                                   ((uint64_t)nLSP << 51);
                     uint64_t tot;
-                    uint64_t ex = block_exscan<BLOCK>(pk, tot, sh, par);
+                    uint64_t ex = block_exscan_packed(pk, tot, sh, par);
                     par ^= 1;
                     uint32_t tQ = (uint32_t)(tot >> 14) & 0x1fffu, tR = (uint32_t)(tot >> 27) & 0x7ffu;
                     uint32_t tLIP = (uint32_t)(tot >> 38) & 0x1fffu, tLSP = (uint32_t)(tot >> 51) & 0x1fffu;
@@ -270,17 +201,9 @@ void k_encode(EncArgs a) {
                         if (isA) {
                             uint32_t ol = lip_len + ((uint32_t)(ex >> 38) & 0x1fffu);
                             uint32_t os = lsp_len + ((uint32_t)(ex >> 51) & 0x1fffu);
-#pragma unroll
-                            for (int q = 0; q < 4; q++) {
-                                uint32_t ci = cb + (q >> 1) * W + (q & 1);
-                                if (sigm & (1u << q)) lsp[os++] = ci; else lip[ol++] = ci;
-                            }
-                            if (nQ) nxt[oq] = idx;  // type B
+                            append_fired_a(idx, cb, W, sigm, nQ, lsp, os, lip, ol, nxt, oq);
                         } else {
-                            nxt[oq] = make_a_entry(cb, cr, ccol, H, W);
-                            nxt[oq + 1] = make_a_entry(cb + 1, cr, ccol + 1, H, W);
-                            nxt[oq + 2] = make_a_entry(cb + W, cr + 1, ccol, H, W);
-                            nxt[oq + 3] = make_a_entry(cb + W + 1, cr + 1, ccol + 1, H, W);
+                            store_a_entries(nxt, oq, cb, cr, ccol, H, W, 0u);
                         }
                     } else if (act) {
                         ret[ret_len + ((uint32_t)(ex >> 27) & 0x7ffu)] = e;
@@ -311,7 +234,7 @@ void k_encode(EncArgs a) {
                 } else if (act0) {
                     e0 = lsp[r];
                 }
-                const uint32_t bit0 = act0 ? ((iabs_u(X[e0]) >> n) & 1u) : 0u, bit1 = act1 ? ((iabs_u(X[e1]) >> n) & 1u) : 0u;
+                const uint32_t bit0 = act0 ? refine_bit(X[e0], n) : 0u, bit1 = act1 ? refine_bit(X[e1], n) : 0u;
                 const uint32_t cnt = (lsp_len0 - base) < 2u * BLOCK ? (lsp_len0 - base) : 2u * BLOCK;
                 emit_bits<BLOCK>(bit0 | (bit1 << 1), (act0 ? 1u : 0u) + (act1 ? 1u : 0u), 2 * tid, cnt, bitpos, max_bits, outw, sh,
                                  wpar);
@@ -325,10 +248,7 @@ void k_encode(EncArgs a) {
         __syncthreads();
         if (tid == 0) {
             if (bitpos & 31) outw[bitpos >> 5] = sh.wbuf[wpar][0];
-            a.out_nbits[b] = bitpos;
-            a.out_maxn[b] = (uint8_t)max_n;
-            if (bad) atomicOr(a.err, maxabs >= (1u << 30) ? 2u : 1u);
-            if (a.max_bits > capb && bitpos >= capb) atomicOr(a.err, 4u);
+            enc_report(a, b, im, maxabs, max_n, bitpos, bad);
         }
         __syncthreads();
     }

@@ -24,7 +24,7 @@
 // whose group gave up, one workgroup each, from scratch -- the call never fails for lack of residency (the reference's
 // encode never fails on valid input, src/lib.rs:24-32), it only takes the single-workgroup time.
 #include "common.h"
-#include "encode_common.h"
+#include "list_coder.h"
 
 #define WB_BLOCK 1024
 #ifndef WIDE_U
@@ -53,34 +53,10 @@ struct WideShared {
     static constexpr int WB = (9 * WIDE_U * WB_BLOCK + 31) / 32 + 3;  // (2 * WIDE_V * WB_BLOCK bits fit as well)
     static_assert(9 * WIDE_U >= 2 * WIDE_V, "staging buffer: the larger of the two chunk kinds");
     uint32_t wbuf[WB];
-    uint64_t part[2][WB_BLOCK / 64];
+    uint64_t part[2][WB_BLOCK / 64];  // block_exscan_packed
     uint32_t E[4];        // the chunk's exclusive prefix, from wave 0 to the block
     uint32_t bc[12];      // broadcasts of thread 0
 };
-
-// packed exclusive scan over the block; one __syncthreads; `par` alternates the partial buffer
-__device__ __forceinline__ uint64_t wide_exscan(uint64_t v, uint64_t &total, WideShared &sh, int par) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t lo = (uint32_t)inc, hi = (uint32_t)(inc >> 32);
-        lo = (uint32_t)__shfl_up((int)lo, o);
-        hi = (uint32_t)__shfl_up((int)hi, o);
-        if (lane >= o) inc += ((uint64_t)hi << 32) | lo;
-    }
-    if (lane == 63) sh.part[par][wave] = inc;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int wv = 0; wv < WB_BLOCK / 64; wv++) {
-        const uint64_t p = sh.part[par][wv];
-        if (wv < wave) pre += p;
-        tot += p;
-    }
-    total = tot;
-    return pre + inc - v;
-}
 
 // wave 0 of the workgroup: exclusive prefix E of chunk c of pass `tag` over the chunks before it; publishes this chunk's
 // aggregate A and its inclusive prefix.  false: the wait for a predecessor ran out (wide_wait_ok).
@@ -160,19 +136,18 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
     uint32_t *const lipbuf[2] = {a.lip0 + (size_t)grp * a.caps.lip, a.lip1 + (size_t)grp * a.caps.lip};
     uint32_t *const lsp = a.lsp + (size_t)grp * a.caps.lsp;
     uint32_t *const qbuf[3] = {a.lis0 + (size_t)grp * a.caps.lis, a.lis1 + (size_t)grp * a.caps.lis, a.lis2 + (size_t)grp * a.caps.lis};
-    const int32_t *__restrict__ X = a.x + (size_t)b * g.n;
-    const uint8_t *__restrict__ DM = a.dmsb + (size_t)b * g.n;
-    const uint8_t *__restrict__ LM = a.lmsb + (size_t)b * g.n;
-    uint32_t *outw = reinterpret_cast<uint32_t *>(a.out + (size_t)b * a.slot_stride);
-    const uint64_t capb = a.slot_stride * 8;  // never write past the slot
-    const uint64_t max_bits = a.max_bits < capb ? a.max_bits : capb;
+    const EncImage im = enc_image(a, b);
+    const int32_t *__restrict__ X = im.X;
+    const uint8_t *__restrict__ DM = im.DM;
+    const uint8_t *__restrict__ LM = im.LM;
+    uint32_t *outw = im.outw;
+    const uint64_t max_bits = im.max_bits;
 
     for (uint32_t t = tid; t < (uint32_t)WideShared::WB; t += BLOCK) sh.wbuf[t] = 0;
     __syncthreads();
 
-    const uint32_t maxabs = a.maxabs[b];
-    const int max_n = start_plane(maxabs, a.log2_thresh);
-    bool bad = maxabs >= (1u << 30);
+    uint32_t maxabs; bool bad;
+    const int max_n = enc_first_plane(a, b, maxabs, bad);
 
     // the coder's state: the same values in every workgroup that has joined
     uint32_t lipr = 0;            // lipbuf[lipr] is the LIP
@@ -223,15 +198,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
     };
     // a token's bits into the LDS staging buffer (chunk bit 0 at LDS bit shft), cut at totv
     auto stage = [&](uint32_t bits, uint32_t nb, uint32_t off, uint32_t totv, uint32_t shft) {
-        if (nb && off < totv) {
-            const uint32_t nbv = (off + nb <= totv) ? nb : (totv - off);
-            const uint32_t v = bits & ((1u << nbv) - 1u);  // nb <= 16
-            const uint32_t p = shft + off, wi = p >> 5, bo = p & 31;
-            if (v) {
-                atomicOr(&sh.wbuf[wi], v << bo);
-                if (bo + nbv > 32) atomicOr(&sh.wbuf[wi + 1], v >> (32 - bo));
-            }
-        }
+        stage_bits(sh.wbuf, bits, nb, off, totv, shft);
     };
     // ... and out: whole words stored, the first / last word shared with the neighbouring chunks ORed
     auto flush = [&](uint64_t bit0, uint32_t totv) {
@@ -272,30 +239,12 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
     };
 
     if (wg == 0) {
-        // ---- initial LIP / LIS (encoder_decoder.rs:169-190): i, j, then channel innermost ----
-        uint32_t *lip = lipbuf[0], *lis = qbuf[0];
-        const uint32_t nroot = (uint32_t)(g.ll_h * g.ll_w * g.c);
-        for (uint32_t base = 0; base < nroot; base += BLOCK) {
-            const uint32_t t = base + tid;
-            const bool act = t < nroot;
-            uint32_t k = 0, i = 0, j = 0;
-            if (act) {
-                const uint32_t ij = t / (uint32_t)g.c;
-                k = t - ij * (uint32_t)g.c;
-                i = ij / (uint32_t)g.ll_w;
-                j = ij - i * (uint32_t)g.ll_w;
-            }
-            const uint32_t idx = k * g.hw + i * W + j;
-            const bool inlis = act && (((i | j) & 1u) != 0);
-            uint64_t tot;
-            const uint64_t ex = wide_exscan(inlis ? 1ull : 0ull, tot, sh, par);
-            par ^= 1;
-            if (act && t < a.caps.lip) lip[t] = idx;
-            if (inlis && lis_len + (uint32_t)ex < a.caps.lis) lis[lis_len + (uint32_t)ex] = idx | ENT_A;
-            lis_len += (uint32_t)tot;
-        }
-        lip_len = nroot;
-        if (lip_len > a.caps.lip || lis_len > a.caps.lis) bad = true;
+        // ---- initial LIP / LIS (encoder_decoder.rs:169-190) ----
+        if (!seed_lists<BLOCK>(g, a.caps, lipbuf[0], qbuf[0], lip_len, lis_len, [&](uint64_t v, uint64_t &tot) {
+                const uint64_t ex = block_exscan_packed(v, tot, sh, par);
+                par ^= 1;
+                return ex;
+            })) bad = true;
         done = bad || (max_bits == 0);
         __syncthreads();
     } else {
@@ -368,8 +317,8 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
 #pragma unroll
                 for (uint32_t u = 0; u < V; u++) {
                     if (u < nact) {
-                        if (iabs_u(x[u]) >= T) {
-                            bits |= (1u | ((x[u] >= 0) ? 2u : 0u)) << nb;
+                        if (is_sig(x[u], T)) {
+                            bits |= sig_token(x[u]) << nb;
                             nb += 2;
                             sgm |= 1u << u;
                         } else {
@@ -379,7 +328,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
                 }
                 const uint32_t ns = (uint32_t)__popc(sgm);
                 uint64_t tot;
-                const uint32_t pS = (uint32_t)wide_exscan((uint64_t)ns, tot, sh, par);
+                const uint32_t pS = (uint32_t)block_exscan_packed((uint64_t)ns, tot, sh, par);
                 par ^= 1;
                 const uint32_t A[4] = {(uint32_t)tot, 0u, 0u, 0u};
                 uint32_t E[4];
@@ -471,8 +420,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
                             cb[u] = child_base(g, k, i, j, cr[u], ccol[u]);
                             if (firedA[u]) {
                                 xc[u][0] = X[cb[u]]; xc[u][1] = X[cb[u] + 1]; xc[u][2] = X[cb[u] + W]; xc[u][3] = X[cb[u] + W + 1];
-                                // has_descendents_past_offspring (encoder_decoder.rs:7-12), raw coordinates
-                                qa1[u] = (4 * i + 3 < H && 4 * j + 3 < W) ? 1u : 0u;
+                                qa1[u] = has_grandchildren(i, j, H, W) ? 1u : 0u;
                             }
                         }
                     }
@@ -482,17 +430,9 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
                     for (uint32_t u = 0; u < U; u++) {
                         bits[u] = 0; nb[u] = u < nact ? 1u : 0u; sigm[u] = 0;
                         if (firedA[u]) {
-                            uint32_t o = 1, bb = 1u;
+                            uint32_t o = 1, bb = 1u;  // token_a (list_coder.h), its loop written out: see there
 #pragma unroll
-                            for (int q = 0; q < 4; q++) {
-                                if (iabs_u(xc[u][q]) >= T) {
-                                    bb |= (1u << o) | ((xc[u][q] >= 0 ? 1u : 0u) << (o + 1));
-                                    o += 2;
-                                    sigm[u] |= 1u << q;
-                                } else {
-                                    o += 1;
-                                }
-                            }
+                            for (int q = 0; q < 4; q++) token_a_offspring(xc[u][q], T, q, bb, o, sigm[u]);
                             bits[u] = bb;
                             nb[u] = o;
                             tS += (uint32_t)__popc(sigm[u]);
@@ -506,7 +446,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
                     // S <= 4 CH, FA, FB, QA <= CH: 16 bits each
                     const uint64_t pk = (uint64_t)tS | ((uint64_t)tFA << 16) | ((uint64_t)tFB << 32) | ((uint64_t)tQA << 48);
                     uint64_t tot;
-                    const uint64_t ex = wide_exscan(pk, tot, sh, par);
+                    const uint64_t ex = block_exscan_packed(pk, tot, sh, par);
                     par ^= 1;
                     const uint32_t pS = (uint32_t)ex & 0xffffu, pFA = (uint32_t)(ex >> 16) & 0xffffu, pFB = (uint32_t)(ex >> 32) & 0xffffu,
                                    pQA = (uint32_t)(ex >> 48) & 0xffffu;
@@ -530,17 +470,10 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
 #pragma unroll
                             for (uint32_t u = 0; u < U; u++) {
                                 if (firedA[u]) {
-#pragma unroll
-                                    for (int q = 0; q < 4; q++) {
-                                        const uint32_t ci = cb[u] + (q >> 1) * W + (q & 1);
-                                        if (sigm[u] & (1u << q)) lsp[os++] = ci; else lip[ol++] = ci;
-                                    }
-                                    if (qa1[u]) nxt[oq++] = e[u] & ENT_IDX;  // type B
+                                    append_fired_a(e[u] & ENT_IDX, cb[u], W, sigm[u], qa1[u], lsp, os, lip, ol, nxt, oq);
+                                    os += (uint32_t)__popc(sigm[u]); ol += 4u - (uint32_t)__popc(sigm[u]); oq += qa1[u];
                                 } else if (firedB[u]) {
-                                    nxt[oq] = make_a_entry(cb[u], cr[u], ccol[u], H, W);
-                                    nxt[oq + 1] = make_a_entry(cb[u] + 1, cr[u], ccol[u] + 1, H, W);
-                                    nxt[oq + 2] = make_a_entry(cb[u] + W, cr[u] + 1, ccol[u], H, W);
-                                    nxt[oq + 3] = make_a_entry(cb[u] + W + 1, cr[u] + 1, ccol[u] + 1, H, W);
+                                    store_a_entries(nxt, oq, cb[u], cr[u], ccol[u], H, W, 0u);
                                     oq += 4;
                                 } else if (u < nact) {
                                     ret[orr++] = e[u];
@@ -598,7 +531,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
                 }
                 uint32_t bits = 0;
 #pragma unroll
-                for (uint32_t u = 0; u < V; u++) bits |= (u < nact ? ((iabs_u(X[e[u]]) >> n) & 1u) : 0u) << u;
+                for (uint32_t u = 0; u < V; u++) bits |= (u < nact ? refine_bit(X[e[u]], n) : 0u) << u;
                 const uint64_t rem = max_bits - bit0;
                 const uint32_t totv = (uint64_t)cnt < rem ? cnt : (uint32_t)rem;
                 stage(bits, nact, t0 < cnt ? t0 : cnt, totv, (uint32_t)(bit0 & 31));
@@ -621,10 +554,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_encode_wide(EncArgs a, WideArgs w)
             }
             const uint32_t cb_ = wu_load(&ctl->bad);
             if (!(cb_ & 2u)) {  // (a group that gave up reports nothing: k_encode<redo> codes the image and reports for it)
-                a.out_nbits[b] = bitpos;
-                a.out_maxn[b] = (uint8_t)max_n;
-                if (bad || (cb_ & 1u)) atomicOr(a.err, maxabs >= (1u << 30) ? 2u : 1u);
-                if (a.max_bits > capb && bitpos >= capb) atomicOr(a.err, 4u);
+                enc_report(a, b, im, maxabs, max_n, bitpos, bad || (cb_ & 1u));
             }
         }
     }

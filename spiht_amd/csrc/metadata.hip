@@ -8,6 +8,7 @@
 // replays that node's few writes in stream order (k_meta_fold).  This is the sequential semantics of the
 // reference for any byte string, not only for encoder-produced streams.
 #include "common.h"
+#include "list_coder.h"  // decomp
 #include <algorithm>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -42,10 +43,8 @@ __device__ __forceinline__ void meta_row(const Geom &g, const int32_t *slices, i
                                          int4 &r1) {
     const uint32_t idx = e & ENT_IDX_META;
     const uint32_t filter = (e >> ENT_FILT_SHIFT) & 3u;
-    const uint32_t k = fdiv(idx, g.div_hw);
-    const uint32_t rem = idx - k * g.hw;
-    const uint32_t i = fdiv(rem, g.div_w);
-    const uint32_t j = rem - i * (uint32_t)g.w;
+    uint32_t k, i, j;
+    decomp(g, idx, k, i, j);
     // generation = halvings until the index-tree ancestor is a root (the tree is index based outside LL)
     uint32_t t = 0, ii = i, jj = j;
     while (!(ii < (uint32_t)g.ll_h && jj < (uint32_t)g.ll_w)) { ii >>= 1; jj >>= 1; t++; }

@@ -20,10 +20,10 @@
 // `round` d >= 3 handles the nodes of depth exactly d, whose offspring were finished before.
 // HBM-bound: 4 B read per coefficient, ~1/4 + 1/16 B written.
 #include "common.h"
+#include "list_coder.h"  // iabs_u
 #include <string.h>
 
 __device__ __forceinline__ uint32_t msb_code(uint32_t v) { return v ? 32u - (uint32_t)__clz((int)v) : 0u; }
-__device__ __forceinline__ uint32_t iabs_u(int32_t x) { return x < 0 ? 0u - (uint32_t)x : (uint32_t)x; }  // (INT32_MIN -> 2^31, no signed overflow)
 
 // max |x| per image (encoder_decoder.rs:165).  grid: (blocks, B)
 __global__ __launch_bounds__(256) void k_absmax(const int32_t *__restrict__ x, uint32_t n, uint32_t *__restrict__ maxabs) {
