@@ -1173,6 +1173,43 @@ int spiht_tile_cut_set(spiht_ctx *ctx, int es, int64_t P, int64_t c, int64_t th,
 int spiht_tile_paste_set(spiht_ctx *ctx, int es, int64_t B, int64_t c, int64_t rh, int64_t rw, int64_t th, int64_t tw,
                          const spiht_tileset_item *items, const void *d_tiles, int64_t S);
 
+/* ---------------------------------------------------------------------------------------
+ * Resized crops (csrc/resample.hip): a box of any size of each of B pictures of a set, resampled to ONE size [c, oh, ow] straight
+ * from the dense batch of the decoded float64 tiles -- the paste above with arithmetic: the antialiased triangle filter
+ * ("bilinear, antialias"), a mirror left to right, (v - mean) / std per channel and ONE rounding to the output's element.  The
+ * rule is spiht_amd/resample.py: resize_rule.  Additions only: the ABI version stays at 2.
+ * The weights are the CALLER's (resample.py: axis_table, the mirror applied by reversing the rows of the column table): the
+ * kernel computes none, it multiplies and adds in the rule's order -- columns first, then rows; acc = s[start] * w[0], then
+ * acc = acc + s[start + k] * w[k], every product and sum rounded on its own -- normalises with IEEE's division and converts.
+ *   elem         the output's element, SPIHT_HS_F64 .. SPIHT_HS_BF16: float64; 8 / 16 bits by the decoder's conversion (clip to
+ *                [0, 1], times 255 / 65535, truncate); a float kind rounded once, to nearest even (the *_flt calls' rule)
+ *   items        B >= 1 HOST rows as spiht_tile_paste_set takes them, read the same way: item b is the box (y0, x0, wh, ww) of
+ *                its H x W picture, made from the sub-grid [i0, i1) x [j0, j1) of tiles; d_out and (sc, sh, sw) are the view
+ *                of its OUTPUT [c, oh, ow], under the rule for a view that is written.  Samples outside the box never
+ *                contribute, and what lies between a view's samples is not written.
+ *   item_tables  HOST, int64 [B][4]: the byte offset in `tables` of item b's column table and its K, then of its row table and
+ *                its K.  A table of an axis with n outputs (ow, oh) lies at a multiple of 8 bytes: int32 start[n], int32
+ *                count[n], float64 weights[n][K]; output i is made from the box's samples start[i] .. start[i] + count[i] - 1
+ *                of the axis.  Tables may be shared between items.
+ *   tables       HOST, table_bytes bytes, 8-byte aligned
+ *   mean, std    HOST, float64 [c] each, or both NULL; not with 8 / 16 bits; std != 0
+ *   d_tiles      DEVICE, dense float64 [S, c, rh, rw], rh >= th, rw >= tw, S the sum of the sub-grid sizes, as for the paste
+ * SPIHT_ERR_ARG, before anything is queued: what spiht_tile_paste_set refuses of an item; B, c, oh or ow < 1; an output
+ * misaligned for its element or overlapping itself; a table that leaves `tables`, lies at no multiple of 8 or has K < 1 or
+ * K > 33 (the taps of a box side of at most 16 output sides); a count < 1 or > K; a run of taps that leaves the box; a row table
+ * whose 8 consecutive outputs (from a multiple of 8) span more than 145 box rows (what a workgroup holds: 16 * 7 + 33); mean
+ * without std.  B, c <= 65535 (SPIHT_ERR_TOO_LARGE).  Rows, tables, mean and std are copied to device memory of the library's
+ * own on the context's stream, as the tables of the calls above: they may be dropped when the call returns, and calls queued
+ * back to back each see their own.  Asynchronous on the context's stream. */
+/* HOST only, no device: the rule's table of one axis of n_in samples resampled to n_out (resample.py: axis_table; flip != 0: its
+ * rows reversed, flip_table), written at `table` (8-byte aligned, cap bytes) in the layout above, bit for bit numpy's.  *K and
+ * *bytes are set whenever the sizes are valid; table == NULL only asks for them; cap < *bytes: SPIHT_ERR_ARG, nothing written. */
+int spiht_resample_axis_table(int64_t n_in, int64_t n_out, int flip, void *table, uint64_t cap, int64_t *K, uint64_t *bytes);
+int spiht_tile_resample_set(spiht_ctx *ctx, int elem, int64_t B, int64_t c, int64_t rh, int64_t rw, int64_t th, int64_t tw,
+                            int64_t oh, int64_t ow, const spiht_tileset_item *items, const int64_t *item_tables,
+                            const void *tables, uint64_t table_bytes, const double *mean, const double *std,
+                            const double *d_tiles, int64_t S);
+
 #ifdef __cplusplus
 }
 #endif

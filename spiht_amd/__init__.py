@@ -13,6 +13,7 @@ from .spiht_wrapper import (encode_image, decode_image, EncodingResult, SpihtSet
                             decode_image_reduced_u16, reduced_shape, decode_image_float, decode_image_reduced_float,
                             encode_image_float)
 from . import floatpx  # noqa: E402,F401
+from . import resample  # noqa: E402,F401
 from .spiht import encode, decode  # noqa: E402,F401
 from .rd import (RDCurve, rd_curve, rd_curve_u8, rd_curve_u16, cut_to_psnr, cut_to_psnr_u8,  # noqa: E402,F401
                  cut_to_psnr_u16)

@@ -1,9 +1,11 @@
 // C ABI of libspiht_hip.so (include/spiht_hip.h), tiled pictures (tiles.hip, overlap.hip, layers.hip): one picture <-> a dense
 // batch of equal tiles -- the grid, the cut (with a margin: overlapping tiles), paste, mosaic (reduced tiles) and blend into a
-// window -- T stream slots <-> one run of bytes, and the quality layers of a tiled picture.  Copies and the cross-fade; the
+// window -- T stream slots <-> one run of bytes, the quality layers of a tiled picture, the cut and the paste of a picture set
+// (tileset.hip) and its resized crops (resample.hip).  Copies, the cross-fade and the resample; the
 // transforms and the coder see the tiles as an ordinary batch.  As in api_image.cpp, a family of views by byte strides has one
 // body, <family>_view, that takes the element; _f32s and the strided _f32 mosaic are views of EL_FLT_F32 (4-byte copies).
 #include "api_internal.h"
+#include "resample.h"
 
 extern "C" int spiht_tile_grid(int64_t H, int64_t W, int64_t th, int64_t tw, int64_t *gy, int64_t *gx) {
     if (H < 1 || W < 1 || th < 8 || tw < 8) return SPIHT_ERR_ARG;
@@ -543,5 +545,132 @@ extern "C" int spiht_tile_paste_set(spiht_ctx *ctx, int es, int64_t B, int64_t c
     a.tiles = (const uint8_t *)d_tiles;
     a.c = (int32_t)c; a.rh = (int32_t)rh; a.rw = (int32_t)rw; a.th = (int32_t)th; a.tw = (int32_t)tw; a.rows = 0;
     LAUNCHCHK(spiht_launch_tile_paste_set(&a, es, S, n, nrows, strided, ctx->stream));
+    return SPIHT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// resized crops (resample.hip): boxes of the pictures of a set, resampled to one size straight from the decoded tiles
+// ------------------------------------------------------------------------------------------------
+// One axis table of n outputs at `off` of the caller's blob (resample.h: start, count, weights), K taps wide, for a box side of
+// `side` samples: it lies in the blob, every run of taps lies in the box and has 1 .. K <= RS_MAX_TAPS taps.  rows: the table
+// of the rows -- the taps of RS_ROWS consecutive outputs span at most the RS_SPAN source rows a workgroup holds
+static int check_axis_table(const uint8_t *tables, uint64_t table_bytes, int64_t off, int64_t K, int64_t n, int64_t side, bool rows) {
+    if (off < 0 || off % 8 || K < 1 || K > RS_MAX_TAPS) return SPIHT_ERR_ARG;
+    if ((uint64_t)off > table_bytes || rs_table_bytes(n, K) > table_bytes - (uint64_t)off) return SPIHT_ERR_ARG;
+    const int32_t *start = (const int32_t *)(tables + off), *count = start + n;
+    for (int64_t i = 0; i < n; i++)
+        if (count[i] < 1 || count[i] > K || start[i] < 0 || (int64_t)start[i] + count[i] > side) return SPIHT_ERR_ARG;
+    for (int64_t r0 = 0; rows && r0 < n; r0 += RS_ROWS) {
+        int64_t lo = start[r0], hi = lo + count[r0];
+        for (int64_t r = r0 + 1; r < std::min<int64_t>(n, r0 + RS_ROWS); r++) {
+            lo = std::min<int64_t>(lo, start[r]);
+            hi = std::max<int64_t>(hi, (int64_t)start[r] + count[r]);
+        }
+        if (hi - lo > RS_SPAN) return SPIHT_ERR_ARG;
+    }
+    return SPIHT_OK;
+}
+// The rule's table of one axis (spiht_amd/resample.py: axis_table, flip_table), written in the layout above: host arithmetic
+// only, every operation and its order the rule's -- float64, nothing fused --, so that a caller need not build B tables in
+// numpy for every call.  tests/test_resample_cpu.py holds it to axis_table bit for bit.
+extern "C" int spiht_resample_axis_table(int64_t n_in, int64_t n_out, int flip, void *table, uint64_t cap, int64_t *K,
+                                         uint64_t *bytes) {
+#pragma clang fp contract(off)
+    if (n_in < 1 || n_out < 1 || !K || !bytes) return SPIHT_ERR_ARG;
+    if (n_in >= (1 << 30) || n_out > (1 << 24)) return SPIHT_ERR_TOO_LARGE;
+    const double scale = (double)n_in / (double)n_out, support = scale > 1.0 ? scale : 1.0, inv = 1.0 / support;
+    auto run = [&](int64_t i, int64_t *start, int64_t *stop) {  // the taps of output i, and its centre
+        const double center = scale * ((double)i + 0.5);
+        *start = std::max<int64_t>(0, (int64_t)(center - support + 0.5));
+        *stop = std::min<int64_t>(n_in, (int64_t)(center + support + 0.5));
+        return center;
+    };
+    int64_t k_max = 0, a, b;
+    for (int64_t i = 0; i < n_out; i++) {
+        run(i, &a, &b);
+        k_max = std::max(k_max, b - a);
+    }
+    *K = k_max;
+    *bytes = rs_table_bytes(n_out, k_max);
+    if (!table) return SPIHT_OK;  // (a question: K and the bytes)
+    if (cap < *bytes || (uintptr_t)table % 8) return SPIHT_ERR_ARG;
+    int32_t *start = (int32_t *)table, *count = start + n_out;
+    double *w = (double *)(count + n_out);
+    for (int64_t x = 0; x < n_out; x++, w += k_max) {
+        const double center = run(flip ? n_out - 1 - x : x, &a, &b);
+        start[x] = (int32_t)a;
+        count[x] = (int32_t)(b - a);
+        double total = 0.0;
+        for (int64_t j = a; j < b; j++) {
+            const double d = fabs(((double)j - center + 0.5) * inv), v = 1.0 - d;
+            w[j - a] = v > 0.0 ? v : 0.0;
+            total = j == a ? w[0] : total + w[j - a];  // in ascending j
+        }
+        for (int64_t k = 0; k < k_max; k++) w[k] = k < b - a ? w[k] / total : 0.0;
+    }
+    return SPIHT_OK;
+}
+extern "C" int spiht_tile_resample_set(spiht_ctx *ctx, int elem, int64_t B, int64_t c, int64_t rh, int64_t rw, int64_t th, int64_t tw,
+                                       int64_t oh, int64_t ow, const spiht_tileset_item *items, const int64_t *item_tables,
+                                       const void *tables, uint64_t table_bytes, const double *mean, const double *std,
+                                       const double *d_tiles, int64_t S) {
+    if (!ctx || elem < SPIHT_HS_F64 || elem > SPIHT_HS_BF16 || !items || !item_tables || !tables || !d_tiles) return SPIHT_ERR_ARG;
+    if (B < 1 || c < 1 || oh < 1 || ow < 1 || S < 0 || (uintptr_t)d_tiles % 8 || (uintptr_t)tables % 8 || !mean != !std) return SPIHT_ERR_ARG;
+    const PicElem el = el_of_hs(elem);
+    if (mean && (el == EL_U8 || el == EL_U16)) return SPIHT_ERR_ARG;  // (8 / 16 bits are clipped to [0, 1]: no normalisation)
+    if (c > 65535 || B > 65535 || S > 0x7FFFFFFF || oh > (1 << 24) || ow > (1 << 24) || table_bytes > ((uint64_t)1 << 31)) return SPIHT_ERR_TOO_LARGE;
+    if (((oh + RS_ROWS - 1) / RS_ROWS) * ((ow + RS_COLS - 1) / RS_COLS) > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    for (int64_t ch = 0; mean && ch < c; ch++)
+        if (std[ch] == 0.0) return SPIHT_ERR_ARG;
+    // the rows and the tables are checked completely before anything is queued
+    int64_t sum = 0;
+    for (int64_t b = 0; b < B; b++) {
+        const spiht_tileset_item &q = items[b];
+        const int64_t *t = item_tables + 4 * b;
+        int64_t gy, gx;
+        if (!q.d_out) return SPIHT_ERR_ARG;
+        CHK(spiht_tile_grid(q.H, q.W, th, tw, &gy, &gx));
+        if (rh < th || rw < tw || rh > th + (1 << 24) || rw > tw + (1 << 24)) return SPIHT_ERR_ARG;
+        CHK(check_window(c, gy, gx, q.H, q.W, th, tw, 0, q.i0, q.i1, q.j0, q.j1, q.y0, q.x0, q.wh, q.ww));
+        const int64_t st[3] = {q.sc, q.sh, q.sw};
+        Pic v;
+        CHK(window_view(&v, q.d_out, el, st, c, oh, ow));
+        CHK(check_axis_table((const uint8_t *)tables, table_bytes, t[0], t[1], ow, q.ww, false));
+        CHK(check_axis_table((const uint8_t *)tables, table_bytes, t[2], t[3], oh, q.wh, true));
+        sum += (q.i1 - q.i0) * (q.j1 - q.j0);
+        if (sum > 0x7FFFFFFF) return SPIHT_ERR_TOO_LARGE;
+    }
+    if (sum != S) return SPIHT_ERR_ARG;
+    // one blob: the items' rows, mean and std, the tables
+    const size_t tab = align16((size_t)B * sizeof(ResampleItem)), norm = mean ? align16((size_t)c * 16) : 0;
+    const size_t bytes = tab + norm + align16((size_t)table_bytes);
+    std::vector<char> h(bytes, 0);
+    ResampleItem *rows = (ResampleItem *)h.data();
+    uint32_t s0 = 0;
+    for (int64_t b = 0; b < B; b++) {
+        const spiht_tileset_item &q = items[b];
+        const int64_t *t = item_tables + 4 * b;
+        rows[b] = {(uint8_t *)q.d_out, q.sc, q.sh, q.sw, (int32_t)q.i0, (int32_t)q.j0, (int32_t)(q.j1 - q.j0), s0,
+                   (int32_t)q.y0, (int32_t)q.x0, (int32_t)q.wh, (int32_t)q.ww,
+                   (uint32_t)(tab + norm + t[0]), (uint32_t)(tab + norm + t[2]), (int32_t)t[1], (int32_t)t[3]};
+        s0 += (uint32_t)((q.i1 - q.i0) * (q.j1 - q.j0));
+    }
+    if (mean) {
+        memcpy(h.data() + tab, mean, (size_t)c * 8);
+        memcpy(h.data() + tab + (size_t)c * 8, std, (size_t)c * 8);
+    }
+    memcpy(h.data() + tab + norm, tables, (size_t)table_bytes);
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    CHK(upload_tables(ctx, h.data(), bytes));
+    ResampleArgs a;
+    a.items = (const ResampleItem *)ctx->tsettab.p;
+    a.tables = (const uint8_t *)ctx->tsettab.p;
+    a.mean = mean ? (const double *)((const char *)ctx->tsettab.p + tab) : nullptr;
+    a.std = mean ? a.mean + c : nullptr;
+    a.tiles = d_tiles;
+    a.c = (int32_t)c; a.rh = (int32_t)rh; a.rw = (int32_t)rw; a.th = (int32_t)th; a.tw = (int32_t)tw;
+    a.oh = (int32_t)oh; a.ow = (int32_t)ow; a.ncol = 0;
+    LAUNCHCHK(spiht_launch_tile_resample_set(&a, el_size(el), el_flt_kind(el), B, ctx->stream));
     return SPIHT_OK;
 }

@@ -48,22 +48,7 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_cut_overlap(const TileCutOv
 }
 
 // ---- blend -------------------------------------------------------------------------------------------------------------------
-// what a sample of the window is stored as.  8 / 16 bits: the decoder's conversion of a float64 sample (dwt_device.h,
-// px8_store_value / px16_store_value): clip to [0, 1], times 255 / 65535, truncate; NaN -> 0 (fmax / fmin return the number
-// of a pair with a NaN).  FK != 0: a float kind (floatpx.h: 1 float32, 2 float16, 3 bfloat16) -- the blended float64 sample
-// rounded once to the kind, as the decoder's float store does
-template <int ES, int FK = 0> __device__ __forceinline__ typename ElemOf<ES>::type blend_store_value(double v) {
-    if constexpr (FK != 0) {
-        return (typename ElemOf<ES>::type)flt_store_value(v, FK);
-    } else if constexpr (ES == 8) {
-        return (uint64_t)__double_as_longlong(v);
-    } else {
-        const double c = fmin(fmax(v, 0.0), 1.0);
-        const double s = c * (ES == 1 ? 255.0 : 65535.0);
-        return (typename ElemOf<ES>::type)(uint32_t)s;
-    }
-}
-
+// what a sample of the window is stored as: px_store_value (tiles_device.h)
 // grid (row chunks of the window, c); block (bx, by): bx lanes along a window row, by rows at a time
 template <int ES, int FK = 0>
 __global__ __launch_bounds__(TL_THREADS) void k_tile_blend(const TileBlendArgs a) {
@@ -99,7 +84,7 @@ __global__ __launch_bounds__(TL_THREADS) void k_tile_blend(const TileBlendArgs a
         auto val = [&](int X) -> T {
             double r = hval(top, X);
             if (zy) r = (by * r + ay * hval(bot, X)) / fm;
-            return blend_store_value<ES, FK>(r);
+            return px_store_value<ES, FK>(r);
         };
         auto elem = [&](int k) { return val(a.x0 + k); };
         store_row<ES, int64_t>(a.out + (int64_t)ch * a.sc + (int64_t)y * a.sh, a.sw, a.ww, lane, nlanes, elem,

@@ -2,6 +2,7 @@
 // margin, the mosaic and the blend, the plain row copy of cut and paste, and the workgroup's exclusive scan.
 #pragma once
 #include "tiles.h"
+#include "floatpx.h"
 
 // 16 bytes, as a lane loads and stores them
 typedef uint32_t Vec16 __attribute__((ext_vector_type(4)));
@@ -15,6 +16,22 @@ __device__ __forceinline__ Vec16 gather_vec(int k0, ELEM elem) {
     Vec16 q;
     __builtin_memcpy(&q, e, 16);
     return q;
+}
+
+// What a float64 sample is stored as by the kernels that do arithmetic on decoded tiles (blend, resample).  8 / 16 bits: the
+// decoder's conversion of a float64 sample (dwt_device.h, px8_store_value / px16_store_value): clip to [0, 1], times 255 /
+// 65535, truncate; NaN -> 0 (fmax / fmin return the number of a pair with a NaN).  FK != 0: a float kind (floatpx.h: 1 float32,
+// 2 float16, 3 bfloat16) -- the float64 sample rounded once to the kind, as the decoder's float store does
+template <int ES, int FK = 0> __device__ __forceinline__ typename ElemOf<ES>::type px_store_value(double v) {
+    if constexpr (FK != 0) {
+        return (typename ElemOf<ES>::type)flt_store_value(v, FK);
+    } else if constexpr (ES == 8) {
+        return (uint64_t)__double_as_longlong(v);
+    } else {
+        const double c = fmin(fmax(v, 0.0), 1.0);
+        const double s = c * (ES == 1 ? 255.0 : 65535.0);
+        return (typename ElemOf<ES>::type)(uint32_t)s;
+    }
 }
 
 // One row of n elements of ES bytes, element k to dst + k * ds; dst and ds are multiples of ES.  The lanes lane, lane + nlanes,

@@ -16,6 +16,11 @@ The rules in numpy, as overlap.py and alloc.py hold theirs: cut_rule (the dense 
 of a tile batch) and set_tables (where every picture's tiles lie in the batch, which tiles every window needs and in which
 order their streams are gathered).
 
+Resized crops (decode_resized_crops*, decode_resized_device) are the read of a training loop: a box of ANY size from each of B
+pictures, resampled to one size, mirrored and normalised, as one array [B, c, oh, ow].  The tiles a box meets are decoded to
+float64 as above and one kernel (csrc/resample.hip: k_tile_resample_set) reads that tile batch through the boxes; the rule in
+numpy is resample.py: resize_rule.
+
 Out of scope, each refused with a ValueError that names it: allocate="rd", roi, target_psnr, layers, overlap > 0 and
 reduce > 0 -- the allocation takes one tile count per picture, the blend and the mosaic are kernels of their own.
 """
@@ -23,7 +28,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, floatpx, px
+from . import _lib, floatpx, px, resample
 from .batch import BatchCodec
 from .spiht_wrapper import SpihtSettings, _check_version
 from .tiles import TiledCodec, TiledResult, _ptr, _tile_arg, window_tiles
@@ -346,25 +351,11 @@ class TileSetCodec:
         if len(r.nbytes) != gy * gx or len(r.max_n) != gy * gx or sum(r.nbytes) != len(r.encoded_bytes):
             raise ValueError("the tables of the result do not describe %d tiles of %d bytes" % (gy * gx, len(r.encoded_bytes)))
 
-    def _decode_host(self, results, windows, dtype, channels_last, name, crop=None, reduce=0):
-        """the frame of every host decode: the checks, the windows and their sub-grids, ONE upload of a blob -- the lengths of
-        the S gathered tiles, their start planes padded to a multiple of 4, their bytes --, the device form, one synchronise and
-        ONE download of all windows.  crop = (h, w): the windows are crops of that size and the output is one array"""
-        _refuse(name, reduce=reduce)
-        results = list(results)
-        if not results:
-            raise ValueError("%s: an empty list of results" % name)
-        dt = px.of_dtype(dtype)
-        if channels_last and not dt.view:
-            raise ValueError("%s: channels_last goes with the elements that have views" % name)
-        for r in results:
-            self._check_result(r)
-        windows = [None] * len(results) if windows is None else list(windows)
-        if len(windows) != len(results):
-            raise ValueError("%s: %d windows for %d results" % (name, len(windows), len(results)))
-        # (a window outside its picture: window_tiles' ValueError, before anything is uploaded)
-        t = set_tables([(r.h, r.w) for r in results], self.th, self.tw, list(enumerate(windows)))
-        S, B = int(t["s0"][-1]), len(results)
+    def _upload_streams(self, results, t):
+        """ONE upload of a blob -- the lengths of the S gathered tiles of set_tables' t, their start planes padded to a multiple
+        of 4, their bytes -- -> (the device buffer, the offset of the bytes in it, their count, the slot stride that holds the
+        longest stream)"""
+        S = int(t["s0"][-1])
         lens = np.empty(S, dtype=np.uint32)
         maxn = np.empty(S, dtype=np.uint8)
         parts = []
@@ -386,18 +377,39 @@ class TileSetCodec:
         blob[4 * S:5 * S] = maxn
         if nb:
             blob[head:head + nb] = np.concatenate(parts)
+        d_in = self._buf("in", blob.nbytes)
+        self.ctx.upload(d_in.ptr, blob)  # the lengths, the start planes and the streams of the gathered tiles: one upload
+        return d_in, head, nb, max(4, (int(lens.max()) + 3) & ~3)
+
+    def _decode_host(self, results, windows, dtype, channels_last, name, crop=None, reduce=0):
+        """the frame of every host decode: the checks, the windows and their sub-grids, ONE upload of a blob -- the lengths of
+        the S gathered tiles, their start planes padded to a multiple of 4, their bytes --, the device form, one synchronise and
+        ONE download of all windows.  crop = (h, w): the windows are crops of that size and the output is one array"""
+        _refuse(name, reduce=reduce)
+        results = list(results)
+        if not results:
+            raise ValueError("%s: an empty list of results" % name)
+        dt = px.of_dtype(dtype)
+        if channels_last and not dt.view:
+            raise ValueError("%s: channels_last goes with the elements that have views" % name)
+        for r in results:
+            self._check_result(r)
+        windows = [None] * len(results) if windows is None else list(windows)
+        if len(windows) != len(results):
+            raise ValueError("%s: %d windows for %d results" % (name, len(windows), len(results)))
+        # (a window outside its picture: window_tiles' ValueError, before anything is uploaded)
+        t = set_tables([(r.h, r.w) for r in results], self.th, self.tw, list(enumerate(windows)))
+        S, B = int(t["s0"][-1]), len(results)
+        d_in, head, nb, stride = self._upload_streams(results, t)
         # the windows in one device buffer: crops as one dense array, other windows one behind the other
         es, c = dt.itemsize, self.c
         offs, o = [], 0
         for (_, _, h, w) in t["windows"]:
             offs.append(o)
             o = o + c * h * w * es if crop else _align(o + c * h * w * es)
-        d_in = self._buf("in", blob.nbytes)
-        self.ctx.upload(d_in.ptr, blob)  # the lengths, the start planes and the streams of the gathered tiles: one upload
         d_out = self._buf("out", max(o, 1))
         outs = [(d_out.ptr + oo, r.h, r.w, dt.channels_last_strides((c, h, w)) if channels_last else None)
                 for oo, r, (_, _, h, w) in zip(offs, results, t["windows"])]
-        stride = max(4, (int(lens.max()) + 3) & ~3)
         self.decode_windows_device(d_in.ptr + head, nb, d_in.ptr, d_in.ptr + 4 * S, list(zip(t["subs"], t["windows"])), outs, dt,
                                    stride)
         self.ctx.synchronize()
@@ -469,3 +481,139 @@ class TileSetCodec:
     def decode_crops_float(self, results, origins, size, dtype=np.float32, channels_last=False, reduce=0):
         """-> one array [B, c, h, w] (or [B, h, w, c]) of the float kind; bfloat16 as uint16 bit patterns"""
         return self._crops(results, origins, size, px.of_kind_id(dtype), channels_last, "decode_crops_float", reduce)
+
+    def _axis_tables(self, keys):
+        """keys: one (n_in, n_out, flip) per table -> (int64 [T, 2]: every table's byte offset and K, the blob): the tables of
+        resample.axis_table -- flip_table'd where flip -- as spiht_tile_resample_set takes them, every distinct key once, written
+        by the library's host code (spiht_resample_axis_table: the rule in C, bit for bit) in place of T numpy calls"""
+        where, off, K, nb = {}, 0, C.c_int64(), C.c_uint64()
+        distinct = list(dict.fromkeys(keys))
+        # (the taps of an output span 2 * support samples: at most ceil(2 * support) + 1 of them)
+        cap = sum(8 * n_out * (2 + int(np.ceil(2.0 * max(n_in / n_out, 1.0)))) for n_in, n_out, _ in distinct)
+        blob = np.empty(cap, dtype=np.uint8)
+        for key in distinct:
+            n_in, n_out, flip = key
+            _lib.check(self.L.spiht_resample_axis_table(n_in, n_out, int(flip), C.c_void_p(blob.ctypes.data + off), cap - off,
+                                                        C.byref(K), C.byref(nb)))
+            where[key] = (off, K.value)
+            off += nb.value
+        return np.asarray([where[k] for k in keys], dtype=np.int64), blob[:off]
+
+    # ---- resized crops: a box of any size of every picture, resampled to one size (resample.py) ------------------------
+    # Row b of every call below is, bit for bit,
+    #     resample.resize_rule(TiledCodec.decode_window(results[b], y0, x0, h, w), (oh, ow), flip=flips[b], mean=mean, std=std,
+    #                          dtype=kind)
+    # -- the crop first, then the resize: samples outside the box never contribute.  The tiles are decoded to float64 whatever the
+    # output's kind and each output sample is rounded once, at the kernel's store (csrc/resample.hip).
+    def decode_resized_device(self, d_packed, packed_bytes, d_lens, d_max_n, items, d_out, size, dtype=None, out_strides=None,
+                              flips=None, mean=None, std=None, slot_stride=None):
+        """d_packed / d_lens / d_max_n / slot_stride: as decode_windows_device.  items: one (sub, box, (H, W)) per output row --
+        box = (y0, x0, h, w) inside its H x W picture, sub = (i0, i1, j0, j1) or None for the tiles the box meets.  d_out: a
+        device address (or an object with .ptr) of the output [B, c, oh, ow], size = (oh, ow), laid out by the BYTE strides
+        out_strides = (sb, sc, sh, sw) (None: dense; what lies between a view's samples is not written).  dtype: the output's
+        element -- None / np.float64, np.uint8 / np.uint16, or a float kind's px.Elem (tiles.float_elem).  flips: B booleans or
+        None; mean / std: one value per channel, both or neither, not with 8 / 16 bits.  One unpack, one batched float64 decode
+        of the S tiles, one resample of all boxes (spiht_tile_resample_set), queued on the codec's context with no host wait;
+        the tables may be dropped when the call returns.  Returns S."""
+        dt = px.of_dtype(np.float64 if dtype is None else dtype)
+        if not dt.view and dt is not px.F64:
+            raise ValueError("decode_resized_device: the float form gives float64 pictures")
+        items = list(items)
+        B, c, vp = len(items), self.c, C.c_void_p
+        if not items:
+            raise ValueError("decode_resized_device: no items")
+        flips = [False] * B if flips is None else [bool(f) for f in flips]
+        if len(flips) != B:
+            raise ValueError("decode_resized_device: %d flips for %d items" % (len(flips), B))
+        mean, std = resample.norm_args(mean, std, c, dt, "decode_resized_device")
+        oh, ow = (int(v) for v in size)
+        es = dt.itemsize
+        sb, sc, sh, sw = (c * oh * ow * es, oh * ow * es, ow * es, es) if out_strides is None else (int(v) for v in out_strides)
+        dt.check_aligned(_ptr(d_out))
+        if out_strides is not None and dt.view:  # (a float64 view: the library's check)
+            dt.check_view((B, c, oh, ow), (sb, sc, sh, sw), True)
+        rows, keys, S = (_lib.TileSetItem * B)(), [], 0
+        for b, (r, (sub, box, (H, W)), flip) in enumerate(zip(rows, items, flips)):
+            H, W = int(H), int(W)
+            gy, gx = _grid(H, W, self.th, self.tw)
+            y0, x0, h, w, _, _ = resample.check_box(H, W, box, (oh, ow), "decode_resized_device")
+            need = window_tiles(H, W, self.th, self.tw, y0, x0, h, w)
+            i0, i1, j0, j1 = need if sub is None else (int(v) for v in sub)
+            if not (0 <= i0 <= need[0] and need[1] <= i1 <= gy and 0 <= j0 <= need[2] and need[3] <= j1 <= gx):
+                raise ValueError("the sub-grid %s does not hold the tiles %s of the box %s" % ((i0, i1, j0, j1), need, (y0, x0, h, w)))
+            r.d_out, r.H, r.W = _ptr(d_out) + b * sb, H, W
+            r.sc, r.sh, r.sw = sc, sh, sw
+            r.i0, r.i1, r.j0, r.j1, r.y0, r.x0, r.wh, r.ww = i0, i1, j0, j1, y0, x0, h, w
+            S += (i1 - i0) * (j1 - j0)
+            keys += [(w, ow, flip), (h, oh, False)]
+        tabs, tables = self._axis_tables(keys)
+        tabs = tabs.reshape(B, 4)
+        stride = self.codec.slot_stride if slot_stride is None else int(slot_stride)
+        d_slots = self._buf("slots", S * stride)
+        d_nbytes = self._buf("nbytes", S * 8)
+        _lib.check(self.L.spiht_tile_unpack(self.ctx.handle, vp(_ptr(d_packed)), int(packed_bytes), vp(_ptr(d_lens)), S,
+                                            vp(d_slots.ptr), stride, vp(d_nbytes.ptr)))
+        rh, rw = self.codec.geom["rec_h"], self.codec.geom["rec_w"]  # the tiles are decoded to float64 whatever the output
+        d_dec = self._buf("dec", S * c * rh * rw * 8)
+        self.codec._decode_device(px.F64, d_slots.ptr, d_nbytes.ptr, _ptr(d_max_n), S, d_dec.ptr, slot_stride=stride)
+        _lib.check(self.L.spiht_tile_resample_set(
+            self.ctx.handle, dt.stream_id, B, c, rh, rw, self.th, self.tw, oh, ow, C.byref(rows), vp(tabs.ctypes.data),
+            vp(tables.ctypes.data), tables.nbytes, None if mean is None else vp(mean.ctypes.data),
+            None if std is None else vp(std.ctypes.data), vp(d_dec.ptr), S))
+        self.last_tiles_decoded = S
+        return S
+
+    def _resized(self, results, boxes, size, flips, mean, std, dtype, channels_last, name, reduce=0):
+        """the frame of the host forms: the checks, ONE upload of the gathered streams (_upload_streams), the device form, one
+        synchronise and ONE download of the [B, ...] array"""
+        _refuse(name, reduce=reduce)
+        results, boxes = list(results), list(boxes)
+        if not results:
+            raise ValueError("%s: an empty list of results" % name)
+        if len(boxes) != len(results):
+            raise ValueError("%s: %d boxes for %d results" % (name, len(boxes), len(results)))
+        dt = px.of_dtype(dtype)
+        if channels_last and not dt.view:
+            raise ValueError("%s: channels_last goes with the elements that have views" % name)
+        for r in results:
+            self._check_result(r)
+        flips = None if flips is None else list(flips)
+        if flips is not None and len(flips) != len(results):
+            raise ValueError("%s: %d flips for %d results" % (name, len(flips), len(results)))
+        resample.norm_args(mean, std, self.c, dt, name)
+        oh, ow = (int(v) for v in size)
+        boxes = [resample.check_box(r.h, r.w, box, (oh, ow), name)[:4] for r, box in zip(results, boxes)]
+        t = set_tables([(r.h, r.w) for r in results], self.th, self.tw, list(enumerate(boxes)))
+        S, B, c = int(t["s0"][-1]), len(results), self.c
+        d_in, head, nb, stride = self._upload_streams(results, t)
+        d_out = self._buf("out", B * c * oh * ow * dt.itemsize)
+        self.decode_resized_device(d_in.ptr + head, nb, d_in.ptr, d_in.ptr + 4 * S,
+                                   [(sub, box, (r.h, r.w)) for sub, box, r in zip(t["subs"], boxes, results)], d_out.ptr, (oh, ow),
+                                   dt, dt.channels_last_strides((B, c, oh, ow)) if channels_last else None, flips, mean, std,
+                                   stride)
+        self.ctx.synchronize()
+        out = _lib.result_array((B, oh, ow, c) if channels_last else (B, c, oh, ow), dt.storage)
+        self.ctx.download(out, d_out.ptr)
+        return out
+
+    def decode_resized_crops(self, results, boxes, size, flips=None, mean=None, std=None, reduce=0):
+        """boxes[b] = (y0, x0, h, w) inside picture b, size = (oh, ow) -> ONE float64 array [B, c, oh, ow]: row b is
+        resample.resize_rule(TiledCodec.decode_window(results[b], y0, x0, h, w), size, flips[b], mean, std).  Only the tiles each
+        box meets are gathered, uploaded and decoded (last_tiles_decoded tells how many); a result may appear several times.  A
+        box that is empty, leaves its picture or has a side above resample.MAX_RATIO output sides: ValueError, before anything
+        is uploaded."""
+        return self._resized(results, boxes, size, flips, mean, std, np.float64, False, "decode_resized_crops", reduce)
+
+    def decode_resized_crops_u8(self, results, boxes, size, flips=None, channels_last=False, reduce=0):
+        """-> uint8 [B, c, oh, ow] (or [B, oh, ow, c]): the resampled sample clipped to [0, 1], times 255, truncated"""
+        return self._resized(results, boxes, size, flips, None, None, np.uint8, channels_last, "decode_resized_crops_u8", reduce)
+
+    def decode_resized_crops_u16(self, results, boxes, size, flips=None, channels_last=False, reduce=0):
+        return self._resized(results, boxes, size, flips, None, None, np.uint16, channels_last, "decode_resized_crops_u16", reduce)
+
+    def decode_resized_crops_float(self, results, boxes, size, flips=None, mean=None, std=None, dtype=np.float32,
+                                   channels_last=False, reduce=0):
+        """-> one array [B, c, oh, ow] (or [B, oh, ow, c]) of the float kind, every sample rounded once from the float64
+        resample; bfloat16 as uint16 bit patterns"""
+        return self._resized(results, boxes, size, flips, mean, std, px.of_kind_id(dtype), channels_last,
+                             "decode_resized_crops_float", reduce)
